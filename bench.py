@@ -9,13 +9,22 @@ step -- so every rank knows its byte offset in the final .lac.
 
 Workloads:
   N = 1   BASELINE configs[1]: 10 min synthetic stereo 16-bit 48 kHz, per-block auto MS/LR, LPC search, 16384-frame
-          blocks.  The last timed step's .lac is compared byte for byte with the CPU reference's and with the golden
-          digest.
+          blocks.  With --full the last timed step's .lac is compared byte for byte with the CPU reference's and with
+          the golden digest.
   N > 1   BASELINE configs[3]: ONE 2 h stereo 16/48 stream (345 600 000 frames, 21 094 blocks); rank r encodes blocks
-          [r*B/N, (r+1)*B/N) (strong split of a fixed stream, no data-path collective).  After the timed loop every
-          rank checks each eighth of its shard against the golden digests minted from the reference
-          (tests/golden/digests.json, cfg4_2h_shard{1..8}of8) -> "byte_identical_shards": "N/N".  The same ranks then
+          [r*B/N, (r+1)*B/N) (strong split of a fixed stream, no data-path collective).  With --full, after the timed
+          loop every rank checks each eighth of its shard against the golden digests minted from the reference
+          (tests/golden/digests.json, cfg4_2h_shard{1..8}of8) -> "byte_identical_shards": "N/N", and the same ranks then
           also time the weak line (10 min per GPU) -> "weak_10min_per_gpu".
+
+A plain run (no --full) does only what the headline figure needs: set-up, warm-up, the --steps timed steps, the outputs
+of the last step when --dump-outputs is given, and the JSON line.  --full adds everything else the line can carry: the
+digest and CPU-reference checks, the CPU baseline, the end-to-end and decode figures, the other BASELINE workloads and,
+at N > 1, the weak lines and the single-process fan-out line.
+
+--dump-outputs DIR writes what the timed path returned in its last step (the shard's block table and payload bytes, see
+dump_outputs) as DIR/<name>.npy; the inputs are seeded, so two builds run with the same arguments can be compared
+output for output.
 
 `python bench.py --gpus N` with no WORLD_SIZE in the environment starts the N ranks itself (a child
 `python -m torch.distributed.run`, started before this process touches any GPU), relays rank 0's JSON line and exits
@@ -88,7 +97,72 @@ def parse_args(argv=None):
                          "thread + stream set per device, RCCL exchange of the shard sizes) instead of one torchrun rank per GPU")
     ap.add_argument("--inflight", type=int, default=1, choices=(1, 2),
                     help="diagnostic: 2 = step i+1 is enqueued on a second encoder before step i's result is collected")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the checks and extra measurements beyond the headline figure (digest and CPU-reference checks, "
+                         "CPU baseline, end to end, device decode, other workloads; at N>1 the weak and fan-out lines); the "
+                         "--no-* options above select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32/float64, at most 64 MB in all)")
     return ap.parse_args(argv)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# inputs and outputs
+# ---------------------------------------------------------------------------------------------------------
+def synth_pcm_parallel(synth, frames, channels, bit_depth, sample_rate, seed, kind, stereo="wide", start=0, threads=16,
+                       piece=1 << 20):
+    """synth.synth_pcm in pieces on a thread pool.  The generator is counter based (every frame is a function of its own
+    index), so the pieces are the same samples as one serial call; numpy releases the GIL inside the piece's arithmetic."""
+    import numpy as np
+    from concurrent.futures import ThreadPoolExecutor
+
+    left = np.empty(frames, dtype=np.int32)
+    right = np.empty(frames, dtype=np.int32) if channels == 2 else None
+
+    def one(p0):
+        m = min(piece, frames - p0)
+        l_, r_ = synth.synth_pcm(m, channels, bit_depth, sample_rate, seed=seed, kind=kind, stereo=stereo, start=start + p0)
+        left[p0:p0 + m] = l_
+        if right is not None:
+            right[p0:p0 + m] = r_
+
+    with ThreadPoolExecutor(max(1, threads)) as ex:
+        list(ex.map(one, range(0, frames, piece)))
+    return left, right
+
+
+def cpu_share() -> int:
+    """Host threads for one process: the cores it may run on (affinity mask, cgroup quota), at most 16."""
+    cores = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    quota = cgroup_cpu_quota()
+    return max(1, min(16, cores, quota or cores))
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_PAYLOAD_SAMPLE = 8 << 20  # payload bytes kept when the payload is larger (float32: 32 MB)
+DUMP_SEED = 2026
+
+
+def dump_outputs(out_dir, payload: bytes, table, suffix="", share=1):
+    """What a caller of the timed path receives from its last step, as .npy files under out_dir:
+      block_table<suffix>.npy     the shard's block table (uint32 [blocks, 2]) as float64 -- exact
+      payload_sample<suffix>.npy  the payload bytes as float32 -- all of them up to DUMP_PAYLOAD_SAMPLE / share bytes,
+                                  beyond that the bytes at the sorted positions numpy.random.default_rng(DUMP_SEED)
+                                  .integers(0, len(payload), DUMP_PAYLOAD_SAMPLE / share) draws (a fixed, seeded sample)
+    share: the number of processes writing into out_dir (ranks), which split the 64 MB between them."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    tab = np.asarray(table, dtype=np.uint32).astype(np.float64)
+    pay = np.frombuffer(payload, dtype=np.uint8)
+    n = DUMP_PAYLOAD_SAMPLE // max(1, share)
+    if pay.size > n:
+        pos = np.sort(np.random.default_rng(DUMP_SEED).integers(0, pay.size, n))
+        pay = pay[pos]
+    sample = pay.astype(np.float32)
+    assert tab.nbytes + sample.nbytes <= DUMP_BUDGET_BYTES // max(1, share)
+    np.save(os.path.join(out_dir, f"block_table{suffix}.npy"), tab)
+    np.save(os.path.join(out_dir, f"payload_sample{suffix}.npy"), sample)
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -248,7 +322,7 @@ def fanout_job(lacx, synth, torch, np, devices, left, right, total_frames, bit_d
         if left is not None:
             l_, r_ = left[f0:f1], right[f0:f1]
         else:
-            l_, r_ = synth.synth_pcm(f1 - f0, 2, bit_depth, sample_rate, seed=gen[1], kind=gen[0], start=f0)
+            l_, r_ = synth_pcm_parallel(synth, f1 - f0, 2, bit_depth, sample_rate, gen[1], gen[0], start=f0, threads=cpu_share())
         inter = synth.interleave(l_, r_, bit_depth)
         d = torch.from_numpy(inter.view(np.int16) if bit_depth == 16 else inter).to(f"cuda:{dev}")
         del inter, l_, r_
@@ -321,10 +395,12 @@ def fanout_single_process(args) -> int:
         total_frames, wl_name = CFG4_SECONDS * sample_rate, "BASELINE configs[3]: one 2 h stream, contiguous block-range split over the devices"
     main, parts, enc = fanout_job(lacx, synth, torch, np, devices, None, None, total_frames, bit_depth, sample_rate, args.steps, args.warmup,
                                   gen=(args.kind, 2026))
-    # verification against the reference-minted digests: the eighths of the 2 h stream / the whole 10 min stream
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, b"".join(p for p, _ in parts), np.concatenate([t for _, t in parts]))
+    # --full: verification against the reference-minted digests: the eighths of the 2 h stream / the whole 10 min stream
     shard_ok = whole_ok = None
     total_blocks = (total_frames + BLOCK - 1) // BLOCK
-    if workload == "cfg4" and not args.seconds and std_format and N in (1, 2, 4, 8):
+    if args.full and workload == "cfg4" and not args.seconds and std_format and N in (1, 2, 4, 8):
         pay = b"".join(p for p, _ in parts)
         tab = np.concatenate([t for _, t in parts])
         good, ob, oy = 0, 0, 0
@@ -339,7 +415,7 @@ def fanout_single_process(args) -> int:
         shard_ok = good
         if good != 8:
             raise SystemExit(f"bench.py --fanout: only {good}/8 eighths are byte-identical to the reference's -- refusing to report a number")
-    if workload == "cfg2" and not args.seconds and std_format:
+    if args.full and workload == "cfg2" and not args.seconds and std_format:
         lac = lacx.assemble(sample_rate, bit_depth, STEREO_MODE, 2, parts)
         d = digests["cfg2_10min_st16_48k_auto"]
         whole_ok = len(lac) == d["lac_bytes"] and hashlib.sha256(lac).hexdigest() == d["lac_sha256"]
@@ -349,7 +425,7 @@ def fanout_single_process(args) -> int:
         "metric": METRIC, "value": main["value"], "unit": "Msamples/s", "n_gpus": N, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": main["ms_per_step"], "higher_is_better": True,
         "scaling": "strong" if (workload == "cfg4" and not args.seconds) else "weak", "vs_baseline": None, "dtype": "int64",
-        "data": "synthetic",
+        "data": "synthetic", "full": bool(args.full),
         "config": {
             "workload": f"{wl_name}: synthetic stereo {bit_depth}-bit {sample_rate // 1000} kHz ({args.kind}), auto MS/LR, LPC search, "
                         "16384-frame blocks, zero-run + partitioning on",
@@ -450,7 +526,7 @@ def worker(args) -> int:
         b1 = (rank + 1) * total_blocks // world
         f0 = b0 * BLOCK
         frames = min(b1 * BLOCK, total_frames) - f0
-        left, right = synth.synth_pcm(frames, 2, bit_depth, sample_rate, seed=seed, kind=kind, start=f0)
+        left, right = synth_pcm_parallel(synth, frames, 2, bit_depth, sample_rate, seed, kind, start=f0, threads=emit_threads)
         if interleaved:  # the WAV data-chunk layout: 2 (3) bytes per sample in HBM
             inter = synth.interleave(left, right, bit_depth)
             d_pcm = torch.from_numpy(inter.view(np.int16) if bit_depth == 16 else inter).cuda()
@@ -565,10 +641,15 @@ def worker(args) -> int:
     else:
         total_frames, wl_name = CFG4_SECONDS * sample_rate, "BASELINE configs[3]: one 2 h stream, contiguous block-range split over the ranks"
     main = measure(total_frames, "main")
+    if args.dump_outputs:
+        if main["last"] is None:
+            raise SystemExit("bench.py: --dump-outputs: this timed path (--analysis-only) returns nothing to the host")
+        dump_outputs(args.dump_outputs, main["last"][0].tobytes(), main["last"][1],
+                     suffix=f"_rank{rank}" if world > 1 else "", share=world)
 
-    # ---- per-shard verification against the reference's golden digests (cfg4 eighths) ------------
+    # ---- --full: per-shard verification against the reference's golden digests (cfg4 eighths) ----
     shard_ok = None
-    if (workload == "cfg4" and not args.seconds and std_format and main["last"] is not None and world in (1, 2, 4, 8)):
+    if (args.full and workload == "cfg4" and not args.seconds and std_format and main["last"] is not None and world in (1, 2, 4, 8)):
         payload, table = main["last"]
         pay = payload.tobytes()
         tab = np.array(table, dtype=np.uint32)
@@ -589,9 +670,9 @@ def worker(args) -> int:
         shard_ok = all_sum(1 if ok else 0)
     ranks_seen = all_sum(1)
 
-    # ---- N > 1: the weak line (10 min per GPU) -----------------------------------------------------
+    # ---- --full, N > 1: the weak line (10 min per GPU) --------------------------------------------
     weak = weak96 = weak_pcm0 = None
-    if world > 1 and workload == "cfg4" and not args.no_weak_line and not args.seconds:
+    if args.full and world > 1 and workload == "cfg4" and not args.no_weak_line and not args.seconds:
         def rank0_round_trip(w, sr, bd):
             """Rank 0's shard of the weak stream as a .lac of its own, decoded on the device: the PCM must come back.  (The
             shard is not the 10 min stream of the golden digests -- block ranges are whole blocks -- so identity with the
@@ -620,7 +701,7 @@ def worker(args) -> int:
             if rank == 0 and line["rank0_decodes_to_input"] is False:
                 raise SystemExit("bench.py: rank 0's weak-line .lac does not decode back to its PCM -- refusing to report a number")
 
-    # ---- N > 1: the library's OWN fan-out, one process driving all N devices (lacx_encoder_create_multi) -------------
+    # ---- --full, N > 1: the library's OWN fan-out, one process driving all N devices (lacx_encoder_create_multi) ------
     # Rank 0 starts `bench.py --gpus N --fanout --workload cfg2` as a CHILD process: the 10 min stream of BASELINE configs[1]
     # spread over the N devices through the C ABI (one host thread + stream set + pinned region per device, RCCL all-gather
     # of the shard sizes inside the library), its .lac checked against the reference's golden digest by the child itself.
@@ -628,13 +709,13 @@ def worker(args) -> int:
     # Outside every timed region of the lines above, and outside this process: whatever happens to the child -- a crash
     # inside a second RCCL instance, a hang (killed after 240 s) -- the headline line is still printed, with the error noted.
     fan_line = None
-    if world > 1 and workload == "cfg4" and not args.no_fanout_line and not args.seconds and std_format:
+    if args.full and world > 1 and workload == "cfg4" and not args.no_fanout_line and not args.seconds and std_format:
         import datetime
 
         store = dist.distributed_c10d._get_default_store()
         if rank == 0:
             cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(world), "--fanout", "--workload", "cfg2",
-                   "--steps", str(max(3, args.steps)), "--warmup", "2"]
+                   "--steps", str(max(3, args.steps)), "--warmup", "2", "--full"]
             env = {k: v for k, v in os.environ.items()
                    if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "GROUP_RANK",
                                 "ROLE_RANK", "ROLE_WORLD_SIZE", "TORCHELASTIC_RUN_ID")}
@@ -754,20 +835,20 @@ def worker(args) -> int:
                 "see DESIGN.md section 5",
     }
 
-    # ---- N = 1: CPU baseline (the unmodified reference, oracle/_ref) + byte comparison + end to end ----------
+    # ---- --full, N = 1: CPU baseline (the unmodified reference, oracle/_ref) + byte comparison + end to end ---
     cpu = cpu_all = e2e = None
     identical = None  # set when the CPU leg encoded the whole stream: GPU bytes == CPU bytes
     digest_ok = None
     left, right = main["left"], main["right"]
     gpu_lac = None
-    if world == 1 and main["last"] is not None:
+    if args.full and world == 1 and main["last"] is not None:
         gpu_lac = lac_of(main["last"][0].tobytes(), np.array(main["last"][1], dtype=np.uint32))
         if default_run:
             d = digests["cfg2_10min_st16_48k_auto"]
             digest_ok = len(gpu_lac) == d["lac_bytes"] and hashlib.sha256(gpu_lac).hexdigest() == d["lac_sha256"]
             if not digest_ok:
                 raise SystemExit("bench.py: the GPU .lac does not match the reference's golden digest -- refusing to report a number")
-    if not args.no_cpu_baseline and world == 1:  # reported at N=1 only (rank 0)
+    if args.full and not args.no_cpu_baseline and world == 1:  # reported at N=1 only (rank 0)
         try:
             import refshim
 
@@ -806,7 +887,7 @@ def worker(args) -> int:
                 raise SystemExit("bench.py: the CPU encoder's output depends on its thread count")
             del data2
         del data
-    if world == 1 and not args.no_end_to_end and not args.analysis_only and not args.host_emit:
+    if args.full and world == 1 and not args.no_end_to_end and not args.analysis_only and not args.host_emit:
         # Host WAV image -> host .lac through lacx_encode_wav (RIFF walk, H2D of the raw data chunk, kernels, container):
         # the PCIe-inclusive product path (ref src/main.cpp:658-697).  Never `value`.
         import wavutil
@@ -834,7 +915,7 @@ def worker(args) -> int:
             raise SystemExit("bench.py: lacx_encode_wav_view output differs from the device-resident encode")
 
     decode_check = None
-    if world == 1 and gpu_lac is not None and not args.no_decode_check:
+    if args.full and world == 1 and gpu_lac is not None and not args.no_decode_check:
         # The product's own decoder (lacx_decode, one lane per block on the device) on the last timed step's .lac: the PCM
         # must come back sample for sample.  No oracle involved; outside every timed region.
         dec = pkg.lacx.Decoder(device=device, reuse_output=True)  # (a decoder handle: buffers live from call to call)
@@ -852,7 +933,7 @@ def worker(args) -> int:
         if not same_pcm:
             raise SystemExit("bench.py: the GPU .lac does not decode back to the PCM -- refusing to report a number")
 
-    # ---- N = 1: the other single-GPU BASELINE configs, each verified against its reference-minted digest -----------
+    # ---- --full, N = 1: the other single-GPU BASELINE configs, each verified against its reference-minted digest ----
     # Outside the headline loop (never part of `value`): BASELINE configs[2] at its stated size (10 min stereo 24-bit 96 kHz,
     # mixed material), ten minutes of white noise 16/48 (the hardest material: every block "uncertain", about five exactly
     # costed candidates per slot) and BASELINE configs[4] (the 16 combinations {mono, stereo} x {16, 24 bit} x {44.1, 48,
@@ -860,7 +941,7 @@ def worker(args) -> int:
     # pinned host memory; every .lac of the last step is compared with the golden digest minted from the reference
     # (tests/golden/make_golden.py) and nothing is printed on a mismatch.
     other = None
-    if world == 1 and default_run and not args.no_other_workloads and not args.analysis_only:
+    if args.full and world == 1 and default_run and not args.no_other_workloads and not args.analysis_only:
         other = []
         # The north_star's literal layout: analysis on the device, plan records back, the bit-serial emit on host threads
         # (LACX_FLAG_HOST_EMIT).  Same stream as the headline, planar int32 resident in HBM, host copies for the emit.
@@ -893,7 +974,7 @@ def worker(args) -> int:
             # specs: (digest name, frames, channels, bit_depth, rate, stereo_mode, kind, stereo family, seed)
             jobs = []
             for dname, frames_j, ch, bd, sr, sm, kind, st, seed in specs:
-                l_, r_ = synth.synth_pcm(frames_j, ch, bd, sr, seed=seed, kind=kind, stereo=st)
+                l_, r_ = synth_pcm_parallel(synth, frames_j, ch, bd, sr, seed, kind, stereo=st, threads=emit_threads)
                 inter = synth.interleave(l_, r_, bd)
                 del l_, r_
                 d = torch.from_numpy(inter.view(np.int16) if bd == 16 else inter).cuda()
@@ -975,6 +1056,7 @@ def worker(args) -> int:
         "vs_baseline": None,
         "dtype": "int64",
         "data": "synthetic",
+        "full": bool(args.full),
         "config": {
             "workload": f"{wl_name}: synthetic stereo {bit_depth}-bit {sample_rate // 1000} kHz ({args.kind}), auto MS/LR, LPC search, "
                         "16384-frame blocks, zero-run + partitioning on",

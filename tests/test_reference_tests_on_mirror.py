@@ -1,6 +1,6 @@
 """The reference's own test sources, unmodified, against the product's drop-in mirror classes.
 
-In the build container (where /root/reference exists) oracle/Makefile `ref-tests` compiles the reference's
+Where the reference sources exist (oracle/Makefile's REF), oracle/Makefile `ref-tests` compiles the reference's
 tests/test_predictors.cpp -- and its whole `lac_tests` executable -- with lossless-audio-codec_amd/include in front of
 the reference's include path and links them with liblacx.so: LAC::Encoder / Block::Encoder are the product's, decoder,
 WAV I/O and bit reader the reference's (a second build of lac_tests also takes the product's LAC::Decoder).  Nothing of the reference is copied; the binaries land in oracle/_ref (ignored
@@ -13,16 +13,16 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
 BIN_PRED = os.path.join(ROOT, "oracle", "_ref", "ref_test_predictors_on_mirror")
 BIN_ALL = os.path.join(ROOT, "oracle", "_ref", "ref_lac_tests_on_mirror")
 CODEC = os.path.join(ROOT, "oracle", "_ref", "ref_lac_tests_on_mirror_codec")
 
 
 def test_reference_tests_compile_and_link_against_the_mirror_headers(pkg):
-    if not os.path.isdir(os.path.join(REF, "tests")):
-        pytest.skip("reference sources absent (GPU box): nothing to compile")
+    # (re)builds them where the reference sources exist, and is a no-op elsewhere
     subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "ref-tests"], stdout=subprocess.DEVNULL)
+    if not any(os.path.exists(b) for b in (BIN_PRED, BIN_ALL, CODEC)):
+        pytest.skip("oracle/_ref/ref_*_on_mirror were not built (the reference sources were absent when the checkers were built)")
     assert os.path.exists(BIN_PRED) and os.path.exists(BIN_ALL) and os.path.exists(CODEC)
     rc = subprocess.call([BIN_PRED], stdout=subprocess.DEVNULL)
     assert rc in (0, 77)  # 77: no HIP device here, built and linked only

@@ -1,15 +1,16 @@
 """Host half of the interleaved WAV ingest: lacx_wav_parse accepts / rejects exactly what the
 reference's read_wav does (ref src/io/wav_io.cpp:167-277) and points at the raw data chunk.  The expectations
-are written out here; where the reference build is present (build container) every case is also run through
-the real read_wav."""
+are written out here; every case is also checked against the real read_wav: live where the reference build
+(oracle/_ref) is present, through its answers pinned in tests/golden/ref_answers.json elsewhere (refpin.py)."""
 import os
 import tempfile
 
 import numpy as np
 import pytest
 
-import refshim
+import refpin
 import wavutil as W
+from refpin import same
 
 
 def _cases(synth):
@@ -81,15 +82,15 @@ def test_wav_parse_accepts_and_rejects_like_read_wav(pkg):
     assert pkg.lacx.wav_parse(b"") is None
 
 
-@pytest.mark.skipif(not refshim.available(), reason="reference build (oracle/_ref) not present")
 def test_wav_parse_cross_checked_with_the_reference_reader(pkg):
+    reference = refpin.reference()
     cases, _ = _cases(pkg.synth)
     with tempfile.TemporaryDirectory() as d:
         for name, wav, ok in cases:
             path = os.path.join(d, name + ".wav")
             with open(path, "wb") as f:
                 f.write(wav)
-            ref = refshim.read_wav(path)
+            ref = reference.read_wav(path)
             assert (ref is not None) == ok, f"expectation for {name} disagrees with the reference"
             info = pkg.lacx.wav_parse(wav)
             assert (info is not None) == (ref is not None), name
@@ -97,4 +98,4 @@ def test_wav_parse_cross_checked_with_the_reference_reader(pkg):
                 rl, rr, ch, sr, bd = ref
                 assert (info.channels, info.sample_rate, info.bit_depth, info.frames) == (ch, sr, bd, rl.size), name
                 left, right = _decode(wav, info)
-                assert np.array_equal(left, rl) and (rr is None or np.array_equal(right, rr)), name
+                assert same(left, rl) and (rr is None or same(right, rr)), name
