@@ -28,6 +28,7 @@
  *   lacx_stream_parse /
  *   lacx_decode            <- LAC::Decoder::decode          ref src/codec/lac/decoder.hpp:10-24, decoder.cpp:76-303,
  *                                                            src/codec/block/decoder.cpp:64-520
+ *   lacx_decoder_decode_wav <- the `decode` command's WAV writer ref src/main.cpp:127-182, 184-431
  *
  * All analysis (and the decode) runs in hand-written HIP kernels on a gfx950 device; there is no CPU fallback: every
  * call that needs the device fails with LACX_E_DEVICE when none is usable.
@@ -345,6 +346,20 @@ int lacx_decoder_create(int device, lacx_decoder** out);
 void lacx_decoder_destroy(lacx_decoder* dec);
 int lacx_decoder_decode(lacx_decoder* dec, const uint8_t* lac, uint64_t size, int32_t* left, int32_t* right, uint64_t frames,
                         float* device_ms);
+/* WAV image of a .lac (ref src/main.cpp:184-431 decode_lac_v3_to_mapped_wav, and write_wav_unchecked_samples for
+ * version-2 streams): 44-byte canonical header + PCM + pad byte, byte-identical to the reference CLI's output file.
+ * The same parse (lacx_stream_parse), error codes and "[decode-error] block=N ..." messages (lacx_decode_last_error) as
+ * lacx_decoder_decode; the mid/side inverse, the bit-depth check and the interleave to 16 / 24-bit little-endian run on the
+ * device in one pass after the block decode, and header + data cross PCIe as one copy.  Limits: lacx_stream_parse's --
+ * the RIFF limit (36 + data + pad < 2^32) is kept, the reference's 1 GiB cap on the decoded PCM is not taken over (see
+ * above).  On failure *out is null.  device_ms (nullable): kernel time (decode and pack).
+ * lacx_decoder_decode_wav: *out is malloc'd, release it with lacx_free.
+ * lacx_decoder_decode_wav_view: *out points into the decoder's pinned image buffer, valid until the decoder's next call
+ * or lacx_decoder_destroy. */
+int lacx_decoder_decode_wav(lacx_decoder* dec, const uint8_t* lac, uint64_t size,
+                            uint8_t** out, uint64_t* out_size, float* device_ms);
+int lacx_decoder_decode_wav_view(lacx_decoder* dec, const uint8_t* lac, uint64_t size,
+                                 const uint8_t** out, uint64_t* out_size, float* device_ms);
 
 /* Block::Encoder::encode drop-in for one channel block of n <= 16384 samples of ANY int32 value: blocks inside the 25-bit
  * mid/side domain of validated 16 / 24-bit input run on the streaming kernels, wider ones on a kernel of their own that

@@ -84,6 +84,9 @@ struct lacx_decoder {
     uint32_t* h_status = nullptr;          // pinned
     unsigned long long* h_offs = nullptr;  // pinned
     uint32_t blocks_cap = 0;
+    uint8_t* d_wav = nullptr;  // WAV image (lacx_decoder_decode_wav*): header + data + pad
+    uint8_t* h_wav = nullptr;  // pinned, behind lacx_decoder_decode_wav_view
+    uint64_t wav_cap = 0;      // bytes of each
     std::string err;
 };
 
@@ -101,6 +104,8 @@ void decoder_release(lacx_decoder* d) {
     if (d->d_ms) (void)hipFree(d->d_ms);
     if (d->h_status) (void)hipHostFree(d->h_status);
     if (d->h_offs) (void)hipHostFree(d->h_offs);
+    if (d->d_wav) (void)hipFree(d->d_wav);
+    if (d->h_wav) (void)hipHostFree(d->h_wav);
     *d = lacx_decoder{};
 }
 // lacx_decode (no handle): one decoder per device for the life of the process (never freed: releasing device memory from
@@ -128,14 +133,33 @@ void lacx_decoder_destroy(lacx_decoder* d) {
     delete d;
 }
 
-int lacx_decoder_decode(lacx_decoder* d, const uint8_t* lac, uint64_t size, int32_t* left, int32_t* right, uint64_t frames,
-                        float* device_ms) {
-    if (!d) return decode_fail(LACX_E_INVALID, "null decoder");
-    lacx_stream_info info;
-    const int prc = lacx_stream_parse(lac, size, &info);
-    if (prc) return prc;
-    if (!left || (info.channels == 2 && !right)) return decode_fail(LACX_E_INVALID, "output arrays missing");
-    if (frames != info.frames) return decode_fail(LACX_E_INVALID, "output arrays do not match the stream's frame count");
+namespace {
+// The 44-byte canonical header of the decoded WAV (ref src/main.cpp:127-148, 248-262); returns the image's size.
+uint64_t wav_header(const lacx_stream_info& info, uint8_t* h) {
+    const uint32_t align = (uint32_t)info.channels * (info.bit_depth / 8u);
+    const uint64_t data = info.frames * align, pad = data & 1u;
+    auto u16 = [&](int at, uint32_t v) { h[at] = (uint8_t)v, h[at + 1] = (uint8_t)(v >> 8); };
+    auto u32 = [&](int at, uint32_t v) { u16(at, v & 0xFFFFu), u16(at + 2, v >> 16); };
+    std::memcpy(h, "RIFF", 4);
+    u32(4, (uint32_t)(36u + data + pad));  // below 2^32: lacx_stream_parse's RIFF limit
+    std::memcpy(h + 8, "WAVEfmt ", 8);
+    u32(16, 16);
+    u16(20, 1);
+    u16(22, info.channels);
+    u32(24, info.sample_rate);
+    u32(28, info.sample_rate * align);
+    u16(32, align);
+    u16(34, info.bit_depth);
+    std::memcpy(h + 36, "data", 4);
+    u32(40, (uint32_t)data);
+    return 44u + data + pad;
+}
+
+// Upload, block decode and the pass after it, status check, download: into left / right (wav = false), or as the WAV
+// image into d->h_wav (wav = true; *wav_size = its size).  info: lacx_stream_parse's of the same bytes.
+int decode_run(lacx_decoder* d, const uint8_t* lac, uint64_t size, const lacx_stream_info& info, int32_t* left,
+               int32_t* right, bool wav, uint64_t* wav_size, float* device_ms) {
+    const uint64_t frames = info.frames;
     if (device_ms) *device_ms = 0.f;
     if (lacx_device_count() <= 0) return decode_fail(LACX_E_DEVICE, "no usable HIP device");
 #define DEC_TRY(call, what)                                                                                  \
@@ -147,6 +171,7 @@ int lacx_decoder_decode(lacx_decoder* d, const uint8_t* lac, uint64_t size, int3
         }                                                                                                    \
     } while (0)
     int rc = LACX_OK;
+    uint64_t image = 0;  // bytes of the WAV image
     const uint32_t nb = info.blocks;
     const bool v2 = info.version == 2;
     const uint64_t entry = v2 ? 4u : 8u;
@@ -193,6 +218,21 @@ int lacx_decoder_decode(lacx_decoder* d, const uint8_t* lac, uint64_t size, int3
         DEC_TRY(hipHostMalloc((void**)&d->h_offs, 2 * ((size_t)cap + 1) * sizeof(unsigned long long), 0), "hipHostMalloc(offsets)");
         d->blocks_cap = cap;
     }
+    if (wav) {
+        uint8_t hdr[44];
+        image = wav_header(info, hdr);
+        if (image > d->wav_cap) {
+            if (d->d_wav) (void)hipFree(d->d_wav);
+            if (d->h_wav) (void)hipHostFree(d->h_wav);
+            d->d_wav = d->h_wav = nullptr;
+            d->wav_cap = 0;
+            const uint64_t cap = (image + 15u) & ~15ull;  // k_wav_pack writes whole dwords, and only inside the image
+            DEC_TRY(hipMalloc((void**)&d->d_wav, cap), "hipMalloc(wav)");
+            DEC_TRY(hipHostMalloc((void**)&d->h_wav, cap, 0), "hipHostMalloc(wav)");
+            d->wav_cap = cap;
+        }
+        std::memcpy(d->h_wav, hdr, sizeof hdr);  // goes up with the offsets, comes back with the data
+    }
     if (frames > d->pcm_cap || (info.channels == 2 && !d->d_right)) {
         if (d->d_left) (void)hipFree(d->d_left);
         if (d->d_right) (void)hipFree(d->d_right);
@@ -214,14 +254,16 @@ int lacx_decoder_decode(lacx_decoder* d, const uint8_t* lac, uint64_t size, int3
         DEC_TRY(hipMemsetAsync(d->d_pay + pay, 0, kDecodeTailPad, st), "memset");  // the bit reader's look-ahead (decode.hip)
         DEC_TRY(hipMemcpyAsync(d->d_offs, d->h_offs, noffs * sizeof(unsigned long long), hipMemcpyHostToDevice, st), "H2D offsets");
         DEC_TRY(hipMemcpyAsync(d->d_pay, lac + head, pay, hipMemcpyHostToDevice, st), "H2D payload");
+        if (wav) DEC_TRY(hipMemcpyAsync(d->d_wav, d->h_wav, 44, hipMemcpyHostToDevice, st), "H2D WAV header");
+        uint8_t* dw = wav ? d->d_wav : nullptr;
         DEC_TRY(hipEventRecord(d->e0, st), "event record");
         int32_t* dr = info.channels == 2 ? d->d_right : nullptr;
         if (v2)
             DEC_TRY(launch_decode_serial(nb, info.channels, info.stereo_mode, info.bit_depth, d->d_pay, (uint32_t)(8ull * pay), d->d_offs + nb + 1,
-                                         d->d_left, dr, d->d_status, d->d_ms, st), "decode launch");
+                                         d->d_left, dr, d->d_status, d->d_ms, st, dw, frames), "decode launch");
         else
             DEC_TRY(launch_decode(nb, info.channels, info.stereo_mode, info.bit_depth, d->d_pay, d->d_offs, d->d_offs + nb + 1, d->d_left, dr,
-                                  d->d_status, d->d_ms, st), "decode launch");
+                                  d->d_status, d->d_ms, st, dw, frames), "decode launch");
         DEC_TRY(hipEventRecord(d->e1, st), "event record");
         DEC_TRY(hipMemcpyAsync(d->h_status, d->d_status, (size_t)nb * sizeof(uint32_t), hipMemcpyDeviceToHost, st), "D2H status");
         DEC_TRY(hipStreamSynchronize(st), "synchronize");
@@ -235,15 +277,66 @@ int lacx_decoder_decode(lacx_decoder* d, const uint8_t* lac, uint64_t size, int3
                 goto done;
             }
         }
-        // the two channels leave on two streams' worth of copy engine time: issue both, then wait
-        DEC_TRY(hipMemcpyAsync(left, d->d_left, frames * sizeof(int32_t), hipMemcpyDeviceToHost, st), "D2H left");
-        if (info.channels == 2) DEC_TRY(hipMemcpyAsync(right, d->d_right, frames * sizeof(int32_t), hipMemcpyDeviceToHost, st), "D2H right");
+        if (wav) {  // header and data in one copy, aligned base to aligned base
+            DEC_TRY(hipMemcpyAsync(d->h_wav, d->d_wav, image, hipMemcpyDeviceToHost, st), "D2H WAV image");
+        } else {
+            // the two channels leave on two streams' worth of copy engine time: issue both, then wait
+            DEC_TRY(hipMemcpyAsync(left, d->d_left, frames * sizeof(int32_t), hipMemcpyDeviceToHost, st), "D2H left");
+            if (info.channels == 2) DEC_TRY(hipMemcpyAsync(right, d->d_right, frames * sizeof(int32_t), hipMemcpyDeviceToHost, st), "D2H right");
+        }
         DEC_TRY(hipStreamSynchronize(st), "synchronize");
+        if (wav) *wav_size = image;
     }
 done:
 #undef DEC_TRY
     if (prev_device >= 0) (void)hipSetDevice(prev_device);
     return rc;
+}
+}  // namespace
+
+int lacx_decoder_decode(lacx_decoder* d, const uint8_t* lac, uint64_t size, int32_t* left, int32_t* right, uint64_t frames,
+                        float* device_ms) {
+    if (!d) return decode_fail(LACX_E_INVALID, "null decoder");
+    lacx_stream_info info;
+    const int prc = lacx_stream_parse(lac, size, &info);
+    if (prc) return prc;
+    if (!left || (info.channels == 2 && !right)) return decode_fail(LACX_E_INVALID, "output arrays missing");
+    if (frames != info.frames) return decode_fail(LACX_E_INVALID, "output arrays do not match the stream's frame count");
+    return decode_run(d, lac, size, info, left, right, false, nullptr, device_ms);
+}
+
+int lacx_decoder_decode_wav_view(lacx_decoder* d, const uint8_t* lac, uint64_t size, const uint8_t** out, uint64_t* out_size,
+                                 float* device_ms) {
+    if (out) *out = nullptr;
+    if (out_size) *out_size = 0;
+    if (!d) return decode_fail(LACX_E_INVALID, "null decoder");
+    if (!out || !out_size) return decode_fail(LACX_E_INVALID, "null argument");
+    lacx_stream_info info;
+    const int prc = lacx_stream_parse(lac, size, &info);
+    if (prc) return prc;
+    uint64_t image = 0;
+    const int rc = decode_run(d, lac, size, info, nullptr, nullptr, true, &image, device_ms);
+    if (rc) return rc;
+    *out = d->h_wav;
+    *out_size = image;
+    return LACX_OK;
+}
+
+int lacx_decoder_decode_wav(lacx_decoder* d, const uint8_t* lac, uint64_t size, uint8_t** out, uint64_t* out_size,
+                            float* device_ms) {
+    if (out) *out = nullptr;
+    if (out_size) *out_size = 0;
+    if (!out || !out_size) return decode_fail(LACX_E_INVALID, "null argument");
+    const uint8_t* view = nullptr;
+    uint64_t n = 0;
+    const int rc = lacx_decoder_decode_wav_view(d, lac, size, &view, &n, device_ms);
+    if (rc) return rc;
+    uint8_t* buf = static_cast<uint8_t*>(std::malloc(n));
+    if (!buf) return decode_fail(LACX_E_RUNTIME, "out of host memory");
+    std::memcpy(buf, view, n);
+    *out = buf;
+    *out_size = n;
+    return LACX_OK;
 }
 
 int lacx_decode(int device, const uint8_t* lac, uint64_t size, int32_t* left, int32_t* right, uint64_t frames,

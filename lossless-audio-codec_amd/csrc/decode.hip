@@ -11,6 +11,8 @@
 //   k_decode      bitstream -> residuals -> samples (fixed / FIR / LPC synthesis), planar int32, per-block status
 //   k_ms_inverse  mid/side -> left/right where the block's flag says so, and the bit-depth range check
 //                                                                        (ref src/codec/lac/decoder.cpp:48-65,30-46)
+//   k_wav_pack    the same per-sample work as k_ms_inverse, written as the data region of a canonical WAV image
+//                 (interleaved little-endian 16 / 24-bit, ref src/main.cpp:150-182) instead of back into left/right
 // The adaptive Rice parameter uses the encoder's division-free formulation (kmean / biased_k of analyze_core.h, proven
 // against Rice::adapt_k there); it assumes zigzag residuals below 2^30 like the encoder does, and a stream with a larger
 // one is refused (status 9) rather than decoded differently from the reference.
@@ -506,9 +508,146 @@ static void launch_ms_inverse(uint32_t num_blocks, int channels, int bit_depth, 
                        left, right, ms_flag, status);
 }
 
+// The block that holds frame f: the regular layout (every block but the last 16384 frames) is a guess that one
+// comparison confirms; any other table (non-final blocks may be any length from 256 frames on) is searched.
+__device__ __forceinline__ uint32_t block_of_frame(const unsigned long long* __restrict__ frame_off, uint32_t num_blocks,
+                                                   unsigned long long f) {
+    uint32_t g = (uint32_t)(f / (unsigned long long)kMaxBlock);
+    if (g >= num_blocks) g = num_blocks - 1u;
+    if (frame_off[g] <= f && f < frame_off[g + 1]) return g;
+    uint32_t lo = 0, hi = num_blocks;  // frame_off[lo] <= f < frame_off[hi]
+    while (hi - lo > 1u) {
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        if (frame_off[mid] <= f) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+__device__ __forceinline__ uint32_t pack16(int32_t a, int32_t b) { return ((uint32_t)a & 0xFFFFu) | ((uint32_t)b << 16); }
+// four 24-bit samples, low three bytes each, little-endian: three dwords
+__device__ __forceinline__ void pack24(int32_t a, int32_t b, int32_t c, int32_t d, uint32_t* w) {
+    const uint32_t ua = (uint32_t)a & 0xFFFFFFu, ub = (uint32_t)b & 0xFFFFFFu, uc = (uint32_t)c & 0xFFFFFFu, ud = (uint32_t)d;
+    w[0] = ua | (ub << 24);
+    w[1] = (ub >> 8) | (uc << 16);
+    w[2] = (uc >> 16) | (ud << 8);
+}
+
+// One thread per unit of four consecutive frames of the stream (frames 4u .. 4u+3): 8, 12, 16 or 24 bytes of the image at
+// 44 + 4u * block_align, always 4-byte aligned, so a whole unit leaves as dword stores (x2 / x3 / x4+x2) and the
+// samples arrive as one 16-byte load per channel.  Block boundaries may fall anywhere (non-final blocks of any length
+// from 256 frames on, odd ones included), so the block -- MS flag and status -- is looked up per frame; a unit spans at
+// most two blocks.  The last unit is written byte by byte and writes the RIFF pad byte when the data size is odd.
+// wav_data: the image's first byte (the 44-byte header is the host's).
+__global__ __launch_bounds__(256) void k_wav_pack(uint32_t num_blocks, int channels, int bit_depth, unsigned long long frames,
+                                                  const unsigned long long* __restrict__ frame_off,
+                                                  const int32_t* __restrict__ left, const int32_t* __restrict__ right,
+                                                  const uint8_t* __restrict__ ms_flag, uint32_t* __restrict__ status,
+                                                  uint8_t* __restrict__ wav_data) {
+    const unsigned long long f0 = 4ull * ((unsigned long long)blockIdx.x * 256u + threadIdx.x);
+    if (f0 >= frames) return;
+    const uint32_t nf = frames - f0 >= 4u ? 4u : (uint32_t)(frames - f0);
+    const bool stereo = channels == 2;
+    int32_t l[4] = {0, 0, 0, 0}, r[4] = {0, 0, 0, 0};
+    if (nf == 4u) {
+        const int4 a = *reinterpret_cast<const int4*>(left + f0);  // f0 is a multiple of 4: 16-byte aligned
+        l[0] = a.x, l[1] = a.y, l[2] = a.z, l[3] = a.w;
+        if (stereo) {
+            const int4 b = *reinterpret_cast<const int4*>(right + f0);
+            r[0] = b.x, r[1] = b.y, r[2] = b.z, r[3] = b.w;
+        }
+    } else {  // (fixed trip counts throughout: l / r stay in registers)
+#pragma unroll
+        for (uint32_t i = 0; i < 3u; ++i) {
+            if (i < nf) {
+                l[i] = left[f0 + i];
+                if (stereo) r[i] = right[f0 + i];
+            }
+        }
+    }
+    const uint32_t b0 = block_of_frame(frame_off, num_blocks, f0);
+    const unsigned long long split = frame_off[b0 + 1];  // frames from here on belong to block b0 + 1
+    const uint32_t b1 = f0 + nf > split ? b0 + 1u : b0;
+    const uint32_t st0 = status[b0], st1 = status[b1];
+    const bool ms0 = stereo && ms_flag[b0] != 0, ms1 = stereo && ms_flag[b1] != 0;
+    const long long lo = bit_depth == 16 ? -32768 : -0x800000, hi = bit_depth == 16 ? 32767 : 0x7FFFFF;
+    bool bad0 = false, bad1 = false;
+#pragma unroll
+    for (uint32_t i = 0; i < 4u; ++i) {
+        const bool second = f0 + i >= split;
+        long long a = l[i], b = r[i];
+        if (second ? ms1 : ms0) {  // ref lac/decoder.cpp:48-65
+            const long long m = a, s = b;
+            a = m + ((s + (s & 1)) >> 1);
+            b = a - s;
+        }
+        l[i] = (int32_t)a;
+        r[i] = (int32_t)b;
+        const bool bad = i < nf && (a < lo || a > hi || (stereo && (b < lo || b > hi)));
+        bad0 = bad0 || (bad && !second);
+        bad1 = bad1 || (bad && second);
+    }
+    // blocks that did not decode are not checked (their status already fails the call)
+    if (bad0 && st0 == 0u) atomicMax(&status[b0], 7u);
+    if (bad1 && st1 == 0u) atomicMax(&status[b1], 7u);
+
+    const uint32_t bps = (uint32_t)bit_depth / 8u, align = (uint32_t)channels * bps;
+    uint8_t* dst = static_cast<uint8_t*>(__builtin_assume_aligned(wav_data + 44 + f0 * align, 4));
+    if (nf == 4u) {
+        uint32_t w[6];
+        if (bps == 2u) {
+            if (stereo) {
+                w[0] = pack16(l[0], r[0]), w[1] = pack16(l[1], r[1]), w[2] = pack16(l[2], r[2]), w[3] = pack16(l[3], r[3]);
+                __builtin_memcpy(dst, w, 16);
+            } else {
+                w[0] = pack16(l[0], l[1]), w[1] = pack16(l[2], l[3]);
+                __builtin_memcpy(dst, w, 8);
+            }
+        } else if (stereo) {
+            pack24(l[0], r[0], l[1], r[1], w);
+            pack24(l[2], r[2], l[3], r[3], w + 3);
+            __builtin_memcpy(dst, w, 24);
+        } else {
+            pack24(l[0], l[1], l[2], l[3], w);
+            __builtin_memcpy(dst, w, 12);
+        }
+    } else {
+#pragma unroll
+        for (uint32_t i = 0; i < 3u; ++i) {
+#pragma unroll
+            for (uint32_t c = 0; c < 2u; ++c) {
+                const uint32_t v = (uint32_t)(c ? r[i] : l[i]);
+#pragma unroll
+                for (uint32_t k = 0; k < 3u; ++k)
+                    if (i < nf && c < (uint32_t)channels && k < bps) dst[i * align + c * bps + k] = (uint8_t)(v >> (8u * k));
+            }
+        }
+    }
+    if (f0 + nf == frames && ((frames * align) & 1ull)) dst[nf * align] = 0;  // RIFF pad byte
+}
+
+static void launch_wav_pack(uint32_t num_blocks, int channels, int bit_depth, unsigned long long frames,
+                            const unsigned long long* frame_off, const int32_t* left, const int32_t* right,
+                            const uint8_t* ms_flag, uint32_t* status, uint8_t* wav_data, hipStream_t stream) {
+    const unsigned long long units = (frames + 3u) / 4u;
+    if (units == 0) return;
+    hipLaunchKernelGGL(k_wav_pack, dim3((uint32_t)((units + 255u) / 256u)), dim3(256), 0, stream, num_blocks, channels, bit_depth,
+                       frames, frame_off, left, right, ms_flag, status, wav_data);
+}
+
+// the pass after the block decode: k_ms_inverse in place, or k_wav_pack into a WAV image
+static void launch_post_decode(uint32_t num_blocks, int channels, int bit_depth, const unsigned long long* frame_off,
+                               int32_t* left, int32_t* right, const uint8_t* ms_flag, uint32_t* status, uint8_t* wav_data,
+                               unsigned long long frames, hipStream_t stream) {
+    if (wav_data)
+        launch_wav_pack(num_blocks, channels, bit_depth, frames, frame_off, left, right, ms_flag, status, wav_data, stream);
+    else
+        launch_ms_inverse(num_blocks, channels, bit_depth, frame_off, left, right, ms_flag, status, stream);
+}
+
 hipError_t launch_decode(uint32_t num_blocks, int channels, int stereo_mode, int bit_depth, const uint8_t* payload,
                          const unsigned long long* byte_off, const unsigned long long* frame_off, int32_t* left,
-                         int32_t* right, uint32_t* status, uint8_t* ms_flag, hipStream_t stream) {
+                         int32_t* right, uint32_t* status, uint8_t* ms_flag, hipStream_t stream, uint8_t* wav_data,
+                         unsigned long long frames) {
     if (num_blocks == 0) return hipSuccess;
     static const uint32_t lanes = [] {  // blocks per wave (see k_decode); LACX_DECODE_LANES: tuning knob, read once
         if (const char* v = std::getenv("LACX_DECODE_LANES")) {  // 1, 2, 4, ... 64
@@ -523,17 +662,18 @@ hipError_t launch_decode(uint32_t num_blocks, int channels, int stereo_mode, int
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_decode, dim3((num_blocks + lanes - 1) / lanes), dim3(kDecThreads), smem, stream, num_blocks, channels,
                        stereo_mode, lanes, payload, byte_off, frame_off, left, right, status, ms_flag);
-    launch_ms_inverse(num_blocks, channels, bit_depth, frame_off, left, right, ms_flag, status, stream);
+    launch_post_decode(num_blocks, channels, bit_depth, frame_off, left, right, ms_flag, status, wav_data, frames, stream);
     return hipGetLastError();
 }
 
 hipError_t launch_decode_serial(uint32_t num_blocks, int channels, int stereo_mode, int bit_depth, const uint8_t* payload,
                                 uint32_t payload_bits, const unsigned long long* frame_off, int32_t* left, int32_t* right,
-                                uint32_t* status, uint8_t* ms_flag, hipStream_t stream) {
+                                uint32_t* status, uint8_t* ms_flag, hipStream_t stream, uint8_t* wav_data,
+                                unsigned long long frames) {
     if (num_blocks == 0) return hipSuccess;
     hipLaunchKernelGGL(k_decode_serial, dim3(1), dim3(kDecThreads), kDecBytesPerCol, stream, num_blocks, channels, stereo_mode,
                        payload, payload_bits, frame_off, left, right, status, ms_flag);
-    launch_ms_inverse(num_blocks, channels, bit_depth, frame_off, left, right, ms_flag, status, stream);
+    launch_post_decode(num_blocks, channels, bit_depth, frame_off, left, right, ms_flag, status, wav_data, frames, stream);
     return hipGetLastError();
 }
 

@@ -178,14 +178,19 @@ hipError_t launch_stream_out(const LaunchSet& ls, const DeviceWorkspace& ws, uin
 constexpr size_t kDecodeTailPad = 128;
 // The decoder's entry points:  byte_off / frame_off:
 // [num_blocks + 1] prefix sums of the block table; status[blk] = 0 or an error code, ms_flag[blk] = the block's LR/MS flag.
+// wav_data = nullptr: left / right end as the decoded PCM (k_ms_inverse in place).  Otherwise the first byte of a WAV
+// image of 44 + data + pad bytes (4-byte aligned; the header is the caller's) whose data region receives the `frames`
+// frames interleaved and narrowed to the bit depth (k_wav_pack); left / right then hold the pre-inverse samples.
 hipError_t launch_decode(uint32_t num_blocks, int channels, int stereo_mode, int bit_depth, const uint8_t* payload,
                          const unsigned long long* byte_off, const unsigned long long* frame_off, int32_t* left,
-                         int32_t* right, uint32_t* status, uint8_t* ms_flag, hipStream_t stream);
+                         int32_t* right, uint32_t* status, uint8_t* ms_flag, hipStream_t stream, uint8_t* wav_data = nullptr,
+                         unsigned long long frames = 0);
 
 // The legacy version-2 container (no compressed block sizes): one lane walks the whole payload.
 hipError_t launch_decode_serial(uint32_t num_blocks, int channels, int stereo_mode, int bit_depth, const uint8_t* payload,
                                 uint32_t payload_bits, const unsigned long long* frame_off, int32_t* left, int32_t* right,
-                                uint32_t* status, uint8_t* ms_flag, hipStream_t stream);
+                                uint32_t* status, uint8_t* ms_flag, hipStream_t stream, uint8_t* wav_data = nullptr,
+                                unsigned long long frames = 0);
 
 // Block::Encoder::encode's analysis for one block of arbitrary int32 samples (wide.hip): d_res = scratch for the eleven
 // candidate residuals ([11][kMaxBlock] int32), d_plan receives the plan.

@@ -107,6 +107,7 @@ EXPORTS = (
     "lacx_encoder_create_multi", "lacx_encoder_lanes", "lacx_fanout_range", "lacx_encode_fanout_resident",
     "lacx_get_fanout_stats", "lacx_get_lane_timing", "lacx_fanout_exchange_note",
     "lacx_decoder_create", "lacx_decoder_destroy", "lacx_decoder_decode", "lacx_sizeof",
+    "lacx_decoder_decode_wav", "lacx_decoder_decode_wav_view",
 )
 
 
@@ -156,6 +157,9 @@ def lib():
         L.lacx_encoder_lanes.restype = C.c_uint32
         L.lacx_encoder_lanes.argtypes = [C.c_void_p]
         L.lacx_fanout_range.restype = None
+        L.lacx_decoder_decode_wav.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), C.c_uint64, C.POINTER(C.POINTER(C.c_uint8)),
+                                              C.POINTER(C.c_uint64), C.POINTER(C.c_float)]
+        L.lacx_decoder_decode_wav_view.argtypes = L.lacx_decoder_decode_wav.argtypes
         # the structs declared in this file against the library's own sizeof(): a layout that has drifted from
         # include/lacx.h would otherwise show up as memory corruption behind the first call that fills one
         L.lacx_sizeof.restype = C.c_uint32
@@ -630,6 +634,7 @@ class Decoder:
         self._h = h
         self._reuse = reuse_output
         self._left = self._right = None
+        self.last_ms = 0.0
 
     def close(self):
         if self._h is not None:
@@ -665,6 +670,45 @@ class Decoder:
         if rc != OK:
             raise RuntimeError(lib().lacx_decode_last_error().decode(errors="replace"))
         return left, right, info, float(ms.value)
+
+    def _decode_wav(self, fn, lac):
+        if self._h is None:
+            raise RuntimeError("decoder is closed")
+        buf = np.frombuffer(lac, dtype=np.uint8)
+        out = C.POINTER(C.c_uint8)()
+        size = C.c_uint64()
+        ms = C.c_float()
+        rc = fn(self._h, buf.ctypes.data_as(C.POINTER(C.c_uint8)), C.c_uint64(buf.size), C.byref(out), C.byref(size),
+                C.byref(ms))
+        if rc != OK:
+            raise RuntimeError(lib().lacx_decode_last_error().decode(errors="replace"))
+        self.last_ms = float(ms.value)
+        return out, size.value
+
+    def decode_wav(self, lac) -> bytes:
+        """The .lac as a canonical WAV file image (44-byte header, interleaved PCM, pad byte), byte-identical to the
+        reference CLI's `decode` output (ref src/main.cpp:184-431); kernel milliseconds in `last_ms`.
+        RuntimeError("[decode-error] ...") like `decode`."""
+        out, size = self._decode_wav(lib().lacx_decoder_decode_wav, lac)
+        try:
+            return C.string_at(out, size)
+        finally:
+            lib().lacx_free(out)
+
+    def decode_wav_view(self, lac) -> np.ndarray:
+        """Zero-copy form of decode_wav: a uint8 view of the decoder's pinned image buffer, valid until this decoder's
+        next call (copy it to keep it)."""
+        out, size = self._decode_wav(lib().lacx_decoder_decode_wav_view, lac)
+        return np.ctypeslib.as_array(out, shape=(size,))
+
+
+def decode_wav(lac, device: int = -1) -> bytes:
+    """Decoder(device).decode_wav(lac) for one stream: the WAV file image of a .lac, made on the device."""
+    dec = Decoder(device)
+    try:
+        return dec.decode_wav(lac)
+    finally:
+        dec.close()
 
 
 def assemble(sample_rate: int, bit_depth: int, stereo_mode: int, channels: int, shards) -> bytes:

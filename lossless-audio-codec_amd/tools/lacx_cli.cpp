@@ -1,10 +1,13 @@
-// lacx_cli -- the `encode` command of the reference's command-line tool on the MI355X path (SURVEY row f-4;
-// ref src/main.cpp:609-710): same positional arguments, every flag of the reference's encode command with the same
+// lacx_cli -- the `encode` and `decode` commands of the reference's command-line tool on the MI355X path (SURVEY row f-4;
+// ref src/main.cpp:609-781).  encode (ref :609-710): same positional arguments, every flag of the reference's encode command with the same
 // meaning and rejection rules (--stereo-mode=lr|ms, --no-partitioning, --threads=N, the --debug-* family), LAC_THREADS
 // resolved by the tool and not by the library (ref :586-591), the same-file check on the resolved paths (ref :433-444),
 // the same messages, staged output (written next to the target, renamed on success).  The WAV file goes through
 // lacx_wav_parse / lacx_encode_wav_view: the raw data chunk is what crosses PCIe, the .lac is written to the file
-// straight from the encoder's pinned result buffer.  Decode and selftest stay with the reference's tool.
+// straight from the encoder's pinned result buffer.  decode (ref :712-781): the same argument checks and messages, the
+// .lac parsed on the host first (structural errors need no device), then lacx_decoder_decode_wav_view on the current
+// device; the WAV file is written, staged like encode's output, straight from the decoder's pinned image buffer.
+// Selftest stays with the reference's tool.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -24,7 +27,8 @@ namespace {
 
 void usage() {
     std::cerr << "Usage:\n  lacx_cli encode input.wav output.lac [--stereo-mode=lr|ms] [--threads=N] [--debug-threads] [--debug-lpc] "
-                 "[--debug-stereo-est] [--debug-zr] [--debug-partitions] [--no-partitioning]\n";
+                 "[--debug-stereo-est] [--debug-zr] [--debug-partitions] [--no-partitioning]\n"
+                 "  lacx_cli decode input.lac output.wav [--threads=N] [--debug-threads]\n";
 }
 
 // A positive decimal integer and nothing else (ref src/main.cpp:560-584, src/codec/lac/thread_limit.hpp:10-28).
@@ -48,6 +52,113 @@ bool same_file(const std::string& a, const std::string& b) {
     return !ec && na == nb;
 }
 
+// --threads=N when given, else LAC_THREADS (ref src/main.cpp:586-591); false after printing the rejection.  0: neither.
+bool resolve_threads(unsigned long long& threads) {
+    if (threads == 0) {
+        const char* env = std::getenv("LAC_THREADS");
+        if (env && *env) {
+            const std::string v = env;
+            bool digits = true;
+            for (char c : v) digits = digits && c >= '0' && c <= '9';
+            if (digits && v.size() > 18) {
+                std::cerr << "Error: LAC_THREADS is too large\n";
+                return false;
+            }
+            if (!positive_integer(v, threads)) {
+                std::cerr << "Error: LAC_THREADS must be a positive integer\n";
+                return false;
+            }
+        }
+    }
+    return true;
+}
+
+// The reference's load_file (ref src/main.cpp:50-63): at most 1 GiB.
+bool load_file(const std::string& path, std::vector<uint8_t>& data) {
+    std::ifstream f(path, std::ios::binary);
+    if (!f) return false;
+    f.seekg(0, std::ios::end);
+    const std::streamsize size = f.tellg();
+    if (size < 0 || (unsigned long long)size > (1ull << 30)) return false;
+    f.seekg(0, std::ios::beg);
+    data.resize((size_t)size);
+    if (size > 0) {
+        f.read(reinterpret_cast<char*>(data.data()), size);
+        if (f.gcount() != size) return false;
+    }
+    return true;
+}
+
+// lacx_cli decode input.lac output.wav [--threads=N] [--debug-threads] (ref src/main.cpp:712-781)
+int decode_command(int argc, char** argv) {
+    const std::string in_path = argv[2], out_path = argv[3];
+    if (same_file(in_path, out_path)) {
+        std::cerr << "Input and output paths must be different\n";
+        return 1;
+    }
+    bool debug_threads = false;
+    unsigned long long threads = 0;
+    for (int i = 4; i < argc; ++i) {
+        const std::string flag = argv[i];
+        const std::string tprefix = "--threads=";
+        if (flag == "--debug-threads") {
+            debug_threads = true;
+        } else if (flag.compare(0, tprefix.size(), tprefix) == 0) {
+            if (!positive_integer(flag.substr(tprefix.size()), threads)) {
+                std::cerr << "Error: --threads requires a positive integer\n";
+                return 1;
+            }
+        } else {
+            usage();
+            return 1;
+        }
+    }
+    if (!resolve_threads(threads)) return 1;  // validated like encode's; the decode itself runs on the device
+    std::vector<uint8_t> lac;
+    if (!load_file(in_path, lac)) {
+        std::cerr << "Failed to read LAC file: " << in_path << "\n";
+        return 1;
+    }
+    lacx_stream_info info{};
+    if (lacx_stream_parse(lac.data(), lac.size(), &info) != LACX_OK) {  // structural errors need no device
+        std::cerr << "Decode failed: " << lacx_decode_last_error() << "\n";
+        return 1;
+    }
+    lacx_decoder* dec = nullptr;
+    if (lacx_decoder_create(-1, &dec) != LACX_OK) {
+        std::cerr << "Error: lacx_decoder_create failed\n";
+        return 1;
+    }
+    const uint8_t* wav = nullptr;
+    uint64_t wav_size = 0;
+    if (lacx_decoder_decode_wav_view(dec, lac.data(), lac.size(), &wav, &wav_size, nullptr) != LACX_OK) {
+        std::cerr << "Decode failed: " << lacx_decode_last_error() << "\n";
+        lacx_decoder_destroy(dec);
+        return 1;
+    }
+    const std::string tmp = out_path + ".lacx-partial";
+    bool ok = false;
+    {
+        std::ofstream out(tmp, std::ios::binary | std::ios::trunc);
+        ok = out && out.write(reinterpret_cast<const char*>(wav), (std::streamsize)wav_size) && out.flush();
+    }
+    ok = ok && !same_file(in_path, out_path) && std::rename(tmp.c_str(), out_path.c_str()) == 0;
+    lacx_decoder_destroy(dec);  // the view dies with the decoder
+    if (!ok) {
+        std::remove(tmp.c_str());
+        std::cerr << "Failed to write WAV: " << out_path << "\n";
+        return 1;
+    }
+    std::cout << "Decoded " << in_path << " -> " << out_path << " (" << info.frames << " samples per channel)\n";
+    if (debug_threads) {
+        // The blocks are decoded on the device; on the host the call uses the calling thread, which is what the
+        // reference reports for a one-thread run (ref :790-799).
+        std::cout << "Decoder thread usage: 1 threads\n  " << std::this_thread::get_id() << "\n";
+        std::cout << "WARNING: Decoder multi-threading may not be active.\n";
+    }
+    return 0;
+}
+
 struct Encoded {
     const uint8_t* data = nullptr;
     uint64_t size = 0;
@@ -56,10 +167,11 @@ struct Encoded {
 }  // namespace
 
 int main(int argc, char** argv) {
-    if (argc < 4 || std::string(argv[1]) != "encode") {
+    if (argc < 4 || (std::string(argv[1]) != "encode" && std::string(argv[1]) != "decode")) {
         usage();
         return 1;
     }
+    if (std::string(argv[1]) == "decode") return decode_command(argc, argv);
     const std::string in_path = argv[2], out_path = argv[3];
     if (same_file(in_path, out_path)) {
         std::cerr << "Input and output paths must be different\n";
@@ -93,22 +205,7 @@ int main(int argc, char** argv) {
             return 1;
         }
     }
-    if (threads == 0) {  // --threads wins, else LAC_THREADS (ref src/main.cpp:586-591)
-        const char* env = std::getenv("LAC_THREADS");
-        if (env && *env) {
-            const std::string v = env;
-            bool digits = true;
-            for (char c : v) digits = digits && c >= '0' && c <= '9';
-            if (digits && v.size() > 18) {
-                std::cerr << "Error: LAC_THREADS is too large\n";
-                return 1;
-            }
-            if (!positive_integer(v, threads)) {
-                std::cerr << "Error: LAC_THREADS must be a positive integer\n";
-                return 1;
-            }
-        }
-    }
+    if (!resolve_threads(threads)) return 1;
     std::ifstream in(in_path, std::ios::binary);
     std::vector<uint8_t> wav;
     if (in) wav.assign(std::istreambuf_iterator<char>(in), std::istreambuf_iterator<char>());
