@@ -29,6 +29,7 @@
  *   lacx_decode            <- LAC::Decoder::decode          ref src/codec/lac/decoder.hpp:10-24, decoder.cpp:76-303,
  *                                                            src/codec/block/decoder.cpp:64-520
  *   lacx_decoder_decode_wav <- the `decode` command's WAV writer ref src/main.cpp:127-182, 184-431
+ *   lacx_decoder_decode_wav_batch_view, lacx_decoder_decode_batch_device <- many .lac streams as one device job
  *
  * All analysis (and the decode) runs in hand-written HIP kernels on a gfx950 device; there is no CPU fallback: every
  * call that needs the device fails with LACX_E_DEVICE when none is usable.
@@ -131,7 +132,7 @@ void lacx_get_timing(const lacx_encoder* enc, lacx_timing* out);
 
 /* sizeof() of a public struct as this library was built, by name without the prefix ("config", "channel_plan",
  * "block_plan", "timing", "pcm", "batch_item", "batch_out", "wav_info", "fanout_shard", "fanout_out", "fanout_stats",
- * "stream_info"); 0 for an unknown name.  A binding that declares the structs itself (ctypes, cgo, JNI) checks its layout
+ * "stream_info", "span", "decode_item"); 0 for an unknown name.  A binding that declares the structs itself (ctypes, cgo, JNI) checks its layout
  * against this before the first call that fills one. */
 uint32_t lacx_sizeof(const char* struct_name);
 
@@ -360,6 +361,45 @@ int lacx_decoder_decode_wav(lacx_decoder* dec, const uint8_t* lac, uint64_t size
                             uint8_t** out, uint64_t* out_size, float* device_ms);
 int lacx_decoder_decode_wav_view(lacx_decoder* dec, const uint8_t* lac, uint64_t size,
                                  const uint8_t** out, uint64_t* out_size, float* device_ms);
+
+/* Many streams as ONE decode.  A single stream never decodes in less than one block's serial chain, however few blocks
+ * it has, and leaves most of the chip idle; a batch puts every block of every item into one launch (one lane per
+ * version-3 block, one lane per version-2 item), so a collection costs about one chain.  Each item keeps its own rate,
+ * depth, channels, stereo mode and container version.
+ * Per-item outcome: one bad stream does not cost the others.  item_rc (nullable, n entries) receives LACX_OK or the
+ * item's code, lacx_decoder_item_error(dec, i) the item's message from the last batch call ("" when it decoded): exactly
+ * what the single-stream call reports for it (lacx_stream_parse's errors, "[decode-error] block=N ...").  The call
+ * returns LACX_OK when every item decoded, else the lowest failing item's code with "stream i: <message>" in
+ * lacx_decode_last_error; LACX_E_DEVICE only for a failure of the whole call (every item that parsed then carries it).
+ * Parse errors are found on the host before any device call; without a device the per-item parse results are still
+ * filled and the call returns LACX_E_DEVICE "no usable HIP device".  n = 0 or a null array: LACX_E_INVALID.
+ * A batch and single-stream calls may alternate on one decoder.  device_ms (nullable): kernel time of the batch. */
+typedef struct lacx_span {
+    const uint8_t* data;
+    uint64_t size;
+} lacx_span;
+/* lacs[i]: the items' .lac bytes.  out[i]: item i's WAV image (what lacx_decoder_decode_wav gives for it alone), {NULL, 0}
+ * for a failed item.  _view: the images lie in the decoder's pinned image buffer (16-byte aligned each, one D2H copy for
+ * all), valid until the decoder's next call; lacx_decoder_decode_wav_batch: each image malloc'd, release with lacx_free. */
+int lacx_decoder_decode_wav_batch_view(lacx_decoder* dec, const lacx_span* lacs, uint32_t n, lacx_span* out, int* item_rc,
+                                       float* device_ms);
+int lacx_decoder_decode_wav_batch(lacx_decoder* dec, const lacx_span* lacs, uint32_t n, lacx_span* out, int* item_rc,
+                                  float* device_ms);
+/* Device-resident output: left / right (right NULL for mono) are caller-owned device arrays of `frames` int32 each on the
+ * decoder's device (a torch tensor's data_ptr()); nothing outside [0, frames) is written.  A missing array or a frames
+ * mismatch fails that item with LACX_E_INVALID (lacx_decoder_decode's messages).  The work goes on `stream` (a
+ * hipStream_t, NULL = the null stream) behind what is already there; the call returns once the outputs are final and the
+ * statuses checked.  The arrays of a failed item hold unspecified samples. */
+typedef struct lacx_decode_item {
+    const uint8_t* lac;
+    uint64_t size;
+    int32_t* left;
+    int32_t* right;
+    uint64_t frames;
+} lacx_decode_item;
+int lacx_decoder_decode_batch_device(lacx_decoder* dec, const lacx_decode_item* items, uint32_t n, void* stream,
+                                     int* item_rc, float* device_ms);
+const char* lacx_decoder_item_error(const lacx_decoder* dec, uint32_t i);
 
 /* Block::Encoder::encode drop-in for one channel block of n <= 16384 samples of ANY int32 value: blocks inside the 25-bit
  * mid/side domain of validated 16 / 24-bit input run on the streaming kernels, wider ones on a kernel of their own that

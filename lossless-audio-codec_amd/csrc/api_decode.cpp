@@ -87,6 +87,10 @@ struct lacx_decoder {
     uint8_t* d_wav = nullptr;  // WAV image (lacx_decoder_decode_wav*): header + data + pad
     uint8_t* h_wav = nullptr;  // pinned, behind lacx_decoder_decode_wav_view
     uint64_t wav_cap = 0;      // bytes of each
+    uint8_t* d_meta = nullptr;  // batch calls: item descriptors, offsets and lane tables (one upload)
+    uint8_t* h_meta = nullptr;  // pinned
+    uint64_t meta_cap = 0;      // bytes of each
+    std::vector<std::string> item_err;  // the last batch call's message per item ("" = decoded)
     std::string err;
 };
 
@@ -106,6 +110,8 @@ void decoder_release(lacx_decoder* d) {
     if (d->h_offs) (void)hipHostFree(d->h_offs);
     if (d->d_wav) (void)hipFree(d->d_wav);
     if (d->h_wav) (void)hipHostFree(d->h_wav);
+    if (d->d_meta) (void)hipFree(d->d_meta);
+    if (d->h_meta) (void)hipHostFree(d->h_meta);
     *d = lacx_decoder{};
 }
 // lacx_decode (no handle): one decoder per device for the life of the process (never freed: releasing device memory from
@@ -155,6 +161,87 @@ uint64_t wav_header(const lacx_stream_info& info, uint8_t* h) {
     return 44u + data + pad;
 }
 
+// The decoder's grow-only buffers, shared by the single-stream and the batch calls.  Each returns the failing call's
+// error and names it in *what.
+hipError_t decoder_open(lacx_decoder* d, int* prev_device, const char** what) {  // *prev_device: to put back, or -1
+    hipError_t e = hipSuccess;
+    *prev_device = -1;
+    if (!d->ready && d->device < 0 && (e = hipGetDevice(&d->device)) != hipSuccess) return *what = "hipGetDevice", e;
+    int cur = -1;
+    if ((e = hipGetDevice(&cur)) != hipSuccess) return *what = "hipGetDevice", e;
+    if (cur != d->device) {
+        if ((e = hipSetDevice(d->device)) != hipSuccess) return *what = "hipSetDevice", e;
+        *prev_device = cur;
+    }
+    if (!d->ready) {
+        if ((e = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking)) != hipSuccess) return *what = "hipStreamCreate", e;
+        if ((e = hipEventCreate(&d->e0)) != hipSuccess) return *what = "hipEventCreate", e;
+        if ((e = hipEventCreate(&d->e1)) != hipSuccess) return *what = "hipEventCreate", e;
+        d->ready = true;
+    }
+    return e;
+}
+hipError_t grow_payload(lacx_decoder* d, uint64_t pay, const char** what) {  // pay bytes + the reader's tail pad
+    if (pay + kDecodeTailPad <= d->pay_cap) return hipSuccess;
+    if (d->d_pay) (void)hipFree(d->d_pay);
+    d->d_pay = nullptr;
+    d->pay_cap = 0;
+    const uint64_t cap = pay + pay / 8 + kDecodeTailPad;
+    *what = "hipMalloc(payload)";
+    const hipError_t e = hipMalloc((void**)&d->d_pay, cap);
+    if (e == hipSuccess) d->pay_cap = cap;
+    return e;
+}
+hipError_t grow_blocks(lacx_decoder* d, uint32_t nb, const char** what) {
+    if (nb <= d->blocks_cap) return hipSuccess;
+    if (d->d_offs) (void)hipFree(d->d_offs);
+    if (d->d_status) (void)hipFree(d->d_status);
+    if (d->d_ms) (void)hipFree(d->d_ms);
+    if (d->h_status) (void)hipHostFree(d->h_status);
+    if (d->h_offs) (void)hipHostFree(d->h_offs);
+    d->d_offs = nullptr;
+    d->d_status = nullptr;
+    d->d_ms = nullptr;
+    d->h_status = nullptr;
+    d->h_offs = nullptr;
+    d->blocks_cap = 0;
+    const uint32_t cap = nb + nb / 8 + 16;
+    hipError_t e;
+    if ((e = hipMalloc((void**)&d->d_offs, 2 * ((size_t)cap + 1) * sizeof(unsigned long long))) != hipSuccess) return *what = "hipMalloc(offsets)", e;
+    if ((e = hipMalloc((void**)&d->d_status, (size_t)cap * sizeof(uint32_t))) != hipSuccess) return *what = "hipMalloc(status)", e;
+    if ((e = hipMalloc((void**)&d->d_ms, cap)) != hipSuccess) return *what = "hipMalloc(flags)", e;
+    if ((e = hipHostMalloc((void**)&d->h_status, (size_t)cap * sizeof(uint32_t), 0)) != hipSuccess) return *what = "hipHostMalloc(status)", e;
+    if ((e = hipHostMalloc((void**)&d->h_offs, 2 * ((size_t)cap + 1) * sizeof(unsigned long long), 0)) != hipSuccess)
+        return *what = "hipHostMalloc(offsets)", e;
+    d->blocks_cap = cap;
+    return e;
+}
+hipError_t grow_wav(lacx_decoder* d, uint64_t bytes, const char** what) {  // device and pinned image buffers
+    if (bytes <= d->wav_cap) return hipSuccess;
+    if (d->d_wav) (void)hipFree(d->d_wav);
+    if (d->h_wav) (void)hipHostFree(d->h_wav);
+    d->d_wav = d->h_wav = nullptr;
+    d->wav_cap = 0;
+    const uint64_t cap = (bytes + 15u) & ~15ull;  // k_wav_pack writes whole dwords, and only inside the image
+    hipError_t e;
+    if ((e = hipMalloc((void**)&d->d_wav, cap)) != hipSuccess) return *what = "hipMalloc(wav)", e;
+    if ((e = hipHostMalloc((void**)&d->h_wav, cap, 0)) != hipSuccess) return *what = "hipHostMalloc(wav)", e;
+    d->wav_cap = cap;
+    return e;
+}
+hipError_t grow_pcm(lacx_decoder* d, uint64_t frames, const char** what) {  // both channels, whatever the stream's count
+    if (frames <= d->pcm_cap && d->d_right) return hipSuccess;
+    if (d->d_left) (void)hipFree(d->d_left);
+    if (d->d_right) (void)hipFree(d->d_right);
+    d->d_left = d->d_right = nullptr;
+    d->pcm_cap = 0;
+    hipError_t e;
+    if ((e = hipMalloc((void**)&d->d_left, frames * sizeof(int32_t))) != hipSuccess) return *what = "hipMalloc(left)", e;
+    if ((e = hipMalloc((void**)&d->d_right, frames * sizeof(int32_t))) != hipSuccess) return *what = "hipMalloc(right)", e;
+    d->pcm_cap = frames;
+    return e;
+}
+
 // Upload, block decode and the pass after it, status check, download: into left / right (wav = false), or as the WAV
 // image into d->h_wav (wav = true; *wav_size = its size).  info: lacx_stream_parse's of the same bytes.
 int decode_run(lacx_decoder* d, const uint8_t* lac, uint64_t size, const lacx_stream_info& info, int32_t* left,
@@ -178,70 +265,17 @@ int decode_run(lacx_decoder* d, const uint8_t* lac, uint64_t size, const lacx_st
     const uint64_t head = 14 + entry * nb, pay = size - head;
     const size_t noffs = 2 * ((size_t)nb + 1);  // byte offsets, then frame offsets
     int prev_device = -1;  // the caller's current device is put back on the way out
-    if (!d->ready) {
-        if (d->device < 0) DEC_TRY(hipGetDevice(&d->device), "hipGetDevice");
-    }
-    DEC_TRY(hipGetDevice(&prev_device), "hipGetDevice");
-    if (prev_device == d->device) prev_device = -1;
-    else DEC_TRY(hipSetDevice(d->device), "hipSetDevice");
-    if (!d->ready) {
-        DEC_TRY(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking), "hipStreamCreate");
-        DEC_TRY(hipEventCreate(&d->e0), "hipEventCreate");
-        DEC_TRY(hipEventCreate(&d->e1), "hipEventCreate");
-        d->ready = true;
-    }
-    if (pay + kDecodeTailPad > d->pay_cap) {
-        if (d->d_pay) (void)hipFree(d->d_pay);
-        d->d_pay = nullptr;
-        d->pay_cap = 0;
-        const uint64_t cap = pay + pay / 8 + kDecodeTailPad;
-        DEC_TRY(hipMalloc((void**)&d->d_pay, cap), "hipMalloc(payload)");
-        d->pay_cap = cap;
-    }
-    if (nb > d->blocks_cap) {
-        if (d->d_offs) (void)hipFree(d->d_offs);
-        if (d->d_status) (void)hipFree(d->d_status);
-        if (d->d_ms) (void)hipFree(d->d_ms);
-        if (d->h_status) (void)hipHostFree(d->h_status);
-        if (d->h_offs) (void)hipHostFree(d->h_offs);
-        d->d_offs = nullptr;
-        d->d_status = nullptr;
-        d->d_ms = nullptr;
-        d->h_status = nullptr;
-        d->h_offs = nullptr;
-        d->blocks_cap = 0;
-        const uint32_t cap = nb + nb / 8 + 16;
-        DEC_TRY(hipMalloc((void**)&d->d_offs, 2 * ((size_t)cap + 1) * sizeof(unsigned long long)), "hipMalloc(offsets)");
-        DEC_TRY(hipMalloc((void**)&d->d_status, (size_t)cap * sizeof(uint32_t)), "hipMalloc(status)");
-        DEC_TRY(hipMalloc((void**)&d->d_ms, cap), "hipMalloc(flags)");
-        DEC_TRY(hipHostMalloc((void**)&d->h_status, (size_t)cap * sizeof(uint32_t), 0), "hipHostMalloc(status)");
-        DEC_TRY(hipHostMalloc((void**)&d->h_offs, 2 * ((size_t)cap + 1) * sizeof(unsigned long long), 0), "hipHostMalloc(offsets)");
-        d->blocks_cap = cap;
-    }
+    const char* what = "";
+    DEC_TRY(decoder_open(d, &prev_device, &what), what);
+    DEC_TRY(grow_payload(d, pay, &what), what);
+    DEC_TRY(grow_blocks(d, nb, &what), what);
     if (wav) {
         uint8_t hdr[44];
         image = wav_header(info, hdr);
-        if (image > d->wav_cap) {
-            if (d->d_wav) (void)hipFree(d->d_wav);
-            if (d->h_wav) (void)hipHostFree(d->h_wav);
-            d->d_wav = d->h_wav = nullptr;
-            d->wav_cap = 0;
-            const uint64_t cap = (image + 15u) & ~15ull;  // k_wav_pack writes whole dwords, and only inside the image
-            DEC_TRY(hipMalloc((void**)&d->d_wav, cap), "hipMalloc(wav)");
-            DEC_TRY(hipHostMalloc((void**)&d->h_wav, cap, 0), "hipHostMalloc(wav)");
-            d->wav_cap = cap;
-        }
+        DEC_TRY(grow_wav(d, image, &what), what);
         std::memcpy(d->h_wav, hdr, sizeof hdr);  // goes up with the offsets, comes back with the data
     }
-    if (frames > d->pcm_cap || (info.channels == 2 && !d->d_right)) {
-        if (d->d_left) (void)hipFree(d->d_left);
-        if (d->d_right) (void)hipFree(d->d_right);
-        d->d_left = d->d_right = nullptr;
-        d->pcm_cap = 0;
-        DEC_TRY(hipMalloc((void**)&d->d_left, frames * sizeof(int32_t)), "hipMalloc(left)");
-        DEC_TRY(hipMalloc((void**)&d->d_right, frames * sizeof(int32_t)), "hipMalloc(right)");
-        d->pcm_cap = frames;
-    }
+    DEC_TRY(grow_pcm(d, frames, &what), what);
     {
         unsigned long long* byte_off = d->h_offs;
         unsigned long long* frame_off = d->h_offs + nb + 1;
@@ -292,6 +326,246 @@ done:
     if (prev_device >= 0) (void)hipSetDevice(prev_device);
     return rc;
 }
+
+const char* block_error(uint32_t st) {
+    static const char* const kWhat[] = {"", "block header", "channel header", "residual", "padding", "sample overflow",
+                                        "trailing bytes", "sample outside the bit depth", "not reached", "residual beyond 2^30"};
+    return st < 10 ? kWhat[st] : "?";
+}
+
+// One item of a batch call: the stream, and for the device form the caller's output arrays.
+struct BatchIn {
+    const uint8_t* lac;
+    uint64_t size;
+    int32_t* left;
+    int32_t* right;
+    uint64_t frames;
+};
+
+// Many streams as one decode (lacx_decoder_decode_wav_batch_view, lacx_decoder_decode_batch_device).  Every item is parsed
+// on the host first; those that parse go to the device together: their payloads back to back in one buffer (the tail pad
+// after the last), their block tables as global prefix sums, one lane per version-3 block (an item's blocks in
+// consecutive lanes) and one lane per version-2 item, then one post pass over all of them.  wav = true: the images into
+// the decoder's pinned image buffer (out[i]: each item's, 16-byte aligned, one D2H copy); false: into the caller's
+// arrays in place, on `stream`.  Per item: d->item_err and item_rc; the call returns the lowest failing item's code with
+// "stream i: <message>", or LACX_E_DEVICE for a failure of the whole call.
+int decode_batch_run(lacx_decoder* d, const BatchIn* in, uint32_t n, bool wav, hipStream_t stream, lacx_span* out,
+                     int* item_rc, float* device_ms) {
+    if (device_ms) *device_ms = 0.f;
+    std::vector<int> code(n, LACX_OK);
+    d->item_err.assign(n, std::string());
+    std::vector<lacx_stream_info> info(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        if (out) out[i] = lacx_span{nullptr, 0};
+        int c = lacx_stream_parse(in[i].lac, in[i].size, &info[i]);
+        if (c == LACX_OK && !wav) {  // lacx_decoder_decode's checks of the output arrays
+            if (!in[i].left || (info[i].channels == 2 && !in[i].right)) c = decode_fail(LACX_E_INVALID, "output arrays missing");
+            else if (in[i].frames != info[i].frames)
+                c = decode_fail(LACX_E_INVALID, "output arrays do not match the stream's frame count");
+        }
+        if (c != LACX_OK) {
+            code[i] = c;
+            d->item_err[i] = g_decode_err;
+        }
+    }
+    // the items that go to the device, and where each one lies in the batch's buffers
+    std::vector<uint32_t> dev;
+    std::vector<DecodeBatchItem> it;
+    std::vector<uint64_t> pcm_at, wav_at, image_size;
+    uint64_t total_blocks = 0, total_frames = 0, total_pay = 0, total_units = 0, pcm_total = 0, image_total = 0;
+    uint32_t v3_blocks = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (code[i] != LACX_OK) continue;
+        const lacx_stream_info& f = info[i];
+        const uint64_t head = 14 + (f.version == 2 ? 4ull : 8ull) * f.blocks;
+        DecodeBatchItem x{};
+        x.frame0 = total_frames;
+        x.frames = f.frames;
+        x.pay_off = total_pay;
+        x.block0 = (uint32_t)total_blocks;
+        x.blocks = f.blocks;
+        x.pay_bits = f.version == 2 ? (uint32_t)(8ull * (in[i].size - head)) : 0u;  // < 2^32: lacx_stream_parse
+        x.channels = f.channels;
+        x.stereo_mode = f.stereo_mode;
+        x.bit_depth = f.bit_depth;
+        x.version = f.version;
+        if (wav) {  // offsets for now, pointers once the buffers exist
+            pcm_at.push_back(pcm_total);
+            pcm_total += (f.frames + 3u) & ~3ull;  // every item's PCM from a multiple of 4 frames: 16-byte loads
+            uint8_t hdr[44];
+            const uint64_t image = wav_header(f, hdr);
+            wav_at.push_back(image_total);
+            image_size.push_back(image);
+            image_total += (image + 15u) & ~15ull;
+            total_units += (f.frames + 3u) / 4u;
+        } else {
+            x.left = in[i].left;
+            x.right = f.channels == 2 ? in[i].right : nullptr;
+        }
+        total_blocks += f.blocks;
+        total_frames += f.frames;
+        total_pay += in[i].size - head;
+        if (f.version != 2) v3_blocks += f.blocks;
+        dev.push_back(i);
+        it.push_back(x);
+    }
+    const char* no_device = lacx_device_count() <= 0 ? "no usable HIP device" : nullptr;
+    if (!no_device && total_blocks >= (1ull << 31)) no_device = "batch holds 2^31 blocks or more";
+    int rc = LACX_OK;
+    int prev_device = -1;
+    const uint32_t m = (uint32_t)dev.size();
+    if (no_device) {
+        rc = decode_fail(LACX_E_DEVICE, no_device);
+    } else if (m > 0) {
+#define DEC_TRY(call, what)                                                                                  \
+    do {                                                                                                     \
+        const hipError_t _e = (call);                                                                        \
+        if (_e != hipSuccess) {                                                                              \
+            rc = decode_fail(LACX_E_DEVICE, std::string(what) + ": " + hipGetErrorString(_e));               \
+            goto done;                                                                                       \
+        }                                                                                                    \
+    } while (0)
+        const char* what = "";
+        const uint32_t T = (uint32_t)total_blocks;
+        // LACX_DECODE_BATCH_PAD=1 (tuning knob, read per call): every item's blocks start a new wave
+        const char* pad_env = std::getenv("LACX_DECODE_BATCH_PAD");
+        const bool pad = pad_env && pad_env[0] == '1';
+        std::vector<uint32_t> lane_blk, v2_items;
+        lane_blk.reserve(v3_blocks);
+        for (uint32_t j = 0; j < m; ++j) {
+            if (it[j].version == 2) {
+                v2_items.push_back(j);
+                continue;
+            }
+            if (pad) while (lane_blk.size() % 64u) lane_blk.push_back(~0u);
+            for (uint32_t b = 0; b < it[j].blocks; ++b) lane_blk.push_back(it[j].block0 + b);
+        }
+        // metadata, one upload: items | byte_off [T + 1] | frame_off [T + 1] | unit_off [m + 1] | blk_item [T] |
+        // lane_blk | v2_items
+        const size_t o_items = 0, o_byte = (sizeof(DecodeBatchItem) * m + 15u) & ~(size_t)15u;
+        const size_t o_frame = o_byte + 8 * ((size_t)T + 1), o_unit = o_frame + 8 * ((size_t)T + 1);
+        const size_t o_bitem = o_unit + 8 * ((size_t)m + 1), o_lane = o_bitem + 4 * (size_t)T;
+        const size_t o_v2 = o_lane + 4 * lane_blk.size(), meta = o_v2 + 4 * v2_items.size();
+        DEC_TRY(decoder_open(d, &prev_device, &what), what);
+        DEC_TRY(grow_payload(d, total_pay, &what), what);
+        DEC_TRY(grow_blocks(d, T, &what), what);
+        if (wav) {
+            DEC_TRY(grow_wav(d, image_total, &what), what);
+            DEC_TRY(grow_pcm(d, pcm_total, &what), what);
+        }
+        if (meta > d->meta_cap) {
+            if (d->d_meta) (void)hipFree(d->d_meta);
+            if (d->h_meta) (void)hipHostFree(d->h_meta);
+            d->d_meta = d->h_meta = nullptr;
+            d->meta_cap = 0;
+            const uint64_t cap = meta + meta / 8 + 256;
+            DEC_TRY(hipMalloc((void**)&d->d_meta, cap), "hipMalloc(batch tables)");
+            DEC_TRY(hipHostMalloc((void**)&d->h_meta, cap, 0), "hipHostMalloc(batch tables)");
+            d->meta_cap = cap;
+        }
+        {
+            uint8_t* h = d->h_meta;
+            auto* byte_off = reinterpret_cast<unsigned long long*>(h + o_byte);
+            auto* frame_off = reinterpret_cast<unsigned long long*>(h + o_frame);
+            auto* unit_off = reinterpret_cast<unsigned long long*>(h + o_unit);
+            auto* blk_item = reinterpret_cast<uint32_t*>(h + o_bitem);
+            byte_off[0] = frame_off[0] = unit_off[0] = 0;
+            for (uint32_t j = 0; j < m; ++j) {
+                const BatchIn& x = in[dev[j]];
+                DecodeBatchItem& y = it[j];
+                const bool v2 = y.version == 2;
+                const uint64_t entry = v2 ? 4u : 8u;
+                for (uint32_t b = 0; b < y.blocks; ++b) {
+                    const uint32_t g = y.block0 + b;
+                    frame_off[g + 1] = frame_off[g] + be32(x.lac + 14 + entry * b);
+                    byte_off[g + 1] = v2 ? byte_off[g] : byte_off[g] + be32(x.lac + 18 + 8ull * b);
+                    blk_item[g] = j;
+                }
+                if (v2) {  // the version-2 item's bytes count in the byte offsets as one lump at its last block
+                    byte_off[y.block0 + y.blocks] = y.pay_off + (y.pay_bits >> 3);
+                }
+                unit_off[j + 1] = unit_off[j] + (y.frames + 3u) / 4u;
+                if (wav) {
+                    y.left = d->d_left + pcm_at[j];
+                    y.right = y.channels == 2 ? d->d_right + pcm_at[j] : nullptr;
+                    y.wav = d->d_wav + wav_at[j];
+                }
+            }
+            std::memcpy(h + o_items, it.data(), sizeof(DecodeBatchItem) * m);
+            if (!lane_blk.empty()) std::memcpy(h + o_lane, lane_blk.data(), 4 * lane_blk.size());
+            if (!v2_items.empty()) std::memcpy(h + o_v2, v2_items.data(), 4 * v2_items.size());
+        }
+        {
+            hipStream_t st = wav ? d->stream : stream;
+            DEC_TRY(hipMemcpyAsync(d->d_meta, d->h_meta, meta, hipMemcpyHostToDevice, st), "H2D batch tables");
+            for (uint32_t j = 0; j < m; ++j) {
+                const BatchIn& x = in[dev[j]];
+                const uint64_t head = 14 + (it[j].version == 2 ? 4ull : 8ull) * it[j].blocks;
+                DEC_TRY(hipMemcpyAsync(d->d_pay + it[j].pay_off, x.lac + head, x.size - head, hipMemcpyHostToDevice, st), "H2D payload");
+            }
+            DEC_TRY(hipMemsetAsync(d->d_pay + total_pay, 0, kDecodeTailPad, st), "memset");  // the bit reader's look-ahead
+            DecodeBatchArgs a;
+            uint8_t* dm = d->d_meta;
+            a.nitems = m;
+            a.total_blocks = T;
+            a.items = reinterpret_cast<const DecodeBatchItem*>(dm + o_items);
+            a.blk_item = reinterpret_cast<const uint32_t*>(dm + o_bitem);
+            a.lanes = (uint32_t)lane_blk.size();
+            a.lane_blk = reinterpret_cast<const uint32_t*>(dm + o_lane);
+            a.nv2 = (uint32_t)v2_items.size();
+            a.v2_items = reinterpret_cast<const uint32_t*>(dm + o_v2);
+            a.payload = d->d_pay;
+            a.byte_off = reinterpret_cast<const unsigned long long*>(dm + o_byte);
+            a.frame_off = reinterpret_cast<const unsigned long long*>(dm + o_frame);
+            a.status = d->d_status;
+            a.ms_flag = d->d_ms;
+            a.wav = wav;
+            a.unit_off = reinterpret_cast<const unsigned long long*>(dm + o_unit);
+            a.total_units = total_units;
+            DEC_TRY(hipEventRecord(d->e0, st), "event record");
+            DEC_TRY(launch_decode_batch(a, st), "decode launch");
+            DEC_TRY(hipEventRecord(d->e1, st), "event record");
+            DEC_TRY(hipMemcpyAsync(d->h_status, d->d_status, (size_t)T * sizeof(uint32_t), hipMemcpyDeviceToHost, st), "D2H status");
+            // the images of the items that decoded are valid whatever the others did: one copy for all
+            if (wav) DEC_TRY(hipMemcpyAsync(d->h_wav, d->d_wav, image_total, hipMemcpyDeviceToHost, st), "D2H WAV images");
+            DEC_TRY(hipStreamSynchronize(st), "synchronize");
+            if (device_ms) (void)hipEventElapsedTime(device_ms, d->e0, d->e1);
+        }
+        for (uint32_t j = 0; j < m; ++j) {
+            const uint32_t i = dev[j];
+            for (uint32_t b = 0; b < it[j].blocks; ++b) {
+                const uint32_t sv = d->h_status[it[j].block0 + b];
+                if (sv) {  // the item's first failing block, the message its own decode gives
+                    code[i] = LACX_E_RUNTIME;
+                    d->item_err[i] = "[decode-error] block=" + std::to_string(b) + " " + block_error(sv);
+                    break;
+                }
+            }
+            if (wav && code[i] == LACX_OK) {
+                uint8_t* img = d->h_wav + wav_at[j];
+                (void)wav_header(info[i], img);
+                if (out) out[i] = lacx_span{img, image_size[j]};
+            }
+        }
+#undef DEC_TRY
+    }
+done:
+    if (prev_device >= 0) (void)hipSetDevice(prev_device);
+    if (rc != LACX_OK) {  // the whole call failed: no item decoded
+        for (uint32_t i = 0; i < n; ++i) {
+            if (code[i] != LACX_OK) continue;
+            code[i] = rc;
+            d->item_err[i] = g_decode_err;
+            if (out) out[i] = lacx_span{nullptr, 0};
+        }
+    }
+    if (item_rc)
+        for (uint32_t i = 0; i < n; ++i) item_rc[i] = code[i];
+    if (rc != LACX_OK) return rc;
+    for (uint32_t i = 0; i < n; ++i)
+        if (code[i] != LACX_OK) return decode_fail(code[i], "stream " + std::to_string(i) + ": " + d->item_err[i]);
+    return LACX_OK;
+}
 }  // namespace
 
 int lacx_decoder_decode(lacx_decoder* d, const uint8_t* lac, uint64_t size, int32_t* left, int32_t* right, uint64_t frames,
@@ -337,6 +611,50 @@ int lacx_decoder_decode_wav(lacx_decoder* d, const uint8_t* lac, uint64_t size, 
     *out = buf;
     *out_size = n;
     return LACX_OK;
+}
+
+int lacx_decoder_decode_wav_batch_view(lacx_decoder* d, const lacx_span* lacs, uint32_t n, lacx_span* out, int* item_rc,
+                                       float* device_ms) {
+    if (!d) return decode_fail(LACX_E_INVALID, "null decoder");
+    if (!lacs || !out || n == 0) return decode_fail(LACX_E_INVALID, "null argument or empty batch");
+    std::vector<BatchIn> in(n);
+    for (uint32_t i = 0; i < n; ++i) in[i] = BatchIn{lacs[i].data, lacs[i].size, nullptr, nullptr, 0};
+    return decode_batch_run(d, in.data(), n, true, nullptr, out, item_rc, device_ms);
+}
+
+int lacx_decoder_decode_wav_batch(lacx_decoder* d, const lacx_span* lacs, uint32_t n, lacx_span* out, int* item_rc,
+                                  float* device_ms) {
+    const int rc = lacx_decoder_decode_wav_batch_view(d, lacs, n, out, item_rc, device_ms);
+    if (!out || !lacs || n == 0 || !d) return rc;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (!out[i].data) continue;
+        uint8_t* buf = static_cast<uint8_t*>(std::malloc(out[i].size));
+        if (!buf) {
+            for (uint32_t k = 0; k < i; ++k) {
+                std::free(const_cast<uint8_t*>(out[k].data));
+                out[k] = lacx_span{nullptr, 0};
+            }
+            for (uint32_t k = i; k < n; ++k) out[k] = lacx_span{nullptr, 0};
+            return decode_fail(LACX_E_RUNTIME, "out of host memory");
+        }
+        std::memcpy(buf, out[i].data, out[i].size);
+        out[i].data = buf;
+    }
+    return rc;
+}
+
+int lacx_decoder_decode_batch_device(lacx_decoder* d, const lacx_decode_item* items, uint32_t n, void* stream, int* item_rc,
+                                     float* device_ms) {
+    if (!d) return decode_fail(LACX_E_INVALID, "null decoder");
+    if (!items || n == 0) return decode_fail(LACX_E_INVALID, "null argument or empty batch");
+    std::vector<BatchIn> in(n);
+    for (uint32_t i = 0; i < n; ++i) in[i] = BatchIn{items[i].lac, items[i].size, items[i].left, items[i].right, items[i].frames};
+    return decode_batch_run(d, in.data(), n, false, static_cast<hipStream_t>(stream), nullptr, item_rc, device_ms);
+}
+
+const char* lacx_decoder_item_error(const lacx_decoder* d, uint32_t i) {
+    if (!d || i >= d->item_err.size()) return "";
+    return d->item_err[i].c_str();
 }
 
 int lacx_decode(int device, const uint8_t* lac, uint64_t size, int32_t* left, int32_t* right, uint64_t frames,

@@ -13,6 +13,8 @@
 //                                                                        (ref src/codec/lac/decoder.cpp:48-65,30-46)
 //   k_wav_pack    the same per-sample work as k_ms_inverse, written as the data region of a canonical WAV image
 //                 (interleaved little-endian 16 / 24-bit, ref src/main.cpp:150-182) instead of back into left/right
+//   k_decode_batch, k_decode_serial_batch, k_ms_inverse_batch, k_wav_pack_batch
+//                 the same for many streams as one job: every block of every item in one launch
 // The adaptive Rice parameter uses the encoder's division-free formulation (kmean / biased_k of analyze_core.h, proven
 // against Rice::adapt_k there); it assumes zigzag residuals below 2^30 like the encoder does, and a stream with a larger
 // one is refused (status 9) rather than decoded differently from the reference.
@@ -44,6 +46,13 @@ struct DecMem {
     __device__ __forceinline__ int16_t& coef(uint32_t slot, int lane) { return coef_[slot * cols + (uint32_t)lane]; }
 };
 constexpr size_t kDecBytesPerCol = 256 * 4 + 32 * 4 + 32 * 2;
+
+// A pointer read from memory (an item descriptor) is generic to the compiler, and its loads and stores would be flat
+// ones; these all point into global memory, and the round trip through the global address space says so.
+template <typename T>
+__device__ __forceinline__ T* global_ptr(T* p) {
+    return (T*)(__attribute__((address_space(1))) T*)(uintptr_t)p;
+}
 
 // MSB-first bit reader over a byte stream in global memory (ref src/codec/bitstream/bit_reader.hpp).  A lane's stream is
 // latency-bound -- every token's position depends on the one before -- so the reader keeps the next bits in a 64-bit
@@ -401,6 +410,64 @@ __device__ uint32_t decode_channel_block(BitIn& r, uint32_t n, int32_t* __restri
 
 }  // namespace
 
+// One block of a version-3 stream by one lane (k_decode, k_decode_batch): blk indexes the global tables; the block's
+// samples go to left / right at frame_off[blk] - frame_base (the first frame of the stream those arrays hold).
+__device__ __forceinline__ void decode_block_lane(uint32_t blk, int channels, int stereo_mode, const uint8_t* __restrict__ payload,
+                                                  const unsigned long long* __restrict__ byte_off,
+                                                  const unsigned long long* __restrict__ frame_off, unsigned long long frame_base,
+                                                  int32_t* __restrict__ left, int32_t* __restrict__ right,
+                                                  uint32_t* __restrict__ status, uint8_t* __restrict__ ms_flag, DecMem& dm, int lane) {
+    const uint32_t n = (uint32_t)(frame_off[blk + 1] - frame_off[blk]);
+    const unsigned long long f0 = frame_off[blk] - frame_base;
+    BitIn r;
+    reader_init(r, payload + byte_off[blk], (uint32_t)(8ull * (byte_off[blk + 1] - byte_off[blk])));
+    uint32_t st = 0;
+    uint32_t ms = stereo_mode == 1 ? 1u : 0u;
+    if (n == 0u || n > (uint32_t)kMaxBlock) st = 1;
+    if (!st && channels == 2 && stereo_mode == 2) {  // per-block flag byte (ref lac/decoder.cpp)
+        const uint32_t flag = get_bits(r, 8);
+        if (overrun(r) || flag > 1u) st = 1;
+        ms = flag;
+    }
+    if (!st) st = decode_channel_block(r, n, left + f0, dm, lane);
+    if (!st && channels == 2) st = decode_channel_block(r, n, right + f0, dm, lane);
+    if (!st && r.pos != r.nbits) st = 6;  // trailing bytes in the block
+    status[blk] = st;
+    ms_flag[blk] = (uint8_t)ms;
+}
+
+// Blocks [0, num_blocks) of one stream by one lane each, in order (version 2: no compressed sizes, so the lane walks the
+// stream); frame_off / status / ms_flag are the stream's own, frame_base the global frame offset of its first block.
+// status[] is set for the blocks up to and including the first that fails, the rest get 8 (not reached).
+__device__ __forceinline__ void decode_serial_lane(uint32_t num_blocks, int channels, int stereo_mode,
+                                                   const uint8_t* __restrict__ payload, uint32_t payload_bits,
+                                                   const unsigned long long* __restrict__ frame_off, unsigned long long frame_base,
+                                                   int32_t* __restrict__ left, int32_t* __restrict__ right,
+                                                   uint32_t* __restrict__ status, uint8_t* __restrict__ ms_flag, DecMem& dm, int lane) {
+    BitIn r;
+    reader_init(r, payload, payload_bits);
+    for (uint32_t blk = 0; blk < num_blocks; ++blk) {
+        const uint32_t n = (uint32_t)(frame_off[blk + 1] - frame_off[blk]);
+        const unsigned long long f0 = frame_off[blk] - frame_base;
+        uint32_t st = 0, ms = stereo_mode == 1 ? 1u : 0u;
+        if (n == 0u || n > (uint32_t)kMaxBlock) st = 1;
+        if (!st && channels == 2 && stereo_mode == 2) {
+            const uint32_t flag = get_bits(r, 8);
+            if (overrun(r) || flag > 1u) st = 1;
+            ms = flag;
+        }
+        if (!st) st = decode_channel_block(r, n, left + f0, dm, lane);
+        if (!st && channels == 2) st = decode_channel_block(r, n, right + f0, dm, lane);
+        if (!st && blk + 1u == num_blocks && r.pos != r.nbits) st = 6;  // trailing frame payload
+        status[blk] = st;
+        ms_flag[blk] = (uint8_t)ms;
+        if (st) {
+            for (uint32_t b = blk + 1u; b < num_blocks; ++b) status[b] = 8;  // not reached
+            break;
+        }
+    }
+}
+
 // lanes_per_wave (a power of two, 1..64): how many blocks one wave decodes -- fewer blocks per wave mean more waves to
 // interleave on a SIMD while the stream has few enough blocks that the idle lanes do not matter (the launcher picks).
 __global__ __launch_bounds__(kDecThreads) void k_decode(uint32_t num_blocks, int channels, int stereo_mode,
@@ -420,22 +487,33 @@ __global__ __launch_bounds__(kDecThreads) void k_decode(uint32_t num_blocks, int
     if ((uint32_t)lane >= lanes_per_wave) return;
     const uint32_t blk = blockIdx.x * lanes_per_wave + threadIdx.x;
     if (blk >= num_blocks) return;
-    const uint32_t n = (uint32_t)(frame_off[blk + 1] - frame_off[blk]);
-    BitIn r;
-    reader_init(r, payload + byte_off[blk], (uint32_t)(8ull * (byte_off[blk + 1] - byte_off[blk])));
-    uint32_t st = 0;
-    uint32_t ms = stereo_mode == 1 ? 1u : 0u;
-    if (n == 0u || n > (uint32_t)kMaxBlock) st = 1;
-    if (!st && channels == 2 && stereo_mode == 2) {  // per-block flag byte (ref lac/decoder.cpp)
-        const uint32_t flag = get_bits(r, 8);
-        if (overrun(r) || flag > 1u) st = 1;
-        ms = flag;
-    }
-    if (!st) st = decode_channel_block(r, n, left + frame_off[blk], dm, lane);
-    if (!st && channels == 2) st = decode_channel_block(r, n, right + frame_off[blk], dm, lane);
-    if (!st && r.pos != r.nbits) st = 6;  // trailing bytes in the block
-    status[blk] = st;
-    ms_flag[blk] = (uint8_t)ms;
+    decode_block_lane(blk, channels, stereo_mode, payload, byte_off, frame_off, 0ull, left, right, status, ms_flag, dm, lane);
+}
+
+// Many streams as one launch: lane g decodes block lane_blk[g] of the global tables (~0u: an idle lane), whatever item
+// it belongs to (blk_item); the item's descriptor gives what k_decode takes as arguments.  The host lays the lanes out
+// so that an item's blocks sit in consecutive lanes (see launch_decode_batch).  64 LDS columns per wave.
+__global__ __launch_bounds__(kDecThreads) void k_decode_batch(uint32_t lanes, const uint32_t* __restrict__ lane_blk,
+                                                              const uint32_t* __restrict__ blk_item,
+                                                              const DecodeBatchItem* __restrict__ items,
+                                                              const uint8_t* __restrict__ payload,
+                                                              const unsigned long long* __restrict__ byte_off,
+                                                              const unsigned long long* __restrict__ frame_off,
+                                                              uint32_t* __restrict__ status, uint8_t* __restrict__ ms_flag) {
+    extern __shared__ __align__(16) unsigned char dec_raw[];
+    DecMem dm;
+    dm.cols = kDecThreads;
+    dm.ring_ = reinterpret_cast<uint32_t*>(dec_raw);
+    dm.hist_ = reinterpret_cast<int32_t*>(dec_raw + (size_t)256 * 4 * kDecThreads);
+    dm.coef_ = reinterpret_cast<int16_t*>(dec_raw + (size_t)(256 + 32) * 4 * kDecThreads);
+    const int lane = (int)threadIdx.x;
+    const uint32_t g = blockIdx.x * kDecThreads + threadIdx.x;
+    if (g >= lanes) return;
+    const uint32_t blk = lane_blk[g];
+    if (blk == ~0u) return;
+    const DecodeBatchItem& it = items[blk_item[blk]];
+    decode_block_lane(blk, it.channels, it.stereo_mode, payload, byte_off, frame_off, it.frame0, global_ptr(it.left),
+                      global_ptr(it.right), status, ms_flag, dm, lane);
 }
 
 // The legacy version-2 container carries no compressed block sizes (ref lac/decoder.cpp:209-219): block i starts where
@@ -453,38 +531,35 @@ __global__ __launch_bounds__(kDecThreads) void k_decode_serial(uint32_t num_bloc
     dm.ring_ = reinterpret_cast<uint32_t*>(dec_raw);
     dm.hist_ = reinterpret_cast<int32_t*>(dec_raw + 256 * 4);
     dm.coef_ = reinterpret_cast<int16_t*>(dec_raw + (256 + 32) * 4);
-    BitIn r;
-    reader_init(r, payload, payload_bits);
-    for (uint32_t blk = 0; blk < num_blocks; ++blk) {
-        const uint32_t n = (uint32_t)(frame_off[blk + 1] - frame_off[blk]);
-        uint32_t st = 0, ms = stereo_mode == 1 ? 1u : 0u;
-        if (n == 0u || n > (uint32_t)kMaxBlock) st = 1;
-        if (!st && channels == 2 && stereo_mode == 2) {
-            const uint32_t flag = get_bits(r, 8);
-            if (overrun(r) || flag > 1u) st = 1;
-            ms = flag;
-        }
-        if (!st) st = decode_channel_block(r, n, left + frame_off[blk], dm, 0);
-        if (!st && channels == 2) st = decode_channel_block(r, n, right + frame_off[blk], dm, 0);
-        if (!st && blk + 1u == num_blocks && r.pos != r.nbits) st = 6;  // trailing frame payload
-        status[blk] = st;
-        ms_flag[blk] = (uint8_t)ms;
-        if (st) {
-            for (uint32_t b = blk + 1u; b < num_blocks; ++b) status[b] = 8;  // not reached
-            break;
-        }
-    }
+    decode_serial_lane(num_blocks, channels, stereo_mode, payload, payload_bits, frame_off, 0ull, left, right, status, ms_flag,
+                       dm, 0);
 }
 
-// grid = (blocks, tiles): the samples of block blockIdx.x in tiles of 1024
-__global__ __launch_bounds__(256) void k_ms_inverse(int channels, int bit_depth,
-                                                    const unsigned long long* __restrict__ frame_off,
-                                                    int32_t* __restrict__ left, int32_t* __restrict__ right,
-                                                    const uint8_t* __restrict__ ms_flag, uint32_t* __restrict__ status) {
-    const uint32_t blk = blockIdx.x, tile = blockIdx.y;
-    if (status[blk]) return;  // (uniform) the block did not decode
-    const unsigned long long f0 = frame_off[blk];
-    const uint32_t n = (uint32_t)(frame_off[blk + 1] - f0);
+// The version-2 items of a batch: one lane per item (v2_items: their indices), each walking its stream like
+// k_decode_serial.  Launched only when the batch has such items.
+__global__ __launch_bounds__(kDecThreads) void k_decode_serial_batch(uint32_t nv2, const uint32_t* __restrict__ v2_items,
+                                                                     const DecodeBatchItem* __restrict__ items,
+                                                                     const uint8_t* __restrict__ payload,
+                                                                     const unsigned long long* __restrict__ frame_off,
+                                                                     uint32_t* __restrict__ status, uint8_t* __restrict__ ms_flag) {
+    extern __shared__ __align__(16) unsigned char dec_raw[];
+    DecMem dm;
+    dm.cols = kDecThreads;
+    dm.ring_ = reinterpret_cast<uint32_t*>(dec_raw);
+    dm.hist_ = reinterpret_cast<int32_t*>(dec_raw + (size_t)256 * 4 * kDecThreads);
+    dm.coef_ = reinterpret_cast<int16_t*>(dec_raw + (size_t)(256 + 32) * 4 * kDecThreads);
+    const uint32_t g = blockIdx.x * kDecThreads + threadIdx.x;
+    if (g >= nv2) return;
+    const DecodeBatchItem& it = items[v2_items[g]];
+    decode_serial_lane(it.blocks, it.channels, it.stereo_mode, payload + it.pay_off, it.pay_bits, frame_off + it.block0, it.frame0,
+                       global_ptr(it.left), global_ptr(it.right), status + it.block0, ms_flag + it.block0, dm, (int)threadIdx.x);
+}
+
+// One tile of 1024 samples of one block: the mid/side inverse in place where the block's flag says so, and the
+// bit-depth range check (k_ms_inverse, k_ms_inverse_batch).  f0: the block's first frame in left / right.
+__device__ __forceinline__ void ms_inverse_tile(uint32_t blk, uint32_t tile, int channels, int bit_depth, unsigned long long f0,
+                                                uint32_t n, int32_t* __restrict__ left, int32_t* __restrict__ right,
+                                                const uint8_t* __restrict__ ms_flag, uint32_t* __restrict__ status) {
     const bool ms = channels == 2 && ms_flag[blk] != 0;
     const long long lo = bit_depth == 16 ? -32768 : -0x800000, hi = bit_depth == 16 ? 32767 : 0x7FFFFF;
     bool bad = false;
@@ -502,6 +577,32 @@ __global__ __launch_bounds__(256) void k_ms_inverse(int channels, int bit_depth,
     if (bad) atomicMax(&status[blk], 7u);
 }
 
+// grid = (blocks, tiles): the samples of block blockIdx.x in tiles of 1024
+__global__ __launch_bounds__(256) void k_ms_inverse(int channels, int bit_depth,
+                                                    const unsigned long long* __restrict__ frame_off,
+                                                    int32_t* __restrict__ left, int32_t* __restrict__ right,
+                                                    const uint8_t* __restrict__ ms_flag, uint32_t* __restrict__ status) {
+    const uint32_t blk = blockIdx.x, tile = blockIdx.y;
+    if (status[blk]) return;  // (uniform) the block did not decode
+    const unsigned long long f0 = frame_off[blk];
+    const uint32_t n = (uint32_t)(frame_off[blk + 1] - f0);
+    ms_inverse_tile(blk, tile, channels, bit_depth, f0, n, left, right, ms_flag, status);
+}
+
+// The same over every block of every item of a batch (grid = (all blocks, tiles)), into each item's own arrays.
+__global__ __launch_bounds__(256) void k_ms_inverse_batch(const uint32_t* __restrict__ blk_item,
+                                                          const DecodeBatchItem* __restrict__ items,
+                                                          const unsigned long long* __restrict__ frame_off,
+                                                          const uint8_t* __restrict__ ms_flag, uint32_t* __restrict__ status) {
+    const uint32_t blk = blockIdx.x, tile = blockIdx.y;
+    if (status[blk]) return;  // (uniform) the block did not decode
+    const DecodeBatchItem& it = items[blk_item[blk]];
+    const unsigned long long f0 = frame_off[blk];
+    const uint32_t n = (uint32_t)(frame_off[blk + 1] - f0);
+    ms_inverse_tile(blk, tile, it.channels, it.bit_depth, f0 - it.frame0, n, global_ptr(it.left), global_ptr(it.right), ms_flag,
+                    status);
+}
+
 static void launch_ms_inverse(uint32_t num_blocks, int channels, int bit_depth, const unsigned long long* frame_off,
                               int32_t* left, int32_t* right, const uint8_t* ms_flag, uint32_t* status, hipStream_t stream) {
     hipLaunchKernelGGL(k_ms_inverse, dim3(num_blocks, kMaxBlock / 1024), dim3(256), 0, stream, channels, bit_depth, frame_off,
@@ -510,15 +611,16 @@ static void launch_ms_inverse(uint32_t num_blocks, int channels, int bit_depth, 
 
 // The block that holds frame f: the regular layout (every block but the last 16384 frames) is a guess that one
 // comparison confirms; any other table (non-final blocks may be any length from 256 frames on) is searched.
+// frame_off: the stream's own num_blocks + 1 entries, frame_base the value of its first (f counts from there).
 __device__ __forceinline__ uint32_t block_of_frame(const unsigned long long* __restrict__ frame_off, uint32_t num_blocks,
-                                                   unsigned long long f) {
+                                                   unsigned long long frame_base, unsigned long long f) {
     uint32_t g = (uint32_t)(f / (unsigned long long)kMaxBlock);
     if (g >= num_blocks) g = num_blocks - 1u;
-    if (frame_off[g] <= f && f < frame_off[g + 1]) return g;
+    if (frame_off[g] - frame_base <= f && f < frame_off[g + 1] - frame_base) return g;
     uint32_t lo = 0, hi = num_blocks;  // frame_off[lo] <= f < frame_off[hi]
     while (hi - lo > 1u) {
         const uint32_t mid = lo + (hi - lo) / 2u;
-        if (frame_off[mid] <= f) lo = mid;
+        if (frame_off[mid] - frame_base <= f) lo = mid;
         else hi = mid;
     }
     return lo;
@@ -537,14 +639,14 @@ __device__ __forceinline__ void pack24(int32_t a, int32_t b, int32_t c, int32_t 
 // samples arrive as one 16-byte load per channel.  Block boundaries may fall anywhere (non-final blocks of any length
 // from 256 frames on, odd ones included), so the block -- MS flag and status -- is looked up per frame; a unit spans at
 // most two blocks.  The last unit is written byte by byte and writes the RIFF pad byte when the data size is odd.
-// wav_data: the image's first byte (the 44-byte header is the host's).
-__global__ __launch_bounds__(256) void k_wav_pack(uint32_t num_blocks, int channels, int bit_depth, unsigned long long frames,
-                                                  const unsigned long long* __restrict__ frame_off,
-                                                  const int32_t* __restrict__ left, const int32_t* __restrict__ right,
-                                                  const uint8_t* __restrict__ ms_flag, uint32_t* __restrict__ status,
-                                                  uint8_t* __restrict__ wav_data) {
-    const unsigned long long f0 = 4ull * ((unsigned long long)blockIdx.x * 256u + threadIdx.x);
-    if (f0 >= frames) return;
+// wav_data: the image's first byte (the 44-byte header is the host's).  wav_pack_unit is one thread's work (k_wav_pack,
+// k_wav_pack_batch): frame_off, ms_flag and status are the stream's own (num_blocks entries from its first block),
+// frame_base the value of frame_off[0].
+__device__ __forceinline__ void wav_pack_unit(unsigned long long f0, uint32_t num_blocks, int channels, int bit_depth,
+                                              unsigned long long frames, const unsigned long long* __restrict__ frame_off,
+                                              unsigned long long frame_base, const int32_t* __restrict__ left,
+                                              const int32_t* __restrict__ right, const uint8_t* __restrict__ ms_flag,
+                                              uint32_t* __restrict__ status, uint8_t* __restrict__ wav_data) {
     const uint32_t nf = frames - f0 >= 4u ? 4u : (uint32_t)(frames - f0);
     const bool stereo = channels == 2;
     int32_t l[4] = {0, 0, 0, 0}, r[4] = {0, 0, 0, 0};
@@ -564,8 +666,8 @@ __global__ __launch_bounds__(256) void k_wav_pack(uint32_t num_blocks, int chann
             }
         }
     }
-    const uint32_t b0 = block_of_frame(frame_off, num_blocks, f0);
-    const unsigned long long split = frame_off[b0 + 1];  // frames from here on belong to block b0 + 1
+    const uint32_t b0 = block_of_frame(frame_off, num_blocks, frame_base, f0);
+    const unsigned long long split = frame_off[b0 + 1] - frame_base;  // frames from here on belong to block b0 + 1
     const uint32_t b1 = f0 + nf > split ? b0 + 1u : b0;
     const uint32_t st0 = status[b0], st1 = status[b1];
     const bool ms0 = stereo && ms_flag[b0] != 0, ms1 = stereo && ms_flag[b1] != 0;
@@ -625,6 +727,52 @@ __global__ __launch_bounds__(256) void k_wav_pack(uint32_t num_blocks, int chann
     if (f0 + nf == frames && ((frames * align) & 1ull)) dst[nf * align] = 0;  // RIFF pad byte
 }
 
+__global__ __launch_bounds__(256) void k_wav_pack(uint32_t num_blocks, int channels, int bit_depth, unsigned long long frames,
+                                                  const unsigned long long* __restrict__ frame_off,
+                                                  const int32_t* __restrict__ left, const int32_t* __restrict__ right,
+                                                  const uint8_t* __restrict__ ms_flag, uint32_t* __restrict__ status,
+                                                  uint8_t* __restrict__ wav_data) {
+    const unsigned long long f0 = 4ull * ((unsigned long long)blockIdx.x * 256u + threadIdx.x);
+    if (f0 >= frames) return;
+    wav_pack_unit(f0, num_blocks, channels, bit_depth, frames, frame_off, 0ull, left, right, ms_flag, status, wav_data);
+}
+
+// k_wav_pack over every item of a batch in one launch: thread u handles unit u of the concatenated unit ranges
+// (unit_off: [nitems + 1] prefix sums of the items' ceil(frames / 4)), found by a binary search there.  Each item's PCM
+// starts at a multiple of 4 frames and its image at a 16-byte boundary, so every unit keeps k_wav_pack's aligned 16-byte
+// loads and dword stores.  The search runs once per workgroup, on its first unit (uniform: scalar loads, and the item's
+// descriptor in scalar registers); only a workgroup that spans items searches again per thread, among the later items.
+__global__ __launch_bounds__(256) void k_wav_pack_batch(uint32_t nitems, unsigned long long total_units,
+                                                        const unsigned long long* __restrict__ unit_off,
+                                                        const DecodeBatchItem* __restrict__ items,
+                                                        const unsigned long long* __restrict__ frame_off,
+                                                        const uint8_t* __restrict__ ms_flag, uint32_t* __restrict__ status) {
+    const unsigned long long first = (unsigned long long)blockIdx.x * 256u;
+    uint32_t lo = 0, hi = nitems;  // unit_off[lo] <= first < unit_off[hi]
+    while (hi - lo > 1u) {
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        if (unit_off[mid] <= first) lo = mid;
+        else hi = mid;
+    }
+    const unsigned long long u = first + threadIdx.x;
+    if (u >= total_units) return;
+    if (unit_off[lo + 1] >= first + 256u) {  // (uniform) the whole workgroup lies in item lo
+        const DecodeBatchItem& it = items[lo];
+        wav_pack_unit(4ull * (u - unit_off[lo]), it.blocks, it.channels, it.bit_depth, it.frames, frame_off + it.block0, it.frame0,
+                      global_ptr(it.left), global_ptr(it.right), ms_flag + it.block0, status + it.block0, global_ptr(it.wav));
+        return;
+    }
+    uint32_t l2 = lo, h2 = nitems;  // unit_off[l2] <= u < unit_off[h2]
+    while (h2 - l2 > 1u) {
+        const uint32_t mid = l2 + (h2 - l2) / 2u;
+        if (unit_off[mid] <= u) l2 = mid;
+        else h2 = mid;
+    }
+    const DecodeBatchItem& it = items[l2];
+    wav_pack_unit(4ull * (u - unit_off[l2]), it.blocks, it.channels, it.bit_depth, it.frames, frame_off + it.block0, it.frame0,
+                  global_ptr(it.left), global_ptr(it.right), ms_flag + it.block0, status + it.block0, global_ptr(it.wav));
+}
+
 static void launch_wav_pack(uint32_t num_blocks, int channels, int bit_depth, unsigned long long frames,
                             const unsigned long long* frame_off, const int32_t* left, const int32_t* right,
                             const uint8_t* ms_flag, uint32_t* status, uint8_t* wav_data, hipStream_t stream) {
@@ -674,6 +822,33 @@ hipError_t launch_decode_serial(uint32_t num_blocks, int channels, int stereo_mo
     hipLaunchKernelGGL(k_decode_serial, dim3(1), dim3(kDecThreads), kDecBytesPerCol, stream, num_blocks, channels, stereo_mode,
                        payload, payload_bits, frame_off, left, right, status, ms_flag);
     launch_post_decode(num_blocks, channels, bit_depth, frame_off, left, right, ms_flag, status, wav_data, frames, stream);
+    return hipGetLastError();
+}
+
+hipError_t launch_decode_batch(const DecodeBatchArgs& a, hipStream_t stream) {
+    const size_t smem = kDecBytesPerCol * kDecThreads;
+    if (a.lanes) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decode_batch),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_decode_batch, dim3((a.lanes + kDecThreads - 1) / kDecThreads), dim3(kDecThreads), smem, stream,
+                           a.lanes, a.lane_blk, a.blk_item, a.items, a.payload, a.byte_off, a.frame_off, a.status, a.ms_flag);
+    }
+    if (a.nv2) {  // version-2 items: a batch without any pays nothing for them
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decode_serial_batch),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_decode_serial_batch, dim3((a.nv2 + kDecThreads - 1) / kDecThreads), dim3(kDecThreads), smem,
+                           stream, a.nv2, a.v2_items, a.items, a.payload, a.frame_off, a.status, a.ms_flag);
+    }
+    if (a.wav) {
+        if (a.total_units)
+            hipLaunchKernelGGL(k_wav_pack_batch, dim3((uint32_t)((a.total_units + 255u) / 256u)), dim3(256), 0, stream, a.nitems,
+                               a.total_units, a.unit_off, a.items, a.frame_off, a.ms_flag, a.status);
+    } else if (a.total_blocks) {
+        hipLaunchKernelGGL(k_ms_inverse_batch, dim3(a.total_blocks, kMaxBlock / 1024), dim3(256), 0, stream, a.blk_item, a.items,
+                           a.frame_off, a.ms_flag, a.status);
+    }
     return hipGetLastError();
 }
 

@@ -192,6 +192,41 @@ hipError_t launch_decode_serial(uint32_t num_blocks, int channels, int stereo_mo
                                 uint32_t* status, uint8_t* ms_flag, hipStream_t stream, uint8_t* wav_data = nullptr,
                                 unsigned long long frames = 0);
 
+// Many streams as one decode (launch_decode_batch).  The blocks of all items are numbered globally: byte_off / frame_off are
+// [total_blocks + 1] prefix sums over the concatenated payloads and frames, status / ms_flag per global block.
+struct DecodeBatchItem {
+    int32_t* left;                // the item's PCM from its frame 0 (16-byte aligned in the WAV form)
+    int32_t* right;               // null for mono
+    uint8_t* wav;                 // WAV form: the item's image (16-byte aligned; header is the host's), else null
+    unsigned long long frame0;    // frame_off of the item's first block
+    unsigned long long frames;
+    unsigned long long pay_off;   // byte offset of the item's payload (where a version-2 item's lane starts)
+    uint32_t block0, blocks;      // the item's global blocks
+    uint32_t pay_bits;            // version 2 only: payload bits
+    uint8_t channels, stereo_mode, bit_depth, version;
+};
+struct DecodeBatchArgs {
+    uint32_t nitems = 0, total_blocks = 0;
+    const DecodeBatchItem* items = nullptr;
+    const uint32_t* blk_item = nullptr;       // [total_blocks] the item of every block
+    // k_decode_batch: lane g decodes block lane_blk[g] (~0u: idle); only version-3 blocks, an item's in consecutive lanes
+    uint32_t lanes = 0;
+    const uint32_t* lane_blk = nullptr;
+    uint32_t nv2 = 0;                         // version-2 items, one lane each (k_decode_serial_batch)
+    const uint32_t* v2_items = nullptr;
+    const uint8_t* payload = nullptr;         // followed by kDecodeTailPad zero bytes
+    const unsigned long long* byte_off = nullptr;
+    const unsigned long long* frame_off = nullptr;
+    uint32_t* status = nullptr;
+    uint8_t* ms_flag = nullptr;
+    // wav = false: k_ms_inverse_batch in place into every item's left / right; true: k_wav_pack_batch into the items'
+    // images (unit_off: [nitems + 1] prefix sums of ceil(frames / 4)), left / right then hold the pre-inverse samples
+    bool wav = false;
+    const unsigned long long* unit_off = nullptr;
+    unsigned long long total_units = 0;
+};
+hipError_t launch_decode_batch(const DecodeBatchArgs& args, hipStream_t stream);
+
 // Block::Encoder::encode's analysis for one block of arbitrary int32 samples (wide.hip): d_res = scratch for the eleven
 // candidate residuals ([11][kMaxBlock] int32), d_plan receives the plan.
 hipError_t launch_wide_block(const int32_t* d_x, uint32_t n, int zero_run, int partitioning, int32_t* d_res,

@@ -108,6 +108,8 @@ EXPORTS = (
     "lacx_get_fanout_stats", "lacx_get_lane_timing", "lacx_fanout_exchange_note",
     "lacx_decoder_create", "lacx_decoder_destroy", "lacx_decoder_decode", "lacx_sizeof",
     "lacx_decoder_decode_wav", "lacx_decoder_decode_wav_view",
+    "lacx_decoder_decode_wav_batch", "lacx_decoder_decode_wav_batch_view", "lacx_decoder_decode_batch_device",
+    "lacx_decoder_item_error",
 )
 
 
@@ -160,6 +162,13 @@ def lib():
         L.lacx_decoder_decode_wav.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), C.c_uint64, C.POINTER(C.POINTER(C.c_uint8)),
                                               C.POINTER(C.c_uint64), C.POINTER(C.c_float)]
         L.lacx_decoder_decode_wav_view.argtypes = L.lacx_decoder_decode_wav.argtypes
+        L.lacx_decoder_decode_wav_batch_view.argtypes = [C.c_void_p, C.POINTER(Span), C.c_uint32, C.POINTER(Span),
+                                                         C.POINTER(C.c_int), C.POINTER(C.c_float)]
+        L.lacx_decoder_decode_wav_batch.argtypes = L.lacx_decoder_decode_wav_batch_view.argtypes
+        L.lacx_decoder_decode_batch_device.argtypes = [C.c_void_p, C.POINTER(DecodeItem), C.c_uint32, C.c_void_p,
+                                                       C.POINTER(C.c_int), C.POINTER(C.c_float)]
+        L.lacx_decoder_item_error.restype = C.c_char_p
+        L.lacx_decoder_item_error.argtypes = [C.c_void_p, C.c_uint32]
         # the structs declared in this file against the library's own sizeof(): a layout that has drifted from
         # include/lacx.h would otherwise show up as memory corruption behind the first call that fills one
         L.lacx_sizeof.restype = C.c_uint32
@@ -177,7 +186,8 @@ def abi_structs() -> dict:
     """include/lacx.h struct name (without the prefix) -> the ctypes class that mirrors it."""
     return {"config": Config, "channel_plan": ChannelPlan, "block_plan": BlockPlan, "timing": Timing, "pcm": Pcm,
             "batch_item": BatchItem, "batch_out": BatchOut, "wav_info": WavInfo, "fanout_shard": FanoutShard,
-            "fanout_out": FanoutOut, "fanout_stats": FanoutStats, "stream_info": StreamInfo}
+            "fanout_out": FanoutOut, "fanout_stats": FanoutStats, "stream_info": StreamInfo, "span": Span,
+            "decode_item": DecodeItem}
 
 
 def device_count() -> int:
@@ -597,6 +607,25 @@ class StreamInfo(C.Structure):
                 ("bit_depth", C.c_uint8), ("stereo_mode", C.c_uint8), ("version", C.c_uint8)]
 
 
+class Span(C.Structure):
+    _fields_ = [("data", C.POINTER(C.c_uint8)), ("size", C.c_uint64)]
+
+
+class DecodeItem(C.Structure):
+    _fields_ = [("lac", C.POINTER(C.c_uint8)), ("size", C.c_uint64), ("left", C.c_void_p), ("right", C.c_void_p),
+                ("frames", C.c_uint64)]
+
+
+class BatchDecodeError(RuntimeError):
+    """Some items of a batch decode failed.  errors: {index: message} (each the message the item's own decode gives);
+    results: the call's results with None at the failed indices.  str(): the lowest failing item, "stream i: ..."."""
+
+    def __init__(self, message, errors, results):
+        super().__init__(message)
+        self.errors = errors
+        self.results = results
+
+
 def stream_parse(lac: bytes):
     """Header + block table of a .lac (ref src/codec/lac/decoder.cpp:90-200); None when inconsistent.  Host-only."""
     info = StreamInfo()
@@ -700,6 +729,81 @@ class Decoder:
         next call (copy it to keep it)."""
         out, size = self._decode_wav(lib().lacx_decoder_decode_wav_view, lac)
         return np.ctypeslib.as_array(out, shape=(size,))
+
+
+    def _batch(self, n, call):
+        """Runs call(item_rc, ms) for a batch of n; returns (rc, {index: message} of the failed items)."""
+        if self._h is None:
+            raise RuntimeError("decoder is closed")
+        rcs = (C.c_int * max(1, n))()
+        ms = C.c_float()
+        rc = call(rcs, C.byref(ms))
+        self.last_ms = float(ms.value)
+        if rc == E_INVALID and n == 0:
+            raise ValueError(lib().lacx_decode_last_error().decode(errors="replace"))
+        if rc == E_DEVICE:  # the whole call failed
+            raise RuntimeError(lib().lacx_decode_last_error().decode(errors="replace"))
+        errors = {i: lib().lacx_decoder_item_error(self._h, i).decode(errors="replace") for i in range(n) if rcs[i] != OK}
+        return rc, errors
+
+    def _wav_batch(self, fn, lacs):
+        bufs = [np.frombuffer(x, dtype=np.uint8) for x in lacs]
+        n = len(bufs)
+        spans = (Span * max(1, n))(*[Span(b.ctypes.data_as(C.POINTER(C.c_uint8)), b.size) for b in bufs])
+        outs = (Span * max(1, n))()
+        rc, errors = self._batch(n, lambda rcs, ms: fn(self._h, spans, C.c_uint32(n), outs, rcs, ms))
+        return rc, errors, outs
+
+    def _raise_batch(self, rc, errors, results):
+        if rc != OK:
+            raise BatchDecodeError(lib().lacx_decode_last_error().decode(errors="replace"), errors, results)
+        return results
+
+    def decode_wav_batch(self, lacs) -> list:
+        """Many .lac streams as one device job: the WAV image of each (what decode_wav gives for it alone), kernel
+        milliseconds of the batch in `last_ms`.  Failed items raise BatchDecodeError once the others are done."""
+        rc, errors, outs = self._wav_batch(lib().lacx_decoder_decode_wav_batch, lacs)
+        results = []
+        for i in range(len(lacs)):
+            o = outs[i]
+            if i in errors or not o.data:
+                results.append(None)
+                continue
+            try:
+                results.append(C.string_at(o.data, o.size))
+            finally:
+                lib().lacx_free(o.data)
+        return self._raise_batch(rc, errors, results)
+
+    def decode_wav_batch_view(self, lacs) -> list:
+        """Zero-copy form of decode_wav_batch: uint8 views of the decoder's pinned image buffer, valid until this
+        decoder's next call."""
+        rc, errors, outs = self._wav_batch(lib().lacx_decoder_decode_wav_batch_view, lacs)
+        results = [None if (i in errors or not outs[i].data) else np.ctypeslib.as_array(outs[i].data, shape=(outs[i].size,))
+                   for i in range(len(lacs))]
+        return self._raise_batch(rc, errors, results)
+
+    def decode_batch_device(self, lacs, outputs, stream: int = 0) -> list:
+        """Many .lac streams decoded into caller-owned device arrays: outputs[i] = (left_ptr, right_ptr or None), raw
+        device addresses of `frames` int32 each on the decoder's device (a torch tensor's data_ptr()); the work goes on
+        `stream` (a raw hipStream_t, 0 = the null stream).  Returns each item's StreamInfo (None where it failed);
+        failed items raise BatchDecodeError once the others are done."""
+        if len(outputs) != len(lacs):
+            raise ValueError("one output pair per stream")
+        bufs = [np.frombuffer(x, dtype=np.uint8) for x in lacs]
+        n = len(bufs)
+        infos = [stream_parse(x) for x in lacs]
+        items = (DecodeItem * max(1, n))()
+        for it, b, (lp, rp), inf in zip(items, bufs, outputs, infos):
+            it.lac = b.ctypes.data_as(C.POINTER(C.c_uint8))
+            it.size = b.size
+            it.left = lp
+            it.right = rp
+            it.frames = inf.frames if inf is not None else 0
+        rc, errors = self._batch(n, lambda rcs, ms: lib().lacx_decoder_decode_batch_device(
+            self._h, items, C.c_uint32(n), C.c_void_p(stream), rcs, ms))
+        results = [None if i in errors else infos[i] for i in range(n)]
+        return self._raise_batch(rc, errors, results)
 
 
 def decode_wav(lac, device: int = -1) -> bytes:
