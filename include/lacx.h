@@ -340,8 +340,8 @@ int lacx_decode(int device, const uint8_t* lac, uint64_t size, int32_t* left, in
                 float* device_ms);
 const char* lacx_decode_last_error(void); /* of the calling thread */
 /* The same through a decoder object (ref LAC::Decoder, src/codec/lac/decoder.hpp:10-24) whose device buffers, stream and
- * events live from call to call; lacx_decode keeps one such object per calling thread and device.  device = -1: the device
- * that is current at the first call. */
+ * events live from call to call; lacx_decode keeps one such object per device for the life of the process, and calls on
+ * one device take turns under a mutex.  device = -1: the device that is current at the first call. */
 typedef struct lacx_decoder lacx_decoder;
 int lacx_decoder_create(int device, lacx_decoder** out);
 void lacx_decoder_destroy(lacx_decoder* dec);

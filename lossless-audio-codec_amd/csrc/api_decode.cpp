@@ -75,19 +75,16 @@ struct lacx_decoder {
     hipEvent_t e0 = nullptr, e1 = nullptr;
     uint8_t* d_pay = nullptr;
     uint64_t pay_cap = 0;
-    unsigned long long* d_offs = nullptr;
-    uint64_t offs_cap = 0;
     int32_t *d_left = nullptr, *d_right = nullptr;
     uint64_t pcm_cap = 0;
     uint32_t* d_status = nullptr;
     uint8_t* d_ms = nullptr;
-    uint32_t* h_status = nullptr;          // pinned
-    unsigned long long* h_offs = nullptr;  // pinned
+    uint32_t* h_status = nullptr;  // pinned
     uint32_t blocks_cap = 0;
     uint8_t* d_wav = nullptr;  // WAV image (lacx_decoder_decode_wav*): header + data + pad
     uint8_t* h_wav = nullptr;  // pinned, behind lacx_decoder_decode_wav_view
     uint64_t wav_cap = 0;      // bytes of each
-    uint8_t* d_meta = nullptr;  // batch calls: item descriptors, offsets and lane tables (one upload)
+    uint8_t* d_meta = nullptr;  // item descriptors, offsets and lane tables (one upload)
     uint8_t* h_meta = nullptr;  // pinned
     uint64_t meta_cap = 0;      // bytes of each
     std::vector<std::string> item_err;  // the last batch call's message per item ("" = decoded)
@@ -101,13 +98,11 @@ void decoder_release(lacx_decoder* d) {
     if (d->e1) (void)hipEventDestroy(d->e1);
     if (d->stream) (void)hipStreamDestroy(d->stream);
     if (d->d_pay) (void)hipFree(d->d_pay);
-    if (d->d_offs) (void)hipFree(d->d_offs);
     if (d->d_left) (void)hipFree(d->d_left);
     if (d->d_right) (void)hipFree(d->d_right);
     if (d->d_status) (void)hipFree(d->d_status);
     if (d->d_ms) (void)hipFree(d->d_ms);
     if (d->h_status) (void)hipHostFree(d->h_status);
-    if (d->h_offs) (void)hipHostFree(d->h_offs);
     if (d->d_wav) (void)hipFree(d->d_wav);
     if (d->h_wav) (void)hipHostFree(d->h_wav);
     if (d->d_meta) (void)hipFree(d->d_meta);
@@ -161,8 +156,7 @@ uint64_t wav_header(const lacx_stream_info& info, uint8_t* h) {
     return 44u + data + pad;
 }
 
-// The decoder's grow-only buffers, shared by the single-stream and the batch calls.  Each returns the failing call's
-// error and names it in *what.
+// The decoder's grow-only buffers.  Each returns the failing call's error and names it in *what.
 hipError_t decoder_open(lacx_decoder* d, int* prev_device, const char** what) {  // *prev_device: to put back, or -1
     hipError_t e = hipSuccess;
     *prev_device = -1;
@@ -194,25 +188,18 @@ hipError_t grow_payload(lacx_decoder* d, uint64_t pay, const char** what) {  // 
 }
 hipError_t grow_blocks(lacx_decoder* d, uint32_t nb, const char** what) {
     if (nb <= d->blocks_cap) return hipSuccess;
-    if (d->d_offs) (void)hipFree(d->d_offs);
     if (d->d_status) (void)hipFree(d->d_status);
     if (d->d_ms) (void)hipFree(d->d_ms);
     if (d->h_status) (void)hipHostFree(d->h_status);
-    if (d->h_offs) (void)hipHostFree(d->h_offs);
-    d->d_offs = nullptr;
     d->d_status = nullptr;
     d->d_ms = nullptr;
     d->h_status = nullptr;
-    d->h_offs = nullptr;
     d->blocks_cap = 0;
     const uint32_t cap = nb + nb / 8 + 16;
     hipError_t e;
-    if ((e = hipMalloc((void**)&d->d_offs, 2 * ((size_t)cap + 1) * sizeof(unsigned long long))) != hipSuccess) return *what = "hipMalloc(offsets)", e;
     if ((e = hipMalloc((void**)&d->d_status, (size_t)cap * sizeof(uint32_t))) != hipSuccess) return *what = "hipMalloc(status)", e;
     if ((e = hipMalloc((void**)&d->d_ms, cap)) != hipSuccess) return *what = "hipMalloc(flags)", e;
     if ((e = hipHostMalloc((void**)&d->h_status, (size_t)cap * sizeof(uint32_t), 0)) != hipSuccess) return *what = "hipHostMalloc(status)", e;
-    if ((e = hipHostMalloc((void**)&d->h_offs, 2 * ((size_t)cap + 1) * sizeof(unsigned long long), 0)) != hipSuccess)
-        return *what = "hipHostMalloc(offsets)", e;
     d->blocks_cap = cap;
     return e;
 }
@@ -242,98 +229,13 @@ hipError_t grow_pcm(lacx_decoder* d, uint64_t frames, const char** what) {  // b
     return e;
 }
 
-// Upload, block decode and the pass after it, status check, download: into left / right (wav = false), or as the WAV
-// image into d->h_wav (wav = true; *wav_size = its size).  info: lacx_stream_parse's of the same bytes.
-int decode_run(lacx_decoder* d, const uint8_t* lac, uint64_t size, const lacx_stream_info& info, int32_t* left,
-               int32_t* right, bool wav, uint64_t* wav_size, float* device_ms) {
-    const uint64_t frames = info.frames;
-    if (device_ms) *device_ms = 0.f;
-    if (lacx_device_count() <= 0) return decode_fail(LACX_E_DEVICE, "no usable HIP device");
-#define DEC_TRY(call, what)                                                                                  \
-    do {                                                                                                     \
-        const hipError_t _e = (call);                                                                        \
-        if (_e != hipSuccess) {                                                                              \
-            rc = decode_fail(LACX_E_DEVICE, std::string(what) + ": " + hipGetErrorString(_e));               \
-            goto done;                                                                                       \
-        }                                                                                                    \
-    } while (0)
-    int rc = LACX_OK;
-    uint64_t image = 0;  // bytes of the WAV image
-    const uint32_t nb = info.blocks;
-    const bool v2 = info.version == 2;
-    const uint64_t entry = v2 ? 4u : 8u;
-    const uint64_t head = 14 + entry * nb, pay = size - head;
-    const size_t noffs = 2 * ((size_t)nb + 1);  // byte offsets, then frame offsets
-    int prev_device = -1;  // the caller's current device is put back on the way out
-    const char* what = "";
-    DEC_TRY(decoder_open(d, &prev_device, &what), what);
-    DEC_TRY(grow_payload(d, pay, &what), what);
-    DEC_TRY(grow_blocks(d, nb, &what), what);
-    if (wav) {
-        uint8_t hdr[44];
-        image = wav_header(info, hdr);
-        DEC_TRY(grow_wav(d, image, &what), what);
-        std::memcpy(d->h_wav, hdr, sizeof hdr);  // goes up with the offsets, comes back with the data
-    }
-    DEC_TRY(grow_pcm(d, frames, &what), what);
-    {
-        unsigned long long* byte_off = d->h_offs;
-        unsigned long long* frame_off = d->h_offs + nb + 1;
-        byte_off[0] = frame_off[0] = 0;
-        for (uint32_t b = 0; b < nb; ++b) {
-            frame_off[b + 1] = frame_off[b] + be32(lac + 14 + entry * b);
-            byte_off[b + 1] = v2 ? 0 : byte_off[b] + be32(lac + 18 + 8ull * b);
-        }
-        hipStream_t st = d->stream;
-        DEC_TRY(hipMemsetAsync(d->d_pay + pay, 0, kDecodeTailPad, st), "memset");  // the bit reader's look-ahead (decode.hip)
-        DEC_TRY(hipMemcpyAsync(d->d_offs, d->h_offs, noffs * sizeof(unsigned long long), hipMemcpyHostToDevice, st), "H2D offsets");
-        DEC_TRY(hipMemcpyAsync(d->d_pay, lac + head, pay, hipMemcpyHostToDevice, st), "H2D payload");
-        if (wav) DEC_TRY(hipMemcpyAsync(d->d_wav, d->h_wav, 44, hipMemcpyHostToDevice, st), "H2D WAV header");
-        uint8_t* dw = wav ? d->d_wav : nullptr;
-        DEC_TRY(hipEventRecord(d->e0, st), "event record");
-        int32_t* dr = info.channels == 2 ? d->d_right : nullptr;
-        if (v2)
-            DEC_TRY(launch_decode_serial(nb, info.channels, info.stereo_mode, info.bit_depth, d->d_pay, (uint32_t)(8ull * pay), d->d_offs + nb + 1,
-                                         d->d_left, dr, d->d_status, d->d_ms, st, dw, frames), "decode launch");
-        else
-            DEC_TRY(launch_decode(nb, info.channels, info.stereo_mode, info.bit_depth, d->d_pay, d->d_offs, d->d_offs + nb + 1, d->d_left, dr,
-                                  d->d_status, d->d_ms, st, dw, frames), "decode launch");
-        DEC_TRY(hipEventRecord(d->e1, st), "event record");
-        DEC_TRY(hipMemcpyAsync(d->h_status, d->d_status, (size_t)nb * sizeof(uint32_t), hipMemcpyDeviceToHost, st), "D2H status");
-        DEC_TRY(hipStreamSynchronize(st), "synchronize");
-        if (device_ms) (void)hipEventElapsedTime(device_ms, d->e0, d->e1);
-        for (uint32_t b = 0; b < nb; ++b) {
-            if (d->h_status[b]) {  // the first failing block, like the reference's message (lac/decoder.cpp:24-32)
-                static const char* const kWhat[] = {"", "block header", "channel header", "residual", "padding", "sample overflow",
-                                                    "trailing bytes", "sample outside the bit depth", "not reached", "residual beyond 2^30"};
-                rc = decode_fail(LACX_E_RUNTIME, "[decode-error] block=" + std::to_string(b) + " " +
-                                                     (d->h_status[b] < 10 ? kWhat[d->h_status[b]] : "?"));
-                goto done;
-            }
-        }
-        if (wav) {  // header and data in one copy, aligned base to aligned base
-            DEC_TRY(hipMemcpyAsync(d->h_wav, d->d_wav, image, hipMemcpyDeviceToHost, st), "D2H WAV image");
-        } else {
-            // the two channels leave on two streams' worth of copy engine time: issue both, then wait
-            DEC_TRY(hipMemcpyAsync(left, d->d_left, frames * sizeof(int32_t), hipMemcpyDeviceToHost, st), "D2H left");
-            if (info.channels == 2) DEC_TRY(hipMemcpyAsync(right, d->d_right, frames * sizeof(int32_t), hipMemcpyDeviceToHost, st), "D2H right");
-        }
-        DEC_TRY(hipStreamSynchronize(st), "synchronize");
-        if (wav) *wav_size = image;
-    }
-done:
-#undef DEC_TRY
-    if (prev_device >= 0) (void)hipSetDevice(prev_device);
-    return rc;
-}
-
 const char* block_error(uint32_t st) {
     static const char* const kWhat[] = {"", "block header", "channel header", "residual", "padding", "sample overflow",
                                         "trailing bytes", "sample outside the bit depth", "not reached", "residual beyond 2^30"};
     return st < 10 ? kWhat[st] : "?";
 }
 
-// One item of a batch call: the stream, and for the device form the caller's output arrays.
+// One item of a decode: the stream, and for the device and host forms the caller's output arrays.
 struct BatchIn {
     const uint8_t* lac;
     uint64_t size;
@@ -342,18 +244,23 @@ struct BatchIn {
     uint64_t frames;
 };
 
-// Many streams as one decode (lacx_decoder_decode_wav_batch_view, lacx_decoder_decode_batch_device).  Every item is parsed
-// on the host first; those that parse go to the device together: their payloads back to back in one buffer (the tail pad
-// after the last), their block tables as global prefix sums, one lane per version-3 block (an item's blocks in
-// consecutive lanes) and one lane per version-2 item, then one post pass over all of them.  wav = true: the images into
-// the decoder's pinned image buffer (out[i]: each item's, 16-byte aligned, one D2H copy); false: into the caller's
-// arrays in place, on `stream`.  Per item: d->item_err and item_rc; the call returns the lowest failing item's code with
-// "stream i: <message>", or LACX_E_DEVICE for a failure of the whole call.
-int decode_batch_run(lacx_decoder* d, const BatchIn* in, uint32_t n, bool wav, hipStream_t stream, lacx_span* out,
-                     int* item_rc, float* device_ms) {
+// Where the decoded items go.  wav: the images into the decoder's pinned image buffer (out[i]: each item's, 16-byte
+// aligned, one D2H copy for all).  device: the caller's device arrays, in place, on the caller's stream.  host: the
+// decoder's own PCM buffers, then, once the statuses are checked, the caller's host arrays of the items that decoded.
+enum class DecodeTo { wav, device, host };
+
+// The decoder: n streams as one decode (a single stream is n = 1).  Every item is parsed on the host first; those that
+// parse go to the device together: their payloads back to back in one buffer (the tail pad after the last), their block
+// tables as global prefix sums, one lane per version-3 block (an item's blocks in consecutive lanes) and one lane per
+// version-2 item, then one post pass over all of them.  Per item, code[i] and err[i] ("" = decoded): the message its
+// decode gives.  Returns LACX_OK, or LACX_E_DEVICE for a failure of the whole call (every item that parsed then carries
+// it).  The caller decides what the outcome becomes: the batch entry points keep it in d->item_err.
+int decode_batch_run(lacx_decoder* d, const BatchIn* in, uint32_t n, DecodeTo to, hipStream_t stream, lacx_span* out,
+                     std::vector<int>& code, std::vector<std::string>& err, float* device_ms) {
     if (device_ms) *device_ms = 0.f;
-    std::vector<int> code(n, LACX_OK);
-    d->item_err.assign(n, std::string());
+    const bool wav = to == DecodeTo::wav, own_pcm = to != DecodeTo::device;  // own_pcm: into d->d_left / d_right
+    code.assign(n, LACX_OK);
+    err.assign(n, std::string());
     std::vector<lacx_stream_info> info(n);
     for (uint32_t i = 0; i < n; ++i) {
         if (out) out[i] = lacx_span{nullptr, 0};
@@ -365,12 +272,12 @@ int decode_batch_run(lacx_decoder* d, const BatchIn* in, uint32_t n, bool wav, h
         }
         if (c != LACX_OK) {
             code[i] = c;
-            d->item_err[i] = g_decode_err;
+            err[i] = g_decode_err;
         }
     }
     // the items that go to the device, and where each one lies in the batch's buffers
     std::vector<uint32_t> dev;
-    std::vector<DecodeBatchItem> it;
+    std::vector<DecodeItem> it;
     std::vector<uint64_t> pcm_at, wav_at, image_size;
     uint64_t total_blocks = 0, total_frames = 0, total_pay = 0, total_units = 0, pcm_total = 0, image_total = 0;
     uint32_t v3_blocks = 0;
@@ -378,7 +285,7 @@ int decode_batch_run(lacx_decoder* d, const BatchIn* in, uint32_t n, bool wav, h
         if (code[i] != LACX_OK) continue;
         const lacx_stream_info& f = info[i];
         const uint64_t head = 14 + (f.version == 2 ? 4ull : 8ull) * f.blocks;
-        DecodeBatchItem x{};
+        DecodeItem x{};
         x.frame0 = total_frames;
         x.frames = f.frames;
         x.pay_off = total_pay;
@@ -389,16 +296,19 @@ int decode_batch_run(lacx_decoder* d, const BatchIn* in, uint32_t n, bool wav, h
         x.stereo_mode = f.stereo_mode;
         x.bit_depth = f.bit_depth;
         x.version = f.version;
-        if (wav) {  // offsets for now, pointers once the buffers exist
+        if (own_pcm) {  // offsets for now, pointers once the buffers exist
             pcm_at.push_back(pcm_total);
             pcm_total += (f.frames + 3u) & ~3ull;  // every item's PCM from a multiple of 4 frames: 16-byte loads
+        }
+        if (wav) {
             uint8_t hdr[44];
             const uint64_t image = wav_header(f, hdr);
             wav_at.push_back(image_total);
             image_size.push_back(image);
             image_total += (image + 15u) & ~15ull;
             total_units += (f.frames + 3u) / 4u;
-        } else {
+        }
+        if (!own_pcm) {
             x.left = in[i].left;
             x.right = f.channels == 2 ? in[i].right : nullptr;
         }
@@ -426,6 +336,7 @@ int decode_batch_run(lacx_decoder* d, const BatchIn* in, uint32_t n, bool wav, h
         }                                                                                                    \
     } while (0)
         const char* what = "";
+        hipStream_t st = to == DecodeTo::device ? stream : d->stream;
         const uint32_t T = (uint32_t)total_blocks;
         // LACX_DECODE_BATCH_PAD=1 (tuning knob, read per call): every item's blocks start a new wave
         const char* pad_env = std::getenv("LACX_DECODE_BATCH_PAD");
@@ -442,17 +353,15 @@ int decode_batch_run(lacx_decoder* d, const BatchIn* in, uint32_t n, bool wav, h
         }
         // metadata, one upload: items | byte_off [T + 1] | frame_off [T + 1] | unit_off [m + 1] | blk_item [T] |
         // lane_blk | v2_items
-        const size_t o_items = 0, o_byte = (sizeof(DecodeBatchItem) * m + 15u) & ~(size_t)15u;
+        const size_t o_items = 0, o_byte = (sizeof(DecodeItem) * m + 15u) & ~(size_t)15u;
         const size_t o_frame = o_byte + 8 * ((size_t)T + 1), o_unit = o_frame + 8 * ((size_t)T + 1);
         const size_t o_bitem = o_unit + 8 * ((size_t)m + 1), o_lane = o_bitem + 4 * (size_t)T;
         const size_t o_v2 = o_lane + 4 * lane_blk.size(), meta = o_v2 + 4 * v2_items.size();
         DEC_TRY(decoder_open(d, &prev_device, &what), what);
         DEC_TRY(grow_payload(d, total_pay, &what), what);
         DEC_TRY(grow_blocks(d, T, &what), what);
-        if (wav) {
-            DEC_TRY(grow_wav(d, image_total, &what), what);
-            DEC_TRY(grow_pcm(d, pcm_total, &what), what);
-        }
+        if (wav) DEC_TRY(grow_wav(d, image_total, &what), what);
+        if (own_pcm) DEC_TRY(grow_pcm(d, pcm_total, &what), what);
         if (meta > d->meta_cap) {
             if (d->d_meta) (void)hipFree(d->d_meta);
             if (d->h_meta) (void)hipHostFree(d->h_meta);
@@ -472,7 +381,7 @@ int decode_batch_run(lacx_decoder* d, const BatchIn* in, uint32_t n, bool wav, h
             byte_off[0] = frame_off[0] = unit_off[0] = 0;
             for (uint32_t j = 0; j < m; ++j) {
                 const BatchIn& x = in[dev[j]];
-                DecodeBatchItem& y = it[j];
+                DecodeItem& y = it[j];
                 const bool v2 = y.version == 2;
                 const uint64_t entry = v2 ? 4u : 8u;
                 for (uint32_t b = 0; b < y.blocks; ++b) {
@@ -485,18 +394,17 @@ int decode_batch_run(lacx_decoder* d, const BatchIn* in, uint32_t n, bool wav, h
                     byte_off[y.block0 + y.blocks] = y.pay_off + (y.pay_bits >> 3);
                 }
                 unit_off[j + 1] = unit_off[j] + (y.frames + 3u) / 4u;
-                if (wav) {
+                if (own_pcm) {
                     y.left = d->d_left + pcm_at[j];
                     y.right = y.channels == 2 ? d->d_right + pcm_at[j] : nullptr;
-                    y.wav = d->d_wav + wav_at[j];
                 }
+                if (wav) y.wav = d->d_wav + wav_at[j];
             }
-            std::memcpy(h + o_items, it.data(), sizeof(DecodeBatchItem) * m);
+            std::memcpy(h + o_items, it.data(), sizeof(DecodeItem) * m);
             if (!lane_blk.empty()) std::memcpy(h + o_lane, lane_blk.data(), 4 * lane_blk.size());
             if (!v2_items.empty()) std::memcpy(h + o_v2, v2_items.data(), 4 * v2_items.size());
         }
         {
-            hipStream_t st = wav ? d->stream : stream;
             DEC_TRY(hipMemcpyAsync(d->d_meta, d->h_meta, meta, hipMemcpyHostToDevice, st), "H2D batch tables");
             for (uint32_t j = 0; j < m; ++j) {
                 const BatchIn& x = in[dev[j]];
@@ -504,11 +412,11 @@ int decode_batch_run(lacx_decoder* d, const BatchIn* in, uint32_t n, bool wav, h
                 DEC_TRY(hipMemcpyAsync(d->d_pay + it[j].pay_off, x.lac + head, x.size - head, hipMemcpyHostToDevice, st), "H2D payload");
             }
             DEC_TRY(hipMemsetAsync(d->d_pay + total_pay, 0, kDecodeTailPad, st), "memset");  // the bit reader's look-ahead
-            DecodeBatchArgs a;
+            DecodeArgs a;
             uint8_t* dm = d->d_meta;
             a.nitems = m;
             a.total_blocks = T;
-            a.items = reinterpret_cast<const DecodeBatchItem*>(dm + o_items);
+            a.items = reinterpret_cast<const DecodeItem*>(dm + o_items);
             a.blk_item = reinterpret_cast<const uint32_t*>(dm + o_bitem);
             a.lanes = (uint32_t)lane_blk.size();
             a.lane_blk = reinterpret_cast<const uint32_t*>(dm + o_lane);
@@ -523,7 +431,7 @@ int decode_batch_run(lacx_decoder* d, const BatchIn* in, uint32_t n, bool wav, h
             a.unit_off = reinterpret_cast<const unsigned long long*>(dm + o_unit);
             a.total_units = total_units;
             DEC_TRY(hipEventRecord(d->e0, st), "event record");
-            DEC_TRY(launch_decode_batch(a, st), "decode launch");
+            DEC_TRY(launch_decode(a, st), "decode launch");
             DEC_TRY(hipEventRecord(d->e1, st), "event record");
             DEC_TRY(hipMemcpyAsync(d->h_status, d->d_status, (size_t)T * sizeof(uint32_t), hipMemcpyDeviceToHost, st), "D2H status");
             // the images of the items that decoded are valid whatever the others did: one copy for all
@@ -535,18 +443,26 @@ int decode_batch_run(lacx_decoder* d, const BatchIn* in, uint32_t n, bool wav, h
             const uint32_t i = dev[j];
             for (uint32_t b = 0; b < it[j].blocks; ++b) {
                 const uint32_t sv = d->h_status[it[j].block0 + b];
-                if (sv) {  // the item's first failing block, the message its own decode gives
+                if (sv) {  // the item's first failing block, like the reference's message (lac/decoder.cpp:24-32)
                     code[i] = LACX_E_RUNTIME;
-                    d->item_err[i] = "[decode-error] block=" + std::to_string(b) + " " + block_error(sv);
+                    err[i] = "[decode-error] block=" + std::to_string(b) + " " + block_error(sv);
                     break;
                 }
             }
-            if (wav && code[i] == LACX_OK) {
+            if (code[i] != LACX_OK) continue;
+            if (wav) {
                 uint8_t* img = d->h_wav + wav_at[j];
                 (void)wav_header(info[i], img);
                 if (out) out[i] = lacx_span{img, image_size[j]};
             }
+            if (to == DecodeTo::host) {  // the two channels leave on two streams' worth of copy engine time: issue, then wait
+                const uint64_t bytes = it[j].frames * sizeof(int32_t);
+                DEC_TRY(hipMemcpyAsync(in[i].left, d->d_left + pcm_at[j], bytes, hipMemcpyDeviceToHost, st), "D2H left");
+                if (it[j].channels == 2)
+                    DEC_TRY(hipMemcpyAsync(in[i].right, d->d_right + pcm_at[j], bytes, hipMemcpyDeviceToHost, st), "D2H right");
+            }
         }
+        if (to == DecodeTo::host) DEC_TRY(hipStreamSynchronize(st), "synchronize");
 #undef DEC_TRY
     }
 done:
@@ -555,28 +471,37 @@ done:
         for (uint32_t i = 0; i < n; ++i) {
             if (code[i] != LACX_OK) continue;
             code[i] = rc;
-            d->item_err[i] = g_decode_err;
+            err[i] = g_decode_err;
             if (out) out[i] = lacx_span{nullptr, 0};
         }
     }
-    if (item_rc)
-        for (uint32_t i = 0; i < n; ++i) item_rc[i] = code[i];
+    return rc;
+}
+
+// A batch entry point's result: the per-item outcome into item_rc and d->item_err, and the lowest failing item's code
+// with "stream i: <message>" (or the whole call's failure).
+int batch_result(lacx_decoder* d, int rc, const std::vector<int>& code, std::vector<std::string>& err, int* item_rc) {
+    if (item_rc) std::copy(code.begin(), code.end(), item_rc);
+    d->item_err = std::move(err);
     if (rc != LACX_OK) return rc;
-    for (uint32_t i = 0; i < n; ++i)
+    for (size_t i = 0; i < code.size(); ++i)
         if (code[i] != LACX_OK) return decode_fail(code[i], "stream " + std::to_string(i) + ": " + d->item_err[i]);
     return LACX_OK;
+}
+
+// A single stream as a batch of one: its own code and message.  d->item_err keeps the last batch call's.
+int decode_one(lacx_decoder* d, const BatchIn& in, DecodeTo to, lacx_span* out, float* device_ms) {
+    std::vector<int> code;
+    std::vector<std::string> err;
+    (void)decode_batch_run(d, &in, 1, to, nullptr, out, code, err, device_ms);
+    return code[0] == LACX_OK ? LACX_OK : decode_fail(code[0], err[0]);
 }
 }  // namespace
 
 int lacx_decoder_decode(lacx_decoder* d, const uint8_t* lac, uint64_t size, int32_t* left, int32_t* right, uint64_t frames,
                         float* device_ms) {
     if (!d) return decode_fail(LACX_E_INVALID, "null decoder");
-    lacx_stream_info info;
-    const int prc = lacx_stream_parse(lac, size, &info);
-    if (prc) return prc;
-    if (!left || (info.channels == 2 && !right)) return decode_fail(LACX_E_INVALID, "output arrays missing");
-    if (frames != info.frames) return decode_fail(LACX_E_INVALID, "output arrays do not match the stream's frame count");
-    return decode_run(d, lac, size, info, left, right, false, nullptr, device_ms);
+    return decode_one(d, BatchIn{lac, size, left, right, frames}, DecodeTo::host, nullptr, device_ms);
 }
 
 int lacx_decoder_decode_wav_view(lacx_decoder* d, const uint8_t* lac, uint64_t size, const uint8_t** out, uint64_t* out_size,
@@ -585,14 +510,11 @@ int lacx_decoder_decode_wav_view(lacx_decoder* d, const uint8_t* lac, uint64_t s
     if (out_size) *out_size = 0;
     if (!d) return decode_fail(LACX_E_INVALID, "null decoder");
     if (!out || !out_size) return decode_fail(LACX_E_INVALID, "null argument");
-    lacx_stream_info info;
-    const int prc = lacx_stream_parse(lac, size, &info);
-    if (prc) return prc;
-    uint64_t image = 0;
-    const int rc = decode_run(d, lac, size, info, nullptr, nullptr, true, &image, device_ms);
+    lacx_span img{nullptr, 0};
+    const int rc = decode_one(d, BatchIn{lac, size, nullptr, nullptr, 0}, DecodeTo::wav, &img, device_ms);
     if (rc) return rc;
-    *out = d->h_wav;
-    *out_size = image;
+    *out = img.data;  // the start of d->h_wav: a batch of one
+    *out_size = img.size;
     return LACX_OK;
 }
 
@@ -619,7 +541,10 @@ int lacx_decoder_decode_wav_batch_view(lacx_decoder* d, const lacx_span* lacs, u
     if (!lacs || !out || n == 0) return decode_fail(LACX_E_INVALID, "null argument or empty batch");
     std::vector<BatchIn> in(n);
     for (uint32_t i = 0; i < n; ++i) in[i] = BatchIn{lacs[i].data, lacs[i].size, nullptr, nullptr, 0};
-    return decode_batch_run(d, in.data(), n, true, nullptr, out, item_rc, device_ms);
+    std::vector<int> code;
+    std::vector<std::string> err;
+    const int rc = decode_batch_run(d, in.data(), n, DecodeTo::wav, nullptr, out, code, err, device_ms);
+    return batch_result(d, rc, code, err, item_rc);
 }
 
 int lacx_decoder_decode_wav_batch(lacx_decoder* d, const lacx_span* lacs, uint32_t n, lacx_span* out, int* item_rc,
@@ -649,7 +574,11 @@ int lacx_decoder_decode_batch_device(lacx_decoder* d, const lacx_decode_item* it
     if (!items || n == 0) return decode_fail(LACX_E_INVALID, "null argument or empty batch");
     std::vector<BatchIn> in(n);
     for (uint32_t i = 0; i < n; ++i) in[i] = BatchIn{items[i].lac, items[i].size, items[i].left, items[i].right, items[i].frames};
-    return decode_batch_run(d, in.data(), n, false, static_cast<hipStream_t>(stream), nullptr, item_rc, device_ms);
+    std::vector<int> code;
+    std::vector<std::string> err;
+    const int rc = decode_batch_run(d, in.data(), n, DecodeTo::device, static_cast<hipStream_t>(stream), nullptr, code, err,
+                                    device_ms);
+    return batch_result(d, rc, code, err, item_rc);
 }
 
 const char* lacx_decoder_item_error(const lacx_decoder* d, uint32_t i) {

@@ -4,24 +4,23 @@
 // What the format allows to run in parallel is the block: inside a block the two channel bitstreams follow each other
 // byte-aligned but without a length field, every token's length depends on the Rice parameter, and the Rice parameter
 // depends on every sample decoded before it (ref src/codec/block/decoder.cpp:64-520, src/codec/rice/rice.hpp:45-114).
-// So: ONE LANE PER BLOCK, both channels one after the other, all blocks of the stream at once -- the duration is one
-// block's serial chain whatever the stream's length (up to the chip's ~65 000 resident lanes = 18 h of audio), and the
-// throughput comes from the number of blocks.  Per-lane state that must be indexed lives in LDS, one column per lane:
-// the last 256 residual magnitudes of the stateful Rice adaptation and the predictor's history.
-//   k_decode      bitstream -> residuals -> samples (fixed / FIR / LPC synthesis), planar int32, per-block status
-//   k_ms_inverse  mid/side -> left/right where the block's flag says so, and the bit-depth range check
+// So: ONE LANE PER BLOCK, both channels one after the other, all blocks of every stream of the job at once -- the
+// duration is one block's serial chain whatever the streams' length (up to the chip's ~65 000 resident lanes = 18 h of
+// audio), and the throughput comes from the number of blocks.  Per-lane state that must be indexed lives in LDS, one
+// column per lane: the last 256 residual magnitudes of the stateful Rice adaptation and the predictor's history.
+//   k_decode        bitstream -> residuals -> samples (fixed / FIR / LPC synthesis), planar int32, per-block status
+//   k_decode_serial the same for a legacy version-2 stream (no compressed block sizes): one lane walks it
+//   k_ms_inverse    mid/side -> left/right where the block's flag says so, and the bit-depth range check
 //                                                                        (ref src/codec/lac/decoder.cpp:48-65,30-46)
-//   k_wav_pack    the same per-sample work as k_ms_inverse, written as the data region of a canonical WAV image
-//                 (interleaved little-endian 16 / 24-bit, ref src/main.cpp:150-182) instead of back into left/right
-//   k_decode_batch, k_decode_serial_batch, k_ms_inverse_batch, k_wav_pack_batch
-//                 the same for many streams as one job: every block of every item in one launch
+//   k_wav_pack      the same per-sample work as k_ms_inverse, written as the data region of a canonical WAV image
+//                   (interleaved little-endian 16 / 24-bit, ref src/main.cpp:150-182) instead of back into left/right
+// Every launch decodes a batch of streams (items) as one job; a single stream is a batch of one.
 // The adaptive Rice parameter uses the encoder's division-free formulation (kmean / biased_k of analyze_core.h, proven
 // against Rice::adapt_k there); it assumes zigzag residuals below 2^30 like the encoder does, and a stream with a larger
 // one is refused (status 9) rather than decoded differently from the reference.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <cstdlib>
 
 #include "analyze_core.h"
 #include "kernels.h"
@@ -34,8 +33,7 @@ constexpr int kDecThreads = 64;
 constexpr uint32_t kModeBin = 2, kModeStatic = 3;  // (0 = adaptive Rice, 1 = zero-run)  ref block/constants.hpp
 constexpr uint32_t kZeroRunMin = 4, kZeroRunK = 2;
 
-// Per-lane state that must be indexed, in LDS, one column per ACTIVE lane (row stride = active lanes of the wave, so a
-// wave that decodes one block needs 1.3 KiB and many such waves share a CU).
+// Per-lane state that must be indexed, in LDS, one column per lane (row stride = cols, the 64 lanes of the wave).
 struct DecMem {
     uint32_t* ring_;  // [256][cols] the last 256 residual magnitudes (stateful adaptation's drift window)
     int32_t* hist_;   // [32][cols]  the last 32 reconstructed samples (only LPC orders above 12 read it)
@@ -46,6 +44,18 @@ struct DecMem {
     __device__ __forceinline__ int16_t& coef(uint32_t slot, int lane) { return coef_[slot * cols + (uint32_t)lane]; }
 };
 constexpr size_t kDecBytesPerCol = 256 * 4 + 32 * 4 + 32 * 2;
+// The workgroup's `cols` columns in its dynamic LDS.  k_decode passes blockDim.x (= kDecThreads) rather than the
+// constant on purpose: with a compile-time stride the compiler strength-reduces the LDS addressing into loop-carried adds
+// that the per-sample loop then pays on every trip, plain trips included (+1.3 % kernel time on the 2 h stream, DESIGN
+// §6b).  (k_decode_serial, one lane per legacy stream, keeps the constant: its code does not get better with it.)
+__device__ __forceinline__ DecMem dec_mem(unsigned char* raw, uint32_t cols) {
+    DecMem dm;
+    dm.cols = cols;
+    dm.ring_ = reinterpret_cast<uint32_t*>(raw);
+    dm.hist_ = reinterpret_cast<int32_t*>(raw + (size_t)256 * 4 * dm.cols);
+    dm.coef_ = reinterpret_cast<int16_t*>(raw + (size_t)(256 + 32) * 4 * dm.cols);
+    return dm;
+}
 
 // A pointer read from memory (an item descriptor) is generic to the compiler, and its loads and stores would be flat
 // ones; these all point into global memory, and the round trip through the global address space says so.
@@ -410,7 +420,7 @@ __device__ uint32_t decode_channel_block(BitIn& r, uint32_t n, int32_t* __restri
 
 }  // namespace
 
-// One block of a version-3 stream by one lane (k_decode, k_decode_batch): blk indexes the global tables; the block's
+// One block of a version-3 stream by one lane (k_decode): blk indexes the global tables; the block's
 // samples go to left / right at frame_off[blk] - frame_base (the first frame of the stream those arrays hold).
 __device__ __forceinline__ void decode_block_lane(uint32_t blk, int channels, int stereo_mode, const uint8_t* __restrict__ payload,
                                                   const unsigned long long* __restrict__ byte_off,
@@ -468,95 +478,47 @@ __device__ __forceinline__ void decode_serial_lane(uint32_t num_blocks, int chan
     }
 }
 
-// lanes_per_wave (a power of two, 1..64): how many blocks one wave decodes -- fewer blocks per wave mean more waves to
-// interleave on a SIMD while the stream has few enough blocks that the idle lanes do not matter (the launcher picks).
-__global__ __launch_bounds__(kDecThreads) void k_decode(uint32_t num_blocks, int channels, int stereo_mode,
-                                                        uint32_t lanes_per_wave,
+// One lane per version-3 block: lane g decodes block lane_blk[g] of the global tables (~0u: an idle lane), whatever item
+// it belongs to (blk_item); the item's descriptor gives the block's format and output arrays.  The host lays the lanes
+// out so that an item's blocks sit in consecutive lanes (see launch_decode).  64 LDS columns per wave.
+__global__ __launch_bounds__(kDecThreads) void k_decode(uint32_t lanes, const uint32_t* __restrict__ lane_blk,
+                                                        const uint32_t* __restrict__ blk_item,
+                                                        const DecodeItem* __restrict__ items,
                                                         const uint8_t* __restrict__ payload,
                                                         const unsigned long long* __restrict__ byte_off,
                                                         const unsigned long long* __restrict__ frame_off,
-                                                        int32_t* __restrict__ left, int32_t* __restrict__ right,
                                                         uint32_t* __restrict__ status, uint8_t* __restrict__ ms_flag) {
     extern __shared__ __align__(16) unsigned char dec_raw[];
-    DecMem dm;
-    dm.cols = lanes_per_wave;
-    dm.ring_ = reinterpret_cast<uint32_t*>(dec_raw);
-    dm.hist_ = reinterpret_cast<int32_t*>(dec_raw + (size_t)256 * 4 * lanes_per_wave);
-    dm.coef_ = reinterpret_cast<int16_t*>(dec_raw + (size_t)(256 + 32) * 4 * lanes_per_wave);
-    const int lane = (int)threadIdx.x;
-    if ((uint32_t)lane >= lanes_per_wave) return;
-    const uint32_t blk = blockIdx.x * lanes_per_wave + threadIdx.x;
-    if (blk >= num_blocks) return;
-    decode_block_lane(blk, channels, stereo_mode, payload, byte_off, frame_off, 0ull, left, right, status, ms_flag, dm, lane);
-}
-
-// Many streams as one launch: lane g decodes block lane_blk[g] of the global tables (~0u: an idle lane), whatever item
-// it belongs to (blk_item); the item's descriptor gives what k_decode takes as arguments.  The host lays the lanes out
-// so that an item's blocks sit in consecutive lanes (see launch_decode_batch).  64 LDS columns per wave.
-__global__ __launch_bounds__(kDecThreads) void k_decode_batch(uint32_t lanes, const uint32_t* __restrict__ lane_blk,
-                                                              const uint32_t* __restrict__ blk_item,
-                                                              const DecodeBatchItem* __restrict__ items,
-                                                              const uint8_t* __restrict__ payload,
-                                                              const unsigned long long* __restrict__ byte_off,
-                                                              const unsigned long long* __restrict__ frame_off,
-                                                              uint32_t* __restrict__ status, uint8_t* __restrict__ ms_flag) {
-    extern __shared__ __align__(16) unsigned char dec_raw[];
-    DecMem dm;
-    dm.cols = kDecThreads;
-    dm.ring_ = reinterpret_cast<uint32_t*>(dec_raw);
-    dm.hist_ = reinterpret_cast<int32_t*>(dec_raw + (size_t)256 * 4 * kDecThreads);
-    dm.coef_ = reinterpret_cast<int16_t*>(dec_raw + (size_t)(256 + 32) * 4 * kDecThreads);
+    DecMem dm = dec_mem(dec_raw, blockDim.x);
     const int lane = (int)threadIdx.x;
     const uint32_t g = blockIdx.x * kDecThreads + threadIdx.x;
     if (g >= lanes) return;
     const uint32_t blk = lane_blk[g];
     if (blk == ~0u) return;
-    const DecodeBatchItem& it = items[blk_item[blk]];
+    const DecodeItem& it = items[blk_item[blk]];
     decode_block_lane(blk, it.channels, it.stereo_mode, payload, byte_off, frame_off, it.frame0, global_ptr(it.left),
                       global_ptr(it.right), status, ms_flag, dm, lane);
 }
 
 // The legacy version-2 container carries no compressed block sizes (ref lac/decoder.cpp:209-219): block i starts where
-// block i-1 ended, so ONE lane walks the whole stream.  Kept for completeness of the reader (the encoder has written
-// version 3 only since); status[] is set for the blocks up to and including the first that fails.
-__global__ __launch_bounds__(kDecThreads) void k_decode_serial(uint32_t num_blocks, int channels, int stereo_mode,
-                                                               const uint8_t* __restrict__ payload, uint32_t payload_bits,
+// block i-1 ended, so ONE lane walks a whole stream.  One lane per version-2 item (v2_items: their indices); launched only
+// when the batch has such items.  Kept for completeness of the reader (the encoder has written version 3 only since).
+__global__ __launch_bounds__(kDecThreads) void k_decode_serial(uint32_t nv2, const uint32_t* __restrict__ v2_items,
+                                                               const DecodeItem* __restrict__ items,
+                                                               const uint8_t* __restrict__ payload,
                                                                const unsigned long long* __restrict__ frame_off,
-                                                               int32_t* __restrict__ left, int32_t* __restrict__ right,
                                                                uint32_t* __restrict__ status, uint8_t* __restrict__ ms_flag) {
     extern __shared__ __align__(16) unsigned char dec_raw[];
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    DecMem dm;
-    dm.cols = 1;
-    dm.ring_ = reinterpret_cast<uint32_t*>(dec_raw);
-    dm.hist_ = reinterpret_cast<int32_t*>(dec_raw + 256 * 4);
-    dm.coef_ = reinterpret_cast<int16_t*>(dec_raw + (256 + 32) * 4);
-    decode_serial_lane(num_blocks, channels, stereo_mode, payload, payload_bits, frame_off, 0ull, left, right, status, ms_flag,
-                       dm, 0);
-}
-
-// The version-2 items of a batch: one lane per item (v2_items: their indices), each walking its stream like
-// k_decode_serial.  Launched only when the batch has such items.
-__global__ __launch_bounds__(kDecThreads) void k_decode_serial_batch(uint32_t nv2, const uint32_t* __restrict__ v2_items,
-                                                                     const DecodeBatchItem* __restrict__ items,
-                                                                     const uint8_t* __restrict__ payload,
-                                                                     const unsigned long long* __restrict__ frame_off,
-                                                                     uint32_t* __restrict__ status, uint8_t* __restrict__ ms_flag) {
-    extern __shared__ __align__(16) unsigned char dec_raw[];
-    DecMem dm;
-    dm.cols = kDecThreads;
-    dm.ring_ = reinterpret_cast<uint32_t*>(dec_raw);
-    dm.hist_ = reinterpret_cast<int32_t*>(dec_raw + (size_t)256 * 4 * kDecThreads);
-    dm.coef_ = reinterpret_cast<int16_t*>(dec_raw + (size_t)(256 + 32) * 4 * kDecThreads);
+    DecMem dm = dec_mem(dec_raw, kDecThreads);
     const uint32_t g = blockIdx.x * kDecThreads + threadIdx.x;
     if (g >= nv2) return;
-    const DecodeBatchItem& it = items[v2_items[g]];
+    const DecodeItem& it = items[v2_items[g]];
     decode_serial_lane(it.blocks, it.channels, it.stereo_mode, payload + it.pay_off, it.pay_bits, frame_off + it.block0, it.frame0,
                        global_ptr(it.left), global_ptr(it.right), status + it.block0, ms_flag + it.block0, dm, (int)threadIdx.x);
 }
 
 // One tile of 1024 samples of one block: the mid/side inverse in place where the block's flag says so, and the
-// bit-depth range check (k_ms_inverse, k_ms_inverse_batch).  f0: the block's first frame in left / right.
+// bit-depth range check (k_ms_inverse).  f0: the block's first frame in left / right.
 __device__ __forceinline__ void ms_inverse_tile(uint32_t blk, uint32_t tile, int channels, int bit_depth, unsigned long long f0,
                                                 uint32_t n, int32_t* __restrict__ left, int32_t* __restrict__ right,
                                                 const uint8_t* __restrict__ ms_flag, uint32_t* __restrict__ status) {
@@ -577,36 +539,18 @@ __device__ __forceinline__ void ms_inverse_tile(uint32_t blk, uint32_t tile, int
     if (bad) atomicMax(&status[blk], 7u);
 }
 
-// grid = (blocks, tiles): the samples of block blockIdx.x in tiles of 1024
-__global__ __launch_bounds__(256) void k_ms_inverse(int channels, int bit_depth,
+// grid = (all blocks of the batch, tiles): the samples of block blockIdx.x in tiles of 1024, in place in its item's arrays
+__global__ __launch_bounds__(256) void k_ms_inverse(const uint32_t* __restrict__ blk_item,
+                                                    const DecodeItem* __restrict__ items,
                                                     const unsigned long long* __restrict__ frame_off,
-                                                    int32_t* __restrict__ left, int32_t* __restrict__ right,
                                                     const uint8_t* __restrict__ ms_flag, uint32_t* __restrict__ status) {
     const uint32_t blk = blockIdx.x, tile = blockIdx.y;
     if (status[blk]) return;  // (uniform) the block did not decode
-    const unsigned long long f0 = frame_off[blk];
-    const uint32_t n = (uint32_t)(frame_off[blk + 1] - f0);
-    ms_inverse_tile(blk, tile, channels, bit_depth, f0, n, left, right, ms_flag, status);
-}
-
-// The same over every block of every item of a batch (grid = (all blocks, tiles)), into each item's own arrays.
-__global__ __launch_bounds__(256) void k_ms_inverse_batch(const uint32_t* __restrict__ blk_item,
-                                                          const DecodeBatchItem* __restrict__ items,
-                                                          const unsigned long long* __restrict__ frame_off,
-                                                          const uint8_t* __restrict__ ms_flag, uint32_t* __restrict__ status) {
-    const uint32_t blk = blockIdx.x, tile = blockIdx.y;
-    if (status[blk]) return;  // (uniform) the block did not decode
-    const DecodeBatchItem& it = items[blk_item[blk]];
+    const DecodeItem& it = items[blk_item[blk]];
     const unsigned long long f0 = frame_off[blk];
     const uint32_t n = (uint32_t)(frame_off[blk + 1] - f0);
     ms_inverse_tile(blk, tile, it.channels, it.bit_depth, f0 - it.frame0, n, global_ptr(it.left), global_ptr(it.right), ms_flag,
                     status);
-}
-
-static void launch_ms_inverse(uint32_t num_blocks, int channels, int bit_depth, const unsigned long long* frame_off,
-                              int32_t* left, int32_t* right, const uint8_t* ms_flag, uint32_t* status, hipStream_t stream) {
-    hipLaunchKernelGGL(k_ms_inverse, dim3(num_blocks, kMaxBlock / 1024), dim3(256), 0, stream, channels, bit_depth, frame_off,
-                       left, right, ms_flag, status);
 }
 
 // The block that holds frame f: the regular layout (every block but the last 16384 frames) is a guess that one
@@ -639,9 +583,9 @@ __device__ __forceinline__ void pack24(int32_t a, int32_t b, int32_t c, int32_t 
 // samples arrive as one 16-byte load per channel.  Block boundaries may fall anywhere (non-final blocks of any length
 // from 256 frames on, odd ones included), so the block -- MS flag and status -- is looked up per frame; a unit spans at
 // most two blocks.  The last unit is written byte by byte and writes the RIFF pad byte when the data size is odd.
-// wav_data: the image's first byte (the 44-byte header is the host's).  wav_pack_unit is one thread's work (k_wav_pack,
-// k_wav_pack_batch): frame_off, ms_flag and status are the stream's own (num_blocks entries from its first block),
-// frame_base the value of frame_off[0].
+// wav_data: the image's first byte (the 44-byte header is the host's).  wav_pack_unit is one thread's work (k_wav_pack):
+// frame_off, ms_flag and status are the stream's own (num_blocks entries from its first block), frame_base the value of
+// frame_off[0].
 __device__ __forceinline__ void wav_pack_unit(unsigned long long f0, uint32_t num_blocks, int channels, int bit_depth,
                                               unsigned long long frames, const unsigned long long* __restrict__ frame_off,
                                               unsigned long long frame_base, const int32_t* __restrict__ left,
@@ -727,26 +671,15 @@ __device__ __forceinline__ void wav_pack_unit(unsigned long long f0, uint32_t nu
     if (f0 + nf == frames && ((frames * align) & 1ull)) dst[nf * align] = 0;  // RIFF pad byte
 }
 
-__global__ __launch_bounds__(256) void k_wav_pack(uint32_t num_blocks, int channels, int bit_depth, unsigned long long frames,
-                                                  const unsigned long long* __restrict__ frame_off,
-                                                  const int32_t* __restrict__ left, const int32_t* __restrict__ right,
-                                                  const uint8_t* __restrict__ ms_flag, uint32_t* __restrict__ status,
-                                                  uint8_t* __restrict__ wav_data) {
-    const unsigned long long f0 = 4ull * ((unsigned long long)blockIdx.x * 256u + threadIdx.x);
-    if (f0 >= frames) return;
-    wav_pack_unit(f0, num_blocks, channels, bit_depth, frames, frame_off, 0ull, left, right, ms_flag, status, wav_data);
-}
-
-// k_wav_pack over every item of a batch in one launch: thread u handles unit u of the concatenated unit ranges
-// (unit_off: [nitems + 1] prefix sums of the items' ceil(frames / 4)), found by a binary search there.  Each item's PCM
-// starts at a multiple of 4 frames and its image at a 16-byte boundary, so every unit keeps k_wav_pack's aligned 16-byte
-// loads and dword stores.  The search runs once per workgroup, on its first unit (uniform: scalar loads, and the item's
+// Every item of a batch in one launch: thread u handles unit u of the concatenated unit ranges (unit_off: [nitems + 1]
+// prefix sums of the items' ceil(frames / 4)), found by a binary search there.  Each item's PCM starts at a multiple of
+// 4 frames and its image at a 16-byte boundary, so every unit keeps the aligned 16-byte loads and dword stores.  The search runs once per workgroup, on its first unit (uniform: scalar loads, and the item's
 // descriptor in scalar registers); only a workgroup that spans items searches again per thread, among the later items.
-__global__ __launch_bounds__(256) void k_wav_pack_batch(uint32_t nitems, unsigned long long total_units,
-                                                        const unsigned long long* __restrict__ unit_off,
-                                                        const DecodeBatchItem* __restrict__ items,
-                                                        const unsigned long long* __restrict__ frame_off,
-                                                        const uint8_t* __restrict__ ms_flag, uint32_t* __restrict__ status) {
+__global__ __launch_bounds__(256) void k_wav_pack(uint32_t nitems, unsigned long long total_units,
+                                                  const unsigned long long* __restrict__ unit_off,
+                                                  const DecodeItem* __restrict__ items,
+                                                  const unsigned long long* __restrict__ frame_off,
+                                                  const uint8_t* __restrict__ ms_flag, uint32_t* __restrict__ status) {
     const unsigned long long first = (unsigned long long)blockIdx.x * 256u;
     uint32_t lo = 0, hi = nitems;  // unit_off[lo] <= first < unit_off[hi]
     while (hi - lo > 1u) {
@@ -757,7 +690,7 @@ __global__ __launch_bounds__(256) void k_wav_pack_batch(uint32_t nitems, unsigne
     const unsigned long long u = first + threadIdx.x;
     if (u >= total_units) return;
     if (unit_off[lo + 1] >= first + 256u) {  // (uniform) the whole workgroup lies in item lo
-        const DecodeBatchItem& it = items[lo];
+        const DecodeItem& it = items[lo];
         wav_pack_unit(4ull * (u - unit_off[lo]), it.blocks, it.channels, it.bit_depth, it.frames, frame_off + it.block0, it.frame0,
                       global_ptr(it.left), global_ptr(it.right), ms_flag + it.block0, status + it.block0, global_ptr(it.wav));
         return;
@@ -768,85 +701,33 @@ __global__ __launch_bounds__(256) void k_wav_pack_batch(uint32_t nitems, unsigne
         if (unit_off[mid] <= u) l2 = mid;
         else h2 = mid;
     }
-    const DecodeBatchItem& it = items[l2];
+    const DecodeItem& it = items[l2];
     wav_pack_unit(4ull * (u - unit_off[l2]), it.blocks, it.channels, it.bit_depth, it.frames, frame_off + it.block0, it.frame0,
                   global_ptr(it.left), global_ptr(it.right), ms_flag + it.block0, status + it.block0, global_ptr(it.wav));
 }
 
-static void launch_wav_pack(uint32_t num_blocks, int channels, int bit_depth, unsigned long long frames,
-                            const unsigned long long* frame_off, const int32_t* left, const int32_t* right,
-                            const uint8_t* ms_flag, uint32_t* status, uint8_t* wav_data, hipStream_t stream) {
-    const unsigned long long units = (frames + 3u) / 4u;
-    if (units == 0) return;
-    hipLaunchKernelGGL(k_wav_pack, dim3((uint32_t)((units + 255u) / 256u)), dim3(256), 0, stream, num_blocks, channels, bit_depth,
-                       frames, frame_off, left, right, ms_flag, status, wav_data);
-}
-
-// the pass after the block decode: k_ms_inverse in place, or k_wav_pack into a WAV image
-static void launch_post_decode(uint32_t num_blocks, int channels, int bit_depth, const unsigned long long* frame_off,
-                               int32_t* left, int32_t* right, const uint8_t* ms_flag, uint32_t* status, uint8_t* wav_data,
-                               unsigned long long frames, hipStream_t stream) {
-    if (wav_data)
-        launch_wav_pack(num_blocks, channels, bit_depth, frames, frame_off, left, right, ms_flag, status, wav_data, stream);
-    else
-        launch_ms_inverse(num_blocks, channels, bit_depth, frame_off, left, right, ms_flag, status, stream);
-}
-
-hipError_t launch_decode(uint32_t num_blocks, int channels, int stereo_mode, int bit_depth, const uint8_t* payload,
-                         const unsigned long long* byte_off, const unsigned long long* frame_off, int32_t* left,
-                         int32_t* right, uint32_t* status, uint8_t* ms_flag, hipStream_t stream, uint8_t* wav_data,
-                         unsigned long long frames) {
-    if (num_blocks == 0) return hipSuccess;
-    static const uint32_t lanes = [] {  // blocks per wave (see k_decode); LACX_DECODE_LANES: tuning knob, read once
-        if (const char* v = std::getenv("LACX_DECODE_LANES")) {  // 1, 2, 4, ... 64
-            const int x = std::atoi(v);
-            if (x >= 1 && x <= 64 && (x & (x - 1)) == 0) return (uint32_t)x;
-        }
-        return 64u;
-    }();
-    const size_t smem = kDecBytesPerCol * lanes;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decode), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)(kDecBytesPerCol * 64));
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_decode, dim3((num_blocks + lanes - 1) / lanes), dim3(kDecThreads), smem, stream, num_blocks, channels,
-                       stereo_mode, lanes, payload, byte_off, frame_off, left, right, status, ms_flag);
-    launch_post_decode(num_blocks, channels, bit_depth, frame_off, left, right, ms_flag, status, wav_data, frames, stream);
-    return hipGetLastError();
-}
-
-hipError_t launch_decode_serial(uint32_t num_blocks, int channels, int stereo_mode, int bit_depth, const uint8_t* payload,
-                                uint32_t payload_bits, const unsigned long long* frame_off, int32_t* left, int32_t* right,
-                                uint32_t* status, uint8_t* ms_flag, hipStream_t stream, uint8_t* wav_data,
-                                unsigned long long frames) {
-    if (num_blocks == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_decode_serial, dim3(1), dim3(kDecThreads), kDecBytesPerCol, stream, num_blocks, channels, stereo_mode,
-                       payload, payload_bits, frame_off, left, right, status, ms_flag);
-    launch_post_decode(num_blocks, channels, bit_depth, frame_off, left, right, ms_flag, status, wav_data, frames, stream);
-    return hipGetLastError();
-}
-
-hipError_t launch_decode_batch(const DecodeBatchArgs& a, hipStream_t stream) {
+hipError_t launch_decode(const DecodeArgs& a, hipStream_t stream) {
     const size_t smem = kDecBytesPerCol * kDecThreads;
     if (a.lanes) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decode_batch),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decode),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_decode_batch, dim3((a.lanes + kDecThreads - 1) / kDecThreads), dim3(kDecThreads), smem, stream,
+        hipLaunchKernelGGL(k_decode, dim3((a.lanes + kDecThreads - 1) / kDecThreads), dim3(kDecThreads), smem, stream,
                            a.lanes, a.lane_blk, a.blk_item, a.items, a.payload, a.byte_off, a.frame_off, a.status, a.ms_flag);
     }
     if (a.nv2) {  // version-2 items: a batch without any pays nothing for them
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decode_serial_batch),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decode_serial),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_decode_serial_batch, dim3((a.nv2 + kDecThreads - 1) / kDecThreads), dim3(kDecThreads), smem,
+        hipLaunchKernelGGL(k_decode_serial, dim3((a.nv2 + kDecThreads - 1) / kDecThreads), dim3(kDecThreads), smem,
                            stream, a.nv2, a.v2_items, a.items, a.payload, a.frame_off, a.status, a.ms_flag);
     }
     if (a.wav) {
         if (a.total_units)
-            hipLaunchKernelGGL(k_wav_pack_batch, dim3((uint32_t)((a.total_units + 255u) / 256u)), dim3(256), 0, stream, a.nitems,
+            hipLaunchKernelGGL(k_wav_pack, dim3((uint32_t)((a.total_units + 255u) / 256u)), dim3(256), 0, stream, a.nitems,
                                a.total_units, a.unit_off, a.items, a.frame_off, a.ms_flag, a.status);
     } else if (a.total_blocks) {
-        hipLaunchKernelGGL(k_ms_inverse_batch, dim3(a.total_blocks, kMaxBlock / 1024), dim3(256), 0, stream, a.blk_item, a.items,
+        hipLaunchKernelGGL(k_ms_inverse, dim3(a.total_blocks, kMaxBlock / 1024), dim3(256), 0, stream, a.blk_item, a.items,
                            a.frame_off, a.ms_flag, a.status);
     }
     return hipGetLastError();

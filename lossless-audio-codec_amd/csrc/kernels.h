@@ -173,28 +173,13 @@ hipError_t launch_stream_out(const LaunchSet& ls, const DeviceWorkspace& ws, uin
                              hipStream_t stream, const RangeProgress& rp = RangeProgress{},
                              const LaunchTuning& tune = LaunchTuning{});
 
-// The decoder (decode.hip): one lane per block; payload must be followed by kDecodeTailPad readable zero bytes (the bit
-// reader's bounded look-ahead past the last block, see BitIn).
+// The decoder (decode.hip): one job decodes a batch of streams (items; a single stream is a batch of one), one lane per
+// version-3 block and one per version-2 item.  The blocks of all items are numbered globally: byte_off / frame_off are
+// [total_blocks + 1] prefix sums over the concatenated payloads and frames; status[blk] = 0 or an error code and
+// ms_flag[blk] = the block's LR/MS flag, per global block.  The payload must be followed by kDecodeTailPad readable zero
+// bytes (the bit reader's bounded look-ahead past the last block, see BitIn).
 constexpr size_t kDecodeTailPad = 128;
-// The decoder's entry points:  byte_off / frame_off:
-// [num_blocks + 1] prefix sums of the block table; status[blk] = 0 or an error code, ms_flag[blk] = the block's LR/MS flag.
-// wav_data = nullptr: left / right end as the decoded PCM (k_ms_inverse in place).  Otherwise the first byte of a WAV
-// image of 44 + data + pad bytes (4-byte aligned; the header is the caller's) whose data region receives the `frames`
-// frames interleaved and narrowed to the bit depth (k_wav_pack); left / right then hold the pre-inverse samples.
-hipError_t launch_decode(uint32_t num_blocks, int channels, int stereo_mode, int bit_depth, const uint8_t* payload,
-                         const unsigned long long* byte_off, const unsigned long long* frame_off, int32_t* left,
-                         int32_t* right, uint32_t* status, uint8_t* ms_flag, hipStream_t stream, uint8_t* wav_data = nullptr,
-                         unsigned long long frames = 0);
-
-// The legacy version-2 container (no compressed block sizes): one lane walks the whole payload.
-hipError_t launch_decode_serial(uint32_t num_blocks, int channels, int stereo_mode, int bit_depth, const uint8_t* payload,
-                                uint32_t payload_bits, const unsigned long long* frame_off, int32_t* left, int32_t* right,
-                                uint32_t* status, uint8_t* ms_flag, hipStream_t stream, uint8_t* wav_data = nullptr,
-                                unsigned long long frames = 0);
-
-// Many streams as one decode (launch_decode_batch).  The blocks of all items are numbered globally: byte_off / frame_off are
-// [total_blocks + 1] prefix sums over the concatenated payloads and frames, status / ms_flag per global block.
-struct DecodeBatchItem {
+struct DecodeItem {
     int32_t* left;                // the item's PCM from its frame 0 (16-byte aligned in the WAV form)
     int32_t* right;               // null for mono
     uint8_t* wav;                 // WAV form: the item's image (16-byte aligned; header is the host's), else null
@@ -205,27 +190,27 @@ struct DecodeBatchItem {
     uint32_t pay_bits;            // version 2 only: payload bits
     uint8_t channels, stereo_mode, bit_depth, version;
 };
-struct DecodeBatchArgs {
+struct DecodeArgs {
     uint32_t nitems = 0, total_blocks = 0;
-    const DecodeBatchItem* items = nullptr;
+    const DecodeItem* items = nullptr;
     const uint32_t* blk_item = nullptr;       // [total_blocks] the item of every block
-    // k_decode_batch: lane g decodes block lane_blk[g] (~0u: idle); only version-3 blocks, an item's in consecutive lanes
+    // k_decode: lane g decodes block lane_blk[g] (~0u: idle); only version-3 blocks, an item's in consecutive lanes
     uint32_t lanes = 0;
     const uint32_t* lane_blk = nullptr;
-    uint32_t nv2 = 0;                         // version-2 items, one lane each (k_decode_serial_batch)
+    uint32_t nv2 = 0;                         // version-2 items, one lane each (k_decode_serial)
     const uint32_t* v2_items = nullptr;
     const uint8_t* payload = nullptr;         // followed by kDecodeTailPad zero bytes
     const unsigned long long* byte_off = nullptr;
     const unsigned long long* frame_off = nullptr;
     uint32_t* status = nullptr;
     uint8_t* ms_flag = nullptr;
-    // wav = false: k_ms_inverse_batch in place into every item's left / right; true: k_wav_pack_batch into the items'
+    // wav = false: k_ms_inverse in place into every item's left / right; true: k_wav_pack into the items'
     // images (unit_off: [nitems + 1] prefix sums of ceil(frames / 4)), left / right then hold the pre-inverse samples
     bool wav = false;
     const unsigned long long* unit_off = nullptr;
     unsigned long long total_units = 0;
 };
-hipError_t launch_decode_batch(const DecodeBatchArgs& args, hipStream_t stream);
+hipError_t launch_decode(const DecodeArgs& args, hipStream_t stream);
 
 // Block::Encoder::encode's analysis for one block of arbitrary int32 samples (wide.hip): d_res = scratch for the eleven
 // candidate residuals ([11][kMaxBlock] int32), d_plan receives the plan.

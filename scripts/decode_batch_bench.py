@@ -4,7 +4,7 @@ GPU.  After a warm-up, best / median of `iters` rounds of:
   kernel ms (events) of Decoder.decode_wav_batch_view over all streams, of the same with every stream's lanes padded to
     a wave boundary (LACX_DECODE_BATCH_PAD=1), and of Decoder.decode_wav_view of the first stream alone;
   wall ms of decode_wav_batch_view against n sequential decode_wav_view calls on a warmed handle.
-Every image's sha256 is checked against the canonical WAV of its input PCM.  k_wav_pack_batch's bytes are printed for
+Every image's sha256 is checked against the canonical WAV of its input PCM.  k_wav_pack's bytes are printed for
 the profile (rocprofv3 --kernel-trace --stats, in a run of its own, gives its time).
 usage: decode_batch_bench.py [n] [iters] [seconds]"""
 import hashlib
@@ -85,5 +85,5 @@ print(f"  kernels  batch {best['k_batch']:.2f} / {med['k_batch']:.2f} ms   batch
       f"   ratio {med['k_batch'] / med['k_one']:.2f}")
 print(f"  wall     decode_wav_batch_view {best['w_batch']:.1f} / {med['w_batch']:.1f} ms   {n} x decode_wav_view "
       f"{best['w_seq']:.1f} / {med['w_seq']:.1f} ms   speed-up {med['w_seq'] / med['w_batch']:.1f}x")
-print(f"  k_wav_pack_batch moves {pack_read / 1e9:.3f} GB read + {pack_write / 1e9:.3f} GB written "
+print(f"  k_wav_pack moves {pack_read / 1e9:.3f} GB read + {pack_write / 1e9:.3f} GB written "
       f"(at 8 TB/s: {(pack_read + pack_write) / 8e12 * 1e3:.3f} ms)")

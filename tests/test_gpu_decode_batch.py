@@ -1,7 +1,8 @@
 """Many .lac streams as one decode on the MI355X (lacx_decoder_decode_wav_batch*, lacx_decoder_decode_batch_device): the
 pinned reference WAV images of tests/golden/decode_wav.json in one call, every format mixed in one batch, failures that
 stay with their item, device-resident outputs, batches larger than one resident round of lanes, and a handle shared by
-batch and single-stream calls.  Every item must equal what the single-stream decoders give for it alone."""
+batch and single-stream calls.  Every item must equal what the single-stream decoders give for it alone (a batch of one)
+and an answer that does not come from the decoder: the pinned reference bytes, or the canonical WAV of the encoded PCM."""
 import hashlib
 import json
 import os
@@ -62,6 +63,7 @@ def test_pinned_reference_wavs_in_one_batch(gpu):
     got = dec.decode_wav_batch(lacs)
     assert [(len(w), _sha(w)) for w in got] == [(e["wav_bytes"], e["wav_sha256"]) for e in ents]
     single = [dec.decode_wav(x) for x in lacs]
+    assert [(len(w), _sha(w)) for w in single] == [(e["wav_bytes"], e["wav_sha256"]) for e in ents]
     # shuffled, with duplicates, and one at a time
     rng = random.Random(7)
     order = list(range(len(lacs))) + [3, 3, 0, 25, 11]
@@ -74,8 +76,9 @@ def test_pinned_reference_wavs_in_one_batch(gpu):
 
 
 def _mixed_streams(gpu):
-    """Every rate, both depths, mono and stereo, LR / MS / auto, 1 frame to several blocks, and version-2 rewrites."""
-    out = []
+    """Every rate, both depths, mono and stereo, LR / MS / auto, 1 frame to several blocks, and version-2 rewrites:
+    (streams, the canonical WAV of each stream's encoded PCM)."""
+    out, wavs = [], []
     k = 0
     for rate in (44100, 48000, 96000, 192000):
         for bd in (16, 24):
@@ -84,24 +87,28 @@ def _mixed_streams(gpu):
                 kind = ("music", "mixed", "noise", "sparse", "tone")[k % 5]
                 left, right = gpu.synth.synth_pcm(frames, ch, bd, rate, seed=300 + k, kind=kind)
                 lac = gpu.lacx.Encoder(12, sm, rate, bd, device=0).encode(left, right)
+                wav = W.make_wav(left, right, rate, bd)
                 out.append(lac)
+                wavs.append(wav)
                 if k % 5 == 0:
                     out.append(lacstreams.to_v2(lac))
+                    wavs.append(wav)
                 k += 1
-    return out
+    return out, wavs
 
 
 def test_mixed_formats(gpu):
-    lacs = _mixed_streams(gpu)
+    lacs, wavs = _mixed_streams(gpu)
     assert len(lacs) >= 38
     dec = gpu.lacx.Decoder(device=0)
     got = dec.decode_wav_batch(lacs)
     views = [bytes(v) for v in dec.decode_wav_batch_view(lacs)]
     for i, lac in enumerate(lacs):
-        left, right, info, _ = gpu.lacx.decode(lac)
-        want = W.make_wav(left, right, info.sample_rate, info.bit_depth)
+        want = wavs[i]
         assert got[i] == want and views[i] == want, i
         assert dec.decode_wav(lac) == want, i
+        left, right, info, _ = gpu.lacx.decode(lac)
+        assert W.make_wav(left, right, info.sample_rate, info.bit_depth) == want, i
     dec.close()
 
 
@@ -125,18 +132,21 @@ def _bad_items(gpu):
 
 
 def test_failures_stay_local(gpu):
-    good = _mixed_streams(gpu)[:12]
+    good, good_wavs = (x[:12] for x in _mixed_streams(gpu))
     bad = _bad_items(gpu)
-    lacs = list(good)
+    lacs, wavs = list(good), list(good_wavs)
     where = {}
     for j, (name, b) in enumerate(bad):
         at = 3 + 4 * j
         lacs.insert(at, b)
+        wavs.insert(at, None)
         where[at] = name
     dec = gpu.lacx.Decoder(device=0)
     want_err = {i: _single_error(gpu, lacs[i]) for i in where}
+    assert all(m.startswith("[decode-error] ") for m in want_err.values()), want_err
     assert "sample outside the bit depth" in want_err[[i for i, n in where.items() if n == "loud"][0]]
     singles = {i: dec.decode_wav(x) for i, x in enumerate(lacs) if i not in where}
+    assert all(singles[i] == wavs[i] for i in singles)
     for fn in (dec.decode_wav_batch, dec.decode_wav_batch_view):
         with pytest.raises(gpu.lacx.BatchDecodeError) as e:
             fn(lacs)
@@ -180,7 +190,7 @@ def _device_outputs(torch, infos, extra=64):
 
 def test_device_output(gpu):
     import torch
-    lacs = _mixed_streams(gpu)[:20]
+    lacs = _mixed_streams(gpu)[0][:20]
     bad = _bad_items(gpu)
     lacs.insert(5, bad[2][1])  # loud: parses, fails on the device
     lacs.insert(9, bad[0][1])  # damaged payload
@@ -257,15 +267,28 @@ def test_more_blocks_than_one_resident_round(gpu):
     dec.close()
 
 
+def _host_decode(gpu, dec, lac, left, right):
+    """lacx_decoder_decode into caller-owned host arrays: the return code."""
+    import ctypes as C
+
+    buf = np.frombuffer(lac, dtype=np.uint8)
+    i32 = C.POINTER(C.c_int32)
+    return gpu.lacx.lib().lacx_decoder_decode(dec._h, buf.ctypes.data_as(C.POINTER(C.c_uint8)), C.c_uint64(buf.size),
+                                              left.ctypes.data_as(i32), right.ctypes.data_as(i32), C.c_uint64(left.size),
+                                              None)
+
+
 def test_handle_reuse(gpu):
     left, right = gpu.synth.synth_pcm(256, 2, 16, 48000, seed=77, kind="music")
     big = [_repeat_block(gpu.lacx.Encoder(12, 2, 48000, 16, device=0).encode(left, right), 3000)] * 4
-    small = _mixed_streams(gpu)[:6]
+    small, small_wavs = (x[:6] for x in _mixed_streams(gpu))
     lone_l, lone_r = gpu.synth.synth_pcm(5 * 16384 + 3, 2, 24, 96000, seed=78, kind="mixed")
     lone = gpu.lacx.Encoder(12, 2, 96000, 24, device=0).encode(lone_l, lone_r)
     fresh = gpu.lacx.Decoder(device=0)
     want_big = fresh.decode_wav(big[0])
+    assert want_big == W.make_wav(np.tile(left, 3000), np.tile(right, 3000), 48000, 16)
     want_small = [fresh.decode_wav(x) for x in small]
+    assert want_small == small_wavs
     fresh.close()
     dec = gpu.lacx.Decoder(device=0)
     assert [bytes(v) for v in dec.decode_wav_batch_view(big)] == [want_big] * 4
@@ -275,4 +298,36 @@ def test_handle_reuse(gpu):
     assert np.array_equal(l, lone_l) and np.array_equal(r, lone_r)
     assert dec.decode_wav_batch(small + [lone]) == want_small + [W.make_wav(lone_l, lone_r, 96000, 24)]
     assert [bytes(v) for v in dec.decode_wav_batch_view(big[:1] + small[:1])] == [want_big, want_small[0]]
+    # single calls are batches of one but leave lacx_decoder_item_error to the last batch call
+    bad = dict(_bad_items(gpu))
+    items = small[:3] + [bad["loud"]] + small[3:]
+    with pytest.raises(gpu.lacx.BatchDecodeError) as e:
+        dec.decode_wav_batch(items)
+    assert set(e.value.errors) == {3} and "sample outside the bit depth" in e.value.errors[3]
+    batch_msgs = [e.value.errors.get(i, "") for i in range(len(items))]
+    L = gpu.lacx.lib()
+
+    def item_errors():
+        return [L.lacx_decoder_item_error(dec._h, i).decode() for i in range(len(items))]
+
+    assert item_errors() == batch_msgs
+    l, r, _, _ = dec.decode(lone)
+    assert np.array_equal(l, lone_l) and np.array_equal(r, lone_r)
+    with pytest.raises(RuntimeError) as single:
+        dec.decode_wav(bad["damaged"])
+    assert str(single.value).startswith("[decode-error] block=")  # the item's own message, no "stream 0: "
+    assert item_errors() == batch_msgs
+    # a failing single decode leaves the caller's arrays as they were: parse errors, and failures on the device
+    info = gpu.lacx.stream_parse(bad["loud"])
+    for lac in (bad["loud"], bad["damaged"], bad["truncated"]):
+        sl = np.full(info.frames, 0x5A5A5A5A, dtype=np.int32)
+        sr = np.full(info.frames, 0x5A5A5A5A, dtype=np.int32)
+        rc = _host_decode(gpu, dec, lac, sl, sr)
+        assert rc in (gpu.lacx.E_RUNTIME, gpu.lacx.E_INVALID)
+        assert L.lacx_decode_last_error().decode().startswith("[decode-error] ")
+        assert (sl == 0x5A5A5A5A).all() and (sr == 0x5A5A5A5A).all()
+    assert item_errors() == batch_msgs
+    sl, sr = np.zeros(lone_l.size, dtype=np.int32), np.zeros(lone_l.size, dtype=np.int32)
+    assert _host_decode(gpu, dec, lone, sl, sr) == gpu.lacx.OK
+    assert np.array_equal(sl, lone_l) and np.array_equal(sr, lone_r)
     dec.close()

@@ -76,10 +76,10 @@ def test_wav_lac_wav_identity(gpu, ch, bd):
 
 def _sweep_streams(gpu):
     """About forty streams: materials, depths, stereo modes, odd lengths, spliced streams with odd non-final blocks, and
-    version-2 rewrites."""
+    version-2 rewrites: (streams, the canonical WAV of each stream's encoded PCM)."""
     rng = np.random.default_rng(4242)
     kinds = ("music", "mixed", "noise", "tone", "sparse", "walk", "silence")
-    out = []
+    out, wavs = [], []
     for i in range(28):
         ch = int(rng.integers(1, 3))
         bd = int(rng.choice([16, 24]))
@@ -89,24 +89,28 @@ def _sweep_streams(gpu):
         left, right = gpu.synth.synth_pcm(frames, ch, bd, rate, seed=1000 + i, kind=kinds[i % len(kinds)])
         lac = gpu.lacx.Encoder(12, sm, rate, bd, device=0).encode(left, right)
         out.append(lac)
+        wavs.append(W.make_wav(left, right, rate, bd))
         if i % 4 == 0:
             out.append(lacstreams.to_v2(lac))
+            wavs.append(wavs[-1])
         if i % 3 == 0 and frames > 257:
             # an odd-length first block: a stream of n frames spliced in front of the stream
             n = 2 * int(rng.integers(128, 8192)) + 1  # 257 .. 16383
             l2, r2 = gpu.synth.synth_pcm(n, ch, bd, rate, seed=2000 + i, kind="mixed")
             head = gpu.lacx.Encoder(12, sm, rate, bd, device=0).encode(l2, r2)
             out.append(lacstreams.splice(head, lac))
-    return out
+            wavs.append(W.make_wav(np.concatenate([l2, left]), None if ch == 1 else np.concatenate([r2, right]), rate, bd))
+    return out, wavs
 
 
 def test_agrees_with_the_pcm_decoder(gpu):
     dec = gpu.lacx.Decoder(device=0)
-    streams = _sweep_streams(gpu)
+    streams, wavs = _sweep_streams(gpu)
     assert len(streams) >= 38
     for k, lac in enumerate(streams):
         left, right, info, _ = gpu.lacx.decode(lac)
         want = W.make_wav(left, right, info.sample_rate, info.bit_depth)
+        assert want == wavs[k], k
         assert dec.decode_wav(lac) == want, k
         assert bytes(dec.decode_wav_view(lac)) == want, k
     dec.close()
