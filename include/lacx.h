@@ -30,6 +30,7 @@
  *                                                            src/codec/block/decoder.cpp:64-520
  *   lacx_decoder_decode_wav <- the `decode` command's WAV writer ref src/main.cpp:127-182, 184-431
  *   lacx_decoder_decode_wav_batch_view, lacx_decoder_decode_batch_device <- many .lac streams as one device job
+ *   lacx_decoder_decode_window, lacx_decoder_decode_window_batch_device <- frame windows of many streams as one job
  *
  * All analysis (and the decode) runs in hand-written HIP kernels on a gfx950 device; there is no CPU fallback: every
  * call that needs the device fails with LACX_E_DEVICE when none is usable.
@@ -132,7 +133,7 @@ void lacx_get_timing(const lacx_encoder* enc, lacx_timing* out);
 
 /* sizeof() of a public struct as this library was built, by name without the prefix ("config", "channel_plan",
  * "block_plan", "timing", "pcm", "batch_item", "batch_out", "wav_info", "fanout_shard", "fanout_out", "fanout_stats",
- * "stream_info", "span", "decode_item"); 0 for an unknown name.  A binding that declares the structs itself (ctypes, cgo, JNI) checks its layout
+ * "stream_info", "span", "decode_item", "window_item"); 0 for an unknown name.  A binding that declares the structs itself (ctypes, cgo, JNI) checks its layout
  * against this before the first call that fills one. */
 uint32_t lacx_sizeof(const char* struct_name);
 
@@ -400,6 +401,41 @@ typedef struct lacx_decode_item {
 int lacx_decoder_decode_batch_device(lacx_decoder* dec, const lacx_decode_item* items, uint32_t n, void* stream,
                                      int* item_rc, float* device_ms);
 const char* lacx_decoder_item_error(const lacx_decoder* dec, uint32_t i);
+
+/* Frame windows: frames [start, start + frames) of each item, for a seek, a preview or random crops of a collection.
+ * Every block decodes on its own (raw warm-up samples, fresh Rice state), so of a version-3 stream only the blocks that
+ * overlap the window are decoded, and only their bytes cross PCIe; a batch of windows is one job of about one block's
+ * serial chain.  Those blocks decode whole and all of their samples are checked against the bit depth: a window fails
+ * if and only if one of its blocks would fail in a full decode, with the message the full decode gives for the lowest
+ * failing block among them ("[decode-error] block=N ...", N counted in the stream); a damaged block outside the window
+ * does not matter.  A version-2 stream has no compressed block sizes: it is decoded in full by one lane and then
+ * windowed, at the cost of a full serial decode, and any of its blocks fails it.
+ * Samples: LACX_SAMPLE_I32 the stream's integer samples, LACX_SAMPLE_F32 sample * 2^-(bit_depth - 1) (exact for 16- and
+ * 24-bit samples).  The outputs need only 4-byte alignment; nothing outside [0, frames) is written, and a mono item's
+ * right array is neither needed nor written.  Before any device call each item is parsed (lacx_stream_parse) and its
+ * window and arrays checked: frames = 0 gives "empty window", start + frames beyond the stream (checked without
+ * wrap-around) "window outside the stream", a missing array "output arrays missing", each LACX_E_INVALID.  An unknown
+ * sample type, n = 0 or a null array fail the whole call with LACX_E_INVALID.
+ * lacx_decoder_decode_window_batch_device: caller-owned device arrays on the decoder's device; per-item outcome, return
+ * code, device-less behaviour and `stream` as lacx_decoder_decode_batch_device.  The arrays of a failed item hold
+ * unspecified samples.
+ * lacx_decoder_decode_window: one window into caller-owned host arrays, a batch of one: the window is copied to them
+ * only once it has decoded, so a failing call leaves them untouched; its message carries no "stream 0: ".
+ * device_ms (nullable): kernel time. */
+#define LACX_SAMPLE_I32 0 /* int32, the stream's integer samples */
+#define LACX_SAMPLE_F32 1 /* float32, sample * 2^-(bit_depth - 1): exact for 16- and 24-bit samples */
+typedef struct lacx_window_item {
+    const uint8_t* lac;
+    uint64_t size;
+    uint64_t start;  /* first frame of the window */
+    uint64_t frames; /* >= 1, start + frames <= the stream's frame count */
+    void* left;      /* `frames` samples of the call's sample type */
+    void* right;     /* stereo only; ignored for a mono item, whose right array is never written */
+} lacx_window_item;
+int lacx_decoder_decode_window_batch_device(lacx_decoder* dec, const lacx_window_item* items, uint32_t n, int sample_type,
+                                            void* stream, int* item_rc, float* device_ms);
+int lacx_decoder_decode_window(lacx_decoder* dec, const uint8_t* lac, uint64_t size, uint64_t start, uint64_t frames,
+                               int sample_type, void* left, void* right, float* device_ms);
 
 /* Block::Encoder::encode drop-in for one channel block of n <= 16384 samples of ANY int32 value: blocks inside the 25-bit
  * mid/side domain of validated 16 / 24-bit input run on the streaming kernels, wider ones on a kernel of their own that

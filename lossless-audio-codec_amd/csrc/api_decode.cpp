@@ -75,6 +75,8 @@ struct lacx_decoder {
     hipEvent_t e0 = nullptr, e1 = nullptr;
     uint8_t* d_pay = nullptr;
     uint64_t pay_cap = 0;
+    uint8_t* h_pay = nullptr;  // pinned: the window form's payload ranges, gathered for one H2D copy
+    uint64_t h_pay_cap = 0;
     int32_t *d_left = nullptr, *d_right = nullptr;
     uint64_t pcm_cap = 0;
     uint32_t* d_status = nullptr;
@@ -98,6 +100,7 @@ void decoder_release(lacx_decoder* d) {
     if (d->e1) (void)hipEventDestroy(d->e1);
     if (d->stream) (void)hipStreamDestroy(d->stream);
     if (d->d_pay) (void)hipFree(d->d_pay);
+    if (d->h_pay) (void)hipHostFree(d->h_pay);
     if (d->d_left) (void)hipFree(d->d_left);
     if (d->d_right) (void)hipFree(d->d_right);
     if (d->d_status) (void)hipFree(d->d_status);
@@ -186,6 +189,42 @@ hipError_t grow_payload(lacx_decoder* d, uint64_t pay, const char** what) {  // 
     if (e == hipSuccess) d->pay_cap = cap;
     return e;
 }
+hipError_t grow_pay_stage(lacx_decoder* d, uint64_t pay, const char** what) {  // pinned twin of the payload buffer
+    if (pay <= d->h_pay_cap) return hipSuccess;
+    if (d->h_pay) (void)hipHostFree(d->h_pay);
+    d->h_pay = nullptr;
+    d->h_pay_cap = 0;
+    const uint64_t cap = pay + pay / 8 + 4096;
+    *what = "hipHostMalloc(payload stage)";
+    const hipError_t e = hipHostMalloc((void**)&d->h_pay, cap, 0);
+    if (e == hipSuccess) d->h_pay_cap = cap;
+    return e;
+}
+// dst[off[j], off[j] + bytes[j]) = src[j][0, bytes[j]) for every j, the destination split into equal byte ranges over up
+// to 8 threads (the calling thread takes the first): a window batch is many short ranges of different streams, which as
+// one pageable copy each would cost 10-20 us apiece in the runtime.
+void gather_ranges(uint8_t* dst, const std::vector<const uint8_t*>& src, const std::vector<uint64_t>& off,
+                   const std::vector<uint64_t>& bytes, uint64_t total) {
+    const unsigned hw = std::thread::hardware_concurrency();
+    const unsigned nt = total < (8u << 20) ? 1u : std::max(1u, std::min(8u, hw));
+    auto part = [&](unsigned t) {
+        const uint64_t lo = total * t / nt, hi = total * (t + 1) / nt;
+        for (size_t j = 0; j < src.size(); ++j) {
+            const uint64_t a = std::max(lo, off[j]), b = std::min(hi, off[j] + bytes[j]);
+            if (a < b) std::memcpy(dst + a, src[j] + (a - off[j]), b - a);
+        }
+    };
+    std::vector<std::thread> pool;
+    unsigned t = 1;
+    try {
+        for (; t < nt; ++t) pool.emplace_back(part, t);
+    } catch (...) {  // no thread to be had: the calling thread copies what is left
+        for (unsigned u = t; u < nt; ++u) part(u);
+    }
+    part(0);
+    for (auto& th : pool) th.join();
+}
+
 hipError_t grow_blocks(lacx_decoder* d, uint32_t nb, const char** what) {
     if (nb <= d->blocks_cap) return hipSuccess;
     if (d->d_status) (void)hipFree(d->d_status);
@@ -235,13 +274,15 @@ const char* block_error(uint32_t st) {
     return st < 10 ? kWhat[st] : "?";
 }
 
-// One item of a decode: the stream, and for the device and host forms the caller's output arrays.
+// One item of a decode: the stream, and for the device and host forms the caller's output arrays.  The window form
+// (decode_batch_run's `window` >= 0): frames [start, start + frames) of the stream, as that sample type.
 struct BatchIn {
     const uint8_t* lac;
     uint64_t size;
     int32_t* left;
     int32_t* right;
     uint64_t frames;
+    uint64_t start = 0;
 };
 
 // Where the decoded items go.  wav: the images into the decoder's pinned image buffer (out[i]: each item's, 16-byte
@@ -255,17 +296,27 @@ enum class DecodeTo { wav, device, host };
 // version-2 item, then one post pass over all of them.  Per item, code[i] and err[i] ("" = decoded): the message its
 // decode gives.  Returns LACX_OK, or LACX_E_DEVICE for a failure of the whole call (every item that parsed then carries
 // it).  The caller decides what the outcome becomes: the batch entry points keep it in d->item_err.
+// window = LACX_SAMPLE_I32 / _F32 (device or host form): each item's window only.  A version-3 item then
+// covers just the blocks that overlap its window -- only their bytes are uploaded, they decode whole into the decoder's
+// PCM buffers (scratch) and are all checked, and k_window_out writes the window's frames out; a version-2 item (no
+// compressed sizes) decodes in full and is then windowed.  The host form's windows go through the decoder's image
+// buffer, copied to the caller once the statuses are checked.
 int decode_batch_run(lacx_decoder* d, const BatchIn* in, uint32_t n, DecodeTo to, hipStream_t stream, lacx_span* out,
-                     std::vector<int>& code, std::vector<std::string>& err, float* device_ms) {
+                     std::vector<int>& code, std::vector<std::string>& err, float* device_ms, int window = -1) {
     if (device_ms) *device_ms = 0.f;
-    const bool wav = to == DecodeTo::wav, own_pcm = to != DecodeTo::device;  // own_pcm: into d->d_left / d_right
+    const bool wav = to == DecodeTo::wav, own_pcm = to != DecodeTo::device || window >= 0;  // own_pcm: into d->d_left / d_right
     code.assign(n, LACX_OK);
     err.assign(n, std::string());
     std::vector<lacx_stream_info> info(n);
     for (uint32_t i = 0; i < n; ++i) {
         if (out) out[i] = lacx_span{nullptr, 0};
         int c = lacx_stream_parse(in[i].lac, in[i].size, &info[i]);
-        if (c == LACX_OK && !wav) {  // lacx_decoder_decode's checks of the output arrays
+        if (c == LACX_OK && window >= 0) {  // the window inside the stream (no wrap-around), then the output arrays
+            const uint64_t total = info[i].frames;
+            if (in[i].frames == 0) c = decode_fail(LACX_E_INVALID, "empty window");
+            else if (in[i].start >= total || in[i].frames > total - in[i].start) c = decode_fail(LACX_E_INVALID, "window outside the stream");
+            else if (!in[i].left || (info[i].channels == 2 && !in[i].right)) c = decode_fail(LACX_E_INVALID, "output arrays missing");
+        } else if (c == LACX_OK && !wav) {  // lacx_decoder_decode's checks of the output arrays
             if (!in[i].left || (info[i].channels == 2 && !in[i].right)) c = decode_fail(LACX_E_INVALID, "output arrays missing");
             else if (in[i].frames != info[i].frames)
                 c = decode_fail(LACX_E_INVALID, "output arrays do not match the stream's frame count");
@@ -281,16 +332,49 @@ int decode_batch_run(lacx_decoder* d, const BatchIn* in, uint32_t n, DecodeTo to
     std::vector<uint64_t> pcm_at, wav_at, image_size;
     uint64_t total_blocks = 0, total_frames = 0, total_pay = 0, total_units = 0, pcm_total = 0, image_total = 0;
     uint32_t v3_blocks = 0;
+    // what an item decodes: its blocks from blk_first on, and their payload bytes from pay_src on (both 0 and the whole
+    // stream but in the window form); win: the window form's outputs, win_at: the host form's place in d->d_wav
+    std::vector<uint32_t> blk_first;
+    std::vector<uint64_t> pay_src, pay_bytes, win_at;
+    std::vector<WindowOut> win;
     for (uint32_t i = 0; i < n; ++i) {
         if (code[i] != LACX_OK) continue;
         const lacx_stream_info& f = info[i];
         const uint64_t head = 14 + (f.version == 2 ? 4ull : 8ull) * f.blocks;
+        uint32_t b0 = 0, nb = f.blocks;
+        uint64_t src = 0, bytes = in[i].size - head, frames = f.frames, fr0 = 0;
+        if (window >= 0 && f.version != 2) {  // the blocks [b0, b0 + nb) that hold the window's first and last frames
+            const uint64_t last = in[i].start + in[i].frames - 1;
+            uint64_t fr = 0, by = 0;
+            for (uint32_t b = 0;; ++b) {  // (the parse guarantees that the window's last frame lies in a block)
+                const uint32_t nfr = be32(in[i].lac + 14 + 8ull * b), nby = be32(in[i].lac + 18 + 8ull * b);
+                if (fr <= in[i].start && in[i].start < fr + nfr) b0 = b, src = by, fr0 = fr;
+                if (last < fr + nfr) {
+                    nb = b + 1 - b0;
+                    bytes = by + nby - src;
+                    frames = fr + nfr - fr0;
+                    break;
+                }
+                fr += nfr;
+                by += nby;
+            }
+        }
+        if (window >= 0) {
+            const uint64_t out_words = in[i].frames * f.channels;  // the host form's staging: left, then right
+            win.push_back(WindowOut{in[i].left, f.channels == 2 ? in[i].right : nullptr, in[i].start - fr0, in[i].frames});
+            win_at.push_back(image_total);
+            image_total += 4 * out_words;
+            total_units += (frames + 3u) / 4u;
+        }
+        blk_first.push_back(b0);
+        pay_src.push_back(src);
+        pay_bytes.push_back(bytes);
         DecodeItem x{};
         x.frame0 = total_frames;
-        x.frames = f.frames;
+        x.frames = frames;
         x.pay_off = total_pay;
         x.block0 = (uint32_t)total_blocks;
-        x.blocks = f.blocks;
+        x.blocks = nb;
         x.pay_bits = f.version == 2 ? (uint32_t)(8ull * (in[i].size - head)) : 0u;  // < 2^32: lacx_stream_parse
         x.channels = f.channels;
         x.stereo_mode = f.stereo_mode;
@@ -298,7 +382,7 @@ int decode_batch_run(lacx_decoder* d, const BatchIn* in, uint32_t n, DecodeTo to
         x.version = f.version;
         if (own_pcm) {  // offsets for now, pointers once the buffers exist
             pcm_at.push_back(pcm_total);
-            pcm_total += (f.frames + 3u) & ~3ull;  // every item's PCM from a multiple of 4 frames: 16-byte loads
+            pcm_total += (frames + 3u) & ~3ull;  // every item's PCM from a multiple of 4 frames: 16-byte loads
         }
         if (wav) {
             uint8_t hdr[44];
@@ -312,10 +396,10 @@ int decode_batch_run(lacx_decoder* d, const BatchIn* in, uint32_t n, DecodeTo to
             x.left = in[i].left;
             x.right = f.channels == 2 ? in[i].right : nullptr;
         }
-        total_blocks += f.blocks;
-        total_frames += f.frames;
-        total_pay += in[i].size - head;
-        if (f.version != 2) v3_blocks += f.blocks;
+        total_blocks += nb;
+        total_frames += frames;
+        total_pay += bytes;
+        if (f.version != 2) v3_blocks += nb;
         dev.push_back(i);
         it.push_back(x);
     }
@@ -356,11 +440,12 @@ int decode_batch_run(lacx_decoder* d, const BatchIn* in, uint32_t n, DecodeTo to
         const size_t o_items = 0, o_byte = (sizeof(DecodeItem) * m + 15u) & ~(size_t)15u;
         const size_t o_frame = o_byte + 8 * ((size_t)T + 1), o_unit = o_frame + 8 * ((size_t)T + 1);
         const size_t o_bitem = o_unit + 8 * ((size_t)m + 1), o_lane = o_bitem + 4 * (size_t)T;
-        const size_t o_v2 = o_lane + 4 * lane_blk.size(), meta = o_v2 + 4 * v2_items.size();
+        const size_t o_v2 = o_lane + 4 * lane_blk.size(), o_win = (o_v2 + 4 * v2_items.size() + 15u) & ~(size_t)15u;
+        const size_t meta = window >= 0 ? o_win + sizeof(WindowOut) * m : o_v2 + 4 * v2_items.size();  // | win [m]
         DEC_TRY(decoder_open(d, &prev_device, &what), what);
         DEC_TRY(grow_payload(d, total_pay, &what), what);
         DEC_TRY(grow_blocks(d, T, &what), what);
-        if (wav) DEC_TRY(grow_wav(d, image_total, &what), what);
+        if (wav || (window >= 0 && to == DecodeTo::host)) DEC_TRY(grow_wav(d, image_total, &what), what);
         if (own_pcm) DEC_TRY(grow_pcm(d, pcm_total, &what), what);
         if (meta > d->meta_cap) {
             if (d->d_meta) (void)hipFree(d->d_meta);
@@ -386,8 +471,9 @@ int decode_batch_run(lacx_decoder* d, const BatchIn* in, uint32_t n, DecodeTo to
                 const uint64_t entry = v2 ? 4u : 8u;
                 for (uint32_t b = 0; b < y.blocks; ++b) {
                     const uint32_t g = y.block0 + b;
-                    frame_off[g + 1] = frame_off[g] + be32(x.lac + 14 + entry * b);
-                    byte_off[g + 1] = v2 ? byte_off[g] : byte_off[g] + be32(x.lac + 18 + 8ull * b);
+                    const uint64_t sb = blk_first[j] + b;  // the block within the stream
+                    frame_off[g + 1] = frame_off[g] + be32(x.lac + 14 + entry * sb);
+                    byte_off[g + 1] = v2 ? byte_off[g] : byte_off[g] + be32(x.lac + 18 + 8ull * sb);
                     blk_item[g] = j;
                 }
                 if (v2) {  // the version-2 item's bytes count in the byte offsets as one lump at its last block
@@ -399,17 +485,34 @@ int decode_batch_run(lacx_decoder* d, const BatchIn* in, uint32_t n, DecodeTo to
                     y.right = y.channels == 2 ? d->d_right + pcm_at[j] : nullptr;
                 }
                 if (wav) y.wav = d->d_wav + wav_at[j];
+                if (window >= 0 && to == DecodeTo::host) {
+                    win[j].left = d->d_wav + win_at[j];
+                    win[j].right = y.channels == 2 ? d->d_wav + win_at[j] + 4 * win[j].frames : nullptr;
+                }
             }
+            if (window >= 0) std::memcpy(h + o_win, win.data(), sizeof(WindowOut) * m);
             std::memcpy(h + o_items, it.data(), sizeof(DecodeItem) * m);
             if (!lane_blk.empty()) std::memcpy(h + o_lane, lane_blk.data(), 4 * lane_blk.size());
             if (!v2_items.empty()) std::memcpy(h + o_v2, v2_items.data(), 4 * v2_items.size());
         }
         {
             DEC_TRY(hipMemcpyAsync(d->d_meta, d->h_meta, meta, hipMemcpyHostToDevice, st), "H2D batch tables");
-            for (uint32_t j = 0; j < m; ++j) {
-                const BatchIn& x = in[dev[j]];
-                const uint64_t head = 14 + (it[j].version == 2 ? 4ull : 8ull) * it[j].blocks;
-                DEC_TRY(hipMemcpyAsync(d->d_pay + it[j].pay_off, x.lac + head, x.size - head, hipMemcpyHostToDevice, st), "H2D payload");
+            if (window >= 0) {  // the windows' ranges through the pinned stage: one copy
+                DEC_TRY(grow_pay_stage(d, total_pay, &what), what);
+                std::vector<const uint8_t*> src(m);
+                std::vector<uint64_t> off(m);
+                for (uint32_t j = 0; j < m; ++j) {
+                    src[j] = in[dev[j]].lac + 14 + (info[dev[j]].version == 2 ? 4ull : 8ull) * info[dev[j]].blocks + pay_src[j];
+                    off[j] = it[j].pay_off;
+                }
+                gather_ranges(d->h_pay, src, off, pay_bytes, total_pay);
+                DEC_TRY(hipMemcpyAsync(d->d_pay, d->h_pay, total_pay, hipMemcpyHostToDevice, st), "H2D payload");
+            } else {
+                for (uint32_t j = 0; j < m; ++j) {
+                    const BatchIn& x = in[dev[j]];
+                    const uint64_t head = 14 + (it[j].version == 2 ? 4ull : 8ull) * it[j].blocks;
+                    DEC_TRY(hipMemcpyAsync(d->d_pay + it[j].pay_off, x.lac + head, x.size - head, hipMemcpyHostToDevice, st), "H2D payload");
+                }
             }
             DEC_TRY(hipMemsetAsync(d->d_pay + total_pay, 0, kDecodeTailPad, st), "memset");  // the bit reader's look-ahead
             DecodeArgs a;
@@ -430,6 +533,8 @@ int decode_batch_run(lacx_decoder* d, const BatchIn* in, uint32_t n, DecodeTo to
             a.wav = wav;
             a.unit_off = reinterpret_cast<const unsigned long long*>(dm + o_unit);
             a.total_units = total_units;
+            if (window >= 0) a.window = reinterpret_cast<const WindowOut*>(dm + o_win);
+            a.f32 = window == LACX_SAMPLE_F32;
             DEC_TRY(hipEventRecord(d->e0, st), "event record");
             DEC_TRY(launch_decode(a, st), "decode launch");
             DEC_TRY(hipEventRecord(d->e1, st), "event record");
@@ -445,7 +550,7 @@ int decode_batch_run(lacx_decoder* d, const BatchIn* in, uint32_t n, DecodeTo to
                 const uint32_t sv = d->h_status[it[j].block0 + b];
                 if (sv) {  // the item's first failing block, like the reference's message (lac/decoder.cpp:24-32)
                     code[i] = LACX_E_RUNTIME;
-                    err[i] = "[decode-error] block=" + std::to_string(b) + " " + block_error(sv);
+                    err[i] = "[decode-error] block=" + std::to_string(blk_first[j] + b) + " " + block_error(sv);
                     break;
                 }
             }
@@ -455,7 +560,11 @@ int decode_batch_run(lacx_decoder* d, const BatchIn* in, uint32_t n, DecodeTo to
                 (void)wav_header(info[i], img);
                 if (out) out[i] = lacx_span{img, image_size[j]};
             }
-            if (to == DecodeTo::host) {  // the two channels leave on two streams' worth of copy engine time: issue, then wait
+            if (to == DecodeTo::host && window >= 0) {
+                const uint64_t bytes = win[j].frames * 4u;
+                DEC_TRY(hipMemcpyAsync(in[i].left, win[j].left, bytes, hipMemcpyDeviceToHost, st), "D2H left");
+                if (it[j].channels == 2) DEC_TRY(hipMemcpyAsync(in[i].right, win[j].right, bytes, hipMemcpyDeviceToHost, st), "D2H right");
+            } else if (to == DecodeTo::host) {  // the two channels leave on two streams' worth of copy engine time: issue, then wait
                 const uint64_t bytes = it[j].frames * sizeof(int32_t);
                 DEC_TRY(hipMemcpyAsync(in[i].left, d->d_left + pcm_at[j], bytes, hipMemcpyDeviceToHost, st), "D2H left");
                 if (it[j].channels == 2)
@@ -490,10 +599,10 @@ int batch_result(lacx_decoder* d, int rc, const std::vector<int>& code, std::vec
 }
 
 // A single stream as a batch of one: its own code and message.  d->item_err keeps the last batch call's.
-int decode_one(lacx_decoder* d, const BatchIn& in, DecodeTo to, lacx_span* out, float* device_ms) {
+int decode_one(lacx_decoder* d, const BatchIn& in, DecodeTo to, lacx_span* out, float* device_ms, int window = -1) {
     std::vector<int> code;
     std::vector<std::string> err;
-    (void)decode_batch_run(d, &in, 1, to, nullptr, out, code, err, device_ms);
+    (void)decode_batch_run(d, &in, 1, to, nullptr, out, code, err, device_ms, window);
     return code[0] == LACX_OK ? LACX_OK : decode_fail(code[0], err[0]);
 }
 }  // namespace
@@ -579,6 +688,30 @@ int lacx_decoder_decode_batch_device(lacx_decoder* d, const lacx_decode_item* it
     const int rc = decode_batch_run(d, in.data(), n, DecodeTo::device, static_cast<hipStream_t>(stream), nullptr, code, err,
                                     device_ms);
     return batch_result(d, rc, code, err, item_rc);
+}
+
+int lacx_decoder_decode_window_batch_device(lacx_decoder* d, const lacx_window_item* items, uint32_t n, int sample_type,
+                                            void* stream, int* item_rc, float* device_ms) {
+    if (!d) return decode_fail(LACX_E_INVALID, "null decoder");
+    if (!items || n == 0) return decode_fail(LACX_E_INVALID, "null argument or empty batch");
+    if (sample_type != LACX_SAMPLE_I32 && sample_type != LACX_SAMPLE_F32) return decode_fail(LACX_E_INVALID, "unknown sample type");
+    std::vector<BatchIn> in(n);
+    for (uint32_t i = 0; i < n; ++i)
+        in[i] = BatchIn{items[i].lac, items[i].size, static_cast<int32_t*>(items[i].left), static_cast<int32_t*>(items[i].right),
+                        items[i].frames, items[i].start};
+    std::vector<int> code;
+    std::vector<std::string> err;
+    const int rc = decode_batch_run(d, in.data(), n, DecodeTo::device, static_cast<hipStream_t>(stream), nullptr, code, err,
+                                    device_ms, sample_type);
+    return batch_result(d, rc, code, err, item_rc);
+}
+
+int lacx_decoder_decode_window(lacx_decoder* d, const uint8_t* lac, uint64_t size, uint64_t start, uint64_t frames,
+                               int sample_type, void* left, void* right, float* device_ms) {
+    if (!d) return decode_fail(LACX_E_INVALID, "null decoder");
+    if (sample_type != LACX_SAMPLE_I32 && sample_type != LACX_SAMPLE_F32) return decode_fail(LACX_E_INVALID, "unknown sample type");
+    return decode_one(d, BatchIn{lac, size, static_cast<int32_t*>(left), static_cast<int32_t*>(right), frames, start},
+                      DecodeTo::host, nullptr, device_ms, sample_type);
 }
 
 const char* lacx_decoder_item_error(const lacx_decoder* d, uint32_t i) {

@@ -14,6 +14,8 @@
 //                                                                        (ref src/codec/lac/decoder.cpp:48-65,30-46)
 //   k_wav_pack      the same per-sample work as k_ms_inverse, written as the data region of a canonical WAV image
 //                   (interleaved little-endian 16 / 24-bit, ref src/main.cpp:150-182) instead of back into left/right
+//   k_window_out    the same per-sample work over the blocks a frame window needs, the window's frames written as
+//                   int32 or float32 into the caller's arrays (lacx_decoder_decode_window*)
 // Every launch decodes a batch of streams (items) as one job; a single stream is a batch of one.
 // The adaptive Rice parameter uses the encoder's division-free formulation (kmean / biased_k of analyze_core.h, proven
 // against Rice::adapt_k there); it assumes zigzag residuals below 2^30 like the encoder does, and a stream with a larger
@@ -706,6 +708,106 @@ __global__ __launch_bounds__(256) void k_wav_pack(uint32_t nitems, unsigned long
                   global_ptr(it.left), global_ptr(it.right), ms_flag + it.block0, status + it.block0, global_ptr(it.wav));
 }
 
+// Window form: one thread per unit of four decoded frames of an item (frames 4u .. 4u+3 of the blocks that
+// overlap its window, in the decoder's scratch, where each item starts at a multiple of 4 frames).  The same per-frame
+// work as wav_pack_unit -- 16-byte loads, the block looked up per frame, the mid/side inverse, the bit-depth check of
+// every decoded sample (status 7 on a block that decoded) -- and then a store of the frames that fall inside the window
+// (w_start / w_frames, in decoded frames) at f - w_start of out_l / out_r: int32, or float32 scaled by
+// 2^-(bit_depth - 1) (exact: a 16- or 24-bit sample and its scaled value are both exact in float32).  The outputs are
+// only element-aligned (a row of an odd-length tensor), so every sample leaves as a dword store of its own; nothing
+// outside [0, w_frames) is written, and out_r is not touched for a mono item.  (Kept apart from wav_pack_unit: shared
+// inline helpers change k_wav_pack's register allocation.)
+__device__ __forceinline__ void window_out_unit(unsigned long long f0, uint32_t num_blocks, int channels, int bit_depth,
+                                                unsigned long long frames, const unsigned long long* __restrict__ frame_off,
+                                                unsigned long long frame_base, const int32_t* __restrict__ left,
+                                                const int32_t* __restrict__ right, const uint8_t* __restrict__ ms_flag,
+                                                uint32_t* __restrict__ status, unsigned long long w_start,
+                                                unsigned long long w_frames, uint32_t* __restrict__ out_l,
+                                                uint32_t* __restrict__ out_r, bool f32) {
+    const uint32_t nf = frames - f0 >= 4u ? 4u : (uint32_t)(frames - f0);
+    const bool stereo = channels == 2;
+    int32_t l[4] = {0, 0, 0, 0}, r[4] = {0, 0, 0, 0};
+    if (nf == 4u) {
+        const int4 a = *reinterpret_cast<const int4*>(left + f0);  // f0 is a multiple of 4: 16-byte aligned
+        l[0] = a.x, l[1] = a.y, l[2] = a.z, l[3] = a.w;
+        if (stereo) {
+            const int4 b = *reinterpret_cast<const int4*>(right + f0);
+            r[0] = b.x, r[1] = b.y, r[2] = b.z, r[3] = b.w;
+        }
+    } else {
+#pragma unroll
+        for (uint32_t i = 0; i < 3u; ++i) {
+            if (i < nf) {
+                l[i] = left[f0 + i];
+                if (stereo) r[i] = right[f0 + i];
+            }
+        }
+    }
+    const uint32_t b0 = block_of_frame(frame_off, num_blocks, frame_base, f0);
+    const unsigned long long split = frame_off[b0 + 1] - frame_base;  // frames from here on belong to block b0 + 1
+    const uint32_t b1 = f0 + nf > split ? b0 + 1u : b0;
+    const uint32_t st0 = status[b0], st1 = status[b1];
+    const bool ms0 = stereo && ms_flag[b0] != 0, ms1 = stereo && ms_flag[b1] != 0;
+    const long long lo = bit_depth == 16 ? -32768 : -0x800000, hi = bit_depth == 16 ? 32767 : 0x7FFFFF;
+    const float scale = bit_depth == 16 ? 1.f / 32768.f : 1.f / 8388608.f;
+    bool bad0 = false, bad1 = false;
+#pragma unroll
+    for (uint32_t i = 0; i < 4u; ++i) {
+        const bool second = f0 + i >= split;
+        long long a = l[i], b = r[i];
+        if (second ? ms1 : ms0) {  // ref lac/decoder.cpp:48-65
+            const long long m = a, s = b;
+            a = m + ((s + (s & 1)) >> 1);
+            b = a - s;
+        }
+        const bool bad = i < nf && (a < lo || a > hi || (stereo && (b < lo || b > hi)));
+        bad0 = bad0 || (bad && !second);
+        bad1 = bad1 || (bad && second);
+        const unsigned long long g = f0 + i - w_start;  // (below the window it wraps to beyond it)
+        if (i < nf && g < w_frames) {
+            out_l[g] = f32 ? __float_as_uint((float)(int32_t)a * scale) : (uint32_t)(int32_t)a;
+            if (stereo) out_r[g] = f32 ? __float_as_uint((float)(int32_t)b * scale) : (uint32_t)(int32_t)b;
+        }
+    }
+    // blocks that did not decode are not checked (their status already fails the item)
+    if (bad0 && st0 == 0u) atomicMax(&status[b0], 7u);
+    if (bad1 && st1 == 0u) atomicMax(&status[b1], 7u);
+}
+
+// Every window item of a batch in one launch, laid out as k_wav_pack: thread u handles unit u of the concatenated unit
+// ranges of the items' decoded frames (unit_off: [nitems + 1] prefix sums of ceil(frames / 4)); the item is found once
+// per workgroup by a uniform binary search, and again per thread only in a workgroup that spans items.
+__global__ __launch_bounds__(256) void k_window_out(uint32_t nitems, unsigned long long total_units,
+                                                    const unsigned long long* __restrict__ unit_off,
+                                                    const DecodeItem* __restrict__ items, const WindowOut* __restrict__ win,
+                                                    const unsigned long long* __restrict__ frame_off,
+                                                    const uint8_t* __restrict__ ms_flag, uint32_t* __restrict__ status,
+                                                    int f32) {
+    const unsigned long long first = (unsigned long long)blockIdx.x * 256u;
+    uint32_t lo = 0, hi = nitems;  // unit_off[lo] <= first < unit_off[hi]
+    while (hi - lo > 1u) {
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        if (unit_off[mid] <= first) lo = mid;
+        else hi = mid;
+    }
+    const unsigned long long u = first + threadIdx.x;
+    if (u >= total_units) return;
+    uint32_t j = lo;
+    if (unit_off[lo + 1] < first + 256u) {  // (uniform) the workgroup spans items: this thread's, among the later ones
+        uint32_t h2 = nitems;  // unit_off[j] <= u < unit_off[h2]
+        while (h2 - j > 1u) {
+            const uint32_t mid = j + (h2 - j) / 2u;
+            if (unit_off[mid] <= u) j = mid;
+            else h2 = mid;
+        }
+    }
+    const DecodeItem& it = items[j];
+    const WindowOut& w = win[j];
+    window_out_unit(4ull * (u - unit_off[j]), it.blocks, it.channels, it.bit_depth, it.frames, frame_off + it.block0, it.frame0,
+                    global_ptr(it.left), global_ptr(it.right), ms_flag + it.block0, status + it.block0, w.start, w.frames,
+                    global_ptr(static_cast<uint32_t*>(w.left)), global_ptr(static_cast<uint32_t*>(w.right)), f32 != 0);
+}
+
 hipError_t launch_decode(const DecodeArgs& a, hipStream_t stream) {
     const size_t smem = kDecBytesPerCol * kDecThreads;
     if (a.lanes) {
@@ -722,7 +824,11 @@ hipError_t launch_decode(const DecodeArgs& a, hipStream_t stream) {
         hipLaunchKernelGGL(k_decode_serial, dim3((a.nv2 + kDecThreads - 1) / kDecThreads), dim3(kDecThreads), smem,
                            stream, a.nv2, a.v2_items, a.items, a.payload, a.frame_off, a.status, a.ms_flag);
     }
-    if (a.wav) {
+    if (a.window) {
+        if (a.total_units)
+            hipLaunchKernelGGL(k_window_out, dim3((uint32_t)((a.total_units + 255u) / 256u)), dim3(256), 0, stream, a.nitems,
+                               a.total_units, a.unit_off, a.items, a.window, a.frame_off, a.ms_flag, a.status, a.f32 ? 1 : 0);
+    } else if (a.wav) {
         if (a.total_units)
             hipLaunchKernelGGL(k_wav_pack, dim3((uint32_t)((a.total_units + 255u) / 256u)), dim3(256), 0, stream, a.nitems,
                                a.total_units, a.unit_off, a.items, a.frame_off, a.ms_flag, a.status);

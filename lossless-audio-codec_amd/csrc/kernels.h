@@ -190,9 +190,16 @@ struct DecodeItem {
     uint32_t pay_bits;            // version 2 only: payload bits
     uint8_t channels, stereo_mode, bit_depth, version;
 };
+// Window form: an item's decoded frames are those of the blocks that overlap its window, from the first of them on.
+struct WindowOut {
+    void* left;                   // the window's samples from its frame 0 on: int32 or float32, 4-byte aligned
+    void* right;                  // null for mono
+    unsigned long long start;     // the window's first frame, counted in the item's decoded frames
+    unsigned long long frames;    // >= 1
+};
 struct DecodeArgs {
     uint32_t nitems = 0, total_blocks = 0;
-    const DecodeItem* items = nullptr;
+    const DecodeItem* items = nullptr;        // (window form: an item covers only the blocks its window needs)
     const uint32_t* blk_item = nullptr;       // [total_blocks] the item of every block
     // k_decode: lane g decodes block lane_blk[g] (~0u: idle); only version-3 blocks, an item's in consecutive lanes
     uint32_t lanes = 0;
@@ -209,6 +216,10 @@ struct DecodeArgs {
     bool wav = false;
     const unsigned long long* unit_off = nullptr;
     unsigned long long total_units = 0;
+    // window form (non-null: k_window_out over the units of unit_off in place of k_ms_inverse / k_wav_pack): window[j]
+    // says which of item j's decoded frames go where; f32: float32 samples scaled by 2^-(bit_depth - 1), else int32
+    const WindowOut* window = nullptr;
+    bool f32 = false;
 };
 hipError_t launch_decode(const DecodeArgs& args, hipStream_t stream);
 

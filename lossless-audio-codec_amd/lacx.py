@@ -109,7 +109,7 @@ EXPORTS = (
     "lacx_decoder_create", "lacx_decoder_destroy", "lacx_decoder_decode", "lacx_sizeof",
     "lacx_decoder_decode_wav", "lacx_decoder_decode_wav_view",
     "lacx_decoder_decode_wav_batch", "lacx_decoder_decode_wav_batch_view", "lacx_decoder_decode_batch_device",
-    "lacx_decoder_item_error",
+    "lacx_decoder_item_error", "lacx_decoder_decode_window_batch_device", "lacx_decoder_decode_window",
 )
 
 
@@ -167,6 +167,10 @@ def lib():
         L.lacx_decoder_decode_wav_batch.argtypes = L.lacx_decoder_decode_wav_batch_view.argtypes
         L.lacx_decoder_decode_batch_device.argtypes = [C.c_void_p, C.POINTER(DecodeItem), C.c_uint32, C.c_void_p,
                                                        C.POINTER(C.c_int), C.POINTER(C.c_float)]
+        L.lacx_decoder_decode_window_batch_device.argtypes = [C.c_void_p, C.POINTER(WindowItem), C.c_uint32, C.c_int,
+                                                              C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_float)]
+        L.lacx_decoder_decode_window.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), C.c_uint64, C.c_uint64, C.c_uint64, C.c_int,
+                                                 C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
         L.lacx_decoder_item_error.restype = C.c_char_p
         L.lacx_decoder_item_error.argtypes = [C.c_void_p, C.c_uint32]
         # the structs declared in this file against the library's own sizeof(): a layout that has drifted from
@@ -187,7 +191,7 @@ def abi_structs() -> dict:
     return {"config": Config, "channel_plan": ChannelPlan, "block_plan": BlockPlan, "timing": Timing, "pcm": Pcm,
             "batch_item": BatchItem, "batch_out": BatchOut, "wav_info": WavInfo, "fanout_shard": FanoutShard,
             "fanout_out": FanoutOut, "fanout_stats": FanoutStats, "stream_info": StreamInfo, "span": Span,
-            "decode_item": DecodeItem}
+            "decode_item": DecodeItem, "window_item": WindowItem}
 
 
 def device_count() -> int:
@@ -616,6 +620,24 @@ class DecodeItem(C.Structure):
                 ("frames", C.c_uint64)]
 
 
+class WindowItem(C.Structure):
+    _fields_ = [("lac", C.POINTER(C.c_uint8)), ("size", C.c_uint64), ("start", C.c_uint64), ("frames", C.c_uint64),
+                ("left", C.c_void_p), ("right", C.c_void_p)]
+
+
+SAMPLE_I32, SAMPLE_F32 = 0, 1  # LACX_SAMPLE_*
+
+
+def _sample_type(dtype) -> int:
+    """numpy dtype (or its name) -> LACX_SAMPLE_*: int32 or float32 only."""
+    dt = np.dtype(dtype)
+    if dt == np.int32:
+        return SAMPLE_I32
+    if dt == np.float32:
+        return SAMPLE_F32
+    raise ValueError(f"window samples are int32 or float32, not {dt}")
+
+
 class BatchDecodeError(RuntimeError):
     """Some items of a batch decode failed.  errors: {index: message} (each the message the item's own decode gives);
     results: the call's results with None at the failed indices.  str(): the lowest failing item, "stream i: ..."."""
@@ -631,6 +653,13 @@ def stream_parse(lac: bytes):
     info = StreamInfo()
     buf = (C.c_uint8 * max(1, len(lac))).from_buffer_copy(lac if lac else b"\0")
     return info if lib().lacx_stream_parse(buf, C.c_uint64(len(lac)), C.byref(info)) == OK else None
+
+
+def _parse_in_place(buf: np.ndarray):
+    """stream_parse of a uint8 array, without copying it."""
+    info = StreamInfo()
+    rc = lib().lacx_stream_parse(buf.ctypes.data_as(C.POINTER(C.c_uint8)), C.c_uint64(buf.size), C.byref(info))
+    return info if rc == OK else None
 
 
 def decode(lac: bytes, device: int = -1):
@@ -802,6 +831,57 @@ class Decoder:
             it.frames = inf.frames if inf is not None else 0
         rc, errors = self._batch(n, lambda rcs, ms: lib().lacx_decoder_decode_batch_device(
             self._h, items, C.c_uint32(n), C.c_void_p(stream), rcs, ms))
+        results = [None if i in errors else infos[i] for i in range(n)]
+        return self._raise_batch(rc, errors, results)
+
+    def decode_window(self, lac, start: int, frames: int, dtype=np.int32):
+        """Frames [start, start + frames) of a .lac as (left, right or None) numpy arrays of `dtype` (int32: the integer
+        samples; float32: sample * 2^-(bit_depth - 1)).  Only the blocks that overlap the window are decoded (a version-2
+        stream decodes in full); kernel milliseconds in `last_ms`.  RuntimeError like `decode`."""
+        if self._h is None:
+            raise RuntimeError("decoder is closed")
+        st = _sample_type(dtype)
+        info = StreamInfo()
+        buf = np.frombuffer(lac, dtype=np.uint8)
+        bp = buf.ctypes.data_as(C.POINTER(C.c_uint8))
+        if lib().lacx_stream_parse(bp, C.c_uint64(buf.size), C.byref(info)) != OK:
+            raise RuntimeError(lib().lacx_decode_last_error().decode(errors="replace"))
+        n = max(int(frames), 0)
+        left = np.empty(n, dtype=np.dtype(dtype))
+        right = np.empty(n, dtype=np.dtype(dtype)) if info.channels == 2 else None
+        ms = C.c_float()
+        rc = lib().lacx_decoder_decode_window(self._h, bp, C.c_uint64(buf.size), C.c_uint64(int(start)),
+                                              C.c_uint64(int(frames)), C.c_int(st), C.c_void_p(left.ctypes.data),
+                                              C.c_void_p(right.ctypes.data) if right is not None else None, C.byref(ms))
+        if rc != OK:
+            raise RuntimeError(lib().lacx_decode_last_error().decode(errors="replace"))
+        self.last_ms = float(ms.value)
+        return left, right
+
+    def decode_window_batch_device(self, lacs, starts, frames, outputs, dtype="int32", stream: int = 0) -> list:
+        """Frame windows of many .lac streams as one device job, into caller-owned device arrays: item i is frames
+        [starts[i], starts[i] + frames[i]) of lacs[i] (`frames`: one int for all items or one per item), written to
+        outputs[i] = (left_ptr, right_ptr or None), raw device addresses of that many int32 or float32 (`dtype`) on the
+        decoder's device, 4-byte aligned (a row of a torch tensor).  The work goes on `stream` (a raw hipStream_t, 0 = the
+        null stream).  Returns each item's StreamInfo (None where it failed); failed items raise BatchDecodeError once
+        the others are done."""
+        st = _sample_type(dtype)
+        n = len(lacs)
+        counts = [int(frames)] * n if np.ndim(frames) == 0 else [int(f) for f in frames]
+        if len(outputs) != n or len(starts) != n or len(counts) != n:
+            raise ValueError("one start, frame count and output pair per stream")
+        bufs = [np.frombuffer(x, dtype=np.uint8) for x in lacs]
+        infos = [_parse_in_place(b) for b in bufs]  # (a window of a long stream: no copy of the stream per item)
+        items = (WindowItem * max(1, n))()
+        for it, b, s0, f, (lp, rp) in zip(items, bufs, starts, counts, outputs):
+            it.lac = b.ctypes.data_as(C.POINTER(C.c_uint8))
+            it.size = b.size
+            it.start = int(s0)
+            it.frames = f
+            it.left = lp
+            it.right = rp
+        rc, errors = self._batch(n, lambda rcs, ms: lib().lacx_decoder_decode_window_batch_device(
+            self._h, items, C.c_uint32(n), C.c_int(st), C.c_void_p(stream), rcs, ms))
         results = [None if i in errors else infos[i] for i in range(n)]
         return self._raise_batch(rc, errors, results)
 
