@@ -44,6 +44,8 @@ struct Geo {
     static constexpr int W96 = 96 / CH_;      // micro window, in chunks
     static constexpr int MAXP = (MAXN >= 8192) ? 8 : ((MAXN >= 4096) ? 7 : ((MAXN >= 2048) ? 6 : ((MAXN >= 1024) ? 5 : ((MAXN >= 512) ? 4 : 3))));
     static constexpr int NSEG = (2 << MAXP) - 2;  // segments over all partition orders 1..MAXP
+    static constexpr int SW = (T_ < 64) ? T_ : 64;   // lanes of one wave that work on the slot (32: two slots share a wave, one per half)
+    static constexpr int NW = (T_ + 63) / 64;        // waves that work on the slot
     static_assert(32 % CH_ == 0, "chunk must divide the 96/256 windows");
     static_assert(MAXN % 64 == 0, "whole groups");
 };
@@ -470,7 +472,17 @@ LACX_HD void plane_counts(const uint32_t* u, uint32_t* cs) {
         sliced_add<4>(l3[0], l3[1], l4);
 #pragma unroll
         for (int l = 0; l < G::LV; ++l) cs[l] = l4[l];
+    } else if (G::CH == 8) {
+        uint32_t l1[4][2], l2[2][3], l3[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) sliced_add<1>(&u[2 * i], &u[2 * i + 1], l1[i]);
+#pragma unroll
+        for (int i = 0; i < 2; ++i) sliced_add<2>(l1[2 * i], l1[2 * i + 1], l2[i]);
+        sliced_add<3>(l2[0], l2[1], l3);
+#pragma unroll
+        for (int l = 0; l < G::LV; ++l) cs[l] = l3[l];
     } else {
+        static_assert(G::CH == 16 || G::CH == 8 || G::CH == 4, "one adder tree per chunk length");
         uint32_t l1[2][2], l2[3];
         sliced_add<1>(&u[0], &u[1], l1[0]);
         sliced_add<1>(&u[2], &u[3], l1[1]);

@@ -113,6 +113,120 @@ __device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) { return wave_last_
 __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) { return wave_last_u32(wave_scan_add_u32(v)); }
 __device__ __forceinline__ uint32_t wave_or_u32(uint32_t v) { return wave_last_u32(wave_scan_or_u32(v)); }
 
+// ---------------------------------------------------------------------------------------------
+// slot-wide forms: SW = 64 is the wave (the functions above, unchanged); SW = 32 is the HALF of the wave the lane is in.
+// Two probe slots share a wave, lanes 0..31 and 32..63, each with its own LDS image, and nothing may cross between them:
+// the row operations stay inside 16 lanes, row_bcast:15 under row mask 0xA feeds rows 1 and 3 from rows 0 and 2, and the
+// step that would carry lane 31 into the upper half (row_bcast:31) is left out.  A half's total sits in its last lane (31 /
+// 63); v_readlane ignores the execution mask, so the halves may diverge -- one of them may have left the surrounding
+// branch or loop -- and each lane picks the value of its own half.  Results that are one scalar for the wave become one
+// value per half, in a vector register.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool upper_half() { return (threadIdx.x & 32u) != 0u; }
+
+// (half_*: the 32-lane forms.  slot_*<SW> names the wave_* function above or the half_* one as a compile-time constant, so
+// that a call at SW = 64 IS the call of the wave-wide function: the whole-block kernel compiles to what it was.)
+__device__ __forceinline__ uint32_t half_last_u32(uint32_t v) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)v, 31), hi = (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+    return upper_half() ? hi : lo;
+}
+__device__ __forceinline__ uint64_t half_last_u64(uint64_t v) {
+    return ((uint64_t)half_last_u32((uint32_t)(v >> 32)) << 32) | half_last_u32((uint32_t)v);
+}
+__device__ __forceinline__ uint32_t half_scan_add_u32(uint32_t v) {
+    v += dpp_mov<kDppRowShr1, 0xF>(0u, v);
+    v += dpp_mov<kDppRowShr2, 0xF>(0u, v);
+    v += dpp_mov<kDppRowShr4, 0xF>(0u, v);
+    v += dpp_mov<kDppRowShr8, 0xF>(0u, v);
+    v += dpp_mov<kDppRowBcast15, 0xA>(0u, v);
+    return v;
+}
+__device__ __forceinline__ uint64_t half_scan_add_u64(uint64_t v) {
+    v += dpp_mov64<kDppRowShr1, 0xF>(v);
+    v += dpp_mov64<kDppRowShr2, 0xF>(v);
+    v += dpp_mov64<kDppRowShr4, 0xF>(v);
+    v += dpp_mov64<kDppRowShr8, 0xF>(v);
+    v += dpp_mov64<kDppRowBcast15, 0xA>(v);
+    return v;
+}
+__device__ __forceinline__ int32_t half_scan_max_i32(int32_t v) {  // identity INT32_MIN
+    constexpr uint32_t kMin = 0x80000000u;
+    auto mx = [](int32_t a, uint32_t b) { return a > (int32_t)b ? a : (int32_t)b; };
+    v = mx(v, dpp_mov<kDppRowShr1, 0xF>(kMin, (uint32_t)v));
+    v = mx(v, dpp_mov<kDppRowShr2, 0xF>(kMin, (uint32_t)v));
+    v = mx(v, dpp_mov<kDppRowShr4, 0xF>(kMin, (uint32_t)v));
+    v = mx(v, dpp_mov<kDppRowShr8, 0xF>(kMin, (uint32_t)v));
+    v = mx(v, dpp_mov<kDppRowBcast15, 0xA>(kMin, (uint32_t)v));
+    return v;
+}
+__device__ __forceinline__ uint32_t half_scan_or_u32(uint32_t v) {
+    v |= dpp_mov<kDppRowShr1, 0xF>(0u, v);
+    v |= dpp_mov<kDppRowShr2, 0xF>(0u, v);
+    v |= dpp_mov<kDppRowShr4, 0xF>(0u, v);
+    v |= dpp_mov<kDppRowShr8, 0xF>(0u, v);
+    v |= dpp_mov<kDppRowBcast15, 0xA>(0u, v);
+    return v;
+}
+__device__ __forceinline__ uint64_t half_scan_min_u64(uint64_t v) {  // identity: all ones
+    auto step = [](uint64_t a, uint32_t lo, uint32_t hi) {
+        const uint64_t b = ((uint64_t)hi << 32) | lo;
+        return b < a ? b : a;
+    };
+#define LACX_MIN_STEP(CTRL, MASK) \
+    v = step(v, dpp_mov<CTRL, MASK>(0xFFFFFFFFu, (uint32_t)v), dpp_mov<CTRL, MASK>(0xFFFFFFFFu, (uint32_t)(v >> 32)))
+    LACX_MIN_STEP(kDppRowShr1, 0xF);
+    LACX_MIN_STEP(kDppRowShr2, 0xF);
+    LACX_MIN_STEP(kDppRowShr4, 0xF);
+    LACX_MIN_STEP(kDppRowShr8, 0xF);
+    LACX_MIN_STEP(kDppRowBcast15, 0xA);
+#undef LACX_MIN_STEP
+    return v;
+}
+__device__ __forceinline__ uint64_t half_sum_u64(uint64_t v) { return half_last_u64(half_scan_add_u64(v)); }
+__device__ __forceinline__ uint32_t half_sum_u32(uint32_t v) { return half_last_u32(half_scan_add_u32(v)); }
+__device__ __forceinline__ uint32_t half_or_u32(uint32_t v) { return half_last_u32(half_scan_or_u32(v)); }
+template <int SW> constexpr auto slot_last_u32 = SW == 64 ? &wave_last_u32 : &half_last_u32;
+template <int SW> constexpr auto slot_last_u64 = SW == 64 ? &wave_last_u64 : &half_last_u64;
+template <int SW> constexpr auto slot_scan_add_u32 = SW == 64 ? &wave_scan_add_u32 : &half_scan_add_u32;
+template <int SW> constexpr auto slot_scan_add_u64 = SW == 64 ? &wave_scan_add_u64 : &half_scan_add_u64;
+template <int SW> constexpr auto slot_scan_max_i32 = SW == 64 ? &wave_scan_max_i32 : &half_scan_max_i32;
+template <int SW> constexpr auto slot_scan_or_u32 = SW == 64 ? &wave_scan_or_u32 : &half_scan_or_u32;
+template <int SW> constexpr auto slot_scan_min_u64 = SW == 64 ? &wave_scan_min_u64 : &half_scan_min_u64;
+template <int SW> constexpr auto slot_sum_u64 = SW == 64 ? &wave_sum_u64 : &half_sum_u64;
+template <int SW> constexpr auto slot_sum_u32 = SW == 64 ? &wave_sum_u32 : &half_sum_u32;
+template <int SW> constexpr auto slot_or_u32 = SW == 64 ? &wave_or_u32 : &half_or_u32;
+// value of the slot's first lane in every lane of the slot
+template <int SW>
+__device__ __forceinline__ uint32_t slot_first_u32(uint32_t v) {
+    static_assert(SW == 64 || SW == 32, "the wave or one of its halves");
+    if constexpr (SW == 64) {
+        return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+    } else {
+        const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)v, 0), hi = (uint32_t)__builtin_amdgcn_readlane((int)v, 32);
+        return upper_half() ? hi : lo;
+    }
+}
+// The lanes of the slot for which pred holds, bit i = lane i of the slot (SW = 32: the ballot word of the lane's own half;
+// only lanes that execute the ballot are counted, as ever).
+template <int SW>
+__device__ __forceinline__ uint64_t slot_ballot(bool pred) {
+    const unsigned long long m = __ballot(pred);
+    if constexpr (SW == 64) {
+        return m;
+    } else {
+        return upper_half() ? (uint32_t)(m >> 32) : (uint32_t)m;
+    }
+}
+// number of set bits of a slot_ballot mask below the lane's own bit
+template <int SW>
+__device__ __forceinline__ uint32_t slot_rank(uint64_t m) {
+    if constexpr (SW == 64) {
+        return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    } else {
+        return (uint32_t)__popc((uint32_t)m & ((1u << (threadIdx.x & 31u)) - 1u));
+    }
+}
+
 // Sum of v over the segment of (1 << LOG) consecutive lanes that contains the lane; valid in the segment's LAST lane
 // (segments are aligned: lanes [k << LOG, (k + 1) << LOG)).  The first LOG steps of the wave scan.
 // LDS atomics of many lanes on ONE address are serialised lane by lane: 1024 threads adding their partial sums to the
@@ -152,11 +266,11 @@ __device__ __forceinline__ void scan_pz_part1(M& sh, int tid, ScanRegs<G>& r) {
     const int lane = tid & 63, wave = tid >> 6;
     r.v = sh.tabP[tid];
     r.z = sh.tabNZ[tid];
-    const uint64_t inc = wave_scan_add_u64(r.v);
-    const int32_t zinc = wave_scan_max_i32(r.z);
+    const uint64_t inc = slot_scan_add_u64<G::SW>(r.v);
+    const int32_t zinc = slot_scan_max_i32<G::SW>(r.z);
     r.inc = inc;
     r.zinc = zinc;
-    if (lane == 63) {
+    if (lane == G::SW - 1) {
         sh.wtotP[wave] = inc;
         sh.wtotZ[wave] = zinc;
     }
@@ -169,7 +283,7 @@ __device__ __forceinline__ uint64_t scan_pz_part2(M& sh, int tid, const ScanRegs
     uint64_t base = 0, total = 0;
     int32_t zbase = -1;
 #pragma unroll
-    for (int w = 0; w < G::T / 64; ++w) {
+    for (int w = 0; w < G::NW; ++w) {
         const uint64_t pw = sh.wtotP[w];
         const int32_t z = sh.wtotZ[w];
         total += pw;
@@ -178,7 +292,7 @@ __device__ __forceinline__ uint64_t scan_pz_part2(M& sh, int tid, const ScanRegs
             zbase = z > zbase ? z : zbase;
         }
     }
-    int32_t zprev = __shfl_up(r.zinc, 1, 64);
+    int32_t zprev = __shfl_up(r.zinc, 1, G::SW);
     if (lane == 0) zprev = -1;
     sh.tabP[tid] = base + r.inc - r.v;
     sh.tabNZ[tid] = zprev > zbase ? zprev : zbase;
@@ -204,6 +318,24 @@ __device__ __forceinline__ void plane_totals_wave(const Thread<G>& th, uint32_t*
     uint32_t any = 0;
 #pragma unroll
     for (int l = 0; l < G::LV; ++l) any |= th.cs[l];
+    if constexpr (G::SW == 32) {
+        // Two slots per wave: the same counts per half.  The ballot words and their population counts are per-half values
+        // in vector registers, the trip count is the half's own (the loop runs under the execution mask to the larger one).
+        const int nplanes = 32 - __clz((int)slot_or_u32<32>(any));  // 0..30
+        uint32_t mine = 0;
+        for (int b = 0; b < nplanes; ++b) {
+            uint32_t tot = 0;
+#pragma unroll
+            for (int l = 0; l < G::LV; ++l) tot += (uint32_t)__popc((uint32_t)slot_ballot<32>((th.cs[l] >> b) & 1u)) << l;
+            if (lane == b) mine = tot;
+        }
+        static_assert(G::SW != 32 || G::W256 == G::SW, "the slot is its own first 256 samples");
+        if (lane < nplanes) {
+            if (lane >= first_plane) atomicAdd(&planeTot[lane], mine);
+            atomicAdd(&planeTot256[lane], mine);
+        }
+        return;
+    }
     const int nplanes = 32 - __clz((int)wave_or_u32(any));  // uniform, 0..30
     // lanes of wave 0 whose chunk lies inside the first 256 samples
     const uint64_t m256 = (G::W256 >= 64) ? ~0ull : ((1ull << (G::W256 & 63)) - 1ull);
@@ -240,10 +372,10 @@ __device__ __forceinline__ void plane_totals_wave(const Thread<G>& th, uint32_t*
 template <class G>
 __device__ __forceinline__ void ksums_wave(const Thread<G>& th, uint32_t* ksum, uint32_t* ksum256, int tid, uint32_t kmask = 0xFFFFu) {
     const int lane = tid & 63, wave = tid >> 6;
-    static_assert(G::W256 == 16 || G::W256 == 64, "the first 256 samples are one DPP row or the whole wave");
+    static_assert(G::W256 == 16 || G::W256 == G::SW, "the first 256 samples are one DPP row or the slot's whole share of the wave");
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
-        const bool wanted = ((kmask >> k) & 1u) != 0u;                 // (uniform)
+        const bool wanted = ((kmask >> k) & 1u) != 0u;                 // (uniform over the slot)
         const bool head256 = wave == 0 && k <= 12;                     // (uniform)
         if (!wanted && !head256) continue;
         uint32_t v = 0;
@@ -254,12 +386,12 @@ __device__ __forceinline__ void ksums_wave(const Thread<G>& th, uint32_t* ksum, 
         v += dpp_mov<kDppRowShr4, 0xF>(0u, v);
         v += dpp_mov<kDppRowShr8, 0xF>(0u, v);
         const uint32_t row = v;  // lane 15: the sum over lanes 0..15
-        if (wanted || G::W256 == 64) {
+        if (wanted || G::W256 == G::SW) {
             v += dpp_mov<kDppRowBcast15, 0xA>(0u, v);
-            v += dpp_mov<kDppRowBcast31, 0xC>(0u, v);
-            if (lane == 63) {
+            if constexpr (G::SW == 64) v += dpp_mov<kDppRowBcast31, 0xC>(0u, v);
+            if (lane == G::SW - 1) {
                 if (wanted) atomicAdd(&ksum[k], v);
-                if (G::W256 == 64 && wave == 0 && k <= 12) atomicAdd(&ksum256[k], v);
+                if (G::W256 == G::SW && wave == 0 && k <= 12) atomicAdd(&ksum256[k], v);
             }
         }
         if (G::W256 == 16 && wave == 0 && lane == 15 && k <= 12) atomicAdd(&ksum256[k], row);
@@ -271,25 +403,27 @@ __device__ __forceinline__ void ksums_wave(const Thread<G>& th, uint32_t* ksum, 
 //   (S - n (2^k - 1)) / 2^k <= A_k <= S >> k,
 // so a k whose lower cost bound exceeds the smallest upper bound over all k can neither be the minimum nor tie with it.
 // Typically four of the sixteen remain (k* - 1 .. k* + 2 around S / n).  Returns the mask of the k to evaluate.
+template <int SW = 64>
 __device__ __forceinline__ uint32_t static_k_candidates(uint64_t S, uint32_t n, int lane) {
     const uint32_t k = (uint32_t)lane & 15u;
     const uint64_t fixed = (uint64_t)n * (1u + k);
     const uint64_t upper = (S >> k) + fixed;
     const uint64_t slack = (uint64_t)n * ((1u << k) - 1u);
     const uint64_t lower = (S > slack ? ((S - slack + ((1u << k) - 1u)) >> k) : 0ull) + fixed;
-    const uint64_t umin = wave_last_u64(wave_scan_min_u64(lane < 16 ? upper : ~0ull));
-    return (uint32_t)__ballot(lane < 16 && lower <= umin) & 0xFFFFu;
+    const uint64_t umin = slot_last_u64<SW>(slot_scan_min_u64<SW>(lane < 16 ? upper : ~0ull));
+    return (uint32_t)slot_ballot<SW>(lane < 16 && lower <= umin) & 0xFFFFu;
 }
 
 // Exclusive scan of an LDS array by one wave (row of 64 at a time, running carry).
+template <int SW = 64>
 __device__ __forceinline__ void wave_exclusive_scan_u32(uint32_t* arr, int len, int lane) {
     uint32_t carry = 0;
-    for (int base = 0; base < len; base += 64) {
+    for (int base = 0; base < len; base += SW) {
         const int i = base + lane;
         const uint32_t v = (i < len) ? arr[i] : 0u;
-        const uint32_t inc = wave_scan_add_u32(v);
+        const uint32_t inc = slot_scan_add_u32<SW>(v);
         if (i < len) arr[i] = carry + inc - v;
-        carry += wave_last_u32(inc);
+        carry += slot_last_u32<SW>(inc);
     }
 }
 

@@ -1,9 +1,10 @@
 // k_analyze.hip -- the whole-block / probe analysis kernel and the launcher of the analysis pipeline.
-//   k_analyze<4,64>     one wave per probe slot of an "uncertain" block (ref lac/encoder.cpp:341-354)
+//   k_analyze<8,32>     one wave per PAIR of probe slots of an "uncertain" block, a slot per half of the wave
+//                       (ref lac/encoder.cpp:341-354; -DLACX_PROBE_HALVES=0: k_analyze<4,64>, one wave per slot)
 //   k_analyze<16,1024>  one 1024-thread workgroup per needed whole-block slot
 //                                                           (ref block/encoder.cpp:313-552)
 //                       + the bit emit of its channel block into a staging slot (ref block/encoder.cpp:554-838)
-// Pipeline per launch set (launch_analysis): k_ingest, k_stereo, k_levinson (k_front.hip), k_analyze<4,64>, k_decide(1),
+// Pipeline per launch set (launch_analysis): k_ingest, k_stereo, k_levinson (k_front.hip), k_analyze<GProbe>, k_decide(1),
 // k_analyze<16,1024> [+ two workgroups per small final block, k_decide(2)]; beside the whole-block kernel, on its own
 // stream, the streaming packer k_stream_out; behind it k_offsets, k_pack, k_emit, k_gather (k_emit.hip).
 #include <hip/hip_runtime.h>
@@ -154,7 +155,8 @@ __device__ __forceinline__ void publish_pending(const FuseArgs& fa, PendingSlot&
     }
 }
 
-// Candidate scoring (ref block/encoder.cpp:337-359) by the 64 lanes of one wave; same result as score_candidate() of
+// Candidate scoring (ref block/encoder.cpp:337-359) by the lanes of one wave that work on the slot (64, or the 32 of a
+// half: thirty lanes are all it takes); same result as score_candidate() of
 // analyze_core.h, which one thread computes in a serial chain of ~150 dependent 64-bit operations while fifteen
 // waves wait for it at the next barrier.  Static Rice cost at k: sum_j (u_j >> k) = T_k >> k with
 // T_k = sum_{b >= k} C_b << b, a suffix sum over the bit-plane counts: lane l takes plane 29 - l, one prefix scan gives
@@ -170,10 +172,10 @@ __device__ __forceinline__ void score_candidate_wave(Smem<G>& sh, int cand, uint
         // (planes below the lowest k of kmask were not counted: the suffix sums T_k of the k in the mask do not need them)
         const int b = 29 - lane;
         const uint64_t w = (lane < 30) ? ((uint64_t)planeTot[b] << b) : 0ull;
-        const uint64_t tk = wave_scan_add_u64(w);  // lane l: T_(29-l)
+        const uint64_t tk = slot_scan_add_u64<G::SW>(w);  // lane l: T_(29-l)
         if (lane >= 14 && lane < 30 && ((kmask >> b) & 1u)) key = (((tk >> b) + (uint64_t)n * (uint64_t)(1 + b)) << 4) | (uint64_t)b;  // cost < 2^45
     }
-    const uint64_t best_key = wave_last_u64(wave_scan_min_u64(key));
+    const uint64_t best_key = slot_last_u64<G::SW>(slot_scan_min_u64<G::SW>(key));
     if (lane == 0) {
         const uint64_t sbits = best_key >> 4;
         const uint32_t sk = (uint32_t)(best_key & 15u);
@@ -199,6 +201,7 @@ __device__ __forceinline__ void score_candidate_wave(Smem<G>& sh, int cand, uint
 
 // estimate_initial_k (ref block/encoder.cpp:121-158) from the plane counts of the first min(256, n) samples, by the 64
 // lanes of one wave (same suffix-sum formulation as score_candidate_wave; k = 0..12, ties to the lower k).
+template <int SW>
 __device__ __forceinline__ uint32_t initial_k_wave(const uint32_t* planes256, uint32_t n, int lane, bool ksums) {
     const uint32_t m = n < 256u ? n : 256u;
     uint64_t key = ~0ull;
@@ -207,21 +210,21 @@ __device__ __forceinline__ uint32_t initial_k_wave(const uint32_t* planes256, ui
     } else {
         const int b = 29 - lane;
         const uint64_t w = (lane < 30) ? ((uint64_t)planes256[b] << b) : 0ull;
-        const uint64_t tk = wave_scan_add_u64(w);  // lane l: T_(29-l)
+        const uint64_t tk = slot_scan_add_u64<SW>(w);  // lane l: T_(29-l)
         if (lane >= 17 && lane < 30) key = (((tk >> b) + (uint64_t)m * (uint64_t)(1 + b)) << 4) | (uint64_t)b;
     }
-    return (uint32_t)(wave_last_u64(wave_scan_min_u64(key)) & 15u);
+    return (uint32_t)(slot_last_u64<SW>(slot_scan_min_u64<SW>(key)) & 15u);
 }
 
 // ---------------------------------------------------------------------------------------------
 // k_analyze
 // ---------------------------------------------------------------------------------------------
-// Barrier between the phases of a slot.  A probe slot is one wave: its LDS accesses execute in order, so all it needs is
-// that they have completed (and that the compiler keeps its order) -- no s_barrier, which lets the twelve probe slots of a
-// block share a workgroup without sharing trip counts.
+// Barrier between the phases of a slot.  A probe slot is one wave or half of one: its LDS accesses execute in order, so all
+// it needs is that they have completed (and that the compiler keeps its order) -- no s_barrier, which lets the twelve probe
+// slots of a block share a workgroup without sharing trip counts, and the two slots of a wave diverge freely.
 template <class G>
 __device__ __forceinline__ void slot_sync() {
-    if constexpr (G::T == 64) {
+    if constexpr (G::T <= 64) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     } else {
         __syncthreads();
@@ -248,7 +251,7 @@ __device__ __forceinline__ void analyze_slot(unsigned char* smem_raw, const Anal
     const uint32_t chunk_bits = stage_samples(th, sh, src, start);
     // (digital silence: every wave says whether it saw a non-zero sample; wtotF is free until the first scan)
     {
-        const bool wave_silent = __ballot(chunk_bits != 0u) == 0ull;
+        const bool wave_silent = slot_ballot<G::SW>(chunk_bits != 0u) == 0ull;
         if ((tid & 63) == 0) sh.wtotF[tid >> 6] = wave_silent ? 0u : 1u;
     }
     for (int i = tid; i < (int)(sizeof(LpcSet) / 2); i += G::T)
@@ -258,7 +261,11 @@ __device__ __forceinline__ void analyze_slot(unsigned char* smem_raw, const Anal
         sh.planeTot256[0][tid] = sh.planeTot256[1][tid] = 0;
     }
     if (tid < 4) sh.acc[0][tid] = sh.acc[1][tid] = 0;
-    if (tid < 33) (&sh.lbacc[0][0])[tid] = 0;
+    if constexpr (G::T >= 33) {
+        if (tid < 33) (&sh.lbacc[0][0])[tid] = 0;
+    } else {  // (fewer lanes than words: the last word is candidate 10's count of run ends)
+        for (int i = tid; i < 33; i += G::T) (&sh.lbacc[0][0])[i] = 0;
+    }
     if (tid < 2) sh.has4[tid] = 0;
     if (tid == 0) {
         sh.best_cand = -1;
@@ -285,13 +292,13 @@ __device__ __forceinline__ void analyze_slot(unsigned char* smem_raw, const Anal
         // Two candidates share a register for the wave sums (each sum stays below 2^16: 64 lanes x 34 x CH).
         const uint32_t per_thread = 34u * (uint32_t)G::CH;
         const int32_t left = (int32_t)n - (int32_t)((tid >> 6) * 64 * G::CH);  // samples of the slot from this wave's first one on
-        const uint32_t valid = left <= 0 ? 0u : (left >= 64 * G::CH ? (uint32_t)(64 * G::CH) : (uint32_t)left);
-        const uint32_t beyond = (uint32_t)(64 * G::CH) - valid;
+        const uint32_t valid = left <= 0 ? 0u : (left >= G::SW * G::CH ? (uint32_t)(G::SW * G::CH) : (uint32_t)left);
+        const uint32_t beyond = (uint32_t)(G::SW * G::CH) - valid;
         auto reduce_pair = [&](int c0, const BoundPartials& b0, bool two, const BoundPartials& b1) {
             const uint32_t lo = per_thread - b0.msum, hi = two ? per_thread - b1.msum : 0u;
-            const uint32_t g2 = wave_sum_u32(lo | (hi << 16));
-            const uint32_t cnt0 = wave_sum_u32(bound_counts<G::CH>(b0));
-            const uint32_t cnt1 = two ? wave_sum_u32(bound_counts<G::CH>(b1)) : 0u;
+            const uint32_t g2 = slot_sum_u32<G::SW>(lo | (hi << 16));
+            const uint32_t cnt0 = slot_sum_u32<G::SW>(bound_counts<G::CH>(b0));
+            const uint32_t cnt1 = two ? slot_sum_u32<G::SW>(bound_counts<G::CH>(b1)) : 0u;
             if ((tid & 63) == 0 && real) {
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
@@ -330,7 +337,7 @@ __device__ __forceinline__ void analyze_slot(unsigned char* smem_raw, const Anal
     // candidate 0 is costed exactly, nothing else is looked at.
     bool silent = true;
 #pragma unroll
-    for (int w = 0; w < G::T / 64; ++w) silent = silent && sh.wtotF[w] == 0u;  // (uniform)
+    for (int w = 0; w < G::NW; ++w) silent = silent && sh.wtotF[w] == 0u;  // (uniform over the slot)
     uint32_t tmpl_key = 0;  // != 0: this slot is silent and its finished channel block is to be left in fuse.silent
     if (silent) {
         // Every silent slot of this length has the same plan and the same bitstream (under the same settings): where an
@@ -441,7 +448,7 @@ __device__ __forceinline__ void analyze_slot(unsigned char* smem_raw, const Anal
             }
             // next: the untried candidate with the smallest (bound, index), unless it cannot win any more
             const uint64_t key = (tid <= 10 && !((tried >> tid) & 1u)) ? sh.cand_key[tid] : ~0ull;
-            const uint64_t best_key = wave_last_u64(wave_scan_min_u64(key));
+            const uint64_t best_key = slot_last_u64<G::SW>(slot_scan_min_u64<G::SW>(key));
             if (tid == 0) {
                 sh.has4[parity] = 0;
                 sh.bqcount = 0;
@@ -473,7 +480,7 @@ __device__ __forceinline__ void analyze_slot(unsigned char* smem_raw, const Anal
         const bool narrow = total_u < kNarrowLimit;  // all prefix sums fit 32 bits (uniform)
         const bool ksums = narrow && !LACX_HOOK(prm, 262144u);
         // (the k whose static cost can still be the smallest follow from the block's sum alone: about four of sixteen)
-        const uint32_t kmask = !LACX_HOOK(prm, 1048576u) ? static_k_candidates(total_u, n, tid & 63) : 0xFFFFu;
+        const uint32_t kmask = !LACX_HOOK(prm, 1048576u) ? static_k_candidates<G::SW>(total_u, n, tid & 63) : 0xFFFFu;
         if (!LACX_HOOK(prm, 1u)) {
             if (ksums) ksums_wave(th, pt, pt256, tid, kmask);
             else plane_totals_wave(th, pt, pt256, tid, kmask ? (int)__builtin_ctz(kmask) : 0);
@@ -481,7 +488,7 @@ __device__ __forceinline__ void analyze_slot(unsigned char* smem_raw, const Anal
         // the first 256 samples all belong to wave 0: its own totals are complete once its atomics are (same wave,
         // program order), so it can derive the initial k at once; every other thread reads it after B3
         if (tid < 64) {
-            const uint32_t k0w = initial_k_wave(pt256, n, tid, ksums);
+            const uint32_t k0w = initial_k_wave<G::SW>(pt256, n, tid, ksums);
             if (tid == 0) sh.cur_k0 = k0w;
         }
         STAMP(6);
@@ -493,7 +500,7 @@ __device__ __forceinline__ void analyze_slot(unsigned char* smem_raw, const Anal
         } else {
             phase_a<G, false>(th, sh);
         }
-        if (__ballot(th.has4 != 0u) != 0ull && (tid & 63) == 0) sh.has4[parity] = 1u;  // read after B3
+        if (slot_ballot<G::SW>(th.has4 != 0u) != 0ull && (tid & 63) == 0) sh.has4[parity] = 1u;  // read after B3
         STAMP(8);
         slot_sync<G>();  // B3: every chunk's flag counts are in tabF (phase B sums the six before its own), prefixes in tabP
         STAMP(10);
@@ -508,7 +515,7 @@ __device__ __forceinline__ void analyze_slot(unsigned char* smem_raw, const Anal
             // the zero-run cost only matters when the residual has a run of >= 4 zeros somewhere
             const bool zr = prm.zero_run && sh.has4[parity] != 0u;
             const bool full = n == (uint32_t)G::MAXN;
-            if (G::T == 64 || LACX_HOOK(prm, 524288u)) {
+            if (G::T <= 64 || LACX_HOOK(prm, 524288u)) {
                 phase_b_dispatch<G>(th, sh, k0, narrow, zr, full);
                 if ((uint32_t)th.a >= n) {
                     th.crice = th.cbin = th.czr = 0;
@@ -552,10 +559,10 @@ __device__ __forceinline__ void analyze_slot(unsigned char* smem_raw, const Anal
         }
         STAMP(12);
         {
-            const uint64_t r0 = wave_sum_u64(th.crice);
-            const uint64_t r1 = wave_sum_u64(th.cbin);
-            const uint64_t r2 = wave_sum_u64(th.czr);
-            const uint32_t r3 = wave_or_u32(th.chasrun);
+            const uint64_t r0 = slot_sum_u64<G::SW>(th.crice);
+            const uint64_t r1 = slot_sum_u64<G::SW>(th.cbin);
+            const uint64_t r2 = slot_sum_u64<G::SW>(th.czr);
+            const uint32_t r3 = slot_or_u32<G::SW>(th.chasrun);
             if ((tid & 63) == 0) {
                 atomicAdd(&acc[0], (unsigned long long)r0);
                 atomicAdd(&acc[1], (unsigned long long)r1);
@@ -609,8 +616,8 @@ __device__ __forceinline__ void analyze_slot(unsigned char* smem_raw, const Anal
         {
             // the TPG neighbouring lanes of a 64-sample group own its table entry: sum them on the DPP network, one plain
             // store by the group's last lane (no atomics; the entries need no clearing)
-            constexpr int kLog = G::TPG == 4 ? 2 : 4;
-            static_assert(G::TPG == 4 || G::TPG == 16, "lanes per 64-sample group");
+            constexpr int kLog = G::TPG == 4 ? 2 : (G::TPG == 8 ? 3 : 4);
+            static_assert(G::TPG == 4 || G::TPG == 8 || G::TPG == 16, "lanes per 64-sample group");
             uint32_t words[15];
             packed_planes(th, words);
             const bool last = (tid & (G::TPG - 1)) == G::TPG - 1;
@@ -623,9 +630,9 @@ __device__ __forceinline__ void analyze_slot(unsigned char* smem_raw, const Anal
         }
         slot_sync<G>();
         {
-            constexpr int NW = G::T / 64;
+            constexpr int NW = G::NW;
             const int wave = tid >> 6, lane = tid & 63;
-            for (int w = wave; w < 15; w += NW) wave_exclusive_scan_u32(pm.grp[w], G::NG + 1, lane);
+            for (int w = wave; w < 15; w += NW) wave_exclusive_scan_u32<G::SW>(pm.grp[w], G::NG + 1, lane);
         }
         slot_sync<G>();
         STAMP(17);
@@ -699,10 +706,10 @@ __device__ __forceinline__ void analyze_slot(unsigned char* smem_raw, const Anal
                 // pairs are queued and walked densely packed
                 // (per wave: no workgroup barrier, no atomic -- a wave's queue is filled and drained by the wave itself)
                 uint16_t* wq = &pm.queue[(tid >> 6) * 64 * G::MAXP];
-                uint32_t queued = 0;  // wave-uniform
+                uint32_t queued = 0;  // uniform over the wave's lanes of the slot
                 auto enqueue = [&](uint32_t entry, bool ambiguous) {
-                    const unsigned long long m = __ballot(ambiguous);
-                    if (ambiguous) wq[queued + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = (uint16_t)entry;
+                    const unsigned long long m = slot_ballot<G::SW>(ambiguous);
+                    if (ambiguous) wq[queued + slot_rank<G::SW>(m)] = (uint16_t)entry;
                     queued += (uint32_t)__popcll(m);
                 };
                 asm volatile("" : "+v"(th.tid));  // (nothing derived from the thread index lives on from the phases before)
@@ -714,8 +721,8 @@ __device__ __forceinline__ void analyze_slot(unsigned char* smem_raw, const Anal
                     // the wave decides for itself (any mix of the two gives the same sums).
                     QuickPrep<G> qp;
                     partition_quick_prepare<G>(th, sh, max_p, qp);
-                    uint32_t pairs = 0;  // wave-uniform
-                    for (int q = 0; q < max_p; ++q) pairs += (uint32_t)__popcll(__ballot((qp.amb >> q) & 1u));
+                    uint32_t pairs = 0;  // uniform over the wave's lanes of the slot
+                    for (int q = 0; q < max_p; ++q) pairs += (uint32_t)__popcll(slot_ballot<G::SW>((qp.amb >> q) & 1u));
                     if (pairs > kQuickMaxPairs) partition_fused<G, true>(th, sh, max_p, flush32);
                     else partition_quick_costs<G>(th, sh, max_p, qp, flush32, enqueue);
                 }
@@ -755,7 +762,7 @@ __device__ __forceinline__ void analyze_slot(unsigned char* smem_raw, const Anal
                     }
                 } else {
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the wave's own LDS stores, before it reads them back
-                    for (uint32_t e = (uint32_t)(tid & 63); e < queued; e += 64u) {
+                    for (uint32_t e = (uint32_t)(tid & 63); e < queued; e += (uint32_t)G::SW) {
                         if (with_zr) partition_slow_entry<G, true>(sh, n, wq[e], flush_entry);
                         else partition_slow_entry<G, false>(sh, n, wq[e], flush_entry);
                     }
@@ -781,7 +788,7 @@ __device__ __forceinline__ void analyze_slot(unsigned char* smem_raw, const Anal
             const bool valid = j >= 2 && idx < nseg;
             const unsigned long long bits = valid ? seg_choose(sh, (uint32_t)idx, prm.zero_run) : 0ull;
             if (j0 >= 64) {
-                const unsigned long long sum = wave_sum_u64(bits);
+                const unsigned long long sum = slot_sum_u64<G::SW>(bits);
                 if ((tid & 63) == 0) atomicAdd(&pm.pbits[31 - __clz(j0)], sum);
             } else if (valid) {
                 atomicAdd(&pm.pbits[31 - __clz(j)], bits);
@@ -815,10 +822,14 @@ __device__ __forceinline__ void analyze_slot(unsigned char* smem_raw, const Anal
 // (At 127 VGPRs x 4 waves per SIMD an analysis workgroup fills the register files of its CU, so every workgroup of the
 // streaming packer takes a whole CU away from the analysis: measured +25 us of kernel time per packer workgroup, hence
 // the packer's small grid.  The compiler offers no way to cap this kernel at 120.)
+// Waves per SIMD of the probe class.  Two slots per wave, eight samples per lane: 4 (127 VGPRs, 2 spilled, 12 bytes of
+// scratch per lane; the chip's 4 096 wave slots hold the bench stream's 2 952 waves in one round).  3 (141 VGPRs, nothing
+// spilled, 3 072 wave slots) measures the same on music and 2 % slower on white noise; 5 and 6 spill more than the one-slot form did
+// (84 / 108 bytes of scratch) and were not pursued.  One slot per wave: 6 (80 VGPRs, 19 spilled, 80 bytes).
 #ifndef LACX_PROBE_WAVES
-#define LACX_PROBE_WAVES 6
+#define LACX_PROBE_WAVES (LACX_PROBE_HALVES ? 4 : 6)
 #endif
-// Probe class: one wave per probe slot, one slot per workgroup.  (Measured against the twelve probe slots of a block as
+// Probe class: one wave per probe slot or pair of slots, one wave per workgroup.  (Measured, in the one-slot form, against the twelve probe slots of a block as
 // the twelve waves of ONE workgroup -- independent, no workgroup barrier (slot_sync), but started together so that the
 // instruction stream is fetched once for twelve waves: white noise, every block probed, 0.69 -> 0.65 ms; music, 28 % of
 // the blocks probed, 0.18 -> 0.26 ms, because 492 twelve-wave workgroups balance worse over 256 CUs than 5 904 single
@@ -827,6 +838,12 @@ __device__ __forceinline__ void analyze_slot(unsigned char* smem_raw, const Anal
 #define LACX_PROBE_WG_WAVES 1
 #endif
 constexpr int kProbeWaves = LACX_PROBE_WG_WAVES;
+// Two slots per wave (LACX_PROBE_HALVES, kernels_internal.h): the wave's halves take the probe slots 4 + 2i and 5 + 2i of
+// one block -- the same window, left / right or mid / side -- so a block is six waves, both halves share the window's
+// start and length, and a wave whose block is not probed leaves as a whole.  Everything per slot (LDS image, survivors,
+// plan record, front_ctr arrival) is per half; where the halves disagree the code runs under the execution mask.
+constexpr int kProbeSlotsPerWave = 64 / GProbe::SW;
+constexpr int kProbeSlotsPerWg = kProbeWaves * kProbeSlotsPerWave;
 // What only the probe class is handed (front_ctr, kernels_internal.h) -- as kernel arguments of the whole-block class the
 // three pointers cost it a spilled VGPR and sixteen spilled SGPRs although it never looks at them.
 template <class G>
@@ -838,7 +855,7 @@ struct TailArgs<GProbe> {
     uint32_t* need_full_out;
 };
 template <class G>
-__global__ __launch_bounds__(G::T == 64 ? 64 * kProbeWaves : G::T, G::T == 64 ? LACX_PROBE_WAVES : 4) void k_analyze(BatchRef br, int probe_class, uint32_t one_block,
+__global__ __launch_bounds__(G::T <= 64 ? 64 * kProbeWaves : G::T, G::T <= 64 ? LACX_PROBE_WAVES : 4) void k_analyze(BatchRef br, int probe_class, uint32_t one_block,
                                                   int which_base, const LpcSet* __restrict__ lpcs,
                                                   const uint32_t* __restrict__ need,
                                                   ChannelPlan* __restrict__ plans,
@@ -850,8 +867,8 @@ __global__ __launch_bounds__(G::T == 64 ? 64 * kProbeWaves : G::T, G::T == 64 ? 
     __shared__ uint32_t s_next;
     __shared__ PendingSlot s_pend;
     static_assert(sizeof(Smem<G>) % 16 == 0, "slot images are 16-byte aligned");
-    const int tid = G::T == 64 ? (int)(threadIdx.x & 63u) : (int)threadIdx.x;
-    unsigned char* smem_raw = smem_all + (G::T == 64 ? (size_t)(threadIdx.x >> 6) * sizeof(Smem<G>) : 0);
+    const int tid = G::T <= 64 ? (int)(threadIdx.x & (uint32_t)(G::SW - 1)) : (int)threadIdx.x;
+    unsigned char* smem_raw = smem_all + (G::T <= 64 ? (size_t)(threadIdx.x / (uint32_t)G::SW) * sizeof(Smem<G>) : 0);
     // the earliest start, kept inverted (the word starts as zero like everything else the call clears)
     if (t_first && tid == 0) atomicMax(t_first, ~(unsigned long long)__builtin_amdgcn_s_memrealtime());
     // Persistent form (work_ctr != nullptr; whole-block class only): one workgroup per CU takes virtual workgroup ids from
@@ -870,7 +887,7 @@ __global__ __launch_bounds__(G::T == 64 ? 64 * kProbeWaves : G::T, G::T == 64 ? 
     // blocks of the stream are handed out slot by slot (units pair_blocks ..), so that the tail of the kernel is balanced
     // in single slots as before.
     uint32_t rep = 0;         // channel slot of a pair unit
-    uint32_t v = G::T == 64 ? blockIdx.x * (uint32_t)kProbeWaves + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : blockIdx.x;  // virtual workgroup id
+    uint32_t v = G::T <= 64 ? blockIdx.x * (uint32_t)kProbeWaves + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : blockIdx.x;  // virtual workgroup id
     if (persistent) {
         if (tid == 0) {
             s_next = atomicAdd(work_ctr, 1u);
@@ -892,10 +909,12 @@ __global__ __launch_bounds__(G::T == 64 ? 64 * kProbeWaves : G::T, G::T == 64 ? 
         int which_in_block = -1;   // position of the slot among the block's needed whole-block slots
         uint32_t needed_slots = 0;
         StreamDesc sd;
-        if (probe_class) {
-            blk = v / 12u;
+        if (G::SW == 32 || probe_class) {
+            constexpr uint32_t kWavesPerBlock = 12u / (uint32_t)(64 / G::SW);
+            blk = v / kWavesPerBlock;
             sd = stream_of_block_uniform(br, blk);
-            const int s = 4 + (int)(v % 12u);
+            int s = 4 + (int)(v % kWavesPerBlock) * (64 / G::SW);
+            if (G::SW == 32 && upper_half()) s += 1;  // (per half)
             if (((uint32_t)__builtin_amdgcn_readfirstlane((int)need[blk]) >> s) & 1u) slot = s;
         } else {
             uint32_t wsel;
@@ -937,10 +956,11 @@ __global__ __launch_bounds__(G::T == 64 ? 64 * kProbeWaves : G::T, G::T == 64 ? 
                 m &= m - 1u;
             }
         }
-        if (slot >= 0) {  // uniform for the workgroup
+        if (slot >= 0) {  // uniform for the workgroup (two slots per wave: per half, the other half idles under the mask)
             const AnalyzeParams prm = sd.prm;
             const uint32_t lblk = blk - sd.first_block;
-            const SlotGeom g = slot_geom(prm, lblk, slot);
+            // (the two slots of a wave share their window: start and length stay in scalar registers)
+            const SlotGeom g = slot_geom(prm, lblk, G::SW == 32 ? __builtin_amdgcn_readfirstlane(slot & ~1) : slot);
             const uint32_t n = g.n;
             const size_t sidx = (size_t)blk * kSlotsPerBlock + slot;
             const SlotSrc src = slot_src(prm, sd.left, sd.right, slot & 3);
@@ -963,7 +983,7 @@ __global__ __launch_bounds__(G::T == 64 ? 64 * kProbeWaves : G::T, G::T == 64 ? 
             analyze_slot<G>(smem_raw, prm, n, src, g.start, &lpcs[sidx], &plans[sidx], slot_tid, fuse, fuse_idx, flag_byte,
                             (uint32_t)((slot & 3) >= 2 ? 1u : 0u), persistent ? &s_pend : nullptr);
             if (t_last && tid == 0) atomicMax(t_last, (unsigned long long)__builtin_amdgcn_s_memrealtime());
-            if constexpr (G::T == 64) {
+            if constexpr (G::T <= 64) {
                 // Probe class: the last of a block's twelve probe slots makes the block's LR/MS choice (front_ctr,
                 // kernels_internal.h).  The slot's size goes out once more with an agent-scope store and is waited for
                 // in front of the count; the last wave reads the twelve sizes with agent-scope loads (no fences).
@@ -976,7 +996,7 @@ __global__ __launch_bounds__(G::T == 64 ? 64 * kProbeWaves : G::T, G::T == 64 ? 
                         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                         last = atomicAdd(&front_ctr[(size_t)blk * 2 + 1], 1u) == 11u ? 1u : 0u;
                     }
-                    if (__builtin_amdgcn_readfirstlane((int)last)) {
+                    if (slot_first_u32<G::SW>(last)) {  // (at most one half: the twelve arrivals of a block are counted one by one)
                         if (tid == 0) front_ctr[(size_t)blk * 2 + 1] = 0u;
                         if (tid < 16) decide_probed_block(blk, tid, tail.bplans, tail.need_full_out, plans);
                     }
@@ -1014,7 +1034,7 @@ int debug_read_stamps(unsigned long long* out32) {
     return 0;
 #endif
 }
-size_t analyze_smem_bytes_probe() { return sizeof(Smem<GProbe>); }
+size_t analyze_smem_bytes_probe() { return sizeof(Smem<GProbe>) * kProbeSlotsPerWave; }
 
 // The opt-in to more than 64 KiB of dynamic LDS (hipFuncAttributeMaxDynamicSharedMemorySize) applies to the device
 // that is current when it is set, and one process may drive several devices (one encoder per lacx_config.device):
@@ -1034,7 +1054,7 @@ hipError_t ensure_kernel_attrs() {
     if (e == hipSuccess) e = set_kernel_attrs_front();
     if (e == hipSuccess)
         e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_analyze<GProbe>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(Smem<GProbe>) * kProbeWaves));
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(Smem<GProbe>) * kProbeSlotsPerWg));
     if (e == hipSuccess) e = set_kernel_attrs_emit();
     if (e == hipSuccess) done[dev] = true;
     return e;
@@ -1088,8 +1108,8 @@ hipError_t launch_analysis(const LaunchSet& ls, const DeviceWorkspace& ws, hipSt
                            sizeof(LevMem), st, r, w.acorr, w.need_probe, w.lpcs);
         if (mark && ev) (void)hipEventRecord(ev[1], st);
         if (any_auto) {
-            static_assert(12 % kProbeWaves == 0, "whole workgroups per block");
-            hipLaunchKernelGGL(k_analyze<GProbe>, dim3(cnt * (12u / kProbeWaves)), dim3(GProbe::T * kProbeWaves), sizeof(Smem<GProbe>) * kProbeWaves, st, r, 1, 0u, 0,
+            static_assert(12 % kProbeSlotsPerWg == 0, "whole workgroups per block");
+            hipLaunchKernelGGL(k_analyze<GProbe>, dim3(cnt * (12u / kProbeSlotsPerWg)), dim3(64 * kProbeWaves), sizeof(Smem<GProbe>) * kProbeSlotsPerWg, st, r, 1, 0u, 0,
                                w.lpcs, w.need_probe, w.plans, (unsigned long long*)nullptr, (unsigned long long*)nullptr, FuseArgs{},
                                (uint32_t*)nullptr, 0u, 0u, TailArgs<GProbe>{fc, w.bplans, w.need_full});
             if (!fc) hipLaunchKernelGGL(k_decide, dim3((cnt + 3) / 4), dim3(64), 0, st, r, 1, w.bplans, w.need_probe, w.need_full, w.plans);

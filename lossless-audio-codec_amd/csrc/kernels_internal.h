@@ -7,7 +7,17 @@
 namespace lacx {
 
 using GFull = Geo<16, 1024>;
+// Probe class: a 256-sample slot as 32 lanes x 8 samples, two independent slots in the halves of one wave (the fixed
+// wave-level work of a slot -- scans, k-sums, partition search -- is paid once for both).  -DLACX_PROBE_HALVES=0 rebuilds
+// the earlier form, one wave of 64 lanes x 4 samples per slot.
+#ifndef LACX_PROBE_HALVES
+#define LACX_PROBE_HALVES 1
+#endif
+#if LACX_PROBE_HALVES
+using GProbe = Geo<8, 32>;
+#else
 using GProbe = Geo<4, 64>;
+#endif
 constexpr int kMaxDevices = 64;
 
 // k_front.hip

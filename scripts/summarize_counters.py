@@ -33,7 +33,7 @@ prof = os.path.join(root, "profiles")
 def short(name):
     n = name.replace("void lacx::", "").replace("lacx::", "")
     n = n.split("(")[0]
-    return n.replace("Geo<16, 1024> ", "16,1024").replace("Geo<4, 64> ", "4,64").replace("<<", "<").replace(" >", ">")
+    return n.replace("Geo<16, 1024> ", "16,1024").replace("Geo<4, 64> ", "4,64").replace("Geo<8, 32> ", "8,32").replace("<<", "<").replace(" >", ">")
 
 
 agg = collections.defaultdict(lambda: collections.defaultdict(list))
