@@ -402,13 +402,21 @@ class Encoder:
             _raise(h, rc)
         return _take(out, size)
 
-    def analyze_device(self, d_left_ptr: int, d_right_ptr: int | None, frames: int, stream: int = 0):
-        """Runs the kernels on device-resident PCM and returns nothing (plans stay in the encoder)."""
+    def analyze_device(self, d_left_ptr: int, d_right_ptr: int | None, frames: int, stream: int = 0, plans: bool = False):
+        """Runs the kernels on device-resident PCM.  plans=False: returns nothing (the records stay in the encoder);
+        plans=True: (block_plans, channel_plans[nblocks*16]) as lacx_analyze returns them."""
         h = self._handle()
+        bplans = cplans = None
+        if plans:
+            nb = (frames + MAX_BLOCK - 1) // MAX_BLOCK
+            bplans = (BlockPlan * nb)()
+            cplans = (ChannelPlan * (nb * SLOTS))()
         rc = lib().lacx_analyze_device(h, C.c_void_p(d_left_ptr), C.c_void_p(d_right_ptr or 0), C.c_uint64(frames),
-                                       C.c_void_p(stream), None, None)
+                                       C.c_void_p(stream), bplans, cplans)
         if rc != OK:
             _raise(h, rc)
+        if plans:
+            return bplans, cplans
 
     def encode_shard_device_view(self, d_left_ptr: int, d_right_ptr: int | None, h_left, h_right, frames: int,
                                  stream: int = 0):

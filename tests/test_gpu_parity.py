@@ -9,6 +9,8 @@ import os
 import numpy as np
 import pytest
 
+import planref
+
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -51,17 +53,6 @@ def test_lpc_kernels_match_oracle(gpu, oracle, kind, bit_depth):
             assert np.array_equal(coef[ci][1:cand + 1], oc[1:cand + 1])
 
 
-def _check_plan(pl, op, nbytes):
-    assert pl.valid == 1
-    assert (pl.predictor_type, pl.order, pl.partition_order, pl.total_bits) == \
-        (op.predictor_type, op.order, op.partition_order, op.total_bits)
-    if op.predictor_type == 2:
-        assert [pl.coef[i] for i in range(op.order)] == [op.coeffs_q15[i + 1] for i in range(op.order)]
-    assert [pl.part_mode_k[i] for i in range(op.part_count)] == \
-        [(op.part_mode[i] << 5) | op.part_k[i] for i in range(op.part_count)]
-    assert pl.payload_bytes == nbytes
-
-
 @pytest.mark.parametrize("kind", KINDS)
 def test_block_plans_match_oracle(gpu, oracle, kind):
     """k_analyze<16,1024> decisions (predictor, coefficients, partition order, modes, k, exact bits)."""
@@ -71,7 +62,7 @@ def test_block_plans_match_oracle(gpu, oracle, kind):
     for x in (left[:16384], s[16384:32768], m[32768:], right[3:4100], left[7:40], s[9:40], m[:1], left[:2],
               right[:13], s[1000:1256], left[:13312], m[:12289]):
         pl = be.plan(x)
-        _check_plan(pl, oracle.block_plan(x), len(oracle.block_encode(x)))
+        planref.check_slot(pl, planref.slot_record(oracle, x))  # every field (planref.slot_diffs)
         assert be.encode(x) == oracle.block_encode(x)
 
 

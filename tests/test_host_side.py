@@ -20,51 +20,12 @@ def test_library_exports_every_declared_symbol(pkg):
     assert set(pkg.lacx.EXPORTS) <= declared
 
 
-def _oracle_plans(pkg, oracle, left, right, sm, zr=True, pt=True):
-    lacx = pkg.lacx
-    n = left.size
-    nb = (n + 16383) // 16384
-    bplans = (lacx.BlockPlan * nb)()
-    plans = (lacx.ChannelPlan * (nb * 16))()
+def _oracle_plans(pkg, oracle, left, right, sm, zr=True, pt=True, chosen_only=False):
+    """The oracle's decisions as the C ABI's plan arrays (tests/planref.py): every slot the device would leave valid, or
+    only the pair that is emitted."""
+    import planref
 
-    def fill(dst, x):
-        op = oracle.block_plan(x, zr, pt)
-        dst.predictor_type, dst.order, dst.partition_order, dst.valid = op.predictor_type, op.order, op.partition_order, 1
-        for i in range(12):
-            dst.coef[i] = op.coeffs_q15[i + 1]
-        dst.total_bits = op.total_bits
-        dst.payload_bytes = len(oracle.block_encode(x, zr, pt))
-        for i in range(op.part_count):
-            dst.part_mode_k[i] = (op.part_mode[i] << 5) | op.part_k[i]
-
-    for b in range(nb):
-        l = left[b * 16384:(b + 1) * 16384]
-        bplans[b].frames = l.size
-        if right is None:
-            fill(plans[b * 16], l)
-            continue
-        r = right[b * 16384:(b + 1) * 16384]
-        m = ((l.astype(np.int64) + r) >> 1).astype(np.int32)
-        s = (l - r).astype(np.int32)
-        chans = [l, r, m, s]
-        size = lambda x: len(oracle.block_encode(x, zr, pt))  # noqa: E731
-        if sm in (0, 1):
-            ms = sm
-        else:
-            st = oracle.stereo_estimate(l, r)
-            ms = st.choose_ms
-            if st.uncertain:
-                if l.size <= 4096:
-                    ms = int(size(m) + size(s) < size(l) + size(r))
-                else:
-                    starts = [0, (l.size - 256) // 2, l.size - 256]
-                    lr = sum(size(c[a:a + 256]) for a in starts for c in (l, r))
-                    mss = sum(size(c[a:a + 256]) for a in starts for c in (m, s))
-                    ms = int(mss < lr)
-        bplans[b].choose_ms = ms
-        for c in ((2, 3) if ms else (0, 1)):
-            fill(plans[b * 16 + c], chans[c])
-    return bplans, plans
+    return planref.to_ctypes(pkg.lacx, planref.expected_stream(oracle, left, right, sm, zr, pt, chosen_only))
 
 
 @pytest.mark.parametrize("case", [(16, 48000, "music", 2, 2), (24, 96000, "mixed", 2, 2), (16, 48000, "noise", 2, 2),
