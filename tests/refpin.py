@@ -10,7 +10,10 @@ interface in every case:
     sha256) that compare equal to exactly the bytes / samples the reference returned; small results come back as
     they are;
   * LACX_REF_RECORD=1 (with oracle/_ref present): the live reference, and the answers are written to the fixture when
-    the process ends:  LACX_REF_RECORD=1 python -m pytest tests/test_oracle_vs_ref.py tests/test_wav_ingest.py
+    the process ends:  LACX_REF_RECORD=1 python -m pytest tests/test_oracle_vs_ref.py tests/test_wav_ingest.py \
+                                                          tests/test_lacgrammar_host.py
+
+A decode the reference refuses is an answer too: it is pinned with its message and replayed as the same RuntimeError.
 
 Calls are keyed by the function name and a digest of their arguments (arrays by value, a WAV path by file content).
 """
@@ -155,11 +158,19 @@ class _Reference:
             if key not in self.answers:
                 raise KeyError(f"no pinned reference answer for this {name} call: re-record {ANSWERS} where oracle/_ref exists")
             return _pinned_result(name, _dec(self.answers[key]))
-        got = getattr(refshim, name)(*args, **kwargs)
+        refusal = None
+        try:
+            got = getattr(refshim, name)(*args, **kwargs)
+        except RuntimeError as err:
+            if name != "decode":
+                raise
+            got, refusal = Refused(str(err)), err
         if self.mode == "record":
             self.recorded[key] = _enc_result(name, got)
         elif key not in self.answers or self.answers[key] != _enc_result(name, got):
             raise AssertionError(f"{ANSWERS} does not hold the reference's answer to this {name} call: re-record it")
+        if refusal is not None:
+            raise refusal
         return got
 
     def __getattr__(self, name):
@@ -168,13 +179,24 @@ class _Reference:
         return lambda *args, **kwargs: self._call(name, args, kwargs)
 
 
+class Refused:
+    """A decode the reference refused: pinned with its message, replayed as the RuntimeError the live call raises."""
+
+    def __init__(self, message: str):
+        self.message = message
+
+
 def _enc_result(name, got):
+    if isinstance(got, Refused):
+        return {"refused": got.message}
     if name == "lpc_analyze":  # (orders used, int16 coefficients) kept by value
         return {"tuple": [int(got[0]), [int(x) for x in got[1]]]}
     return _enc(got)
 
 
 def _pinned_result(name, v):
+    if isinstance(v, dict) and "refused" in v:
+        raise RuntimeError(v["refused"])
     if name == "lpc_analyze":
         used, co = v
         return used, np.asarray(co, dtype=np.int16)

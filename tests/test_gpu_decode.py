@@ -10,6 +10,7 @@ import pytest
 
 import __graft_entry__ as ge
 import oracleshim
+from lacgrammar import Bits as _Bits, zigzag as _zigzag
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -172,31 +173,6 @@ def test_damaged_streams_are_refused(gpu):
             assert l2.size == left.size
         except RuntimeError as err:
             assert "decode-error" in str(err)
-
-
-class _Bits:
-    """MSB-first bit writer (the layout of ref src/codec/bitstream/bit_writer.cpp), for hand-made channel blocks."""
-
-    def __init__(self):
-        self.v, self.n = 0, 0
-
-    def put(self, value, bits):
-        assert 0 <= value < (1 << bits) or bits == 0
-        self.v = (self.v << bits) | value
-        self.n += bits
-
-    def rice(self, u, k):
-        self.put((1 << (u >> k)) - 1, u >> k)  # unary quotient: ones ...
-        self.put(0, 1)                         # ... and their terminator
-        self.put(u & ((1 << k) - 1), k)
-
-    def bytes(self):
-        pad = (-self.n) % 8
-        return ((self.v << pad)).to_bytes((self.n + pad) // 8, "big")
-
-
-def _zigzag(x):
-    return (x << 1) ^ (x >> 63)
 
 
 def test_foreign_streams_high_lpc_orders_and_escapes(gpu, oracle):
