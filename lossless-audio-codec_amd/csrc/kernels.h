@@ -178,7 +178,7 @@ hipError_t launch_stream_out(const LaunchSet& ls, const DeviceWorkspace& ws, uin
 // [total_blocks + 1] prefix sums over the concatenated payloads and frames; status[blk] = 0 or an error code and
 // ms_flag[blk] = the block's LR/MS flag, per global block.  The payload must be followed by kDecodeTailPad readable zero
 // bytes (the bit reader's bounded look-ahead past the last block, see BitIn).
-constexpr size_t kDecodeTailPad = 128;
+// (kDecodeTailPad: lacx_types.h)
 struct DecodeItem {
     int32_t* left;                // the item's PCM from its frame 0 (16-byte aligned in the WAV form)
     int32_t* right;               // null for mono

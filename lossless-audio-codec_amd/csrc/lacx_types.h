@@ -1,5 +1,6 @@
 // lacx_types.h -- records exchanged between the HIP kernels and the host side of the encoder.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 namespace lacx {
@@ -8,6 +9,8 @@ constexpr int kMaxBlock = 16384;  // Block::MAX_BLOCK_SIZE        (ref src/codec
 constexpr int kMaxParts = 256;    // 1 << MAX_PARTITION_ORDER     (ref constants.hpp:11)
 constexpr int kMinPartition = 32; // MIN_PARTITION_SIZE           (ref constants.hpp:10)
 constexpr int kMaxPartitionOrder = 8;
+// zero bytes behind the decoder's payload buffer: the bit reader's bounded look-ahead past the last block (decode_core.h)
+constexpr size_t kDecodeTailPad = 128;
 constexpr int kProbe = 256;             // kStereoProbeSize             (ref src/codec/lac/encoder.cpp:19)
 constexpr int kFullCompareLimit = 4096; // kStereoFullComparisonLimit   (ref lac/encoder.cpp:20)
 

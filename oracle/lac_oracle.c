@@ -1066,7 +1066,11 @@ typedef struct {
     const uint8_t* d;
     uint64_t nbits, pos;
     int err;
+    uint32_t maxu; /* the largest zigzag residual value decoded through this reader (laco_decode_ex) */
 } bitr;
+static void seen(bitr* r, uint32_t u) {
+    if (u > r->maxu) r->maxu = u;
+}
 
 static uint32_t br_bit(bitr* r) {
     if (r->pos >= r->nbits) {
@@ -1117,6 +1121,7 @@ static int decode_segment(bitr* r, uint32_t samples, uint32_t k0, uint8_t mode, 
         for (uint32_t i = 0; i < samples; ++i) {
             uint32_t u;
             if (!read_rice_unsigned(r, k, &u)) return 0;
+            seen(r, u);
             res[i] = unzigzag(u);
             sum += u;
             ++count;
@@ -1128,6 +1133,7 @@ static int decode_segment(bitr* r, uint32_t samples, uint32_t k0, uint8_t mode, 
         for (uint32_t i = 0; i < samples; ++i) {
             uint32_t u;
             if (!read_rice_unsigned(r, k0, &u)) return 0;
+            seen(r, u);
             res[i] = unzigzag(u);
         }
         return 1;
@@ -1149,6 +1155,7 @@ static int decode_segment(bitr* r, uint32_t samples, uint32_t k0, uint8_t mode, 
             } else {
                 u = 0;
             }
+            seen(r, u);
             res[i] = v;
             sum += u;
             ++count;
@@ -1164,6 +1171,7 @@ static int decode_segment(bitr* r, uint32_t samples, uint32_t k0, uint8_t mode, 
         if (tag == 0) {
             uint32_t u;
             if (!read_rice_unsigned(r, k, &u)) return 0;
+            seen(r, u);
             res[idx++] = unzigzag(u);
             sum += u;
             ++count;
@@ -1187,6 +1195,7 @@ static int decode_segment(bitr* r, uint32_t samples, uint32_t k0, uint8_t mode, 
         } else {
             const uint32_t zz = br_bits(r, 32);
             if (r->err) return 0;
+            seen(r, zz);
             const int32_t v = unzigzag(zz);
             res[idx++] = v;
             sum += zigzag(v);
@@ -1273,60 +1282,93 @@ static int decode_channel_block(bitr* r, uint32_t n, int32_t* out) { /* block/de
     return 1;
 }
 
-int laco_decode(const uint8_t* data, uint64_t size, int32_t** left, int32_t** right, uint64_t* frames,
-                int* channels, uint32_t* sample_rate, int* bit_depth, int* stereo_mode) {
-    if (size < 14 || data[0] != 0x4C || data[1] != 0x41 || data[2] != 3) return 1;
+/* One block of the container behind its table entry: the per-block stereo flag, the channel blocks, the mid/side inverse
+ * and the bit-depth check (lac/decoder.cpp:167-207).  The reader goes on from where it stands. */
+static int decode_stream_block(bitr* r, uint32_t n, int ch, int sm, int32_t* L, int32_t* R) {
+    int ms = (sm == 1);
+    if (n == 0 || n > (uint32_t)kMaxBlock) return 0;
+    if (ch == 2 && sm == 2) {
+        const uint32_t flag = br_bits(r, 8);
+        if (r->err || flag > 1) return 0;
+        ms = (int)flag;
+    }
+    if (!decode_channel_block(r, n, L)) return 0;
+    if (ch == 2 && !decode_channel_block(r, n, R)) return 0;
+    return 1 + ms;
+}
+static int finish_stream_block(uint32_t n, int ch, int ms, int bd, int32_t* L, int32_t* R) {
+    const int32_t lo = bd == 16 ? -32768 : -0x800000, hi = bd == 16 ? 32767 : 0x7FFFFF;
+    if (ch == 2 && ms) { /* lac/decoder.cpp:48-65 */
+        for (uint32_t i = 0; i < n; ++i) {
+            const int64_t m = L[i], s = R[i];
+            const int64_t l = m + ((s + (s & 1)) >> 1);
+            const int64_t rr = l - s;
+            L[i] = (int32_t)l;
+            R[i] = (int32_t)rr;
+        }
+    }
+    for (uint32_t i = 0; i < n; ++i) {
+        if (L[i] < lo || L[i] > hi) return 0;
+        if (ch == 2 && (R[i] < lo || R[i] > hi)) return 0;
+    }
+    return 1;
+}
+
+int laco_channel_block_end(const uint8_t* data, uint64_t size, uint32_t n, uint64_t* end_bits) {
+    if (n == 0 || n > (uint32_t)kMaxBlock) return 1;
+    int32_t* out = (int32_t*)malloc(sizeof(int32_t) * n);
+    bitr r = {data, 8ull * size, 0, 0, 0};
+    const int ok = decode_channel_block(&r, n, out);
+    free(out);
+    if (ok) *end_bits = r.pos;
+    return !ok;
+}
+
+int laco_decode_ex(const uint8_t* data, uint64_t size, int32_t** left, int32_t** right, uint64_t* frames,
+                   int* channels, uint32_t* sample_rate, int* bit_depth, int* stereo_mode, uint32_t* bad_block,
+                   uint32_t* max_zigzag) {
+    if (bad_block) *bad_block = ~0u;
+    if (max_zigzag) *max_zigzag = 0;
+    if (size < 14 || data[0] != 0x4C || data[1] != 0x41 || (data[2] != 3 && data[2] != 2)) return 1;
+    const int v3 = data[2] == 3;
     const int ch = data[3], sm = data[4];
     const uint32_t sr = ((uint32_t)data[5] << 8) | data[6] | ((uint32_t)data[7] << 16);
     const int bd = data[8];
     if ((ch != 1 && ch != 2) || sm > 2 || (bd != 16 && bd != 24) || data[9] != 0) return 1;
     const uint32_t nb = ((uint32_t)data[10] << 24) | ((uint32_t)data[11] << 16) | ((uint32_t)data[12] << 8) | data[13];
-    if (size < 14 + 8ull * nb) return 1;
+    const uint64_t entry = v3 ? 8u : 4u;
+    if (size < 14 + entry * nb) return 1;
     uint64_t total = 0, pay = 0;
     for (uint32_t b = 0; b < nb; ++b) {
-        const uint8_t* e = data + 14 + 8ull * b;
+        const uint8_t* e = data + 14 + entry * b;
         total += ((uint32_t)e[0] << 24) | ((uint32_t)e[1] << 16) | ((uint32_t)e[2] << 8) | e[3];
-        pay += ((uint32_t)e[4] << 24) | ((uint32_t)e[5] << 16) | ((uint32_t)e[6] << 8) | e[7];
+        if (v3) pay += ((uint32_t)e[4] << 24) | ((uint32_t)e[5] << 16) | ((uint32_t)e[6] << 8) | e[7];
     }
-    if (14 + 8ull * nb + pay != size) return 1;
+    if (v3 && 14 + 8ull * nb + pay != size) return 1;
     int32_t* L = (int32_t*)malloc(sizeof(int32_t) * (total ? total : 1));
     int32_t* R = ch == 2 ? (int32_t*)malloc(sizeof(int32_t) * (total ? total : 1)) : NULL;
-    uint64_t off = 0, poff = 14 + 8ull * nb;
-    const int32_t lo = bd == 16 ? -32768 : -0x800000, hi = bd == 16 ? 32767 : 0x7FFFFF;
+    uint64_t off = 0, poff = 14 + entry * nb;
+    /* version 2 (lac/decoder.cpp:209-218): no compressed sizes, one reader walks the whole payload */
+    bitr whole = {data + poff, 8ull * (size - poff), 0, 0, 0};
+    uint32_t maxu = 0;
     int ok = 1;
     for (uint32_t b = 0; b < nb && ok; ++b) {
-        const uint8_t* e = data + 14 + 8ull * b;
+        const uint8_t* e = data + 14 + entry * b;
         const uint32_t n = ((uint32_t)e[0] << 24) | ((uint32_t)e[1] << 16) | ((uint32_t)e[2] << 8) | e[3];
-        const uint32_t by = ((uint32_t)e[4] << 24) | ((uint32_t)e[5] << 16) | ((uint32_t)e[6] << 8) | e[7];
-        bitr r = {data + poff, 8ull * by, 0, 0};
-        int ms = (sm == 1);
-        if (n == 0 || n > (uint32_t)kMaxBlock) ok = 0;
-        if (ok && ch == 2 && sm == 2) {
-            const uint32_t flag = br_bits(&r, 8);
-            if (flag > 1) ok = 0;
-            ms = (int)flag;
-        }
-        if (ok) ok = decode_channel_block(&r, n, L + off);
-        if (ok && ch == 2) ok = decode_channel_block(&r, n, R + off);
-        if (ok && r.pos != r.nbits) ok = 0;
-        if (ok && ch == 2 && ms) { /* lac/decoder.cpp:48-65 */
-            for (uint32_t i = 0; i < n; ++i) {
-                const int64_t m = L[off + i], s = R[off + i];
-                const int64_t l = m + ((s + (s & 1)) >> 1);
-                const int64_t rr = l - s;
-                L[off + i] = (int32_t)l;
-                R[off + i] = (int32_t)rr;
-            }
-        }
-        if (ok) {
-            for (uint32_t i = 0; i < n; ++i) {
-                if (L[off + i] < lo || L[off + i] > hi) ok = 0;
-                if (R && (R[off + i] < lo || R[off + i] > hi)) ok = 0;
-            }
-        }
+        const uint32_t by = v3 ? ((uint32_t)e[4] << 24) | ((uint32_t)e[5] << 16) | ((uint32_t)e[6] << 8) | e[7] : 0;
+        bitr own = {data + poff, 8ull * by, 0, 0, 0};
+        bitr* r = v3 ? &own : &whole;
+        const int got = decode_stream_block(r, n, ch, sm, L + off, R ? R + off : NULL);
+        if (r->maxu > maxu) maxu = r->maxu;
+        ok = got != 0;
+        if (ok && v3 && r->pos != r->nbits) ok = 0;
+        if (ok) ok = finish_stream_block(n, ch, got - 1, bd, L + off, R ? R + off : NULL);
+        if (ok && !v3 && b + 1 == nb && r->pos != r->nbits) ok = 0; /* trailing frame payload */
+        if (!ok && bad_block) *bad_block = b;
         off += n;
         poff += by;
     }
+    if (max_zigzag) *max_zigzag = maxu;
     if (!ok) {
         free(L);
         free(R);
@@ -1340,4 +1382,10 @@ int laco_decode(const uint8_t* data, uint64_t size, int32_t** left, int32_t** ri
     *bit_depth = bd;
     *stereo_mode = sm;
     return 0;
+}
+
+int laco_decode(const uint8_t* data, uint64_t size, int32_t** left, int32_t** right, uint64_t* frames,
+                int* channels, uint32_t* sample_rate, int* bit_depth, int* stereo_mode) {
+    if (size >= 3 && data[2] != 3) return 1; /* version 3 only, as ever */
+    return laco_decode_ex(data, size, left, right, frames, channels, sample_rate, bit_depth, stereo_mode, NULL, NULL);
 }

@@ -75,6 +75,18 @@ void laco_adapt_k_sequence(const uint32_t* u, uint32_t n, uint32_t* k_out);
 int laco_decode(const uint8_t* data, uint64_t size, int32_t** left, int32_t** right, uint64_t* frames,
                 int* channels, uint32_t* sample_rate, int* bit_depth, int* stereo_mode);
 
+/* laco_decode for version 3 and the legacy version 2 (no compressed sizes: one reader walks the payload,
+ * lac/decoder.cpp:209-218), which also reports where and how far it got: *bad_block = the index of the block it refused
+ * (~0 when it refused above block level, or accepted), *max_zigzag = the largest zigzag residual value it decoded before
+ * stopping or finishing.  Either may be NULL. */
+int laco_decode_ex(const uint8_t* data, uint64_t size, int32_t** left, int32_t** right, uint64_t* frames,
+                   int* channels, uint32_t* sample_rate, int* bit_depth, int* stereo_mode, uint32_t* bad_block,
+                   uint32_t* max_zigzag);
+
+/* Where a channel block of n samples that starts at data[0] ends, in bits (byte padding included): the tests use it to
+ * find the second channel block of a stereo block.  Returns 0 ok. */
+int laco_channel_block_end(const uint8_t* data, uint64_t size, uint32_t n, uint64_t* end_bits);
+
 #ifdef __cplusplus
 }
 #endif

@@ -156,3 +156,34 @@ def decode(data: bytes):
         lib().laco_free(rp)
     return left, right, dict(channels=ch.value, sample_rate=sr.value, bit_depth=bd.value,
                              stereo_mode=sm.value)
+
+
+def decode_ex(data: bytes):
+    """laco_decode_ex: version 3 and version 2.  Returns (left, right, bad_block, max_zigzag): left is None where the
+    oracle refuses, bad_block then the block it refused (None: above block level)."""
+    buf = (C.c_uint8 * len(data)).from_buffer_copy(data)
+    lp = C.POINTER(C.c_int32)()
+    rp = C.POINTER(C.c_int32)()
+    frames = C.c_uint64()
+    ch, sr, bd, sm = C.c_int(), C.c_uint32(), C.c_int(), C.c_int()
+    bad, maxu = C.c_uint32(), C.c_uint32()
+    rc = lib().laco_decode_ex(buf, C.c_uint64(len(data)), C.byref(lp), C.byref(rp), C.byref(frames), C.byref(ch),
+                              C.byref(sr), C.byref(bd), C.byref(sm), C.byref(bad), C.byref(maxu))
+    if rc != 0:
+        return None, None, (None if bad.value == 0xFFFFFFFF else bad.value), maxu.value
+    n = frames.value
+    left = np.ctypeslib.as_array(lp, shape=(n,)).copy() if n else np.zeros(0, np.int32)
+    lib().laco_free(lp)
+    right = None
+    if ch.value == 2:
+        right = np.ctypeslib.as_array(rp, shape=(n,)).copy() if n else np.zeros(0, np.int32)
+        lib().laco_free(rp)
+    return left, right, None, maxu.value
+
+
+def channel_block_end(data: bytes, n: int):
+    """Bytes a channel block of n samples at the start of `data` takes, or None where it does not decode."""
+    end = C.c_uint64()
+    if lib().laco_channel_block_end(data, C.c_uint64(len(data)), C.c_uint32(n), C.byref(end)) != 0:
+        return None
+    return end.value // 8
