@@ -96,6 +96,19 @@ def slot_record(oracle, x, zr=True, pt=True, start=0) -> SlotRecord:
                       len(oracle.block_encode(x, zr, pt)), start, int(np.asarray(x).size))
 
 
+def wide_slot_record(oracle, x, zr=True, pt=True) -> SlotRecord:
+    """slot_record for Block::Encoder's whole int32 domain (csrc/wide.hip).  `payload_bytes` is what the plan itself
+    implies, (16 header bits + 16 per LPC coefficient + total_bits) >> 3, not the emitted length: at k = 31 the reference's
+    estimate drops the quotient that its emit writes (csrc/api_encode.cpp, lacx_block_encode), so the two can differ
+    there, and the emitted length is checked through the bytes themselves."""
+    op = oracle.block_plan(x, zr, pt)
+    coef = tuple(int(op.coeffs_q15[i + 1]) for i in range(op.order)) if op.predictor_type == 2 else ()
+    pmk = tuple((int(op.part_mode[i]) << 5) | int(op.part_k[i]) for i in range(op.part_count))
+    payload = (16 + (16 * int(op.order) if op.predictor_type == 2 else 0) + int(op.total_bits)) >> 3
+    return SlotRecord(int(op.predictor_type), int(op.order), int(op.partition_order), coef, pmk, int(op.total_bits),
+                      payload, 0, int(np.asarray(x).size))
+
+
 def expected_block(oracle, l, r, stereo_mode, zr=True, pt=True, chosen_only=False, records=True) -> BlockRecord:
     """The expectation of one block (r is None: mono).  chosen_only: only the pair (or the mono slot) that is emitted,
     which is all lacx_emit_from_plans needs.  records=False: a whole-block slot whose record decides nothing is expected
