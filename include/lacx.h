@@ -31,6 +31,9 @@
  *   lacx_decoder_decode_wav <- the `decode` command's WAV writer ref src/main.cpp:127-182, 184-431
  *   lacx_decoder_decode_wav_batch_view, lacx_decoder_decode_batch_device <- many .lac streams as one device job
  *   lacx_decoder_decode_window, lacx_decoder_decode_window_batch_device <- frame windows of many streams as one job
+ *   lacx_decoder_verify_batch_device,
+ *   lacx_decoder_verify_wav <- the roundtrip comparison of `lac_cli selftest` (ref src/main.cpp:803-909) and of an
+ *                             archive's "decode it again and compare" step: streams against their source PCM, on the device
  *
  * All analysis (and the decode) runs in hand-written HIP kernels on a gfx950 device; there is no CPU fallback: every
  * call that needs the device fails with LACX_E_DEVICE when none is usable.
@@ -48,6 +51,7 @@ extern "C" {
 #define LACX_E_INVALID 1 /* maps to std::invalid_argument (ref lac/encoder.cpp:220-241) */
 #define LACX_E_RUNTIME 2 /* maps to std::runtime_error   (ref lac/encoder.cpp:447-449) */
 #define LACX_E_DEVICE 3  /* HIP failure / no device: std::runtime_error in the C++ mirror */
+#define LACX_E_MISMATCH 4 /* the stream decodes, but not to the given PCM */
 
 #define LACX_MAX_BLOCK 16384u
 #define LACX_SLOTS_PER_BLOCK 16u /* slot = window*4 + channel(L,R,M,S); window 0 = whole block, 1..3 = probes */
@@ -133,7 +137,7 @@ void lacx_get_timing(const lacx_encoder* enc, lacx_timing* out);
 
 /* sizeof() of a public struct as this library was built, by name without the prefix ("config", "channel_plan",
  * "block_plan", "timing", "pcm", "batch_item", "batch_out", "wav_info", "fanout_shard", "fanout_out", "fanout_stats",
- * "stream_info", "span", "decode_item", "window_item"); 0 for an unknown name.  A binding that declares the structs itself (ctypes, cgo, JNI) checks its layout
+ * "stream_info", "span", "decode_item", "window_item", "verify_item", "verify_result"); 0 for an unknown name.  A binding that declares the structs itself (ctypes, cgo, JNI) checks its layout
  * against this before the first call that fills one. */
 uint32_t lacx_sizeof(const char* struct_name);
 
@@ -436,6 +440,46 @@ int lacx_decoder_decode_window_batch_device(lacx_decoder* dec, const lacx_window
                                             void* stream, int* item_rc, float* device_ms);
 int lacx_decoder_decode_window(lacx_decoder* dec, const uint8_t* lac, uint64_t size, uint64_t start, uint64_t frames,
                                int sample_type, void* left, void* right, float* device_ms);
+
+/* Verification: does a .lac decode to exactly the PCM it was made from?  The stream is decoded into the decoder's own
+ * buffers and compared there, sample by sample as full int32 values, with the source PCM in the source's own layout
+ * (lacx_pcm, as on the encode side: planar int32 with 4-byte aligned arrays, interleaved int16 with a 4-byte aligned
+ * base, packed interleaved int24 at any byte alignment); no PCM crosses PCIe towards the host, only 32 bytes per item.
+ * Nothing outside [data, data + frames * channels * bytes per sample) of an interleaved source, or outside [0, frames)
+ * of a planar array, is read.
+ * lacx_decoder_verify_batch_device: many streams as one device job, versions 3 and 2.  Per-item outcome, return code,
+ * lacx_decoder_item_error, device-less behaviour and `stream` exactly as lacx_decoder_decode_batch_device.  Checked per
+ * item on the host before any device call, each LACX_E_INVALID: "unknown source layout", "source channel count does not
+ * match the stream", "source arrays missing", "source frame count does not match the stream", "source layout does not
+ * match the stream's bit depth" (an interleaved layout fixes the depth), "source arrays are not 4-byte aligned".  An item
+ * that does not decode gets the decode's own code and message and a zeroed result.  An item that decodes to something
+ * else gets LACX_E_MISMATCH, its result filled, and the message
+ *   [verify-error] block=N channel=left|right frame=F decoded=X source=Y mismatches=M
+ * results (nullable, n entries): all zero for an item that is identical to its source (and for one that failed).
+ * lacx_decoder_verify_wav: a stream against a WAV file image in host memory (lacx_wav_parse's rules; an image it refuses
+ * gives LACX_E_INVALID).  A difference in format gives LACX_E_MISMATCH "[verify-error] <field>: stream A, source B"
+ * (field: channels, bit depth, sample rate, frames) without touching the device, and a zeroed result.  Otherwise the data
+ * chunk is uploaded as it is, 2 or 3 bytes per sample, into the decoder's payload buffer behind the payload, and compared
+ * as a batch of one: the message carries no "stream 0: ".
+ * device_ms (nullable): kernel time (decode and compare). */
+typedef struct lacx_verify_item {   /* 48 bytes */
+    const uint8_t* lac;
+    uint64_t size;
+    lacx_pcm pcm;                   /* device-resident source, any LACX_PCM_* layout */
+    uint64_t frames;
+} lacx_verify_item;
+typedef struct lacx_verify_result { /* 32 bytes */
+    uint64_t mismatches;            /* samples that differ; 0 = identical */
+    uint64_t frame;                 /* lowest differing frame (then lowest channel) */
+    uint32_t block;                 /* the block of that frame, counted in the stream */
+    uint8_t channel;
+    uint8_t reserved[3];
+    int32_t decoded, source;        /* the two values there */
+} lacx_verify_result;
+int lacx_decoder_verify_batch_device(lacx_decoder* dec, const lacx_verify_item* items, uint32_t n, void* stream,
+                                     int* item_rc, lacx_verify_result* results, float* device_ms);
+int lacx_decoder_verify_wav(lacx_decoder* dec, const uint8_t* lac, uint64_t size, const uint8_t* wav, uint64_t wav_size,
+                            lacx_verify_result* result, float* device_ms);
 
 /* Block::Encoder::encode drop-in for one channel block of n <= 16384 samples of ANY int32 value: blocks inside the 25-bit
  * mid/side domain of validated 16 / 24-bit input run on the streaming kernels, wider ones on a kernel of their own that

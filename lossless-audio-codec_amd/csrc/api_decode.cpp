@@ -283,12 +283,19 @@ struct BatchIn {
     int32_t* right;
     uint64_t frames;
     uint64_t start = 0;
+    // verify form: the source PCM (device-resident), or -- lacx_decoder_verify_wav, a batch of one -- the WAV data chunk
+    // in host memory, which the decoder uploads behind the payload and pcm.data0 then points at
+    lacx_pcm pcm = {nullptr, nullptr, 0, 0};
+    const uint8_t* host_src = nullptr;
+    uint64_t host_src_bytes = 0;
 };
 
 // Where the decoded items go.  wav: the images into the decoder's pinned image buffer (out[i]: each item's, 16-byte
 // aligned, one D2H copy for all).  device: the caller's device arrays, in place, on the caller's stream.  host: the
 // decoder's own PCM buffers, then, once the statuses are checked, the caller's host arrays of the items that decoded.
-enum class DecodeTo { wav, device, host };
+// verify: the decoder's own PCM buffers, compared there with each item's source PCM (k_verify in place of the other post
+// passes, on the caller's stream); what comes back is vres[i] and, for an item that differs, LACX_E_MISMATCH.
+enum class DecodeTo { wav, device, host, verify };
 
 // The decoder: n streams as one decode (a single stream is n = 1).  Every item is parsed on the host first; those that
 // parse go to the device together: their payloads back to back in one buffer (the tail pad after the last), their block
@@ -302,9 +309,12 @@ enum class DecodeTo { wav, device, host };
 // compressed sizes) decodes in full and is then windowed.  The host form's windows go through the decoder's image
 // buffer, copied to the caller once the statuses are checked.
 int decode_batch_run(lacx_decoder* d, const BatchIn* in, uint32_t n, DecodeTo to, hipStream_t stream, lacx_span* out,
-                     std::vector<int>& code, std::vector<std::string>& err, float* device_ms, int window = -1) {
+                     std::vector<int>& code, std::vector<std::string>& err, float* device_ms, int window = -1,
+                     lacx_verify_result* vres = nullptr) {
     if (device_ms) *device_ms = 0.f;
     const bool wav = to == DecodeTo::wav, own_pcm = to != DecodeTo::device || window >= 0;  // own_pcm: into d->d_left / d_right
+    const bool verify = to == DecodeTo::verify;
+    if (vres) std::memset(vres, 0, sizeof(lacx_verify_result) * n);
     code.assign(n, LACX_OK);
     err.assign(n, std::string());
     std::vector<lacx_stream_info> info(n);
@@ -316,6 +326,19 @@ int decode_batch_run(lacx_decoder* d, const BatchIn* in, uint32_t n, DecodeTo to
             if (in[i].frames == 0) c = decode_fail(LACX_E_INVALID, "empty window");
             else if (in[i].start >= total || in[i].frames > total - in[i].start) c = decode_fail(LACX_E_INVALID, "window outside the stream");
             else if (!in[i].left || (info[i].channels == 2 && !in[i].right)) c = decode_fail(LACX_E_INVALID, "output arrays missing");
+        } else if (c == LACX_OK && verify) {  // the source against the stream
+            const lacx_pcm& p = in[i].pcm;
+            const uintptr_t a0 = (uintptr_t)p.data0, a1 = (uintptr_t)p.data1;
+            const bool planar = p.layout == LACX_PCM_PLANAR_I32;
+            if (p.layout > LACX_PCM_INTERLEAVED_I24) c = decode_fail(LACX_E_INVALID, "unknown source layout");
+            else if (p.channels != info[i].channels) c = decode_fail(LACX_E_INVALID, "source channel count does not match the stream");
+            else if ((!p.data0 && !in[i].host_src) || (planar && p.channels == 2 && !p.data1)) c = decode_fail(LACX_E_INVALID, "source arrays missing");
+            else if (in[i].frames != info[i].frames) c = decode_fail(LACX_E_INVALID, "source frame count does not match the stream");
+            else if ((p.layout == LACX_PCM_INTERLEAVED_I16 && info[i].bit_depth != 16) ||
+                     (p.layout == LACX_PCM_INTERLEAVED_I24 && info[i].bit_depth != 24))
+                c = decode_fail(LACX_E_INVALID, "source layout does not match the stream's bit depth");
+            else if ((p.layout != LACX_PCM_INTERLEAVED_I24 && (a0 & 3u)) || (planar && (a1 & 3u)))
+                c = decode_fail(LACX_E_INVALID, "source arrays are not 4-byte aligned");
         } else if (c == LACX_OK && !wav) {  // lacx_decoder_decode's checks of the output arrays
             if (!in[i].left || (info[i].channels == 2 && !in[i].right)) c = decode_fail(LACX_E_INVALID, "output arrays missing");
             else if (in[i].frames != info[i].frames)
@@ -366,6 +389,7 @@ int decode_batch_run(lacx_decoder* d, const BatchIn* in, uint32_t n, DecodeTo to
             image_total += 4 * out_words;
             total_units += (frames + 3u) / 4u;
         }
+        if (verify) total_units += (frames + 3u) / 4u;
         blk_first.push_back(b0);
         pay_src.push_back(src);
         pay_bytes.push_back(bytes);
@@ -420,7 +444,11 @@ int decode_batch_run(lacx_decoder* d, const BatchIn* in, uint32_t n, DecodeTo to
         }                                                                                                    \
     } while (0)
         const char* what = "";
-        hipStream_t st = to == DecodeTo::device ? stream : d->stream;
+        // the verify form of a WAV image in host memory (a batch of one): the data chunk behind the payload and its pad
+        const uint8_t* host_src = verify && m == 1 ? in[dev[0]].host_src : nullptr;
+        const uint64_t host_src_bytes = host_src ? in[dev[0]].host_src_bytes : 0;
+        const uint64_t src_at = (total_pay + kDecodeTailPad + 15u) & ~15ull;  // 16-byte aligned: hipMalloc's base is
+        hipStream_t st = to == DecodeTo::device || (verify && !host_src) ? stream : d->stream;
         const uint32_t T = (uint32_t)total_blocks;
         // LACX_DECODE_BATCH_PAD=1 (tuning knob, read per call): every item's blocks start a new wave
         const char* pad_env = std::getenv("LACX_DECODE_BATCH_PAD");
@@ -441,9 +469,12 @@ int decode_batch_run(lacx_decoder* d, const BatchIn* in, uint32_t n, DecodeTo to
         const size_t o_frame = o_byte + 8 * ((size_t)T + 1), o_unit = o_frame + 8 * ((size_t)T + 1);
         const size_t o_bitem = o_unit + 8 * ((size_t)m + 1), o_lane = o_bitem + 4 * (size_t)T;
         const size_t o_v2 = o_lane + 4 * lane_blk.size(), o_win = (o_v2 + 4 * v2_items.size() + 15u) & ~(size_t)15u;
-        const size_t meta = window >= 0 ? o_win + sizeof(WindowOut) * m : o_v2 + 4 * v2_items.size();  // | win [m]
+        const size_t o_res = o_win + sizeof(VerifySource) * m;  // verify form: | ver [m] | res [m] in the window form's place
+        const size_t meta = verify ? o_res + sizeof(VerifyWords) * m
+                                   : window >= 0 ? o_win + sizeof(WindowOut) * m : o_v2 + 4 * v2_items.size();  // | win [m]
         DEC_TRY(decoder_open(d, &prev_device, &what), what);
-        DEC_TRY(grow_payload(d, total_pay, &what), what);
+        if (host_src) st = d->stream;  // (created by decoder_open)
+        DEC_TRY(grow_payload(d, host_src ? src_at + host_src_bytes : total_pay, &what), what);
         DEC_TRY(grow_blocks(d, T, &what), what);
         if (wav || (window >= 0 && to == DecodeTo::host)) DEC_TRY(grow_wav(d, image_total, &what), what);
         if (own_pcm) DEC_TRY(grow_pcm(d, pcm_total, &what), what);
@@ -491,6 +522,15 @@ int decode_batch_run(lacx_decoder* d, const BatchIn* in, uint32_t n, DecodeTo to
                 }
             }
             if (window >= 0) std::memcpy(h + o_win, win.data(), sizeof(WindowOut) * m);
+            if (verify) {
+                auto* ver = reinterpret_cast<VerifySource*>(h + o_win);
+                auto* res = reinterpret_cast<VerifyWords*>(h + o_res);
+                for (uint32_t j = 0; j < m; ++j) {
+                    const lacx_pcm& p = in[dev[j]].pcm;
+                    ver[j] = VerifySource{host_src ? d->d_pay + src_at : p.data0, p.data1, p.layout, 0};
+                    res[j] = VerifyWords{0, ~0ull, 0, 0, 0, 0};
+                }
+            }
             std::memcpy(h + o_items, it.data(), sizeof(DecodeItem) * m);
             if (!lane_blk.empty()) std::memcpy(h + o_lane, lane_blk.data(), 4 * lane_blk.size());
             if (!v2_items.empty()) std::memcpy(h + o_v2, v2_items.data(), 4 * v2_items.size());
@@ -515,6 +555,7 @@ int decode_batch_run(lacx_decoder* d, const BatchIn* in, uint32_t n, DecodeTo to
                 }
             }
             DEC_TRY(hipMemsetAsync(d->d_pay + total_pay, 0, kDecodeTailPad, st), "memset");  // the bit reader's look-ahead
+            if (host_src) DEC_TRY(hipMemcpyAsync(d->d_pay + src_at, host_src, host_src_bytes, hipMemcpyHostToDevice, st), "H2D source");
             DecodeArgs a;
             uint8_t* dm = d->d_meta;
             a.nitems = m;
@@ -535,12 +576,18 @@ int decode_batch_run(lacx_decoder* d, const BatchIn* in, uint32_t n, DecodeTo to
             a.total_units = total_units;
             if (window >= 0) a.window = reinterpret_cast<const WindowOut*>(dm + o_win);
             a.f32 = window == LACX_SAMPLE_F32;
+            if (verify) {
+                a.verify = reinterpret_cast<const VerifySource*>(dm + o_win);
+                a.verify_res = reinterpret_cast<VerifyWords*>(dm + o_res);
+            }
             DEC_TRY(hipEventRecord(d->e0, st), "event record");
             DEC_TRY(launch_decode(a, st), "decode launch");
             DEC_TRY(hipEventRecord(d->e1, st), "event record");
             DEC_TRY(hipMemcpyAsync(d->h_status, d->d_status, (size_t)T * sizeof(uint32_t), hipMemcpyDeviceToHost, st), "D2H status");
             // the images of the items that decoded are valid whatever the others did: one copy for all
             if (wav) DEC_TRY(hipMemcpyAsync(d->h_wav, d->d_wav, image_total, hipMemcpyDeviceToHost, st), "D2H WAV images");
+            // the verify form's whole answer: 32 bytes per item
+            if (verify) DEC_TRY(hipMemcpyAsync(d->h_meta + o_res, d->d_meta + o_res, sizeof(VerifyWords) * m, hipMemcpyDeviceToHost, st), "D2H verify results");
             DEC_TRY(hipStreamSynchronize(st), "synchronize");
             if (device_ms) (void)hipEventElapsedTime(device_ms, d->e0, d->e1);
         }
@@ -555,6 +602,23 @@ int decode_batch_run(lacx_decoder* d, const BatchIn* in, uint32_t n, DecodeTo to
                 }
             }
             if (code[i] != LACX_OK) continue;
+            if (verify) {
+                const VerifyWords& w = reinterpret_cast<const VerifyWords*>(d->h_meta + o_res)[j];
+                if (w.count == 0) continue;
+                lacx_verify_result r{};
+                r.mismatches = w.count;
+                r.frame = w.key >> 1;
+                r.block = w.block;
+                r.channel = (uint8_t)(w.key & 1u);
+                r.decoded = w.decoded;
+                r.source = w.source;
+                if (vres) vres[i] = r;
+                code[i] = LACX_E_MISMATCH;
+                err[i] = "[verify-error] block=" + std::to_string(r.block) + " channel=" + (r.channel ? "right" : "left") +
+                         " frame=" + std::to_string(r.frame) + " decoded=" + std::to_string(r.decoded) +
+                         " source=" + std::to_string(r.source) + " mismatches=" + std::to_string(r.mismatches);
+                continue;
+            }
             if (wav) {
                 uint8_t* img = d->h_wav + wav_at[j];
                 (void)wav_header(info[i], img);
@@ -712,6 +776,53 @@ int lacx_decoder_decode_window(lacx_decoder* d, const uint8_t* lac, uint64_t siz
     if (sample_type != LACX_SAMPLE_I32 && sample_type != LACX_SAMPLE_F32) return decode_fail(LACX_E_INVALID, "unknown sample type");
     return decode_one(d, BatchIn{lac, size, static_cast<int32_t*>(left), static_cast<int32_t*>(right), frames, start},
                       DecodeTo::host, nullptr, device_ms, sample_type);
+}
+
+int lacx_decoder_verify_batch_device(lacx_decoder* d, const lacx_verify_item* items, uint32_t n, void* stream, int* item_rc,
+                                     lacx_verify_result* results, float* device_ms) {
+    if (!d) return decode_fail(LACX_E_INVALID, "null decoder");
+    if (!items || n == 0) return decode_fail(LACX_E_INVALID, "null argument or empty batch");
+    std::vector<BatchIn> in(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        in[i] = BatchIn{items[i].lac, items[i].size, nullptr, nullptr, items[i].frames};
+        in[i].pcm = items[i].pcm;
+    }
+    std::vector<int> code;
+    std::vector<std::string> err;
+    const int rc = decode_batch_run(d, in.data(), n, DecodeTo::verify, static_cast<hipStream_t>(stream), nullptr, code, err,
+                                    device_ms, -1, results);
+    return batch_result(d, rc, code, err, item_rc);
+}
+
+// A WAV file image in host memory against a stream: the formats are compared on the host (a difference is an answer
+// that needs no device), then the data chunk goes to the device as it is, 2 or 3 bytes per sample, and is compared
+// there as an interleaved source -- a batch of one.  No PCM comes back.
+int lacx_decoder_verify_wav(lacx_decoder* d, const uint8_t* lac, uint64_t size, const uint8_t* wav, uint64_t wav_size,
+                            lacx_verify_result* result, float* device_ms) {
+    if (device_ms) *device_ms = 0.f;
+    if (result) std::memset(result, 0, sizeof(*result));
+    if (!d) return decode_fail(LACX_E_INVALID, "null decoder");
+    if (!wav) return decode_fail(LACX_E_INVALID, "null argument");
+    lacx_stream_info info;
+    const int prc = lacx_stream_parse(lac, size, &info);
+    if (prc != LACX_OK) return prc;
+    lacx_wav_info w;
+    if (lacx_wav_parse(wav, wav_size, &w) != LACX_OK) return decode_fail(LACX_E_INVALID, "[verify-error] source is not a PCM WAV file the encoder reads");
+    auto differs = [](const char* field, uint64_t a, uint64_t b) {
+        return decode_fail(LACX_E_MISMATCH, std::string("[verify-error] ") + field + ": stream " + std::to_string(a) + ", source " + std::to_string(b));
+    };
+    if (w.channels != info.channels) return differs("channels", info.channels, w.channels);
+    if (w.bit_depth != info.bit_depth) return differs("bit depth", info.bit_depth, w.bit_depth);
+    if (w.sample_rate != info.sample_rate) return differs("sample rate", info.sample_rate, w.sample_rate);
+    if (w.frames != info.frames) return differs("frames", info.frames, w.frames);
+    BatchIn in{lac, size, nullptr, nullptr, w.frames};
+    in.pcm = lacx_pcm{nullptr, nullptr, w.bit_depth == 16 ? LACX_PCM_INTERLEAVED_I16 : LACX_PCM_INTERLEAVED_I24, w.channels};
+    in.host_src = wav + w.data_offset;
+    in.host_src_bytes = w.frames * w.channels * (uint64_t)(w.bit_depth / 8);
+    std::vector<int> code;
+    std::vector<std::string> err;
+    (void)decode_batch_run(d, &in, 1, DecodeTo::verify, nullptr, nullptr, code, err, device_ms, -1, result);
+    return code[0] == LACX_OK ? LACX_OK : decode_fail(code[0], err[0]);
 }
 
 const char* lacx_decoder_item_error(const lacx_decoder* d, uint32_t i) {

@@ -16,6 +16,8 @@
 //                   (interleaved little-endian 16 / 24-bit, ref src/main.cpp:150-182) instead of back into left/right
 //   k_window_out    the same per-sample work over the blocks a frame window needs, the window's frames written as
 //                   int32 or float32 into the caller's arrays (lacx_decoder_decode_window*)
+//   k_verify        the same per-sample work, compared with the source PCM in its own layout instead of stored: a count
+//                   of differing samples and the first of them per item (lacx_decoder_verify_*; verify_core.h)
 // Every launch decodes a batch of streams (items) as one job; a single stream is a batch of one.
 // The adaptive Rice parameter uses the encoder's division-free formulation (kmean / biased_k of analyze_core.h, proven
 // against Rice::adapt_k there); it assumes zigzag residuals below 2^30 like the encoder does, and a stream with a larger
@@ -26,6 +28,7 @@
 
 #include "decode_core.h"
 #include "kernels.h"
+#include "verify_core.h"
 
 namespace lacx {
 
@@ -348,6 +351,78 @@ __global__ __launch_bounds__(256) void k_window_out(uint32_t nitems, unsigned lo
                     global_ptr(static_cast<uint32_t*>(w.left)), global_ptr(static_cast<uint32_t*>(w.right)), f32 != 0);
 }
 
+// Verify form: laid out as k_wav_pack and k_window_out -- thread u handles unit u of the concatenated unit
+// ranges of the items' frames, the item found once per workgroup by a uniform binary search and again per thread only in a
+// workgroup that spans items -- and verify_unit (verify_core.h) compares the unit's decoded frames with the item's source
+// ver[j] instead of storing them.  What leaves: res[j].count += the differing samples, res[j].key = min(frame * 2 + channel)
+// over them (the host sets 0 and all ones per call).  A wave in which nothing differs -- the common case -- issues no
+// atomic at all.  Otherwise, in a workgroup that lies in one item, the wave reduces first: the count is the sum of the
+// ballots' populations over the eight sample positions of a unit, and the wave's lowest key is that of the lowest lane
+// that differs (the keys rise with the lane), which issues the wave's one atomicAdd and one atomicMin.  In a workgroup
+// that spans items the lanes of a wave may belong to different items, and each lane that differs reports for itself.
+__global__ __launch_bounds__(256) void k_verify(uint32_t nitems, unsigned long long total_units,
+                                                const unsigned long long* __restrict__ unit_off,
+                                                const DecodeItem* __restrict__ items, const VerifySource* __restrict__ ver,
+                                                VerifyWords* __restrict__ res,
+                                                const unsigned long long* __restrict__ frame_off,
+                                                const uint8_t* __restrict__ ms_flag, uint32_t* __restrict__ status) {
+    const unsigned long long first = (unsigned long long)blockIdx.x * 256u;
+    uint32_t lo = 0, hi = nitems;  // unit_off[lo] <= first < unit_off[hi]
+    while (hi - lo > 1u) {
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        if (unit_off[mid] <= first) lo = mid;
+        else hi = mid;
+    }
+    const unsigned long long u = first + threadIdx.x;
+    const bool one_item = unit_off[lo + 1] >= first + 256u;  // (uniform) the whole workgroup lies in item lo
+    uint32_t j = lo, differ = 0;
+    unsigned long long f0 = 0;
+    if (u < total_units) {
+        if (!one_item) {  // this thread's item, among the later ones
+            uint32_t h2 = nitems;  // unit_off[j] <= u < unit_off[h2]
+            while (h2 - j > 1u) {
+                const uint32_t mid = j + (h2 - j) / 2u;
+                if (unit_off[mid] <= u) j = mid;
+                else h2 = mid;
+            }
+        }
+        const DecodeItem& it = items[j];
+        const VerifySource& s = ver[j];
+        f0 = 4ull * (u - unit_off[j]);
+        differ = verify_unit(f0, it.blocks, it.channels, it.bit_depth, it.frames, frame_off + it.block0, it.frame0,
+                             global_ptr(it.left), global_ptr(it.right), ms_flag + it.block0, status + it.block0,
+                             global_ptr(s.data0), global_ptr(s.data1), s.layout);
+    }
+    const unsigned long long any = __ballot(differ != 0u);
+    if (any == 0ull) return;
+    const unsigned long long key = 2ull * f0 + (uint32_t)(__ffs((int)differ) - 1);
+    if (one_item) {
+        uint32_t n = 0;
+#pragma unroll
+        for (uint32_t b = 0; b < 8u; ++b) n += (uint32_t)__popcll(__ballot(((differ >> b) & 1u) != 0u));
+        if ((threadIdx.x & 63u) == (uint32_t)(__ffsll((long long)any) - 1)) {
+            atomicAdd(&res[j].count, (unsigned long long)n);
+            atomicMin(&res[j].key, key);
+        }
+    } else if (differ) {
+        atomicAdd(&res[j].count, (unsigned long long)__popc(differ));
+        atomicMin(&res[j].key, key);
+    }
+}
+
+// One thread per item, after k_verify: the block and the two values at an item's first mismatch (verify_fill_item).
+__global__ __launch_bounds__(64) void k_verify_fill(uint32_t nitems, const DecodeItem* __restrict__ items,
+                                                    const VerifySource* __restrict__ ver, VerifyWords* __restrict__ res,
+                                                    const unsigned long long* __restrict__ frame_off,
+                                                    const uint8_t* __restrict__ ms_flag) {
+    const uint32_t j = blockIdx.x * 64u + threadIdx.x;
+    if (j >= nitems) return;
+    const DecodeItem& it = items[j];
+    const VerifySource& s = ver[j];
+    verify_fill_item(it.blocks, it.channels, frame_off + it.block0, it.frame0, global_ptr(it.left), global_ptr(it.right),
+                     ms_flag + it.block0, global_ptr(s.data0), global_ptr(s.data1), s.layout, res[j]);
+}
+
 hipError_t launch_decode(const DecodeArgs& a, hipStream_t stream) {
     const size_t smem = kDecBytesPerCol * kDecThreads;
     if (a.lanes) {
@@ -364,7 +439,14 @@ hipError_t launch_decode(const DecodeArgs& a, hipStream_t stream) {
         hipLaunchKernelGGL(k_decode_serial, dim3((a.nv2 + kDecThreads - 1) / kDecThreads), dim3(kDecThreads), smem,
                            stream, a.nv2, a.v2_items, a.items, a.payload, a.frame_off, a.status, a.ms_flag);
     }
-    if (a.window) {
+    if (a.verify) {
+        if (a.total_units) {
+            hipLaunchKernelGGL(k_verify, dim3((uint32_t)((a.total_units + 255u) / 256u)), dim3(256), 0, stream, a.nitems,
+                               a.total_units, a.unit_off, a.items, a.verify, a.verify_res, a.frame_off, a.ms_flag, a.status);
+            hipLaunchKernelGGL(k_verify_fill, dim3((a.nitems + 63u) / 64u), dim3(64), 0, stream, a.nitems, a.items, a.verify,
+                               a.verify_res, a.frame_off, a.ms_flag);
+        }
+    } else if (a.window) {
         if (a.total_units)
             hipLaunchKernelGGL(k_window_out, dim3((uint32_t)((a.total_units + 255u) / 256u)), dim3(256), 0, stream, a.nitems,
                                a.total_units, a.unit_off, a.items, a.window, a.frame_off, a.ms_flag, a.status, a.f32 ? 1 : 0);

@@ -220,6 +220,10 @@ struct DecodeArgs {
     // says which of item j's decoded frames go where; f32: float32 samples scaled by 2^-(bit_depth - 1), else int32
     const WindowOut* window = nullptr;
     bool f32 = false;
+    // verify form (non-null: k_verify over the units of unit_off in place of the other post passes, then k_verify_fill):
+    // verify[j] is the source PCM of item j, verify_res[j] its result words (count 0 and key all ones on entry)
+    const VerifySource* verify = nullptr;
+    VerifyWords* verify_res = nullptr;
 };
 hipError_t launch_decode(const DecodeArgs& args, hipStream_t stream);
 

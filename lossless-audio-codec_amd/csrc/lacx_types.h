@@ -93,4 +93,20 @@ struct BatchRef {
     StreamDesc single;
 };
 
+// Verify form of the decoder (verify_core.h, k_verify): the source PCM an item's decoded samples are compared with, in its
+// own layout, and the words the comparison leaves per item.
+struct VerifySource {
+    const void* data0;  // planar: left; interleaved layouts: the WAV data chunk
+    const void* data1;  // planar: right (null for mono)
+    uint32_t layout;    // PCM_PLANAR_I32 / PCM_INTERLEAVED_I16 / PCM_INTERLEAVED_I24 (analyze_core.h)
+    uint32_t pad;
+};
+struct VerifyWords {
+    unsigned long long count;  // samples that differ (zeroed per call)
+    unsigned long long key;    // lowest frame * 2 + channel that differs (all ones per call: none)
+    int32_t decoded, source;   // the two values at `key` (filled by verify_fill_item when count != 0)
+    uint32_t block;            // the block of that frame, counted in the item
+    uint32_t pad;
+};
+
 }  // namespace lacx

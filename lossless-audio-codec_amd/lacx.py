@@ -24,7 +24,7 @@ HOOKS_LIB_PATH = os.path.join(HERE, "liblacx_hooks.so")
 DEVICE_ALL = -2
 MAX_FANOUT = 16
 
-OK, E_INVALID, E_RUNTIME, E_DEVICE = 0, 1, 2, 3
+OK, E_INVALID, E_RUNTIME, E_DEVICE, E_MISMATCH = 0, 1, 2, 3, 4
 MAX_BLOCK = 16384
 SLOTS = 16
 CH_L, CH_R, CH_M, CH_S = 0, 1, 2, 3
@@ -110,6 +110,7 @@ EXPORTS = (
     "lacx_decoder_decode_wav", "lacx_decoder_decode_wav_view",
     "lacx_decoder_decode_wav_batch", "lacx_decoder_decode_wav_batch_view", "lacx_decoder_decode_batch_device",
     "lacx_decoder_item_error", "lacx_decoder_decode_window_batch_device", "lacx_decoder_decode_window",
+    "lacx_decoder_verify_batch_device", "lacx_decoder_verify_wav",
 )
 
 
@@ -171,6 +172,10 @@ def lib():
                                                               C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_float)]
         L.lacx_decoder_decode_window.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), C.c_uint64, C.c_uint64, C.c_uint64, C.c_int,
                                                  C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+        L.lacx_decoder_verify_batch_device.argtypes = [C.c_void_p, C.POINTER(VerifyItem), C.c_uint32, C.c_void_p,
+                                                       C.POINTER(C.c_int), C.POINTER(VerifyResult), C.POINTER(C.c_float)]
+        L.lacx_decoder_verify_wav.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), C.c_uint64, C.POINTER(C.c_uint8), C.c_uint64,
+                                              C.POINTER(VerifyResult), C.POINTER(C.c_float)]
         L.lacx_decoder_item_error.restype = C.c_char_p
         L.lacx_decoder_item_error.argtypes = [C.c_void_p, C.c_uint32]
         # the structs declared in this file against the library's own sizeof(): a layout that has drifted from
@@ -191,7 +196,8 @@ def abi_structs() -> dict:
     return {"config": Config, "channel_plan": ChannelPlan, "block_plan": BlockPlan, "timing": Timing, "pcm": Pcm,
             "batch_item": BatchItem, "batch_out": BatchOut, "wav_info": WavInfo, "fanout_shard": FanoutShard,
             "fanout_out": FanoutOut, "fanout_stats": FanoutStats, "stream_info": StreamInfo, "span": Span,
-            "decode_item": DecodeItem, "window_item": WindowItem}
+            "decode_item": DecodeItem, "window_item": WindowItem, "verify_item": VerifyItem,
+            "verify_result": VerifyResult}
 
 
 def device_count() -> int:
@@ -633,6 +639,17 @@ class WindowItem(C.Structure):
                 ("left", C.c_void_p), ("right", C.c_void_p)]
 
 
+class VerifyItem(C.Structure):
+    _fields_ = [("lac", C.POINTER(C.c_uint8)), ("size", C.c_uint64), ("pcm", Pcm), ("frames", C.c_uint64)]
+
+
+class VerifyResult(C.Structure):
+    """mismatches == 0: the stream decodes to exactly its source; else the first differing sample (lowest frame, then
+    lowest channel), its block in the stream and the two values there."""
+    _fields_ = [("mismatches", C.c_uint64), ("frame", C.c_uint64), ("block", C.c_uint32), ("channel", C.c_uint8),
+                ("reserved", C.c_uint8 * 3), ("decoded", C.c_int32), ("source", C.c_int32)]
+
+
 SAMPLE_I32, SAMPLE_F32 = 0, 1  # LACX_SAMPLE_*
 
 
@@ -892,6 +909,62 @@ class Decoder:
             self._h, items, C.c_uint32(n), C.c_int(st), C.c_void_p(stream), rcs, ms))
         results = [None if i in errors else infos[i] for i in range(n)]
         return self._raise_batch(rc, errors, results)
+
+
+    def verify_batch_device(self, lacs, sources, stream: int = 0) -> list:
+        """Many .lac streams compared on the device with the PCM they were made from: sources[i] = (data0_ptr,
+        data1_ptr or None, layout, channels, frames), device-resident PCM in any PCM_* layout on the decoder's device
+        (planar: left and right int32 arrays; interleaved: the WAV data chunk).  The work goes on `stream` (a raw
+        hipStream_t, 0 = the null stream); nothing but a few words per item comes back.  Returns each item's VerifyResult
+        (all zero: identical).  An item that differs or does not decode raises BatchDecodeError once the others are
+        done: errors[i] is its message ("[verify-error] block=N ..." or the decode's own), results[i] its VerifyResult
+        where it decoded and differed, None where it failed."""
+        if len(sources) != len(lacs):
+            raise ValueError("one source per stream")
+        bufs = [np.frombuffer(x, dtype=np.uint8) for x in lacs]
+        n = len(bufs)
+        items = (VerifyItem * max(1, n))()
+        for it, b, (d0, d1, layout, channels, frames) in zip(items, bufs, sources):
+            it.lac = b.ctypes.data_as(C.POINTER(C.c_uint8))
+            it.size = b.size
+            it.pcm = Pcm(d0, d1, layout, channels)
+            it.frames = frames
+        res = (VerifyResult * max(1, n))()
+        rcs_seen = []
+
+        def call(rcs, ms):
+            rcs_seen.append(rcs)
+            return lib().lacx_decoder_verify_batch_device(self._h, items, C.c_uint32(n), C.c_void_p(stream), rcs, res, ms)
+
+        rc, errors = self._batch(n, call)
+        rcs = rcs_seen[0]
+        results = [res[i] if rcs[i] in (OK, E_MISMATCH) else None for i in range(n)]
+        return self._raise_batch(rc, errors, results)
+
+    def verify_wav(self, lac, wav) -> VerifyResult:
+        """A .lac against the WAV file image it was made from (both in host memory): the image's data chunk goes to the
+        device as it is and is compared there with the decoded stream.  Returns the VerifyResult -- a mismatch is an
+        answer, not an exception: `identical` is False and `message` holds "[verify-error] ..." (also for a difference
+        in format, where the counts stay zero and `format_differs` is set); kernel milliseconds in `last_ms`.  RuntimeError where the stream
+        does not decode, ValueError for an image that is no PCM WAV."""
+        if self._h is None:
+            raise RuntimeError("decoder is closed")
+        lbuf = np.frombuffer(lac, dtype=np.uint8)
+        wbuf = np.frombuffer(wav, dtype=np.uint8)
+        res = VerifyResult()
+        ms = C.c_float()
+        u8 = C.POINTER(C.c_uint8)
+        rc = lib().lacx_decoder_verify_wav(self._h, lbuf.ctypes.data_as(u8), C.c_uint64(lbuf.size), wbuf.ctypes.data_as(u8),
+                                           C.c_uint64(wbuf.size), C.byref(res), C.byref(ms))
+        self.last_ms = float(ms.value)
+        res.message = "" if rc == OK else lib().lacx_decode_last_error().decode(errors="replace")
+        res.identical = rc == OK
+        res.format_differs = rc == E_MISMATCH and res.mismatches == 0
+        if rc in (OK, E_MISMATCH):
+            return res
+        if rc == E_INVALID and res.message.startswith("[verify-error]"):
+            raise ValueError(res.message)
+        raise RuntimeError(res.message)
 
 
 def decode_wav(lac, device: int = -1) -> bytes:

@@ -1,4 +1,4 @@
-// lacx_cli -- the `encode` and `decode` commands of the reference's command-line tool on the MI355X path (SURVEY row f-4;
+// lacx_cli -- the `encode`, `decode` and `selftest` commands of the reference's command-line tool on the MI355X path (SURVEY row f-4;
 // ref src/main.cpp:609-781).  encode (ref :609-710): same positional arguments, every flag of the reference's encode command with the same
 // meaning and rejection rules (--stereo-mode=lr|ms, --no-partitioning, --threads=N, the --debug-* family), LAC_THREADS
 // resolved by the tool and not by the library (ref :586-591), the same-file check on the resolved paths (ref :433-444),
@@ -7,7 +7,15 @@
 // straight from the encoder's pinned result buffer.  decode (ref :712-781): the same argument checks and messages, the
 // .lac parsed on the host first (structural errors need no device), then lacx_decoder_decode_wav_view on the current
 // device; the WAV file is written, staged like encode's output, straight from the decoder's pinned image buffer.
-// Selftest stays with the reference's tool.
+// verify (no counterpart in the reference's tool; `flac -t` with the source at hand): a .lac against the WAV it was made
+// from, decoded and compared on the device (lacx_decoder_verify_wav) -- no PCM comes back.  encode --verify runs the same
+// comparison on the bytes just produced, before the staged output is published (--verify-against=FILE: with another copy
+// of the source instead of the input file).  selftest (ref :803-909): the reference's
+// four format pairs, signal and frame count, LR / MS / auto / mono encodes through lacx_encode, each verified on the
+// device against its source, the header fields read back through lacx_stream_parse, the reference's output lines.
+#include <algorithm>
+#include <chrono>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -27,8 +35,10 @@ namespace {
 
 void usage() {
     std::cerr << "Usage:\n  lacx_cli encode input.wav output.lac [--stereo-mode=lr|ms] [--threads=N] [--debug-threads] [--debug-lpc] "
-                 "[--debug-stereo-est] [--debug-zr] [--debug-partitions] [--no-partitioning]\n"
-                 "  lacx_cli decode input.lac output.wav [--threads=N] [--debug-threads]\n";
+                 "[--debug-stereo-est] [--debug-zr] [--debug-partitions] [--no-partitioning] [--verify] [--verify-against=other.wav]\n"
+                 "  lacx_cli decode input.lac output.wav [--threads=N] [--debug-threads]\n"
+                 "  lacx_cli verify input.lac input.wav\n"
+                 "  lacx_cli selftest\n";
 }
 
 // A positive decimal integer and nothing else (ref src/main.cpp:560-584, src/codec/lac/thread_limit.hpp:10-28).
@@ -159,6 +169,149 @@ int decode_command(int argc, char** argv) {
     return 0;
 }
 
+// lacx_cli verify input.lac input.wav: exit 0 when the stream decodes to exactly the WAV's samples in the WAV's format
+int verify_command(char** argv) {
+    const std::string lac_path = argv[2], wav_path = argv[3];
+    std::vector<uint8_t> lac, wav;
+    if (!load_file(lac_path, lac)) {
+        std::cerr << "Failed to read LAC file: " << lac_path << "\n";
+        return 1;
+    }
+    lacx_wav_info winfo{};
+    if (!load_file(wav_path, wav) || lacx_wav_parse(wav.data(), wav.size(), &winfo) != LACX_OK) {
+        std::cerr << "Failed to read WAV: " << wav_path << "\n";
+        return 1;
+    }
+    lacx_decoder* dec = nullptr;
+    if (lacx_decoder_create(-1, &dec) != LACX_OK) {
+        std::cerr << "Error: lacx_decoder_create failed\n";
+        return 1;
+    }
+    lacx_verify_result res{};
+    const int rc = lacx_decoder_verify_wav(dec, lac.data(), lac.size(), wav.data(), wav.size(), &res, nullptr);
+    lacx_decoder_destroy(dec);
+    if (rc != LACX_OK) {
+        std::cerr << (rc == LACX_E_MISMATCH ? "Verify failed: " : "Decode failed: ") << lacx_decode_last_error() << "\n";
+        return 1;
+    }
+    std::cout << "Verified " << lac_path << " == " << wav_path << " (" << winfo.frames << " samples per channel)\n";
+    return 0;
+}
+
+// The canonical WAV image of planar PCM (the source form lacx_decoder_verify_wav takes).
+std::vector<uint8_t> wav_image(const std::vector<int32_t>& left, const std::vector<int32_t>* right, uint32_t rate, uint32_t bits) {
+    const uint32_t ch = right ? 2u : 1u, bps = bits / 8u, align = ch * bps;
+    const uint64_t data = (uint64_t)left.size() * align;
+    std::vector<uint8_t> w(44 + data + (data & 1u), 0);
+    auto u16 = [&](size_t at, uint32_t v) { w[at] = (uint8_t)v, w[at + 1] = (uint8_t)(v >> 8); };
+    auto u32 = [&](size_t at, uint32_t v) { u16(at, v & 0xFFFFu), u16(at + 2, v >> 16); };
+    std::memcpy(&w[0], "RIFF", 4);
+    u32(4, (uint32_t)(36u + data + (data & 1u)));
+    std::memcpy(&w[8], "WAVEfmt ", 8);
+    u32(16, 16), u16(20, 1), u16(22, ch), u32(24, rate), u32(28, rate * align), u16(32, align), u16(34, bits);
+    std::memcpy(&w[36], "data", 4);
+    u32(40, (uint32_t)data);
+    uint8_t* p = &w[44];
+    for (size_t i = 0; i < left.size(); ++i)
+        for (uint32_t c = 0; c < ch; ++c) {
+            const uint32_t v = (uint32_t)(c ? (*right)[i] : left[i]);
+            for (uint32_t k = 0; k < bps; ++k) *p++ = (uint8_t)(v >> (8u * k));
+        }
+    return w;
+}
+
+// lacx_cli selftest (ref src/main.cpp:803-909)
+int selftest_command() {
+    const double pi = 3.14159265358979323846;
+    lacx_decoder* dec = nullptr;
+    if (lacx_decoder_create(-1, &dec) != LACX_OK) {
+        std::cerr << "Error: lacx_decoder_create failed\n";
+        return 1;
+    }
+    struct Run {
+        std::vector<uint8_t> lac;
+        lacx_stream_info info{};
+        long long verify_us = 0;
+    };
+    // one encode, verified on the device against its source; false after printing why
+    auto roundtrip = [&](const char* what, uint32_t rate, uint8_t depth, uint8_t mode, const std::vector<int32_t>& left,
+                         const std::vector<int32_t>* right, Run& out) -> bool {
+        lacx_config cfg{};
+        cfg.sample_rate = rate, cfg.bit_depth = depth, cfg.stereo_mode = mode;
+        cfg.zero_run_enabled = 1, cfg.partitioning_enabled = 1, cfg.device = -1;
+        lacx_encoder* enc = nullptr;
+        if (lacx_encoder_create(&cfg, &enc) != LACX_OK) {
+            std::cerr << "Error: lacx_encoder_create failed\n";
+            return false;
+        }
+        uint8_t* bytes = nullptr;
+        uint64_t size = 0;
+        if (lacx_encode(enc, left.data(), right ? right->data() : nullptr, left.size(), &bytes, &size) != LACX_OK) {
+            std::cerr << "Error: " << lacx_last_error(enc) << "\n";
+            lacx_encoder_destroy(enc);
+            return false;
+        }
+        out.lac.assign(bytes, bytes + size);
+        lacx_free(bytes);
+        lacx_encoder_destroy(enc);
+        const std::vector<uint8_t> wav = wav_image(left, right, rate, depth);
+        lacx_verify_result res{};
+        const auto t0 = std::chrono::high_resolution_clock::now();
+        const int rc = lacx_decoder_verify_wav(dec, out.lac.data(), out.lac.size(), wav.data(), wav.size(), &res, nullptr);
+        const auto t1 = std::chrono::high_resolution_clock::now();
+        out.verify_us = std::chrono::duration_cast<std::chrono::microseconds>(t1 - t0).count();
+        if (rc != LACX_OK) {
+            std::cerr << what << " roundtrip mismatch for sr=" << rate << " depth=" << int(depth) << ": " << lacx_decode_last_error() << "\n";
+            return false;
+        }
+        if (lacx_stream_parse(out.lac.data(), out.lac.size(), &out.info) != LACX_OK) {
+            std::cerr << what << " header unreadable: " << lacx_decode_last_error() << "\n";
+            return false;
+        }
+        return true;
+    };
+    auto run_pair = [&](uint32_t rate, uint8_t depth) -> bool {
+        const size_t frames = std::max<size_t>(rate / 20, 2048);
+        std::vector<int32_t> left(frames), right(frames);
+        const int64_t amplitude = depth == 24 ? (int64_t)0x7FFFFF / 3 : (int64_t)30000;
+        for (size_t i = 0; i < frames; ++i) {
+            const double t = (double)i / (double)rate;
+            left[i] = (int32_t)(std::sin(2.0 * pi * 440.0 * t) * amplitude);
+            right[i] = (int32_t)(std::sin(2.0 * pi * 443.0 * t) * (amplitude * 0.95));
+        }
+        Run lr, ms, au, mono;
+        if (!roundtrip("LR", rate, depth, 0, left, &right, lr)) return false;
+        if (lr.info.sample_rate != rate || lr.info.bit_depth != depth) {
+            std::cerr << "LR header mismatch sr=" << lr.info.sample_rate << " depth=" << int(lr.info.bit_depth) << "\n";
+            return false;
+        }
+        if (!roundtrip("MS", rate, depth, 1, left, &right, ms)) return false;
+        if (ms.info.sample_rate != rate || ms.info.bit_depth != depth) {
+            std::cerr << "MS header mismatch sr=" << ms.info.sample_rate << " depth=" << int(ms.info.bit_depth) << "\n";
+            return false;
+        }
+        if (!roundtrip("Auto-stereo", rate, depth, 2, left, &right, au)) return false;
+        if (au.info.stereo_mode != 2) {
+            std::cerr << "Auto-stereo header mismatch stereo_mode=" << int(au.info.stereo_mode) << "\n";
+            return false;
+        }
+        if (!roundtrip("Mono", rate, depth, 0, left, nullptr, mono)) return false;
+        if (mono.info.channels != 1) {
+            std::cerr << "Mono header mismatch channels=" << int(mono.info.channels) << "\n";
+            return false;
+        }
+        std::cout << "Selftest sr=" << rate << "Hz depth=" << int(depth) << " LR=" << lr.lac.size() << " bytes (" << lr.verify_us
+                  << "us decode) MS=" << ms.lac.size() << " bytes (" << ms.verify_us << "us decode) -> MS is "
+                  << (ms.lac.size() < lr.lac.size() ? "smaller" : "not smaller") << "\n";
+        return true;
+    };
+    const bool ok = run_pair(44100, 16) && run_pair(48000, 24) && run_pair(96000, 24) && run_pair(192000, 24);
+    lacx_decoder_destroy(dec);
+    if (!ok) return 1;
+    std::cout << "Selftest complete: adaptive block tests passed.\n";
+    return 0;
+}
+
 struct Encoded {
     const uint8_t* data = nullptr;
     uint64_t size = 0;
@@ -167,22 +320,26 @@ struct Encoded {
 }  // namespace
 
 int main(int argc, char** argv) {
-    if (argc < 4 || (std::string(argv[1]) != "encode" && std::string(argv[1]) != "decode")) {
+    const std::string mode = argc > 1 ? argv[1] : "";
+    if (mode == "selftest" && argc == 2) return selftest_command();
+    if (mode == "verify" && argc == 4) return verify_command(argv);
+    if (argc < 4 || (mode != "encode" && mode != "decode")) {
         usage();
         return 1;
     }
-    if (std::string(argv[1]) == "decode") return decode_command(argc, argv);
+    if (mode == "decode") return decode_command(argc, argv);
     const std::string in_path = argv[2], out_path = argv[3];
     if (same_file(in_path, out_path)) {
         std::cerr << "Input and output paths must be different\n";
         return 1;
     }
     uint8_t stereo_mode = 2;
-    bool partitioning = true, debug_threads = false, debug_zr = false;
+    bool partitioning = true, debug_threads = false, debug_zr = false, verify = false;
     unsigned long long threads = 0;
+    std::string verify_path;  // --verify-against: another copy of the source (the master the input was made from)
     for (int i = 4; i < argc; ++i) {
         const std::string flag = argv[i];
-        const std::string tprefix = "--threads=";
+        const std::string tprefix = "--threads=", vprefix = "--verify-against=";
         if (flag == "--no-partitioning") {
             partitioning = false;
         } else if (flag == "--stereo-mode=lr") {
@@ -193,6 +350,11 @@ int main(int argc, char** argv) {
             debug_threads = true;
         } else if (flag == "--debug-zr") {
             debug_zr = true;
+        } else if (flag == "--verify") {
+            verify = true;
+        } else if (flag.compare(0, vprefix.size(), vprefix) == 0 && flag.size() > vprefix.size()) {
+            verify = true;
+            verify_path = flag.substr(vprefix.size());
         } else if (flag == "--debug-lpc" || flag == "--debug-stereo-est" || flag == "--debug-partitions") {
             // accepted like the reference does; its per-block log lines only exist in debug builds (LAC_DEBUG_LOG)
         } else if (flag.compare(0, tprefix.size(), tprefix) == 0) {
@@ -248,6 +410,26 @@ int main(int argc, char** argv) {
         const double gain = b.size ? (1.0 - (double)lac.size / (double)b.size) * 100.0 : 0.0;
         std::cout << "[debug-zr] baseline_bytes=" << b.size << " zr_bytes=" << lac.size << " gain=" << gain << "%\n";
         lacx_encoder_destroy(base);
+    }
+    if (verify) {  // the produced bytes against the input file image, on the device, before anything is published
+        std::vector<uint8_t> other;
+        if (!verify_path.empty() && !load_file(verify_path, other)) {
+            std::cerr << "Failed to read WAV: " << verify_path << "\n";
+            lacx_encoder_destroy(enc);
+            return 1;
+        }
+        const std::vector<uint8_t>& against = verify_path.empty() ? wav : other;
+        lacx_decoder* dec = nullptr;
+        lacx_verify_result res{};
+        int vrc = lacx_decoder_create(-1, &dec);
+        if (vrc == LACX_OK) vrc = lacx_decoder_verify_wav(dec, lac.data, lac.size, against.data(), against.size(), &res, nullptr);
+        if (vrc != LACX_OK) {
+            std::cerr << "Verify failed: " << (dec ? lacx_decode_last_error() : "lacx_decoder_create failed") << "\n";
+            if (dec) lacx_decoder_destroy(dec);
+            lacx_encoder_destroy(enc);
+            return 1;
+        }
+        lacx_decoder_destroy(dec);
     }
     const std::string tmp = out_path + ".lacx-partial";
     bool ok = false;
