@@ -1,0 +1,387 @@
+// decode_plan.h -- the host-only half of the decoder's host side: the container walk, and the plan of a decode job --
+// which blocks every item needs, where its payload, PCM and image lie in the job's buffers, the lane table, the layout
+// of the tables the kernels read, and the capacities the run must provide.  Plain C++, no HIP: api_decode.cpp runs a
+// plan on the device, tests/native/sim_decode.cpp runs the same plan on the host.
+#pragma once
+#include <cstdint>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "lacx.h"
+#include "lacx_types.h"
+
+namespace lacx {
+
+inline uint32_t be32(const uint8_t* p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
+// header + block table: 4 bytes per block in version 2 (no compressed sizes, ref lac/decoder.cpp:100-104), else 8
+inline uint64_t stream_head_bytes(int version, uint32_t blocks) { return 14 + (version == 2 ? 4ull : 8ull) * blocks; }
+
+// Container header + block table: the structural rules of the reference's reader (src/codec/frame/frame_header.hpp:48-74,
+// lac/decoder.cpp:84-145) -- sync, version 3, channels, stereo mode (0 for mono), one of the four sample rates, depth,
+// reserved byte; at least one block; every block 1..16384 frames, non-final ones at least 256; non-zero compressed
+// sizes that add up to the file; at most 6 912 000 000 samples and a WAV that RIFF can hold.  NOT taken over: its cap on
+// the decoded PCM (1 GiB) and the block count that follows from it, which would refuse the 2 h stream of BASELINE
+// configs[3].  The legacy version-2 container (no compressed sizes, hence no parallelism) is read too: one lane walks it.
+// Returns LACX_OK, or LACX_E_INVALID with the message in *why.
+inline int parse_stream(const uint8_t* lac, uint64_t size, lacx_stream_info* out, const char** why) {
+    auto fail = [&](const char* msg) { return *why = msg, LACX_E_INVALID; };
+    if (!lac || !out) return fail("null argument");
+    if (size == 0) return fail("[decode-error] empty input");
+    if (size < 10 || lac[0] != 0x4C || lac[1] != 0x41 || (lac[2] != 3 && lac[2] != 2)) return fail("[decode-error] invalid frame header");
+    const int version = lac[2], ch = lac[3], sm = lac[4], bd = lac[8];
+    const uint32_t sr = ((uint32_t)lac[5] << 8) | lac[6] | ((uint32_t)lac[7] << 16);
+    const bool rate_ok = sr == 44100 || sr == 48000 || sr == 96000 || sr == 192000;
+    if ((ch != 1 && ch != 2) || sm > 2 || (ch == 1 && sm != 0) || !rate_ok || (bd != 16 && bd != 24) || lac[9] != 0)
+        return fail("[decode-error] invalid frame header");
+    if (size < 14) return fail("[decode-error] invalid block count");
+    const uint32_t nb = be32(lac + 10);
+    if (nb == 0) return fail("[decode-error] invalid block count");
+    const uint64_t entry = version >= 3 ? 8u : 4u, head = stream_head_bytes(version, nb);
+    if (size < head) return fail("[decode-error] truncated block size table");
+    uint64_t frames = 0, pay = 0;
+    for (uint32_t b = 0; b < nb; ++b) {
+        const uint32_t n = be32(lac + 14 + entry * b);
+        if (n == 0 || n > (uint32_t)kMaxBlock || (b + 1 < nb && n < 256u)) return fail("[decode-error] invalid block size");
+        frames += n;
+        if (frames > 6912000000ull) return fail("[decode-error] total samples exceed maximum");
+        if (version >= 3) {
+            const uint32_t by = be32(lac + 18 + 8ull * b);
+            // The device reader's bit positions are 32-bit and relative to the block: a block must stay below 2^29 bytes.
+            // (The reference takes any non-zero size that fits the file; a block this long -- a Rice token at k = 0 may
+            // carry a unary part of up to 2^30 bits -- is a documented deviation, see lacx.h.)
+            if (by == 0 || by >= (1u << 29)) return fail("[decode-error] invalid compressed block size");
+            pay += by;
+            if (pay > size) return fail("[decode-error] compressed block sizes exceed frame payload");
+        }
+    }
+    const uint64_t wav_bytes = frames * (uint64_t)ch * (uint64_t)(bd / 8);
+    if (36u + wav_bytes + (wav_bytes & 1u) > 0xFFFFFFFFull) return fail("[decode-error] decoded WAV data exceeds RIFF limit");
+    if (version >= 3 && head + pay != size) return fail("[decode-error] block payloads do not fill the file");
+    if (version == 2 && size - head >= (1ull << 29)) return fail("[decode-error] version-2 payload too large for the serial reader");
+    out->sample_rate = sr;
+    out->blocks = nb;
+    out->frames = frames;
+    out->channels = (uint8_t)ch;
+    out->bit_depth = (uint8_t)bd;
+    out->stereo_mode = (uint8_t)sm;
+    out->version = (uint8_t)version;
+    return LACX_OK;
+}
+
+// the decoded WAV image of a stream: 44-byte header, data, pad byte (below 2^32: parse_stream's RIFF limit)
+inline uint64_t wav_image_bytes(const lacx_stream_info& f) {
+    const uint64_t data = f.frames * (uint64_t)f.channels * (f.bit_depth / 8u);
+    return 44u + data + (data & 1u);
+}
+
+// One item of a decode job: the stream, and for the device and host forms the caller's output arrays.  With a sample type
+// (window job): frames [start, start + frames) of the stream, as that sample type.
+struct BatchIn {
+    const uint8_t* lac;
+    uint64_t size;
+    int32_t* left;
+    int32_t* right;
+    uint64_t frames;
+    uint64_t start = 0;
+    // verify form: the source PCM (device-resident), or -- lacx_decoder_verify_wav, a batch of one -- the WAV data chunk
+    // in host memory, which the decoder uploads behind the payload and VerifySource::data0 then points at
+    lacx_pcm pcm = {nullptr, nullptr, 0, 0};
+    const uint8_t* host_src = nullptr;
+    uint64_t host_src_bytes = 0;
+};
+
+// Where the decoded items go.  wav: the images into the decoder's pinned image buffer (each item's 16-byte aligned, one
+// D2H copy for all).  device: the caller's device arrays, in place, on the caller's stream.  host: the decoder's own PCM
+// buffers, then, once the statuses are checked, the caller's host arrays of the items that decoded.  verify: the
+// decoder's own PCM buffers, compared there with each item's source PCM (k_verify in place of the other post passes);
+// what comes back is a result per item and, for an item that differs, LACX_E_MISMATCH.
+// The device and host forms also come as window jobs (sample_type = LACX_SAMPLE_I32 / _F32 instead of kWholeStreams,
+// DESIGN §6b): a version-3 item then covers just the blocks that overlap its window -- only their bytes are uploaded,
+// they decode whole into the decoder's PCM buffers (scratch) and are all checked, and k_window_out writes the window's
+// frames out; a version-2 item (no compressed sizes) decodes in full and is then windowed.  The host form's windows go
+// through the decoder's image buffer, copied to the caller once the statuses are checked.
+enum class DecodeForm { wav, device, host, verify };
+constexpr int kWholeStreams = -1;
+
+// One item that goes to the device (j counts these; the items that failed their checks are not among them).
+struct PlanItem {
+    uint32_t src;        // its index in the job's BatchIn array
+    uint32_t blk_first;  // what it decodes: its blocks from blk_first on (item.blocks of them) ...
+    uint64_t pay_src;    // ... and their pay_bytes payload bytes from pay_src on, counted from the end of the stream's
+    uint64_t pay_bytes;  //     head (0 and the whole stream but for a window)
+    uint64_t head;       // stream_head_bytes of the stream
+    uint64_t pcm_at;     // own PCM buffers: the item's first frame there, a multiple of 4 (16-byte loads)
+    uint64_t image_at, image_size;  // image buffer: the WAV image (16-byte aligned), or a host window's left, then right
+    lacx_stream_info info;
+    DecodeItem item;     // left / right / wav are null until plan_fill_tables
+    WindowOut win;       // window job; left / right as above
+};
+
+// The tables the kernels read, one upload: items | byte_off [T + 1] | frame_off [T + 1] | unit_off [m + 1] | blk_item [T]
+// | lane_blk | v2_items, then for a window job | win [m], for the verify form | ver [m] | res [m] (byte offsets)
+struct TableLayout {
+    size_t items, byte_off, frame_off, unit_off, blk_item, lane_blk, v2_items, win, res, size;
+};
+
+struct DecodePlan {
+    DecodeForm form = DecodeForm::host;
+    int sample_type = kWholeStreams;
+    bool window() const { return sample_type != kWholeStreams; }
+    bool own_pcm() const { return form != DecodeForm::device || window(); }  // into the decoder's PCM buffers
+    bool host_window() const { return form == DecodeForm::host && window(); }
+    std::vector<PlanItem> items;
+    // k_decode's lanes: lane g decodes global block lane_blk[g] (~0u: idle); version-3 blocks only, an item's in
+    // consecutive lanes.  v2_items: the version-2 items, one lane each (k_decode_serial)
+    std::vector<uint32_t> lane_blk, v2_items;
+    uint64_t total_blocks = 0, total_frames = 0, total_pay = 0, total_units = 0, pcm_total = 0, image_total = 0;
+    // the verify form of a WAV image in host memory (a batch of one): the data chunk lies behind the payload and its pad,
+    // at the 16-byte aligned src_at (a device allocation's base is aligned further)
+    const uint8_t* host_src = nullptr;
+    uint64_t host_src_bytes = 0, src_at = 0;
+    TableLayout at{};
+    // What the run must provide (0: that buffer is not used).  payload: bytes, with kDecodeTailPad behind the last block
+    // (and behind the host source, where there is one); blocks: status and flag entries; pcm_frames: samples of each
+    // channel's buffer; image, stage (the pinned payload stage of a window job), tables: bytes.
+    struct {
+        uint64_t payload, blocks, pcm_frames, image, stage, tables;
+    } need{};
+};
+
+namespace plan_detail {
+inline const char* check_window(const BatchIn& x, const lacx_stream_info& f) {  // inside the stream (no wrap-around), then the arrays
+    if (x.frames == 0) return "empty window";
+    if (x.start >= f.frames || x.frames > f.frames - x.start) return "window outside the stream";
+    if (!x.left || (f.channels == 2 && !x.right)) return "output arrays missing";
+    return nullptr;
+}
+inline const char* check_source(const BatchIn& x, const lacx_stream_info& f) {  // the verify form's source against the stream
+    const lacx_pcm& p = x.pcm;
+    const uintptr_t a0 = (uintptr_t)p.data0, a1 = (uintptr_t)p.data1;
+    const bool planar = p.layout == LACX_PCM_PLANAR_I32;
+    if (p.layout > LACX_PCM_INTERLEAVED_I24) return "unknown source layout";
+    if (p.channels != f.channels) return "source channel count does not match the stream";
+    if ((!p.data0 && !x.host_src) || (planar && p.channels == 2 && !p.data1)) return "source arrays missing";
+    if (x.frames != f.frames) return "source frame count does not match the stream";
+    if ((p.layout == LACX_PCM_INTERLEAVED_I16 && f.bit_depth != 16) || (p.layout == LACX_PCM_INTERLEAVED_I24 && f.bit_depth != 24))
+        return "source layout does not match the stream's bit depth";
+    if ((p.layout != LACX_PCM_INTERLEAVED_I24 && (a0 & 3u)) || (planar && (a1 & 3u))) return "source arrays are not 4-byte aligned";
+    return nullptr;
+}
+inline const char* check_arrays(const BatchIn& x, const lacx_stream_info& f) {  // lacx_decoder_decode's checks of the output arrays
+    if (!x.left || (f.channels == 2 && !x.right)) return "output arrays missing";
+    if (x.frames != f.frames) return "output arrays do not match the stream's frame count";
+    return nullptr;
+}
+constexpr size_t up16(size_t v) { return (v + 15u) & ~(size_t)15u; }
+}  // namespace plan_detail
+
+// Plans n streams as one decode (a single stream is n = 1).  Every item is parsed and checked on the host; those that
+// pass go to the device together: their payloads back to back in one buffer (the tail pad after the last), their block
+// tables as global prefix sums, one lane per version-3 block and one per version-2 item, then one post pass over all of
+// them.  Per item, code[i] and err[i] ("" = goes to the device).  pad_waves: every item's blocks start a new wave.
+// Returns null, or why the job as a whole cannot run (nothing is laid out then).
+inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, int sample_type, bool pad_waves, DecodePlan& plan,
+                               std::vector<int>& code, std::vector<std::string>& err) {
+    using namespace plan_detail;
+    plan = DecodePlan{};
+    plan.form = form;
+    plan.sample_type = sample_type;
+    const bool window = plan.window(), own_pcm = plan.own_pcm(), wav = form == DecodeForm::wav, verify = form == DecodeForm::verify;
+    code.assign(n, LACX_OK);
+    err.assign(n, std::string());
+    plan.items.reserve(n);
+    uint32_t v3_blocks = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const BatchIn& x = in[i];
+        PlanItem p{};
+        lacx_stream_info& f = p.info;
+        const char* why = nullptr;
+        int c = parse_stream(x.lac, x.size, &f, &why);
+        if (c == LACX_OK && (why = window ? check_window(x, f) : verify ? check_source(x, f) : wav ? nullptr : check_arrays(x, f)))
+            c = LACX_E_INVALID;
+        if (c != LACX_OK) {
+            code[i] = c;
+            err[i] = why;
+            continue;
+        }
+        p.src = i;
+        p.head = stream_head_bytes(f.version, f.blocks);
+        uint32_t nb = f.blocks;
+        uint64_t frames = f.frames, fr0 = 0;
+        p.pay_bytes = x.size - p.head;
+        if (window && f.version != 2) {  // the blocks [blk_first, blk_first + nb) that hold the window's first and last frames
+            const uint64_t last = x.start + x.frames - 1;
+            uint64_t fr = 0, by = 0;
+            for (uint32_t b = 0;; ++b) {  // (the parse guarantees that the window's last frame lies in a block)
+                const uint32_t nfr = be32(x.lac + 14 + 8ull * b), nby = be32(x.lac + 18 + 8ull * b);
+                if (fr <= x.start && x.start < fr + nfr) p.blk_first = b, p.pay_src = by, fr0 = fr;
+                if (last < fr + nfr) {
+                    nb = b + 1 - p.blk_first;
+                    p.pay_bytes = by + nby - p.pay_src;
+                    frames = fr + nfr - fr0;
+                    break;
+                }
+                fr += nfr;
+                by += nby;
+            }
+        }
+        if (window) {
+            p.win = WindowOut{nullptr, nullptr, x.start - fr0, x.frames};
+            p.image_at = plan.image_total;  // the host form's staging: left, then right
+            p.image_size = 4 * x.frames * f.channels;
+            plan.image_total += p.image_size;
+        }
+        if (wav) {
+            p.image_at = plan.image_total;
+            p.image_size = wav_image_bytes(f);
+            plan.image_total += up16(p.image_size);
+        }
+        if (window || verify || wav) plan.total_units += (frames + 3u) / 4u;  // the post passes' units of 4 frames
+        DecodeItem& y = p.item;
+        y.frame0 = plan.total_frames;
+        y.frames = frames;
+        y.pay_off = plan.total_pay;
+        y.block0 = (uint32_t)plan.total_blocks;
+        y.blocks = nb;
+        y.pay_bits = f.version == 2 ? (uint32_t)(8ull * (x.size - p.head)) : 0u;  // < 2^32: parse_stream
+        y.channels = f.channels;
+        y.stereo_mode = f.stereo_mode;
+        y.bit_depth = f.bit_depth;
+        y.version = f.version;
+        if (own_pcm) {
+            p.pcm_at = plan.pcm_total;
+            plan.pcm_total += (frames + 3u) & ~3ull;
+        }
+        plan.total_blocks += nb;
+        plan.total_frames += frames;
+        plan.total_pay += p.pay_bytes;
+        if (f.version != 2) v3_blocks += nb;
+        plan.items.push_back(p);
+    }
+    if (plan.total_blocks >= (1ull << 31)) return "batch holds 2^31 blocks or more";
+    const size_t m = plan.items.size(), T = (size_t)plan.total_blocks;
+    plan.lane_blk.reserve(v3_blocks);
+    for (uint32_t j = 0; j < m; ++j) {
+        const DecodeItem& y = plan.items[j].item;
+        if (y.version == 2) {
+            plan.v2_items.push_back(j);
+            continue;
+        }
+        if (pad_waves) while (plan.lane_blk.size() % 64u) plan.lane_blk.push_back(~0u);
+        for (uint32_t b = 0; b < y.blocks; ++b) plan.lane_blk.push_back(y.block0 + b);
+    }
+    if (verify && m == 1 && in[plan.items[0].src].host_src) {
+        plan.host_src = in[plan.items[0].src].host_src;
+        plan.host_src_bytes = in[plan.items[0].src].host_src_bytes;
+        plan.src_at = up16(plan.total_pay + kDecodeTailPad);
+    }
+    TableLayout& at = plan.at;
+    at.items = 0;
+    at.byte_off = up16(sizeof(DecodeItem) * m);
+    at.frame_off = at.byte_off + 8 * (T + 1);
+    at.unit_off = at.frame_off + 8 * (T + 1);
+    at.blk_item = at.unit_off + 8 * (m + 1);
+    at.lane_blk = at.blk_item + 4 * T;
+    at.v2_items = at.lane_blk + 4 * plan.lane_blk.size();
+    const size_t end = at.v2_items + 4 * plan.v2_items.size();
+    at.win = up16(end);
+    at.res = at.win + sizeof(VerifySource) * m;
+    at.size = verify ? at.res + sizeof(VerifyWords) * m : window ? at.win + sizeof(WindowOut) * m : end;
+    plan.need.payload = (plan.host_src ? plan.src_at + plan.host_src_bytes : plan.total_pay) + kDecodeTailPad;
+    plan.need.blocks = T;
+    plan.need.pcm_frames = own_pcm ? plan.pcm_total : 0;
+    plan.need.image = wav || plan.host_window() ? up16(plan.image_total) : 0;  // k_wav_pack writes whole dwords, and only inside the image
+    plan.need.stage = window ? plan.total_pay : 0;
+    plan.need.tables = at.size;
+    return nullptr;
+}
+
+// The base addresses of the run's buffers, as the kernels will see them.
+struct PlanBases {
+    uint8_t* payload;
+    int32_t* left;  // own PCM buffers
+    int32_t* right;
+    uint8_t* image;
+};
+
+// The plan's offsets as pointers: fills the tables (plan.at, plan.need.tables bytes at h), the verify form's initial result
+// words among them.
+inline void plan_fill_tables(const DecodePlan& plan, const BatchIn* in, const PlanBases& base, uint8_t* h) {
+    const TableLayout& at = plan.at;
+    const uint32_t m = (uint32_t)plan.items.size();
+    auto* items = reinterpret_cast<DecodeItem*>(h + at.items);
+    auto* byte_off = reinterpret_cast<unsigned long long*>(h + at.byte_off);
+    auto* frame_off = reinterpret_cast<unsigned long long*>(h + at.frame_off);
+    auto* unit_off = reinterpret_cast<unsigned long long*>(h + at.unit_off);
+    auto* blk_item = reinterpret_cast<uint32_t*>(h + at.blk_item);
+    auto* win = reinterpret_cast<WindowOut*>(h + at.win);
+    auto* ver = reinterpret_cast<VerifySource*>(h + at.win);
+    auto* res = reinterpret_cast<VerifyWords*>(h + at.res);
+    byte_off[0] = frame_off[0] = unit_off[0] = 0;
+    for (uint32_t j = 0; j < m; ++j) {
+        const PlanItem& p = plan.items[j];
+        const BatchIn& x = in[p.src];
+        DecodeItem y = p.item;
+        const bool v2 = y.version == 2, stereo = y.channels == 2;
+        const uint64_t entry = v2 ? 4u : 8u;
+        for (uint32_t b = 0; b < y.blocks; ++b) {
+            const uint32_t g = y.block0 + b;
+            const uint64_t sb = p.blk_first + b;  // the block within the stream
+            frame_off[g + 1] = frame_off[g] + be32(x.lac + 14 + entry * sb);
+            byte_off[g + 1] = v2 ? byte_off[g] : byte_off[g] + be32(x.lac + 18 + 8ull * sb);
+            blk_item[g] = j;
+        }
+        // the version-2 item's bytes count in the byte offsets as one lump at its last block
+        if (v2) byte_off[y.block0 + y.blocks] = y.pay_off + (y.pay_bits >> 3);
+        unit_off[j + 1] = unit_off[j] + (y.frames + 3u) / 4u;
+        y.left = plan.own_pcm() ? base.left + p.pcm_at : x.left;
+        y.right = !stereo ? nullptr : plan.own_pcm() ? base.right + p.pcm_at : x.right;
+        if (plan.form == DecodeForm::wav) y.wav = base.image + p.image_at;
+        items[j] = y;
+        if (plan.window()) {
+            WindowOut w = p.win;
+            uint8_t* stage = base.image + p.image_at;
+            w.left = plan.host_window() ? (void*)stage : x.left;
+            w.right = !stereo ? nullptr : plan.host_window() ? (void*)(stage + 4 * w.frames) : x.right;
+            win[j] = w;
+        }
+        if (plan.form == DecodeForm::verify) {
+            ver[j] = VerifySource{plan.host_src ? base.payload + plan.src_at : x.pcm.data0, x.pcm.data1, x.pcm.layout, 0};
+            res[j] = VerifyWords{0, ~0ull, 0, 0, 0, 0};
+        }
+    }
+    if (!plan.lane_blk.empty()) std::memcpy(h + at.lane_blk, plan.lane_blk.data(), 4 * plan.lane_blk.size());
+    if (!plan.v2_items.empty()) std::memcpy(h + at.v2_items, plan.v2_items.data(), 4 * plan.v2_items.size());
+}
+
+// The kernels' arguments: the tables at `tables` (where the kernels see them), the run's payload, status and flag arrays.
+inline DecodeArgs plan_args(const DecodePlan& plan, const uint8_t* tables, const uint8_t* payload, uint32_t* status, uint8_t* ms_flag) {
+    const TableLayout& at = plan.at;
+    DecodeArgs a;
+    a.nitems = (uint32_t)plan.items.size();
+    a.total_blocks = (uint32_t)plan.total_blocks;
+    a.items = reinterpret_cast<const DecodeItem*>(tables + at.items);
+    a.blk_item = reinterpret_cast<const uint32_t*>(tables + at.blk_item);
+    a.lanes = (uint32_t)plan.lane_blk.size();
+    a.lane_blk = reinterpret_cast<const uint32_t*>(tables + at.lane_blk);
+    a.nv2 = (uint32_t)plan.v2_items.size();
+    a.v2_items = reinterpret_cast<const uint32_t*>(tables + at.v2_items);
+    a.payload = payload;
+    a.byte_off = reinterpret_cast<const unsigned long long*>(tables + at.byte_off);
+    a.frame_off = reinterpret_cast<const unsigned long long*>(tables + at.frame_off);
+    a.status = status;
+    a.ms_flag = ms_flag;
+    a.wav = plan.form == DecodeForm::wav;
+    a.unit_off = reinterpret_cast<const unsigned long long*>(tables + at.unit_off);
+    a.total_units = plan.total_units;
+    if (plan.window()) a.window = reinterpret_cast<const WindowOut*>(tables + at.win);
+    a.f32 = plan.sample_type == LACX_SAMPLE_F32;
+    if (plan.form == DecodeForm::verify) {
+        a.verify = reinterpret_cast<const VerifySource*>(tables + at.win);
+        a.verify_res = reinterpret_cast<VerifyWords*>(const_cast<uint8_t*>(tables) + at.res);
+    }
+    return a;
+}
+
+}  // namespace lacx

@@ -178,53 +178,7 @@ hipError_t launch_stream_out(const LaunchSet& ls, const DeviceWorkspace& ws, uin
 // [total_blocks + 1] prefix sums over the concatenated payloads and frames; status[blk] = 0 or an error code and
 // ms_flag[blk] = the block's LR/MS flag, per global block.  The payload must be followed by kDecodeTailPad readable zero
 // bytes (the bit reader's bounded look-ahead past the last block, see BitIn).
-// (kDecodeTailPad: lacx_types.h)
-struct DecodeItem {
-    int32_t* left;                // the item's PCM from its frame 0 (16-byte aligned in the WAV form)
-    int32_t* right;               // null for mono
-    uint8_t* wav;                 // WAV form: the item's image (16-byte aligned; header is the host's), else null
-    unsigned long long frame0;    // frame_off of the item's first block
-    unsigned long long frames;
-    unsigned long long pay_off;   // byte offset of the item's payload (where a version-2 item's lane starts)
-    uint32_t block0, blocks;      // the item's global blocks
-    uint32_t pay_bits;            // version 2 only: payload bits
-    uint8_t channels, stereo_mode, bit_depth, version;
-};
-// Window form: an item's decoded frames are those of the blocks that overlap its window, from the first of them on.
-struct WindowOut {
-    void* left;                   // the window's samples from its frame 0 on: int32 or float32, 4-byte aligned
-    void* right;                  // null for mono
-    unsigned long long start;     // the window's first frame, counted in the item's decoded frames
-    unsigned long long frames;    // >= 1
-};
-struct DecodeArgs {
-    uint32_t nitems = 0, total_blocks = 0;
-    const DecodeItem* items = nullptr;        // (window form: an item covers only the blocks its window needs)
-    const uint32_t* blk_item = nullptr;       // [total_blocks] the item of every block
-    // k_decode: lane g decodes block lane_blk[g] (~0u: idle); only version-3 blocks, an item's in consecutive lanes
-    uint32_t lanes = 0;
-    const uint32_t* lane_blk = nullptr;
-    uint32_t nv2 = 0;                         // version-2 items, one lane each (k_decode_serial)
-    const uint32_t* v2_items = nullptr;
-    const uint8_t* payload = nullptr;         // followed by kDecodeTailPad zero bytes
-    const unsigned long long* byte_off = nullptr;
-    const unsigned long long* frame_off = nullptr;
-    uint32_t* status = nullptr;
-    uint8_t* ms_flag = nullptr;
-    // wav = false: k_ms_inverse in place into every item's left / right; true: k_wav_pack into the items'
-    // images (unit_off: [nitems + 1] prefix sums of ceil(frames / 4)), left / right then hold the pre-inverse samples
-    bool wav = false;
-    const unsigned long long* unit_off = nullptr;
-    unsigned long long total_units = 0;
-    // window form (non-null: k_window_out over the units of unit_off in place of k_ms_inverse / k_wav_pack): window[j]
-    // says which of item j's decoded frames go where; f32: float32 samples scaled by 2^-(bit_depth - 1), else int32
-    const WindowOut* window = nullptr;
-    bool f32 = false;
-    // verify form (non-null: k_verify over the units of unit_off in place of the other post passes, then k_verify_fill):
-    // verify[j] is the source PCM of item j, verify_res[j] its result words (count 0 and key all ones on entry)
-    const VerifySource* verify = nullptr;
-    VerifyWords* verify_res = nullptr;
-};
+// DecodeItem, WindowOut, DecodeArgs: lacx_types.h (the host-only plan, decode_plan.h, fills them)
 hipError_t launch_decode(const DecodeArgs& args, hipStream_t stream);
 
 // Block::Encoder::encode's analysis for one block of arbitrary int32 samples (wide.hip): d_res = scratch for the eleven

@@ -23,6 +23,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "lossless-audio-codec_amd", "csrc")
+INCLUDE = os.path.join(ROOT, "include")  # lacx.h: decode_plan.h speaks the ABI's types
 BUILD = os.path.join(ROOT, "tests", "native", "_build")
 SRC = os.path.join(ROOT, "tests", "native", "sim_decode.cpp")
 DEFAULT_PAD = 0xFFFFFFFF  # "what the device path appends": the twin takes kDecodeTailPad from lacx_types.h itself
@@ -37,7 +38,7 @@ _lib = None
 
 
 def _sources():
-    return [SRC] + [os.path.join(CSRC, h) for h in ("decode_core.h", "analyze_core.h", "lacx_types.h", "x87.h")]
+    return [SRC] + [os.path.join(CSRC, h) for h in ("decode_core.h", "analyze_core.h", "lacx_types.h", "x87.h", "decode_plan.h")]
 
 
 def _stale(target):
@@ -51,7 +52,7 @@ def lib():
         os.makedirs(BUILD, exist_ok=True)
         so = os.path.join(BUILD, "libsim_decode.so")
         if _stale(so):
-            subprocess.check_call(["g++", "-O2", "-std=c++20", "-fPIC", "-shared", "-I", CSRC, SRC, "-o", so])
+            subprocess.check_call(["g++", "-O2", "-std=c++20", "-fPIC", "-shared", "-I", CSRC, "-I", INCLUDE, SRC, "-o", so])
         _lib = C.CDLL(so)
         _lib.sim_hash.restype = C.c_uint64
         _lib.sim_tail_pad.restype = C.c_uint32
@@ -65,7 +66,7 @@ def sanitized_exe(extra=(), name="sim_decode_san"):
     if extra or _stale(exe):
         # compile, then link: only a failing LINK for want of the sanitizer runtime means "not available"
         obj = exe + ".o"
-        flags = ["g++", "-std=c++20", *SANITIZE, "-DSIM_DECODE_MAIN", *extra, "-I", CSRC]
+        flags = ["g++", "-std=c++20", *SANITIZE, "-DSIM_DECODE_MAIN", *extra, "-I", CSRC, "-I", INCLUDE]
         built = subprocess.run(flags + ["-c", SRC, "-o", obj], capture_output=True, text=True)
         assert built.returncode == 0, built.stderr
         linked = subprocess.run(["g++", *SANITIZE, obj, "-o", exe], capture_output=True, text=True)
@@ -170,3 +171,133 @@ def run_sanitized(streams, settings=ALL_SETTINGS, pad=DEFAULT_PAD, exe=None, wor
             rc = run.returncode or 1
             err += run.stderr[-4000:]
     return lines, rc, err
+
+
+# ---- batches: sim_decode_batch / sim_batch_digest / sim_plan_dump (jobs planned by csrc/decode_plan.h) ----
+BatchItem = namedtuple("BatchItem", "refused status ms left right start frames blk_first blocks")
+FORMS = {"wav": 0, "device": 1, "host": 2, "verify": 3}  # DecodeForm
+WHOLE, I32, F32 = -1, 0, 1                                 # sample type: whole streams, or windows of that type
+
+
+def _job(lacs, windows):
+    n = len(lacs)
+    ptrs = (C.c_char_p * n)(*lacs)
+    sizes = (C.c_uint64 * n)(*[len(x) for x in lacs])
+    start = (C.c_uint64 * n)(*[w[0] for w in windows]) if windows else None
+    frames = (C.c_uint64 * n)(*[w[1] for w in windows]) if windows else None
+    return n, ptrs, sizes, start, frames
+
+
+def decode_batch(lacs, windows=None, pad_waves=False, never_lean=False, cols=1):
+    """n streams as one job (windows: [(start, frames)] per stream, or whole streams) -> ([BatchItem], over).  An item's
+    left / right are the scratch PCM of the blocks it covers (blocks from blk_first on); a window is
+    left[start:start + frames] of that."""
+    n, ptrs, sizes, start, frames = _job(lacs, windows)
+    shapes = [_shape(x) if len(x) >= 14 and x[2] in (2, 3) else (0, []) for x in lacs]
+    nblocks = sum(min(nb, len(fr)) for nb, fr in shapes) + 1
+    npcm = sum((sum(fr) + 3) // 4 * 4 for _, fr in shapes) + 4
+    rec = np.zeros(8 * n, np.uint64)
+    status, ms = np.zeros(nblocks, np.uint32), np.zeros(nblocks, np.uint8)
+    left, right = np.zeros(npcm, np.int32), np.zeros(npcm, np.int32)
+    over = C.c_uint32()
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    rc = lib().sim_decode_batch(ptrs, sizes, C.c_uint32(n), start, frames, int(pad_waves), int(never_lean), int(cols), vp(rec),
+                                vp(status), vp(ms), vp(left), vp(right), C.byref(over))
+    assert rc == 0
+    items = []
+    for i, lac in enumerate(lacs):
+        refused, at, got, w0, wn, b0, nb, g0 = (int(v) for v in rec[8 * i:8 * i + 8])
+        if refused:
+            items.append(BatchItem(True, None, None, None, None, 0, 0, 0, 0))
+            continue
+        items.append(BatchItem(False, status[g0:g0 + nb], ms[g0:g0 + nb], left[at:at + got],
+                               right[at:at + got] if lac[3] == 2 else None, w0, wn, b0, nb))
+    return items, over.value
+
+
+def batch_case(lacs, windows=None, pad_waves=False, never_lean=False, cols=1) -> bytes:
+    """The case blob sim_batch_digest reads."""
+    flags = int(pad_waves) | (2 if windows else 0) | (4 if never_lean else 0) | (8 if cols == 64 else 0)
+    out = struct.pack("<II", len(lacs), flags)
+    for i, lac in enumerate(lacs):
+        s, f = windows[i] if windows else (0, 0)
+        out += struct.pack("<QQQ", s, f, len(lac)) + lac
+    return out
+
+
+def batch_digest(case: bytes, index: int) -> str:
+    """The plain build's line for a batch case (what the sanitized program must print for it)."""
+    buf = C.create_string_buffer(1 << 20)
+    rc = lib().sim_batch_digest(case, C.c_uint64(len(case)), C.c_uint32(index), buf, C.c_uint32(len(buf)))
+    assert rc == 0
+    return buf.value.decode()
+
+
+def run_sanitized_batches(cases, exe=None):
+    """Every batch case through the sanitized program (its `batch` mode): (lines, returncode, stderr)."""
+    if exe is None:
+        exe, why = sanitized_exe()
+        assert exe, why
+    with tempfile.NamedTemporaryFile(prefix="lac_batches_", suffix=".bin") as f:
+        for c in cases:
+            f.write(struct.pack("<I", len(c)))
+            f.write(c)
+        f.flush()
+        env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:verify_asan_link_order=0:abort_on_error=0",
+                   UBSAN_OPTIONS="print_stacktrace=1")
+        run = subprocess.run([exe, "batch", f.name], capture_output=True, text=True, env=env, timeout=900)
+    lines = [t for t in run.stdout.splitlines() if t and not t.startswith("done")]
+    rc = run.returncode or (0 if "done %d" % len(cases) in run.stdout else 1)
+    return lines, rc, run.stderr[-4000:]
+
+
+ITEM_DTYPE = np.dtype([("left", "<u8"), ("right", "<u8"), ("wav", "<u8"), ("frame0", "<u8"), ("frames", "<u8"), ("pay_off", "<u8"),
+                       ("block0", "<u4"), ("blocks", "<u4"), ("pay_bits", "<u4"), ("channels", "u1"), ("stereo_mode", "u1"),
+                       ("bit_depth", "u1"), ("version", "u1")])
+WINDOW_DTYPE = np.dtype([("left", "<u8"), ("right", "<u8"), ("start", "<u8"), ("frames", "<u8")])
+SOURCE_DTYPE = np.dtype([("data0", "<u8"), ("data1", "<u8"), ("layout", "<u4"), ("pad", "<u4")])
+WORDS_DTYPE = np.dtype([("count", "<u8"), ("key", "<u8"), ("decoded", "<i4"), ("source", "<i4"), ("block", "<u4"), ("pad", "<u4")])
+HEAD = ("m total_blocks total_frames total_pay total_units pcm_total image_total src_at host_src_bytes lanes nv2 "
+        "o_items o_byte o_frame o_unit o_bitem o_lane o_v2 o_win o_res o_size need_payload need_blocks need_pcm need_image "
+        "need_stage need_tables sizeof_item sizeof_window sizeof_source sizeof_words tail_pad").split()
+ITEM = "src blk_first pay_src pay_bytes head pcm_at image_at image_size frames win_start win_frames blocks".split()
+
+
+def base(k, i=0):
+    """The made-up address sim_plan_dump gives buffer k (0 payload, 1 left, 2 right, 3 image, 4 / 5 the caller's left /
+    right, 6 / 7 the sources) of input i."""
+    return ((k + 1) << 40) + (i << 32)
+
+
+def plan_dump(lacs, form, windows=None, sample_type=WHOLE, pad_waves=False, host_src_bytes=0):
+    """The product's plan of a job and its filled tables: a dict of the HEAD fields, `items` (dicts of ITEM), `rc` and
+    `msg` per input, and the tables: item, byte_off, frame_off, unit_off, blk_item, lane_blk, v2_items, window / source /
+    words where the form has them, and `raw`."""
+    n, ptrs, sizes, start, frames = _job(lacs, windows)
+    L = lib()
+    L.sim_plan_dump.restype = C.c_int64
+    head = np.zeros(len(HEAD), np.uint64)
+    item = np.zeros(len(ITEM) * n, np.uint64)
+    rc = np.zeros(n, np.int32)
+    msg = C.create_string_buffer(1 << 16)
+    cap = 1 << 22
+    raw = np.zeros(cap, np.uint8)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    size = L.sim_plan_dump(ptrs, sizes, C.c_uint32(n), start, frames, FORMS[form], int(sample_type), int(pad_waves),
+                           C.c_uint64(host_src_bytes), vp(head), vp(item), vp(rc), msg, C.c_uint32(len(msg)), vp(raw), C.c_uint64(cap))
+    assert size >= 0, msg.value
+    p = {k: int(v) for k, v in zip(HEAD, head)}
+    m, T = p["m"], p["total_blocks"]
+    p["items"] = [dict(zip(ITEM, (int(v) for v in item[len(ITEM) * j:len(ITEM) * (j + 1)]))) for j in range(m)]
+    p["rc"], p["msg"] = rc.tolist(), msg.value.decode().split("\n")
+    p["raw"] = raw = raw[:size]
+    tab = lambda off, dtype, count: np.frombuffer(raw, dtype=dtype, count=count, offset=off)  # noqa: E731
+    p["item"] = tab(p["o_items"], ITEM_DTYPE, m)
+    p["byte_off"], p["frame_off"] = tab(p["o_byte"], "<u8", T + 1), tab(p["o_frame"], "<u8", T + 1)
+    p["unit_off"], p["blk_item"] = tab(p["o_unit"], "<u8", m + 1), tab(p["o_bitem"], "<u4", T)
+    p["lane_blk"], p["v2_items"] = tab(p["o_lane"], "<u4", p["lanes"]), tab(p["o_v2"], "<u4", p["nv2"])
+    if sample_type != WHOLE:
+        p["window"] = tab(p["o_win"], WINDOW_DTYPE, m)
+    if form == "verify":
+        p["source"], p["words"] = tab(p["o_win"], SOURCE_DTYPE, m), tab(p["o_res"], WORDS_DTYPE, m)
+    return p
