@@ -352,6 +352,13 @@ int sim_block_encode(const int32_t* x, uint32_t n, int zero_run, int partitionin
     return run_emit_sim<Geo<16, 1024>>(x, n, &plan, out, cap);
 }
 
+// the same with the plan handed back as well: one analysis for both comparisons (tests/test_narrow_blocks_host.py)
+int sim_block_plan_and_encode(const int32_t* x, uint32_t n, int zero_run, int partitioning, int force_wide,
+                              ChannelPlan* plan, uint8_t* out, uint32_t cap) {
+    if (run_sim<Geo<16, 1024>>(x, n, zero_run, partitioning, force_wide, plan) != 0) return -1;
+    return run_emit_sim<Geo<16, 1024>>(x, n, plan, out, cap);
+}
+
 // geo: 0 = <16,1024> (full blocks), 1 = <4,64> (probe windows)
 // force_wide bit 0: run the 64-bit arithmetic variants even where the 32-bit fast path would be taken;
 // bit 1: use the per-order partition passes even where the fused pass applies; bit 2: no candidate pruning;
