@@ -187,6 +187,24 @@ int lacx_encode_shard_device_view(lacx_encoder* enc, const int32_t* d_left, cons
 #define LACX_PCM_PLANAR_I32 0u      /* data0 = left, data1 = right (NULL for mono) */
 #define LACX_PCM_INTERLEAVED_I16 1u /* data0 = interleaved little-endian int16 frames, 4-byte aligned */
 #define LACX_PCM_INTERLEAVED_I24 2u /* data0 = interleaved packed 3-byte little-endian samples */
+/* Tensor layouts (what torchaudio.load returns, what lacx_decoder_decode_window_batch_device writes); 3..15 and everything
+ * above 18 are unknown layouts.  Accepted by lacx_encode_shard_pcm_device_view / _begin, lacx_encode_batch_device and
+ * lacx_decoder_verify_batch_device; every other entry point that takes a lacx_pcm refuses them.
+ * A float32 sample x stands for the integer x * 2^(bit_depth - 1) of the configured bit depth (encode) or of the stream's
+ * (verify), the exact inverse of LACX_SAMPLE_F32.  It is a valid sample when that product is an integer inside
+ * [-2^(b-1), 2^(b-1) - 1]: -0.0 is 0 and -1.0 the most negative sample; 1.0, NaN, +-Inf, denormals and anything off the grid
+ * are not.  Nothing is ever rounded.  The encoder imports such a source into a buffer of its own with one kernel in
+ * front of the analysis (interleaved int16 at depth 16, packed int24 at depth 24) and validates it in the same pass: an
+ * integer outside the range fails the call with LACX_E_INVALID "<left|right> sample at index I is outside the configured PCM
+ * bit depth", any other invalid value with "<left|right> sample at index I is not an exact B-bit PCM value" (all of left
+ * first, then right; "stream i: " in front in a batch); no payload is returned and the encoder stays usable.  A mono
+ * LACX_PCM_PLANAR_I16 source on a 4-byte aligned address is LACX_PCM_INTERLEAVED_I16 mono and is read in place.
+ * Host checks, each LACX_E_INVALID: LACX_PCM_PLANAR_I16 at depth 24 "PCM layout does not match the configured bit depth",
+ * a planar source whose data1 does not fit its channel count (the planar text), "PCM arrays are not 2-byte aligned" /
+ * "PCM arrays are not 4-byte aligned".  Nothing outside [data, data + frames * channels * element size) is read. */
+#define LACX_PCM_PLANAR_I16      16u /* data0 = left, data1 = right (NULL for mono): int16, 2-byte aligned, bit depth 16 only */
+#define LACX_PCM_PLANAR_F32      17u /* data0 = left, data1 = right (NULL for mono): float32, 4-byte aligned               */
+#define LACX_PCM_INTERLEAVED_F32 18u /* data0 = frames interleaved (L R L R ...): float32, 4-byte aligned                  */
 typedef struct lacx_pcm {
     const void* data0;
     const void* data1;
@@ -285,7 +303,8 @@ uint32_t lacx_encoder_lanes(const lacx_encoder* enc); /* 1 for a plain encoder *
 void lacx_fanout_range(uint32_t nblocks, uint32_t nlanes, uint32_t lane, uint32_t* first, uint32_t* count);
 
 /* Shards already resident in device memory, shards[g] on the device of lane g (every shard but the last a whole number of
- * blocks): every lane encodes its shard, the sizes are exchanged, out[g] views the lane's payload and block table in its
+ * blocks; LACX_PCM_PLANAR_I32 or an interleaved integer layout -- a tensor layout gives LACX_E_INVALID "PCM layout is not
+ * supported by the fan-out"): every lane encodes its shard, the sizes are exchanged, out[g] views the lane's payload and block table in its
  * pinned result region (valid until the encoder's next call) with its byte offset in the stream's payload.  No
  * concatenation: lacx_assemble builds the .lac from the views where one contiguous buffer is wanted. */
 typedef struct lacx_fanout_shard {
@@ -444,14 +463,19 @@ int lacx_decoder_decode_window(lacx_decoder* dec, const uint8_t* lac, uint64_t s
 /* Verification: does a .lac decode to exactly the PCM it was made from?  The stream is decoded into the decoder's own
  * buffers and compared there, sample by sample as full int32 values, with the source PCM in the source's own layout
  * (lacx_pcm, as on the encode side: planar int32 with 4-byte aligned arrays, interleaved int16 with a 4-byte aligned
- * base, packed interleaved int24 at any byte alignment); no PCM crosses PCIe towards the host, only 32 bytes per item.
+ * base, packed interleaved int24 at any byte alignment, planar int16 with 2-byte aligned arrays -- depth 16 only --, planar
+ * and interleaved float32 with 4-byte aligned arrays); no PCM crosses PCIe towards the host, only 32 bytes per item.
+ * A float32 source sample that is no valid sample of the stream's bit depth (see LACX_PCM_PLANAR_F32) can never equal a
+ * decoded one: it counts as a differing sample, and lacx_verify_result.source then holds x * 2^(b-1) rounded to nearest
+ * (ties to even) and saturated to int32, INT32_MIN for a NaN.
  * Nothing outside [data, data + frames * channels * bytes per sample) of an interleaved source, or outside [0, frames)
  * of a planar array, is read.
  * lacx_decoder_verify_batch_device: many streams as one device job, versions 3 and 2.  Per-item outcome, return code,
  * lacx_decoder_item_error, device-less behaviour and `stream` exactly as lacx_decoder_decode_batch_device.  Checked per
  * item on the host before any device call, each LACX_E_INVALID: "unknown source layout", "source channel count does not
  * match the stream", "source arrays missing", "source frame count does not match the stream", "source layout does not
- * match the stream's bit depth" (an interleaved layout fixes the depth), "source arrays are not 4-byte aligned".  An item
+ * match the stream's bit depth" (an interleaved integer layout and planar int16 fix the depth), "source arrays are not 4-byte
+ * aligned", "source arrays are not 2-byte aligned" (planar int16).  An item
  * that does not decode gets the decode's own code and message and a zeroed result.  An item that decodes to something
  * else gets LACX_E_MISMATCH, its result filled, and the message
  *   [verify-error] block=N channel=left|right frame=F decoded=X source=Y mismatches=M

@@ -578,6 +578,7 @@ void lacx_encoder_destroy(lacx_encoder* e) {
         if (e->d_raw) (void)hipFree(e->d_raw);
         if (e->d_batch) (void)hipFree(e->d_batch);
         if (e->d_wide) (void)hipFree(e->d_wide);
+        import_free(e);
         if (e->h_payload_base) (void)hipHostFree(e->h_payload_base);
         if (e->h_table) (void)hipHostFree(e->h_table);
         if (e->h_totals) (void)hipHostFree(e->h_totals);

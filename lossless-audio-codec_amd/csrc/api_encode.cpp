@@ -326,6 +326,22 @@ int lacx_encode_shard_pcm_device_begin(lacx_encoder* e, const lacx_pcm* pcm, uin
         return encode_device_begin(e, static_cast<const int32_t*>(pcm->data0), static_cast<const int32_t*>(pcm->data1), frames,
                                    static_cast<hipStream_t>(stream));
     }
+    if (is_import_layout(pcm->layout)) {
+        // a tensor layout: one import kernel on the call's stream rewrites it into the encoder's own buffer, in a layout the
+        // front kernels read, and validates it; _end looks at the outcome
+        if (const char* why = import_source_error(*pcm, e->cfg.bit_depth, false)) return fail(e, LACX_E_INVALID, why);
+        if (e->pend.active) return fail(e, LACX_E_RUNTIME, "an encode is already in flight on this encoder");
+        import_reset(e);
+        int layout = 0;
+        const int item = import_add(e, *pcm, frames, e->cfg.bit_depth, 0, &layout);
+        hipStream_t st = stream ? static_cast<hipStream_t>(stream) : e->stream[0];
+        rc = import_enqueue(e, st);
+        if (rc) return rc;
+        const int32_t* data = item < 0 ? static_cast<const int32_t*>(pcm->data0) : import_data(e, item);
+        rc = encode_device_begin(e, data, nullptr, frames, static_cast<hipStream_t>(stream), layout, (int)pcm->channels);
+        if (rc) e->imp.pending = false;
+        return rc;
+    }
     const int want_depth = pcm->layout == LACX_PCM_INTERLEAVED_I16 ? 16 : (pcm->layout == LACX_PCM_INTERLEAVED_I24 ? 24 : 0);
     if (want_depth == 0) return fail(e, LACX_E_INVALID, "unknown PCM layout");
     if (e->cfg.bit_depth != want_depth) return fail(e, LACX_E_INVALID, "PCM layout does not match the configured bit depth");
@@ -339,6 +355,10 @@ int lacx_encode_shard_end(lacx_encoder* e, const uint8_t** payload, uint64_t* pa
     const uint32_t nb = e->pend.nb;
     uint64_t pay = 0;
     const int rc = encode_device_end(e, &pay);
+    // an imported source that held a float which is no sample: the call fails, whatever the kernels made of the zeros
+    // that stand in for it (its words are final: the import kernel ran in front of everything the call just waited for)
+    const int ic = import_check(e, false);
+    if (ic && (rc == LACX_OK || rc == -1)) return ic;
     if (rc == -1) return fail(e, LACX_E_RUNTIME, "payload exceeds the pinned result reservation");
     if (rc) return rc;
     *payload = e->h_payload;

@@ -534,6 +534,8 @@ uint32_t lacx_encoder_lanes(const lacx_encoder* e) { return e && e->fan ? (uint3
 
 int lacx_encode_fanout_resident(lacx_encoder* e, const lacx_fanout_shard* shards, uint32_t nshards, lacx_fanout_out* out) {
     if (!e || !shards || !out) return LACX_E_INVALID;
+    for (uint32_t g = 0; g < nshards; ++g)
+        if (is_import_layout(shards[g].pcm.layout)) return fail(e, LACX_E_INVALID, "PCM layout is not supported by the fan-out");
     if (!e->fan) {  // a plain encoder: one shard, no exchange
         if (nshards != 1) return fail(e, LACX_E_INVALID, "more shards than the encoder has lanes");
         const int rc = lacx_encode_shard_pcm_device_view(e, &shards[0].pcm, shards[0].frames, nullptr, &out[0].payload,

@@ -840,6 +840,8 @@ int encode_batch(lacx_encoder* e, const lacx_batch_item* items, uint32_t n, hipS
     uint32_t nb = 0, nitems = 0, nwg = 0;
     uint64_t region = 0;
     int max_depth = 16;
+    import_reset(e);
+    std::vector<int> imp_item(n, -1);  // streams in a tensor layout: their item of the import pass
     for (uint32_t i = 0; i < n; ++i) {
         const lacx_batch_item& it = items[i];
         const std::string who = "stream " + std::to_string(i) + ": ";
@@ -856,6 +858,9 @@ int encode_batch(lacx_encoder* e, const lacx_batch_item* items, uint32_t n, hipS
             if ((it.pcm.layout == LACX_PCM_INTERLEAVED_I16 ? 16 : 24) != it.bit_depth)
                 return fail(e, LACX_E_INVALID, who + "PCM layout does not match the bit depth");
             layout = (int)it.pcm.layout;
+        } else if (is_import_layout(it.pcm.layout)) {
+            if (const char* why = import_source_error(it.pcm, it.bit_depth, true)) return fail(e, LACX_E_INVALID, who + why);
+            imp_item[i] = import_add(e, it.pcm, it.frames, it.bit_depth, i, &layout);
         } else {
             return fail(e, LACX_E_INVALID, who + "unknown PCM layout");
         }
@@ -933,6 +938,11 @@ int encode_batch(lacx_encoder* e, const lacx_batch_item* items, uint32_t n, hipS
     e->timing.emit_ms = 0;
     const auto t0 = clk::now();
     hipStream_t s = user_stream ? user_stream : e->stream[0];
+    // the streams in a tensor layout: ONE import kernel for all of them, in front of everything else on the job's stream
+    rc = import_enqueue(e, s);
+    if (rc) return rc;
+    for (uint32_t i = 0; i < n; ++i)
+        if (imp_item[i] >= 0) sds[i].left = import_data(e, imp_item[i]);
     HIP_TRY(e, hipMemcpyAsync(e->d_batch, sds.data(), (size_t)n * sizeof(StreamDesc), hipMemcpyHostToDevice, s), "H2D batch table");
     HIP_TRY(e, hipMemcpyAsync(e->d_batch + tab_bytes, item_stream.data(), map_bytes, hipMemcpyHostToDevice, s), "H2D batch map");
     HIP_TRY(e, hipStreamSynchronize(s), "synchronize");  // (item_stream is a local; the copies are tiny)
@@ -996,11 +1006,15 @@ int encode_batch(lacx_encoder* e, const lacx_batch_item* items, uint32_t n, hipS
     rc = run();
     if (rc != LACX_OK) {
         (void)hipDeviceSynchronize();
+        e->imp.pending = false;
         return rc;
     }
     e->timing.d2h_ms = ms_since(t0);
+    e->imp.pending = false;  // (looked at here, stream by stream)
     for (uint32_t i = 0; i < n; ++i) {  // sample-range errors, stream by stream, the reference's wording per stream
         const StreamDesc& sd = sds[i];
+        if (imp_item[i] >= 0)
+            if (const int ic = import_check_item(e, (size_t)imp_item[i], true)) return ic;
         for (int pass = 0; pass < 2; ++pass) {
             for (uint32_t b = 0; b < sd.prm.num_blocks; ++b) {
                 const BlockPlan& bp = e->h_bplans[sd.first_block + b];

@@ -420,7 +420,7 @@ __global__ __launch_bounds__(64) void k_verify_fill(uint32_t nitems, const Decod
     const DecodeItem& it = items[j];
     const VerifySource& s = ver[j];
     verify_fill_item(it.blocks, it.channels, frame_off + it.block0, it.frame0, global_ptr(it.left), global_ptr(it.right),
-                     ms_flag + it.block0, global_ptr(s.data0), global_ptr(s.data1), s.layout, res[j]);
+                     ms_flag + it.block0, global_ptr(s.data0), global_ptr(s.data1), s.layout, res[j], it.bit_depth);
 }
 
 hipError_t launch_decode(const DecodeArgs& a, hipStream_t stream) {

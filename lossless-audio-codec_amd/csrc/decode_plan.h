@@ -158,14 +158,20 @@ inline const char* check_window(const BatchIn& x, const lacx_stream_info& f) {  
 inline const char* check_source(const BatchIn& x, const lacx_stream_info& f) {  // the verify form's source against the stream
     const lacx_pcm& p = x.pcm;
     const uintptr_t a0 = (uintptr_t)p.data0, a1 = (uintptr_t)p.data1;
-    const bool planar = p.layout == LACX_PCM_PLANAR_I32;
-    if (p.layout > LACX_PCM_INTERLEAVED_I24) return "unknown source layout";
+    const bool tensor = p.layout == LACX_PCM_PLANAR_I16 || p.layout == LACX_PCM_PLANAR_F32 || p.layout == LACX_PCM_INTERLEAVED_F32;
+    const bool planar = p.layout == LACX_PCM_PLANAR_I32 || p.layout == LACX_PCM_PLANAR_I16 || p.layout == LACX_PCM_PLANAR_F32;
+    if (p.layout > LACX_PCM_INTERLEAVED_I24 && !tensor) return "unknown source layout";
     if (p.channels != f.channels) return "source channel count does not match the stream";
     if ((!p.data0 && !x.host_src) || (planar && p.channels == 2 && !p.data1)) return "source arrays missing";
     if (x.frames != f.frames) return "source frame count does not match the stream";
-    if ((p.layout == LACX_PCM_INTERLEAVED_I16 && f.bit_depth != 16) || (p.layout == LACX_PCM_INTERLEAVED_I24 && f.bit_depth != 24))
+    if (((p.layout == LACX_PCM_INTERLEAVED_I16 || p.layout == LACX_PCM_PLANAR_I16) && f.bit_depth != 16) ||
+        (p.layout == LACX_PCM_INTERLEAVED_I24 && f.bit_depth != 24))
         return "source layout does not match the stream's bit depth";
-    if ((p.layout != LACX_PCM_INTERLEAVED_I24 && (a0 & 3u)) || (planar && (a1 & 3u))) return "source arrays are not 4-byte aligned";
+    if (p.layout == LACX_PCM_PLANAR_I16) {
+        if ((a0 & 1u) || (a1 & 1u)) return "source arrays are not 2-byte aligned";
+    } else if ((p.layout != LACX_PCM_INTERLEAVED_I24 && (a0 & 3u)) || (planar && (a1 & 3u))) {
+        return "source arrays are not 4-byte aligned";
+    }
     return nullptr;
 }
 inline const char* check_arrays(const BatchIn& x, const lacx_stream_info& f) {  // lacx_decoder_decode's checks of the output arrays

@@ -213,6 +213,24 @@ struct lacx_encoder {
     std::vector<StreamDesc> batch_streams;
     uint8_t* d_batch = nullptr;
     size_t d_batch_cap = 0;
+    // The import pass (api_import.cpp): sources in a tensor layout are rewritten into d_import in front of the front kernels.
+    // imp: the call's items (dst_off: where each lies in d_import, owner: its stream number in the call); d_import_tab: the
+    // validation words, then -- several items -- the item table and its unit prefix sums; h_import_bad: pinned copy of the
+    // words, looked at once the call's kernels are done (imp.pending)
+    struct {
+        std::vector<ImportItem> items;
+        std::vector<unsigned long long> unit_off;
+        std::vector<uint64_t> dst_off;
+        std::vector<uint32_t> owner;
+        uint64_t bytes = 0;
+        bool pending = false;
+    } imp;
+    uint8_t* d_import = nullptr;
+    uint64_t d_import_cap = 0;
+    uint8_t* d_import_tab = nullptr;
+    size_t d_import_tab_cap = 0;
+    ImportBad* h_import_bad = nullptr;
+    uint32_t h_import_cap = 0;
     int32_t* d_wide = nullptr;  // lacx_block_encode outside the 25-bit domain: the eleven candidate residuals (wide.hip)
     // Copy-engine drain of the payload (one-stream encodes): the packer packs into d_payload (HBM) and reports complete
     // ranges in h_range (pinned); encode_device_end lets a copy engine fetch them while the analysis still runs.
@@ -290,6 +308,20 @@ int fill_table(lacx_encoder* e, uint8_t* buf, uint32_t nb, const std::vector<uin
 // device; the results are views into e's buffers (valid until its next call)
 int encode_host_shard_view(lacx_encoder* e, const HostSrc& hs, int layout, int channels, uint64_t frames, const uint8_t** payload,
                            uint64_t* payload_size, const uint32_t** table, uint32_t* nblocks);
+// api_import.cpp: sources in the tensor layouts (LACX_PCM_PLANAR_I16, _PLANAR_F32, _INTERLEAVED_F32).  A call that takes
+// them checks each on the host (import_source_error: the message, or null), adds it (import_add: the layout the kernels
+// will read it in, and its item number or -1 where the source is used in place), enqueues one import kernel for all of
+// them in front of its front kernels (import_enqueue; import_data is valid from then on), and asks for the validation's
+// outcome once its kernels are done (import_check: LACX_OK, or LACX_E_INVALID with the lowest stream's message).
+bool is_import_layout(uint32_t layout);
+const char* import_source_error(const lacx_pcm& p, int bit_depth, bool batch);
+void import_reset(lacx_encoder* e);
+int import_add(lacx_encoder* e, const lacx_pcm& p, uint64_t frames, int bit_depth, uint32_t owner, int* layout);
+int import_enqueue(lacx_encoder* e, hipStream_t s);
+const int32_t* import_data(const lacx_encoder* e, int item);
+int import_check(lacx_encoder* e, bool batch);
+int import_check_item(lacx_encoder* e, size_t item, bool batch);  // one item's outcome (the call's kernels are done)
+void import_free(lacx_encoder* e);
 // api_fanout.cpp
 bool is_fanout(const lacx_encoder* e);
 void destroy_fanout(lacx_encoder* e);

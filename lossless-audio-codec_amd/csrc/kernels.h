@@ -1,9 +1,10 @@
 // kernels.h -- host-visible interface of the kernel translation units (k_front.hip, k_analyze.hip, k_emit.hip,
-// decode.hip, wide.hip).
+// decode.hip, wide.hip, k_import.hip).
 #pragma once
 #include <cstdlib>
 #include <hip/hip_runtime_api.h>
 
+#include "import_core.h"
 #include "lacx_types.h"
 
 namespace lacx {
@@ -185,6 +186,10 @@ hipError_t launch_decode(const DecodeArgs& args, hipStream_t stream);
 // candidate residuals ([11][kMaxBlock] int32), d_plan receives the plan.
 hipError_t launch_wide_block(const int32_t* d_x, uint32_t n, int zero_run, int partitioning, int32_t* d_res,
                              ChannelPlan* d_plan, hipStream_t stream);
+
+// The import pass (k_import.hip, import_core.h): every source of the job in one launch.  bad: [nitems] device words, all
+// ones on entry (ImportBad).
+hipError_t launch_import(const ImportJob& job, ImportBad* bad, hipStream_t stream);
 
 size_t analyze_smem_bytes_full();
 // Diagnostic builds (-DLACX_STAMPS) only: per-phase shader-cycle sums over all waves; returns 0 otherwise.

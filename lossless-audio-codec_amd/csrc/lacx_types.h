@@ -98,7 +98,8 @@ struct BatchRef {
 struct VerifySource {
     const void* data0;  // planar: left; interleaved layouts: the WAV data chunk
     const void* data1;  // planar: right (null for mono)
-    uint32_t layout;    // PCM_PLANAR_I32 / PCM_INTERLEAVED_I16 / PCM_INTERLEAVED_I24 (analyze_core.h)
+    uint32_t layout;    // PCM_PLANAR_I32 / PCM_INTERLEAVED_I16 / PCM_INTERLEAVED_I24 (analyze_core.h), or a tensor layout:
+                        // PCM_PLANAR_I16 / PCM_PLANAR_F32 / PCM_INTERLEAVED_F32 (import_core.h)
     uint32_t pad;
 };
 struct VerifyWords {

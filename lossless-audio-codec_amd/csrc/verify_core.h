@@ -9,6 +9,7 @@
 #include <cstdint>
 
 #include "decode_core.h"
+#include "import_core.h"
 
 namespace lacx {
 
@@ -36,15 +37,30 @@ LACX_HDF int32_t get24(const uint32_t* w, uint32_t k) {
     return sext24((uint32_t)(two >> (8u * (b & 3u))));
 }
 
-// One sample of the source, read element by element: channel c of frame f.  The partial last unit of an item and the
-// report of the first mismatch come through here; it touches the bytes of that sample only.
-LACX_HDF int32_t verify_src_sample(const void* __restrict__ src0, const void* __restrict__ src1, uint32_t layout, int channels,
-                                   unsigned long long f, uint32_t c) {
-    if (layout == (uint32_t)PCM_PLANAR_I32) return static_cast<const int32_t*>(c ? src1 : src0)[f];
+// One sample of the source, read element by element: channel c of frame f, as it lies there -- an integer sample, or the
+// bits of a float32.  The partial last unit of an item and the report of the first mismatch come through here; it touches
+// the bytes of that sample only.
+LACX_HDF int32_t verify_src_raw(const void* __restrict__ src0, const void* __restrict__ src1, uint32_t layout, int channels,
+                                unsigned long long f, uint32_t c) {
+    if (layout == (uint32_t)PCM_PLANAR_I32 || layout == (uint32_t)PCM_PLANAR_F32) return static_cast<const int32_t*>(c ? src1 : src0)[f];
+    if (layout == (uint32_t)PCM_PLANAR_I16) return static_cast<const int16_t*>(c ? src1 : src0)[f];
     const unsigned long long k = f * (unsigned long long)channels + c;
+    if (layout == (uint32_t)PCM_INTERLEAVED_F32) return static_cast<const int32_t*>(src0)[k];
     if (layout == (uint32_t)PCM_INTERLEAVED_I16) return static_cast<const int16_t*>(src0)[k];
     const uint8_t* p = static_cast<const uint8_t*>(src0) + 3ull * k;
     return sext24((uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16));
+}
+LACX_HDF bool verify_is_f32(uint32_t layout) { return layout == (uint32_t)PCM_PLANAR_F32 || layout == (uint32_t)PCM_INTERLEAVED_F32; }
+// The same as a sample value.  A float32 that is no sample of the depth (f32_to_pcm, import_core.h) gives the product
+// rounded to nearest and saturated, INT32_MIN for a NaN, and *invalid: it differs from whatever was decoded.
+LACX_HDF int32_t verify_src_sample(const void* __restrict__ src0, const void* __restrict__ src1, uint32_t layout, int channels,
+                                   unsigned long long f, uint32_t c, int bit_depth = 0, bool* invalid = nullptr) {
+    int32_t v = verify_src_raw(src0, src1, layout, channels, f, c);
+    if (verify_is_f32(layout)) {
+        const bool bad = f32_to_pcm((uint32_t)v, bit_depth, v) != 0;
+        if (invalid) *invalid = bad;
+    }
+    return v;
 }
 
 // One thread's work: frames f0 .. f0 + 3 of an item (f0 a multiple of 4).  left / right, frame_off, ms_flag and status are
@@ -56,6 +72,9 @@ LACX_HDF int32_t verify_src_sample(const void* __restrict__ src0, const void* __
 //   interleaved int16 8 (mono) or 16 (stereo) bytes from a 4-byte aligned base, as dwords
 //   interleaved int24 12 or 24 bytes: dwords where the base is 4-byte aligned (the unit's offset is a multiple of 12),
 //                     bytes otherwise; sign-extended from bit 23
+//   planar int16      8 bytes per channel where the row's base is 8-byte aligned, else int16 loads (2-byte aligned bases)
+//   planar float32    as planar int32, then every float through f32_to_pcm at the item's depth
+//   interleaved float32  16 (mono) or 32 (stereo) bytes where the base is 16-byte aligned, else dword loads; likewise
 // and the partial last unit element by element, so that no byte outside [0, frames * block_align) of an interleaved
 // source and no element outside [0, frames) of a planar array is read.  The full int32 values are compared: a planar
 // source sample that equals the decoded one only modulo 2^24 differs.  Only frames of blocks with status 0 count.
@@ -72,7 +91,7 @@ LACX_HDF uint32_t verify_unit(unsigned long long f0, uint32_t num_blocks, int ch
     if (nf == 4u) {
         __builtin_memcpy(l, __builtin_assume_aligned(left + f0, 16), 16);  // f0 is a multiple of 4: 16-byte aligned
         if (stereo) __builtin_memcpy(r, __builtin_assume_aligned(right + f0, 16), 16);
-        if (layout == (uint32_t)PCM_PLANAR_I32) {
+        if (layout == (uint32_t)PCM_PLANAR_I32 || layout == (uint32_t)PCM_PLANAR_F32) {
             const int32_t* a = static_cast<const int32_t*>(src0) + f0;
             if (((uintptr_t)src0 & 15u) == 0) {
                 __builtin_memcpy(sl, __builtin_assume_aligned(a, 16), 16);
@@ -86,6 +105,24 @@ LACX_HDF uint32_t verify_unit(unsigned long long f0, uint32_t num_blocks, int ch
                 } else {
                     sr[0] = b[0], sr[1] = b[1], sr[2] = b[2], sr[3] = b[3];
                 }
+            }
+        } else if (layout == (uint32_t)PCM_PLANAR_I16) {
+            import_detail::load_i16x4(static_cast<const int16_t*>(src0) + f0, ((uintptr_t)src0 & 7u) == 0, 4u, sl);
+            if (stereo) import_detail::load_i16x4(static_cast<const int16_t*>(src1) + f0, ((uintptr_t)src1 & 7u) == 0, 4u, sr);
+        } else if (layout == (uint32_t)PCM_INTERLEAVED_F32) {
+            const bool wide = ((uintptr_t)src0 & 15u) == 0;
+            if (stereo) {
+                uint32_t w[8];
+                const uint32_t* p = static_cast<const uint32_t*>(src0) + 2ull * f0;
+                import_detail::load_u32x4(p, wide, 4u, w);
+                import_detail::load_u32x4(p + 4, wide, 4u, w + 4);
+#pragma unroll
+                for (uint32_t i = 0; i < 4u; ++i) sl[i] = (int32_t)w[2u * i], sr[i] = (int32_t)w[2u * i + 1u];
+            } else {
+                uint32_t w[4];
+                import_detail::load_u32x4(static_cast<const uint32_t*>(src0) + f0, wide, 4u, w);
+#pragma unroll
+                for (uint32_t i = 0; i < 4u; ++i) sl[i] = (int32_t)w[i];
             }
         } else if (layout == (uint32_t)PCM_INTERLEAVED_I16) {
             uint32_t w[4];
@@ -120,12 +157,20 @@ LACX_HDF uint32_t verify_unit(unsigned long long f0, uint32_t num_blocks, int ch
         for (uint32_t i = 0; i < 3u; ++i) {
             if (i < nf) {
                 l[i] = left[f0 + i];
-                sl[i] = verify_src_sample(src0, src1, layout, channels, f0 + i, 0u);
+                sl[i] = verify_src_raw(src0, src1, layout, channels, f0 + i, 0u);
                 if (stereo) {
                     r[i] = right[f0 + i];
-                    sr[i] = verify_src_sample(src0, src1, layout, channels, f0 + i, 1u);
+                    sr[i] = verify_src_raw(src0, src1, layout, channels, f0 + i, 1u);
                 }
             }
+        }
+    }
+    uint32_t inval = 0;  // float sources: bit 2 * i + c for a value that is no sample of the depth
+    if (verify_is_f32(layout)) {
+#pragma unroll
+        for (uint32_t i = 0; i < 4u; ++i) {
+            if (f32_to_pcm((uint32_t)sl[i], bit_depth, sl[i]) != 0) inval |= 1u << (2u * i);
+            if (stereo && f32_to_pcm((uint32_t)sr[i], bit_depth, sr[i]) != 0) inval |= 2u << (2u * i);
         }
     }
     const uint32_t b0 = verify_block_of_frame(frame_off, num_blocks, frame_base, f0);
@@ -149,8 +194,8 @@ LACX_HDF uint32_t verify_unit(unsigned long long f0, uint32_t num_blocks, int ch
         bad0 = bad0 || (bad && !second);
         bad1 = bad1 || (bad && second);
         const bool compared = i < nf && (second ? st1 : st0) == 0u;  // only blocks that decoded
-        if (compared && (int32_t)a != sl[i]) differ |= 1u << (2u * i);
-        if (compared && stereo && (int32_t)b != sr[i]) differ |= 2u << (2u * i);
+        if (compared && ((int32_t)a != sl[i] || ((inval >> (2u * i)) & 1u))) differ |= 1u << (2u * i);
+        if (compared && stereo && ((int32_t)b != sr[i] || ((inval >> (2u * i)) & 2u))) differ |= 2u << (2u * i);
     }
     // blocks that did not decode are not checked (their status already fails the item)
     if (bad0 && st0 == 0u) status_max(&status[b0], 7u);
@@ -159,11 +204,13 @@ LACX_HDF uint32_t verify_unit(unsigned long long f0, uint32_t num_blocks, int ch
 }
 
 // An item whose comparison found a difference: the block and the two values at its first-mismatch key (one thread per
-// item after k_verify; the decoded value is made from the scratch again, the source read element by element).
+// item after k_verify; the decoded value is made from the scratch again, the source read element by element; bit_depth:
+// the item's, which a float32 source is scaled by).
 LACX_HDF void verify_fill_item(uint32_t num_blocks, int channels, const unsigned long long* __restrict__ frame_off,
                                unsigned long long frame_base, const int32_t* __restrict__ left,
                                const int32_t* __restrict__ right, const uint8_t* __restrict__ ms_flag,
-                               const void* __restrict__ src0, const void* __restrict__ src1, uint32_t layout, VerifyWords& w) {
+                               const void* __restrict__ src0, const void* __restrict__ src1, uint32_t layout, VerifyWords& w,
+                               int bit_depth = 0) {
     if (w.count == 0) return;
     const unsigned long long f = w.key >> 1;
     const uint32_t c = (uint32_t)(w.key & 1u);
@@ -175,7 +222,7 @@ LACX_HDF void verify_fill_item(uint32_t num_blocks, int channels, const unsigned
         b = a - s;
     }
     w.decoded = (int32_t)(c ? b : a);
-    w.source = verify_src_sample(src0, src1, layout, channels, f, c);
+    w.source = verify_src_sample(src0, src1, layout, channels, f, c, bit_depth);
     w.block = blk;
 }
 

@@ -444,10 +444,11 @@ class Encoder:
         table = np.ctypeslib.as_array(tab, shape=(nb.value, 2))
         return PayloadView(pay, psize.value), table
 
-    def encode_shard_pcm_device_begin(self, data_ptr: int, layout: int, channels: int, frames: int, stream: int = 0,
-                                      data1_ptr: int | None = None):
-        """Enqueues a shard encode of device-resident PCM and returns at once (see encode_shard_end)."""
-        pcm = Pcm(data_ptr, data1_ptr, layout, channels)
+    def encode_shard_pcm_device_begin(self, data_ptr, layout: int | None = None, channels: int | None = None,
+                                      frames: int | None = None, stream: int = 0, data1_ptr: int | None = None):
+        """Enqueues a shard encode of device-resident PCM and returns at once (see encode_shard_end).  data_ptr: a raw
+        device address with its layout, channel count and frame count, or a device tensor (see pcm_of) by itself."""
+        pcm, frames = _pcm_arg(data_ptr, layout, channels, frames, data1_ptr, self._cfg.bit_depth)
         h = self._handle()
         rc = lib().lacx_encode_shard_pcm_device_begin(h, C.byref(pcm), C.c_uint64(frames), C.c_void_p(stream))
         if rc != OK:
@@ -495,9 +496,11 @@ class Encoder:
             _raise(h, rc)
         return PayloadView(out, size.value)
 
-    def encode_shard_pcm_device_view(self, data_ptr: int, layout: int, channels: int, frames: int, stream: int = 0):
-        """Zero-copy shard encode of device-resident PCM in its source layout (interleaved int16 / int24)."""
-        pcm = Pcm(data_ptr, None, layout, channels)
+    def encode_shard_pcm_device_view(self, data_ptr, layout: int | None = None, channels: int | None = None,
+                                     frames: int | None = None, stream: int = 0, data1_ptr: int | None = None):
+        """Zero-copy shard encode of device-resident PCM in its source layout (any PCM_* layout).  data_ptr: a raw device
+        address with its layout, channel count and frame count, or a device tensor (see pcm_of) by itself."""
+        pcm, frames = _pcm_arg(data_ptr, layout, channels, frames, data1_ptr, self._cfg.bit_depth)
         pay = C.POINTER(C.c_uint8)()
         psize = C.c_uint64()
         tab = C.POINTER(C.c_uint32)()
@@ -509,6 +512,15 @@ class Encoder:
             _raise(h, rc)
         table = np.ctypeslib.as_array(tab, shape=(nb.value, 2))
         return PayloadView(pay, psize.value), table
+
+    def encode_tensor(self, t, stream: int = 0) -> bytes:
+        """The complete .lac of a device tensor ([channels, frames], [frames, channels] or [frames]; int16, int32 or
+        float32, see pcm_of) at the encoder's rate, depth and stereo mode: a shard encode of the tensor where it lies,
+        then the container around it.  A float that is no exact sample of the depth raises ValueError."""
+        pcm, _ = pcm_of(t, self._cfg.bit_depth)
+        payload, table = self.encode_shard_pcm_device_view(t, stream=stream)
+        return assemble(self._cfg.sample_rate, self._cfg.bit_depth, self._cfg.stereo_mode, int(pcm.channels),
+                        [(payload.tobytes(), table)])
 
     def encode_shard_device(self, d_left_ptr: int, d_right_ptr: int | None, h_left, h_right, frames: int,
                             stream: int = 0, copy: bool = True):
@@ -565,6 +577,69 @@ def fanout_range(nblocks: int, nlanes: int, lane: int):
 
 
 PCM_PLANAR_I32, PCM_INTERLEAVED_I16, PCM_INTERLEAVED_I24 = 0, 1, 2
+PCM_PLANAR_I16, PCM_PLANAR_F32, PCM_INTERLEAVED_F32 = 16, 17, 18  # the tensor layouts
+
+
+def pcm_of(x, bit_depth: int):
+    """(Pcm, frames) of an array where it lies: a numpy array (the host-side twins) or anything with data_ptr(), dtype,
+    shape and stride() -- a torch tensor, which this module does not import.
+      [channels, frames] with contiguous rows   planar: data1 is the second row's address (a slice of a wider tensor is fine)
+      [frames, channels] contiguous             interleaved;  [frames]: mono
+      int32 -> PCM_PLANAR_I32, int16 -> PCM_PLANAR_I16 (interleaved: PCM_INTERLEAVED_I16), float32 -> PCM_PLANAR_F32 /
+      PCM_INTERLEAVED_F32 (sample * 2^-(bit_depth - 1), what decode_window_batch_device writes)
+    A two-dimensional array whose first extent is 1 or 2 is taken as [channels, frames].  Everything else raises
+    ValueError with the reason: another dtype, more than two channels, a non-unit inner stride, rows that overlap,
+    interleaved int32, int16 at a depth other than 16, an empty array."""
+    if isinstance(x, np.ndarray):
+        ptr, dtype, shape = int(x.ctypes.data), x.dtype.name, tuple(x.shape)
+        strides = tuple(s // x.itemsize if s % x.itemsize == 0 else None for s in x.strides)
+    elif all(hasattr(x, a) for a in ("data_ptr", "dtype", "shape", "stride")):
+        ptr, dtype, shape = int(x.data_ptr()), str(x.dtype).replace("torch.", ""), tuple(int(n) for n in x.shape)
+        strides = tuple(int(n) for n in x.stride())
+    else:
+        raise ValueError(f"pcm_of: {type(x).__name__} is neither a numpy array nor a tensor with data_ptr(), dtype, shape and stride()")
+    size = {"int16": 2, "int32": 4, "float32": 4}.get(dtype)
+    if size is None:
+        raise ValueError(f"pcm_of: dtype {dtype} is not int16, int32 or float32")
+    if dtype == "int16" and bit_depth != 16:
+        raise ValueError(f"pcm_of: int16 samples need bit depth 16, not {bit_depth}")
+    if len(shape) not in (1, 2) or 0 in shape:
+        raise ValueError(f"pcm_of: shape {shape} is not [channels, frames], [frames, channels] or [frames], or is empty")
+    if None in strides or any(s < 0 for s in strides):
+        raise ValueError(f"pcm_of: strides {strides} are not whole, non-negative element counts")
+    planar = {"int16": PCM_PLANAR_I16, "int32": PCM_PLANAR_I32, "float32": PCM_PLANAR_F32}[dtype]
+    if len(shape) == 1:
+        if shape[0] > 1 and strides[0] != 1:
+            raise ValueError(f"pcm_of: inner stride {strides[0]} is not 1")
+        return Pcm(ptr, None, planar, 1), shape[0]
+    if shape[0] <= 2:  # [channels, frames]
+        ch, frames = shape
+        if frames > 1 and strides[1] != 1:
+            raise ValueError(f"pcm_of: inner stride {strides[1]} is not 1")
+        if ch == 2 and strides[0] < frames:
+            raise ValueError(f"pcm_of: row stride {strides[0]} is shorter than a row of {frames} frames")
+        return Pcm(ptr, ptr + strides[0] * size if ch == 2 else None, planar, ch), frames
+    frames, ch = shape  # [frames, channels]
+    if ch > 2:
+        raise ValueError(f"pcm_of: more than two channels (shape {shape})")
+    if strides != (ch, 1):
+        raise ValueError(f"pcm_of: [frames, channels] must be contiguous, strides are {strides}")
+    if ch == 1:
+        return Pcm(ptr, None, planar, 1), frames
+    if dtype == "int32":
+        raise ValueError("pcm_of: interleaved int32 is not a supported layout")
+    return Pcm(ptr, None, PCM_INTERLEAVED_I16 if dtype == "int16" else PCM_INTERLEAVED_F32, 2), frames
+
+
+def _pcm_arg(data, layout, channels, frames, data1_ptr, bit_depth):
+    """(Pcm, frames) of an entry point's PCM argument: a raw address with its description, or a tensor by itself."""
+    if isinstance(data, (int, np.integer)) or data is None:
+        if layout is None or channels is None or frames is None:
+            raise ValueError("a raw device address needs its layout, channel count and frame count")
+        return Pcm(data, data1_ptr, layout, channels), int(frames)
+    if not (layout is None and channels is None and frames is None and data1_ptr is None):
+        raise ValueError("a tensor describes itself: layout, channels, frames and data1_ptr must not be given")
+    return pcm_of(data, bit_depth)
 
 
 class PayloadView:
@@ -918,16 +993,21 @@ class Decoder:
         hipStream_t, 0 = the null stream); nothing but a few words per item comes back.  Returns each item's VerifyResult
         (all zero: identical).  An item that differs or does not decode raises BatchDecodeError once the others are
         done: errors[i] is its message ("[verify-error] block=N ..." or the decode's own), results[i] its VerifyResult
-        where it decoded and differed, None where it failed."""
+        where it decoded and differed, None where it failed.  A source may also be a device tensor by itself (pcm_of)."""
         if len(sources) != len(lacs):
             raise ValueError("one source per stream")
         bufs = [np.frombuffer(x, dtype=np.uint8) for x in lacs]
         n = len(bufs)
         items = (VerifyItem * max(1, n))()
-        for it, b, (d0, d1, layout, channels, frames) in zip(items, bufs, sources):
+        for it, b, src in zip(items, bufs, sources):
             it.lac = b.ctypes.data_as(C.POINTER(C.c_uint8))
             it.size = b.size
-            it.pcm = Pcm(d0, d1, layout, channels)
+            if isinstance(src, (tuple, list)):
+                d0, d1, layout, channels, frames = src
+                it.pcm = Pcm(d0, d1, layout, channels)
+            else:  # a tensor, described by itself at the stream's bit depth (see pcm_of)
+                info = _parse_in_place(b)  # (a stream that does not parse fails on its own account)
+                it.pcm, frames = pcm_of(src, info.bit_depth if info else 16)
             it.frames = frames
         res = (VerifyResult * max(1, n))()
         rcs_seen = []
@@ -1070,15 +1150,18 @@ class BatchEncoder:
         return self._enc.timing()
 
     def encode_device(self, streams, stream: int = 0):
-        """streams: [(data_ptr, layout, channels, frames[, data1_ptr]), ...] device-resident PCM; returns a list of
+        """streams: [(data_ptr, layout, channels, frames[, data1_ptr]) or a device tensor (pcm_of), ...] device-resident PCM; returns a list of
         (PayloadView, table uint32[nblocks, 2]) views into the encoder's pinned result buffer."""
         n = len(streams)
         if n != len(self.formats):
             raise ValueError("one stream per format")
         items = (BatchItem * n)()
         for it, st, (sr, bd, sm) in zip(items, streams, self.formats):
-            ptr, layout, ch, frames = st[:4]
-            it.pcm = Pcm(ptr, st[4] if len(st) > 4 else None, layout, ch)
+            if isinstance(st, (tuple, list)):
+                ptr, layout, ch, frames = st[:4]
+                it.pcm = Pcm(ptr, st[4] if len(st) > 4 else None, layout, ch)
+            else:  # a tensor, described by itself at the stream's bit depth (see pcm_of)
+                it.pcm, frames = pcm_of(st, bd)
             it.frames = frames
             it.sample_rate = sr
             it.bit_depth = bd
