@@ -1,5 +1,5 @@
 // api_core.cpp -- the encoder object behind the C ABI (include/lacx.h): device and stream set-up, the device workspace and
-// the pinned buffers, argument validation, pipeline chunking, timing and small helpers shared by the other host units.
+// the pinned buffers, argument validation, timing and small helpers shared by the other host units.
 // There is no CPU analysis path here: without a usable HIP device every analysing call fails.
 #include "encoder_impl.h"
 
@@ -11,20 +11,14 @@ Knobs read_knobs() {
         const char* v = std::getenv(name);
         return v != nullptr;
     };
-    auto on = [](const char* name) {  // set, non-empty and not "0"
-        const char* v = std::getenv(name);
-        return v && *v && *v != '0';
-    };
     auto num = [](const char* name) -> unsigned long long {
         const char* v = std::getenv(name);
         return v ? std::strtoull(v, nullptr, 0) : 0ull;
     };
     k.stream_priority = !set("LACX_NO_STREAM_PRIORITY");
     if (const char* v = std::getenv("LACX_FUSED_EMIT")) k.fused_emit = *v != '0';
-    k.emit_staged = on("LACX_EMIT_STAGED");
     k.direct_packer = set("LACX_DIRECT_PACKER");
     k.packer = !set("LACX_NO_PACKER");
-    k.chain = !set("LACX_NO_CHAIN");
     k.persistent = !set("LACX_NO_PERSISTENT");
     k.debug_drain = set("LACX_DEBUG_DRAIN");
     k.two_copy_streams = !set("LACX_ONE_COPY_STREAM");
@@ -40,7 +34,6 @@ Knobs read_knobs() {
     k.tune.fold_front = !set("LACX_NO_FRONT_FOLD");
     k.lazy_repair = !set("LACX_NO_LAZY_REPAIR");
     k.silent_template = !set("LACX_NO_SILENT_TEMPLATE");
-    k.front_stream_split = set("LACX_FRONT_STREAM");  // (measured: slower, see DESIGN 8 -- kept as an experiment switch)
     k.pinned_cap_bytes = num("LACX_PINNED_CAP_BYTES");
     k.debug_skip = (uint32_t)num("LACX_DEBUG_SKIP");
     k.pipe_chunks = (uint32_t)num("LACX_PIPE_CHUNKS");
@@ -263,32 +256,18 @@ int ensure_workspace(lacx_encoder* e, uint32_t nblocks) {
 int ensure_slots(lacx_encoder* e, uint32_t nblocks, int channels, int bit_depth) {
     const unsigned long long stride = (unsigned long long)kMaxBlock * ((bit_depth ? bit_depth : e->cfg.bit_depth) == 16 ? 3u : 5u);
     const unsigned long long need = stride * nblocks * (unsigned)channels + 64u;
-    if (need > e->slots_cap) {
-        if (e->slots) (void)hipFree(e->slots);
-        e->slots = nullptr;
-        e->slots_cap = 0;
-        HIP_TRY(e, hipMalloc((void**)&e->slots, need), "hipMalloc(emit slots)");
-        e->slots_cap = need;
-    }
-    e->ws.slots = e->slots;
+    if (const int rc = grow(e, e->slot_mem, need)) return rc;
+    e->ws.slots = e->slot_mem.as<uint8_t>();
     e->ws.slot_stride = stride;
     return LACX_OK;
 }
 
-int ensure_pcm(lacx_encoder* e, uint64_t frames, bool stereo) {
-    if (frames > e->d_cap || (stereo && !e->d_right)) {
-        if (e->d_left) (void)hipFree(e->d_left);
-        if (e->d_right) (void)hipFree(e->d_right);
-        e->d_left = e->d_right = nullptr;
-        e->d_cap = 0;
-        HIP_TRY(e, hipMalloc((void**)&e->d_left, frames * sizeof(int32_t)), "hipMalloc(left)");
-        HIP_TRY(e, hipMalloc((void**)&e->d_right, frames * sizeof(int32_t)), "hipMalloc(right)");
-        e->d_cap = frames;
-    }
-    return LACX_OK;
+int grow(lacx_encoder* e, Buf& b, uint64_t need) {
+    const DevErr d = buf_grow(b, need, 0);
+    return d ? hip_fail(e, d.e, d.what) : LACX_OK;
 }
 
-bool rate_ok(uint32_t sr) { return sr == 44100 || sr == 48000 || sr == 96000 || sr == 192000; }
+int ensure_pcm(lacx_encoder* e, uint64_t frames, bool) { return grow(e, e->pcm, frames); }  // (both channels, whatever the call's count)
 
 // Argument validation of LAC::Encoder::encode (ref lac/encoder.cpp:220-237), same order and wording.
 int validate_stream_args(lacx_encoder* e, const void* left, uint64_t frames) {
@@ -302,22 +281,8 @@ int validate_stream_args(lacx_encoder* e, const void* left, uint64_t frames) {
     return LACX_OK;
 }
 
-uint32_t blocks_for(uint64_t frames) { return (uint32_t)((frames + kMaxBlock - 1) / kMaxBlock); }
-
-AnalyzeParams make_params(const lacx_encoder* e, uint64_t frames, int channels, int stereo_mode, int bit_depth,
-                          int layout) {
-    AnalyzeParams prm{};
-    prm.layout = layout;
-    prm.frames = frames;
-    prm.num_blocks = blocks_for(frames);
-    prm.first_block = 0;
-    prm.channels = channels;
-    prm.stereo_mode = channels == 2 ? stereo_mode : 0;
-    prm.bit_depth = bit_depth;
-    prm.zero_run = e->cfg.zero_run_enabled ? 1 : 0;
-    prm.partitioning = e->cfg.partitioning_enabled ? 1 : 0;
-    prm.debug_skip = e->knobs.debug_skip;  // test hooks / ablations (only a -DLACX_TEST_HOOKS library looks at it)
-    return prm;
+AnalyzeParams make_params(const lacx_encoder* e, uint64_t frames, int channels, int stereo_mode, int bit_depth, int layout) {
+    return make_params(param_base(e), frames, channels, stereo_mode, bit_depth, layout);
 }
 
 // Launch set of one stream (or one pipeline chunk of it): the descriptor travels in the kernel arguments.
@@ -354,63 +319,6 @@ DeviceWorkspace ws_at(const DeviceWorkspace& ws, uint32_t first_block) {
     if (w.front_ctr) w.front_ctr += (size_t)first_block * 2;
     w.table += (size_t)first_block * 2;
     return w;
-}
-
-// Host emit wants many chunks (emit of chunk i overlaps the analysis of chunk i+1); with the emit on the
-// device the only host work is a copy, and two chunks (payload copy of one under the kernels of the other)
-// measured best.
-std::vector<Chunk> plan_chunks(const Knobs& kn, uint32_t nb, bool device_emit, bool fused, bool upload) {
-    uint32_t nchunks = nb / kMinChunkBlocks;
-    // device emit without the fused path: 3 chunks up to an hour of stereo 48 kHz per call, 4 and 6 beyond (measured on a
-    // 2 h shard).  With the fused emit + streaming packer nothing is left to overlap by chunking -- the payload leaves
-    // while the analysis runs, and ingest / probes keep every CU busy by themselves -- and one launch set measured best
-    // from 10 min to 2 h of audio (a chunked run only adds kernel boundaries).
-    // With the input still in host memory the chunks pipeline the upload (the uploader thread copies chunk c + 1 while
-    // chunk c's kernels are enqueued and run): four equal chunks measured best once the copies came from their own thread
-    // and the packer's stream had a priority level of its own (10 min stream, WAV image -> .lac: 3.40 ms; 1:2:3 3.57,
-    // 1:3:4 3.6, one chunk 4.65; round 3, copies issued by the calling thread: 1:3:4 3.75).
-    const uint32_t dev_chunks = fused ? (upload ? 4u : 1u) : (nb >= 12000u ? 6u : (nb >= 6000u ? 4u : 3u));
-    nchunks = std::max(1u, std::min(nchunks, device_emit ? dev_chunks : 8u));
-    bool forced = false;
-    if (kn.pipe_chunks >= 1 && kn.pipe_chunks <= (uint32_t)kMaxChunks) {  // tuning knob
-        nchunks = std::min<uint32_t>(kn.pipe_chunks, nb);
-        forced = true;
-    }
-    std::vector<Chunk> out;
-    const char* split_env = kn.pipe_split.empty() ? nullptr : kn.pipe_split.c_str();  // tuning knob: relative chunk sizes, e.g. "5,3,1"
-    // Device emit: three chunks on three streams of falling priority, the last one a little smaller -- its
-    // emit is the only one whose PCIe writes are not hidden under another chunk's analysis (measured best).
-    if (!split_env && !forced && device_emit && nchunks == 3u) split_env = (fused && upload) ? "1,2,3" : "5,5,4";
-    if (const char* env = split_env) {
-        std::vector<double> w;
-        double sum = 0;
-        for (const char* p = env; *p && w.size() < (size_t)kMaxChunks;) {
-            char* end = nullptr;
-            const double v = std::strtod(p, &end);
-            if (end == p) break;
-            if (v > 0) {
-                w.push_back(v);
-                sum += v;
-            }
-            p = (*end == ',') ? end + 1 : end;
-        }
-        if (!w.empty() && nb >= w.size()) {
-            uint32_t f = 0;
-            double acc = 0;
-            for (size_t i = 0; i < w.size(); ++i) {
-                acc += w[i];
-                uint32_t end = i + 1 == w.size() ? nb : (uint32_t)(nb * (acc / sum));
-                end = std::max(end, f + 1);
-                end = std::min(end, nb - (uint32_t)(w.size() - 1 - i));
-                out.push_back({f, end - f});
-                f = end;
-            }
-            return out;
-        }
-    }
-    const uint32_t per = (nb + nchunks - 1) / nchunks;
-    for (uint32_t f = 0; f < nb; f += per) out.push_back({f, std::min(per, nb - f)});
-    return out;
 }
 
 void add_chunk_timing(lacx_encoder* e, int c) {
@@ -489,10 +397,10 @@ int upload(lacx_encoder* e, const int32_t* left, const int32_t* right, uint64_t 
     const auto t0 = clk::now();
     int rc = ensure_pcm(e, frames, right != nullptr);
     if (rc) return rc;
-    HIP_TRY(e, hipMemcpyAsync(e->d_left, left, frames * sizeof(int32_t), hipMemcpyHostToDevice, e->stream[0]),
+    HIP_TRY(e, hipMemcpyAsync(e->d_left(), left, frames * sizeof(int32_t), hipMemcpyHostToDevice, e->stream[0]),
             "H2D left");
     if (right)
-        HIP_TRY(e, hipMemcpyAsync(e->d_right, right, frames * sizeof(int32_t), hipMemcpyHostToDevice, e->stream[0]),
+        HIP_TRY(e, hipMemcpyAsync(e->d_right(), right, frames * sizeof(int32_t), hipMemcpyHostToDevice, e->stream[0]),
                 "H2D right");
     HIP_TRY(e, hipStreamSynchronize(e->stream[0]), "H2D synchronize");
     e->timing.h2d_ms = ms_since(t0);
@@ -557,8 +465,7 @@ void lacx_encoder_destroy(lacx_encoder* e) {
     if (e->device_ready) {
         (void)hipSetDevice(e->device);
         free_workspace(e);
-        if (e->d_left) (void)hipFree(e->d_left);
-        if (e->d_right) (void)hipFree(e->d_right);
+        for (Buf* b : e->all_bufs()) buf_free(*b);
         if (e->h_plans) (void)hipHostFree(e->h_plans);
         if (e->h_bplans) (void)hipHostFree(e->h_bplans);
         for (auto& row : e->ev)
@@ -573,24 +480,13 @@ void lacx_encoder_destroy(lacx_encoder* e) {
             if (ev) (void)hipEventDestroy(ev);
         if (e->pack_done) (void)hipEventDestroy(e->pack_done);
         if (e->pack_stream) (void)hipStreamDestroy(e->pack_stream);
-        if (e->d_payload) (void)hipFree(e->d_payload);
-        if (e->slots) (void)hipFree(e->slots);
-        if (e->d_raw) (void)hipFree(e->d_raw);
-        if (e->d_batch) (void)hipFree(e->d_batch);
         if (e->d_wide) (void)hipFree(e->d_wide);
-        import_free(e);
-        if (e->h_payload_base) (void)hipHostFree(e->h_payload_base);
-        if (e->h_table) (void)hipHostFree(e->h_table);
         if (e->h_totals) (void)hipHostFree(e->h_totals);
         if (e->h_err) (void)hipHostFree(e->h_err);
-        if (e->h_emitted) (void)hipHostFree(e->h_emitted);
-        if (e->h_sizes) (void)hipHostFree(e->h_sizes);
         if (e->h_tspan) (void)hipHostFree(e->h_tspan);
         if (e->up_stream) (void)hipStreamDestroy(e->up_stream);
-        if (e->front_stream) (void)hipStreamDestroy(e->front_stream);
         for (auto& ev : e->up_ev)
             if (ev) (void)hipEventDestroy(ev);
-        if (e->h_range) (void)hipHostFree(e->h_range);
         if (e->copy_stream) (void)hipStreamDestroy(e->copy_stream);
         if (e->copy_stream2) (void)hipStreamDestroy(e->copy_stream2);
         for (auto& s : e->stream)

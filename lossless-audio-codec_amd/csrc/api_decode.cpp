@@ -1,5 +1,6 @@
 // api_decode.cpp -- the decode entry points of the C ABI: container parsing and the device decoder's host side.
 #include "decode_plan.h"
+#include "device_buf.h"
 #include "encoder_impl.h"
 
 // (the entry points are declared extern "C" in lacx.h)
@@ -19,49 +20,6 @@ int lacx_stream_parse(const uint8_t* lac, uint64_t size, lacx_stream_info* out) 
     const int c = parse_stream(lac, size, out, &why);
     return c == LACX_OK ? c : decode_fail(c, why);
 }
-
-namespace {
-// A failing HIP call, by name.
-struct DevErr {
-    const char* what = "";
-    hipError_t e = hipSuccess;
-    explicit operator bool() const { return e != hipSuccess; }
-};
-DevErr chk(hipError_t e, const char* what) { return DevErr{what, e}; }
-
-// Up to three allocations that share one grow-only capacity, counted in elements: device or pinned, each with its element
-// size and the name a failing allocation is reported under.
-struct Buf {
-    struct Part {
-        bool pinned;
-        uint32_t elem;  // 0: unused
-        const char* what;
-        void* p = nullptr;
-    } part[3];
-    uint64_t cap = 0;
-};
-void buf_free(Buf& b) {
-    for (Buf::Part& x : b.part) {
-        if (x.p) (void)(x.pinned ? hipHostFree(x.p) : hipFree(x.p));
-        x.p = nullptr;
-    }
-    b.cap = 0;
-}
-// need elements, or need + slack where it has to grow (or a part is missing)
-DevErr buf_grow(Buf& b, uint64_t need, uint64_t slack) {
-    bool have = need <= b.cap;
-    for (const Buf::Part& x : b.part) have = have && (x.p || !x.elem);
-    if (have) return DevErr{};
-    buf_free(b);
-    for (Buf::Part& x : b.part) {
-        if (!x.elem) continue;
-        const size_t bytes = (size_t)(need + slack) * x.elem;
-        if (DevErr e = chk(x.pinned ? hipHostMalloc(&x.p, bytes, 0) : hipMalloc(&x.p, bytes), x.what)) return e;
-    }
-    b.cap = need + slack;
-    return DevErr{};
-}
-}  // namespace
 
 // The decoder object: device buffers, a stream and two events that live from call to call (grow-only), so that a decode
 // costs its copies and its kernel, not six allocations (ref LAC::Decoder is an object too, src/codec/lac/decoder.hpp:10-24).

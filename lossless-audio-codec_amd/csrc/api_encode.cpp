@@ -5,16 +5,7 @@
 namespace lacx_host {
 
 // Device buffer for a WAV data chunk of `bytes` bytes (+ the look-ahead the staging loads may touch).
-static int ensure_raw(lacx_encoder* e, uint64_t bytes) {
-    if (bytes + 16u > e->d_raw_cap) {
-        if (e->d_raw) (void)hipFree(e->d_raw);
-        e->d_raw = nullptr;
-        e->d_raw_cap = 0;
-        HIP_TRY(e, hipMalloc((void**)&e->d_raw, bytes + 16u), "hipMalloc(wav data)");
-        e->d_raw_cap = bytes + 16u;
-    }
-    return LACX_OK;
-}
+static int ensure_raw(lacx_encoder* e, uint64_t bytes) { return grow(e, e->raw, bytes + 16u); }
 
 // One lane's work in a fan-out, and what a plain encoder does with host input: the frames of hs on e's device, upload
 // pipelined with the kernels; results are views into e's buffers.
@@ -27,31 +18,26 @@ int encode_host_shard_view(lacx_encoder* e, const HostSrc& hs, int layout, int c
     if (layout == 0 && (e->cfg.flags & LACX_FLAG_HOST_EMIT)) {  // north_star layout: plans back, bit emit on host threads
         rc = upload(e, left, right, frames);
         if (rc) return rc;
-        return lacx_encode_shard_device_view(e, e->d_left, right ? e->d_right : nullptr, left, right, frames, nullptr, payload,
+        return lacx_encode_shard_device_view(e, e->d_left(), right ? e->d_right() : nullptr, left, right, frames, nullptr, payload,
                                              payload_size, table, nblocks);
     }
     const int32_t *dl, *dr = nullptr;
     if (layout == 0) {
         rc = ensure_pcm(e, frames, right != nullptr);
         if (rc) return rc;
-        dl = e->d_left;
-        dr = right ? e->d_right : nullptr;
+        dl = e->d_left();
+        dr = right ? e->d_right() : nullptr;
     } else {
         rc = ensure_raw(e, frames * hs.frame_bytes);
         if (rc) return rc;
-        dl = reinterpret_cast<const int32_t*>(e->d_raw);
+        dl = reinterpret_cast<const int32_t*>(e->d_raw());
     }
     uint64_t pay = 0;
     rc = encode_pipelined_device(e, dl, dr, frames, nullptr, &pay, layout, channels, &hs);
-    if (rc == -1) {
-        if (layout != 0) return fail(e, LACX_E_RUNTIME, "payload exceeds the pinned result reservation");
-        // (only with LACX_EMIT_STAGED) the host-emit pipeline; the PCM is on the device already
-        return lacx_encode_shard_device_view(e, dl, dr, left, right, frames, nullptr, payload, payload_size, table, nblocks);
-    }
     if (rc) return rc;
     *payload = e->h_payload;
     *payload_size = pay;
-    *table = e->h_table;
+    *table = e->h_table();
     *nblocks = blocks_for(frames);
     return LACX_OK;
 }
@@ -82,7 +68,7 @@ int lacx_analyze(lacx_encoder* e, const int32_t* left, const int32_t* right, uin
     if (rc) return rc;
     rc = upload(e, left, right, frames);
     if (rc) return rc;
-    return lacx_analyze_device(e, e->d_left, right ? e->d_right : nullptr, frames, nullptr, bplans, plans);
+    return lacx_analyze_device(e, e->d_left(), right ? e->d_right() : nullptr, frames, nullptr, bplans, plans);
 }
 
 int lacx_emit_from_plans(lacx_encoder* e, const int32_t* left, const int32_t* right, uint64_t frames,
@@ -143,26 +129,24 @@ int lacx_encode_device(lacx_encoder* e, const int32_t* d_left, const int32_t* d_
     if (!(e->cfg.flags & LACX_FLAG_HOST_EMIT)) {
         uint64_t pay = 0;
         rc = encode_pipelined_device(e, d_left, d_right, frames, static_cast<hipStream_t>(stream), &pay);
-        if (rc == LACX_OK) {
-            uint8_t* buf = static_cast<uint8_t*>(std::malloc(head + pay));
-            if (!buf) return fail(e, LACX_E_RUNTIME, "out of memory");
-            write_frame_header(stream_params(e->cfg, d_right ? 2 : 1), buf);
-            put32(buf + 10, nb);
-            for (uint32_t b = 0; b < nb; ++b) {
-                if (e->h_table[2 * b + 1] == 0) {
-                    std::free(buf);
-                    return fail(e, LACX_E_RUNTIME, "encoded block size is outside format limits");
-                }
-                put32(buf + 14 + 8ull * b, e->h_table[2 * b]);
-                put32(buf + 18 + 8ull * b, e->h_table[2 * b + 1]);
+        if (rc) return rc;
+        uint8_t* buf = static_cast<uint8_t*>(std::malloc(head + pay));
+        if (!buf) return fail(e, LACX_E_RUNTIME, "out of memory");
+        write_frame_header(stream_params(e->cfg, d_right ? 2 : 1), buf);
+        put32(buf + 10, nb);
+        for (uint32_t b = 0; b < nb; ++b) {
+            if (e->h_table()[2 * b + 1] == 0) {
+                std::free(buf);
+                return fail(e, LACX_E_RUNTIME, "encoded block size is outside format limits");
             }
-            big_copy(buf + head, e->h_payload, pay);
-            *out = buf;
-            *out_size = head + pay;
-            e->timing.total_ms = ms_since(t0);
-            return LACX_OK;
+            put32(buf + 14 + 8ull * b, e->h_table()[2 * b]);
+            put32(buf + 18 + 8ull * b, e->h_table()[2 * b + 1]);
         }
-        if (rc != -1) return rc;  // -1: pinned reservation too small -> host-emit pipeline below
+        big_copy(buf + head, e->h_payload, pay);
+        *out = buf;
+        *out_size = head + pay;
+        e->timing.total_ms = ms_since(t0);
+        return LACX_OK;
     }
     std::vector<int32_t> tl, tr;
     rc = fetch_pcm_if_needed(e, d_left, d_right, frames, h_left, h_right, tl, tr);
@@ -209,35 +193,29 @@ int lacx_encode(lacx_encoder* e, const int32_t* left, const int32_t* right, uint
         hs.p1 = reinterpret_cast<const uint8_t*>(right);
         hs.frame_bytes = sizeof(int32_t);
         uint64_t pay = 0;
-        rc = encode_pipelined_device(e, e->d_left, right ? e->d_right : nullptr, frames, nullptr, &pay, 0, 0, &hs);
-        if (rc == LACX_OK) {
-            const uint32_t nb = blocks_for(frames);
-            const uint64_t head = 10 + 4 + 8ull * nb;
-            uint8_t* lac = e->h_payload - head;  // h_prefix >= head bytes are reserved in front of the payload
-            write_frame_header(stream_params(e->cfg, right ? 2 : 1), lac);
-            put32(lac + 10, nb);
-            for (uint32_t b = 0; b < nb; ++b) {
-                if (e->h_table[2 * b + 1] == 0) return fail(e, LACX_E_RUNTIME, "encoded block size is outside format limits");
-                put32(lac + 14 + 8ull * b, e->h_table[2 * b]);
-                put32(lac + 18 + 8ull * b, e->h_table[2 * b + 1]);
-            }
-            uint8_t* buf = static_cast<uint8_t*>(std::malloc(head + pay));
-            if (!buf) return fail(e, LACX_E_RUNTIME, "out of memory");
-            big_copy(buf, lac, head + pay);
-            *out = buf;
-            *out_size = head + pay;
-            e->timing.total_ms = ms_since(t0);
-            return LACX_OK;
+        rc = encode_pipelined_device(e, e->d_left(), right ? e->d_right() : nullptr, frames, nullptr, &pay, 0, 0, &hs);
+        if (rc) return rc;
+        const uint32_t nb = blocks_for(frames);
+        const uint64_t head = 10 + 4 + 8ull * nb;
+        uint8_t* lac = e->h_payload - head;  // h_prefix >= head bytes are reserved in front of the payload
+        write_frame_header(stream_params(e->cfg, right ? 2 : 1), lac);
+        put32(lac + 10, nb);
+        for (uint32_t b = 0; b < nb; ++b) {
+            if (e->h_table()[2 * b + 1] == 0) return fail(e, LACX_E_RUNTIME, "encoded block size is outside format limits");
+            put32(lac + 14 + 8ull * b, e->h_table()[2 * b]);
+            put32(lac + 18 + 8ull * b, e->h_table()[2 * b + 1]);
         }
-        if (rc != -1) return rc;
-        // -1 (only with LACX_EMIT_STAGED): fall through to the host-emit pipeline; the PCM is on the device already
-        rc = lacx_encode_device(e, e->d_left, right ? e->d_right : nullptr, left, right, frames, nullptr, out, out_size);
+        uint8_t* buf = static_cast<uint8_t*>(std::malloc(head + pay));
+        if (!buf) return fail(e, LACX_E_RUNTIME, "out of memory");
+        big_copy(buf, lac, head + pay);
+        *out = buf;
+        *out_size = head + pay;
         e->timing.total_ms = ms_since(t0);
-        return rc;
+        return LACX_OK;
     }
     rc = upload(e, left, right, frames);
     if (rc) return rc;
-    rc = lacx_encode_device(e, e->d_left, right ? e->d_right : nullptr, left, right, frames, nullptr, out, out_size);
+    rc = lacx_encode_device(e, e->d_left(), right ? e->d_right() : nullptr, left, right, frames, nullptr, out, out_size);
     e->timing.total_ms = ms_since(t0);
     return rc;
 }
@@ -285,15 +263,13 @@ int lacx_encode_shard_device_view(lacx_encoder* e, const int32_t* d_left, const 
     if (!(e->cfg.flags & LACX_FLAG_HOST_EMIT)) {
         uint64_t pay = 0;
         rc = encode_pipelined_device(e, d_left, d_right, frames, static_cast<hipStream_t>(stream), &pay);
-        if (rc == LACX_OK) {
-            *payload = e->h_payload;
-            *payload_size = pay;
-            *table = e->h_table;
-            *nblocks = blocks_for(frames);
-            e->timing.total_ms = ms_since(t0);
-            return LACX_OK;
-        }
-        if (rc != -1) return rc;
+        if (rc) return rc;
+        *payload = e->h_payload;
+        *payload_size = pay;
+        *table = e->h_table();
+        *nblocks = blocks_for(frames);
+        e->timing.total_ms = ms_since(t0);
+        return LACX_OK;
     }
     std::free(e->view_buf);
     std::free(e->view_table);
@@ -352,18 +328,17 @@ int lacx_encode_shard_pcm_device_begin(lacx_encoder* e, const lacx_pcm* pcm, uin
 int lacx_encode_shard_end(lacx_encoder* e, const uint8_t** payload, uint64_t* payload_size, const uint32_t** table,
                           uint32_t* nblocks) {
     if (!e || !payload || !payload_size || !table || !nblocks) return LACX_E_INVALID;
-    const uint32_t nb = e->pend.nb;
+    const uint32_t nb = e->pend.plan.nb;
     uint64_t pay = 0;
     const int rc = encode_device_end(e, &pay);
     // an imported source that held a float which is no sample: the call fails, whatever the kernels made of the zeros
     // that stand in for it (its words are final: the import kernel ran in front of everything the call just waited for)
     const int ic = import_check(e, false);
-    if (ic && (rc == LACX_OK || rc == -1)) return ic;
-    if (rc == -1) return fail(e, LACX_E_RUNTIME, "payload exceeds the pinned result reservation");
+    if (ic && rc == LACX_OK) return ic;
     if (rc) return rc;
     *payload = e->h_payload;
     *payload_size = pay;
-    *table = e->h_table;
+    *table = e->h_table();
     *nblocks = nb;
     e->timing.total_ms = ms_since(e->pend.t0);
     return LACX_OK;
@@ -427,7 +402,7 @@ int lacx_encode_shard(lacx_encoder* e, const int32_t* left, const int32_t* right
     if (rc) return rc;
     rc = upload(e, left, right, frames);
     if (rc) return rc;
-    return lacx_encode_shard_device(e, e->d_left, right ? e->d_right : nullptr, left, right, frames, nullptr,
+    return lacx_encode_shard_device(e, e->d_left(), right ? e->d_right() : nullptr, left, right, frames, nullptr,
                                     payload, payload_size, table, nblocks);
 }
 
@@ -475,9 +450,8 @@ static int encode_wav_in_place(lacx_encoder* e, const uint8_t* wav, uint64_t siz
     hs.frame_bytes = (uint64_t)w.channels * (w.bit_depth / 8u);
     const int layout = w.bit_depth == 16 ? (int)LACX_PCM_INTERLEAVED_I16 : (int)LACX_PCM_INTERLEAVED_I24;
     uint64_t pay = 0;
-    rc = encode_pipelined_device(e, reinterpret_cast<const int32_t*>(e->d_raw), nullptr, w.frames, nullptr, &pay, layout,
+    rc = encode_pipelined_device(e, reinterpret_cast<const int32_t*>(e->d_raw()), nullptr, w.frames, nullptr, &pay, layout,
                                  (int)w.channels, &hs);
-    if (rc == -1) return fail(e, LACX_E_RUNTIME, "payload exceeds the pinned result reservation");
     if (rc) return rc;
     const uint32_t nb = blocks_for(w.frames);
     const uint64_t head = 10 + 4 + 8ull * nb;
@@ -485,9 +459,9 @@ static int encode_wav_in_place(lacx_encoder* e, const uint8_t* wav, uint64_t siz
     write_frame_header(stream_params(e->cfg, (int)w.channels), lac);
     put32(lac + 10, nb);
     for (uint32_t b = 0; b < nb; ++b) {
-        if (e->h_table[2 * b + 1] == 0) return fail(e, LACX_E_RUNTIME, "encoded block size is outside format limits");
-        put32(lac + 14 + 8ull * b, e->h_table[2 * b]);
-        put32(lac + 18 + 8ull * b, e->h_table[2 * b + 1]);
+        if (e->h_table()[2 * b + 1] == 0) return fail(e, LACX_E_RUNTIME, "encoded block size is outside format limits");
+        put32(lac + 14 + 8ull * b, e->h_table()[2 * b]);
+        put32(lac + 18 + 8ull * b, e->h_table()[2 * b + 1]);
     }
     *out = lac;
     *out_size = head + pay;
@@ -575,13 +549,13 @@ static int block_analyze(lacx_encoder* e, const int32_t* pcm, uint32_t n) {
         if (rc) return rc;
         if (!e->d_wide) HIP_TRY(e, hipMalloc((void**)&e->d_wide, (size_t)11 * kMaxBlock * sizeof(int32_t)), "hipMalloc(wide residuals)");
         hipStream_t st = e->stream[0];
-        HIP_TRY(e, launch_wide_block(e->d_left, n, e->cfg.zero_run_enabled ? 1 : 0, e->cfg.partitioning_enabled ? 1 : 0, e->d_wide,
+        HIP_TRY(e, launch_wide_block(e->d_left(), n, e->cfg.zero_run_enabled ? 1 : 0, e->cfg.partitioning_enabled ? 1 : 0, e->d_wide,
                                      e->ws.plans, st), "kernel launch");
         HIP_TRY(e, hipMemcpyAsync(e->h_plans, e->ws.plans, sizeof(ChannelPlan), hipMemcpyDeviceToHost, st), "D2H plan");
         HIP_TRY(e, hipStreamSynchronize(st), "synchronize");
         return LACX_OK;
     }
-    return analyze_on_device(e, e->d_left, nullptr, n, 1, 0, /*bit_depth=*/0, e->stream[0]);
+    return analyze_on_device(e, e->d_left(), nullptr, n, 1, 0, /*bit_depth=*/0, e->stream[0]);
 }
 
 int lacx_block_plan_only(lacx_encoder* e, const int32_t* pcm, uint32_t n, lacx_channel_plan* plan) {

@@ -6,10 +6,6 @@
 
 namespace lacx_host {
 
-bool is_import_layout(uint32_t layout) {
-    return layout == LACX_PCM_PLANAR_I16 || layout == LACX_PCM_PLANAR_F32 || layout == LACX_PCM_INTERLEAVED_F32;
-}
-
 const char* import_source_error(const lacx_pcm& p, int bit_depth, bool batch) {
     if (p.layout == LACX_PCM_PLANAR_I16 && bit_depth != 16)
         return batch ? "PCM layout does not match the bit depth" : "PCM layout does not match the configured bit depth";
@@ -32,7 +28,7 @@ void import_reset(lacx_encoder* e) {
 }
 
 int import_add(lacx_encoder* e, const lacx_pcm& p, uint64_t frames, int bit_depth, uint32_t owner, int* layout) {
-    *layout = bit_depth == 16 ? (int)LACX_PCM_INTERLEAVED_I16 : (int)LACX_PCM_INTERLEAVED_I24;
+    *layout = import_target_layout(bit_depth);
     if (import_is_alias(p.layout, p.channels, p.data0)) return -1;
     ImportItem it{};
     it.src0 = p.data0;
@@ -55,38 +51,20 @@ int import_enqueue(lacx_encoder* e, hipStream_t s) {
     const size_t n = imp.items.size();
     if (n == 0) return LACX_OK;
     if (imp.unit_off.back() > 0x7FFFFFFFull) return fail(e, LACX_E_INVALID, "too many frames for one import pass");
-    if (imp.bytes > e->d_import_cap) {
-        if (e->d_import) (void)hipFree(e->d_import);
-        e->d_import = nullptr;
-        e->d_import_cap = 0;
-        HIP_TRY(e, hipMalloc((void**)&e->d_import, imp.bytes), "hipMalloc(import)");
-        e->d_import_cap = imp.bytes;
-    }
-    for (size_t i = 0; i < n; ++i) imp.items[i].dst = e->d_import + imp.dst_off[i];
+    if (const int rc = grow(e, e->import_pcm, imp.bytes)) return rc;
+    for (size_t i = 0; i < n; ++i) imp.items[i].dst = e->d_import() + imp.dst_off[i];
     const size_t bad_bytes = (n * sizeof(ImportBad) + 15u) & ~(size_t)15u, item_bytes = (n * sizeof(ImportItem) + 15u) & ~(size_t)15u;
     const size_t tab_bytes = bad_bytes + item_bytes + (n + 1) * sizeof(unsigned long long);
-    if (tab_bytes > e->d_import_tab_cap) {
-        if (e->d_import_tab) (void)hipFree(e->d_import_tab);
-        e->d_import_tab = nullptr;
-        e->d_import_tab_cap = 0;
-        HIP_TRY(e, hipMalloc((void**)&e->d_import_tab, tab_bytes), "hipMalloc(import table)");
-        e->d_import_tab_cap = tab_bytes;
-    }
-    if (n > e->h_import_cap) {
-        if (e->h_import_bad) (void)hipHostFree(e->h_import_bad);
-        e->h_import_bad = nullptr;
-        e->h_import_cap = 0;
-        HIP_TRY(e, hipHostMalloc((void**)&e->h_import_bad, n * sizeof(ImportBad), 0), "hipHostMalloc(import)");
-        e->h_import_cap = (uint32_t)n;
-    }
-    ImportBad* bad = reinterpret_cast<ImportBad*>(e->d_import_tab);
+    if (const int rc = grow(e, e->import_tab, tab_bytes)) return rc;
+    if (const int rc = grow(e, e->import_bad, n)) return rc;
+    ImportBad* bad = reinterpret_cast<ImportBad*>(e->d_import_tab());
     ImportJob job{};
     job.nitems = (uint32_t)n;
     job.total_units = imp.unit_off.back();
     job.single = imp.items[0];
     HIP_TRY(e, hipMemsetAsync(bad, 0xFF, n * sizeof(ImportBad), s), "memset");
     if (n > 1) {  // (the vectors live in the encoder until its next call)
-        uint8_t* items = e->d_import_tab + bad_bytes;
+        uint8_t* items = e->d_import_tab() + bad_bytes;
         HIP_TRY(e, hipMemcpyAsync(items, imp.items.data(), n * sizeof(ImportItem), hipMemcpyHostToDevice, s), "H2D import table");
         HIP_TRY(e, hipMemcpyAsync(items + item_bytes, imp.unit_off.data(), (n + 1) * sizeof(unsigned long long), hipMemcpyHostToDevice, s),
                 "H2D import table");
@@ -94,20 +72,20 @@ int import_enqueue(lacx_encoder* e, hipStream_t s) {
         job.unit_off = reinterpret_cast<const unsigned long long*>(items + item_bytes);
     }
     HIP_TRY(e, launch_import(job, bad, s), "import launch");
-    HIP_TRY(e, hipMemcpyAsync(e->h_import_bad, bad, n * sizeof(ImportBad), hipMemcpyDeviceToHost, s), "D2H import result");
+    HIP_TRY(e, hipMemcpyAsync(e->h_import_bad(), bad, n * sizeof(ImportBad), hipMemcpyDeviceToHost, s), "D2H import result");
     imp.pending = true;
     return LACX_OK;
 }
 
 const int32_t* import_data(const lacx_encoder* e, int item) {
-    return reinterpret_cast<const int32_t*>(e->d_import + e->imp.dst_off[(size_t)item]);
+    return reinterpret_cast<const int32_t*>(e->d_import() + e->imp.dst_off[(size_t)item]);
 }
 
 int import_check_item(lacx_encoder* e, size_t i, bool batch) {
     int ch = 0;
     unsigned long long idx = 0;
     std::string what;
-    if (!import_bad_message(e->h_import_bad[i], e->imp.items[i].bit_depth, &ch, &idx, what)) return LACX_OK;
+    if (!import_bad_message(e->h_import_bad()[i], e->imp.items[i].bit_depth, &ch, &idx, what)) return LACX_OK;
     e->bad_channel = ch;
     e->bad_index = idx;
     return fail(e, LACX_E_INVALID, (batch ? "stream " + std::to_string(e->imp.owner[i]) + ": " : std::string()) + what);
@@ -119,14 +97,6 @@ int import_check(lacx_encoder* e, bool batch) {
     for (size_t i = 0; i < e->imp.items.size(); ++i)  // (in stream order: the items were added that way)
         if (const int rc = import_check_item(e, i, batch)) return rc;
     return LACX_OK;
-}
-
-void import_free(lacx_encoder* e) {
-    if (e->d_import) (void)hipFree(e->d_import);
-    if (e->d_import_tab) (void)hipFree(e->d_import_tab);
-    if (e->h_import_bad) (void)hipHostFree(e->h_import_bad);
-    e->d_import = e->d_import_tab = nullptr;
-    e->h_import_bad = nullptr;
 }
 
 }  // namespace lacx_host

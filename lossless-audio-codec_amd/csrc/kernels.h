@@ -54,11 +54,6 @@ struct LaunchTuning {
     int pack_grid = 0;             // the streaming packer's workgroups (0 = default)
     bool fold_front = true;        // the block's stereo estimate by its last ingest workgroup, its LR/MS choice by its last probe slot (LACX_NO_FRONT_FOLD: k_stereo / k_decide as kernels)
     bool no_pairs = false;         // persistent analysis: hand every slot out singly (LACX_NO_PAIRS; A/B of the pair units)
-    // Front kernels (ingest, stereo, Levinson, probes, decision) on a stream of their own: `stream` of launch_analysis then
-    // carries only the whole-block kernel and what follows, ordered behind the front by an event.  Used by the upload
-    // pipeline with a high-priority front stream: the next chunk's front kernels -- short, latency-bound -- then take the
-    // CUs that the current chunk's whole-block workgroups free one by one instead of waiting for the end of that kernel.
-    hipStream_t front_stream = nullptr;
     // One stream's front kernels in two block halves (one launch set = one stream, >= 1024 blocks): the first half on the
     // launch's stream, the second on `aux_stream` (lower priority, so that it starts when the first half's ingest kernel
     // has been dispatched): the Levinson kernel of a half -- one wave per SIMD, latency-bound, the chip nearly idle -- then
