@@ -90,35 +90,33 @@ int ensure_device(lacx_encoder* e) {
     if (dev >= count) return fail(e, LACX_E_DEVICE, "HIP device ordinal out of range");
     HIP_TRY(e, hipSetDevice(dev), "hipSetDevice");
     e->device = dev;
-    {
-        // Stream priorities.  The HIP runtime multiplexes streams onto a small pool of hardware queues PER PRIORITY LEVEL,
-        // and commands of streams that share a hardware queue execute in order.  The streaming packer must therefore be
-        // alone on its level: behind the analysis kernel in a shared queue it starts when the analysis is over (every
-        // encoder of a process but the first few: drain_first_ms 4.4 instead of 0.9 ms, steps 50 % longer -- the round-4
-        // bench caught it); sharing a queue with the uploader's stream it deadlocks against the upload it waits for until
-        // its 20 ms bound expires (a test caught that).  So: the analysis streams (pipeline chunk c on stream c) at HIGH
-        // priority (front kernels measured 20 % slower at normal), the packer at LOW, where no other stream of this
-        // library or, by default, of anybody else lives; copy, upload and decoder streams at the default (normal).
-        // Measured (WAV -> .lac, 10 min stream, 4 chunks): high/high/low 3.42 ms, high/low/normal 3.40, high/normal/low
-        // 3.73, all high (round 3) 3.41.  LACX_STREAM_PRIO=main,chunks,pack overrides.
-        int least = 0, greatest = 0;
-        (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-        const bool prio = e->knobs.stream_priority && greatest < least;
-        const int normal = (greatest + least) / 2 > greatest ? (greatest + least) / 2 : std::min(greatest + 1, least);
-        auto level = [&](int code) { return code < 0 ? greatest : (code == 0 ? normal : least); };  // -1 high, 0 normal, 1 low
-        int i = 0;
-        for (auto& s : e->stream) {
-            if (prio) {
-                // (the last stream doubles as the lower-priority stream of the second half's front kernels,
-                // LaunchTuning::aux_stream: NORMAL, not low -- the packer must stay alone on its level, see above; two
-                // encoders on one device whose fourth pipeline chunk shared a hardware queue with a packer stalled 20 ms)
-                const int p = level(i == 0 ? e->knobs.prio_main : (i == kStreams - 1 ? 0 : e->knobs.prio_chunks));
-                HIP_TRY(e, hipStreamCreateWithPriority(&s, hipStreamNonBlocking, p), "hipStreamCreate");
-            } else {
-                HIP_TRY(e, hipStreamCreateWithFlags(&s, hipStreamNonBlocking), "hipStreamCreate");
-            }
-            ++i;
+    // Stream priorities.  The HIP runtime multiplexes streams onto a small pool of hardware queues PER PRIORITY LEVEL,
+    // and commands of streams that share a hardware queue execute in order.  The streaming packer must therefore be
+    // alone on its level: behind the analysis kernel in a shared queue it starts when the analysis is over (every
+    // encoder of a process but the first few: drain_first_ms 4.4 instead of 0.9 ms, steps 50 % longer -- the round-4
+    // bench caught it); sharing a queue with the uploader's stream it deadlocks against the upload it waits for until
+    // its 20 ms bound expires (a test caught that).  So: the analysis streams (pipeline chunk c on stream c) at HIGH
+    // priority (front kernels measured 20 % slower at normal), the packer at LOW, where no other stream of this
+    // library or, by default, of anybody else lives; copy, upload and decoder streams at the default (normal).
+    // Measured (WAV -> .lac, 10 min stream, 4 chunks): high/high/low 3.42 ms, high/low/normal 3.40, high/normal/low
+    // 3.73, all high (round 3) 3.41.  LACX_STREAM_PRIO=main,chunks,pack overrides.
+    int least = 0, greatest = 0;
+    (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
+    const bool prio = e->knobs.stream_priority && greatest < least;
+    const int normal = (greatest + least) / 2 > greatest ? (greatest + least) / 2 : std::min(greatest + 1, least);
+    auto level = [&](int code) { return code < 0 ? greatest : (code == 0 ? normal : least); };  // -1 high, 0 normal, 1 low
+    int i = 0;
+    for (auto& s : e->stream) {
+        if (prio) {
+            // (the last stream doubles as the lower-priority stream of the second half's front kernels,
+            // LaunchTuning::aux_stream: NORMAL, not low -- the packer must stay alone on its level, see above; two
+            // encoders on one device whose fourth pipeline chunk shared a hardware queue with a packer stalled 20 ms)
+            const int p = level(i == 0 ? e->knobs.prio_main : (i == kStreams - 1 ? 0 : e->knobs.prio_chunks));
+            HIP_TRY(e, hipStreamCreateWithPriority(&s, hipStreamNonBlocking, p), "hipStreamCreate");
+        } else {
+            HIP_TRY(e, hipStreamCreateWithFlags(&s, hipStreamNonBlocking), "hipStreamCreate");
         }
+        ++i;
     }
     for (auto& row : e->ev)
         for (auto& ev : row) HIP_TRY(e, hipEventCreate(&ev), "hipEventCreate");
@@ -128,13 +126,7 @@ int ensure_device(lacx_encoder* e) {
     for (auto& ev : e->aux_ev) HIP_TRY(e, hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate");
     HIP_TRY(e, hipHostMalloc((void**)&e->h_totals, sizeof(unsigned long long) * kMaxChunks, 0), "hipHostMalloc");
     HIP_TRY(e, hipHostMalloc((void**)&e->h_err, sizeof(uint32_t) * (kMaxChunks + 8), 0), "hipHostMalloc");
-    {
-        int least = 0, greatest = 0;
-        (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-        const int normal = (greatest + least) / 2 > greatest ? (greatest + least) / 2 : std::min(greatest + 1, least);
-        const int pp = e->knobs.prio_pack < 0 ? greatest : (e->knobs.prio_pack == 0 ? normal : least);
-        HIP_TRY(e, hipStreamCreateWithPriority(&e->pack_stream, hipStreamNonBlocking, pp), "hipStreamCreate");
-    }
+    HIP_TRY(e, hipStreamCreateWithPriority(&e->pack_stream, hipStreamNonBlocking, level(e->knobs.prio_pack)), "hipStreamCreate");
     HIP_TRY(e, hipEventCreateWithFlags(&e->pack_done, hipEventDisableTiming), "hipEventCreate");
     HIP_TRY(e, hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking), "hipStreamCreate");
     HIP_TRY(e, hipStreamCreateWithFlags(&e->copy_stream2, hipStreamNonBlocking), "hipStreamCreate");
@@ -377,13 +369,6 @@ StreamParams stream_params(const lacx_config& c, int channels) {
     return sp;
 }
 
-void put32(uint8_t* p, uint32_t v) {
-    p[0] = (uint8_t)(v >> 24);
-    p[1] = (uint8_t)(v >> 16);
-    p[2] = (uint8_t)(v >> 8);
-    p[3] = (uint8_t)v;
-}
-
 // Bytes reserved for the payload of a shard.  The buffer is virtual memory until touched, so the bound
 // is generous: 12 bytes per sample (the costliest realistic material, full-scale 24-bit noise, needs
 // about 3.3).  The real size is known from the plans before any block is published; a stream that
@@ -413,18 +398,6 @@ int prepare(lacx_encoder* e, const void* left, uint64_t frames) {
     rc = ensure_device(e);
     if (rc) return rc;
     HIP_TRY(e, hipSetDevice(e->device), "hipSetDevice");
-    return LACX_OK;
-}
-
-int fill_table(lacx_encoder* e, uint8_t* buf, uint32_t nb, const std::vector<uint64_t>& offsets) {
-    put32(buf + 10, nb);
-    for (uint32_t b = 0; b < nb; ++b) {
-        const uint64_t size = offsets[b + 1] - offsets[b];
-        if (size == 0 || size > 0xFFFFFFFFull)
-            return fail(e, LACX_E_RUNTIME, "encoded block size is outside format limits");
-        put32(buf + 14 + 8ull * b, e->h_bplans[b].frames);
-        put32(buf + 18 + 8ull * b, (uint32_t)size);
-    }
     return LACX_OK;
 }
 

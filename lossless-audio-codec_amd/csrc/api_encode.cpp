@@ -7,6 +7,54 @@ namespace lacx_host {
 // Device buffer for a WAV data chunk of `bytes` bytes (+ the look-ahead the staging loads may touch).
 static int ensure_raw(lacx_encoder* e, uint64_t bytes) { return grow(e, e->raw, bytes + 16u); }
 
+// Planar int32 in host memory as the pipelines take it.
+static HostSrc planar_src(const int32_t* left, const int32_t* right) {
+    return HostSrc{reinterpret_cast<const uint8_t*>(left), reinterpret_cast<const uint8_t*>(right), sizeof(int32_t)};
+}
+// The data chunk of a parsed WAV image as it is in the file: interleaved little-endian int16 / packed int24 (coalesced
+// ingest); *layout: what the kernels are told it is.
+static HostSrc wav_src(const uint8_t* wav, const WavInfo& w, int* layout) {
+    *layout = w.bit_depth == 16 ? (int)LACX_PCM_INTERLEAVED_I16 : (int)LACX_PCM_INTERLEAVED_I24;
+    return HostSrc{wav + w.data_offset, nullptr, (uint64_t)w.channels * (w.bit_depth / 8u)};
+}
+
+// A call on device input starts its timing afresh but keeps h2d_ms: the upload in front of it belongs to the same encode.
+static void reset_timing_keep_h2d(lacx_encoder* e) {
+    const double h2d = e->timing.h2d_ms;
+    e->timing = lacx_timing{};
+    e->timing.h2d_ms = h2d;
+}
+
+// The table rows of a host emit (container.h), a refusal as the encoder's error.
+static int host_rows(lacx_encoder* e, const std::vector<uint64_t>& offsets, const BlockPlan* bplans, uint32_t nb,
+                     std::vector<uint32_t>& rows) {
+    rows.resize(2 * (size_t)nb);
+    return rows_from_offsets(offsets.data(), bplans, nb, rows.data()) ? LACX_OK : fail(e, LACX_E_RUNTIME, kBlockSizeError);
+}
+
+// Device emit: the whole .lac in place in the pinned result buffer -- the container's head from the pinned block table,
+// written into the prefix in front of the payload the device put there itself (valid until the encoder's next call).
+static int lac_in_place(lacx_encoder* e, int channels, uint64_t frames, uint64_t pay, const uint8_t** lac, uint64_t* size) {
+    const uint32_t nb = blocks_for(frames);
+    const uint64_t head = stream_head_bytes(nb);
+    if (head > e->h_prefix) return fail(e, LACX_E_RUNTIME, "the container's head does not fit in front of the pinned payload (internal error)");
+    uint8_t* at = e->h_payload - head;
+    write_stream_start(stream_params(e->cfg, channels), nb, at);
+    if (!write_rows(at, 0, e->h_table(), nb)) return fail(e, LACX_E_RUNTIME, kBlockSizeError);
+    *lac = at;
+    *size = head + pay;
+    return LACX_OK;
+}
+
+// A view into the encoder's buffers as memory the caller owns (lacx_free); n == 0 still yields an allocation.
+static int owned_copy(lacx_encoder* e, const uint8_t* view, uint64_t n, uint8_t** out) {
+    uint8_t* buf = static_cast<uint8_t*>(std::malloc(n ? n : 1));
+    if (!buf) return fail(e, LACX_E_RUNTIME, "out of memory");
+    big_copy(buf, view, n);
+    *out = buf;
+    return LACX_OK;
+}
+
 // One lane's work in a fan-out, and what a plain encoder does with host input: the frames of hs on e's device, upload
 // pipelined with the kernels; results are views into e's buffers.
 int encode_host_shard_view(lacx_encoder* e, const HostSrc& hs, int layout, int channels, uint64_t frames, const uint8_t** payload,
@@ -75,7 +123,7 @@ int lacx_emit_from_plans(lacx_encoder* e, const int32_t* left, const int32_t* ri
                          const lacx_block_plan* bplans_c, const lacx_channel_plan* plans_c, uint8_t** out,
                          uint64_t* out_size) {
     if (!e || !out || !out_size || !bplans_c || !plans_c) return LACX_E_INVALID;
-    const int rc = validate_stream_args(e, left, frames);
+    int rc = validate_stream_args(e, left, frames);
     if (rc) return rc;
     const BlockPlan* bplans = reinterpret_cast<const BlockPlan*>(bplans_c);
     const ChannelPlan* plans = reinterpret_cast<const ChannelPlan*>(plans_c);
@@ -89,20 +137,14 @@ int lacx_emit_from_plans(lacx_encoder* e, const int32_t* left, const int32_t* ri
         off += block_payload_bytes(sp, bplans[b], plans + (size_t)b * kSlotsPerBlock);
     }
     offsets[nb] = off;
-    const uint64_t head = 10 + 4 + 8ull * nb;
+    std::vector<uint32_t> rows;
+    rc = host_rows(e, offsets, bplans, nb, rows);
+    if (rc) return rc;
+    const uint64_t head = stream_head_bytes(nb);
     uint8_t* buf = static_cast<uint8_t*>(std::malloc(head + off));
     if (!buf) return fail(e, LACX_E_RUNTIME, "out of memory");
-    write_frame_header(sp, buf);
-    put32(buf + 10, nb);
-    for (uint32_t b = 0; b < nb; ++b) {
-        const uint64_t size = offsets[b + 1] - offsets[b];
-        if (size == 0 || size > 0xFFFFFFFFull) {
-            std::free(buf);
-            return fail(e, LACX_E_RUNTIME, "encoded block size is outside format limits");
-        }
-        put32(buf + 14 + 8ull * b, bplans[b].frames);
-        put32(buf + 18 + 8ull * b, (uint32_t)size);
-    }
+    write_stream_start(sp, nb, buf);
+    write_rows(buf, 0, rows.data(), nb);
     const std::string err = emit_blocks(sp, left, right, frames, bplans, plans, nb, offsets.data(), buf + head, off,
                                         e->cfg.emit_threads);
     if (!err.empty()) {
@@ -119,35 +161,23 @@ int lacx_encode_device(lacx_encoder* e, const int32_t* d_left, const int32_t* d_
                        uint64_t* out_size) {
     if (!e || !out || !out_size) return LACX_E_INVALID;
     const auto t0 = clk::now();
-    const double h2d = e->timing.h2d_ms;
-    e->timing = lacx_timing{};
-    e->timing.h2d_ms = h2d;
+    reset_timing_keep_h2d(e);
     int rc = prepare(e, d_left, frames);
     if (rc) return rc;
-    const uint32_t nb = blocks_for(frames);
-    const uint64_t head = 10 + 4 + 8ull * nb;
+    const int channels = d_right ? 2 : 1;
     if (!(e->cfg.flags & LACX_FLAG_HOST_EMIT)) {
         uint64_t pay = 0;
         rc = encode_pipelined_device(e, d_left, d_right, frames, static_cast<hipStream_t>(stream), &pay);
         if (rc) return rc;
-        uint8_t* buf = static_cast<uint8_t*>(std::malloc(head + pay));
-        if (!buf) return fail(e, LACX_E_RUNTIME, "out of memory");
-        write_frame_header(stream_params(e->cfg, d_right ? 2 : 1), buf);
-        put32(buf + 10, nb);
-        for (uint32_t b = 0; b < nb; ++b) {
-            if (e->h_table()[2 * b + 1] == 0) {
-                std::free(buf);
-                return fail(e, LACX_E_RUNTIME, "encoded block size is outside format limits");
-            }
-            put32(buf + 14 + 8ull * b, e->h_table()[2 * b]);
-            put32(buf + 18 + 8ull * b, e->h_table()[2 * b + 1]);
-        }
-        big_copy(buf + head, e->h_payload, pay);
-        *out = buf;
-        *out_size = head + pay;
+        const uint8_t* lac = nullptr;
+        rc = lac_in_place(e, channels, frames, pay, &lac, out_size);
+        if (!rc) rc = owned_copy(e, lac, *out_size, out);
+        if (rc) return rc;
         e->timing.total_ms = ms_since(t0);
         return LACX_OK;
     }
+    const uint32_t nb = blocks_for(frames);
+    const uint64_t head = stream_head_bytes(nb);
     std::vector<int32_t> tl, tr;
     rc = fetch_pcm_if_needed(e, d_left, d_right, frames, h_left, h_right, tl, tr);
     if (rc) return rc;
@@ -157,12 +187,14 @@ int lacx_encode_device(lacx_encoder* e, const int32_t* d_left, const int32_t* d_
     rc = encode_pipelined(e, d_left, d_right, h_left, d_right ? h_right : nullptr, frames,
                           static_cast<hipStream_t>(stream), head, &buf, &pay, offsets);
     if (rc) return rc;
-    write_frame_header(stream_params(e->cfg, d_right ? 2 : 1), buf);
-    rc = fill_table(e, buf, nb, offsets);
+    std::vector<uint32_t> rows;
+    rc = host_rows(e, offsets, e->h_bplans, nb, rows);
     if (rc) {
         std::free(buf);
         return rc;
     }
+    write_stream_start(stream_params(e->cfg, channels), nb, buf);
+    write_rows(buf, 0, rows.data(), nb);
     *out = buf;
     *out_size = head + pay;
     e->timing.total_ms = ms_since(t0);
@@ -177,39 +209,20 @@ int lacx_encode(lacx_encoder* e, const int32_t* left, const int32_t* right, uint
     e->timing = lacx_timing{};
     int rc = prepare(e, left, frames);
     if (rc) return rc;
-    if (is_fanout(e)) {  // the blocks spread over the encoder's devices (api_fanout.cpp)
-        HostSrc hs;
-        hs.p0 = reinterpret_cast<const uint8_t*>(left);
-        hs.p1 = reinterpret_cast<const uint8_t*>(right);
-        hs.frame_bytes = sizeof(int32_t);
+    const HostSrc hs = planar_src(left, right);
+    if (is_fanout(e))  // the blocks spread over the encoder's devices (api_fanout.cpp)
         return fanout_encode_host(e, hs, 0, right ? 2 : 1, frames, true, out, out_size);
-    }
     if (!(e->cfg.flags & LACX_FLAG_HOST_EMIT)) {
         // device emit: the upload is pipelined with the analysis (chunk c+1's PCM crosses PCIe under chunk c's kernels)
         rc = ensure_pcm(e, frames, right != nullptr);
         if (rc) return rc;
-        HostSrc hs;
-        hs.p0 = reinterpret_cast<const uint8_t*>(left);
-        hs.p1 = reinterpret_cast<const uint8_t*>(right);
-        hs.frame_bytes = sizeof(int32_t);
         uint64_t pay = 0;
         rc = encode_pipelined_device(e, e->d_left(), right ? e->d_right() : nullptr, frames, nullptr, &pay, 0, 0, &hs);
         if (rc) return rc;
-        const uint32_t nb = blocks_for(frames);
-        const uint64_t head = 10 + 4 + 8ull * nb;
-        uint8_t* lac = e->h_payload - head;  // h_prefix >= head bytes are reserved in front of the payload
-        write_frame_header(stream_params(e->cfg, right ? 2 : 1), lac);
-        put32(lac + 10, nb);
-        for (uint32_t b = 0; b < nb; ++b) {
-            if (e->h_table()[2 * b + 1] == 0) return fail(e, LACX_E_RUNTIME, "encoded block size is outside format limits");
-            put32(lac + 14 + 8ull * b, e->h_table()[2 * b]);
-            put32(lac + 18 + 8ull * b, e->h_table()[2 * b + 1]);
-        }
-        uint8_t* buf = static_cast<uint8_t*>(std::malloc(head + pay));
-        if (!buf) return fail(e, LACX_E_RUNTIME, "out of memory");
-        big_copy(buf, lac, head + pay);
-        *out = buf;
-        *out_size = head + pay;
+        const uint8_t* lac = nullptr;
+        rc = lac_in_place(e, right ? 2 : 1, frames, pay, &lac, out_size);
+        if (!rc) rc = owned_copy(e, lac, *out_size, out);
+        if (rc) return rc;
         e->timing.total_ms = ms_since(t0);
         return LACX_OK;
     }
@@ -238,9 +251,10 @@ static int shard_host_path(lacx_encoder* e, const int32_t* d_left, const int32_t
         std::free(buf);
         return fail(e, LACX_E_RUNTIME, "out of memory");
     }
-    for (uint32_t b = 0; b < nb; ++b) {
-        tab[2 * b] = e->h_bplans[b].frames;
-        tab[2 * b + 1] = (uint32_t)(offsets[b + 1] - offsets[b]);
+    if (!rows_from_offsets(offsets.data(), e->h_bplans, nb, tab)) {
+        std::free(buf);
+        std::free(tab);
+        return fail(e, LACX_E_RUNTIME, kBlockSizeError);
     }
     *payload = buf;
     *payload_size = pay;
@@ -255,9 +269,7 @@ int lacx_encode_shard_device_view(lacx_encoder* e, const int32_t* d_left, const 
                                   uint32_t* nblocks) {
     if (!e || !payload || !payload_size || !table || !nblocks) return LACX_E_INVALID;
     const auto t0 = clk::now();
-    const double h2d = e->timing.h2d_ms;
-    e->timing = lacx_timing{};
-    e->timing.h2d_ms = h2d;
+    reset_timing_keep_h2d(e);
     int rc = prepare(e, d_left, frames);
     if (rc) return rc;
     if (!(e->cfg.flags & LACX_FLAG_HOST_EMIT)) {
@@ -376,16 +388,16 @@ int lacx_encode_shard_device(lacx_encoder* e, const int32_t* d_left, const int32
     const uint32_t* vt = nullptr;
     uint64_t pay = 0;
     uint32_t nb = 0;
-    const int rc = lacx_encode_shard_device_view(e, d_left, d_right, h_left, h_right, frames, stream, &vp, &pay, &vt, &nb);
+    int rc = lacx_encode_shard_device_view(e, d_left, d_right, h_left, h_right, frames, stream, &vp, &pay, &vt, &nb);
     if (rc) return rc;
-    uint8_t* buf = static_cast<uint8_t*>(std::malloc(pay ? pay : 1));
+    uint8_t* buf = nullptr;
+    rc = owned_copy(e, vp, pay, &buf);
+    if (rc) return rc;
     uint32_t* tab = static_cast<uint32_t*>(std::malloc(sizeof(uint32_t) * 2 * (nb ? nb : 1)));
-    if (!buf || !tab) {
+    if (!tab) {
         std::free(buf);
-        std::free(tab);
         return fail(e, LACX_E_RUNTIME, "out of memory");
     }
-    big_copy(buf, vp, pay);
     std::memcpy(tab, vt, sizeof(uint32_t) * 2 * nb);
     *payload = buf;
     *payload_size = pay;
@@ -431,40 +443,24 @@ static int encode_wav_in_place(lacx_encoder* e, const uint8_t* wav, uint64_t siz
                                            std::to_string((int)w.bit_depth) + " bit) differs from the encoder's");
     int rc = prepare(e, wav + w.data_offset, w.frames);
     if (rc) return rc;
+    int layout = 0;
+    const HostSrc hs = wav_src(wav, w, &layout);
     if (is_fanout(e)) {
-        HostSrc fs;
-        fs.p0 = wav + w.data_offset;
-        fs.frame_bytes = (uint64_t)w.channels * (w.bit_depth / 8u);
         uint8_t* buf = nullptr;
-        rc = fanout_encode_host(e, fs, w.bit_depth == 16 ? (int)LACX_PCM_INTERLEAVED_I16 : (int)LACX_PCM_INTERLEAVED_I24,
-                                (int)w.channels, w.frames, false, &buf, out_size);
+        rc = fanout_encode_host(e, hs, layout, (int)w.channels, w.frames, false, &buf, out_size);
         *out = buf;
         return rc;
     }
     rc = ensure_raw(e, w.data_bytes);
     if (rc) return rc;
-    // The data chunk as it is in the file: interleaved little-endian int16 / packed int24 (coalesced ingest), uploaded
-    // chunk by chunk in front of each pipeline chunk's kernels (the upload of chunk c+1 overlaps the analysis of chunk c).
-    HostSrc hs;
-    hs.p0 = wav + w.data_offset;
-    hs.frame_bytes = (uint64_t)w.channels * (w.bit_depth / 8u);
-    const int layout = w.bit_depth == 16 ? (int)LACX_PCM_INTERLEAVED_I16 : (int)LACX_PCM_INTERLEAVED_I24;
+    // The data chunk is uploaded chunk by chunk in front of each pipeline chunk's kernels (the upload of chunk c+1 overlaps
+    // the analysis of chunk c).
     uint64_t pay = 0;
     rc = encode_pipelined_device(e, reinterpret_cast<const int32_t*>(e->d_raw()), nullptr, w.frames, nullptr, &pay, layout,
                                  (int)w.channels, &hs);
     if (rc) return rc;
-    const uint32_t nb = blocks_for(w.frames);
-    const uint64_t head = 10 + 4 + 8ull * nb;
-    uint8_t* lac = e->h_payload - head;  // h_prefix >= head bytes are reserved in front of the payload
-    write_frame_header(stream_params(e->cfg, (int)w.channels), lac);
-    put32(lac + 10, nb);
-    for (uint32_t b = 0; b < nb; ++b) {
-        if (e->h_table()[2 * b + 1] == 0) return fail(e, LACX_E_RUNTIME, "encoded block size is outside format limits");
-        put32(lac + 14 + 8ull * b, e->h_table()[2 * b]);
-        put32(lac + 18 + 8ull * b, e->h_table()[2 * b + 1]);
-    }
-    *out = lac;
-    *out_size = head + pay;
+    rc = lac_in_place(e, (int)w.channels, w.frames, pay, out, out_size);
+    if (rc) return rc;
     e->timing.total_ms = ms_since(t0);
     return LACX_OK;
 }
@@ -479,12 +475,9 @@ int lacx_encode_wav(lacx_encoder* e, const uint8_t* wav, uint64_t size, uint8_t*
     const auto t0 = clk::now();
     const uint8_t* view = nullptr;
     uint64_t n = 0;
-    const int rc = encode_wav_in_place(e, wav, size, &view, &n);
+    int rc = encode_wav_in_place(e, wav, size, &view, &n);
+    if (!rc) rc = owned_copy(e, view, n, out);
     if (rc) return rc;
-    uint8_t* buf = static_cast<uint8_t*>(std::malloc(n ? n : 1));
-    if (!buf) return fail(e, LACX_E_RUNTIME, "out of memory");
-    big_copy(buf, view, n);
-    *out = buf;
     *out_size = n;
     e->timing.total_ms = ms_since(t0);
     return LACX_OK;
@@ -500,21 +493,17 @@ int lacx_assemble(const lacx_config* cfg, int channels, uint32_t nshards, const 
         pay += payload_sizes[s];
     }
     if (nb == 0 || nb > 0xFFFFFFFFull) return LACX_E_INVALID;
-    const uint64_t head = 10 + 4 + 8 * nb;
+    const uint64_t head = stream_head_bytes((uint32_t)nb);
     uint8_t* buf = static_cast<uint8_t*>(std::malloc(head + pay));
     if (!buf) return LACX_E_RUNTIME;
-    write_frame_header(stream_params(*cfg, channels), buf);
-    put32(buf + 10, (uint32_t)nb);
+    write_stream_start(stream_params(*cfg, channels), (uint32_t)nb, buf);
     uint64_t bi = 0, off = head;
     for (uint32_t s = 0; s < nshards; ++s) {
-        for (uint32_t b = 0; b < nblocks[s]; ++b, ++bi) {
-            if (tables[s][2 * b + 1] == 0) {
-                std::free(buf);
-                return LACX_E_RUNTIME;
-            }
-            put32(buf + 14 + 8 * bi, tables[s][2 * b]);
-            put32(buf + 18 + 8 * bi, tables[s][2 * b + 1]);
+        if (!write_rows(buf, bi, tables[s], nblocks[s])) {
+            std::free(buf);
+            return LACX_E_RUNTIME;
         }
+        bi += nblocks[s];
         big_copy(buf + off, payloads[s], payload_sizes[s]);
         off += payload_sizes[s];
     }

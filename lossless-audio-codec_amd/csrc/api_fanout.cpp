@@ -16,7 +16,6 @@
 
 #include <atomic>
 #include <barrier>
-#include <condition_variable>
 #include <functional>
 #include <mutex>
 
@@ -64,11 +63,7 @@ struct Lane {
     lacx_encoder* enc = nullptr;  // lane 0: the owning encoder itself; others: children (owned)
     int device = 0;
     bool shares_device = false;   // another lane of the list uses the same device (rehearsal on fewer GPUs)
-    std::thread th;
-    std::mutex mu;
-    std::condition_variable cv;
-    std::function<void()> job;
-    bool has_job = false, quit = false;
+    std::unique_ptr<Worker> worker;  // null for lane 0: its jobs run on the calling thread
     // RCCL exchange buffers (device: 2 u64 in, 2 * lanes u64 out; pinned host mirrors)
     ncclComm_t comm = nullptr;
     unsigned long long* d_x = nullptr;
@@ -96,36 +91,6 @@ struct Fanout {
 };
 
 namespace {
-
-void lane_loop(Lane* ln) {
-    for (;;) {
-        std::function<void()> job;
-        {
-            std::unique_lock<std::mutex> lock(ln->mu);
-            ln->cv.wait(lock, [&] { return ln->has_job || ln->quit; });
-            if (ln->quit) return;
-            job = std::move(ln->job);
-        }
-        job();
-        {
-            std::lock_guard<std::mutex> lock(ln->mu);
-            ln->has_job = false;
-        }
-        ln->cv.notify_all();
-    }
-}
-void lane_post(Lane* ln, std::function<void()> job) {
-    {
-        std::lock_guard<std::mutex> lock(ln->mu);
-        ln->job = std::move(job);
-        ln->has_job = true;
-    }
-    ln->cv.notify_all();
-}
-void lane_wait(Lane* ln) {
-    std::unique_lock<std::mutex> lock(ln->mu);
-    ln->cv.wait(lock, [&] { return !ln->has_job; });
-}
 
 // Communicators and exchange buffers, once per encoder, before the first fanned-out call that wants RCCL.
 void setup_rccl(lacx_encoder* e) {
@@ -249,9 +214,9 @@ int run_fanout(lacx_encoder* e, FanCall& call, const std::vector<uint64_t>& lane
         }
         ln.concat_ms = ms_since(t2);
     };
-    for (uint32_t g = 1; g < G; ++g) lane_post(f.lanes[g].get(), [&lane_job, g] { lane_job(g); });
+    for (uint32_t g = 1; g < G; ++g) f.lanes[g]->worker->post([&lane_job, g] { lane_job(g); });
     lane_job(0);
-    for (uint32_t g = 1; g < G; ++g) lane_wait(f.lanes[g].get());
+    for (uint32_t g = 1; g < G; ++g) f.lanes[g]->worker->wait();
     (void)hipSetDevice(e->device);
     // statistics of the call
     lacx_fanout_stats& st = f.stats;
@@ -333,14 +298,7 @@ void destroy_fanout(lacx_encoder* e) {
     Fanout* f = e->fan;
     for (size_t g = 0; g < f->lanes.size(); ++g) {
         Lane& ln = *f->lanes[g];
-        if (ln.th.joinable()) {
-            {
-                std::lock_guard<std::mutex> lock(ln.mu);
-                ln.quit = true;
-            }
-            ln.cv.notify_all();
-            ln.th.join();
-        }
+        ln.worker.reset();  // joins the lane's thread
         if (ln.comm) {
             if (Rccl* r = rccl()) (void)r->CommDestroy(ln.comm);
         }
@@ -365,7 +323,7 @@ int fanout_encode_host(lacx_encoder* e, const HostSrc& hs, int layout, int chann
     const auto t0 = clk::now();
     const uint32_t nb = blocks_for(frames);
     const uint32_t G = lanes_for(f, nb);
-    const uint64_t head = 10 + 4 + 8ull * nb;
+    const uint64_t head = stream_head_bytes(nb);
     uint8_t* buf = nullptr;
     std::vector<uint64_t> lane_f0(G), lane_frames(G);
     for (uint32_t g = 0; g < G; ++g) {
@@ -397,19 +355,12 @@ int fanout_encode_host(lacx_encoder* e, const HostSrc& hs, int layout, int chann
             buf = f.result;
         }
         oom = buf == nullptr;
-        if (buf) {
-            write_frame_header(stream_params(e->cfg, channels), buf);
-            put32(buf + 10, nb);
-        }
+        if (buf) write_stream_start(stream_params(e->cfg, channels), nb, buf);
     };
     std::atomic<bool> bad_block{false};
     call.place = [&](uint32_t, Lane& ln, uint64_t blocks_before) {
         if (!buf) return;
-        for (uint32_t b = 0; b < ln.nb; ++b) {
-            if (ln.table[2 * b + 1] == 0) bad_block = true;
-            put32(buf + 14 + 8ull * (blocks_before + b), ln.table[2 * b]);
-            put32(buf + 18 + 8ull * (blocks_before + b), ln.table[2 * b + 1]);
-        }
+        if (!write_rows(buf, blocks_before, ln.table, ln.nb)) bad_block = true;
         // (one thread per lane copies its own payload: the concat runs G-wide; pieces above 32 MB split further)
         if (ln.pay > (32ull << 20)) big_copy(buf + head + ln.byte_off, ln.payload, ln.pay);
         else std::memcpy(buf + head + ln.byte_off, ln.payload, ln.pay);
@@ -424,7 +375,7 @@ int fanout_encode_host(lacx_encoder* e, const HostSrc& hs, int layout, int chann
     if (oom) return fail(e, LACX_E_RUNTIME, "out of memory");
     if (bad_block) {
         if (owned) std::free(buf);
-        return fail(e, LACX_E_RUNTIME, "encoded block size is outside format limits");
+        return fail(e, LACX_E_RUNTIME, kBlockSizeError);
     }
     uint64_t total = 0;
     for (uint32_t g = 0; g < G; ++g) total += f.lanes[g]->pay;
@@ -513,7 +464,7 @@ int lacx_encoder_create_multi(const lacx_config* cfg, const int32_t* devices, ui
                 ci.device = devices[i];
                 rc = lacx_encoder_create(&ci, &ln->enc);
                 if (rc) break;
-                ln->th = std::thread(lane_loop, ln.get());
+                ln->worker = std::make_unique<Worker>();
             }
             // Lanes that share a device (a rehearsal on fewer GPUs than lanes): persistent analysis workgroups never retire,
             // so two such grids and their packers on one device starve each other -- the launched grid time-slices.

@@ -364,9 +364,11 @@ int prepare_shard(lacx_encoder* e, const int32_t* d_left, const int32_t* d_right
 // begin, step 2 (host input): the uploader thread copies the chunks in order and announces each.
 int start_upload(lacx_encoder* e, const HostSrc& src) {
     if (!e->uploader) {
-        e->uploader.reset(new Uploader());
-        HIP_TRY(e, hipStreamCreateWithFlags(&e->up_stream, hipStreamNonBlocking), "hipStreamCreate");
-        for (auto& ev : e->up_ev) HIP_TRY(e, hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate");
+        // the thread last: a creation that fails leaves no uploader behind, and the next call makes what is still missing
+        if (!e->up_stream) HIP_TRY(e, hipStreamCreateWithFlags(&e->up_stream, hipStreamNonBlocking), "hipStreamCreate");
+        for (auto& ev : e->up_ev)
+            if (!ev) HIP_TRY(e, hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate");
+        e->uploader.reset(new Worker());
     }
     for (auto& d : e->up_done) d.store(0, std::memory_order_relaxed);
     e->up_ms = 0;

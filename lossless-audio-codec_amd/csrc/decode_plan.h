@@ -1,4 +1,4 @@
-// decode_plan.h -- the host-only half of the decoder's host side: the container walk, and the plan of a decode job --
+// decode_plan.h -- the host-only half of the decoder's host side: the plan of a decode job (its streams parsed by container.h) --
 // which blocks every item needs, where its payload, PCM and image lie in the job's buffers, the lane table, the layout
 // of the tables the kernels read, and the capacities the run must provide.  Plain C++, no HIP: api_decode.cpp runs a
 // plan on the device, tests/native/sim_decode.cpp runs the same plan on the host.
@@ -8,66 +8,11 @@
 #include <string>
 #include <vector>
 
+#include "container.h"
 #include "lacx.h"
 #include "lacx_types.h"
 
 namespace lacx {
-
-inline uint32_t be32(const uint8_t* p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
-// header + block table: 4 bytes per block in version 2 (no compressed sizes, ref lac/decoder.cpp:100-104), else 8
-inline uint64_t stream_head_bytes(int version, uint32_t blocks) { return 14 + (version == 2 ? 4ull : 8ull) * blocks; }
-
-// Container header + block table: the structural rules of the reference's reader (src/codec/frame/frame_header.hpp:48-74,
-// lac/decoder.cpp:84-145) -- sync, version 3, channels, stereo mode (0 for mono), one of the four sample rates, depth,
-// reserved byte; at least one block; every block 1..16384 frames, non-final ones at least 256; non-zero compressed
-// sizes that add up to the file; at most 6 912 000 000 samples and a WAV that RIFF can hold.  NOT taken over: its cap on
-// the decoded PCM (1 GiB) and the block count that follows from it, which would refuse the 2 h stream of BASELINE
-// configs[3].  The legacy version-2 container (no compressed sizes, hence no parallelism) is read too: one lane walks it.
-// Returns LACX_OK, or LACX_E_INVALID with the message in *why.
-inline int parse_stream(const uint8_t* lac, uint64_t size, lacx_stream_info* out, const char** why) {
-    auto fail = [&](const char* msg) { return *why = msg, LACX_E_INVALID; };
-    if (!lac || !out) return fail("null argument");
-    if (size == 0) return fail("[decode-error] empty input");
-    if (size < 10 || lac[0] != 0x4C || lac[1] != 0x41 || (lac[2] != 3 && lac[2] != 2)) return fail("[decode-error] invalid frame header");
-    const int version = lac[2], ch = lac[3], sm = lac[4], bd = lac[8];
-    const uint32_t sr = ((uint32_t)lac[5] << 8) | lac[6] | ((uint32_t)lac[7] << 16);
-    const bool rate_ok = sr == 44100 || sr == 48000 || sr == 96000 || sr == 192000;
-    if ((ch != 1 && ch != 2) || sm > 2 || (ch == 1 && sm != 0) || !rate_ok || (bd != 16 && bd != 24) || lac[9] != 0)
-        return fail("[decode-error] invalid frame header");
-    if (size < 14) return fail("[decode-error] invalid block count");
-    const uint32_t nb = be32(lac + 10);
-    if (nb == 0) return fail("[decode-error] invalid block count");
-    const uint64_t entry = version >= 3 ? 8u : 4u, head = stream_head_bytes(version, nb);
-    if (size < head) return fail("[decode-error] truncated block size table");
-    uint64_t frames = 0, pay = 0;
-    for (uint32_t b = 0; b < nb; ++b) {
-        const uint32_t n = be32(lac + 14 + entry * b);
-        if (n == 0 || n > (uint32_t)kMaxBlock || (b + 1 < nb && n < 256u)) return fail("[decode-error] invalid block size");
-        frames += n;
-        if (frames > 6912000000ull) return fail("[decode-error] total samples exceed maximum");
-        if (version >= 3) {
-            const uint32_t by = be32(lac + 18 + 8ull * b);
-            // The device reader's bit positions are 32-bit and relative to the block: a block must stay below 2^29 bytes.
-            // (The reference takes any non-zero size that fits the file; a block this long -- a Rice token at k = 0 may
-            // carry a unary part of up to 2^30 bits -- is a documented deviation, see lacx.h.)
-            if (by == 0 || by >= (1u << 29)) return fail("[decode-error] invalid compressed block size");
-            pay += by;
-            if (pay > size) return fail("[decode-error] compressed block sizes exceed frame payload");
-        }
-    }
-    const uint64_t wav_bytes = frames * (uint64_t)ch * (uint64_t)(bd / 8);
-    if (36u + wav_bytes + (wav_bytes & 1u) > 0xFFFFFFFFull) return fail("[decode-error] decoded WAV data exceeds RIFF limit");
-    if (version >= 3 && head + pay != size) return fail("[decode-error] block payloads do not fill the file");
-    if (version == 2 && size - head >= (1ull << 29)) return fail("[decode-error] version-2 payload too large for the serial reader");
-    out->sample_rate = sr;
-    out->blocks = nb;
-    out->frames = frames;
-    out->channels = (uint8_t)ch;
-    out->bit_depth = (uint8_t)bd;
-    out->stereo_mode = (uint8_t)sm;
-    out->version = (uint8_t)version;
-    return LACX_OK;
-}
 
 // the decoded WAV image of a stream: 44-byte header, data, pad byte (below 2^32: parse_stream's RIFF limit)
 inline uint64_t wav_image_bytes(const lacx_stream_info& f) {
@@ -220,7 +165,7 @@ inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, i
             const uint64_t last = x.start + x.frames - 1;
             uint64_t fr = 0, by = 0;
             for (uint32_t b = 0;; ++b) {  // (the parse guarantees that the window's last frame lies in a block)
-                const uint32_t nfr = be32(x.lac + 14 + 8ull * b), nby = be32(x.lac + 18 + 8ull * b);
+                const uint32_t nfr = row_frames(x.lac, f.version, b), nby = row_bytes(x.lac, b);
                 if (fr <= x.start && x.start < fr + nfr) p.blk_first = b, p.pay_src = by, fr0 = fr;
                 if (last < fr + nfr) {
                     nb = b + 1 - p.blk_first;
@@ -330,12 +275,11 @@ inline void plan_fill_tables(const DecodePlan& plan, const BatchIn* in, const Pl
         const BatchIn& x = in[p.src];
         DecodeItem y = p.item;
         const bool v2 = y.version == 2, stereo = y.channels == 2;
-        const uint64_t entry = v2 ? 4u : 8u;
         for (uint32_t b = 0; b < y.blocks; ++b) {
             const uint32_t g = y.block0 + b;
             const uint64_t sb = p.blk_first + b;  // the block within the stream
-            frame_off[g + 1] = frame_off[g] + be32(x.lac + 14 + entry * sb);
-            byte_off[g + 1] = v2 ? byte_off[g] : byte_off[g] + be32(x.lac + 18 + 8ull * sb);
+            frame_off[g + 1] = frame_off[g] + row_frames(x.lac, y.version, sb);
+            byte_off[g + 1] = v2 ? byte_off[g] : byte_off[g] + row_bytes(x.lac, sb);
             blk_item[g] = j;
         }
         // the version-2 item's bytes count in the byte offsets as one lump at its last block

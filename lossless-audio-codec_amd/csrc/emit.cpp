@@ -466,17 +466,4 @@ std::string emit_blocks(const StreamParams& sp, const int32_t* left, const int32
     return std::string();
 }
 
-void write_frame_header(const StreamParams& sp, uint8_t* o) {
-    o[0] = 0x4C;
-    o[1] = 0x41;
-    o[2] = 3;
-    o[3] = sp.channels;
-    o[4] = sp.stereo_mode;
-    o[5] = (uint8_t)((sp.sample_rate >> 8) & 0xFF);
-    o[6] = (uint8_t)(sp.sample_rate & 0xFF);
-    o[7] = (uint8_t)((sp.sample_rate >> 16) & 0xFF);
-    o[8] = sp.bit_depth;
-    o[9] = 0;
-}
-
 }  // namespace lacx

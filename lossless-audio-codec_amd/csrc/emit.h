@@ -1,12 +1,13 @@
 // emit.h -- host side of the encoder: the bit-serial Rice / zero-run / bin emit that BASELINE.json's
-// north_star leaves on the host, driven by the ChannelPlan records the kernels produce, and the v3
-// container writer.
+// north_star leaves on the host, driven by the ChannelPlan records the kernels produce (the container
+// around the blocks: container.h).
 #pragma once
 #include <cstddef>
 #include <cstdint>
 #include <string>
 #include <vector>
 
+#include "container.h"  // StreamParams
 #include "lacx_types.h"
 
 namespace lacx {
@@ -17,13 +18,6 @@ namespace lacx {
 // plan is consistent with the samples; (size_t)-1 if the buffer would overflow (inconsistent plan).
 size_t emit_channel(const ChannelPlan& plan, const int32_t* a, const int32_t* b, int kind, uint32_t n,
                     uint8_t* out, size_t cap, int32_t* scratch /* n int32 */);
-
-struct StreamParams {
-    uint32_t sample_rate;
-    uint8_t bit_depth;
-    uint8_t channels;
-    uint8_t stereo_mode;  // header value: 0 for mono
-};
 
 // Bytes of one block's payload: [flag byte if per-block stereo] + the chosen channel payloads.
 uint32_t block_payload_bytes(const StreamParams& sp, const BlockPlan& bp, const ChannelPlan* slots);
@@ -64,8 +58,5 @@ private:
     struct Impl;
     Impl* impl_;
 };
-
-// 10-byte frame header (ref src/codec/frame/frame_header.hpp:25-36).
-void write_frame_header(const StreamParams& sp, uint8_t* out10);
 
 }  // namespace lacx

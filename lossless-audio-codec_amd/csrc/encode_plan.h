@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "container.h"
 #include "lacx.h"
 #include "lacx_types.h"
 
@@ -67,7 +68,7 @@ inline uint64_t pinned_reservation(uint64_t frames, int channels, int bit_depth,
     return frames * (uint64_t)channels * ((unsigned)bit_depth / 8u) * 5u / 4u + (uint64_t)nb * 64u + 4096u;
 }
 // room in front of the payload for the container header + block table, so that a whole .lac is handed out without a copy
-inline uint64_t prefix_bytes(uint32_t nb) { return (14ull + 8ull * nb + 4095ull) & ~4095ull; }
+inline uint64_t prefix_bytes(uint32_t nb) { return (stream_head_bytes(nb) + 4095ull) & ~4095ull; }
 // Stream indices that take part in the fused emit: all but those of a final block of <= 4096 frames in per-block stereo
 // mode, which may be encoded both ways and compared afterwards (ref lac/encoder.cpp:336-340).
 inline uint32_t fuse_items_of(uint64_t frames, uint32_t nb, int channels, int stereo_mode) {

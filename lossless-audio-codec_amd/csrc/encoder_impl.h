@@ -67,14 +67,13 @@ struct Knobs : PlanKnobs {
     LaunchTuning tune;             // LACX_PERSISTENT_GRID, LACX_PACK_NAP, LACX_PACK_GRID
 };
 
-// One persistent host thread per encoder that performs the host-to-device copies of an encode whose input starts in host
-// memory.  hipMemcpyAsync from pageable memory returns only when the copy is (all but) done, so issued from the calling
-// thread every chunk's upload stands between that thread and the next chunk's kernel launches; issued from here, the
-// calling thread enqueues chunk c's kernels the moment chunk c's bytes are on their way, while chunk c + 1 is uploading.
-class Uploader {
+// One persistent host thread with a single job slot.  post(job) hands it a job, wait() returns once the posted job has
+// finished, the destructor joins; posting while a job is pending is the caller's error.  The encoder's uploader and the
+// fan-out's lanes (api_fanout.cpp) are Workers.
+class Worker {
 public:
-    Uploader() : th_([this] { loop(); }) {}
-    ~Uploader() {
+    Worker() : th_([this] { loop(); }) {}
+    ~Worker() {
         {
             std::lock_guard<std::mutex> lock(mu_);
             quit_ = true;
@@ -221,8 +220,12 @@ struct lacx_encoder {
     uint32_t* d_range_cnt = nullptr;        // device, inside zero_region
     unsigned long long* d_range_end = nullptr;
     std::unique_ptr<EmitPool> pool;
-    // host-resident input: the uploader thread, its stream, one event per pipeline chunk, and the hand-over words
-    std::unique_ptr<Uploader> uploader;
+    // Host-resident input: the uploader thread, its stream, one event per pipeline chunk, and the hand-over words.  The
+    // thread performs the host-to-device copies: hipMemcpyAsync from pageable memory returns only when the copy is (all
+    // but) done, so issued from the calling thread every chunk's upload stands between that thread and the next chunk's
+    // kernel launches; issued from here, the calling thread enqueues chunk c's kernels the moment chunk c's bytes are on
+    // their way, while chunk c + 1 is uploading.
+    std::unique_ptr<Worker> uploader;
     hipStream_t up_stream = nullptr;
     hipEvent_t up_ev[kMaxChunks] = {};
     std::atomic<int> up_done[kMaxChunks] = {};  // 1: the chunk's copy has been issued and its event recorded; -1: failed
@@ -268,7 +271,6 @@ int check_sample_range(lacx_encoder* e, uint32_t nb);
 void reset_device_timing(lacx_encoder* e);
 int analyze_on_device(lacx_encoder* e, const int32_t* d_left, const int32_t* d_right, uint64_t frames, int channels, int stereo_mode, int bit_depth, hipStream_t st);
 StreamParams stream_params(const lacx_config& c, int channels);
-void put32(uint8_t* p, uint32_t v);
 uint64_t payload_upper_bound(uint64_t frames, int channels, uint32_t nb);
 int encode_pipelined(lacx_encoder* e, const int32_t* d_left, const int32_t* d_right, const int32_t* h_left, const int32_t* h_right, uint64_t frames, hipStream_t user_stream, uint64_t head, uint8_t** buf_out, uint64_t* payload_size, std::vector<uint64_t>& offsets);
 int encode_device_begin(lacx_encoder* e, const int32_t* d_left, const int32_t* d_right, uint64_t frames, hipStream_t user_stream, int layout = 0, int layout_channels = 0, const HostSrc* hs = nullptr);
@@ -281,7 +283,6 @@ int upload(lacx_encoder* e, const int32_t* left, const int32_t* right, uint64_t 
 int prepare(lacx_encoder* e, const void* left, uint64_t frames);
 int encode_batch(lacx_encoder* e, const lacx_batch_item* items, uint32_t n, hipStream_t user_stream, lacx_batch_out* out,
                  const uint64_t* exact_caps = nullptr);
-int fill_table(lacx_encoder* e, uint8_t* buf, uint32_t nb, const std::vector<uint64_t>& offsets);
 // api_encode.cpp: `frames` frames of host PCM (layout 0: planar int32 in hs.p0 / hs.p1; 1 / 2: the WAV data chunk) on e's
 // device; the results are views into e's buffers (valid until its next call)
 int encode_host_shard_view(lacx_encoder* e, const HostSrc& hs, int layout, int channels, uint64_t frames, const uint8_t** payload,

@@ -97,6 +97,8 @@ STREAMS = [
     (16384 + 300, 2, 16, 48000, 2, "silence", "identical"),
     (16384 * 2, 2, 24, 48000, 2, "sparse", "half_silent"),
     (16384 * 2 + 9, 2, 16, 96000, 2, "near_silence", "independent"),
+    (16384 * 2 + 77, 2, 16, 48000, 2, "mixed", "wide"),  # three blocks, the last one short
+    (300, 1, 24, 96000, 0, "music", "wide"),  # one block: the smallest head
 ]
 
 

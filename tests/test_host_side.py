@@ -73,6 +73,20 @@ def test_assemble_matches_single_stream(pkg, oracle):
         bounds = [0] + cuts + [nb]
         shards = [(payload[offs[a]:offs[b]], table[a:b]) for a, b in zip(bounds[:-1], bounds[1:])]
         assert pkg.lacx.assemble(48000, 16, 2, 2, shards) == whole
+    # a shard table with a row of no bytes: LACX_E_RUNTIME and no output
+    import ctypes as C
+
+    bad = table.copy()
+    bad[nb - 2, 1] = 0
+    cfg = pkg.lacx.Config(48000, 16, 2, 1, 1, -1, 0, 0)
+    pays = (C.c_char_p * 2)(payload[:offs[2]], payload[offs[2]:])
+    sizes = (C.c_uint64 * 2)(offs[2], len(payload) - offs[2])
+    tabs_np = [np.ascontiguousarray(bad[:2]), np.ascontiguousarray(bad[2:])]
+    tabs = (C.POINTER(C.c_uint32) * 2)(*[t.ctypes.data_as(C.POINTER(C.c_uint32)) for t in tabs_np])
+    out, size = C.POINTER(C.c_uint8)(), C.c_uint64(0)
+    rc = pkg.lacx.lib().lacx_assemble(C.byref(cfg), 2, 2, C.cast(pays, C.POINTER(C.POINTER(C.c_uint8))), sizes, tabs,
+                                      (C.c_uint32 * 2)(2, nb - 2), C.byref(out), C.byref(size))
+    assert rc == pkg.lacx.E_RUNTIME and not out and size.value == 0
 
 
 def _build_mirror_test():
