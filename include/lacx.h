@@ -34,6 +34,10 @@
  *   lacx_decoder_verify_batch_device,
  *   lacx_decoder_verify_wav <- the roundtrip comparison of `lac_cli selftest` (ref src/main.cpp:803-909) and of an
  *                             archive's "decode it again and compare" step: streams against their source PCM, on the device
+ *   lacx_decoder_digest_batch_device,
+ *   lacx_decoder_digest_pcm_batch_device,
+ *   lacx_crc32_combine      <- the check the container has no field for (the reference's format carries no checksum of its
+ *                             audio): CRC-32 of what streams decode to and of source PCM, made on the device
  *
  * All analysis (and the decode) runs in hand-written HIP kernels on a gfx950 device; there is no CPU fallback: every
  * call that needs the device fails with LACX_E_DEVICE when none is usable.
@@ -137,7 +141,7 @@ void lacx_get_timing(const lacx_encoder* enc, lacx_timing* out);
 
 /* sizeof() of a public struct as this library was built, by name without the prefix ("config", "channel_plan",
  * "block_plan", "timing", "pcm", "batch_item", "batch_out", "wav_info", "fanout_shard", "fanout_out", "fanout_stats",
- * "stream_info", "span", "decode_item", "window_item", "verify_item", "verify_result"); 0 for an unknown name.  A binding that declares the structs itself (ctypes, cgo, JNI) checks its layout
+ * "stream_info", "span", "decode_item", "window_item", "verify_item", "verify_result", "digest", "digest_source"); 0 for an unknown name.  A binding that declares the structs itself (ctypes, cgo, JNI) checks its layout
  * against this before the first call that fills one. */
 uint32_t lacx_sizeof(const char* struct_name);
 
@@ -504,6 +508,55 @@ int lacx_decoder_verify_batch_device(lacx_decoder* dec, const lacx_verify_item* 
                                      int* item_rc, lacx_verify_result* results, float* device_ms);
 int lacx_decoder_verify_wav(lacx_decoder* dec, const uint8_t* lac, uint64_t size, const uint8_t* wav, uint64_t wav_size,
                             lacx_verify_result* result, float* device_ms);
+
+/* Digests: what does a .lac decode to, without the source and without moving the PCM?  The stream is decoded into the
+ * decoder's own buffers as for a verification, and the bytes its WAV data chunk would have -- interleaved little-endian,
+ * bit_depth / 8 per sample -- are checksummed where they lie; the same kernel checksums device-resident source PCM in any
+ * lacx_pcm layout, so that a pipeline can record the digest of what it hands to the encoder and later check the .lac alone
+ * against that record.  The checksum is the standard CRC-32 (zlib, ISO-HDLC: reflected polynomial 0xEDB88320, init and
+ * final xor 0xFFFFFFFF): data_crc32 is zlib.crc32 of the data chunk, wav_crc32 that of the whole file `lac_cli decode` /
+ * lacx_decoder_decode_wav writes (canonical 44-byte header, data, pad byte), made on the host from data_crc32 with
+ * lacx_crc32_combine.  CRC-32 is linear, so every thread digests four frames and the pieces are added up in any order;
+ * no PCM crosses PCIe towards the host, only 8 bytes per item.
+ * lacx_decoder_digest_batch_device: many streams as one device job, versions 3 and 2.  Per-item outcome, return code,
+ * lacx_decoder_item_error, device-less behaviour, n = 0 / null arrays and `stream` exactly as
+ * lacx_decoder_decode_batch_device.  An item that does not parse or does not decode gets the decode's own code and
+ * message and a zeroed digest.
+ * lacx_decoder_digest_pcm_batch_device: device-resident PCM on the decoder's device; the same layouts, alignments and
+ * bounds as the verify form's sources (nothing outside the source's bytes is read), the same per-item outcome.  Checked
+ * per item on the host before any device call, each LACX_E_INVALID: "unknown source layout", "unsupported channel count",
+ * "source arrays missing", "source has no frames", "source frame count out of range" (2^56 and more), "unsupported sample
+ * rate: R", "unsupported bit depth: B", "source layout does not match the stream's bit depth" (the verify form's text: an interleaved integer layout and
+ * planar int16 fix the depth), "source arrays are not 4-byte aligned", "source arrays are not 2-byte aligned" (planar
+ * int16).  Found on the device, LACX_E_INVALID with the encoder's texts (all of left first, then right, the lowest index):
+ * a planar int32 sample outside the depth, or a float32 whose product is an integer outside it, "<left|right> sample at index I
+ * is outside the configured PCM bit depth"; any other float32 that is no sample of the depth (see LACX_PCM_PLANAR_F32)
+ * "<left|right> sample at index I is not an exact B-bit PCM value".  A failed item gets a zeroed digest.
+ * out (n entries; nullable).  device_ms (nullable): kernel time (the decode, where there is one, and the digest).
+ * lacx_crc32_combine: host only, no device: crc32(A || B) from crc32(A), crc32(B) and the length of B (zlib's
+ * crc32_combine). */
+typedef struct lacx_digest {          /* 32 bytes */
+    uint32_t data_crc32;              /* CRC-32 of the WAV data chunk's bytes, pad byte excluded */
+    uint32_t wav_crc32;               /* CRC-32 of the whole WAV file image (44-byte header + data + pad); 0 when wav_valid == 0 */
+    uint64_t frames;
+    uint64_t data_bytes;              /* frames * channels * bit_depth / 8 */
+    uint32_t sample_rate;
+    uint8_t channels, bit_depth;
+    uint8_t wav_valid;                /* 0: the image would break the RIFF limit (36 + data + pad < 2^32): a source only */
+    uint8_t reserved;
+} lacx_digest;
+typedef struct lacx_digest_source {   /* 40 bytes */
+    lacx_pcm pcm;                     /* device-resident source, any LACX_PCM_* layout */
+    uint64_t frames;
+    uint32_t sample_rate;             /* 44100 / 48000 / 96000 / 192000 */
+    uint8_t bit_depth;                /* 16 / 24 */
+    uint8_t reserved[3];
+} lacx_digest_source;
+int lacx_decoder_digest_batch_device(lacx_decoder* dec, const lacx_span* lacs, uint32_t n, void* stream, int* item_rc,
+                                     lacx_digest* out, float* device_ms);
+int lacx_decoder_digest_pcm_batch_device(lacx_decoder* dec, const lacx_digest_source* src, uint32_t n, void* stream,
+                                         int* item_rc, lacx_digest* out, float* device_ms);
+uint32_t lacx_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
 
 /* Block::Encoder::encode drop-in for one channel block of n <= 16384 samples of ANY int32 value: blocks inside the 25-bit
  * mid/side domain of validated 16 / 24-bit input run on the streaming kernels, wider ones on a kernel of their own that

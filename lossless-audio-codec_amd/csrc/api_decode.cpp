@@ -1,7 +1,9 @@
 // api_decode.cpp -- the decode entry points of the C ABI: container parsing and the device decoder's host side.
+#include "crc32_core.h"
 #include "decode_plan.h"
 #include "device_buf.h"
 #include "encoder_impl.h"
+#include "import_msg.h"
 
 // (the entry points are declared extern "C" in lacx.h)
 // ---- decode -------------------------------------------------------------------------------------
@@ -120,7 +122,27 @@ struct DecodeJob {
     lacx_span* out = nullptr;            // wav form: [n] each item's image in the decoder's pinned image buffer
     lacx_verify_result* vres = nullptr;  // verify form: [n]
     float* device_ms = nullptr;
+    lacx_digest* dres = nullptr;         // digest form: [n]
 };
+
+// What the digest kernel left for an item (DigestWords::raw), as the caller's record: the init term and the final xor
+// depend on the length alone, and the image's CRC-32 follows from its parts -- header, data, pad byte.
+lacx_digest make_digest(uint32_t raw, uint64_t frames, uint32_t sample_rate, uint8_t channels, uint8_t bit_depth) {
+    lacx_digest g{};
+    g.frames = frames;
+    g.data_bytes = frames * channels * (bit_depth / 8u);
+    g.sample_rate = sample_rate;
+    g.channels = channels;
+    g.bit_depth = bit_depth;
+    g.data_crc32 = crc_finish(raw, g.data_bytes);
+    const uint64_t pad = g.data_bytes & 1u;
+    g.wav_valid = 36u + g.data_bytes + pad < (1ull << 32) ? 1 : 0;
+    if (g.wav_valid) {
+        g.wav_crc32 = crc32_combine(crc32_wav_header(channels, bit_depth, sample_rate, g.data_bytes), g.data_crc32, g.data_bytes);
+        if (pad) g.wav_crc32 = crc32_combine(g.wav_crc32, crc_finish(0u, 1), 1);  // (the raw value of a zero byte is 0)
+    }
+    return g;
+}
 
 // ---- the steps of a run (decode_batch_run) ----
 DevErr decoder_open(lacx_decoder* d, int* prev_device) {  // *prev_device: to put back, or -1
@@ -221,6 +243,10 @@ DevErr launch_and_wait(lacx_decoder* d, const DecodeJob& job, const DecodePlan& 
     if (plan.form == DecodeForm::verify)
         if (DevErr e = chk(hipMemcpyAsync(d->h_meta() + res, d->d_meta() + res, sizeof(VerifyWords) * m, hipMemcpyDeviceToHost, st), "D2H verify results"))
             return e;
+    // the digest form's whole answer: 8 bytes per item
+    if (plan.form == DecodeForm::digest)
+        if (DevErr e = chk(hipMemcpyAsync(d->h_meta() + res, d->d_meta() + res, sizeof(DigestWords) * m, hipMemcpyDeviceToHost, st), "D2H digests"))
+            return e;
     if (DevErr e = chk(hipStreamSynchronize(st), "synchronize")) return e;
     if (job.device_ms) (void)hipEventElapsedTime(job.device_ms, d->e0, d->e1);
     return DevErr{};
@@ -243,7 +269,10 @@ DevErr collect(lacx_decoder* d, const DecodeJob& job, const DecodePlan& plan, hi
             }
         }
         if (code[i] != LACX_OK) continue;
-        if (plan.form == DecodeForm::verify) {
+        if (plan.form == DecodeForm::digest) {
+            const DigestWords& w = reinterpret_cast<const DigestWords*>(d->h_meta() + plan.at.res)[j];
+            if (job.dres) job.dres[i] = make_digest(w.raw, p.info.frames, p.info.sample_rate, p.info.channels, p.info.bit_depth);
+        } else if (plan.form == DecodeForm::verify) {
             const VerifyWords& w = reinterpret_cast<const VerifyWords*>(d->h_meta() + plan.at.res)[j];
             if (w.count == 0) continue;
             lacx_verify_result r{};
@@ -282,6 +311,7 @@ DevErr collect(lacx_decoder* d, const DecodeJob& job, const DecodePlan& plan, hi
 int decode_batch_run(lacx_decoder* d, const DecodeJob& job, std::vector<int>& code, std::vector<std::string>& err) {
     if (job.device_ms) *job.device_ms = 0.f;
     if (job.vres) std::memset(job.vres, 0, sizeof(lacx_verify_result) * job.n);
+    if (job.dres) std::memset(job.dres, 0, sizeof(lacx_digest) * job.n);
     // LACX_DECODE_BATCH_PAD=1 (tuning knob, read per call): every item's blocks start a new wave
     const char* pad_env = std::getenv("LACX_DECODE_BATCH_PAD");
     DecodePlan plan;
@@ -292,7 +322,7 @@ int decode_batch_run(lacx_decoder* d, const DecodeJob& job, std::vector<int>& co
         int prev_device = -1;
         DevErr e = decoder_open(d, &prev_device);
         // (d->stream: created by decoder_open)
-        hipStream_t st = job.form == DecodeForm::device || (job.form == DecodeForm::verify && !plan.host_src) ? job.stream : d->stream;
+        hipStream_t st = job.form == DecodeForm::device || job.form == DecodeForm::digest || (job.form == DecodeForm::verify && !plan.host_src) ? job.stream : d->stream;
         if (!e) e = ensure_capacities(d, plan);
         if (!e) e = upload_tables(d, job, plan, st);
         if (!e) e = upload_payload(d, job, plan, st);
@@ -473,6 +503,145 @@ int lacx_decoder_verify_wav(lacx_decoder* d, const uint8_t* lac, uint64_t size, 
     in.host_src_bytes = w.frames * w.channels * (uint64_t)(w.bit_depth / 8);
     return run_one(d, in, DecodeJob{nullptr, 1, DecodeForm::verify, kWholeStreams, nullptr, nullptr, result, device_ms});
 }
+
+int lacx_decoder_digest_batch_device(lacx_decoder* d, const lacx_span* lacs, uint32_t n, void* stream, int* item_rc, lacx_digest* out,
+                                     float* device_ms) {
+    if (!d) return decode_fail(LACX_E_INVALID, "null decoder");
+    if (!lacs || n == 0) return decode_fail(LACX_E_INVALID, "null argument or empty batch");
+    std::vector<BatchIn> in(n);
+    for (uint32_t i = 0; i < n; ++i) in[i] = BatchIn{lacs[i].data, lacs[i].size, nullptr, nullptr, 0};
+    return run_batch(d, DecodeJob{in.data(), n, DecodeForm::digest, kWholeStreams, static_cast<hipStream_t>(stream), nullptr, nullptr, device_ms, out},
+                     item_rc);
+}
+
+namespace {
+// The source form's checks of an item, in the verify form's words where it has them.
+const char* check_digest_source(const lacx_digest_source& x, std::string& text) {
+    const lacx_pcm& p = x.pcm;
+    const uintptr_t a0 = (uintptr_t)p.data0, a1 = (uintptr_t)p.data1;
+    const bool tensor = p.layout == LACX_PCM_PLANAR_I16 || p.layout == LACX_PCM_PLANAR_F32 || p.layout == LACX_PCM_INTERLEAVED_F32;
+    const bool planar = p.layout == LACX_PCM_PLANAR_I32 || p.layout == LACX_PCM_PLANAR_I16 || p.layout == LACX_PCM_PLANAR_F32;
+    if (p.layout > LACX_PCM_INTERLEAVED_I24 && !tensor) return "unknown source layout";
+    if (p.channels != 1 && p.channels != 2) return "unsupported channel count";
+    if (!p.data0 || (planar && p.channels == 2 && !p.data1)) return "source arrays missing";
+    if (x.frames == 0) return "source has no frames";
+    if (x.frames >> 56) return "source frame count out of range";
+    if (!rate_ok(x.sample_rate)) return (text = "unsupported sample rate: " + std::to_string(x.sample_rate)).c_str();
+    if (x.bit_depth != 16 && x.bit_depth != 24) return (text = "unsupported bit depth: " + std::to_string((int)x.bit_depth)).c_str();
+    if (((p.layout == LACX_PCM_INTERLEAVED_I16 || p.layout == LACX_PCM_PLANAR_I16) && x.bit_depth != 16) ||
+        (p.layout == LACX_PCM_INTERLEAVED_I24 && x.bit_depth != 24))
+        return "source layout does not match the stream's bit depth";
+    if (p.layout == LACX_PCM_PLANAR_I16) {
+        if ((a0 & 1u) || (planar && p.channels == 2 && (a1 & 1u))) return "source arrays are not 2-byte aligned";
+    } else if ((p.layout != LACX_PCM_INTERLEAVED_I24 && (a0 & 3u)) || (planar && p.channels == 2 && (a1 & 3u))) {
+        return "source arrays are not 4-byte aligned";
+    }
+    return nullptr;
+}
+
+// The source form: no stream, no decode -- the items' records and the prefix sums of their unit counts in the decoder's
+// table buffers, k_digest over them on the caller's stream, and 16 bytes per item back (the result word and the lowest
+// invalid sample's key).  Table layout: src [m] | unit_off [m + 1] | res [m] | bad [m].
+int digest_pcm_run(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, hipStream_t st, lacx_digest* out, float* device_ms,
+                   std::vector<int>& code, std::vector<std::string>& err) {
+    if (device_ms) *device_ms = 0.f;
+    if (out) std::memset(out, 0, sizeof(lacx_digest) * n);
+    code.assign(n, LACX_OK);
+    err.assign(n, std::string());
+    std::vector<uint32_t> went;  // the items that go to the device
+    for (uint32_t i = 0; i < n; ++i) {
+        std::string text;
+        if (const char* why = check_digest_source(src[i], text)) {
+            code[i] = LACX_E_INVALID;
+            err[i] = why;
+        } else {
+            went.push_back(i);
+        }
+    }
+    int rc = lacx_device_count() <= 0 ? decode_fail(LACX_E_DEVICE, "no usable HIP device") : LACX_OK;
+    const size_t m = went.size();
+    if (rc == LACX_OK && m) {
+        const size_t at_off = sizeof(DigestSource) * m, at_res = at_off + 8 * (m + 1), at_bad = at_res + sizeof(DigestWords) * m,
+                     size = at_bad + 8 * m;
+        int prev_device = -1;
+        DevErr e = decoder_open(d, &prev_device);
+        if (!e) e = buf_grow(d->tables, size, size / 8 + 256);
+        if (!e) {
+            auto* hs = reinterpret_cast<DigestSource*>(d->h_meta());
+            auto* unit_off = reinterpret_cast<unsigned long long*>(d->h_meta() + at_off);
+            unit_off[0] = 0;
+            for (size_t j = 0; j < m; ++j) {
+                const lacx_digest_source& x = src[went[j]];
+                hs[j] = DigestSource{x.pcm.data0, x.pcm.channels == 2 ? x.pcm.data1 : nullptr, x.frames, x.pcm.layout, (uint8_t)x.pcm.channels,
+                                     x.bit_depth, {0, 0}};
+                unit_off[j + 1] = unit_off[j] + (x.frames + 3u) / 4u;
+                reinterpret_cast<DigestWords*>(d->h_meta() + at_res)[j] = DigestWords{0, 0};
+                reinterpret_cast<unsigned long long*>(d->h_meta() + at_bad)[j] = kDigestClean;
+            }
+            DigestPcmArgs a;
+            a.nitems = (uint32_t)m;
+            a.total_units = unit_off[m];
+            a.unit_off = reinterpret_cast<const unsigned long long*>(d->d_meta() + at_off);
+            a.src = reinterpret_cast<const DigestSource*>(d->d_meta());
+            a.res = reinterpret_cast<DigestWords*>(d->d_meta() + at_res);
+            a.bad = reinterpret_cast<unsigned long long*>(d->d_meta() + at_bad);
+            e = chk(hipMemcpyAsync(d->d_meta(), d->h_meta(), size, hipMemcpyHostToDevice, st), "H2D digest tables");
+            if (!e) e = chk(hipEventRecord(d->e0, st), "event record");
+            if (!e) e = chk(launch_digest_pcm(a, st), "digest launch");
+            if (!e) e = chk(hipEventRecord(d->e1, st), "event record");
+            if (!e) e = chk(hipMemcpyAsync(d->h_meta() + at_res, d->d_meta() + at_res, size - at_res, hipMemcpyDeviceToHost, st), "D2H digests");
+            if (!e) e = chk(hipStreamSynchronize(st), "synchronize");
+            if (!e && device_ms) (void)hipEventElapsedTime(device_ms, d->e0, d->e1);
+        }
+        if (prev_device >= 0) (void)hipSetDevice(prev_device);
+        if (e) {
+            rc = decode_fail(LACX_E_DEVICE, std::string(e.what) + ": " + hipGetErrorString(e.e));
+        } else {
+            for (size_t j = 0; j < m; ++j) {
+                const uint32_t i = went[j];
+                const lacx_digest_source& x = src[i];
+                const unsigned long long key = reinterpret_cast<const unsigned long long*>(d->h_meta() + at_bad)[j];
+                if (key != kDigestClean) {  // the encoder's words for it (import_msg.h): all of left first, then right
+                    ImportBad b{{kImportClean, kImportClean}};
+                    b.key[key >> 63] = key & ~(1ull << 63);
+                    int ch = 0;
+                    unsigned long long index = 0;
+                    (void)import_bad_message(b, x.bit_depth, &ch, &index, err[i]);
+                    code[i] = LACX_E_INVALID;
+                    continue;
+                }
+                const uint32_t raw = reinterpret_cast<const DigestWords*>(d->h_meta() + at_res)[j].raw;
+                if (out) out[i] = make_digest(raw, x.frames, x.sample_rate, (uint8_t)x.pcm.channels, x.bit_depth);
+            }
+        }
+    }
+    if (rc != LACX_OK) {  // the whole call failed: no item was digested
+        for (uint32_t i = 0; i < n; ++i) {
+            if (code[i] != LACX_OK) continue;
+            code[i] = rc;
+            err[i] = g_decode_err;
+        }
+    }
+    return rc;
+}
+}  // namespace
+
+int lacx_decoder_digest_pcm_batch_device(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, void* stream, int* item_rc,
+                                         lacx_digest* out, float* device_ms) {
+    if (!d) return decode_fail(LACX_E_INVALID, "null decoder");
+    if (!src || n == 0) return decode_fail(LACX_E_INVALID, "null argument or empty batch");
+    std::vector<int> code;
+    std::vector<std::string> err;
+    const int rc = digest_pcm_run(d, src, n, static_cast<hipStream_t>(stream), out, device_ms, code, err);
+    if (item_rc) std::copy(code.begin(), code.end(), item_rc);
+    d->item_err = std::move(err);
+    if (rc != LACX_OK) return rc;
+    for (size_t i = 0; i < code.size(); ++i)
+        if (code[i] != LACX_OK) return decode_fail(code[i], "stream " + std::to_string(i) + ": " + d->item_err[i]);
+    return LACX_OK;
+}
+
+uint32_t lacx_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b) { return crc32_combine(crc_a, crc_b, len_b); }
 
 const char* lacx_decoder_item_error(const lacx_decoder* d, uint32_t i) {
     if (!d || i >= d->item_err.size()) return "";

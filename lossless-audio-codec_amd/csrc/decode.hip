@@ -18,6 +18,7 @@
 //                   int32 or float32 into the caller's arrays (lacx_decoder_decode_window*)
 //   k_verify        the same per-sample work, compared with the source PCM in its own layout instead of stored: a count
 //                   of differing samples and the first of them per item (lacx_decoder_verify_*; verify_core.h)
+//   (k_digest       the same per-sample work, digested instead of stored: k_digest.hip, launched from launch_decode)
 // Every launch decodes a batch of streams (items) as one job; a single stream is a batch of one.
 // The adaptive Rice parameter uses the encoder's division-free formulation (kmean / biased_k of analyze_core.h, proven
 // against Rice::adapt_k there); it assumes zigzag residuals below 2^30 like the encoder does, and a stream with a larger
@@ -439,7 +440,9 @@ hipError_t launch_decode(const DecodeArgs& a, hipStream_t stream) {
         hipLaunchKernelGGL(k_decode_serial, dim3((a.nv2 + kDecThreads - 1) / kDecThreads), dim3(kDecThreads), smem,
                            stream, a.nv2, a.v2_items, a.items, a.payload, a.frame_off, a.status, a.ms_flag);
     }
-    if (a.verify) {
+    if (a.digest) {
+        if (a.total_units) return launch_digest(a, stream);
+    } else if (a.verify) {
         if (a.total_units) {
             hipLaunchKernelGGL(k_verify, dim3((uint32_t)((a.total_units + 255u) / 256u)), dim3(256), 0, stream, a.nitems,
                                a.total_units, a.unit_off, a.items, a.verify, a.verify_res, a.frame_off, a.ms_flag, a.status);

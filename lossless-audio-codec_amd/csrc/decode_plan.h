@@ -40,13 +40,15 @@ struct BatchIn {
 // D2H copy for all).  device: the caller's device arrays, in place, on the caller's stream.  host: the decoder's own PCM
 // buffers, then, once the statuses are checked, the caller's host arrays of the items that decoded.  verify: the
 // decoder's own PCM buffers, compared there with each item's source PCM (k_verify in place of the other post passes);
-// what comes back is a result per item and, for an item that differs, LACX_E_MISMATCH.
+// what comes back is a result per item and, for an item that differs, LACX_E_MISMATCH.  digest: the decoder's own PCM
+// buffers like verify, digested there (k_digest in place of the other post passes); what comes back is one result word
+// per item (DigestWords).
 // The device and host forms also come as window jobs (sample_type = LACX_SAMPLE_I32 / _F32 instead of kWholeStreams,
 // DESIGN §6b): a version-3 item then covers just the blocks that overlap its window -- only their bytes are uploaded,
 // they decode whole into the decoder's PCM buffers (scratch) and are all checked, and k_window_out writes the window's
 // frames out; a version-2 item (no compressed sizes) decodes in full and is then windowed.  The host form's windows go
 // through the decoder's image buffer, copied to the caller once the statuses are checked.
-enum class DecodeForm { wav, device, host, verify };
+enum class DecodeForm { wav, device, host, verify, digest };
 constexpr int kWholeStreams = -1;
 
 // One item that goes to the device (j counts these; the items that failed their checks are not among them).
@@ -64,7 +66,8 @@ struct PlanItem {
 };
 
 // The tables the kernels read, one upload: items | byte_off [T + 1] | frame_off [T + 1] | unit_off [m + 1] | blk_item [T]
-// | lane_blk | v2_items, then for a window job | win [m], for the verify form | ver [m] | res [m] (byte offsets)
+// | lane_blk | v2_items, then for a window job | win [m], for the verify form | ver [m] | res [m], for the digest form
+// | res [m] at `win` (byte offsets)
 struct TableLayout {
     size_t items, byte_off, frame_off, unit_off, blk_item, lane_blk, v2_items, win, res, size;
 };
@@ -138,7 +141,8 @@ inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, i
     plan = DecodePlan{};
     plan.form = form;
     plan.sample_type = sample_type;
-    const bool window = plan.window(), own_pcm = plan.own_pcm(), wav = form == DecodeForm::wav, verify = form == DecodeForm::verify;
+    const bool window = plan.window(), own_pcm = plan.own_pcm(), wav = form == DecodeForm::wav, verify = form == DecodeForm::verify,
+               digest = form == DecodeForm::digest;
     code.assign(n, LACX_OK);
     err.assign(n, std::string());
     plan.items.reserve(n);
@@ -149,7 +153,7 @@ inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, i
         lacx_stream_info& f = p.info;
         const char* why = nullptr;
         int c = parse_stream(x.lac, x.size, &f, &why);
-        if (c == LACX_OK && (why = window ? check_window(x, f) : verify ? check_source(x, f) : wav ? nullptr : check_arrays(x, f)))
+        if (c == LACX_OK && (why = window ? check_window(x, f) : verify ? check_source(x, f) : wav || digest ? nullptr : check_arrays(x, f)))
             c = LACX_E_INVALID;
         if (c != LACX_OK) {
             code[i] = c;
@@ -188,7 +192,7 @@ inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, i
             p.image_size = wav_image_bytes(f);
             plan.image_total += up16(p.image_size);
         }
-        if (window || verify || wav) plan.total_units += (frames + 3u) / 4u;  // the post passes' units of 4 frames
+        if (window || verify || wav || digest) plan.total_units += (frames + 3u) / 4u;  // the post passes' units of 4 frames
         DecodeItem& y = p.item;
         y.frame0 = plan.total_frames;
         y.frames = frames;
@@ -237,8 +241,8 @@ inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, i
     at.v2_items = at.lane_blk + 4 * plan.lane_blk.size();
     const size_t end = at.v2_items + 4 * plan.v2_items.size();
     at.win = up16(end);
-    at.res = at.win + sizeof(VerifySource) * m;
-    at.size = verify ? at.res + sizeof(VerifyWords) * m : window ? at.win + sizeof(WindowOut) * m : end;
+    at.res = digest ? at.win : at.win + sizeof(VerifySource) * m;
+    at.size = verify ? at.res + sizeof(VerifyWords) * m : digest ? at.res + sizeof(DigestWords) * m : window ? at.win + sizeof(WindowOut) * m : end;
     plan.need.payload = (plan.host_src ? plan.src_at + plan.host_src_bytes : plan.total_pay) + kDecodeTailPad;
     plan.need.blocks = T;
     plan.need.pcm_frames = own_pcm ? plan.pcm_total : 0;
@@ -257,7 +261,7 @@ struct PlanBases {
 };
 
 // The plan's offsets as pointers: fills the tables (plan.at, plan.need.tables bytes at h), the verify form's initial result
-// words among them.
+// words (and the digest form's) among them.
 inline void plan_fill_tables(const DecodePlan& plan, const BatchIn* in, const PlanBases& base, uint8_t* h) {
     const TableLayout& at = plan.at;
     const uint32_t m = (uint32_t)plan.items.size();
@@ -300,6 +304,7 @@ inline void plan_fill_tables(const DecodePlan& plan, const BatchIn* in, const Pl
             ver[j] = VerifySource{plan.host_src ? base.payload + plan.src_at : x.pcm.data0, x.pcm.data1, x.pcm.layout, 0};
             res[j] = VerifyWords{0, ~0ull, 0, 0, 0, 0};
         }
+        if (plan.form == DecodeForm::digest) reinterpret_cast<DigestWords*>(h + at.res)[j] = DigestWords{0, 0};
     }
     if (!plan.lane_blk.empty()) std::memcpy(h + at.lane_blk, plan.lane_blk.data(), 4 * plan.lane_blk.size());
     if (!plan.v2_items.empty()) std::memcpy(h + at.v2_items, plan.v2_items.data(), 4 * plan.v2_items.size());
@@ -331,6 +336,7 @@ inline DecodeArgs plan_args(const DecodePlan& plan, const uint8_t* tables, const
         a.verify = reinterpret_cast<const VerifySource*>(tables + at.win);
         a.verify_res = reinterpret_cast<VerifyWords*>(const_cast<uint8_t*>(tables) + at.res);
     }
+    if (plan.form == DecodeForm::digest) a.digest = reinterpret_cast<DigestWords*>(const_cast<uint8_t*>(tables) + at.res);
     return a;
 }
 

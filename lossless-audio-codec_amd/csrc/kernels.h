@@ -1,5 +1,5 @@
 // kernels.h -- host-visible interface of the kernel translation units (k_front.hip, k_analyze.hip, k_emit.hip,
-// decode.hip, wide.hip, k_import.hip).
+// decode.hip, k_digest.hip, wide.hip, k_import.hip).
 #pragma once
 #include <cstdlib>
 #include <hip/hip_runtime_api.h>
@@ -176,6 +176,11 @@ hipError_t launch_stream_out(const LaunchSet& ls, const DeviceWorkspace& ws, uin
 // bytes (the bit reader's bounded look-ahead past the last block, see BitIn).
 // DecodeItem, WindowOut, DecodeArgs: lacx_types.h (the host-only plan, decode_plan.h, fills them)
 hipError_t launch_decode(const DecodeArgs& args, hipStream_t stream);
+
+// The digest form (k_digest.hip): k_digest over the units of a decode job's items, behind its decode kernels
+// (launch_decode calls it for a job with DecodeArgs::digest), and the same kernel over device-resident source PCM.
+hipError_t launch_digest(const DecodeArgs& args, hipStream_t stream);
+hipError_t launch_digest_pcm(const DigestPcmArgs& args, hipStream_t stream);
 
 // Block::Encoder::encode's analysis for one block of arbitrary int32 samples (wide.hip): d_res = scratch for the eleven
 // candidate residuals ([11][kMaxBlock] int32), d_plan receives the plan.

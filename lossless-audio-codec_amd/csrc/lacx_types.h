@@ -110,6 +110,29 @@ struct VerifyWords {
     uint32_t pad;
 };
 
+// Digest form of the decoder (digest_core.h, k_digest.hip): what the kernel leaves per item, and -- the source form, a job
+// without a decode -- the device-resident PCM that is digested in its own layout.
+struct DigestWords {
+    uint32_t raw;  // XOR of every unit's raw CRC-32 value shifted to the item's end (zeroed per call)
+    uint32_t pad;
+};
+struct DigestSource {
+    const void* data0;          // as VerifySource
+    const void* data1;
+    unsigned long long frames;  // >= 1
+    uint32_t layout;
+    uint8_t channels, bit_depth, pad[2];
+};
+constexpr unsigned long long kDigestClean = ~0ull;  // DigestPcmArgs::bad: no invalid sample (digest_bad_key, digest_core.h)
+struct DigestPcmArgs {
+    uint32_t nitems = 0;
+    unsigned long long total_units = 0;
+    const unsigned long long* unit_off = nullptr;  // [nitems + 1] prefix sums of ceil(frames / 4)
+    const DigestSource* src = nullptr;
+    DigestWords* res = nullptr;                    // [nitems], zero on entry
+    unsigned long long* bad = nullptr;             // [nitems] lowest digest_bad_key per item, all ones on entry
+};
+
 // The decoder's job records (decode.hip; filled by the host-only plan, decode_plan.h).  One job decodes a batch of streams
 // (items), its blocks numbered globally: see launch_decode (kernels.h).
 struct DecodeItem {
@@ -157,5 +180,8 @@ struct DecodeArgs {
     // verify[j] is the source PCM of item j, verify_res[j] its result words (count 0 and key all ones on entry)
     const VerifySource* verify = nullptr;
     VerifyWords* verify_res = nullptr;
+    // digest form (non-null: k_digest over the units of unit_off in place of the other post passes): digest[j] is item
+    // j's result word (zero on entry)
+    DigestWords* digest = nullptr;
 };
 }  // namespace lacx

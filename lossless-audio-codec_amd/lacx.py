@@ -111,6 +111,7 @@ EXPORTS = (
     "lacx_decoder_decode_wav_batch", "lacx_decoder_decode_wav_batch_view", "lacx_decoder_decode_batch_device",
     "lacx_decoder_item_error", "lacx_decoder_decode_window_batch_device", "lacx_decoder_decode_window",
     "lacx_decoder_verify_batch_device", "lacx_decoder_verify_wav",
+    "lacx_decoder_digest_batch_device", "lacx_decoder_digest_pcm_batch_device", "lacx_crc32_combine",
 )
 
 
@@ -176,6 +177,12 @@ def lib():
                                                        C.POINTER(C.c_int), C.POINTER(VerifyResult), C.POINTER(C.c_float)]
         L.lacx_decoder_verify_wav.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), C.c_uint64, C.POINTER(C.c_uint8), C.c_uint64,
                                               C.POINTER(VerifyResult), C.POINTER(C.c_float)]
+        L.lacx_decoder_digest_batch_device.argtypes = [C.c_void_p, C.POINTER(Span), C.c_uint32, C.c_void_p, C.POINTER(C.c_int),
+                                                       C.POINTER(Digest), C.POINTER(C.c_float)]
+        L.lacx_decoder_digest_pcm_batch_device.argtypes = [C.c_void_p, C.POINTER(DigestSource), C.c_uint32, C.c_void_p,
+                                                           C.POINTER(C.c_int), C.POINTER(Digest), C.POINTER(C.c_float)]
+        L.lacx_crc32_combine.restype = C.c_uint32
+        L.lacx_crc32_combine.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64]
         L.lacx_decoder_item_error.restype = C.c_char_p
         L.lacx_decoder_item_error.argtypes = [C.c_void_p, C.c_uint32]
         # the structs declared in this file against the library's own sizeof(): a layout that has drifted from
@@ -197,7 +204,7 @@ def abi_structs() -> dict:
             "batch_item": BatchItem, "batch_out": BatchOut, "wav_info": WavInfo, "fanout_shard": FanoutShard,
             "fanout_out": FanoutOut, "fanout_stats": FanoutStats, "stream_info": StreamInfo, "span": Span,
             "decode_item": DecodeItem, "window_item": WindowItem, "verify_item": VerifyItem,
-            "verify_result": VerifyResult}
+            "verify_result": VerifyResult, "digest": Digest, "digest_source": DigestSource}
 
 
 def device_count() -> int:
@@ -725,6 +732,25 @@ class VerifyResult(C.Structure):
                 ("reserved", C.c_uint8 * 3), ("decoded", C.c_int32), ("source", C.c_int32)]
 
 
+class Digest(C.Structure):
+    """CRC-32 (zlib.crc32) of what a stream decodes to, or of source PCM: data_crc32 over the bytes of the WAV data chunk
+    (interleaved little-endian, bit_depth / 8 per sample), wav_crc32 over the whole canonical WAV file image (0 with
+    wav_valid == 0: an image beyond the RIFF limit), and the format those bytes have."""
+    _fields_ = [("data_crc32", C.c_uint32), ("wav_crc32", C.c_uint32), ("frames", C.c_uint64), ("data_bytes", C.c_uint64),
+                ("sample_rate", C.c_uint32), ("channels", C.c_uint8), ("bit_depth", C.c_uint8), ("wav_valid", C.c_uint8),
+                ("reserved", C.c_uint8)]
+
+
+class DigestSource(C.Structure):
+    _fields_ = [("pcm", Pcm), ("frames", C.c_uint64), ("sample_rate", C.c_uint32), ("bit_depth", C.c_uint8),
+                ("reserved", C.c_uint8 * 3)]
+
+
+def crc32_combine(crc_a: int, crc_b: int, len_b: int) -> int:
+    """zlib's crc32_combine: crc32(A + B) from crc32(A), crc32(B) and len(B).  Host only."""
+    return int(lib().lacx_crc32_combine(C.c_uint32(crc_a), C.c_uint32(crc_b), C.c_uint64(len_b)))
+
+
 SAMPLE_I32, SAMPLE_F32 = 0, 1  # LACX_SAMPLE_*
 
 
@@ -1020,6 +1046,46 @@ class Decoder:
         rcs = rcs_seen[0]
         results = [res[i] if rcs[i] in (OK, E_MISMATCH) else None for i in range(n)]
         return self._raise_batch(rc, errors, results)
+
+    def digest_batch(self, lacs, stream: int = 0) -> list:
+        """Many .lac streams decoded and digested on the device as one job: each item's Digest (CRC-32 of the WAV data
+        chunk and of the whole WAV image it decodes to, and its format); only a few bytes per item come back.  The work
+        goes on `stream` (a raw hipStream_t, 0 = the null stream); kernel milliseconds in `last_ms`.  An item that does
+        not decode raises BatchDecodeError once the others are done (results[i] is None there)."""
+        bufs = [np.frombuffer(x, dtype=np.uint8) for x in lacs]
+        n = len(bufs)
+        spans = (Span * max(1, n))(*[Span(b.ctypes.data_as(C.POINTER(C.c_uint8)), b.size) for b in bufs])
+        out = (Digest * max(1, n))()
+        rc, errors = self._batch(n, lambda rcs, ms: lib().lacx_decoder_digest_batch_device(
+            self._h, spans, C.c_uint32(n), C.c_void_p(stream), rcs, out, ms))
+        return self._raise_batch(rc, errors, [None if i in errors else out[i] for i in range(n)])
+
+    def digest(self, lac) -> Digest:
+        """digest_batch of one stream; RuntimeError with the decode's own message where it does not decode."""
+        try:
+            return self.digest_batch([lac])[0]
+        except BatchDecodeError as e:
+            raise RuntimeError(e.errors[0]) from None
+
+    def digest_pcm_batch(self, sources, stream: int = 0) -> list:
+        """Device-resident PCM digested where it lies, as one job: sources[i] = (pcm, sample_rate, bit_depth) with pcm a
+        device tensor (described by pcm_of at that depth) or a tuple (data0_ptr, data1_ptr or None, layout, channels,
+        frames).  Returns each item's Digest: what digest_batch gives for a stream encoded from that source.  An item with
+        a sample that is no sample of the depth, or that fails the host's checks, raises BatchDecodeError once the others
+        are done."""
+        n = len(sources)
+        items = (DigestSource * max(1, n))()
+        for it, (pcm, rate, depth) in zip(items, sources):
+            if isinstance(pcm, (tuple, list)):
+                d0, d1, layout, channels, frames = pcm
+                it.pcm = Pcm(d0, d1, layout, channels)
+            else:
+                it.pcm, frames = pcm_of(pcm, depth)
+            it.frames, it.sample_rate, it.bit_depth = frames, rate, depth
+        out = (Digest * max(1, n))()
+        rc, errors = self._batch(n, lambda rcs, ms: lib().lacx_decoder_digest_pcm_batch_device(
+            self._h, items, C.c_uint32(n), C.c_void_p(stream), rcs, out, ms))
+        return self._raise_batch(rc, errors, [None if i in errors else out[i] for i in range(n)])
 
     def verify_wav(self, lac, wav) -> VerifyResult:
         """A .lac against the WAV file image it was made from (both in host memory): the image's data chunk goes to the

@@ -13,6 +13,9 @@
 // of the source instead of the input file).  selftest (ref :803-909): the reference's
 // four format pairs, signal and frame count, LR / MS / auto / mono encodes through lacx_encode, each verified on the
 // device against its source, the header fields read back through lacx_stream_parse, the reference's output lines.
+// digest (no counterpart in the reference's tool; `flac -t` without the source, and the STREAMINFO MD5's role): the CRC-32
+// of what every .lac decodes to and of every WAV's data chunk, made on the device (lacx_decoder_digest_batch_device /
+// lacx_decoder_digest_pcm_batch_device): a .lac and the WAV it was made from print the same fields.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -29,6 +32,8 @@
 #include <thread>
 #include <vector>
 
+#include <hip/hip_runtime_api.h>
+
 #include "lacx.h"
 
 namespace {
@@ -38,6 +43,7 @@ void usage() {
                  "[--debug-stereo-est] [--debug-zr] [--debug-partitions] [--no-partitioning] [--verify] [--verify-against=other.wav]\n"
                  "  lacx_cli decode input.lac output.wav [--threads=N] [--debug-threads]\n"
                  "  lacx_cli verify input.lac input.wav\n"
+                 "  lacx_cli digest FILE...   (.lac and .wav files, told apart by content)\n"
                  "  lacx_cli selftest\n";
 }
 
@@ -198,6 +204,92 @@ int verify_command(char** argv) {
     return 0;
 }
 
+// lacx_cli digest FILE...: one line per file that gave a digest, in argument order; the streams are one device job, the
+// WAV files' data chunks, uploaded as they are, another.  Exit 0 when every file gave a digest; otherwise the failed
+// files' messages on stderr and exit 1.
+int digest_command(int argc, char** argv) {
+    const int n = argc - 2;
+    std::vector<std::vector<uint8_t>> data(n);
+    std::vector<std::string> error(n);
+    std::vector<lacx_digest> digest(n, lacx_digest{});
+    std::vector<int> lacs, wavs;  // indices of the files of each kind that go to the device
+    std::vector<lacx_wav_info> winfo(n, lacx_wav_info{});
+    for (int i = 0; i < n; ++i) {
+        if (!load_file(argv[2 + i], data[i])) {
+            error[i] = "Failed to read file";
+        } else if (data[i].size() >= 4 && std::memcmp(data[i].data(), "RIFF", 4) == 0) {
+            if (lacx_wav_parse(data[i].data(), data[i].size(), &winfo[i]) != LACX_OK) error[i] = "Failed to read WAV";
+            else wavs.push_back(i);
+        } else {
+            lacs.push_back(i);
+        }
+    }
+    lacx_decoder* dec = nullptr;
+    if (lacx_decoder_create(-1, &dec) != LACX_OK) {
+        std::cerr << "Error: lacx_decoder_create failed\n";
+        return 1;
+    }
+    // the outcome of a batch call for its files: the items' digests and messages
+    auto collect = [&](const std::vector<int>& which, int rc, const std::vector<int>& item_rc, const std::vector<lacx_digest>& out) {
+        for (size_t k = 0; k < which.size(); ++k) {
+            if (item_rc[k] == LACX_OK) digest[which[k]] = out[k];
+            else error[which[k]] = rc == LACX_E_DEVICE ? lacx_decode_last_error() : lacx_decoder_item_error(dec, (uint32_t)k);
+        }
+    };
+    if (!lacs.empty()) {
+        std::vector<lacx_span> spans;
+        for (int i : lacs) spans.push_back(lacx_span{data[i].data(), data[i].size()});
+        std::vector<int> item_rc(lacs.size(), LACX_OK);
+        std::vector<lacx_digest> out(lacs.size());
+        const int rc = lacx_decoder_digest_batch_device(dec, spans.data(), (uint32_t)spans.size(), nullptr, item_rc.data(), out.data(), nullptr);
+        collect(lacs, rc, item_rc, out);
+    }
+    if (!wavs.empty()) {
+        std::vector<lacx_digest_source> src;
+        std::vector<void*> dev;
+        std::vector<int> sent;
+        for (int i : wavs) {
+            const lacx_wav_info& w = winfo[i];
+            const uint64_t bytes = w.frames * w.channels * (uint64_t)(w.bit_depth / 8);
+            void* p = nullptr;
+            if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess ||
+                hipMemcpy(p, data[i].data() + w.data_offset, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+                error[i] = "Failed to upload WAV data to the device";
+                if (p) (void)hipFree(p);
+                continue;
+            }
+            lacx_digest_source s{};
+            s.pcm = lacx_pcm{p, nullptr, w.bit_depth == 16 ? LACX_PCM_INTERLEAVED_I16 : LACX_PCM_INTERLEAVED_I24, w.channels};
+            s.frames = w.frames;
+            s.sample_rate = w.sample_rate;
+            s.bit_depth = (uint8_t)w.bit_depth;
+            src.push_back(s), dev.push_back(p), sent.push_back(i);
+        }
+        if (!src.empty()) {
+            std::vector<int> item_rc(src.size(), LACX_OK);
+            std::vector<lacx_digest> out(src.size());
+            const int rc = lacx_decoder_digest_pcm_batch_device(dec, src.data(), (uint32_t)src.size(), nullptr, item_rc.data(), out.data(), nullptr);
+            collect(sent, rc, item_rc, out);
+        }
+        for (void* p : dev) (void)hipFree(p);
+    }
+    lacx_decoder_destroy(dec);
+    int status = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!error[i].empty()) {
+            std::cerr << "Digest failed: " << argv[2 + i] << ": " << error[i] << "\n";
+            status = 1;
+            continue;
+        }
+        const lacx_digest& g = digest[i];
+        char line[160];
+        std::snprintf(line, sizeof(line), "data_crc32=%08x wav_crc32=%08x frames=%llu channels=%u bits=%u rate=%u ", g.data_crc32, g.wav_crc32,
+                      (unsigned long long)g.frames, (unsigned)g.channels, (unsigned)g.bit_depth, (unsigned)g.sample_rate);
+        std::cout << line << argv[2 + i] << "\n";
+    }
+    return status;
+}
+
 // The canonical WAV image of planar PCM (the source form lacx_decoder_verify_wav takes).
 std::vector<uint8_t> wav_image(const std::vector<int32_t>& left, const std::vector<int32_t>* right, uint32_t rate, uint32_t bits) {
     const uint32_t ch = right ? 2u : 1u, bps = bits / 8u, align = ch * bps;
@@ -323,6 +415,7 @@ int main(int argc, char** argv) {
     const std::string mode = argc > 1 ? argv[1] : "";
     if (mode == "selftest" && argc == 2) return selftest_command();
     if (mode == "verify" && argc == 4) return verify_command(argv);
+    if (mode == "digest" && argc >= 3) return digest_command(argc, argv);
     if (argc < 4 || (mode != "encode" && mode != "decode")) {
         usage();
         return 1;
