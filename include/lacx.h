@@ -38,6 +38,9 @@
  *   lacx_decoder_digest_pcm_batch_device,
  *   lacx_crc32_combine      <- the check the container has no field for (the reference's format carries no checksum of its
  *                             audio): CRC-32 of what streams decode to and of source PCM, made on the device
+ *   lacx_decoder_salvage_wav, lacx_decoder_salvage_wav_batch_view,
+ *   lacx_decoder_salvage_batch_device <- beyond the reference (like `flac -F`): decode through errors, the blocks of a
+ *                             damaged or truncated stream that still decode, silence where one does not
  *
  * All analysis (and the decode) runs in hand-written HIP kernels on a gfx950 device; there is no CPU fallback: every
  * call that needs the device fails with LACX_E_DEVICE when none is usable.
@@ -141,7 +144,7 @@ void lacx_get_timing(const lacx_encoder* enc, lacx_timing* out);
 
 /* sizeof() of a public struct as this library was built, by name without the prefix ("config", "channel_plan",
  * "block_plan", "timing", "pcm", "batch_item", "batch_out", "wav_info", "fanout_shard", "fanout_out", "fanout_stats",
- * "stream_info", "span", "decode_item", "window_item", "verify_item", "verify_result", "digest", "digest_source"); 0 for an unknown name.  A binding that declares the structs itself (ctypes, cgo, JNI) checks its layout
+ * "stream_info", "span", "decode_item", "window_item", "verify_item", "verify_result", "digest", "digest_source", "block_fault", "salvage_result"); 0 for an unknown name.  A binding that declares the structs itself (ctypes, cgo, JNI) checks its layout
  * against this before the first call that fills one. */
 uint32_t lacx_sizeof(const char* struct_name);
 
@@ -557,6 +560,66 @@ int lacx_decoder_digest_batch_device(lacx_decoder* dec, const lacx_span* lacs, u
 int lacx_decoder_digest_pcm_batch_device(lacx_decoder* dec, const lacx_digest_source* src, uint32_t n, void* stream,
                                          int* item_rc, lacx_digest* out, float* device_ms);
 uint32_t lacx_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
+
+/* Salvage: decode through errors.  Every other decode entry point refuses an item at its lowest failing block; these
+ * give back whatever still decodes.  A salvage decode of an item always yields the stream's full frame count, every
+ * frame at its own position, described as the header and the block table describe the stream.  A block that decodes
+ * holds exactly what the strict decode gives for it (mid/side inverse applied, both channels inside the bit depth).  A
+ * block that does not is digital silence, every frame 0 in both channels -- nothing of a half-decoded block leaks out:
+ *   1..6, 9  its lane ended with that status (the "[decode-error] block=N <text>" causes of the strict decode)
+ *   7        one of its samples lies outside the bit depth after the inverse
+ *   8        a version-2 block behind the first failing one ("not reached": that container has no sizes to find it by)
+ *   10       LACX_BLOCK_MISSING, "payload missing": the file ends before the block's last byte
+ * Truncation: for a version-3 stream the parse is lenient in exactly one respect, the payload's length.  Header and
+ * block table must pass every rule of lacx_stream_parse (a damaged table fails the item with that parser's message); the
+ * file may end early.  A block is present when its whole byte range lies inside the file; the others -- always a suffix
+ * of the stream -- are missing and never decoded, and only the present blocks' bytes go to the device.  A short file is
+ * flagged LACX_SALVAGE_TRUNCATED; bytes behind the last block's end are ignored and flagged LACX_SALVAGE_TRAILING.  A
+ * truncated version-2 stream needs no such rule: it shows as a failing block of the serial lane, followed by 8s.
+ * The device works in two passes in stream order, because status 7 is final only once every sample of a block has been
+ * examined: the mid/side inverse with the range check in place, then one pass that only reads the final status words
+ * and packs (WAV forms) or blanks (device form).  Against lacx_decoder_decode_wav the WAV forms pay one more write and
+ * read of the PCM.  The status copy of every decode is the whole report: no second round trip.
+ * Outcome: an item's code is LACX_OK whenever its container was accepted, even when every block is lost; the result
+ * says how much was lost, lacx_decoder_item_faults which blocks.  An item whose container is refused keeps the strict
+ * code and message.  item_rc, lacx_decoder_item_error, the return code ("stream i: <message>" of the lowest failing
+ * item), LACX_E_DEVICE for a failure of the whole call, n = 0 / null arrays and device-less behaviour exactly as
+ * lacx_decoder_decode_batch_device.  A clean stream gives the bytes lacx_decoder_decode_wav gives and no fault.
+ * lacx_stream_scan: host only, the lenient parse: *info as lacx_stream_parse fills it (frames from the table),
+ *   *present_blocks, *flags (LACX_SALVAGE_*).  What a caller of lacx_decoder_salvage_batch_device sizes its arrays by.
+ * lacx_decoder_salvage_wav_batch_view: out[i] = item i's WAV image in the decoder's pinned image buffer (as
+ *   lacx_decoder_decode_wav_batch_view), results[i] (n entries, nullable) its loss; zeroed for a refused item.
+ * lacx_decoder_salvage_wav: a batch of one; *out malloc'd (lacx_free); the message carries no "stream 0: ".
+ * lacx_decoder_salvage_batch_device: caller-owned device int32 arrays of items[i].frames each, the value
+ *   lacx_stream_scan reports; nothing outside [0, frames) is written, a mono item's right array is not touched.  The work
+ *   goes on `stream`, and the call returns when it is done.
+ * lacx_decoder_item_faults: the lost blocks of item i of the decoder's last salvage call, ascending by block; valid until
+ *   the decoder's next call.  LACX_E_INVALID for an index outside that call.
+ * lacx_block_fault_text: "block header", "channel header", "residual", "padding", "sample overflow", "trailing bytes",
+ *   "sample outside the bit depth", "not reached", "residual beyond 2^30", "payload missing" for 1..10; "" for 0, else "?". */
+#define LACX_BLOCK_MISSING 10u
+#define LACX_SALVAGE_TRUNCATED 1u
+#define LACX_SALVAGE_TRAILING 2u
+typedef struct lacx_block_fault { /* 24 bytes */
+    uint32_t block, code;         /* block counted in the stream; 1..10 */
+    uint64_t frame;               /* first frame of the block in the stream */
+    uint32_t frames, reserved;
+} lacx_block_fault;
+typedef struct lacx_salvage_result { /* 32 bytes */
+    uint32_t blocks, bad_blocks;
+    uint64_t frames, lost_frames;
+    uint32_t first_bad; /* lowest lost block; == blocks when none */
+    uint32_t flags;     /* LACX_SALVAGE_* */
+} lacx_salvage_result;
+int lacx_stream_scan(const uint8_t* lac, uint64_t size, lacx_stream_info* info, uint32_t* present_blocks, uint32_t* flags);
+int lacx_decoder_salvage_wav_batch_view(lacx_decoder* dec, const lacx_span* lacs, uint32_t n, lacx_span* out, int* item_rc,
+                                        lacx_salvage_result* results, float* device_ms);
+int lacx_decoder_salvage_wav(lacx_decoder* dec, const uint8_t* lac, uint64_t size, uint8_t** out, uint64_t* out_size,
+                             lacx_salvage_result* result, float* device_ms);
+int lacx_decoder_salvage_batch_device(lacx_decoder* dec, const lacx_decode_item* items, uint32_t n, void* stream,
+                                      int* item_rc, lacx_salvage_result* results, float* device_ms);
+int lacx_decoder_item_faults(const lacx_decoder* dec, uint32_t i, const lacx_block_fault** faults, uint32_t* count);
+const char* lacx_block_fault_text(uint32_t code);
 
 /* Block::Encoder::encode drop-in for one channel block of n <= 16384 samples of ANY int32 value: blocks inside the 25-bit
  * mid/side domain of validated 16 / 24-bit input run on the streaming kernels, wider ones on a kernel of their own that

@@ -48,6 +48,7 @@ struct lacx_decoder {
     uint8_t* d_meta() const { return static_cast<uint8_t*>(tables.part[0].p); }
     uint8_t* h_meta() const { return static_cast<uint8_t*>(tables.part[1].p); }
     std::vector<std::string> item_err;  // the last batch call's message per item ("" = decoded)
+    std::vector<std::vector<lacx_block_fault>> item_faults;  // the last salvage call's lost blocks per item
     std::string err;
 };
 
@@ -109,7 +110,7 @@ void wav_header(const lacx_stream_info& info, uint8_t* h) {
 const char* block_error(uint32_t st) {
     static const char* const kWhat[] = {"", "block header", "channel header", "residual", "padding", "sample overflow",
                                         "trailing bytes", "sample outside the bit depth", "not reached", "residual beyond 2^30"};
-    return st < 10 ? kWhat[st] : "?";
+    return st < 10 ? kWhat[st] : st == LACX_BLOCK_MISSING ? "payload missing" : "?";
 }
 
 // A decode job: the items (BatchIn, DecodeForm, sample type: decode_plan.h) and where the call's answers go.
@@ -123,6 +124,8 @@ struct DecodeJob {
     lacx_verify_result* vres = nullptr;  // verify form: [n]
     float* device_ms = nullptr;
     lacx_digest* dres = nullptr;         // digest form: [n]
+    bool salvage = false;                // wav and device forms: decode through errors (DecodePlan::salvage)
+    lacx_salvage_result* sres = nullptr; // salvage: [n]
 };
 
 // What the digest kernel left for an item (DigestWords::raw), as the caller's record: the init term and the final xor
@@ -218,9 +221,10 @@ DevErr upload_payload(lacx_decoder* d, const DecodeJob& job, const DecodePlan& p
         if (DevErr e = chk(hipMemcpyAsync(d->d_pay(), d->h_pay(), plan.total_pay, hipMemcpyHostToDevice, st), "H2D payload")) return e;
     } else {
         for (const PlanItem& p : plan.items)
-            if (DevErr e = chk(hipMemcpyAsync(d->d_pay() + p.item.pay_off, job.in[p.src].lac + p.head, p.pay_bytes, hipMemcpyHostToDevice, st),
-                               "H2D payload"))
-                return e;
+            if (p.pay_bytes)  // (a salvage item whose first block is cut has none)
+                if (DevErr e = chk(hipMemcpyAsync(d->d_pay() + p.item.pay_off, job.in[p.src].lac + p.head, p.pay_bytes, hipMemcpyHostToDevice, st),
+                                   "H2D payload"))
+                    return e;
     }
     if (DevErr e = chk(hipMemsetAsync(d->d_pay() + plan.total_pay, 0, kDecodeTailPad, st), "memset")) return e;  // the bit reader's look-ahead
     if (!plan.host_src) return DevErr{};
@@ -260,6 +264,16 @@ DevErr collect(lacx_decoder* d, const DecodeJob& job, const DecodePlan& plan, hi
         const PlanItem& p = plan.items[j];
         const BatchIn& x = job.in[p.src];
         const uint32_t i = p.src;
+        if (plan.salvage) {  // every block's outcome, not the first: the status words and present_blocks are the whole report
+            const lacx_salvage_result r = salvage_report(p, x.lac, d->h_status(), d->item_faults[i]);
+            if (job.sres) job.sres[i] = r;
+            if (plan.form == DecodeForm::wav) {
+                uint8_t* img = d->h_wav() + p.image_at;
+                wav_header(p.info, img);
+                if (job.out) job.out[i] = lacx_span{img, p.image_size};
+            }
+            continue;
+        }
         for (uint32_t b = 0; b < p.item.blocks; ++b) {
             const uint32_t sv = d->h_status()[p.item.block0 + b];
             if (sv) {  // the item's first failing block, like the reference's message (lac/decoder.cpp:24-32)
@@ -312,10 +326,12 @@ int decode_batch_run(lacx_decoder* d, const DecodeJob& job, std::vector<int>& co
     if (job.device_ms) *job.device_ms = 0.f;
     if (job.vres) std::memset(job.vres, 0, sizeof(lacx_verify_result) * job.n);
     if (job.dres) std::memset(job.dres, 0, sizeof(lacx_digest) * job.n);
+    if (job.sres) std::memset(job.sres, 0, sizeof(lacx_salvage_result) * job.n);
+    if (job.salvage) d->item_faults.assign(job.n, {});
     // LACX_DECODE_BATCH_PAD=1 (tuning knob, read per call): every item's blocks start a new wave
     const char* pad_env = std::getenv("LACX_DECODE_BATCH_PAD");
     DecodePlan plan;
-    const char* whole = plan_decode(job.in, job.n, job.form, job.sample_type, pad_env && pad_env[0] == '1', plan, code, err);
+    const char* whole = plan_decode(job.in, job.n, job.form, job.sample_type, pad_env && pad_env[0] == '1', plan, code, err, job.salvage);
     if (lacx_device_count() <= 0) whole = "no usable HIP device";
     int rc = whole ? decode_fail(LACX_E_DEVICE, whole) : LACX_OK;
     if (!whole && !plan.items.empty()) {
@@ -332,6 +348,8 @@ int decode_batch_run(lacx_decoder* d, const DecodeJob& job, std::vector<int>& co
         if (e) rc = decode_fail(LACX_E_DEVICE, std::string(e.what) + ": " + hipGetErrorString(e.e));
     }
     if (rc != LACX_OK) {  // the whole call failed: no item decoded
+        if (job.sres) std::memset(job.sres, 0, sizeof(lacx_salvage_result) * job.n);
+        if (job.salvage) d->item_faults.assign(job.n, {});
         for (uint32_t i = 0; i < job.n; ++i) {
             if (code[i] != LACX_OK) continue;
             code[i] = rc;
@@ -640,6 +658,76 @@ int lacx_decoder_digest_pcm_batch_device(lacx_decoder* d, const lacx_digest_sour
         if (code[i] != LACX_OK) return decode_fail(code[i], "stream " + std::to_string(i) + ": " + d->item_err[i]);
     return LACX_OK;
 }
+
+// ---- salvage: decode through errors (lacx.h) ----
+int lacx_stream_scan(const uint8_t* lac, uint64_t size, lacx_stream_info* info, uint32_t* present_blocks, uint32_t* flags) {
+    const char* why = "";
+    const int c = scan_stream(lac, size, info, present_blocks, flags, &why);
+    return c == LACX_OK ? c : decode_fail(c, why);
+}
+
+namespace {
+DecodeJob salvage_job(DecodeForm form, hipStream_t stream, lacx_span* out, lacx_salvage_result* results, float* device_ms) {
+    DecodeJob job{nullptr, 0, form, kWholeStreams, stream, out, nullptr, device_ms};
+    job.salvage = true;
+    job.sres = results;
+    return job;
+}
+}  // namespace
+
+int lacx_decoder_salvage_wav_batch_view(lacx_decoder* d, const lacx_span* lacs, uint32_t n, lacx_span* out, int* item_rc,
+                                        lacx_salvage_result* results, float* device_ms) {
+    if (!d) return decode_fail(LACX_E_INVALID, "null decoder");
+    if (!lacs || !out || n == 0) return decode_fail(LACX_E_INVALID, "null argument or empty batch");
+    std::vector<BatchIn> in(n);
+    for (uint32_t i = 0; i < n; ++i) in[i] = BatchIn{lacs[i].data, lacs[i].size, nullptr, nullptr, 0};
+    DecodeJob job = salvage_job(DecodeForm::wav, nullptr, out, results, device_ms);
+    job.in = in.data();
+    job.n = n;
+    return run_batch(d, job, item_rc);
+}
+
+int lacx_decoder_salvage_wav(lacx_decoder* d, const uint8_t* lac, uint64_t size, uint8_t** out, uint64_t* out_size,
+                             lacx_salvage_result* result, float* device_ms) {
+    if (out) *out = nullptr;
+    if (out_size) *out_size = 0;
+    if (result) std::memset(result, 0, sizeof(*result));
+    if (!d) return decode_fail(LACX_E_INVALID, "null decoder");
+    if (!out || !out_size) return decode_fail(LACX_E_INVALID, "null argument");
+    lacx_span img{nullptr, 0};
+    const int rc = run_one(d, BatchIn{lac, size, nullptr, nullptr, 0}, salvage_job(DecodeForm::wav, nullptr, &img, result, device_ms));
+    if (rc) return rc;
+    uint8_t* buf = static_cast<uint8_t*>(std::malloc(img.size));
+    if (!buf) return decode_fail(LACX_E_RUNTIME, "out of host memory");
+    std::memcpy(buf, img.data, img.size);
+    *out = buf;
+    *out_size = img.size;
+    return LACX_OK;
+}
+
+int lacx_decoder_salvage_batch_device(lacx_decoder* d, const lacx_decode_item* items, uint32_t n, void* stream, int* item_rc,
+                                      lacx_salvage_result* results, float* device_ms) {
+    if (!d) return decode_fail(LACX_E_INVALID, "null decoder");
+    if (!items || n == 0) return decode_fail(LACX_E_INVALID, "null argument or empty batch");
+    std::vector<BatchIn> in(n);
+    for (uint32_t i = 0; i < n; ++i) in[i] = BatchIn{items[i].lac, items[i].size, items[i].left, items[i].right, items[i].frames};
+    DecodeJob job = salvage_job(DecodeForm::device, static_cast<hipStream_t>(stream), nullptr, results, device_ms);
+    job.in = in.data();
+    job.n = n;
+    return run_batch(d, job, item_rc);
+}
+
+int lacx_decoder_item_faults(const lacx_decoder* d, uint32_t i, const lacx_block_fault** faults, uint32_t* count) {
+    if (faults) *faults = nullptr;
+    if (count) *count = 0;
+    if (!d || !faults || !count) return decode_fail(LACX_E_INVALID, "null argument");
+    if (i >= d->item_faults.size()) return decode_fail(LACX_E_INVALID, "no such item in the last salvage call");
+    *faults = d->item_faults[i].data();
+    *count = (uint32_t)d->item_faults[i].size();
+    return LACX_OK;
+}
+
+const char* lacx_block_fault_text(uint32_t code) { return block_error(code); }
 
 uint32_t lacx_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b) { return crc32_combine(crc_a, crc_b, len_b); }
 

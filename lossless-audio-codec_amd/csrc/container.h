@@ -90,7 +90,12 @@ inline bool rows_from_offsets(const uint64_t* offsets, const BlockPlan* bplans, 
 // the decoded PCM (1 GiB) and the block count that follows from it, which would refuse the 2 h stream of BASELINE
 // configs[3].  The legacy version-2 container (no compressed sizes, hence no parallelism) is read too: one lane walks it.
 // Returns LACX_OK, or LACX_E_INVALID with the message in *why.
-inline int parse_stream(const uint8_t* lac, uint64_t size, lacx_stream_info* out, const char** why) {
+namespace container_detail {
+// The walk both readers share.  present == null: the strict reader.  Else the lenient one (scan_stream): the two rules on
+// the length of a version-3 payload are not applied, *present = the blocks whose whole byte range lies inside the file
+// (the others are a suffix) and *flags says how the file's length differs from what the table states.
+inline int walk_stream(const uint8_t* lac, uint64_t size, lacx_stream_info* out, const char** why, uint32_t* present, uint32_t* flags) {
+    const bool lenient = present != nullptr;
     auto fail = [&](const char* msg) { return *why = msg, LACX_E_INVALID; };
     if (!lac || !out) return fail("null argument");
     if (size == 0) return fail("[decode-error] empty input");
@@ -106,6 +111,7 @@ inline int parse_stream(const uint8_t* lac, uint64_t size, lacx_stream_info* out
     const uint64_t head = stream_head_bytes(version, nb);
     if (size < head) return fail("[decode-error] truncated block size table");
     uint64_t frames = 0, pay = 0;
+    uint32_t inside = 0;  // rows whose bytes end inside the file: a prefix, the sizes being positive
     for (uint32_t b = 0; b < nb; ++b) {
         const uint32_t n = row_frames(lac, version, b);
         if (n == 0 || n > (uint32_t)kMaxBlock || (b + 1 < nb && n < 256u)) return fail("[decode-error] invalid block size");
@@ -118,12 +124,13 @@ inline int parse_stream(const uint8_t* lac, uint64_t size, lacx_stream_info* out
             // carry a unary part of up to 2^30 bits -- is a documented deviation, see lacx.h.)
             if (by == 0 || by >= (1u << 29)) return fail("[decode-error] invalid compressed block size");
             pay += by;
-            if (pay > size) return fail("[decode-error] compressed block sizes exceed frame payload");
+            if (!lenient && pay > size) return fail("[decode-error] compressed block sizes exceed frame payload");
+            if (head + pay <= size) inside = b + 1;
         }
     }
     const uint64_t wav_bytes = frames * (uint64_t)ch * (uint64_t)(bd / 8);
     if (36u + wav_bytes + (wav_bytes & 1u) > 0xFFFFFFFFull) return fail("[decode-error] decoded WAV data exceeds RIFF limit");
-    if (version >= 3 && head + pay != size) return fail("[decode-error] block payloads do not fill the file");
+    if (!lenient && version >= 3 && head + pay != size) return fail("[decode-error] block payloads do not fill the file");
     if (version == 2 && size - head >= (1ull << 29)) return fail("[decode-error] version-2 payload too large for the serial reader");
     out->sample_rate = sr;
     out->blocks = nb;
@@ -132,7 +139,28 @@ inline int parse_stream(const uint8_t* lac, uint64_t size, lacx_stream_info* out
     out->bit_depth = (uint8_t)bd;
     out->stereo_mode = (uint8_t)sm;
     out->version = (uint8_t)version;
+    if (lenient) {  // (a version-2 stream has no sizes to miss: every block is the serial lane's to find)
+        *present = version >= 3 ? inside : nb;
+        *flags = version < 3 || head + pay == size ? 0u : head + pay > size ? LACX_SALVAGE_TRUNCATED : LACX_SALVAGE_TRAILING;
+    }
     return LACX_OK;
+}
+}  // namespace container_detail
+
+inline int parse_stream(const uint8_t* lac, uint64_t size, lacx_stream_info* out, const char** why) {
+    return container_detail::walk_stream(lac, size, out, why, nullptr, nullptr);
+}
+
+// The lenient reader of the salvage decode: parse_stream's rules and messages for the header and the block table, but a
+// version-3 file may end early or carry bytes behind its last block.  *present_blocks: the blocks whose whole byte range
+// [start, start + bytes) lies inside the file -- the missing ones are always a suffix; *flags: LACX_SALVAGE_TRUNCATED for
+// a file shorter than its table states, LACX_SALVAGE_TRAILING for a longer one (the bytes behind the last block are
+// ignored).  A stream parse_stream accepts gives the same info, every block present and no flag; version 2 is read as
+// parse_stream reads it.
+inline int scan_stream(const uint8_t* lac, uint64_t size, lacx_stream_info* out, uint32_t* present_blocks, uint32_t* flags, const char** why) {
+    if (!present_blocks || !flags) return *why = "null argument", LACX_E_INVALID;
+    *present_blocks = 0, *flags = 0;
+    return container_detail::walk_stream(lac, size, out, why, present_blocks, flags);
 }
 
 }  // namespace lacx

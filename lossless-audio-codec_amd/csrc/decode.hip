@@ -19,6 +19,9 @@
 //   k_verify        the same per-sample work, compared with the source PCM in its own layout instead of stored: a count
 //                   of differing samples and the first of them per item (lacx_decoder_verify_*; verify_core.h)
 //   (k_digest       the same per-sample work, digested instead of stored: k_digest.hip, launched from launch_decode)
+//   k_salvage_wav   salvage job (decode through errors): after k_ms_inverse, the WAV image from the final status words --
+//                   the blocks that decoded as they are, zeros for every frame of a lost one (salvage_core.h)
+//   k_salvage_blank the same for caller-owned arrays: zeros over the lost blocks, nothing else touched
 // Every launch decodes a batch of streams (items) as one job; a single stream is a batch of one.
 // The adaptive Rice parameter uses the encoder's division-free formulation (kmean / biased_k of analyze_core.h, proven
 // against Rice::adapt_k there); it assumes zigzag residuals below 2^30 like the encoder does, and a stream with a larger
@@ -29,6 +32,7 @@
 
 #include "decode_core.h"
 #include "kernels.h"
+#include "salvage_core.h"
 #include "verify_core.h"
 
 namespace lacx {
@@ -424,6 +428,54 @@ __global__ __launch_bounds__(64) void k_verify_fill(uint32_t nitems, const Decod
                      ms_flag + it.block0, global_ptr(s.data0), global_ptr(s.data1), s.layout, res[j], it.bit_depth);
 }
 
+// Salvage job, WAV form: laid out as k_wav_pack -- thread u handles unit u of the concatenated unit ranges of
+// the items' frames, the item found once per workgroup by a uniform binary search and again per thread only in a workgroup
+// that spans items.  Runs after k_ms_inverse: it reads the inverted samples and the FINAL status words, and writes every
+// byte of every image's data region (salvage_wav_unit).  present[j]: the blocks of item j that had a lane.
+__global__ __launch_bounds__(256) void k_salvage_wav(uint32_t nitems, unsigned long long total_units,
+                                                     const unsigned long long* __restrict__ unit_off,
+                                                     const DecodeItem* __restrict__ items, const uint32_t* __restrict__ present,
+                                                     const unsigned long long* __restrict__ frame_off,
+                                                     const uint32_t* __restrict__ status) {
+    const unsigned long long first = (unsigned long long)blockIdx.x * 256u;
+    uint32_t lo = 0, hi = nitems;  // unit_off[lo] <= first < unit_off[hi]
+    while (hi - lo > 1u) {
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        if (unit_off[mid] <= first) lo = mid;
+        else hi = mid;
+    }
+    const unsigned long long u = first + threadIdx.x;
+    if (u >= total_units) return;
+    uint32_t j = lo;
+    if (unit_off[lo + 1] < first + 256u) {  // (uniform) the workgroup spans items: this thread's, among the later ones
+        uint32_t h2 = nitems;  // unit_off[j] <= u < unit_off[h2]
+        while (h2 - j > 1u) {
+            const uint32_t mid = j + (h2 - j) / 2u;
+            if (unit_off[mid] <= u) j = mid;
+            else h2 = mid;
+        }
+    }
+    const DecodeItem& it = items[j];
+    salvage_wav_unit(4ull * (u - unit_off[j]), it.blocks, present[j], it.channels, it.bit_depth, it.frames, frame_off + it.block0,
+                     it.frame0, global_ptr(it.left), global_ptr(it.right), status + it.block0, global_ptr(it.wav));
+}
+
+// Salvage job, device form: grid = (all blocks of the batch, tiles) like k_ms_inverse, after it.  A block that decoded
+// leaves at once (uniform: its item's record and present count as scalar loads, then one status word), so a healthy
+// stream pays the launch and those loads; a lost block's frames in the caller's arrays become zeros (salvage_blank_tile).
+__global__ __launch_bounds__(256) void k_salvage_blank(const uint32_t* __restrict__ blk_item, const DecodeItem* __restrict__ items,
+                                                       const uint32_t* __restrict__ present,
+                                                       const unsigned long long* __restrict__ frame_off,
+                                                       const uint32_t* __restrict__ status) {
+    const uint32_t blk = blockIdx.x, tile = blockIdx.y;
+    const uint32_t j = blk_item[blk];
+    const DecodeItem& it = items[j];
+    if (!salvage_lost(status + it.block0, blk - it.block0, present[j])) return;  // (uniform) the block decoded
+    const unsigned long long f0 = frame_off[blk];
+    const uint32_t n = (uint32_t)(frame_off[blk + 1] - f0);
+    salvage_blank_tile(tile, f0 - it.frame0, n, global_ptr(it.left), it.channels == 2 ? global_ptr(it.right) : nullptr, threadIdx.x);
+}
+
 hipError_t launch_decode(const DecodeArgs& a, hipStream_t stream) {
     const size_t smem = kDecBytesPerCol * kDecThreads;
     if (a.lanes) {
@@ -440,7 +492,20 @@ hipError_t launch_decode(const DecodeArgs& a, hipStream_t stream) {
         hipLaunchKernelGGL(k_decode_serial, dim3((a.nv2 + kDecThreads - 1) / kDecThreads), dim3(kDecThreads), smem,
                            stream, a.nv2, a.v2_items, a.items, a.payload, a.frame_off, a.status, a.ms_flag);
     }
-    if (a.digest) {
+    if (a.present) {  // salvage: two passes in stream order (status 7 is final only after the first)
+        if (a.total_blocks) {
+            hipLaunchKernelGGL(k_ms_inverse, dim3(a.total_blocks, kMaxBlock / 1024), dim3(256), 0, stream, a.blk_item, a.items,
+                               a.frame_off, a.ms_flag, a.status);
+            if (a.wav) {
+                if (a.total_units)
+                    hipLaunchKernelGGL(k_salvage_wav, dim3((uint32_t)((a.total_units + 255u) / 256u)), dim3(256), 0, stream, a.nitems,
+                                       a.total_units, a.unit_off, a.items, a.present, a.frame_off, a.status);
+            } else {
+                hipLaunchKernelGGL(k_salvage_blank, dim3(a.total_blocks, kMaxBlock / 1024), dim3(256), 0, stream, a.blk_item, a.items,
+                                   a.present, a.frame_off, a.status);
+            }
+        }
+    } else if (a.digest) {
         if (a.total_units) return launch_digest(a, stream);
     } else if (a.verify) {
         if (a.total_units) {

@@ -48,6 +48,9 @@ struct BatchIn {
 // they decode whole into the decoder's PCM buffers (scratch) and are all checked, and k_window_out writes the window's
 // frames out; a version-2 item (no compressed sizes) decodes in full and is then windowed.  The host form's windows go
 // through the decoder's image buffer, copied to the caller once the statuses are checked.
+// The wav and device forms also come as salvage jobs (DecodePlan::salvage, lacx_decoder_salvage_*): the items are read
+// by scan_stream, so a version-3 file may end early -- only its present blocks get a lane, only their bytes are payload --
+// and the post pass is k_ms_inverse in place, then k_salvage_wav / k_salvage_blank over the final status words.
 enum class DecodeForm { wav, device, host, verify, digest };
 constexpr int kWholeStreams = -1;
 
@@ -63,11 +66,13 @@ struct PlanItem {
     lacx_stream_info info;
     DecodeItem item;     // left / right / wav are null until plan_fill_tables
     WindowOut win;       // window job; left / right as above
+    uint32_t present_blocks;  // the blocks whose bytes the file holds, a prefix: item.blocks but for a truncated salvage item
+    uint32_t scan_flags;      // salvage job: LACX_SALVAGE_*
 };
 
 // The tables the kernels read, one upload: items | byte_off [T + 1] | frame_off [T + 1] | unit_off [m + 1] | blk_item [T]
 // | lane_blk | v2_items, then for a window job | win [m], for the verify form | ver [m] | res [m], for the digest form
-// | res [m] at `win` (byte offsets)
+// | res [m] at `win`, for a salvage job | present [m] (uint32) at `win` (byte offsets)
 struct TableLayout {
     size_t items, byte_off, frame_off, unit_off, blk_item, lane_blk, v2_items, win, res, size;
 };
@@ -75,8 +80,10 @@ struct TableLayout {
 struct DecodePlan {
     DecodeForm form = DecodeForm::host;
     int sample_type = kWholeStreams;
+    bool salvage = false;  // wav and device forms of whole streams only
     bool window() const { return sample_type != kWholeStreams; }
     bool own_pcm() const { return form != DecodeForm::device || window(); }  // into the decoder's PCM buffers
+    bool post_units() const { return window() || form == DecodeForm::verify || form == DecodeForm::wav || form == DecodeForm::digest; }
     bool host_window() const { return form == DecodeForm::host && window(); }
     std::vector<PlanItem> items;
     // k_decode's lanes: lane g decodes global block lane_blk[g] (~0u: idle); version-3 blocks only, an item's in
@@ -135,16 +142,20 @@ constexpr size_t up16(size_t v) { return (v + 15u) & ~(size_t)15u; }
 // tables as global prefix sums, one lane per version-3 block and one per version-2 item, then one post pass over all of
 // them.  Per item, code[i] and err[i] ("" = goes to the device).  pad_waves: every item's blocks start a new wave.
 // Returns null, or why the job as a whole cannot run (nothing is laid out then).
+// salvage: a salvage job (DecodeForm above): an item's blocks and frames are still the whole table's, its payload the
+// bytes of its present blocks.
 inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, int sample_type, bool pad_waves, DecodePlan& plan,
-                               std::vector<int>& code, std::vector<std::string>& err) {
+                               std::vector<int>& code, std::vector<std::string>& err, bool salvage = false) {
     using namespace plan_detail;
     plan = DecodePlan{};
     plan.form = form;
     plan.sample_type = sample_type;
+    plan.salvage = salvage;
     const bool window = plan.window(), own_pcm = plan.own_pcm(), wav = form == DecodeForm::wav, verify = form == DecodeForm::verify,
                digest = form == DecodeForm::digest;
     code.assign(n, LACX_OK);
     err.assign(n, std::string());
+    if (salvage && (sample_type != kWholeStreams || (form != DecodeForm::wav && form != DecodeForm::device))) return "salvage is a whole-stream WAV or device job";
     plan.items.reserve(n);
     uint32_t v3_blocks = 0;
     for (uint32_t i = 0; i < n; ++i) {
@@ -152,7 +163,7 @@ inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, i
         PlanItem p{};
         lacx_stream_info& f = p.info;
         const char* why = nullptr;
-        int c = parse_stream(x.lac, x.size, &f, &why);
+        int c = salvage ? scan_stream(x.lac, x.size, &f, &p.present_blocks, &p.scan_flags, &why) : parse_stream(x.lac, x.size, &f, &why);
         if (c == LACX_OK && (why = window ? check_window(x, f) : verify ? check_source(x, f) : wav || digest ? nullptr : check_arrays(x, f)))
             c = LACX_E_INVALID;
         if (c != LACX_OK) {
@@ -165,6 +176,10 @@ inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, i
         uint32_t nb = f.blocks;
         uint64_t frames = f.frames, fr0 = 0;
         p.pay_bytes = x.size - p.head;
+        if (salvage && f.version != 2) {  // the present blocks' bytes: not those of a cut block, not what trails the last
+            p.pay_bytes = 0;
+            for (uint32_t b = 0; b < p.present_blocks; ++b) p.pay_bytes += row_bytes(x.lac, b);
+        }
         if (window && f.version != 2) {  // the blocks [blk_first, blk_first + nb) that hold the window's first and last frames
             const uint64_t last = x.start + x.frames - 1;
             uint64_t fr = 0, by = 0;
@@ -181,6 +196,7 @@ inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, i
                 by += nby;
             }
         }
+        if (!salvage) p.present_blocks = nb;  // (a window's blocks: all of them lie inside a file the strict parser took)
         if (window) {
             p.win = WindowOut{nullptr, nullptr, x.start - fr0, x.frames};
             p.image_at = plan.image_total;  // the host form's staging: left, then right
@@ -192,7 +208,7 @@ inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, i
             p.image_size = wav_image_bytes(f);
             plan.image_total += up16(p.image_size);
         }
-        if (window || verify || wav || digest) plan.total_units += (frames + 3u) / 4u;  // the post passes' units of 4 frames
+        if (plan.post_units()) plan.total_units += (frames + 3u) / 4u;  // the post passes' units of 4 frames
         DecodeItem& y = p.item;
         y.frame0 = plan.total_frames;
         y.frames = frames;
@@ -224,7 +240,7 @@ inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, i
             continue;
         }
         if (pad_waves) while (plan.lane_blk.size() % 64u) plan.lane_blk.push_back(~0u);
-        for (uint32_t b = 0; b < y.blocks; ++b) plan.lane_blk.push_back(y.block0 + b);
+        for (uint32_t b = 0; b < plan.items[j].present_blocks; ++b) plan.lane_blk.push_back(y.block0 + b);
     }
     if (verify && m == 1 && in[plan.items[0].src].host_src) {
         plan.host_src = in[plan.items[0].src].host_src;
@@ -242,7 +258,7 @@ inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, i
     const size_t end = at.v2_items + 4 * plan.v2_items.size();
     at.win = up16(end);
     at.res = digest ? at.win : at.win + sizeof(VerifySource) * m;
-    at.size = verify ? at.res + sizeof(VerifyWords) * m : digest ? at.res + sizeof(DigestWords) * m : window ? at.win + sizeof(WindowOut) * m : end;
+    at.size = salvage ? at.win + 4 * m : verify ? at.res + sizeof(VerifyWords) * m : digest ? at.res + sizeof(DigestWords) * m : window ? at.win + sizeof(WindowOut) * m : end;
     plan.need.payload = (plan.host_src ? plan.src_at + plan.host_src_bytes : plan.total_pay) + kDecodeTailPad;
     plan.need.blocks = T;
     plan.need.pcm_frames = own_pcm ? plan.pcm_total : 0;
@@ -250,6 +266,30 @@ inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, i
     plan.need.stage = window ? plan.total_pay : 0;
     plan.need.tables = at.size;
     return nullptr;
+}
+
+// What a salvage job reports for an item, from what every decode copies back anyway: the job's status words (status, by
+// global block) and the item's present_blocks.  A block is lost with its lane's or the range check's status (1..9), or --
+// behind the present ones, where nobody wrote a status word -- as LACX_BLOCK_MISSING.  faults: the lost blocks, ascending.
+inline lacx_salvage_result salvage_report(const PlanItem& p, const uint8_t* lac, const uint32_t* status, std::vector<lacx_block_fault>& faults) {
+    lacx_salvage_result r{};
+    r.blocks = r.first_bad = p.item.blocks;
+    r.frames = p.info.frames;
+    r.flags = p.scan_flags;
+    faults.clear();
+    uint64_t frame = 0;
+    for (uint32_t b = 0; b < p.item.blocks; ++b) {
+        const uint32_t n = row_frames(lac, p.info.version, b);
+        const uint32_t code = b >= p.present_blocks ? LACX_BLOCK_MISSING : status[p.item.block0 + b];
+        if (code) {
+            if (faults.empty()) r.first_bad = b;
+            faults.push_back(lacx_block_fault{b, code, frame, n, 0});
+            r.lost_frames += n;
+        }
+        frame += n;
+    }
+    r.bad_blocks = (uint32_t)faults.size();
+    return r;
 }
 
 // The base addresses of the run's buffers, as the kernels will see them.
@@ -283,7 +323,8 @@ inline void plan_fill_tables(const DecodePlan& plan, const BatchIn* in, const Pl
             const uint32_t g = y.block0 + b;
             const uint64_t sb = p.blk_first + b;  // the block within the stream
             frame_off[g + 1] = frame_off[g] + row_frames(x.lac, y.version, sb);
-            byte_off[g + 1] = v2 ? byte_off[g] : byte_off[g] + row_bytes(x.lac, sb);
+            // (a missing block of a salvage item has no bytes in the payload buffer, and no lane that would ask)
+            byte_off[g + 1] = v2 || b >= p.present_blocks ? byte_off[g] : byte_off[g] + row_bytes(x.lac, sb);
             blk_item[g] = j;
         }
         // the version-2 item's bytes count in the byte offsets as one lump at its last block
@@ -305,6 +346,7 @@ inline void plan_fill_tables(const DecodePlan& plan, const BatchIn* in, const Pl
             res[j] = VerifyWords{0, ~0ull, 0, 0, 0, 0};
         }
         if (plan.form == DecodeForm::digest) reinterpret_cast<DigestWords*>(h + at.res)[j] = DigestWords{0, 0};
+        if (plan.salvage) reinterpret_cast<uint32_t*>(h + at.win)[j] = p.present_blocks;
     }
     if (!plan.lane_blk.empty()) std::memcpy(h + at.lane_blk, plan.lane_blk.data(), 4 * plan.lane_blk.size());
     if (!plan.v2_items.empty()) std::memcpy(h + at.v2_items, plan.v2_items.data(), 4 * plan.v2_items.size());
@@ -336,6 +378,7 @@ inline DecodeArgs plan_args(const DecodePlan& plan, const uint8_t* tables, const
         a.verify = reinterpret_cast<const VerifySource*>(tables + at.win);
         a.verify_res = reinterpret_cast<VerifyWords*>(const_cast<uint8_t*>(tables) + at.res);
     }
+    if (plan.salvage) a.present = reinterpret_cast<const uint32_t*>(tables + at.win);
     if (plan.form == DecodeForm::digest) a.digest = reinterpret_cast<DigestWords*>(const_cast<uint8_t*>(tables) + at.res);
     return a;
 }

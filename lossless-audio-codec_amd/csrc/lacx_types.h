@@ -183,5 +183,9 @@ struct DecodeArgs {
     // digest form (non-null: k_digest over the units of unit_off in place of the other post passes): digest[j] is item
     // j's result word (zero on entry)
     DigestWords* digest = nullptr;
+    // salvage job (non-null: k_ms_inverse in place, then k_salvage_wav (wav) or k_salvage_blank over the final status
+    // words, in place of the other post passes): present[j] = the blocks of item j that had a lane; the status words
+    // of the others were written by nobody
+    const uint32_t* present = nullptr;
 };
 }  // namespace lacx

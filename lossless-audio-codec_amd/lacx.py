@@ -112,6 +112,8 @@ EXPORTS = (
     "lacx_decoder_item_error", "lacx_decoder_decode_window_batch_device", "lacx_decoder_decode_window",
     "lacx_decoder_verify_batch_device", "lacx_decoder_verify_wav",
     "lacx_decoder_digest_batch_device", "lacx_decoder_digest_pcm_batch_device", "lacx_crc32_combine",
+    "lacx_stream_scan", "lacx_decoder_salvage_wav_batch_view", "lacx_decoder_salvage_wav",
+    "lacx_decoder_salvage_batch_device", "lacx_decoder_item_faults", "lacx_block_fault_text",
 )
 
 
@@ -183,6 +185,17 @@ def lib():
                                                            C.POINTER(C.c_int), C.POINTER(Digest), C.POINTER(C.c_float)]
         L.lacx_crc32_combine.restype = C.c_uint32
         L.lacx_crc32_combine.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64]
+        L.lacx_stream_scan.argtypes = [C.POINTER(C.c_uint8), C.c_uint64, C.POINTER(StreamInfo), C.POINTER(C.c_uint32),
+                                       C.POINTER(C.c_uint32)]
+        L.lacx_decoder_salvage_wav_batch_view.argtypes = [C.c_void_p, C.POINTER(Span), C.c_uint32, C.POINTER(Span),
+                                                          C.POINTER(C.c_int), C.POINTER(SalvageResult), C.POINTER(C.c_float)]
+        L.lacx_decoder_salvage_wav.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), C.c_uint64, C.POINTER(C.POINTER(C.c_uint8)),
+                                               C.POINTER(C.c_uint64), C.POINTER(SalvageResult), C.POINTER(C.c_float)]
+        L.lacx_decoder_salvage_batch_device.argtypes = [C.c_void_p, C.POINTER(DecodeItem), C.c_uint32, C.c_void_p,
+                                                        C.POINTER(C.c_int), C.POINTER(SalvageResult), C.POINTER(C.c_float)]
+        L.lacx_decoder_item_faults.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.POINTER(BlockFault)), C.POINTER(C.c_uint32)]
+        L.lacx_block_fault_text.restype = C.c_char_p
+        L.lacx_block_fault_text.argtypes = [C.c_uint32]
         L.lacx_decoder_item_error.restype = C.c_char_p
         L.lacx_decoder_item_error.argtypes = [C.c_void_p, C.c_uint32]
         # the structs declared in this file against the library's own sizeof(): a layout that has drifted from
@@ -204,7 +217,8 @@ def abi_structs() -> dict:
             "batch_item": BatchItem, "batch_out": BatchOut, "wav_info": WavInfo, "fanout_shard": FanoutShard,
             "fanout_out": FanoutOut, "fanout_stats": FanoutStats, "stream_info": StreamInfo, "span": Span,
             "decode_item": DecodeItem, "window_item": WindowItem, "verify_item": VerifyItem,
-            "verify_result": VerifyResult, "digest": Digest, "digest_source": DigestSource}
+            "verify_result": VerifyResult, "digest": Digest, "digest_source": DigestSource,
+            "block_fault": BlockFault, "salvage_result": SalvageResult}
 
 
 def device_count() -> int:
@@ -746,6 +760,40 @@ class DigestSource(C.Structure):
                 ("reserved", C.c_uint8 * 3)]
 
 
+BLOCK_MISSING = 10                           # LACX_BLOCK_MISSING
+SALVAGE_TRUNCATED, SALVAGE_TRAILING = 1, 2   # LACX_SALVAGE_*
+
+
+class BlockFault(C.Structure):
+    """A lost block of a salvage decode: its number and first frame in the stream, its frames, and why (1..10)."""
+    _fields_ = [("block", C.c_uint32), ("code", C.c_uint32), ("frame", C.c_uint64), ("frames", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+    @property
+    def text(self) -> str:
+        return block_fault_text(self.code)
+
+
+class SalvageResult(C.Structure):
+    """How much of a stream a salvage decode lost: first_bad == blocks when nothing; flags: SALVAGE_*."""
+    _fields_ = [("blocks", C.c_uint32), ("bad_blocks", C.c_uint32), ("frames", C.c_uint64), ("lost_frames", C.c_uint64),
+                ("first_bad", C.c_uint32), ("flags", C.c_uint32)]
+
+
+def block_fault_text(code: int) -> str:
+    return lib().lacx_block_fault_text(C.c_uint32(code)).decode()
+
+
+def stream_scan(lac: bytes):
+    """The lenient parse of the salvage decode: (StreamInfo, present_blocks, flags), or None when header or block table
+    are refused (lacx_decode_last_error has stream_parse's message).  A version-3 file may end early or carry bytes
+    behind its last block: present_blocks of its blocks lie whole inside the file.  Host-only."""
+    info, present, flags = StreamInfo(), C.c_uint32(), C.c_uint32()
+    buf = (C.c_uint8 * max(1, len(lac))).from_buffer_copy(lac if lac else b"\0")
+    rc = lib().lacx_stream_scan(buf, C.c_uint64(len(lac)), C.byref(info), C.byref(present), C.byref(flags))
+    return (info, int(present.value), int(flags.value)) if rc == OK else None
+
+
 def crc32_combine(crc_a: int, crc_b: int, len_b: int) -> int:
     """zlib's crc32_combine: crc32(A + B) from crc32(A), crc32(B) and len(B).  Host only."""
     return int(lib().lacx_crc32_combine(C.c_uint32(crc_a), C.c_uint32(crc_b), C.c_uint64(len_b)))
@@ -936,6 +984,79 @@ class Decoder:
         rc, errors, outs = self._wav_batch(lib().lacx_decoder_decode_wav_batch_view, lacs)
         results = [None if (i in errors or not outs[i].data) else np.ctypeslib.as_array(outs[i].data, shape=(outs[i].size,))
                    for i in range(len(lacs))]
+        return self._raise_batch(rc, errors, results)
+
+    def _faults(self, i) -> list:
+        ptr, count = C.POINTER(BlockFault)(), C.c_uint32()
+        if lib().lacx_decoder_item_faults(self._h, C.c_uint32(i), C.byref(ptr), C.byref(count)) != OK:
+            return []
+        out = []
+        for k in range(count.value):  # copies: the list dies with the decoder's next call
+            f = BlockFault()
+            C.memmove(C.byref(f), C.byref(ptr[k]), C.sizeof(BlockFault))
+            out.append(f)
+        return out
+
+    @staticmethod
+    def _copy_result(r) -> SalvageResult:
+        out = SalvageResult()
+        C.memmove(C.byref(out), C.byref(r), C.sizeof(SalvageResult))
+        return out
+
+    def salvage_wav(self, lac):
+        """Decode through errors: (WAV image bytes, SalvageResult, [BlockFault]).  The image always has the stream's full
+        frame count; blocks that do not decode -- or that a truncated file no longer holds -- are silence, listed in the
+        fault list.  A clean stream gives decode_wav's bytes and no fault.  RuntimeError only where the container itself
+        is refused (stream_parse's message) or the call as a whole fails."""
+        if self._h is None:
+            raise RuntimeError("decoder is closed")
+        buf = np.frombuffer(lac, dtype=np.uint8)
+        out, size, ms, res = C.POINTER(C.c_uint8)(), C.c_uint64(), C.c_float(), SalvageResult()
+        rc = lib().lacx_decoder_salvage_wav(self._h, buf.ctypes.data_as(C.POINTER(C.c_uint8)), C.c_uint64(buf.size), C.byref(out),
+                                            C.byref(size), C.byref(res), C.byref(ms))
+        if rc != OK:
+            raise RuntimeError(lib().lacx_decode_last_error().decode(errors="replace"))
+        self.last_ms = float(ms.value)
+        try:
+            return C.string_at(out, size.value), res, self._faults(0)
+        finally:
+            lib().lacx_free(out)
+
+    def salvage_wav_batch(self, lacs) -> list:
+        """Many streams salvaged as one device job: (WAV image bytes, SalvageResult, [BlockFault]) per item, None for an
+        item whose container is refused; those raise BatchDecodeError once the others are done."""
+        bufs = [np.frombuffer(x, dtype=np.uint8) for x in lacs]
+        n = len(bufs)
+        spans = (Span * max(1, n))(*[Span(b.ctypes.data_as(C.POINTER(C.c_uint8)), b.size) for b in bufs])
+        outs = (Span * max(1, n))()
+        res = (SalvageResult * max(1, n))()
+        rc, errors = self._batch(n, lambda rcs, ms: lib().lacx_decoder_salvage_wav_batch_view(
+            self._h, spans, C.c_uint32(n), outs, rcs, res, ms))
+        results = [None if (i in errors or not outs[i].data) else
+                   (C.string_at(outs[i].data, outs[i].size), self._copy_result(res[i]), self._faults(i)) for i in range(n)]
+        return self._raise_batch(rc, errors, results)
+
+    def salvage_batch_device(self, lacs, outputs, stream: int = 0) -> list:
+        """Many streams salvaged into caller-owned device arrays: outputs[i] = (left_ptr, right_ptr or None), int32 arrays
+        of stream_scan(lacs[i])[0].frames each on the decoder's device.  Lost blocks are zeros; nothing outside
+        [0, frames) is written.  Returns (StreamInfo, SalvageResult, [BlockFault]) per item, None where the container is
+        refused; those raise BatchDecodeError once the others are done."""
+        if len(outputs) != len(lacs):
+            raise ValueError("one output pair per stream")
+        bufs = [np.frombuffer(x, dtype=np.uint8) for x in lacs]
+        n = len(bufs)
+        scans = [stream_scan(x) for x in lacs]
+        items = (DecodeItem * max(1, n))()
+        for it, b, (lp, rp), sc in zip(items, bufs, outputs, scans):
+            it.lac = b.ctypes.data_as(C.POINTER(C.c_uint8))
+            it.size = b.size
+            it.left = lp
+            it.right = rp
+            it.frames = sc[0].frames if sc is not None else 0
+        res = (SalvageResult * max(1, n))()
+        rc, errors = self._batch(n, lambda rcs, ms: lib().lacx_decoder_salvage_batch_device(
+            self._h, items, C.c_uint32(n), C.c_void_p(stream), rcs, res, ms))
+        results = [None if i in errors else (scans[i][0], self._copy_result(res[i]), self._faults(i)) for i in range(n)]
         return self._raise_batch(rc, errors, results)
 
     def decode_batch_device(self, lacs, outputs, stream: int = 0) -> list:

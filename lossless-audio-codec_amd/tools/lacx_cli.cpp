@@ -13,6 +13,9 @@
 // of the source instead of the input file).  selftest (ref :803-909): the reference's
 // four format pairs, signal and frame count, LR / MS / auto / mono encodes through lacx_encode, each verified on the
 // device against its source, the header fields read back through lacx_stream_parse, the reference's output lines.
+// decode --salvage (no counterpart in the reference's tool; `flac -F`): lacx_decoder_salvage_wav -- whatever blocks of a
+// damaged or truncated stream still decode, silence for the others, the lost blocks listed on stderr, exit status 3
+// when any was lost.
 // digest (no counterpart in the reference's tool; `flac -t` without the source, and the STREAMINFO MD5's role): the CRC-32
 // of what every .lac decodes to and of every WAV's data chunk, made on the device (lacx_decoder_digest_batch_device /
 // lacx_decoder_digest_pcm_batch_device): a .lac and the WAV it was made from print the same fields.
@@ -41,7 +44,9 @@ namespace {
 void usage() {
     std::cerr << "Usage:\n  lacx_cli encode input.wav output.lac [--stereo-mode=lr|ms] [--threads=N] [--debug-threads] [--debug-lpc] "
                  "[--debug-stereo-est] [--debug-zr] [--debug-partitions] [--no-partitioning] [--verify] [--verify-against=other.wav]\n"
-                 "  lacx_cli decode input.lac output.wav [--threads=N] [--debug-threads]\n"
+                 "  lacx_cli decode input.lac output.wav [--threads=N] [--debug-threads] [--salvage]\n"
+                 "      --salvage: decode through errors -- lost blocks become silence, one \"[salvage] block=N ...\" line each on\n"
+                 "      stderr; exit 0 when nothing was lost, 3 when the file was written with blocks lost\n"
                  "  lacx_cli verify input.lac input.wav\n"
                  "  lacx_cli digest FILE...   (.lac and .wav files, told apart by content)\n"
                  "  lacx_cli selftest\n";
@@ -105,20 +110,24 @@ bool load_file(const std::string& path, std::vector<uint8_t>& data) {
     return true;
 }
 
-// lacx_cli decode input.lac output.wav [--threads=N] [--debug-threads] (ref src/main.cpp:712-781)
+constexpr int kExitSalvagedWithLoss = 3;  // decode --salvage: the WAV was written, with lost blocks as silence
+
+// lacx_cli decode input.lac output.wav [--threads=N] [--debug-threads] [--salvage] (ref src/main.cpp:712-781)
 int decode_command(int argc, char** argv) {
     const std::string in_path = argv[2], out_path = argv[3];
     if (same_file(in_path, out_path)) {
         std::cerr << "Input and output paths must be different\n";
         return 1;
     }
-    bool debug_threads = false;
+    bool debug_threads = false, salvage = false;
     unsigned long long threads = 0;
     for (int i = 4; i < argc; ++i) {
         const std::string flag = argv[i];
         const std::string tprefix = "--threads=";
         if (flag == "--debug-threads") {
             debug_threads = true;
+        } else if (flag == "--salvage") {
+            salvage = true;
         } else if (flag.compare(0, tprefix.size(), tprefix) == 0) {
             if (!positive_integer(flag.substr(tprefix.size()), threads)) {
                 std::cerr << "Error: --threads requires a positive integer\n";
@@ -136,7 +145,9 @@ int decode_command(int argc, char** argv) {
         return 1;
     }
     lacx_stream_info info{};
-    if (lacx_stream_parse(lac.data(), lac.size(), &info) != LACX_OK) {  // structural errors need no device
+    uint32_t present = 0, scan_flags = 0;
+    if ((salvage ? lacx_stream_scan(lac.data(), lac.size(), &info, &present, &scan_flags)
+                 : lacx_stream_parse(lac.data(), lac.size(), &info)) != LACX_OK) {  // structural errors need no device
         std::cerr << "Decode failed: " << lacx_decode_last_error() << "\n";
         return 1;
     }
@@ -147,7 +158,22 @@ int decode_command(int argc, char** argv) {
     }
     const uint8_t* wav = nullptr;
     uint64_t wav_size = 0;
-    if (lacx_decoder_decode_wav_view(dec, lac.data(), lac.size(), &wav, &wav_size, nullptr) != LACX_OK) {
+    lacx_span lac_span{lac.data(), lac.size()}, image{nullptr, 0};
+    lacx_salvage_result loss{};
+    std::vector<lacx_block_fault> faults;
+    if (salvage) {  // a batch of one, as a view: the file is written straight from the pinned image buffer
+        int item_rc = LACX_OK;
+        const int rc = lacx_decoder_salvage_wav_batch_view(dec, &lac_span, 1, &image, &item_rc, &loss, nullptr);
+        if (rc != LACX_OK) {
+            std::cerr << "Decode failed: " << (rc == LACX_E_DEVICE ? lacx_decode_last_error() : lacx_decoder_item_error(dec, 0)) << "\n";
+            lacx_decoder_destroy(dec);
+            return 1;
+        }
+        const lacx_block_fault* f = nullptr;
+        uint32_t nf = 0;
+        if (lacx_decoder_item_faults(dec, 0, &f, &nf) == LACX_OK) faults.assign(f, f + nf);
+        wav = image.data, wav_size = image.size;
+    } else if (lacx_decoder_decode_wav_view(dec, lac.data(), lac.size(), &wav, &wav_size, nullptr) != LACX_OK) {
         std::cerr << "Decode failed: " << lacx_decode_last_error() << "\n";
         lacx_decoder_destroy(dec);
         return 1;
@@ -166,13 +192,21 @@ int decode_command(int argc, char** argv) {
         return 1;
     }
     std::cout << "Decoded " << in_path << " -> " << out_path << " (" << info.frames << " samples per channel)\n";
+    if (salvage) {
+        for (const lacx_block_fault& f : faults)
+            std::cerr << "[salvage] block=" << f.block << " frames=" << f.frame << ".." << f.frame + f.frames - 1 << " "
+                      << lacx_block_fault_text(f.code) << "\n";
+        std::cerr << "[salvage] lost " << loss.bad_blocks << " of " << loss.blocks << " blocks, " << loss.lost_frames << " of "
+                  << loss.frames << " frames" << ((loss.flags & LACX_SALVAGE_TRUNCATED) ? ", file truncated" : "")
+                  << ((loss.flags & LACX_SALVAGE_TRAILING) ? ", trailing bytes ignored" : "") << "\n";
+    }
     if (debug_threads) {
         // The blocks are decoded on the device; on the host the call uses the calling thread, which is what the
         // reference reports for a one-thread run (ref :790-799).
         std::cout << "Decoder thread usage: 1 threads\n  " << std::this_thread::get_id() << "\n";
         std::cout << "WARNING: Decoder multi-threading may not be active.\n";
     }
-    return 0;
+    return salvage && loss.bad_blocks ? kExitSalvagedWithLoss : 0;
 }
 
 // lacx_cli verify input.lac input.wav: exit 0 when the stream decodes to exactly the WAV's samples in the WAV's format
