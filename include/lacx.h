@@ -41,6 +41,13 @@
  *   lacx_decoder_salvage_wav, lacx_decoder_salvage_wav_batch_view,
  *   lacx_decoder_salvage_batch_device <- beyond the reference (like `flac -F`): decode through errors, the blocks of a
  *                             damaged or truncated stream that still decode, silence where one does not
+ *   lacx_decoder_digest_blocks_batch_device, lacx_decoder_item_block_digests,
+ *   lacx_decoder_digest_pcm_blocks_batch_device,
+ *   lacx_manifest_build, lacx_manifest_parse,
+ *   lacx_decoder_check_batch_device,
+ *   lacx_decoder_salvage_wav_batch_view_checked,
+ *   lacx_decoder_salvage_batch_device_checked <- damage that still decodes: one CRC-32 per block, kept in a manifest
+ *                             beside the stream and honoured by the decoder (code 11, "digest mismatch")
  *
  * All analysis (and the decode) runs in hand-written HIP kernels on a gfx950 device; there is no CPU fallback: every
  * call that needs the device fails with LACX_E_DEVICE when none is usable.
@@ -144,7 +151,7 @@ void lacx_get_timing(const lacx_encoder* enc, lacx_timing* out);
 
 /* sizeof() of a public struct as this library was built, by name without the prefix ("config", "channel_plan",
  * "block_plan", "timing", "pcm", "batch_item", "batch_out", "wav_info", "fanout_shard", "fanout_out", "fanout_stats",
- * "stream_info", "span", "decode_item", "window_item", "verify_item", "verify_result", "digest", "digest_source", "block_fault", "salvage_result"); 0 for an unknown name.  A binding that declares the structs itself (ctypes, cgo, JNI) checks its layout
+ * "stream_info", "span", "decode_item", "window_item", "verify_item", "verify_result", "digest", "digest_source", "block_fault", "salvage_result", "block_digest", "manifest_info"); 0 for an unknown name.  A binding that declares the structs itself (ctypes, cgo, JNI) checks its layout
  * against this before the first call that fills one. */
 uint32_t lacx_sizeof(const char* struct_name);
 
@@ -596,7 +603,7 @@ uint32_t lacx_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
  * lacx_decoder_item_faults: the lost blocks of item i of the decoder's last salvage call, ascending by block; valid until
  *   the decoder's next call.  LACX_E_INVALID for an index outside that call.
  * lacx_block_fault_text: "block header", "channel header", "residual", "padding", "sample overflow", "trailing bytes",
- *   "sample outside the bit depth", "not reached", "residual beyond 2^30", "payload missing" for 1..10; "" for 0, else "?". */
+ *   "sample outside the bit depth", "not reached", "residual beyond 2^30", "payload missing" for 1..10, "digest mismatch" for 11 (LACX_BLOCK_DIGEST, below); "" for 0, else "?". */
 #define LACX_BLOCK_MISSING 10u
 #define LACX_SALVAGE_TRUNCATED 1u
 #define LACX_SALVAGE_TRAILING 2u
@@ -620,6 +627,68 @@ int lacx_decoder_salvage_batch_device(lacx_decoder* dec, const lacx_decode_item*
                                       int* item_rc, lacx_salvage_result* results, float* device_ms);
 int lacx_decoder_item_faults(const lacx_decoder* dec, uint32_t i, const lacx_block_fault** faults, uint32_t* count);
 const char* lacx_block_fault_text(uint32_t code);
+
+/* Block digests and manifests: finding damage that still decodes.  Salvage sees a block only when its lane or the range
+ * check refuses it; a flipped residual bit usually decodes cleanly to other samples inside the bit depth, and the LAC
+ * container has no checksum.  A manifest is a sidecar kept beside the stream: one CRC-32 per block of what the stream
+ * decodes to (the bytes that block has in the WAV data chunk), made on the device where the samples lie; the decoder
+ * honours it: a block that decodes to something else is lost with code 11, LACX_BLOCK_DIGEST, "digest mismatch".
+ * On the device k_digest_blocks runs behind the in-place mid/side inverse of a salvage job and adds every four-frame
+ * unit's value up at the end of its BLOCK; with a manifest k_digest_judge then compares and stores status 11 in front of
+ * the salvage pass, which blanks such a block like any other lost one.  4 bytes per block come back beside the statuses.
+ * Manifest, big-endian like the container, 32 + 8 * blocks bytes: "LACM", version 1, channels, bit depth, 0, sample rate
+ * u32, frames u64, blocks u32, data_crc32 u32 (of the whole data chunk: what lacx_decoder_digest_batch_device gives),
+ * per block frames u32 and crc32 u32, and the zlib CRC-32 of all bytes before it.
+ * lacx_decoder_digest_blocks_batch_device: lenient like salvage, versions 3 and 2: an item is LACX_OK whenever its
+ *   container is accepted.  lacx_decoder_item_block_digests then gives item i's rows, valid until the decoder's next call:
+ *   a row of a lost block carries its fault code (1..10) and crc32 0.  out[i] (nullable array) has data_crc32 / wav_crc32
+ *   only when every block decoded, made on the host from the rows with lacx_crc32_combine -- what
+ *   lacx_decoder_digest_batch_device gives for that stream; otherwise both are 0 and wav_valid is 0.
+ * lacx_decoder_digest_pcm_blocks_batch_device: device-resident source PCM on a regular grid of block_frames frames (0
+ *   means 16384; else 256..16384, anything else LACX_E_INVALID for the call); per-item checks, validation texts and bounds
+ *   exactly those of lacx_decoder_digest_pcm_batch_device.  The rows through lacx_decoder_item_block_digests.
+ * lacx_manifest_build: host only.  Refuses a row with code != 0 (LACX_E_INVALID, "manifest needs every block's digest:
+ *   block N is lost") and rows that do not fit d.  *out is malloc'd (lacx_free).
+ * lacx_manifest_parse: host only; rows nullable (rows_cap entries otherwise).  LACX_E_INVALID, each message starting
+ *   "[manifest-error] " (lacx_decode_last_error): short input, wrong magic, wrong version, size != 32 + 8 * blocks, wrong
+ *   own checksum, channels not 1 or 2, bit depth not 16 or 24, an unsupported sample rate, blocks = 0, a row of 0 or more
+ *   than 16384 frames, a non-final row below 256 frames, rows that do not sum to frames, a data_crc32 that is not the
+ *   lacx_crc32_combine of the rows.
+ * lacx_decoder_check_batch_device: is this stream intact?  No fault and not truncated: LACX_OK.  A fault or a truncation:
+ *   LACX_E_MISMATCH "[check-error] block=N <fault text> bad_blocks=M" (N the lowest bad block), results[i] filled as
+ *   salvage fills it, the blocks through lacx_decoder_item_faults, code 11 among them.  A difference in format:
+ *   LACX_E_MISMATCH "[check-error] <field>: stream A, manifest B" before any device work for that item (fields: channels,
+ *   bit depth, sample rate, frames, blocks, block N frames).  A refused manifest: LACX_E_INVALID with the parser's text; a
+ *   refused container keeps the strict code and text.  A version-2 block with status 8 is "not reached" and not judged.
+ * lacx_decoder_salvage_wav_batch_view_checked / lacx_decoder_salvage_batch_device_checked: the salvage forms with a
+ *   manifest per item; {NULL, 0} means plain salvage for that item.  A block whose digest differs is silence and is listed
+ *   with code 11.  An item whose manifest is refused or does not fit fails as in check and yields nothing.
+ * Everything else as lacx_decoder_decode_batch_device: the return code, "stream i: " prefixes, n = 0, null arrays,
+ * device-less behaviour and `stream`. */
+#define LACX_BLOCK_DIGEST 11u
+typedef struct lacx_block_digest { /* 16 bytes */
+    uint32_t frames, crc32;        /* crc32 of the block's bytes in the WAV data chunk; 0 for a lost block */
+    uint32_t code, reserved;       /* 0, or why the block is lost (1..10) */
+} lacx_block_digest;
+typedef struct lacx_manifest_info { /* 24 bytes */
+    uint32_t sample_rate, blocks;
+    uint64_t frames;
+    uint32_t data_crc32;
+    uint8_t channels, bit_depth, reserved[2];
+} lacx_manifest_info;
+int lacx_decoder_digest_blocks_batch_device(lacx_decoder* dec, const lacx_span* lacs, uint32_t n, void* stream, int* item_rc,
+                                            lacx_digest* out, float* device_ms);
+int lacx_decoder_item_block_digests(const lacx_decoder* dec, uint32_t i, const lacx_block_digest** rows, uint32_t* count);
+int lacx_decoder_digest_pcm_blocks_batch_device(lacx_decoder* dec, const lacx_digest_source* src, uint32_t n, uint32_t block_frames,
+                                                void* stream, int* item_rc, lacx_digest* out, float* device_ms);
+int lacx_manifest_build(const lacx_digest* d, const lacx_block_digest* rows, uint32_t count, uint8_t** out, uint64_t* size);
+int lacx_manifest_parse(const uint8_t* m, uint64_t size, lacx_manifest_info* info, lacx_block_digest* rows, uint32_t rows_cap);
+int lacx_decoder_check_batch_device(lacx_decoder* dec, const lacx_span* lacs, const lacx_span* manifests, uint32_t n, void* stream,
+                                    int* item_rc, lacx_salvage_result* results, float* device_ms);
+int lacx_decoder_salvage_wav_batch_view_checked(lacx_decoder* dec, const lacx_span* lacs, const lacx_span* manifests, uint32_t n,
+                                                lacx_span* out, int* item_rc, lacx_salvage_result* results, float* device_ms);
+int lacx_decoder_salvage_batch_device_checked(lacx_decoder* dec, const lacx_decode_item* items, const lacx_span* manifests, uint32_t n,
+                                              void* stream, int* item_rc, lacx_salvage_result* results, float* device_ms);
 
 /* Block::Encoder::encode drop-in for one channel block of n <= 16384 samples of ANY int32 value: blocks inside the 25-bit
  * mid/side domain of validated 16 / 24-bit input run on the streaming kernels, wider ones on a kernel of their own that

@@ -491,7 +491,8 @@ uint32_t lacx_sizeof(const char* name) {
                  {"window_item", sizeof(lacx_window_item)}, {"verify_item", sizeof(lacx_verify_item)},
                  {"verify_result", sizeof(lacx_verify_result)}, {"digest", sizeof(lacx_digest)},
                  {"digest_source", sizeof(lacx_digest_source)}, {"block_fault", sizeof(lacx_block_fault)},
-                 {"salvage_result", sizeof(lacx_salvage_result)}};
+                 {"salvage_result", sizeof(lacx_salvage_result)}, {"block_digest", sizeof(lacx_block_digest)},
+                 {"manifest_info", sizeof(lacx_manifest_info)}};
     for (const auto& t : table)
         if (std::strcmp(name, t.name) == 0) return (uint32_t)t.size;
     return 0;

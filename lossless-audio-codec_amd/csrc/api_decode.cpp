@@ -49,6 +49,7 @@ struct lacx_decoder {
     uint8_t* h_meta() const { return static_cast<uint8_t*>(tables.part[1].p); }
     std::vector<std::string> item_err;  // the last batch call's message per item ("" = decoded)
     std::vector<std::vector<lacx_block_fault>> item_faults;  // the last salvage call's lost blocks per item
+    std::vector<std::vector<lacx_block_digest>> item_rows;   // the last block digest call's rows per item
     std::string err;
 };
 
@@ -110,7 +111,7 @@ void wav_header(const lacx_stream_info& info, uint8_t* h) {
 const char* block_error(uint32_t st) {
     static const char* const kWhat[] = {"", "block header", "channel header", "residual", "padding", "sample overflow",
                                         "trailing bytes", "sample outside the bit depth", "not reached", "residual beyond 2^30"};
-    return st < 10 ? kWhat[st] : st == LACX_BLOCK_MISSING ? "payload missing" : "?";
+    return st < 10 ? kWhat[st] : st == LACX_BLOCK_MISSING ? "payload missing" : st == LACX_BLOCK_DIGEST ? "digest mismatch" : "?";
 }
 
 // A decode job: the items (BatchIn, DecodeForm, sample type: decode_plan.h) and where the call's answers go.
@@ -126,24 +127,42 @@ struct DecodeJob {
     lacx_digest* dres = nullptr;         // digest form: [n]
     bool salvage = false;                // wav and device forms: decode through errors (DecodePlan::salvage)
     lacx_salvage_result* sres = nullptr; // salvage: [n]
+    bool blocks = false;                 // salvage with block digests (DecodePlan::blocks); the items' manifests in BatchIn
+    bool check = false;                  // ... as a question: a fault or a truncation fails the item with LACX_E_MISMATCH
 };
 
 // What the digest kernel left for an item (DigestWords::raw), as the caller's record: the init term and the final xor
 // depend on the length alone, and the image's CRC-32 follows from its parts -- header, data, pad byte.
-lacx_digest make_digest(uint32_t raw, uint64_t frames, uint32_t sample_rate, uint8_t channels, uint8_t bit_depth) {
+// (crc_known: data_crc32 is the data chunk's finished CRC-32 -- the combination of block digests -- not a raw word)
+lacx_digest make_digest(uint32_t raw, uint64_t frames, uint32_t sample_rate, uint8_t channels, uint8_t bit_depth, bool crc_known = false) {
     lacx_digest g{};
     g.frames = frames;
     g.data_bytes = frames * channels * (bit_depth / 8u);
     g.sample_rate = sample_rate;
     g.channels = channels;
     g.bit_depth = bit_depth;
-    g.data_crc32 = crc_finish(raw, g.data_bytes);
+    g.data_crc32 = crc_known ? raw : crc_finish(raw, g.data_bytes);
     const uint64_t pad = g.data_bytes & 1u;
     g.wav_valid = 36u + g.data_bytes + pad < (1ull << 32) ? 1 : 0;
     if (g.wav_valid) {
         g.wav_crc32 = crc32_combine(crc32_wav_header(channels, bit_depth, sample_rate, g.data_bytes), g.data_crc32, g.data_bytes);
         if (pad) g.wav_crc32 = crc32_combine(g.wav_crc32, crc_finish(0u, 1), 1);  // (the raw value of a zero byte is 0)
     }
+    return g;
+}
+
+// The digest of an item from its block rows: the data chunk's CRC-32 is their combination, known only when every block
+// decoded; otherwise the format alone, both CRCs 0 and wav_valid 0.
+lacx_digest digest_of_rows(const std::vector<lacx_block_digest>& rows, uint64_t frames, uint32_t sample_rate, uint8_t channels, uint8_t bit_depth) {
+    const uint32_t align = (uint32_t)channels * (bit_depth / 8u);
+    uint32_t all = 0;
+    bool whole = !rows.empty();
+    for (size_t b = 0; b < rows.size(); ++b) {
+        whole = whole && rows[b].code == 0;
+        all = b ? crc32_combine(all, rows[b].crc32, (unsigned long long)rows[b].frames * align) : rows[b].crc32;
+    }
+    lacx_digest g = make_digest(whole ? all : 0u, frames, sample_rate, channels, bit_depth, true);
+    if (!whole) g.wav_crc32 = 0, g.wav_valid = 0;
     return g;
 }
 
@@ -251,6 +270,11 @@ DevErr launch_and_wait(lacx_decoder* d, const DecodeJob& job, const DecodePlan& 
     if (plan.form == DecodeForm::digest)
         if (DevErr e = chk(hipMemcpyAsync(d->h_meta() + res, d->d_meta() + res, sizeof(DigestWords) * m, hipMemcpyDeviceToHost, st), "D2H digests"))
             return e;
+    // block digests: 4 bytes per block beside the statuses
+    if (plan.blocks && plan.total_blocks)
+        if (DevErr e = chk(hipMemcpyAsync(d->h_meta() + plan.at.raw, d->d_meta() + plan.at.raw, 4 * (size_t)plan.total_blocks, hipMemcpyDeviceToHost, st),
+                           "D2H block digests"))
+            return e;
     if (DevErr e = chk(hipStreamSynchronize(st), "synchronize")) return e;
     if (job.device_ms) (void)hipEventElapsedTime(job.device_ms, d->e0, d->e1);
     return DevErr{};
@@ -267,6 +291,22 @@ DevErr collect(lacx_decoder* d, const DecodeJob& job, const DecodePlan& plan, hi
         if (plan.salvage) {  // every block's outcome, not the first: the status words and present_blocks are the whole report
             const lacx_salvage_result r = salvage_report(p, x.lac, d->h_status(), d->item_faults[i]);
             if (job.sres) job.sres[i] = r;
+            if (plan.blocks) {  // the rows: every block's frames and, where it decoded, its finished CRC-32
+                const uint32_t* raw = reinterpret_cast<const uint32_t*>(d->h_meta() + plan.at.raw) + p.item.block0;
+                const uint32_t align = (uint32_t)p.info.channels * (p.info.bit_depth / 8u);
+                std::vector<lacx_block_digest>& rows = d->item_rows[i];
+                rows.assign(p.item.blocks, lacx_block_digest{});
+                for (uint32_t b = 0; b < p.item.blocks; ++b) rows[b].frames = row_frames(x.lac, p.info.version, b);
+                for (const lacx_block_fault& f : d->item_faults[i]) rows[f.block].code = f.code;
+                for (uint32_t b = 0; b < p.item.blocks; ++b)
+                    if (!rows[b].code) rows[b].crc32 = crc_finish(raw[b], (unsigned long long)rows[b].frames * align);
+                if (job.dres) job.dres[i] = digest_of_rows(rows, p.info.frames, p.info.sample_rate, p.info.channels, p.info.bit_depth);
+                if (job.check && (r.bad_blocks || (r.flags & LACX_SALVAGE_TRUNCATED))) {
+                    code[i] = LACX_E_MISMATCH;
+                    err[i] = "[check-error] block=" + std::to_string(r.first_bad) + " " +
+                             block_error(r.bad_blocks ? d->item_faults[i][0].code : LACX_BLOCK_MISSING) + " bad_blocks=" + std::to_string(r.bad_blocks);
+                }
+            }
             if (plan.form == DecodeForm::wav) {
                 uint8_t* img = d->h_wav() + p.image_at;
                 wav_header(p.info, img);
@@ -328,17 +368,18 @@ int decode_batch_run(lacx_decoder* d, const DecodeJob& job, std::vector<int>& co
     if (job.dres) std::memset(job.dres, 0, sizeof(lacx_digest) * job.n);
     if (job.sres) std::memset(job.sres, 0, sizeof(lacx_salvage_result) * job.n);
     if (job.salvage) d->item_faults.assign(job.n, {});
+    if (job.blocks) d->item_rows.assign(job.n, {});
     // LACX_DECODE_BATCH_PAD=1 (tuning knob, read per call): every item's blocks start a new wave
     const char* pad_env = std::getenv("LACX_DECODE_BATCH_PAD");
     DecodePlan plan;
-    const char* whole = plan_decode(job.in, job.n, job.form, job.sample_type, pad_env && pad_env[0] == '1', plan, code, err, job.salvage);
+    const char* whole = plan_decode(job.in, job.n, job.form, job.sample_type, pad_env && pad_env[0] == '1', plan, code, err, job.salvage, job.blocks);
     if (lacx_device_count() <= 0) whole = "no usable HIP device";
     int rc = whole ? decode_fail(LACX_E_DEVICE, whole) : LACX_OK;
     if (!whole && !plan.items.empty()) {
         int prev_device = -1;
         DevErr e = decoder_open(d, &prev_device);
         // (d->stream: created by decoder_open)
-        hipStream_t st = job.form == DecodeForm::device || job.form == DecodeForm::digest || (job.form == DecodeForm::verify && !plan.host_src) ? job.stream : d->stream;
+        hipStream_t st = job.form == DecodeForm::device || job.form == DecodeForm::digest || job.form == DecodeForm::blocks || (job.form == DecodeForm::verify && !plan.host_src) ? job.stream : d->stream;
         if (!e) e = ensure_capacities(d, plan);
         if (!e) e = upload_tables(d, job, plan, st);
         if (!e) e = upload_payload(d, job, plan, st);
@@ -350,6 +391,8 @@ int decode_batch_run(lacx_decoder* d, const DecodeJob& job, std::vector<int>& co
     if (rc != LACX_OK) {  // the whole call failed: no item decoded
         if (job.sres) std::memset(job.sres, 0, sizeof(lacx_salvage_result) * job.n);
         if (job.salvage) d->item_faults.assign(job.n, {});
+        if (job.blocks) d->item_rows.assign(job.n, {});
+        if (job.dres) std::memset(job.dres, 0, sizeof(lacx_digest) * job.n);
         for (uint32_t i = 0; i < job.n; ++i) {
             if (code[i] != LACX_OK) continue;
             code[i] = rc;
@@ -560,8 +603,10 @@ const char* check_digest_source(const lacx_digest_source& x, std::string& text) 
 // The source form: no stream, no decode -- the items' records and the prefix sums of their unit counts in the decoder's
 // table buffers, k_digest over them on the caller's stream, and 16 bytes per item back (the result word and the lowest
 // invalid sample's key).  Table layout: src [m] | unit_off [m + 1] | res [m] | bad [m].
+// grid != 0: block digests on a regular grid of `grid` frames instead (k_digest_blocks); the tables then go on with
+// | block_off [m + 1] | raw [blocks], and every item's rows are left in d->item_rows.
 int digest_pcm_run(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, hipStream_t st, lacx_digest* out, float* device_ms,
-                   std::vector<int>& code, std::vector<std::string>& err) {
+                   std::vector<int>& code, std::vector<std::string>& err, uint32_t grid = 0) {
     if (device_ms) *device_ms = 0.f;
     if (out) std::memset(out, 0, sizeof(lacx_digest) * n);
     code.assign(n, LACX_OK);
@@ -578,16 +623,26 @@ int digest_pcm_run(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, h
     }
     int rc = lacx_device_count() <= 0 ? decode_fail(LACX_E_DEVICE, "no usable HIP device") : LACX_OK;
     const size_t m = went.size();
+    if (grid) d->item_rows.assign(n, {});
+    unsigned long long nblocks = 0;
+    for (size_t j = 0; grid && j < m; ++j) nblocks += (src[went[j]].frames + grid - 1u) / grid;
+    if (rc == LACX_OK && nblocks >= (1ull << 31)) rc = decode_fail(LACX_E_DEVICE, "batch holds 2^31 blocks or more");
     if (rc == LACX_OK && m) {
         const size_t at_off = sizeof(DigestSource) * m, at_res = at_off + 8 * (m + 1), at_bad = at_res + sizeof(DigestWords) * m,
-                     size = at_bad + 8 * m;
+                     at_blk = at_bad + 8 * m, at_raw = at_blk + (grid ? 8 * (m + 1) : 0), size = at_raw + 4 * (size_t)nblocks;
         int prev_device = -1;
         DevErr e = decoder_open(d, &prev_device);
         if (!e) e = buf_grow(d->tables, size, size / 8 + 256);
         if (!e) {
             auto* hs = reinterpret_cast<DigestSource*>(d->h_meta());
             auto* unit_off = reinterpret_cast<unsigned long long*>(d->h_meta() + at_off);
+            auto* block_off = reinterpret_cast<unsigned long long*>(d->h_meta() + at_blk);
             unit_off[0] = 0;
+            if (grid) {
+                block_off[0] = 0;
+                for (size_t j = 0; j < m; ++j) block_off[j + 1] = block_off[j] + (src[went[j]].frames + grid - 1u) / grid;
+                std::memset(d->h_meta() + at_raw, 0, 4 * (size_t)nblocks);
+            }
             for (size_t j = 0; j < m; ++j) {
                 const lacx_digest_source& x = src[went[j]];
                 hs[j] = DigestSource{x.pcm.data0, x.pcm.channels == 2 ? x.pcm.data1 : nullptr, x.frames, x.pcm.layout, (uint8_t)x.pcm.channels,
@@ -605,7 +660,12 @@ int digest_pcm_run(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, h
             a.bad = reinterpret_cast<unsigned long long*>(d->d_meta() + at_bad);
             e = chk(hipMemcpyAsync(d->d_meta(), d->h_meta(), size, hipMemcpyHostToDevice, st), "H2D digest tables");
             if (!e) e = chk(hipEventRecord(d->e0, st), "event record");
-            if (!e) e = chk(launch_digest_pcm(a, st), "digest launch");
+            BlockPcmArgs ba;
+            ba.pcm = a;
+            ba.grid = grid;
+            ba.block_off = reinterpret_cast<const unsigned long long*>(d->d_meta() + at_blk);
+            ba.raw = reinterpret_cast<uint32_t*>(d->d_meta() + at_raw);
+            if (!e) e = chk(grid ? launch_digest_pcm_blocks(ba, st) : launch_digest_pcm(a, st), "digest launch");
             if (!e) e = chk(hipEventRecord(d->e1, st), "event record");
             if (!e) e = chk(hipMemcpyAsync(d->h_meta() + at_res, d->d_meta() + at_res, size - at_res, hipMemcpyDeviceToHost, st), "D2H digests");
             if (!e) e = chk(hipStreamSynchronize(st), "synchronize");
@@ -628,12 +688,26 @@ int digest_pcm_run(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, h
                     code[i] = LACX_E_INVALID;
                     continue;
                 }
+                if (grid) {
+                    const auto* block_off = reinterpret_cast<const unsigned long long*>(d->h_meta() + at_blk);
+                    const uint32_t* braw = reinterpret_cast<const uint32_t*>(d->h_meta() + at_raw) + block_off[j];
+                    const uint32_t nb = (uint32_t)(block_off[j + 1] - block_off[j]), align = (uint32_t)x.pcm.channels * (x.bit_depth / 8u);
+                    std::vector<lacx_block_digest>& rows = d->item_rows[i];
+                    rows.assign(nb, lacx_block_digest{});
+                    for (uint32_t b = 0; b < nb; ++b) {
+                        rows[b].frames = b + 1u < nb ? grid : (uint32_t)(x.frames - (unsigned long long)grid * b);
+                        rows[b].crc32 = crc_finish(braw[b], (unsigned long long)rows[b].frames * align);
+                    }
+                    if (out) out[i] = digest_of_rows(rows, x.frames, x.sample_rate, (uint8_t)x.pcm.channels, x.bit_depth);
+                    continue;
+                }
                 const uint32_t raw = reinterpret_cast<const DigestWords*>(d->h_meta() + at_res)[j].raw;
                 if (out) out[i] = make_digest(raw, x.frames, x.sample_rate, (uint8_t)x.pcm.channels, x.bit_depth);
             }
         }
     }
     if (rc != LACX_OK) {  // the whole call failed: no item was digested
+        if (grid) d->item_rows.assign(n, {});
         for (uint32_t i = 0; i < n; ++i) {
             if (code[i] != LACX_OK) continue;
             code[i] = rc;
@@ -715,6 +789,106 @@ int lacx_decoder_salvage_batch_device(lacx_decoder* d, const lacx_decode_item* i
     job.in = in.data();
     job.n = n;
     return run_batch(d, job, item_rc);
+}
+
+// ---- block digests and manifests (lacx.h) ----
+namespace {
+// a salvage job with block digests: the blocks form (nothing is output), or a salvage form with manifests
+int run_blocks(lacx_decoder* d, std::vector<BatchIn>& in, const lacx_span* manifests, DecodeJob job, int* item_rc) {
+    for (size_t i = 0; manifests && i < in.size(); ++i) in[i].manifest = manifests[i].data, in[i].manifest_size = manifests[i].size;
+    job.in = in.data();
+    job.n = (uint32_t)in.size();
+    job.blocks = true;
+    return run_batch(d, job, item_rc);
+}
+}  // namespace
+
+int lacx_decoder_digest_blocks_batch_device(lacx_decoder* d, const lacx_span* lacs, uint32_t n, void* stream, int* item_rc, lacx_digest* out,
+                                            float* device_ms) {
+    if (!d) return decode_fail(LACX_E_INVALID, "null decoder");
+    if (!lacs || n == 0) return decode_fail(LACX_E_INVALID, "null argument or empty batch");
+    std::vector<BatchIn> in(n);
+    for (uint32_t i = 0; i < n; ++i) in[i] = BatchIn{lacs[i].data, lacs[i].size, nullptr, nullptr, 0};
+    DecodeJob job = salvage_job(DecodeForm::blocks, static_cast<hipStream_t>(stream), nullptr, nullptr, device_ms);
+    job.dres = out;
+    return run_blocks(d, in, nullptr, job, item_rc);
+}
+
+int lacx_decoder_check_batch_device(lacx_decoder* d, const lacx_span* lacs, const lacx_span* manifests, uint32_t n, void* stream, int* item_rc,
+                                    lacx_salvage_result* results, float* device_ms) {
+    if (!d) return decode_fail(LACX_E_INVALID, "null decoder");
+    if (!lacs || !manifests || n == 0) return decode_fail(LACX_E_INVALID, "null argument or empty batch");
+    std::vector<BatchIn> in(n);
+    for (uint32_t i = 0; i < n; ++i) in[i] = BatchIn{lacs[i].data, lacs[i].size, nullptr, nullptr, 0};
+    DecodeJob job = salvage_job(DecodeForm::blocks, static_cast<hipStream_t>(stream), nullptr, results, device_ms);
+    job.check = true;
+    return run_blocks(d, in, manifests, job, item_rc);
+}
+
+int lacx_decoder_salvage_wav_batch_view_checked(lacx_decoder* d, const lacx_span* lacs, const lacx_span* manifests, uint32_t n, lacx_span* out,
+                                                int* item_rc, lacx_salvage_result* results, float* device_ms) {
+    if (!d) return decode_fail(LACX_E_INVALID, "null decoder");
+    if (!lacs || !manifests || !out || n == 0) return decode_fail(LACX_E_INVALID, "null argument or empty batch");
+    std::vector<BatchIn> in(n);
+    for (uint32_t i = 0; i < n; ++i) in[i] = BatchIn{lacs[i].data, lacs[i].size, nullptr, nullptr, 0};
+    return run_blocks(d, in, manifests, salvage_job(DecodeForm::wav, nullptr, out, results, device_ms), item_rc);
+}
+
+int lacx_decoder_salvage_batch_device_checked(lacx_decoder* d, const lacx_decode_item* items, const lacx_span* manifests, uint32_t n, void* stream,
+                                              int* item_rc, lacx_salvage_result* results, float* device_ms) {
+    if (!d) return decode_fail(LACX_E_INVALID, "null decoder");
+    if (!items || !manifests || n == 0) return decode_fail(LACX_E_INVALID, "null argument or empty batch");
+    std::vector<BatchIn> in(n);
+    for (uint32_t i = 0; i < n; ++i) in[i] = BatchIn{items[i].lac, items[i].size, items[i].left, items[i].right, items[i].frames};
+    return run_blocks(d, in, manifests, salvage_job(DecodeForm::device, static_cast<hipStream_t>(stream), nullptr, results, device_ms), item_rc);
+}
+
+int lacx_decoder_digest_pcm_blocks_batch_device(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, uint32_t block_frames, void* stream,
+                                                int* item_rc, lacx_digest* out, float* device_ms) {
+    if (!d) return decode_fail(LACX_E_INVALID, "null decoder");
+    if (!src || n == 0) return decode_fail(LACX_E_INVALID, "null argument or empty batch");
+    if (block_frames != 0 && (block_frames < 256u || block_frames > (uint32_t)kMaxBlock)) return decode_fail(LACX_E_INVALID, "block_frames must be 0 or 256..16384");
+    std::vector<int> code;
+    std::vector<std::string> err;
+    const int rc = digest_pcm_run(d, src, n, static_cast<hipStream_t>(stream), out, device_ms, code, err, block_frames ? block_frames : (uint32_t)kMaxBlock);
+    if (item_rc) std::copy(code.begin(), code.end(), item_rc);
+    d->item_err = std::move(err);
+    if (rc != LACX_OK) return rc;
+    for (size_t i = 0; i < code.size(); ++i)
+        if (code[i] != LACX_OK) return decode_fail(code[i], "stream " + std::to_string(i) + ": " + d->item_err[i]);
+    return LACX_OK;
+}
+
+int lacx_decoder_item_block_digests(const lacx_decoder* d, uint32_t i, const lacx_block_digest** rows, uint32_t* count) {
+    if (rows) *rows = nullptr;
+    if (count) *count = 0;
+    if (!d || !rows || !count) return decode_fail(LACX_E_INVALID, "null argument");
+    if (i >= d->item_rows.size()) return decode_fail(LACX_E_INVALID, "no such item in the last block digest call");
+    *rows = d->item_rows[i].data();
+    *count = (uint32_t)d->item_rows[i].size();
+    return LACX_OK;
+}
+
+int lacx_manifest_build(const lacx_digest* dg, const lacx_block_digest* rows, uint32_t count, uint8_t** out, uint64_t* size) {
+    if (out) *out = nullptr;
+    if (size) *size = 0;
+    if (!dg || !rows || !out || !size || count == 0) return decode_fail(LACX_E_INVALID, "null argument or no rows");
+    std::vector<uint8_t> m;
+    std::string why;
+    const int rc = manifest_build(*dg, rows, count, m, why);
+    if (rc != LACX_OK) return decode_fail(rc, why);
+    uint8_t* buf = static_cast<uint8_t*>(std::malloc(m.size()));
+    if (!buf) return decode_fail(LACX_E_RUNTIME, "out of host memory");
+    std::memcpy(buf, m.data(), m.size());
+    *out = buf;
+    *size = m.size();
+    return LACX_OK;
+}
+
+int lacx_manifest_parse(const uint8_t* m, uint64_t size, lacx_manifest_info* info, lacx_block_digest* rows, uint32_t rows_cap) {
+    std::string why;
+    const int rc = manifest_parse(m, size, info, rows, rows_cap, why);
+    return rc == LACX_OK ? rc : decode_fail(rc, why);
 }
 
 int lacx_decoder_item_faults(const lacx_decoder* d, uint32_t i, const lacx_block_fault** faults, uint32_t* count) {

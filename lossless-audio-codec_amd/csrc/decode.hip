@@ -496,6 +496,11 @@ hipError_t launch_decode(const DecodeArgs& a, hipStream_t stream) {
         if (a.total_blocks) {
             hipLaunchKernelGGL(k_ms_inverse, dim3(a.total_blocks, kMaxBlock / 1024), dim3(256), 0, stream, a.blk_item, a.items,
                                a.frame_off, a.ms_flag, a.status);
+            if (a.block_raw) {  // the block digests of what decoded, then the judge: status 11 before anything leaves
+                hipError_t e = launch_digest_blocks(a, stream);
+                if (e != hipSuccess) return e;
+            }
+            if (a.no_output) return hipGetLastError();  // the blocks form: nothing leaves but statuses and digests
             if (a.wav) {
                 if (a.total_units)
                     hipLaunchKernelGGL(k_salvage_wav, dim3((uint32_t)((a.total_units + 255u) / 256u)), dim3(256), 0, stream, a.nitems,

@@ -11,6 +11,7 @@
 #include "container.h"
 #include "lacx.h"
 #include "lacx_types.h"
+#include "manifest.h"
 
 namespace lacx {
 
@@ -34,6 +35,9 @@ struct BatchIn {
     lacx_pcm pcm = {nullptr, nullptr, 0, 0};
     const uint8_t* host_src = nullptr;
     uint64_t host_src_bytes = 0;
+    // a job with block digests: the item's manifest, or null -- nothing is expected of its blocks
+    const uint8_t* manifest = nullptr;
+    uint64_t manifest_size = 0;
 };
 
 // Where the decoded items go.  wav: the images into the decoder's pinned image buffer (each item's 16-byte aligned, one
@@ -51,7 +55,12 @@ struct BatchIn {
 // The wav and device forms also come as salvage jobs (DecodePlan::salvage, lacx_decoder_salvage_*): the items are read
 // by scan_stream, so a version-3 file may end early -- only its present blocks get a lane, only their bytes are payload --
 // and the post pass is k_ms_inverse in place, then k_salvage_wav / k_salvage_blank over the final status words.
-enum class DecodeForm { wav, device, host, verify, digest };
+// A salvage job may carry block digests (DecodePlan::blocks, lacx_decoder_digest_blocks_* / _check_* / *_checked):
+// k_digest_blocks behind k_ms_inverse leaves one raw word per global block, and where an item has a manifest
+// (DecodePlan::judged) k_digest_judge compares them with the expected words and stores status 11 in front of the salvage
+// pass.  blocks: the form of such a job that outputs nothing -- the decoder's own PCM buffers as verify and digest have
+// them, and no salvage pass.
+enum class DecodeForm { wav, device, host, verify, digest, blocks };
 constexpr int kWholeStreams = -1;
 
 // One item that goes to the device (j counts these; the items that failed their checks are not among them).
@@ -68,22 +77,28 @@ struct PlanItem {
     WindowOut win;       // window job; left / right as above
     uint32_t present_blocks;  // the blocks whose bytes the file holds, a prefix: item.blocks but for a truncated salvage item
     uint32_t scan_flags;      // salvage job: LACX_SALVAGE_*
+    bool judged;              // a job with block digests: the item has a manifest, its rows' CRCs are `expect`
+    std::vector<uint32_t> expect;
 };
 
 // The tables the kernels read, one upload: items | byte_off [T + 1] | frame_off [T + 1] | unit_off [m + 1] | blk_item [T]
 // | lane_blk | v2_items, then for a window job | win [m], for the verify form | ver [m] | res [m], for the digest form
-// | res [m] at `win`, for a salvage job | present [m] (uint32) at `win` (byte offsets)
+// | res [m] at `win`, for a salvage job | present [m] (uint32) at `win` (byte offsets); with block digests behind that
+// | judged [m] (uint32) | raw [T] (uint32, 16-byte aligned) and for a judged job | expect [T] (uint32)
 struct TableLayout {
     size_t items, byte_off, frame_off, unit_off, blk_item, lane_blk, v2_items, win, res, size;
+    size_t judged = 0, raw = 0, expect = 0;  // block digests only
 };
 
 struct DecodePlan {
     DecodeForm form = DecodeForm::host;
     int sample_type = kWholeStreams;
-    bool salvage = false;  // wav and device forms of whole streams only
+    bool salvage = false;  // wav and device forms of whole streams only, and the blocks form
+    bool blocks = false;   // salvage job with block digests; judged: one item at least has a manifest
+    bool judged = false;
     bool window() const { return sample_type != kWholeStreams; }
     bool own_pcm() const { return form != DecodeForm::device || window(); }  // into the decoder's PCM buffers
-    bool post_units() const { return window() || form == DecodeForm::verify || form == DecodeForm::wav || form == DecodeForm::digest; }
+    bool post_units() const { return window() || form == DecodeForm::verify || form == DecodeForm::wav || form == DecodeForm::digest || blocks; }
     bool host_window() const { return form == DecodeForm::host && window(); }
     std::vector<PlanItem> items;
     // k_decode's lanes: lane g decodes global block lane_blk[g] (~0u: idle); version-3 blocks only, an item's in
@@ -135,6 +150,30 @@ inline const char* check_arrays(const BatchIn& x, const lacx_stream_info& f) {  
     return nullptr;
 }
 constexpr size_t up16(size_t v) { return (v + 15u) & ~(size_t)15u; }
+// A judged item: its manifest parsed (a refusal keeps the parser's text) and compared with the stream it is to judge --
+// the format and every block's frame count; a difference is an answer that needs no device.  expect: the rows' CRCs.
+inline int check_manifest(const BatchIn& x, const lacx_stream_info& f, std::vector<uint32_t>& expect, std::string& why) {
+    lacx_manifest_info mi{};
+    std::vector<lacx_block_digest> rows((size_t)(x.manifest_size >= kManifestFixed ? (x.manifest_size - kManifestFixed) / 8u : 0u));
+    const int rc = manifest_parse(x.manifest, x.manifest_size, &mi, rows.data(), (uint32_t)rows.size(), why);
+    if (rc != LACX_OK) return rc;
+    auto differs = [&](const std::string& field, uint64_t a, uint64_t b) {
+        why = "[check-error] " + field + ": stream " + std::to_string(a) + ", manifest " + std::to_string(b);
+        return LACX_E_MISMATCH;
+    };
+    if (mi.channels != f.channels) return differs("channels", f.channels, mi.channels);
+    if (mi.bit_depth != f.bit_depth) return differs("bit depth", f.bit_depth, mi.bit_depth);
+    if (mi.sample_rate != f.sample_rate) return differs("sample rate", f.sample_rate, mi.sample_rate);
+    if (mi.frames != f.frames) return differs("frames", f.frames, mi.frames);
+    if (mi.blocks != f.blocks) return differs("blocks", f.blocks, mi.blocks);
+    expect.resize(mi.blocks);
+    for (uint32_t b = 0; b < mi.blocks; ++b) {
+        const uint32_t n = row_frames(x.lac, f.version, b);
+        if (rows[b].frames != n) return differs("block " + std::to_string(b) + " frames", n, rows[b].frames);
+        expect[b] = rows[b].crc32;
+    }
+    return LACX_OK;
+}
 }  // namespace plan_detail
 
 // Plans n streams as one decode (a single stream is n = 1).  Every item is parsed and checked on the host; those that
@@ -145,17 +184,19 @@ constexpr size_t up16(size_t v) { return (v + 15u) & ~(size_t)15u; }
 // salvage: a salvage job (DecodeForm above): an item's blocks and frames are still the whole table's, its payload the
 // bytes of its present blocks.
 inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, int sample_type, bool pad_waves, DecodePlan& plan,
-                               std::vector<int>& code, std::vector<std::string>& err, bool salvage = false) {
+                               std::vector<int>& code, std::vector<std::string>& err, bool salvage = false, bool blocks = false) {
     using namespace plan_detail;
     plan = DecodePlan{};
     plan.form = form;
     plan.sample_type = sample_type;
     plan.salvage = salvage;
+    plan.blocks = blocks;
     const bool window = plan.window(), own_pcm = plan.own_pcm(), wav = form == DecodeForm::wav, verify = form == DecodeForm::verify,
-               digest = form == DecodeForm::digest;
+               digest = form == DecodeForm::digest, quiet = form == DecodeForm::blocks;
     code.assign(n, LACX_OK);
     err.assign(n, std::string());
-    if (salvage && (sample_type != kWholeStreams || (form != DecodeForm::wav && form != DecodeForm::device))) return "salvage is a whole-stream WAV or device job";
+    if (salvage && (sample_type != kWholeStreams || (form != DecodeForm::wav && form != DecodeForm::device && !quiet))) return "salvage is a whole-stream WAV or device job";
+    if ((quiet && !blocks) || (blocks && !salvage)) return "block digests belong to a salvage job";
     plan.items.reserve(n);
     uint32_t v3_blocks = 0;
     for (uint32_t i = 0; i < n; ++i) {
@@ -164,13 +205,19 @@ inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, i
         lacx_stream_info& f = p.info;
         const char* why = nullptr;
         int c = salvage ? scan_stream(x.lac, x.size, &f, &p.present_blocks, &p.scan_flags, &why) : parse_stream(x.lac, x.size, &f, &why);
-        if (c == LACX_OK && (why = window ? check_window(x, f) : verify ? check_source(x, f) : wav || digest ? nullptr : check_arrays(x, f)))
+        if (c == LACX_OK && (why = window ? check_window(x, f) : verify ? check_source(x, f) : wav || digest || quiet ? nullptr : check_arrays(x, f)))
             c = LACX_E_INVALID;
+        std::string text;
+        if (c == LACX_OK && blocks && x.manifest) {
+            p.judged = true;
+            if ((c = check_manifest(x, f, p.expect, text)) != LACX_OK) why = text.c_str();
+        }
         if (c != LACX_OK) {
             code[i] = c;
             err[i] = why;
             continue;
         }
+        plan.judged = plan.judged || p.judged;
         p.src = i;
         p.head = stream_head_bytes(f.version, f.blocks);
         uint32_t nb = f.blocks;
@@ -258,7 +305,12 @@ inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, i
     const size_t end = at.v2_items + 4 * plan.v2_items.size();
     at.win = up16(end);
     at.res = digest ? at.win : at.win + sizeof(VerifySource) * m;
-    at.size = salvage ? at.win + 4 * m : verify ? at.res + sizeof(VerifyWords) * m : digest ? at.res + sizeof(DigestWords) * m : window ? at.win + sizeof(WindowOut) * m : end;
+    if (blocks) {
+        at.judged = at.win + 4 * m;
+        at.raw = at.res = up16(at.judged + 4 * m);
+        at.expect = at.raw + 4 * T;
+    }
+    at.size = blocks ? at.expect + (plan.judged ? 4 * T : 0) : salvage ? at.win + 4 * m : verify ? at.res + sizeof(VerifyWords) * m : digest ? at.res + sizeof(DigestWords) * m : window ? at.win + sizeof(WindowOut) * m : end;
     plan.need.payload = (plan.host_src ? plan.src_at + plan.host_src_bytes : plan.total_pay) + kDecodeTailPad;
     plan.need.blocks = T;
     plan.need.pcm_frames = own_pcm ? plan.pcm_total : 0;
@@ -347,6 +399,14 @@ inline void plan_fill_tables(const DecodePlan& plan, const BatchIn* in, const Pl
         }
         if (plan.form == DecodeForm::digest) reinterpret_cast<DigestWords*>(h + at.res)[j] = DigestWords{0, 0};
         if (plan.salvage) reinterpret_cast<uint32_t*>(h + at.win)[j] = p.present_blocks;
+        if (plan.blocks) {
+            reinterpret_cast<uint32_t*>(h + at.judged)[j] = p.judged ? 1u : 0u;
+            std::memset(h + at.raw + 4 * (size_t)y.block0, 0, 4 * (size_t)y.blocks);
+            if (plan.judged) {
+                uint32_t* e = reinterpret_cast<uint32_t*>(h + at.expect) + y.block0;
+                for (uint32_t b = 0; b < y.blocks; ++b) e[b] = p.judged ? p.expect[b] : 0u;
+            }
+        }
     }
     if (!plan.lane_blk.empty()) std::memcpy(h + at.lane_blk, plan.lane_blk.data(), 4 * plan.lane_blk.size());
     if (!plan.v2_items.empty()) std::memcpy(h + at.v2_items, plan.v2_items.data(), 4 * plan.v2_items.size());
@@ -379,6 +439,12 @@ inline DecodeArgs plan_args(const DecodePlan& plan, const uint8_t* tables, const
         a.verify_res = reinterpret_cast<VerifyWords*>(const_cast<uint8_t*>(tables) + at.res);
     }
     if (plan.salvage) a.present = reinterpret_cast<const uint32_t*>(tables + at.win);
+    if (plan.blocks) {
+        a.block_raw = reinterpret_cast<uint32_t*>(const_cast<uint8_t*>(tables) + at.raw);
+        a.judged = reinterpret_cast<const uint32_t*>(tables + at.judged);
+        if (plan.judged) a.block_expect = reinterpret_cast<const uint32_t*>(tables + at.expect);
+        a.no_output = plan.form == DecodeForm::blocks;
+    }
     if (plan.form == DecodeForm::digest) a.digest = reinterpret_cast<DigestWords*>(const_cast<uint8_t*>(tables) + at.res);
     return a;
 }

@@ -1,5 +1,5 @@
 // kernels.h -- host-visible interface of the kernel translation units (k_front.hip, k_analyze.hip, k_emit.hip,
-// decode.hip, k_digest.hip, wide.hip, k_import.hip).
+// decode.hip, k_digest.hip, k_blockdigest.hip, wide.hip, k_import.hip).
 #pragma once
 #include <cstdlib>
 #include <hip/hip_runtime_api.h>
@@ -181,6 +181,12 @@ hipError_t launch_decode(const DecodeArgs& args, hipStream_t stream);
 // (launch_decode calls it for a job with DecodeArgs::digest), and the same kernel over device-resident source PCM.
 hipError_t launch_digest(const DecodeArgs& args, hipStream_t stream);
 hipError_t launch_digest_pcm(const DigestPcmArgs& args, hipStream_t stream);
+
+// Block digests (k_blockdigest.hip): k_digest_blocks over the units of a salvage job's items behind k_ms_inverse, then
+// k_digest_judge where the job has expected values (launch_decode calls it for a job with DecodeArgs::block_raw), and
+// k_digest_blocks over device-resident source PCM on a regular grid.
+hipError_t launch_digest_blocks(const DecodeArgs& args, hipStream_t stream);
+hipError_t launch_digest_pcm_blocks(const BlockPcmArgs& args, hipStream_t stream);
 
 // Block::Encoder::encode's analysis for one block of arbitrary int32 samples (wide.hip): d_res = scratch for the eleven
 // candidate residuals ([11][kMaxBlock] int32), d_plan receives the plan.

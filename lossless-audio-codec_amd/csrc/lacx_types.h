@@ -187,5 +187,20 @@ struct DecodeArgs {
     // words, in place of the other post passes): present[j] = the blocks of item j that had a lane; the status words
     // of the others were written by nobody
     const uint32_t* present = nullptr;
+    // block digests (non-null, salvage jobs only: k_digest_blocks behind k_ms_inverse, blockdigest_core.h): block_raw[g] is
+    // global block g's raw word (zero on entry).  block_expect (non-null: k_digest_judge behind it, in front of the
+    // salvage pass): the expected CRC-32 per global block, looked at for the blocks of the items with judged[j] != 0.
+    // no_output: the blocks form -- the items lie in the decoder's own buffers and no salvage pass follows
+    uint32_t* block_raw = nullptr;
+    const uint32_t* block_expect = nullptr;
+    const uint32_t* judged = nullptr;
+    bool no_output = false;
+};
+// Block digests of device-resident source PCM (k_digest_blocks<true>): the digest form's sources on a regular grid.
+struct BlockPcmArgs {
+    DigestPcmArgs pcm;                             // (res is not used)
+    uint32_t grid = 0;                             // frames per block, 256 .. 16384
+    const unsigned long long* block_off = nullptr; // [nitems + 1] prefix sums of ceil(frames / grid)
+    uint32_t* raw = nullptr;                       // [block_off[nitems]], zero on entry
 };
 }  // namespace lacx

@@ -114,6 +114,9 @@ EXPORTS = (
     "lacx_decoder_digest_batch_device", "lacx_decoder_digest_pcm_batch_device", "lacx_crc32_combine",
     "lacx_stream_scan", "lacx_decoder_salvage_wav_batch_view", "lacx_decoder_salvage_wav",
     "lacx_decoder_salvage_batch_device", "lacx_decoder_item_faults", "lacx_block_fault_text",
+    "lacx_decoder_digest_blocks_batch_device", "lacx_decoder_item_block_digests", "lacx_decoder_digest_pcm_blocks_batch_device",
+    "lacx_manifest_build", "lacx_manifest_parse", "lacx_decoder_check_batch_device",
+    "lacx_decoder_salvage_wav_batch_view_checked", "lacx_decoder_salvage_batch_device_checked",
 )
 
 
@@ -194,6 +197,19 @@ def lib():
         L.lacx_decoder_salvage_batch_device.argtypes = [C.c_void_p, C.POINTER(DecodeItem), C.c_uint32, C.c_void_p,
                                                         C.POINTER(C.c_int), C.POINTER(SalvageResult), C.POINTER(C.c_float)]
         L.lacx_decoder_item_faults.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.POINTER(BlockFault)), C.POINTER(C.c_uint32)]
+        L.lacx_decoder_digest_blocks_batch_device.argtypes = L.lacx_decoder_digest_batch_device.argtypes
+        L.lacx_decoder_item_block_digests.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.POINTER(BlockDigest)), C.POINTER(C.c_uint32)]
+        L.lacx_decoder_digest_pcm_blocks_batch_device.argtypes = [C.c_void_p, C.POINTER(DigestSource), C.c_uint32, C.c_uint32, C.c_void_p,
+                                                                  C.POINTER(C.c_int), C.POINTER(Digest), C.POINTER(C.c_float)]
+        L.lacx_manifest_build.argtypes = [C.POINTER(Digest), C.POINTER(BlockDigest), C.c_uint32, C.POINTER(C.POINTER(C.c_uint8)),
+                                          C.POINTER(C.c_uint64)]
+        L.lacx_manifest_parse.argtypes = [C.POINTER(C.c_uint8), C.c_uint64, C.POINTER(ManifestInfo), C.POINTER(BlockDigest), C.c_uint32]
+        L.lacx_decoder_check_batch_device.argtypes = [C.c_void_p, C.POINTER(Span), C.POINTER(Span), C.c_uint32, C.c_void_p,
+                                                      C.POINTER(C.c_int), C.POINTER(SalvageResult), C.POINTER(C.c_float)]
+        L.lacx_decoder_salvage_wav_batch_view_checked.argtypes = [C.c_void_p, C.POINTER(Span), C.POINTER(Span), C.c_uint32, C.POINTER(Span),
+                                                                  C.POINTER(C.c_int), C.POINTER(SalvageResult), C.POINTER(C.c_float)]
+        L.lacx_decoder_salvage_batch_device_checked.argtypes = [C.c_void_p, C.POINTER(DecodeItem), C.POINTER(Span), C.c_uint32, C.c_void_p,
+                                                                C.POINTER(C.c_int), C.POINTER(SalvageResult), C.POINTER(C.c_float)]
         L.lacx_block_fault_text.restype = C.c_char_p
         L.lacx_block_fault_text.argtypes = [C.c_uint32]
         L.lacx_decoder_item_error.restype = C.c_char_p
@@ -218,7 +234,8 @@ def abi_structs() -> dict:
             "fanout_out": FanoutOut, "fanout_stats": FanoutStats, "stream_info": StreamInfo, "span": Span,
             "decode_item": DecodeItem, "window_item": WindowItem, "verify_item": VerifyItem,
             "verify_result": VerifyResult, "digest": Digest, "digest_source": DigestSource,
-            "block_fault": BlockFault, "salvage_result": SalvageResult}
+            "block_fault": BlockFault, "salvage_result": SalvageResult, "block_digest": BlockDigest,
+            "manifest_info": ManifestInfo}
 
 
 def device_count() -> int:
@@ -780,6 +797,50 @@ class SalvageResult(C.Structure):
                 ("first_bad", C.c_uint32), ("flags", C.c_uint32)]
 
 
+BLOCK_DIGEST = 11                            # LACX_BLOCK_DIGEST: the block decodes, but not to what its manifest says
+
+
+class BlockDigest(C.Structure):
+    """One block of a stream or of source PCM: its frames and the CRC-32 (zlib.crc32) of the bytes it has in the WAV data
+    chunk; code != 0: the block is lost (1..10) and crc32 is 0."""
+    _fields_ = [("frames", C.c_uint32), ("crc32", C.c_uint32), ("code", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class ManifestInfo(C.Structure):
+    _fields_ = [("sample_rate", C.c_uint32), ("blocks", C.c_uint32), ("frames", C.c_uint64), ("data_crc32", C.c_uint32),
+                ("channels", C.c_uint8), ("bit_depth", C.c_uint8), ("reserved", C.c_uint8 * 2)]
+
+
+def manifest_build(digest: Digest, rows) -> bytes:
+    """The manifest (sidecar of block digests) of `digest` and its rows, as digest_blocks_batch / digest_pcm_blocks_batch
+    give them.  ValueError where a block is lost or the rows do not fit the digest.  Host only."""
+    arr = (BlockDigest * max(1, len(rows)))(*rows)
+    out, size = C.POINTER(C.c_uint8)(), C.c_uint64()
+    rc = lib().lacx_manifest_build(C.byref(digest), arr, C.c_uint32(len(rows)), C.byref(out), C.byref(size))
+    if rc != OK:
+        raise ValueError(lib().lacx_decode_last_error().decode(errors="replace"))
+    try:
+        return C.string_at(out, size.value)
+    finally:
+        lib().lacx_free(out)
+
+
+def manifest_parse(manifest: bytes):
+    """(ManifestInfo, [BlockDigest]) of a manifest; ValueError with the parser's "[manifest-error] ..." text.  Host only."""
+    buf = (C.c_uint8 * max(1, len(manifest))).from_buffer_copy(manifest if manifest else b"\0")
+    cap = max(1, (len(manifest) - 32) // 8) if len(manifest) >= 32 else 1
+    info, rows = ManifestInfo(), (BlockDigest * cap)()
+    if lib().lacx_manifest_parse(buf, C.c_uint64(len(manifest)), C.byref(info), rows, C.c_uint32(cap)) != OK:
+        raise ValueError(lib().lacx_decode_last_error().decode(errors="replace"))
+    return info, [_copy_struct(rows[b]) for b in range(info.blocks)]
+
+
+def _copy_struct(x):
+    out = type(x)()
+    C.memmove(C.byref(out), C.byref(x), C.sizeof(x))
+    return out
+
+
 def block_fault_text(code: int) -> str:
     return lib().lacx_block_fault_text(C.c_uint32(code)).decode()
 
@@ -1003,13 +1064,28 @@ class Decoder:
         C.memmove(C.byref(out), C.byref(r), C.sizeof(SalvageResult))
         return out
 
-    def salvage_wav(self, lac):
+    @staticmethod
+    def _manifest_spans(manifests, n):
+        """manifests[i]: bytes, or None (plain salvage for that item) -> (Span array, the buffers that back it)."""
+        if len(manifests) != n:
+            raise ValueError("one manifest (or None) per stream")
+        bufs = [None if m is None else np.frombuffer(m, dtype=np.uint8) for m in manifests]
+        spans = (Span * max(1, n))(*[Span(None, 0) if b is None else Span(b.ctypes.data_as(C.POINTER(C.c_uint8)), b.size) for b in bufs])
+        return spans, bufs
+
+    def salvage_wav(self, lac, manifests=None):
         """Decode through errors: (WAV image bytes, SalvageResult, [BlockFault]).  The image always has the stream's full
         frame count; blocks that do not decode -- or that a truncated file no longer holds -- are silence, listed in the
         fault list.  A clean stream gives decode_wav's bytes and no fault.  RuntimeError only where the container itself
-        is refused (stream_parse's message) or the call as a whole fails."""
+        is refused (stream_parse's message) or the call as a whole fails.
+        manifests: the stream's manifest (bytes); a block that decodes to something else is then silence too, code 11."""
         if self._h is None:
             raise RuntimeError("decoder is closed")
+        if manifests is not None:
+            try:
+                return self.salvage_wav_batch([lac], manifests=[manifests])[0]
+            except BatchDecodeError as e:
+                raise RuntimeError(e.errors[0]) from None
         buf = np.frombuffer(lac, dtype=np.uint8)
         out, size, ms, res = C.POINTER(C.c_uint8)(), C.c_uint64(), C.c_float(), SalvageResult()
         rc = lib().lacx_decoder_salvage_wav(self._h, buf.ctypes.data_as(C.POINTER(C.c_uint8)), C.c_uint64(buf.size), C.byref(out),
@@ -1022,21 +1098,28 @@ class Decoder:
         finally:
             lib().lacx_free(out)
 
-    def salvage_wav_batch(self, lacs) -> list:
+    def salvage_wav_batch(self, lacs, manifests=None) -> list:
         """Many streams salvaged as one device job: (WAV image bytes, SalvageResult, [BlockFault]) per item, None for an
-        item whose container is refused; those raise BatchDecodeError once the others are done."""
+        item whose container is refused; those raise BatchDecodeError once the others are done.
+        manifests: per item its manifest (bytes) or None; a block whose digest differs is silence, listed with code 11; an
+        item whose manifest is refused or does not fit its stream fails."""
         bufs = [np.frombuffer(x, dtype=np.uint8) for x in lacs]
         n = len(bufs)
         spans = (Span * max(1, n))(*[Span(b.ctypes.data_as(C.POINTER(C.c_uint8)), b.size) for b in bufs])
         outs = (Span * max(1, n))()
         res = (SalvageResult * max(1, n))()
-        rc, errors = self._batch(n, lambda rcs, ms: lib().lacx_decoder_salvage_wav_batch_view(
-            self._h, spans, C.c_uint32(n), outs, rcs, res, ms))
+        if manifests is not None:
+            mspans, _keep = self._manifest_spans(manifests, n)
+            rc, errors = self._batch(n, lambda rcs, ms: lib().lacx_decoder_salvage_wav_batch_view_checked(
+                self._h, spans, mspans, C.c_uint32(n), outs, rcs, res, ms))
+        else:
+            rc, errors = self._batch(n, lambda rcs, ms: lib().lacx_decoder_salvage_wav_batch_view(
+                self._h, spans, C.c_uint32(n), outs, rcs, res, ms))
         results = [None if (i in errors or not outs[i].data) else
                    (C.string_at(outs[i].data, outs[i].size), self._copy_result(res[i]), self._faults(i)) for i in range(n)]
         return self._raise_batch(rc, errors, results)
 
-    def salvage_batch_device(self, lacs, outputs, stream: int = 0) -> list:
+    def salvage_batch_device(self, lacs, outputs, stream: int = 0, manifests=None) -> list:
         """Many streams salvaged into caller-owned device arrays: outputs[i] = (left_ptr, right_ptr or None), int32 arrays
         of stream_scan(lacs[i])[0].frames each on the decoder's device.  Lost blocks are zeros; nothing outside
         [0, frames) is written.  Returns (StreamInfo, SalvageResult, [BlockFault]) per item, None where the container is
@@ -1054,8 +1137,13 @@ class Decoder:
             it.right = rp
             it.frames = sc[0].frames if sc is not None else 0
         res = (SalvageResult * max(1, n))()
-        rc, errors = self._batch(n, lambda rcs, ms: lib().lacx_decoder_salvage_batch_device(
-            self._h, items, C.c_uint32(n), C.c_void_p(stream), rcs, res, ms))
+        if manifests is not None:  # per item its manifest (bytes) or None, as salvage_wav_batch
+            mspans, _keep = self._manifest_spans(manifests, n)
+            rc, errors = self._batch(n, lambda rcs, ms: lib().lacx_decoder_salvage_batch_device_checked(
+                self._h, items, mspans, C.c_uint32(n), C.c_void_p(stream), rcs, res, ms))
+        else:
+            rc, errors = self._batch(n, lambda rcs, ms: lib().lacx_decoder_salvage_batch_device(
+                self._h, items, C.c_uint32(n), C.c_void_p(stream), rcs, res, ms))
         results = [None if i in errors else (scans[i][0], self._copy_result(res[i]), self._faults(i)) for i in range(n)]
         return self._raise_batch(rc, errors, results)
 
@@ -1207,6 +1295,80 @@ class Decoder:
         rc, errors = self._batch(n, lambda rcs, ms: lib().lacx_decoder_digest_pcm_batch_device(
             self._h, items, C.c_uint32(n), C.c_void_p(stream), rcs, out, ms))
         return self._raise_batch(rc, errors, [None if i in errors else out[i] for i in range(n)])
+
+    def _rows(self, i) -> list:
+        ptr, count = C.POINTER(BlockDigest)(), C.c_uint32()
+        if lib().lacx_decoder_item_block_digests(self._h, C.c_uint32(i), C.byref(ptr), C.byref(count)) != OK:
+            return []
+        return [_copy_struct(ptr[k]) for k in range(count.value)]  # copies: the rows die with the decoder's next call
+
+    def digest_blocks_batch(self, lacs, stream: int = 0) -> list:
+        """Many streams decoded and digested block by block as one device job, lenient like salvage: per item
+        (Digest, [BlockDigest]), None where the container is refused (those raise BatchDecodeError once the others are
+        done).  A lost block's row carries its fault code and crc32 0; the Digest's CRCs are those of digest_batch when
+        every block decoded, else 0."""
+        bufs = [np.frombuffer(x, dtype=np.uint8) for x in lacs]
+        n = len(bufs)
+        spans = (Span * max(1, n))(*[Span(b.ctypes.data_as(C.POINTER(C.c_uint8)), b.size) for b in bufs])
+        out = (Digest * max(1, n))()
+        rc, errors = self._batch(n, lambda rcs, ms: lib().lacx_decoder_digest_blocks_batch_device(
+            self._h, spans, C.c_uint32(n), C.c_void_p(stream), rcs, out, ms))
+        return self._raise_batch(rc, errors, [None if i in errors else (_copy_struct(out[i]), self._rows(i)) for i in range(n)])
+
+    def manifest(self, lac) -> bytes:
+        """The manifest of what `lac` decodes to; RuntimeError where the container is refused, ValueError where a block
+        does not decode."""
+        try:
+            digest, rows = self.digest_blocks_batch([lac])[0]
+        except BatchDecodeError as e:
+            raise RuntimeError(e.errors[0]) from None
+        return manifest_build(digest, rows)
+
+    def digest_pcm_blocks_batch(self, sources, block_frames: int = 16384, stream: int = 0) -> list:
+        """digest_pcm_batch block by block on a regular grid of block_frames frames (256..16384): per item
+        (Digest, [BlockDigest]) -- with the encoder's grid of 16384, the rows of the manifest of the .lac made from it."""
+        n = len(sources)
+        items = (DigestSource * max(1, n))()
+        for it, (pcm, rate, depth) in zip(items, sources):
+            if isinstance(pcm, (tuple, list)):
+                d0, d1, layout, channels, frames = pcm
+                it.pcm = Pcm(d0, d1, layout, channels)
+            else:
+                it.pcm, frames = pcm_of(pcm, depth)
+            it.frames, it.sample_rate, it.bit_depth = frames, rate, depth
+        out = (Digest * max(1, n))()
+        if self._h is None:
+            raise RuntimeError("decoder is closed")
+        rcs, ms = (C.c_int * max(1, n))(), C.c_float()
+        rc = lib().lacx_decoder_digest_pcm_blocks_batch_device(self._h, items, C.c_uint32(n), C.c_uint32(block_frames), C.c_void_p(stream),
+                                                               rcs, out, C.byref(ms))
+        self.last_ms = float(ms.value)
+        if rc == E_INVALID and all(rcs[i] == OK for i in range(n)):  # the call's own arguments
+            raise ValueError(lib().lacx_decode_last_error().decode(errors="replace"))
+        if rc == E_DEVICE:
+            raise RuntimeError(lib().lacx_decode_last_error().decode(errors="replace"))
+        errors = {i: lib().lacx_decoder_item_error(self._h, i).decode(errors="replace") for i in range(n) if rcs[i] != OK}
+        return self._raise_batch(rc, errors, [None if i in errors else (_copy_struct(out[i]), self._rows(i)) for i in range(n)])
+
+    def check_batch(self, lacs, manifests, stream: int = 0) -> list:
+        """Is each stream intact -- does every block decode to what its manifest says?  Per item (SalvageResult,
+        [BlockFault]); a damaged or truncated stream (E_MISMATCH, "[check-error] block=N ..."), a manifest of another
+        stream, a refused manifest or container raise BatchDecodeError once the others are done, with the results of the
+        damaged ones in place (None for the others that failed)."""
+        bufs = [np.frombuffer(x, dtype=np.uint8) for x in lacs]
+        n = len(bufs)
+        spans = (Span * max(1, n))(*[Span(b.ctypes.data_as(C.POINTER(C.c_uint8)), b.size) for b in bufs])
+        mspans, _keep = self._manifest_spans(manifests, n)
+        res = (SalvageResult * max(1, n))()
+        codes = []
+        def call(rcs, ms):
+            rc = lib().lacx_decoder_check_batch_device(self._h, spans, mspans, C.c_uint32(n), C.c_void_p(stream), rcs, res, ms)
+            codes.extend(rcs[i] for i in range(n))
+            return rc
+        rc, errors = self._batch(n, call)
+        results = [(self._copy_result(res[i]), self._faults(i)) if codes[i] == OK or (codes[i] == E_MISMATCH and res[i].blocks) else None
+                   for i in range(n)]
+        return self._raise_batch(rc, errors, results)
 
     def verify_wav(self, lac, wav) -> VerifyResult:
         """A .lac against the WAV file image it was made from (both in host memory): the image's data chunk goes to the

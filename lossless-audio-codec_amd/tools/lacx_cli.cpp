@@ -43,11 +43,14 @@ namespace {
 
 void usage() {
     std::cerr << "Usage:\n  lacx_cli encode input.wav output.lac [--stereo-mode=lr|ms] [--threads=N] [--debug-threads] [--debug-lpc] "
-                 "[--debug-stereo-est] [--debug-zr] [--debug-partitions] [--no-partitioning] [--verify] [--verify-against=other.wav]\n"
-                 "  lacx_cli decode input.lac output.wav [--threads=N] [--debug-threads] [--salvage]\n"
+                 "[--debug-stereo-est] [--debug-zr] [--debug-partitions] [--no-partitioning] [--verify] [--verify-against=other.wav] [--manifest=output.lacm]\n"
+                 "  lacx_cli decode input.lac output.wav [--threads=N] [--debug-threads] [--salvage] [--manifest=input.lacm]\n"
                  "      --salvage: decode through errors -- lost blocks become silence, one \"[salvage] block=N ...\" line each on\n"
                  "      stderr; exit 0 when nothing was lost, 3 when the file was written with blocks lost\n"
+                 "      --manifest (with --salvage): a block that decodes to something else than its manifest says is lost too\n"
                  "  lacx_cli verify input.lac input.wav\n"
+                 "  lacx_cli manifest input.lac output.lacm   (one CRC-32 per block of what the stream decodes to)\n"
+                 "  lacx_cli check input.lac input.lacm       (exit 0 intact, 1 damaged: one \"[check] block=N ...\" line each, 2 refused)\n"
                  "  lacx_cli digest FILE...   (.lac and .wav files, told apart by content)\n"
                  "  lacx_cli selftest\n";
 }
@@ -110,6 +113,110 @@ bool load_file(const std::string& path, std::vector<uint8_t>& data) {
     return true;
 }
 
+bool save_file(const std::string& path, const uint8_t* data, uint64_t size) {
+    const std::string tmp = path + ".lacx-partial";
+    bool ok = false;
+    {
+        std::ofstream out(tmp, std::ios::binary | std::ios::trunc);
+        ok = out && out.write(reinterpret_cast<const char*>(data), (std::streamsize)size) && out.flush();
+    }
+    ok = ok && std::rename(tmp.c_str(), path.c_str()) == 0;
+    if (!ok) std::remove(tmp.c_str());
+    return ok;
+}
+
+// The manifest of what a stream decodes to: its block digests from the device, built on the host.  err: why not.
+bool make_manifest(const uint8_t* lac, uint64_t size, std::vector<uint8_t>& out, std::string& err) {
+    lacx_decoder* dec = nullptr;
+    if (lacx_decoder_create(-1, &dec) != LACX_OK) return err = "lacx_decoder_create failed", false;
+    const lacx_span span{lac, size};
+    lacx_digest d{};
+    int item_rc = LACX_OK;
+    const lacx_block_digest* rows = nullptr;
+    uint32_t count = 0;
+    uint8_t* m = nullptr;
+    uint64_t msize = 0;
+    bool ok = false;
+    const int rc = lacx_decoder_digest_blocks_batch_device(dec, &span, 1, nullptr, &item_rc, &d, nullptr);
+    if (rc != LACX_OK) {
+        err = rc == LACX_E_DEVICE ? lacx_decode_last_error() : lacx_decoder_item_error(dec, 0);
+    } else if (lacx_decoder_item_block_digests(dec, 0, &rows, &count) != LACX_OK || lacx_manifest_build(&d, rows, count, &m, &msize) != LACX_OK) {
+        err = lacx_decode_last_error();
+    } else {
+        out.assign(m, m + msize);
+        lacx_free(m);
+        ok = true;
+    }
+    lacx_decoder_destroy(dec);
+    return ok;
+}
+
+// lacx_cli manifest input.lac output.lacm
+int manifest_command(char** argv) {
+    const std::string in_path = argv[2], out_path = argv[3];
+    if (same_file(in_path, out_path)) {
+        std::cerr << "Input and output paths must be different\n";
+        return 1;
+    }
+    std::vector<uint8_t> lac, m;
+    if (!load_file(in_path, lac)) {
+        std::cerr << "Failed to read LAC file: " << in_path << "\n";
+        return 1;
+    }
+    std::string err;
+    if (!make_manifest(lac.data(), lac.size(), m, err)) {
+        std::cerr << "Manifest failed: " << err << "\n";
+        return 1;
+    }
+    if (!save_file(out_path, m.data(), m.size())) {
+        std::cerr << "Failed to write manifest: " << out_path << "\n";
+        return 1;
+    }
+    std::cout << "Manifest " << in_path << " -> " << out_path << " (" << (m.size() - 32) / 8 << " blocks)\n";
+    return 0;
+}
+
+// lacx_cli check input.lac input.lacm: exit 0 when every block decodes to what the manifest says, 1 when the stream is
+// damaged or truncated (one line per bad block), 2 when stream or manifest are refused or do not belong together
+int check_command(char** argv) {
+    const std::string lac_path = argv[2], man_path = argv[3];
+    std::vector<uint8_t> lac, man;
+    if (!load_file(lac_path, lac)) {
+        std::cerr << "Failed to read LAC file: " << lac_path << "\n";
+        return 2;
+    }
+    if (!load_file(man_path, man)) {
+        std::cerr << "Failed to read manifest: " << man_path << "\n";
+        return 2;
+    }
+    lacx_decoder* dec = nullptr;
+    if (lacx_decoder_create(-1, &dec) != LACX_OK) {
+        std::cerr << "Error: lacx_decoder_create failed\n";
+        return 2;
+    }
+    const lacx_span ls{lac.data(), lac.size()}, ms{man.data(), man.size()};
+    lacx_salvage_result res{};
+    int item_rc = LACX_OK, status = 0;
+    const int rc = lacx_decoder_check_batch_device(dec, &ls, &ms, 1, nullptr, &item_rc, &res, nullptr);
+    if (rc == LACX_E_MISMATCH && res.blocks) {  // damaged: the device looked at it
+        const lacx_block_fault* f = nullptr;
+        uint32_t nf = 0;
+        if (lacx_decoder_item_faults(dec, 0, &f, &nf) == LACX_OK)
+            for (uint32_t k = 0; k < nf; ++k)
+                std::cerr << "[check] block=" << f[k].block << " frames=" << f[k].frame << ".." << f[k].frame + f[k].frames - 1 << " "
+                          << lacx_block_fault_text(f[k].code) << "\n";
+        std::cerr << "Check failed: " << lacx_decoder_item_error(dec, 0) << "\n";
+        status = 1;
+    } else if (rc != LACX_OK) {
+        std::cerr << "Check refused: " << (rc == LACX_E_DEVICE ? lacx_decode_last_error() : lacx_decoder_item_error(dec, 0)) << "\n";
+        status = 2;
+    } else {
+        std::cout << "Intact: " << lac_path << " (" << res.blocks << " blocks, " << res.frames << " samples per channel)\n";
+    }
+    lacx_decoder_destroy(dec);
+    return status;
+}
+
 constexpr int kExitSalvagedWithLoss = 3;  // decode --salvage: the WAV was written, with lost blocks as silence
 
 // lacx_cli decode input.lac output.wav [--threads=N] [--debug-threads] [--salvage] (ref src/main.cpp:712-781)
@@ -121,13 +228,16 @@ int decode_command(int argc, char** argv) {
     }
     bool debug_threads = false, salvage = false;
     unsigned long long threads = 0;
+    std::string manifest_path;
     for (int i = 4; i < argc; ++i) {
         const std::string flag = argv[i];
-        const std::string tprefix = "--threads=";
+        const std::string tprefix = "--threads=", mprefix = "--manifest=";
         if (flag == "--debug-threads") {
             debug_threads = true;
         } else if (flag == "--salvage") {
             salvage = true;
+        } else if (flag.compare(0, mprefix.size(), mprefix) == 0 && flag.size() > mprefix.size()) {
+            manifest_path = flag.substr(mprefix.size());
         } else if (flag.compare(0, tprefix.size(), tprefix) == 0) {
             if (!positive_integer(flag.substr(tprefix.size()), threads)) {
                 std::cerr << "Error: --threads requires a positive integer\n";
@@ -139,7 +249,15 @@ int decode_command(int argc, char** argv) {
         }
     }
     if (!resolve_threads(threads)) return 1;  // validated like encode's; the decode itself runs on the device
-    std::vector<uint8_t> lac;
+    if (!manifest_path.empty() && !salvage) {
+        std::cerr << "Error: --manifest belongs to --salvage (lacx_cli check answers for the strict decode)\n";
+        return 1;
+    }
+    std::vector<uint8_t> lac, man;
+    if (!manifest_path.empty() && !load_file(manifest_path, man)) {
+        std::cerr << "Failed to read manifest: " << manifest_path << "\n";
+        return 1;
+    }
     if (!load_file(in_path, lac)) {
         std::cerr << "Failed to read LAC file: " << in_path << "\n";
         return 1;
@@ -163,7 +281,9 @@ int decode_command(int argc, char** argv) {
     std::vector<lacx_block_fault> faults;
     if (salvage) {  // a batch of one, as a view: the file is written straight from the pinned image buffer
         int item_rc = LACX_OK;
-        const int rc = lacx_decoder_salvage_wav_batch_view(dec, &lac_span, 1, &image, &item_rc, &loss, nullptr);
+        const lacx_span man_span{man.data(), man.size()};
+        const int rc = manifest_path.empty() ? lacx_decoder_salvage_wav_batch_view(dec, &lac_span, 1, &image, &item_rc, &loss, nullptr)
+                                             : lacx_decoder_salvage_wav_batch_view_checked(dec, &lac_span, &man_span, 1, &image, &item_rc, &loss, nullptr);
         if (rc != LACX_OK) {
             std::cerr << "Decode failed: " << (rc == LACX_E_DEVICE ? lacx_decode_last_error() : lacx_decoder_item_error(dec, 0)) << "\n";
             lacx_decoder_destroy(dec);
@@ -450,6 +570,8 @@ int main(int argc, char** argv) {
     if (mode == "selftest" && argc == 2) return selftest_command();
     if (mode == "verify" && argc == 4) return verify_command(argv);
     if (mode == "digest" && argc >= 3) return digest_command(argc, argv);
+    if (mode == "manifest" && argc == 4) return manifest_command(argv);
+    if (mode == "check" && argc == 4) return check_command(argv);
     if (argc < 4 || (mode != "encode" && mode != "decode")) {
         usage();
         return 1;
@@ -464,10 +586,13 @@ int main(int argc, char** argv) {
     bool partitioning = true, debug_threads = false, debug_zr = false, verify = false;
     unsigned long long threads = 0;
     std::string verify_path;  // --verify-against: another copy of the source (the master the input was made from)
+    std::string manifest_path;  // --manifest: the manifest of what the written stream decodes to
     for (int i = 4; i < argc; ++i) {
         const std::string flag = argv[i];
-        const std::string tprefix = "--threads=", vprefix = "--verify-against=";
-        if (flag == "--no-partitioning") {
+        const std::string tprefix = "--threads=", vprefix = "--verify-against=", mprefix = "--manifest=";
+        if (flag.compare(0, mprefix.size(), mprefix) == 0 && flag.size() > mprefix.size()) {
+            manifest_path = flag.substr(mprefix.size());
+        } else if (flag == "--no-partitioning") {
             partitioning = false;
         } else if (flag == "--stereo-mode=lr") {
             stereo_mode = 0;
@@ -557,6 +682,16 @@ int main(int argc, char** argv) {
             return 1;
         }
         lacx_decoder_destroy(dec);
+    }
+    if (!manifest_path.empty()) {  // of the produced bytes, before anything is published; with --verify: the source's own
+        std::vector<uint8_t> m;
+        std::string err;
+        if (same_file(manifest_path, out_path) || same_file(manifest_path, in_path)) err = "the manifest needs a path of its own";
+        if (!err.empty() || !make_manifest(lac.data, lac.size, m, err) || !save_file(manifest_path, m.data(), m.size())) {
+            std::cerr << "Manifest failed: " << (err.empty() ? "cannot write " + manifest_path : err) << "\n";
+            lacx_encoder_destroy(enc);
+            return 1;
+        }
     }
     const std::string tmp = out_path + ".lacx-partial";
     bool ok = false;
