@@ -48,6 +48,11 @@
  *   lacx_decoder_salvage_wav_batch_view_checked,
  *   lacx_decoder_salvage_batch_device_checked <- damage that still decodes: one CRC-32 per block, kept in a manifest
  *                             beside the stream and honoured by the decoder (code 11, "digest mismatch")
+ *   lacx_recovery_build, lacx_recovery_build_batch_view, lacx_recovery_parse,
+ *   lacx_recovery_scan_batch, lacx_recovery_repair, lacx_recovery_repair_batch_view,
+ *   lacx_decoder_item_bad_slices <- bringing lost bytes back: a parity sidecar ("LACR", Reed-Solomon over GF(2^8)) beside
+ *                             the .lac file, made and used on the device; the manifest finds damage at the PCM level, this
+ *                             sidecar locates and repairs it at the byte level
  *
  * All analysis (and the decode) runs in hand-written HIP kernels on a gfx950 device; there is no CPU fallback: every
  * call that needs the device fails with LACX_E_DEVICE when none is usable.
@@ -689,6 +694,92 @@ int lacx_decoder_salvage_wav_batch_view_checked(lacx_decoder* dec, const lacx_sp
                                                 lacx_span* out, int* item_rc, lacx_salvage_result* results, float* device_ms);
 int lacx_decoder_salvage_batch_device_checked(lacx_decoder* dec, const lacx_decode_item* items, const lacx_span* manifests, uint32_t n,
                                               void* stream, int* item_rc, lacx_salvage_result* results, float* device_ms);
+
+/* Recovery data: repairing a damaged .lac file from a parity sidecar.  Digests, salvage and the manifest all end in "this
+ * block is lost"; the container has no redundancy of its own.  A recovery sidecar ("LACR") kept beside the file brings the
+ * exact original bytes back when the file has rotted or been cut short.  The two sidecars differ: the manifest (LACM)
+ * finds damage at the PCM level -- a block that decodes to other samples --, the recovery sidecar locates and repairs
+ * damage at the byte level and knows nothing of blocks; after a repair, lacx_decoder_check_batch_device with the manifest
+ * confirms it.
+ * The code is Reed-Solomon erasure coding over GF(2^8) (polynomial 0x11D, generator 2).  The protected object is the whole
+ * file of L >= 1 bytes, cut into k = ceil(L / S) slices, the last counted as zero-extended to S; a slice's CRC-32 (zlib)
+ * covers its real bytes only.  G = ceil(k / K) groups; slice i is member i div G of group i mod G -- interleaved, so a
+ * burst spreads over the groups --, group g has ceil((k - g) / G) members.  Parity slice p of group g is
+ * P[g][p][j] = XOR_i c(p, i) * D[g + i * G][j] with the Cauchy coefficient c(p, i) = 1 / (p XOR (r + i)); r + K <= 256
+ * keeps the two index sets apart, so every square submatrix is invertible: a group is repairable exactly when its damaged
+ * data slices number at most its usable parity slices, and any damaged byte range of up to (r * G - 1) * S + 1 bytes is
+ * repaired.  Parameters: slice_bytes S a multiple of 16 in 64..65536 (default 4096), parity r in 1..32 (default 8),
+ * group_data K in 1..256 - r (default 128); a zero field of lacx_recovery_params, or a null pointer, means the default.
+ * Sidecar, big-endian, 40 + 4k + G * r * (S + 4) bytes:
+ *   0 "LACR" | 4 version = 1 | 5 r | 6 K u16 | 8 S u32 | 12 L u64 | 20 file_crc32 u32 | 24 k u32 | 28 G u32 |
+ *   32 CRC-32 of bytes 0..31 | 36 k slice CRC-32 u32 | 36 + 4k CRC-32 of the slice table |
+ *   40 + 4k parity records in (g, p) order, each S bytes followed by their CRC-32 u32
+ * The head (bytes 0 .. 40 + 4k) must be intact and consistent -- k = ceil(L / S), G = ceil(k / K), the parameter ranges,
+ * file_crc32 the lacx_crc32_combine of the slice CRCs --, else the sidecar is refused: LACX_E_INVALID, the message starting
+ * "[recovery-error] ".  The parity area is treated leniently, the way salvage treats a payload: a parity record counts
+ * only when it lies wholly inside the sidecar and its CRC matches; a short sidecar is flagged
+ * (LACX_REPAIR_SIDECAR_TRUNCATED), not refused, and bytes behind the last record are ignored.
+ * On the device (k_recovery.hip): k_slice_crc makes one CRC-32 per slice and parity record, all items of a batch in one
+ * launch; k_gf_combine computes out[o] = XOR_i M[o][i] * in[i] per group -- with the Cauchy rows it makes parity, with the
+ * matrix the host solved (the inverse of the <= 32 x 32 Cauchy submatrix of the lowest usable parity rows, folded with the
+ * surviving slices' coefficients) it rebuilds the lost slices.  A repair is two round trips: slice CRCs come down (4 bytes
+ * per slice), solved matrices go up, the output comes down.
+ * All calls take a lacx_decoder handle -- its device, stream and grow-only buffers -- and follow lacx_decoder_decode_batch_device:
+ * item_rc, lacx_decoder_item_error, "stream i: " prefixes, n = 0 or null arrays LACX_E_INVALID; without a device the
+ * host-side outcomes (refused files, sidecars and parameters) are still filled and the call returns LACX_E_DEVICE.
+ * lacx_recovery_build_batch_view: out[i] = item i's sidecar in the decoder's pinned buffer, valid until its next call.
+ *   Refuses a file that lacx_stream_parse refuses, with that parser's code and text, and parameters out of range with
+ *   LACX_E_INVALID "[recovery-error] ..." (the whole call).  lacx_recovery_build: a batch of one, *out malloc'd (lacx_free).
+ * lacx_recovery_parse: host only: the head's fields; parity_present = the records that lie wholly inside the sidecar
+ *   (their checksums are not looked at), flags = LACX_REPAIR_SIDECAR_TRUNCATED or 0.
+ * The input of scan and repair is the file's first min(size, L) bytes, zero-extended to L; a slice is damaged when the
+ * CRC-32 of its bytes in that input is not the table's.  results[i]: first_bad = the lowest damaged slice (== slices when
+ * none), parity_slices = G * r, bad_parity = those that are missing or fail their CRC, worst_group = the group with the
+ * largest (damaged slices - usable parity slices), the lowest of equals, with its two counts; flags LACX_REPAIR_*.
+ * lacx_decoder_item_bad_slices: the damaged slices of item i of the last scan or repair call, ascending, valid until the
+ * decoder's next call.
+ * lacx_recovery_scan_batch locates damage only: LACX_OK when intact and not truncated, else LACX_E_MISMATCH
+ *   "[recovery-error] slice=N bad_slices=M repairable|unrepairable" (N = first_bad), the result filled.
+ * lacx_recovery_repair_batch_view: out[i] in the decoder's pinned buffer.  An intact file: LACX_OK and a copy of its L
+ *   bytes.  A fully repaired file: LACX_OK, L bytes; its repaired slices are digested again on the device and the file's
+ *   combined CRC-32 equals file_crc32.  A group beyond capacity: LACX_E_MISMATCH "[recovery-error] group G: B damaged
+ *   slices, P parity slices usable" for the lowest such group, LACX_REPAIR_UNREPAIRED set, out[i] = {NULL, 0}; with
+ *   LACX_REPAIR_BEST_EFFORT out[i] is the L bytes with every repairable group repaired and the rest as found, the code
+ *   still LACX_E_MISMATCH.  A rebuilt slice whose CRC differs (a CRC collision hid a damaged slice): LACX_E_MISMATCH
+ *   "[recovery-error] repaired file does not match its checksum" and no output.  repaired_slices counts what the output
+ *   holds rebuilt.  lacx_recovery_repair: a batch of one, *out malloc'd. */
+typedef struct lacx_recovery_params { /* 8 bytes; zeros = defaults */
+    uint32_t slice_bytes;
+    uint16_t parity, group_data;
+} lacx_recovery_params;
+typedef struct lacx_recovery_info { /* 40 bytes */
+    uint64_t file_bytes;
+    uint32_t file_crc32, slice_bytes, slices, groups;
+    uint16_t parity, group_data;
+    uint32_t parity_present, flags, reserved;
+} lacx_recovery_info;
+typedef struct lacx_repair_result { /* 48 bytes */
+    uint64_t file_bytes;
+    uint32_t slices, bad_slices, repaired_slices, first_bad, parity_slices, bad_parity, worst_group, worst_group_bad,
+        worst_group_parity, flags;
+} lacx_repair_result;
+#define LACX_REPAIR_TRUNCATED 1u         /* file shorter than L */
+#define LACX_REPAIR_TRAILING 2u          /* bytes behind L ignored */
+#define LACX_REPAIR_SIDECAR_TRUNCATED 4u
+#define LACX_REPAIR_UNREPAIRED 8u
+#define LACX_REPAIR_BEST_EFFORT 1u       /* call flag */
+int lacx_recovery_build_batch_view(lacx_decoder* dec, const lacx_span* lacs, uint32_t n, const lacx_recovery_params* params, lacx_span* out,
+                                   int* item_rc, float* device_ms);
+int lacx_recovery_build(lacx_decoder* dec, const uint8_t* lac, uint64_t size, const lacx_recovery_params* params, uint8_t** out,
+                        uint64_t* out_size, float* device_ms);
+int lacx_recovery_parse(const uint8_t* sidecar, uint64_t size, lacx_recovery_info* info);
+int lacx_recovery_scan_batch(lacx_decoder* dec, const lacx_span* files, const lacx_span* sidecars, uint32_t n, int* item_rc,
+                             lacx_repair_result* results, float* device_ms);
+int lacx_recovery_repair_batch_view(lacx_decoder* dec, const lacx_span* files, const lacx_span* sidecars, uint32_t n, uint32_t flags,
+                                    lacx_span* out, int* item_rc, lacx_repair_result* results, float* device_ms);
+int lacx_recovery_repair(lacx_decoder* dec, const uint8_t* file, uint64_t size, const uint8_t* sidecar, uint64_t sidecar_size, uint32_t flags,
+                         uint8_t** out, uint64_t* out_size, lacx_repair_result* result, float* device_ms);
+int lacx_decoder_item_bad_slices(const lacx_decoder* dec, uint32_t i, const uint32_t** slices, uint32_t* count);
 
 /* Block::Encoder::encode drop-in for one channel block of n <= 16384 samples of ANY int32 value: blocks inside the 25-bit
  * mid/side domain of validated 16 / 24-bit input run on the streaming kernels, wider ones on a kernel of their own that

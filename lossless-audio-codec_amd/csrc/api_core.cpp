@@ -492,7 +492,8 @@ uint32_t lacx_sizeof(const char* name) {
                  {"verify_result", sizeof(lacx_verify_result)}, {"digest", sizeof(lacx_digest)},
                  {"digest_source", sizeof(lacx_digest_source)}, {"block_fault", sizeof(lacx_block_fault)},
                  {"salvage_result", sizeof(lacx_salvage_result)}, {"block_digest", sizeof(lacx_block_digest)},
-                 {"manifest_info", sizeof(lacx_manifest_info)}};
+                 {"manifest_info", sizeof(lacx_manifest_info)},   {"recovery_params", sizeof(lacx_recovery_params)},
+                 {"recovery_info", sizeof(lacx_recovery_info)}, {"repair_result", sizeof(lacx_repair_result)}};
     for (const auto& t : table)
         if (std::strcmp(name, t.name) == 0) return (uint32_t)t.size;
     return 0;

@@ -1,6 +1,7 @@
 // api_decode.cpp -- the decode entry points of the C ABI: container parsing and the device decoder's host side.
 #include "crc32_core.h"
 #include "decode_plan.h"
+#include "decoder_impl.h"
 #include "device_buf.h"
 #include "encoder_impl.h"
 #include "import_msg.h"
@@ -9,11 +10,13 @@
 // ---- decode -------------------------------------------------------------------------------------
 namespace {
 thread_local std::string g_decode_err;
+}  // namespace
+namespace lacx_host {
 int decode_fail(int code, const std::string& msg) {
     g_decode_err = msg;
     return code;
 }
-}  // namespace
+}  // namespace lacx_host
 
 const char* lacx_decode_last_error(void) { return g_decode_err.c_str(); }
 
@@ -22,36 +25,6 @@ int lacx_stream_parse(const uint8_t* lac, uint64_t size, lacx_stream_info* out) 
     const int c = parse_stream(lac, size, out, &why);
     return c == LACX_OK ? c : decode_fail(c, why);
 }
-
-// The decoder object: device buffers, a stream and two events that live from call to call (grow-only), so that a decode
-// costs its copies and its kernel, not six allocations (ref LAC::Decoder is an object too, src/codec/lac/decoder.hpp:10-24).
-struct lacx_decoder {
-    int device = -1;  // -1: whatever device is current at the first call
-    bool ready = false;
-    hipStream_t stream = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    Buf pay{{{false, 1, "hipMalloc(payload)"}}};
-    Buf stage{{{true, 1, "hipHostMalloc(payload stage)"}}};  // the window form's payload ranges, gathered for one H2D copy
-    Buf pcm{{{false, 4, "hipMalloc(left)"}, {false, 4, "hipMalloc(right)"}}};  // both channels, whatever the streams' count
-    Buf blocks{{{false, 4, "hipMalloc(status)"}, {false, 1, "hipMalloc(flags)"}, {true, 4, "hipHostMalloc(status)"}}};
-    Buf image{{{false, 1, "hipMalloc(wav)"}, {true, 1, "hipHostMalloc(wav)"}}};  // WAV images (header + data + pad), host windows
-    Buf tables{{{false, 1, "hipMalloc(batch tables)"}, {true, 1, "hipHostMalloc(batch tables)"}}};  // one upload (TableLayout)
-    uint8_t* d_pay() const { return static_cast<uint8_t*>(pay.part[0].p); }
-    uint8_t* h_pay() const { return static_cast<uint8_t*>(stage.part[0].p); }
-    int32_t* d_left() const { return static_cast<int32_t*>(pcm.part[0].p); }
-    int32_t* d_right() const { return static_cast<int32_t*>(pcm.part[1].p); }
-    uint32_t* d_status() const { return static_cast<uint32_t*>(blocks.part[0].p); }
-    uint8_t* d_ms() const { return static_cast<uint8_t*>(blocks.part[1].p); }
-    uint32_t* h_status() const { return static_cast<uint32_t*>(blocks.part[2].p); }
-    uint8_t* d_wav() const { return static_cast<uint8_t*>(image.part[0].p); }
-    uint8_t* h_wav() const { return static_cast<uint8_t*>(image.part[1].p); }  // behind lacx_decoder_decode_wav_view
-    uint8_t* d_meta() const { return static_cast<uint8_t*>(tables.part[0].p); }
-    uint8_t* h_meta() const { return static_cast<uint8_t*>(tables.part[1].p); }
-    std::vector<std::string> item_err;  // the last batch call's message per item ("" = decoded)
-    std::vector<std::vector<lacx_block_fault>> item_faults;  // the last salvage call's lost blocks per item
-    std::vector<std::vector<lacx_block_digest>> item_rows;   // the last block digest call's rows per item
-    std::string err;
-};
 
 namespace {
 void decoder_release(lacx_decoder* d) {
@@ -166,7 +139,9 @@ lacx_digest digest_of_rows(const std::vector<lacx_block_digest>& rows, uint64_t 
     return g;
 }
 
+}  // namespace
 // ---- the steps of a run (decode_batch_run) ----
+namespace lacx_host {
 DevErr decoder_open(lacx_decoder* d, int* prev_device) {  // *prev_device: to put back, or -1
     *prev_device = -1;
     if (!d->ready && d->device < 0)
@@ -185,6 +160,8 @@ DevErr decoder_open(lacx_decoder* d, int* prev_device) {  // *prev_device: to pu
     }
     return DevErr{};
 }
+}  // namespace lacx_host
+namespace {
 
 // The plan's capacities, each buffer with its own slack: the image buffer and the PCM buffers grow to what is asked.
 DevErr ensure_capacities(lacx_decoder* d, const DecodePlan& plan) {

@@ -1,0 +1,47 @@
+// decoder_impl.h -- the decoder object behind lacx_decoder*, shared by the translation units of its entry points
+// (api_decode.cpp: decode, verify, digest, salvage, manifests; api_recovery.cpp: recovery data).
+#pragma once
+#include <string>
+#include <vector>
+
+#include "device_buf.h"
+#include "lacx.h"
+
+// The decoder object: device buffers, a stream and two events that live from call to call (grow-only), so that a decode
+// costs its copies and its kernel, not six allocations (ref LAC::Decoder is an object too, src/codec/lac/decoder.hpp:10-24).
+struct lacx_decoder {
+    int device = -1;  // -1: whatever device is current at the first call
+    bool ready = false;
+    hipStream_t stream = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    lacx::Buf pay{{{false, 1, "hipMalloc(payload)"}}};             // (recovery data: the arena of a job)
+    lacx::Buf stage{{{true, 1, "hipHostMalloc(payload stage)"}}};  // the window form's payload ranges, gathered for one H2D copy
+                                                                    // (recovery data: the sidecars or files a call hands out)
+    lacx::Buf pcm{{{false, 4, "hipMalloc(left)"}, {false, 4, "hipMalloc(right)"}}};  // both channels, whatever the streams' count
+    lacx::Buf blocks{{{false, 4, "hipMalloc(status)"}, {false, 1, "hipMalloc(flags)"}, {true, 4, "hipHostMalloc(status)"}}};
+    lacx::Buf image{{{false, 1, "hipMalloc(wav)"}, {true, 1, "hipHostMalloc(wav)"}}};  // WAV images (header + data + pad), host windows
+    lacx::Buf tables{{{false, 1, "hipMalloc(batch tables)"}, {true, 1, "hipHostMalloc(batch tables)"}}};  // one upload (TableLayout)
+    uint8_t* d_pay() const { return static_cast<uint8_t*>(pay.part[0].p); }
+    uint8_t* h_pay() const { return static_cast<uint8_t*>(stage.part[0].p); }
+    int32_t* d_left() const { return static_cast<int32_t*>(pcm.part[0].p); }
+    int32_t* d_right() const { return static_cast<int32_t*>(pcm.part[1].p); }
+    uint32_t* d_status() const { return static_cast<uint32_t*>(blocks.part[0].p); }
+    uint8_t* d_ms() const { return static_cast<uint8_t*>(blocks.part[1].p); }
+    uint32_t* h_status() const { return static_cast<uint32_t*>(blocks.part[2].p); }
+    uint8_t* d_wav() const { return static_cast<uint8_t*>(image.part[0].p); }
+    uint8_t* h_wav() const { return static_cast<uint8_t*>(image.part[1].p); }  // behind lacx_decoder_decode_wav_view
+    uint8_t* d_meta() const { return static_cast<uint8_t*>(tables.part[0].p); }
+    uint8_t* h_meta() const { return static_cast<uint8_t*>(tables.part[1].p); }
+    std::vector<std::string> item_err;  // the last batch call's message per item ("" = decoded)
+    std::vector<std::vector<lacx_block_fault>> item_faults;  // the last salvage call's lost blocks per item
+    std::vector<std::vector<lacx_block_digest>> item_rows;   // the last block digest call's rows per item
+    std::vector<std::vector<uint32_t>> item_bad;             // the last recovery scan / repair call's damaged slices per item
+    std::string err;
+};
+
+namespace lacx_host {
+// keeps msg for lacx_decode_last_error (per thread) and returns code
+int decode_fail(int code, const std::string& msg);
+// makes the decoder's device current, creating its stream and events at the first call; *prev_device: to put back, or -1
+lacx::DevErr decoder_open(lacx_decoder* d, int* prev_device);
+}  // namespace lacx_host

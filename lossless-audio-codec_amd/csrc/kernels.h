@@ -1,11 +1,12 @@
 // kernels.h -- host-visible interface of the kernel translation units (k_front.hip, k_analyze.hip, k_emit.hip,
-// decode.hip, k_digest.hip, k_blockdigest.hip, wide.hip, k_import.hip).
+// decode.hip, k_digest.hip, k_blockdigest.hip, k_recovery.hip, wide.hip, k_import.hip).
 #pragma once
 #include <cstdlib>
 #include <hip/hip_runtime_api.h>
 
 #include "import_core.h"
 #include "lacx_types.h"
+#include "recovery_core.h"
 
 namespace lacx {
 
@@ -187,6 +188,10 @@ hipError_t launch_digest_pcm(const DigestPcmArgs& args, hipStream_t stream);
 // k_digest_blocks over device-resident source PCM on a regular grid.
 hipError_t launch_digest_blocks(const DecodeArgs& args, hipStream_t stream);
 hipError_t launch_digest_pcm_blocks(const BlockPcmArgs& args, hipStream_t stream);
+
+// Recovery data (k_recovery.hip, recovery_core.h): k_gf_combine over the task table, one launch per accumulator tier that
+// has tasks, then k_slice_crc over the listed byte ranges.
+hipError_t launch_recovery(const RecoveryArgs& args, hipStream_t stream);
 
 // Block::Encoder::encode's analysis for one block of arbitrary int32 samples (wide.hip): d_res = scratch for the eleven
 // candidate residuals ([11][kMaxBlock] int32), d_plan receives the plan.

@@ -117,6 +117,8 @@ EXPORTS = (
     "lacx_decoder_digest_blocks_batch_device", "lacx_decoder_item_block_digests", "lacx_decoder_digest_pcm_blocks_batch_device",
     "lacx_manifest_build", "lacx_manifest_parse", "lacx_decoder_check_batch_device",
     "lacx_decoder_salvage_wav_batch_view_checked", "lacx_decoder_salvage_batch_device_checked",
+    "lacx_recovery_build_batch_view", "lacx_recovery_build", "lacx_recovery_parse", "lacx_recovery_scan_batch",
+    "lacx_recovery_repair_batch_view", "lacx_recovery_repair", "lacx_decoder_item_bad_slices",
 )
 
 
@@ -210,6 +212,19 @@ def lib():
                                                                   C.POINTER(C.c_int), C.POINTER(SalvageResult), C.POINTER(C.c_float)]
         L.lacx_decoder_salvage_batch_device_checked.argtypes = [C.c_void_p, C.POINTER(DecodeItem), C.POINTER(Span), C.c_uint32, C.c_void_p,
                                                                 C.POINTER(C.c_int), C.POINTER(SalvageResult), C.POINTER(C.c_float)]
+        u8p = C.POINTER(C.c_uint8)
+        L.lacx_recovery_build_batch_view.argtypes = [C.c_void_p, C.POINTER(Span), C.c_uint32, C.POINTER(RecoveryParams), C.POINTER(Span),
+                                                     C.POINTER(C.c_int), C.POINTER(C.c_float)]
+        L.lacx_recovery_build.argtypes = [C.c_void_p, u8p, C.c_uint64, C.POINTER(RecoveryParams), C.POINTER(u8p), C.POINTER(C.c_uint64),
+                                          C.POINTER(C.c_float)]
+        L.lacx_recovery_parse.argtypes = [u8p, C.c_uint64, C.POINTER(RecoveryInfo)]
+        L.lacx_recovery_scan_batch.argtypes = [C.c_void_p, C.POINTER(Span), C.POINTER(Span), C.c_uint32, C.POINTER(C.c_int),
+                                               C.POINTER(RepairResult), C.POINTER(C.c_float)]
+        L.lacx_recovery_repair_batch_view.argtypes = [C.c_void_p, C.POINTER(Span), C.POINTER(Span), C.c_uint32, C.c_uint32, C.POINTER(Span),
+                                                      C.POINTER(C.c_int), C.POINTER(RepairResult), C.POINTER(C.c_float)]
+        L.lacx_recovery_repair.argtypes = [C.c_void_p, u8p, C.c_uint64, u8p, C.c_uint64, C.c_uint32, C.POINTER(u8p), C.POINTER(C.c_uint64),
+                                           C.POINTER(RepairResult), C.POINTER(C.c_float)]
+        L.lacx_decoder_item_bad_slices.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint32)]
         L.lacx_block_fault_text.restype = C.c_char_p
         L.lacx_block_fault_text.argtypes = [C.c_uint32]
         L.lacx_decoder_item_error.restype = C.c_char_p
@@ -235,7 +250,8 @@ def abi_structs() -> dict:
             "decode_item": DecodeItem, "window_item": WindowItem, "verify_item": VerifyItem,
             "verify_result": VerifyResult, "digest": Digest, "digest_source": DigestSource,
             "block_fault": BlockFault, "salvage_result": SalvageResult, "block_digest": BlockDigest,
-            "manifest_info": ManifestInfo}
+            "manifest_info": ManifestInfo, "recovery_params": RecoveryParams, "recovery_info": RecoveryInfo,
+            "repair_result": RepairResult}
 
 
 def device_count() -> int:
@@ -811,6 +827,38 @@ class ManifestInfo(C.Structure):
                 ("channels", C.c_uint8), ("bit_depth", C.c_uint8), ("reserved", C.c_uint8 * 2)]
 
 
+REPAIR_TRUNCATED, REPAIR_TRAILING, REPAIR_SIDECAR_TRUNCATED, REPAIR_UNREPAIRED = 1, 2, 4, 8  # LACX_REPAIR_* (result flags)
+REPAIR_BEST_EFFORT = 1                                                                       # LACX_REPAIR_BEST_EFFORT (call flag)
+
+
+class RecoveryParams(C.Structure):
+    """The parameters of a recovery sidecar; a zero field means its default (4096, 8, 128)."""
+    _fields_ = [("slice_bytes", C.c_uint32), ("parity", C.c_uint16), ("group_data", C.c_uint16)]
+
+
+class RecoveryInfo(C.Structure):
+    """The head of a recovery sidecar; parity_present: the parity records that lie wholly inside it."""
+    _fields_ = [("file_bytes", C.c_uint64), ("file_crc32", C.c_uint32), ("slice_bytes", C.c_uint32), ("slices", C.c_uint32),
+                ("groups", C.c_uint32), ("parity", C.c_uint16), ("group_data", C.c_uint16), ("parity_present", C.c_uint32),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class RepairResult(C.Structure):
+    """What a recovery scan or repair found: first_bad == slices when no slice is damaged; flags: REPAIR_*."""
+    _fields_ = [("file_bytes", C.c_uint64), ("slices", C.c_uint32), ("bad_slices", C.c_uint32), ("repaired_slices", C.c_uint32),
+                ("first_bad", C.c_uint32), ("parity_slices", C.c_uint32), ("bad_parity", C.c_uint32), ("worst_group", C.c_uint32),
+                ("worst_group_bad", C.c_uint32), ("worst_group_parity", C.c_uint32), ("flags", C.c_uint32)]
+
+
+def recovery_parse(sidecar: bytes) -> RecoveryInfo:
+    """The head of a recovery sidecar; ValueError with the parser's "[recovery-error] ..." text.  Host only."""
+    buf = (C.c_uint8 * max(1, len(sidecar))).from_buffer_copy(sidecar if sidecar else b"\0")
+    info = RecoveryInfo()
+    if lib().lacx_recovery_parse(buf, C.c_uint64(len(sidecar)), C.byref(info)) != OK:
+        raise ValueError(lib().lacx_decode_last_error().decode(errors="replace"))
+    return info
+
+
 def manifest_build(digest: Digest, rows) -> bytes:
     """The manifest (sidecar of block digests) of `digest` and its rows, as digest_blocks_batch / digest_pcm_blocks_batch
     give them.  ValueError where a block is lost or the rows do not fit the digest.  Host only."""
@@ -1369,6 +1417,101 @@ class Decoder:
         results = [(self._copy_result(res[i]), self._faults(i)) if codes[i] == OK or (codes[i] == E_MISMATCH and res[i].blocks) else None
                    for i in range(n)]
         return self._raise_batch(rc, errors, results)
+
+    # ---- recovery data: a parity sidecar that brings lost bytes back ----
+    @staticmethod
+    def _spans(blobs):
+        bufs = [np.frombuffer(x, dtype=np.uint8) for x in blobs]
+        return (Span * max(1, len(bufs)))(*[Span(b.ctypes.data_as(C.POINTER(C.c_uint8)) if b.size else None, b.size) for b in bufs]), bufs
+
+    def _bad_slices(self, i) -> list:
+        ptr, count = C.POINTER(C.c_uint32)(), C.c_uint32()
+        if lib().lacx_decoder_item_bad_slices(self._h, C.c_uint32(i), C.byref(ptr), C.byref(count)) != OK:
+            return []
+        return [int(ptr[k]) for k in range(count.value)]
+
+    def recovery_build_batch(self, lacs, slice_bytes: int = 0, parity: int = 0, group_data: int = 0) -> list:
+        """The recovery sidecar ("LACR") of each .lac file, all made as one device job; 0 = the default (4096, 8, 128).
+        ValueError for parameters out of range; a file that stream_parse refuses raises BatchDecodeError once the others
+        are done (results[i] is None there)."""
+        spans, _keep = self._spans(lacs)
+        n = len(lacs)
+        if not (0 <= slice_bytes < 1 << 32 and 0 <= parity < 1 << 16 and 0 <= group_data < 1 << 16):
+            raise ValueError("[recovery-error] parameters out of range")
+        prm = RecoveryParams(slice_bytes, parity, group_data)
+        outs = (Span * max(1, n))()
+        codes = []
+
+        def call(rcs, ms):
+            rc = lib().lacx_recovery_build_batch_view(self._h, spans, C.c_uint32(n), C.byref(prm), outs, rcs, ms)
+            codes.extend(rcs[i] for i in range(n))
+            return rc
+        rc, errors = self._batch(n, call)
+        if rc == E_INVALID and all(c == OK for c in codes):  # the call's own arguments
+            raise ValueError(lib().lacx_decode_last_error().decode(errors="replace"))
+        return self._raise_batch(rc, errors, [None if (i in errors or not outs[i].data) else C.string_at(outs[i].data, outs[i].size) for i in range(n)])
+
+    def recovery(self, lac, slice_bytes: int = 0, parity: int = 0, group_data: int = 0) -> bytes:
+        """recovery_build_batch of one file; RuntimeError with the parser's message where the container is refused."""
+        try:
+            return self.recovery_build_batch([lac], slice_bytes, parity, group_data)[0]
+        except BatchDecodeError as e:
+            raise RuntimeError(e.errors[0]) from None
+
+    def recovery_scan_batch(self, files, sidecars) -> list:
+        """Where is each file damaged?  Per item (RepairResult, [damaged slices]); a damaged or truncated file (E_MISMATCH,
+        "[recovery-error] slice=N bad_slices=M repairable|unrepairable") and a refused sidecar raise BatchDecodeError once
+        the others are done, with the results of the damaged ones in place (None for a refused sidecar)."""
+        if len(files) != len(sidecars):
+            raise ValueError("one sidecar per file")
+        n = len(files)
+        fspans, _k1 = self._spans(files)
+        sspans, _k2 = self._spans(sidecars)
+        res = (RepairResult * max(1, n))()
+        codes = []
+
+        def call(rcs, ms):
+            rc = lib().lacx_recovery_scan_batch(self._h, fspans, sspans, C.c_uint32(n), rcs, res, ms)
+            codes.extend(rcs[i] for i in range(n))
+            return rc
+        rc, errors = self._batch(n, call)
+        results = [(_copy_struct(res[i]), self._bad_slices(i)) if codes[i] in (OK, E_MISMATCH) else None for i in range(n)]
+        return self._raise_batch(rc, errors, results)
+
+    def repair_batch(self, files, sidecars, best_effort: bool = False) -> list:
+        """Each file's original bytes, rebuilt from its recovery sidecar where it is damaged or cut short, all as one
+        device job.  Per item (bytes or None, RepairResult, [damaged slices]).  An item with a group beyond its parity
+        (E_MISMATCH, "[recovery-error] group G: B damaged slices, P parity slices usable"; bytes only with best_effort:
+        every repairable group repaired, the rest as found), one whose repaired bytes miss the checksum and a refused
+        sidecar (results[i] is None) raise BatchDecodeError once the others are done."""
+        if len(files) != len(sidecars):
+            raise ValueError("one sidecar per file")
+        n = len(files)
+        fspans, _k1 = self._spans(files)
+        sspans, _k2 = self._spans(sidecars)
+        res = (RepairResult * max(1, n))()
+        outs = (Span * max(1, n))()
+        codes = []
+
+        def call(rcs, ms):
+            rc = lib().lacx_recovery_repair_batch_view(self._h, fspans, sspans, C.c_uint32(n), C.c_uint32(REPAIR_BEST_EFFORT if best_effort else 0),
+                                                       outs, rcs, res, ms)
+            codes.extend(rcs[i] for i in range(n))
+            return rc
+        rc, errors = self._batch(n, call)
+        results = [(C.string_at(outs[i].data, outs[i].size) if outs[i].data else None, _copy_struct(res[i]), self._bad_slices(i))
+                   if codes[i] in (OK, E_MISMATCH) else None for i in range(n)]
+        return self._raise_batch(rc, errors, results)
+
+    def repair(self, file, sidecar, best_effort: bool = False):
+        """repair_batch of one file: (bytes, RepairResult, [damaged slices]); RuntimeError with the item's message where it
+        is not fully repaired (the partial answer in the exception's `result`) or the sidecar is refused."""
+        try:
+            return self.repair_batch([file], [sidecar], best_effort)[0]
+        except BatchDecodeError as e:
+            err = RuntimeError(e.errors[0])
+            err.result = e.results[0]
+            raise err from None
 
     def verify_wav(self, lac, wav) -> VerifyResult:
         """A .lac against the WAV file image it was made from (both in host memory): the image's data chunk goes to the

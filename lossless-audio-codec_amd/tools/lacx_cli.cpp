@@ -43,7 +43,7 @@ namespace {
 
 void usage() {
     std::cerr << "Usage:\n  lacx_cli encode input.wav output.lac [--stereo-mode=lr|ms] [--threads=N] [--debug-threads] [--debug-lpc] "
-                 "[--debug-stereo-est] [--debug-zr] [--debug-partitions] [--no-partitioning] [--verify] [--verify-against=other.wav] [--manifest=output.lacm]\n"
+                 "[--debug-stereo-est] [--debug-zr] [--debug-partitions] [--no-partitioning] [--verify] [--verify-against=other.wav] [--manifest=output.lacm] [--recovery=output.lacr]\n"
                  "  lacx_cli decode input.lac output.wav [--threads=N] [--debug-threads] [--salvage] [--manifest=input.lacm]\n"
                  "      --salvage: decode through errors -- lost blocks become silence, one \"[salvage] block=N ...\" line each on\n"
                  "      stderr; exit 0 when nothing was lost, 3 when the file was written with blocks lost\n"
@@ -51,6 +51,9 @@ void usage() {
                  "  lacx_cli verify input.lac input.wav\n"
                  "  lacx_cli manifest input.lac output.lacm   (one CRC-32 per block of what the stream decodes to)\n"
                  "  lacx_cli check input.lac input.lacm       (exit 0 intact, 1 damaged: one \"[check] block=N ...\" line each, 2 refused)\n"
+                 "  lacx_cli protect input.lac output.lacr [--slice=N] [--parity=R] [--group=K]   (a parity sidecar that brings lost bytes back)\n"
+                 "  lacx_cli repair input.lac input.lacr output.lac [--best-effort]\n"
+                 "      exit 0 intact or fully repaired, 1 not fully repaired (output.lac only with --best-effort), 2 refused\n"
                  "  lacx_cli digest FILE...   (.lac and .wav files, told apart by content)\n"
                  "  lacx_cli selftest\n";
 }
@@ -213,6 +216,124 @@ int check_command(char** argv) {
     } else {
         std::cout << "Intact: " << lac_path << " (" << res.blocks << " blocks, " << res.frames << " samples per channel)\n";
     }
+    lacx_decoder_destroy(dec);
+    return status;
+}
+
+// The recovery sidecar of a file's bytes, made on the device.  err: why not.
+bool make_recovery(const uint8_t* lac, uint64_t size, const lacx_recovery_params& prm, std::vector<uint8_t>& out, std::string& err) {
+    lacx_decoder* dec = nullptr;
+    if (lacx_decoder_create(-1, &dec) != LACX_OK) return err = "lacx_decoder_create failed", false;
+    uint8_t* m = nullptr;
+    uint64_t msize = 0;
+    const bool ok = lacx_recovery_build(dec, lac, size, &prm, &m, &msize, nullptr) == LACX_OK;
+    if (ok) {
+        out.assign(m, m + msize);
+        lacx_free(m);
+    } else {
+        err = lacx_decode_last_error();
+    }
+    lacx_decoder_destroy(dec);
+    return ok;
+}
+
+// lacx_cli protect input.lac output.lacr [--slice=N] [--parity=R] [--group=K]: exit 0, or 2 where anything is refused
+int protect_command(int argc, char** argv) {
+    const std::string in_path = argv[2], out_path = argv[3];
+    if (same_file(in_path, out_path)) {
+        std::cerr << "Input and output paths must be different\n";
+        return 2;
+    }
+    lacx_recovery_params prm{};
+    for (int i = 4; i < argc; ++i) {
+        const std::string flag = argv[i];
+        const std::string sprefix = "--slice=", pprefix = "--parity=", gprefix = "--group=";
+        unsigned long long v = 0;
+        if (flag.compare(0, sprefix.size(), sprefix) == 0 && positive_integer(flag.substr(sprefix.size()), v) && v <= 0xFFFFFFFFull) {
+            prm.slice_bytes = (uint32_t)v;
+        } else if (flag.compare(0, pprefix.size(), pprefix) == 0 && positive_integer(flag.substr(pprefix.size()), v) && v <= 0xFFFFull) {
+            prm.parity = (uint16_t)v;
+        } else if (flag.compare(0, gprefix.size(), gprefix) == 0 && positive_integer(flag.substr(gprefix.size()), v) && v <= 0xFFFFull) {
+            prm.group_data = (uint16_t)v;
+        } else {
+            usage();
+            return 2;
+        }
+    }
+    std::vector<uint8_t> lac, m;
+    if (!load_file(in_path, lac)) {
+        std::cerr << "Failed to read LAC file: " << in_path << "\n";
+        return 2;
+    }
+    std::string err;
+    if (!make_recovery(lac.data(), lac.size(), prm, m, err)) {
+        std::cerr << "Protect failed: " << err << "\n";
+        return 2;
+    }
+    if (!save_file(out_path, m.data(), m.size())) {
+        std::cerr << "Failed to write recovery data: " << out_path << "\n";
+        return 2;
+    }
+    lacx_recovery_info info{};
+    (void)lacx_recovery_parse(m.data(), m.size(), &info);
+    std::cout << "Protected " << in_path << " -> " << out_path << " (" << m.size() << " bytes: " << info.slices << " slices of " << info.slice_bytes
+              << " bytes in " << info.groups << " groups, " << info.parity << " parity slices each)\n";
+    return 0;
+}
+
+// lacx_cli repair input.lac input.lacr output.lac [--best-effort]: exit 0 when the file is intact or fully repaired, 1
+// when it is not (output.lac is written only with --best-effort), 2 when the sidecar is refused or nothing could run
+int repair_command(int argc, char** argv) {
+    const std::string in_path = argv[2], side_path = argv[3], out_path = argv[4];
+    bool best_effort = false;
+    for (int i = 5; i < argc; ++i) {
+        if (std::string(argv[i]) != "--best-effort") {
+            usage();
+            return 2;
+        }
+        best_effort = true;
+    }
+    if (same_file(in_path, out_path) || same_file(side_path, out_path)) {
+        std::cerr << "Input and output paths must be different\n";
+        return 2;
+    }
+    std::vector<uint8_t> file, side;
+    if (!load_file(in_path, file)) {
+        std::cerr << "Failed to read LAC file: " << in_path << "\n";
+        return 2;
+    }
+    if (!load_file(side_path, side)) {
+        std::cerr << "Failed to read recovery data: " << side_path << "\n";
+        return 2;
+    }
+    lacx_decoder* dec = nullptr;
+    if (lacx_decoder_create(-1, &dec) != LACX_OK) {
+        std::cerr << "Error: lacx_decoder_create failed\n";
+        return 2;
+    }
+    uint8_t* out = nullptr;
+    uint64_t out_size = 0;
+    lacx_repair_result res{};
+    const int rc = lacx_recovery_repair(dec, file.data(), file.size(), side.data(), side.size(), best_effort ? LACX_REPAIR_BEST_EFFORT : 0u, &out, &out_size,
+                                        &res, nullptr);
+    int status = rc == LACX_OK ? 0 : rc == LACX_E_MISMATCH ? 1 : 2;
+    if (status == 2) std::cerr << "Repair refused: " << lacx_decode_last_error() << "\n";
+    if (status == 1) std::cerr << "Repair failed: " << lacx_decode_last_error() << "\n";
+    if (out && !save_file(out_path, out, out_size)) {
+        std::cerr << "Failed to write LAC file: " << out_path << "\n";
+        status = 2;
+    }
+    if (status != 2) {
+        const char* flags = (res.flags & LACX_REPAIR_TRUNCATED) ? ", file was cut short" : (res.flags & LACX_REPAIR_TRAILING) ? ", trailing bytes ignored" : "";
+        if (status == 0 && res.bad_slices == 0 && !(res.flags & LACX_REPAIR_TRUNCATED))
+            std::cout << "Intact: " << in_path << " (" << res.slices << " slices, " << res.parity_slices - res.bad_parity << " of " << res.parity_slices
+                      << " parity slices usable" << flags << ")\n";
+        else
+            std::cout << (status == 0 ? "Repaired: " : "Not repaired: ") << res.repaired_slices << " of " << res.bad_slices << " damaged slices of "
+                      << res.slices << " rebuilt, " << res.parity_slices - res.bad_parity << " of " << res.parity_slices << " parity slices usable" << flags
+                      << (out ? " -> " + out_path : std::string()) << "\n";
+    }
+    if (out) lacx_free(out);
     lacx_decoder_destroy(dec);
     return status;
 }
@@ -572,6 +693,8 @@ int main(int argc, char** argv) {
     if (mode == "digest" && argc >= 3) return digest_command(argc, argv);
     if (mode == "manifest" && argc == 4) return manifest_command(argv);
     if (mode == "check" && argc == 4) return check_command(argv);
+    if (mode == "protect" && argc >= 4) return protect_command(argc, argv);
+    if (mode == "repair" && argc >= 5) return repair_command(argc, argv);
     if (argc < 4 || (mode != "encode" && mode != "decode")) {
         usage();
         return 1;
@@ -587,11 +710,14 @@ int main(int argc, char** argv) {
     unsigned long long threads = 0;
     std::string verify_path;  // --verify-against: another copy of the source (the master the input was made from)
     std::string manifest_path;  // --manifest: the manifest of what the written stream decodes to
+    std::string recovery_path;  // --recovery: the recovery sidecar of the written bytes (default parameters)
     for (int i = 4; i < argc; ++i) {
         const std::string flag = argv[i];
-        const std::string tprefix = "--threads=", vprefix = "--verify-against=", mprefix = "--manifest=";
+        const std::string tprefix = "--threads=", vprefix = "--verify-against=", mprefix = "--manifest=", rprefix = "--recovery=";
         if (flag.compare(0, mprefix.size(), mprefix) == 0 && flag.size() > mprefix.size()) {
             manifest_path = flag.substr(mprefix.size());
+        } else if (flag.compare(0, rprefix.size(), rprefix) == 0 && flag.size() > rprefix.size()) {
+            recovery_path = flag.substr(rprefix.size());
         } else if (flag == "--no-partitioning") {
             partitioning = false;
         } else if (flag == "--stereo-mode=lr") {
@@ -689,6 +815,17 @@ int main(int argc, char** argv) {
         if (same_file(manifest_path, out_path) || same_file(manifest_path, in_path)) err = "the manifest needs a path of its own";
         if (!err.empty() || !make_manifest(lac.data, lac.size, m, err) || !save_file(manifest_path, m.data(), m.size())) {
             std::cerr << "Manifest failed: " << (err.empty() ? "cannot write " + manifest_path : err) << "\n";
+            lacx_encoder_destroy(enc);
+            return 1;
+        }
+    }
+    if (!recovery_path.empty()) {  // of the produced bytes, before anything is published
+        std::vector<uint8_t> m;
+        std::string err;
+        if (same_file(recovery_path, out_path) || same_file(recovery_path, in_path) || (!manifest_path.empty() && same_file(recovery_path, manifest_path)))
+            err = "the recovery data needs a path of its own";
+        if (!err.empty() || !make_recovery(lac.data, lac.size, lacx_recovery_params{}, m, err) || !save_file(recovery_path, m.data(), m.size())) {
+            std::cerr << "Recovery data failed: " << (err.empty() ? "cannot write " + recovery_path : err) << "\n";
             lacx_encoder_destroy(enc);
             return 1;
         }
