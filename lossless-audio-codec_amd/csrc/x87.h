@@ -4,9 +4,11 @@
 // Why: the reference solves the LPC normal equations in `long double` (src/codec/lpc/lpc.cpp:98-154),
 // which on its x86-64 build is the x87 extended format; the Q15 coefficients it emits -- and so the
 // .lac bytes -- depend on that arithmetic.  CDNA4 has no such type, so the kernel carries its own.
-// Scope: finite, normal values only (what the recursion can produce for |R| < 2^62); no NaN/Inf/
-// denormal handling.  Every operation rounds once, exactly like fadd/fsub/fmul/fdiv under the default
-// x87 control word (precision control = extended, RC = nearest).
+// Scope: finite, normal values only; no NaN/Inf/denormal handling.  Tested on the host and on the device
+// (tests/x87recipes.py): every operation against long double for exponents within +-200 of 0, and the recursion
+// for any int64 table -- negative R[0] and INT64_MIN included, as wrapped sums produce them -- where k stays
+// clamped to +-0.999 and E >= 1e-8, so nothing leaves the normal range.  Every operation rounds once, exactly
+// like fadd/fsub/fmul/fdiv under the default x87 control word (precision control = extended, RC = nearest).
 #pragma once
 #include <stdint.h>
 
@@ -182,7 +184,9 @@ LACX_HD xf80 xf_div(xf80 a, xf80 b) {  // b != 0
     const uint32_t q0 = div96by64((uint32_t)(r1 >> 32), (r1 << 32) | (nl & 0xFFFFFFFFull), b.m, rcp_d, &rem);
     uint64_t q = ((uint64_t)q1 << 32) | q0;
     int32_t e = a.e - b.e - (t ? 1 : 0);
-    // round to nearest even on the remainder: compare 2 * rem with b.m
+    // round to nearest even on the remainder: compare 2 * rem with b.m.  (2 * rem == b.m never happens for normalised
+    // operands -- a.m * 2^k = (2 q + 1) * b.m would put the 65 significant bits of 2 q + 1 into a 64-bit significand --
+    // so the tie term below is kept for the rule's sake only; tests/x87recipes.py counts the ties of its corpus: none.)
     const uint64_t other = b.m - rem;  // > 0
     const bool up = rem != 0 && (rem > other || (rem == other && (q & 1u)));
     q += up ? 1u : 0u;
