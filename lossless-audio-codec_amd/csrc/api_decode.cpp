@@ -270,13 +270,8 @@ DevErr collect(lacx_decoder* d, const DecodeJob& job, const DecodePlan& plan, hi
             if (job.sres) job.sres[i] = r;
             if (plan.blocks) {  // the rows: every block's frames and, where it decoded, its finished CRC-32
                 const uint32_t* raw = reinterpret_cast<const uint32_t*>(d->h_meta() + plan.at.raw) + p.item.block0;
-                const uint32_t align = (uint32_t)p.info.channels * (p.info.bit_depth / 8u);
                 std::vector<lacx_block_digest>& rows = d->item_rows[i];
-                rows.assign(p.item.blocks, lacx_block_digest{});
-                for (uint32_t b = 0; b < p.item.blocks; ++b) rows[b].frames = row_frames(x.lac, p.info.version, b);
-                for (const lacx_block_fault& f : d->item_faults[i]) rows[f.block].code = f.code;
-                for (uint32_t b = 0; b < p.item.blocks; ++b)
-                    if (!rows[b].code) rows[b].crc32 = crc_finish(raw[b], (unsigned long long)rows[b].frames * align);
+                rows_of_decoded(x.lac, p.info.version, p.item.blocks, p.info.channels, p.info.bit_depth, d->item_faults[i], raw, rows);
                 if (job.dres) job.dres[i] = digest_of_rows(rows, p.info.frames, p.info.sample_rate, p.info.channels, p.info.bit_depth);
                 if (job.check && (r.bad_blocks || (r.flags & LACX_SALVAGE_TRUNCATED))) {
                     code[i] = LACX_E_MISMATCH;
@@ -381,18 +376,30 @@ int decode_batch_run(lacx_decoder* d, const DecodeJob& job, std::vector<int>& co
     return rc;
 }
 
-// A batch entry point: runs the job; the per-item outcome into item_rc and d->item_err, and back the lowest failing item's
-// code with "stream i: <message>" (or the whole call's failure).
-int run_batch(lacx_decoder* d, const DecodeJob& job, int* item_rc) {
-    std::vector<int> code;
-    std::vector<std::string> err;
-    const int rc = decode_batch_run(d, job, code, err);
+// How a batch entry point ends: the per-item outcome into item_rc and d->item_err, and back the lowest failing item's
+// code with "stream i: <message>" (or rc, the whole call's failure).
+int batch_outcome(lacx_decoder* d, int rc, const std::vector<int>& code, std::vector<std::string>& err, int* item_rc) {
     if (item_rc) std::copy(code.begin(), code.end(), item_rc);
     d->item_err = std::move(err);
     if (rc != LACX_OK) return rc;
     for (size_t i = 0; i < code.size(); ++i)
         if (code[i] != LACX_OK) return decode_fail(code[i], "stream " + std::to_string(i) + ": " + d->item_err[i]);
     return LACX_OK;
+}
+
+// A copy of a view for the caller to free; null where the host is out of memory.
+uint8_t* owned_copy(const uint8_t* data, uint64_t size) {
+    uint8_t* buf = static_cast<uint8_t*>(std::malloc(size));
+    if (buf) std::memcpy(buf, data, size);
+    return buf;
+}
+
+// A batch entry point: runs the job and ends as batch_outcome says.
+int run_batch(lacx_decoder* d, const DecodeJob& job, int* item_rc) {
+    std::vector<int> code;
+    std::vector<std::string> err;
+    const int rc = decode_batch_run(d, job, code, err);
+    return batch_outcome(d, rc, code, err, item_rc);
 }
 
 // A single stream as a batch of one: its own code and message.  d->item_err keeps the last batch call's.
@@ -435,9 +442,8 @@ int lacx_decoder_decode_wav(lacx_decoder* d, const uint8_t* lac, uint64_t size, 
     uint64_t n = 0;
     const int rc = lacx_decoder_decode_wav_view(d, lac, size, &view, &n, device_ms);
     if (rc) return rc;
-    uint8_t* buf = static_cast<uint8_t*>(std::malloc(n));
+    uint8_t* buf = owned_copy(view, n);
     if (!buf) return decode_fail(LACX_E_RUNTIME, "out of host memory");
-    std::memcpy(buf, view, n);
     *out = buf;
     *out_size = n;
     return LACX_OK;
@@ -458,7 +464,7 @@ int lacx_decoder_decode_wav_batch(lacx_decoder* d, const lacx_span* lacs, uint32
     if (!out || !lacs || n == 0 || !d) return rc;
     for (uint32_t i = 0; i < n; ++i) {
         if (!out[i].data) continue;
-        uint8_t* buf = static_cast<uint8_t*>(std::malloc(out[i].size));
+        uint8_t* buf = owned_copy(out[i].data, out[i].size);
         if (!buf) {
             for (uint32_t k = 0; k < i; ++k) {
                 std::free(const_cast<uint8_t*>(out[k].data));
@@ -467,7 +473,6 @@ int lacx_decoder_decode_wav_batch(lacx_decoder* d, const lacx_span* lacs, uint32
             for (uint32_t k = i; k < n; ++k) out[k] = lacx_span{nullptr, 0};
             return decode_fail(LACX_E_RUNTIME, "out of host memory");
         }
-        std::memcpy(buf, out[i].data, out[i].size);
         out[i].data = buf;
     }
     return rc;
@@ -668,13 +673,8 @@ int digest_pcm_run(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, h
                 if (grid) {
                     const auto* block_off = reinterpret_cast<const unsigned long long*>(d->h_meta() + at_blk);
                     const uint32_t* braw = reinterpret_cast<const uint32_t*>(d->h_meta() + at_raw) + block_off[j];
-                    const uint32_t nb = (uint32_t)(block_off[j + 1] - block_off[j]), align = (uint32_t)x.pcm.channels * (x.bit_depth / 8u);
                     std::vector<lacx_block_digest>& rows = d->item_rows[i];
-                    rows.assign(nb, lacx_block_digest{});
-                    for (uint32_t b = 0; b < nb; ++b) {
-                        rows[b].frames = b + 1u < nb ? grid : (uint32_t)(x.frames - (unsigned long long)grid * b);
-                        rows[b].crc32 = crc_finish(braw[b], (unsigned long long)rows[b].frames * align);
-                    }
+                    rows_of_source(x.frames, grid, (uint32_t)(block_off[j + 1] - block_off[j]), (uint32_t)x.pcm.channels, x.bit_depth, braw, rows);
                     if (out) out[i] = digest_of_rows(rows, x.frames, x.sample_rate, (uint8_t)x.pcm.channels, x.bit_depth);
                     continue;
                 }
@@ -702,12 +702,7 @@ int lacx_decoder_digest_pcm_batch_device(lacx_decoder* d, const lacx_digest_sour
     std::vector<int> code;
     std::vector<std::string> err;
     const int rc = digest_pcm_run(d, src, n, static_cast<hipStream_t>(stream), out, device_ms, code, err);
-    if (item_rc) std::copy(code.begin(), code.end(), item_rc);
-    d->item_err = std::move(err);
-    if (rc != LACX_OK) return rc;
-    for (size_t i = 0; i < code.size(); ++i)
-        if (code[i] != LACX_OK) return decode_fail(code[i], "stream " + std::to_string(i) + ": " + d->item_err[i]);
-    return LACX_OK;
+    return batch_outcome(d, rc, code, err, item_rc);
 }
 
 // ---- salvage: decode through errors (lacx.h) ----
@@ -748,9 +743,8 @@ int lacx_decoder_salvage_wav(lacx_decoder* d, const uint8_t* lac, uint64_t size,
     lacx_span img{nullptr, 0};
     const int rc = run_one(d, BatchIn{lac, size, nullptr, nullptr, 0}, salvage_job(DecodeForm::wav, nullptr, &img, result, device_ms));
     if (rc) return rc;
-    uint8_t* buf = static_cast<uint8_t*>(std::malloc(img.size));
+    uint8_t* buf = owned_copy(img.data, img.size);
     if (!buf) return decode_fail(LACX_E_RUNTIME, "out of host memory");
-    std::memcpy(buf, img.data, img.size);
     *out = buf;
     *out_size = img.size;
     return LACX_OK;
@@ -828,12 +822,7 @@ int lacx_decoder_digest_pcm_blocks_batch_device(lacx_decoder* d, const lacx_dige
     std::vector<int> code;
     std::vector<std::string> err;
     const int rc = digest_pcm_run(d, src, n, static_cast<hipStream_t>(stream), out, device_ms, code, err, block_frames ? block_frames : (uint32_t)kMaxBlock);
-    if (item_rc) std::copy(code.begin(), code.end(), item_rc);
-    d->item_err = std::move(err);
-    if (rc != LACX_OK) return rc;
-    for (size_t i = 0; i < code.size(); ++i)
-        if (code[i] != LACX_OK) return decode_fail(code[i], "stream " + std::to_string(i) + ": " + d->item_err[i]);
-    return LACX_OK;
+    return batch_outcome(d, rc, code, err, item_rc);
 }
 
 int lacx_decoder_item_block_digests(const lacx_decoder* d, uint32_t i, const lacx_block_digest** rows, uint32_t* count) {

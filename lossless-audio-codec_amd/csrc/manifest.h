@@ -1,5 +1,7 @@
-// manifest.h -- the sidecar of block digests (lacx.h): its bytes, its builder and its parser.  Host only, no HIP: the C
-// ABI (api_decode.cpp), the plan (decode_plan.h: a judged item's expected values) and tests/native/sim_blockdigest.cpp.
+// manifest.h -- the sidecar of block digests (lacx.h): its bytes, its builder and its parser, and the rows of block digests
+// themselves as the host side finishes them from what the device summed.  Host only, no HIP: the C ABI (api_decode.cpp),
+// the plan (decode_plan.h: a judged item's expected values) and tests/native/sim_blockdigest.cpp, which calls the same
+// row builders the ABI calls.
 // Big-endian like the container, 32 + 8 * blocks bytes:
 //   0 "LACM" | 4 version = 1 | 5 channels | 6 bit depth | 7 zero | 8 sample rate u32 | 12 frames u64 | 20 blocks u32 |
 //   24 data_crc32 u32 (of the whole data chunk) | 28 rows: frames u32, crc32 u32 | end - 4: zlib CRC-32 of all before it
@@ -9,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "container.h"
 #include "crc32_core.h"
 #include "lacx.h"
 
@@ -93,6 +96,29 @@ inline int manifest_build(const lacx_digest& d, const lacx_block_digest* rows, u
     const int rc = manifest_parse(m, out.size(), nullptr, nullptr, 0, why);
     if (rc != LACX_OK) out.clear();
     return rc;
+}
+
+// The rows of a decoded item: every block's frames from the stream's table, its fault code where it has one, and where it
+// decoded its finished CRC-32.  raw: the words the device summed, the item's first block's first.
+inline void rows_of_decoded(const uint8_t* lac, int version, uint32_t blocks, uint32_t channels, uint32_t bit_depth,
+                            const std::vector<lacx_block_fault>& faults, const uint32_t* raw, std::vector<lacx_block_digest>& rows) {
+    const uint32_t align = channels * (bit_depth / 8u);
+    rows.assign(blocks, lacx_block_digest{});
+    for (uint32_t b = 0; b < blocks; ++b) rows[b].frames = row_frames(lac, version, b);
+    for (const lacx_block_fault& f : faults) rows[f.block].code = f.code;
+    for (uint32_t b = 0; b < blocks; ++b)
+        if (!rows[b].code) rows[b].crc32 = crc_finish(raw[b], (unsigned long long)rows[b].frames * align);
+}
+
+// The rows of a source item of `frames` frames on a regular grid of `grid` frames: nb blocks, the last the remainder.
+inline void rows_of_source(unsigned long long frames, uint32_t grid, uint32_t nb, uint32_t channels, uint32_t bit_depth, const uint32_t* raw,
+                           std::vector<lacx_block_digest>& rows) {
+    const uint32_t align = channels * (bit_depth / 8u);
+    rows.assign(nb, lacx_block_digest{});
+    for (uint32_t b = 0; b < nb; ++b) {
+        rows[b].frames = b + 1u < nb ? grid : (uint32_t)(frames - (unsigned long long)grid * b);
+        rows[b].crc32 = crc_finish(raw[b], (unsigned long long)rows[b].frames * align);
+    }
 }
 
 }  // namespace lacx

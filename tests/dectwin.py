@@ -14,22 +14,17 @@ from __future__ import annotations
 import ctypes as C
 import os
 import struct
-import subprocess
-import tempfile
 from collections import namedtuple
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "lossless-audio-codec_amd", "csrc")
-INCLUDE = os.path.join(ROOT, "include")  # lacx.h: decode_plan.h speaks the ABI's types
-BUILD = os.path.join(ROOT, "tests", "native", "_build")
-SRC = os.path.join(ROOT, "tests", "native", "sim_decode.cpp")
+import twinbuild
+
+SRC = os.path.join(twinbuild.NATIVE, "sim_decode.cpp")
 DEFAULT_PAD = 0xFFFFFFFF  # "what the device path appends": the twin takes kDecodeTailPad from lacx_types.h itself
 ALL_SETTINGS = 0xFF
 HALF_SETTINGS = 0   # four settings per stream that vary every switch and every pair of switches (see sim_digest)
-SANITIZE = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
+ENV = dict(ASAN_OPTIONS="detect_leaks=0:verify_asan_link_order=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
 
 Result = namedtuple("Result", "status ms left right over")
 Line = namedtuple("Line", "index over pcm_hash same status")
@@ -37,23 +32,11 @@ Line = namedtuple("Line", "index over pcm_hash same status")
 _lib = None
 
 
-def _sources():
-    return [SRC] + [os.path.join(CSRC, h) for h in ("decode_core.h", "analyze_core.h", "lacx_types.h", "x87.h", "decode_plan.h")]
-
-
-def _stale(target):
-    return not os.path.exists(target) or any(os.path.getmtime(target) < os.path.getmtime(s) for s in _sources())
-
-
 def lib():
     """The plain build."""
     global _lib
     if _lib is None:
-        os.makedirs(BUILD, exist_ok=True)
-        so = os.path.join(BUILD, "libsim_decode.so")
-        if _stale(so):
-            subprocess.check_call(["g++", "-O2", "-std=c++20", "-fPIC", "-shared", "-I", CSRC, "-I", INCLUDE, SRC, "-o", so])
-        _lib = C.CDLL(so)
+        _lib = C.CDLL(twinbuild.shared_lib("sim_decode", [SRC]))
         _lib.sim_hash.restype = C.c_uint64
         _lib.sim_tail_pad.restype = C.c_uint32
     return _lib
@@ -61,19 +44,7 @@ def lib():
 
 def sanitized_exe(extra=(), name="sim_decode_san"):
     """The sanitized program's path, or (None, why) where the sanitizer runtime is missing."""
-    os.makedirs(BUILD, exist_ok=True)
-    exe = os.path.join(BUILD, name)
-    if extra or _stale(exe):
-        # compile, then link: only a failing LINK for want of the sanitizer runtime means "not available"
-        obj = exe + ".o"
-        flags = ["g++", "-std=c++20", *SANITIZE, "-DSIM_DECODE_MAIN", *extra, "-I", CSRC, "-I", INCLUDE]
-        built = subprocess.run(flags + ["-c", SRC, "-o", obj], capture_output=True, text=True)
-        assert built.returncode == 0, built.stderr
-        linked = subprocess.run(["g++", *SANITIZE, obj, "-o", exe], capture_output=True, text=True)
-        if linked.returncode != 0 and any(w in linked.stderr for w in ("asan", "ubsan", "sanitize")):
-            return None, "sanitizer runtime not available: " + linked.stderr.strip().splitlines()[-1]
-        assert linked.returncode == 0, linked.stderr
-    return exe, ""
+    return twinbuild.sanitized_exe(name, [SRC], ["-DSIM_DECODE_MAIN"], extra)
 
 
 def tail_pad() -> int:
@@ -130,47 +101,16 @@ def digest(lac: bytes, index: int, settings=ALL_SETTINGS, pad=DEFAULT_PAD) -> Li
     return parse_line(buf.value.decode())
 
 
-def run_sanitized(streams, settings=ALL_SETTINGS, pad=DEFAULT_PAD, exe=None, workers=None):
+def run_sanitized(streams, settings=ALL_SETTINGS, pad=DEFAULT_PAD, exe=None, workers=8):
     """Every stream through the sanitized program, split over a few processes.  Returns (lines, returncode, stderr):
     lines[i] is None where a process stopped before stream i (a sanitizer report: returncode != 0, the report in stderr)."""
     if exe is None:
         exe, why = sanitized_exe()
         assert exe, why
-    workers = workers or max(1, min(8, os.cpu_count() or 1))
     # slices of about equal bytes, so that the long streams do not land in one process
-    total = sum(len(s) for s in streams) or 1
-    cuts, acc = [0], 0
-    for i, s in enumerate(streams):
-        acc += len(s)
-        if acc >= total * len(cuts) / workers and len(cuts) < workers:
-            cuts.append(i + 1)
-    if cuts[-1] != len(streams):
-        cuts.append(len(streams))
-    with tempfile.NamedTemporaryFile(prefix="lac_corpus_", suffix=".bin") as f:
-        for s in streams:
-            f.write(struct.pack("<I", len(s)))
-            f.write(s)
-        f.flush()
-        env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:verify_asan_link_order=0:abort_on_error=0",
-                   UBSAN_OPTIONS="print_stacktrace=1")
-
-        def part(k):
-            a, b = cuts[k], cuts[k + 1]
-            return subprocess.run([exe, f.name, str(a), str(b - a), str(settings), str(pad)], capture_output=True, text=True,
-                                  env=env, timeout=900)
-
-        with ThreadPoolExecutor(len(cuts) - 1) as pool:
-            runs = list(pool.map(part, range(len(cuts) - 1)))
-    lines, rc, err = [None] * len(streams), 0, ""
-    for run in runs:
-        for text in run.stdout.splitlines():
-            if text and not text.startswith("done"):
-                ln = parse_line(text)
-                lines[ln.index] = ln
-        if run.returncode != 0 or "done" not in run.stdout:
-            rc = run.returncode or 1
-            err += run.stderr[-4000:]
-    return lines, rc, err
+    lines, rc, err = twinbuild.run_cases(exe, streams, ENV, lambda path, a, n: [path, str(a), str(n), str(settings), str(pad)],
+                                         workers=workers, slices=True, prefix="lac_corpus_")
+    return [parse_line(t) if t else None for t in lines], rc, err
 
 
 # ---- batches: sim_decode_batch / sim_batch_digest / sim_plan_dump (jobs planned by csrc/decode_plan.h) ----
@@ -238,17 +178,7 @@ def run_sanitized_batches(cases, exe=None):
     if exe is None:
         exe, why = sanitized_exe()
         assert exe, why
-    with tempfile.NamedTemporaryFile(prefix="lac_batches_", suffix=".bin") as f:
-        for c in cases:
-            f.write(struct.pack("<I", len(c)))
-            f.write(c)
-        f.flush()
-        env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:verify_asan_link_order=0:abort_on_error=0",
-                   UBSAN_OPTIONS="print_stacktrace=1")
-        run = subprocess.run([exe, "batch", f.name], capture_output=True, text=True, env=env, timeout=900)
-    lines = [t for t in run.stdout.splitlines() if t and not t.startswith("done")]
-    rc = run.returncode or (0 if "done %d" % len(cases) in run.stdout else 1)
-    return lines, rc, run.stderr[-4000:]
+    return twinbuild.run_cases(exe, cases, ENV, lambda path, a, n: ["batch", path], prefix="lac_batches_")
 
 
 ITEM_DTYPE = np.dtype([("left", "<u8"), ("right", "<u8"), ("wav", "<u8"), ("frame0", "<u8"), ("frames", "<u8"), ("pay_off", "<u8"),

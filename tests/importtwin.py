@@ -18,18 +18,15 @@ from __future__ import annotations
 import ctypes as C
 import os
 import struct
-import subprocess
 import tempfile
 from collections import namedtuple
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "lossless-audio-codec_amd", "csrc")
-BUILD = os.path.join(ROOT, "tests", "native", "_build")
-SRC = os.path.join(ROOT, "tests", "native", "sim_import.cpp")
-SRC_VERIFY = os.path.join(ROOT, "tests", "native", "sim_verify_layouts.cpp")
-SANITIZE = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
+import twinbuild
+
+SRC = twinbuild.NATIVE + "/sim_import.cpp"
+SRC_VERIFY = twinbuild.NATIVE + "/sim_verify_layouts.cpp"
 PLANAR_I32, INTERLEAVED_I16, INTERLEAVED_I24 = 0, 1, 2
 PLANAR_I16, PLANAR_F32, INTERLEAVED_F32 = 16, 17, 18
 NO_KEY = (1 << 64) - 1
@@ -39,24 +36,11 @@ Answer = namedtuple("Answer", "alias code message dst")
 _lib = None
 
 
-def _sources():
-    return [SRC, SRC_VERIFY] + [os.path.join(CSRC, h) for h in ("import_core.h", "import_msg.h", "verify_core.h", "decode_core.h",
-                                                                 "analyze_core.h", "lacx_types.h", "x87.h")]
-
-
-def _stale(target):
-    return not os.path.exists(target) or any(os.path.getmtime(target) < os.path.getmtime(s) for s in _sources())
-
-
 def lib():
     """The plain build (both twins)."""
     global _lib
     if _lib is None:
-        os.makedirs(BUILD, exist_ok=True)
-        so = os.path.join(BUILD, "libsim_import.so")
-        if _stale(so):
-            subprocess.check_call(["g++", "-O2", "-std=c++20", "-fPIC", "-shared", "-I", CSRC, SRC, SRC_VERIFY, "-o", so])
-        _lib = C.CDLL(so)
+        _lib = C.CDLL(twinbuild.shared_lib("sim_import", [SRC, SRC_VERIFY]))
         _lib.sim_import_answer.restype = C.c_longlong
         _lib.sim_import_unit_frames.restype = C.c_uint32
     return _lib
@@ -68,18 +52,7 @@ def unit_frames() -> int:
 
 def sanitized_exe():
     """The sanitized program's path, or (None, why) where the sanitizer runtime is missing."""
-    os.makedirs(BUILD, exist_ok=True)
-    exe = os.path.join(BUILD, "sim_import_san")
-    if _stale(exe):
-        obj = exe + ".o"
-        built = subprocess.run(["g++", "-std=c++20", *SANITIZE, "-DSIM_IMPORT_MAIN", "-I", CSRC, "-c", SRC, "-o", obj],
-                               capture_output=True, text=True)
-        assert built.returncode == 0, built.stderr
-        linked = subprocess.run(["g++", *SANITIZE, obj, "-o", exe], capture_output=True, text=True)
-        if linked.returncode != 0 and any(w in linked.stderr for w in ("asan", "ubsan", "sanitize")):
-            return None, "sanitizer runtime not available: " + linked.stderr.strip().splitlines()[-1]
-        assert linked.returncode == 0, linked.stderr
-    return exe, ""
+    return twinbuild.sanitized_exe("sim_import_san", [SRC], ["-DSIM_IMPORT_MAIN"])
 
 
 def to_float(samples, bit_depth) -> np.ndarray:
@@ -199,17 +172,12 @@ def run_sanitized(cases, exe=None):
         exe, why = sanitized_exe()
         assert exe, why
     with tempfile.TemporaryDirectory(prefix="import_cases_") as d:
-        src, dst = os.path.join(d, "cases.bin"), os.path.join(d, "answers.bin")
-        with open(src, "wb") as f:
-            for case in cases:
-                blob = case.blob()
-                f.write(struct.pack("<I", len(blob)))
-                f.write(blob)
-        env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-        run = subprocess.run([exe, src, dst], capture_output=True, text=True, env=env, timeout=600)
-        answers = parse_answers(open(dst, "rb").read()) if os.path.exists(dst) and run.returncode == 0 else []
-    rc = run.returncode if run.returncode != 0 or f"done {len(cases)}" in run.stdout else 1
-    return answers, rc, run.stderr[-4000:]
+        dst = os.path.join(d, "answers.bin")
+        env = dict(ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+        _, rc, err = twinbuild.run_cases(exe, [case.blob() for case in cases], env, lambda path, a, n: [path, dst], prefix="import_cases_",
+                                         timeout=600)
+        answers = parse_answers(open(dst, "rb").read()) if os.path.exists(dst) and rc == 0 else []
+    return answers, rc, err
 
 
 def f32_to_pcm(x, bit_depth):

@@ -16,46 +16,19 @@
 //
 // Built twice by tests/blockdigesttwin.py: a plain -O2 shared library for ctypes, and (-DSIM_BLOCKDIGEST_MAIN) a
 // sanitized program that runs a file of cases and prints one line per case.
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <string>
-#include <vector>
+#define SIM_JOB_SIMULATOR
+#include "sim_job.h"
 
 #include "blockdigest_core.h"
-#include "decode_core.h"
-#include "decode_plan.h"
-#include "salvage_core.h"
 
 using namespace lacx;
+using namespace simjob;
 
 namespace {
 
-template <typename T>
-struct Heap {  // exactly n elements, nothing behind them
-    T* p;
-    explicit Heap(size_t n, int fill = 0) : p(static_cast<T*>(std::malloc(n ? n * sizeof(T) : 1))) {
-        if (n) std::memset(p, fill, n * sizeof(T));
-    }
-    ~Heap() { std::free(p); }
-    Heap(const Heap&) = delete;
-    Heap& operator=(const Heap&) = delete;
-};
-
 constexpr int kFill = 0xCD;
 
-uint64_t fnv(const void* data, uint64_t bytes, uint64_t h) {
-    const uint8_t* p = static_cast<const uint8_t*>(data);
-    for (uint64_t i = 0; i < bytes; ++i) {
-        h ^= p[i];
-        h *= 0x100000001B3ull;
-    }
-    return h;
-}
-
-struct Lane {
+struct UnitLane {
     bool valid = false;
     uint32_t j = 0, align = 0, fmt = 0, g0 = 0;
     BlockUnit bu{};
@@ -72,10 +45,10 @@ bool sum_like_kernel(uint32_t nitems, unsigned long long total_units, const unsi
         const bool one_item = unit_off[lo + 1] >= first + kDigestThreads;
         uint32_t wave_sum[kDigestThreads / 64u], wave_blk[kDigestThreads / 64u];
         for (uint32_t w = 0; w < kDigestThreads / 64u; ++w) {
-            Lane ln[64];
+            UnitLane ln[64];
             for (uint32_t lane = 0; lane < 64u; ++lane) {
                 const unsigned long long u = first + 64u * w + lane;
-                Lane& t = ln[lane];
+                UnitLane& t = ln[lane];
                 t.valid = u < total_units;
                 if (!t.valid) continue;
                 t.j = lo;
@@ -114,7 +87,7 @@ bool sum_like_kernel(uint32_t nitems, unsigned long long total_units, const unsi
                 }
             } else {
                 for (uint32_t lane = 0; lane < 64u; ++lane) {
-                    const Lane& t = ln[lane];
+                    const UnitLane& t = ln[lane];
                     if (!t.valid) continue;
                     if (t.bu.use0 && t.bu.p0.bytes) raw[t.g0] ^= crc_shift(t.bu.p0.raw, t.bu.dist0), ++*atomics;
                     if (t.bu.use1 && t.bu.p1.bytes) raw[t.g0 + 1u] ^= crc_shift(t.bu.p1.raw, t.bu.dist1), ++*atomics;
@@ -139,82 +112,32 @@ bool sum_like_kernel(uint32_t nitems, unsigned long long total_units, const unsi
 }
 
 struct Job {
-    std::vector<BatchIn> in;
-    std::vector<std::unique_ptr<Heap<int32_t>>> own;  // device form: the caller's arrays
+    SalvageIn src;
     DecodePlan plan;
     std::vector<int> code;
     std::vector<std::string> err;
-    std::unique_ptr<Heap<uint8_t>> payload, tables, flag, image;
-    std::unique_ptr<Heap<int32_t>> L, R;
-    std::unique_ptr<Heap<uint32_t>> st;
-    DecodeArgs a;
+    std::unique_ptr<Run> run;
     uint64_t atomics = 0;
+    Job(const uint8_t* const* lacs, const uint64_t* sizes, uint32_t n, int form) : src(lacs, sizes, n, form == 2) {}
 };
 
 // form: 0 the blocks form, 1 the WAV form, 2 the device form.  mans[i] null: no manifest for item i.
-bool run(const uint8_t* const* lacs, const uint64_t* sizes, const uint8_t* const* mans, const uint64_t* man_sizes, uint32_t n, int form, int cols,
-         bool zero_status, Job& j) {
-    j.in.resize(n);
-    for (uint32_t i = 0; i < n; ++i) {
-        lacx_stream_info info{};
-        uint32_t present = 0, flags = 0;
-        const char* why = nullptr;
-        int32_t *l = nullptr, *r = nullptr;
-        uint64_t frames = 0;
-        if (form == 2 && scan_stream(lacs[i], sizes[i], &info, &present, &flags, &why) == LACX_OK) {
-            frames = info.frames;
-            j.own.emplace_back(new Heap<int32_t>(frames, 0x5A));
-            l = j.own.back()->p;
-            if (info.channels == 2) {
-                j.own.emplace_back(new Heap<int32_t>(frames, 0x5A));
-                r = j.own.back()->p;
-            }
-        }
-        j.in[i] = BatchIn{lacs[i], sizes[i], l, r, frames};
-        if (mans && mans[i]) j.in[i].manifest = mans[i], j.in[i].manifest_size = man_sizes[i];
-    }
+bool run(const uint8_t* const* mans, const uint64_t* man_sizes, uint32_t n, int form, int cols, bool zero_status, Job& j) {
+    for (uint32_t i = 0; i < n; ++i)
+        if (mans && mans[i]) j.src.in[i].manifest = mans[i], j.src.in[i].manifest_size = man_sizes[i];
+    const BatchIn* in = j.src.in.data();
     const DecodeForm f = form == 0 ? DecodeForm::blocks : form == 1 ? DecodeForm::wav : DecodeForm::device;
-    if (plan_decode(j.in.data(), n, f, kWholeStreams, false, j.plan, j.code, j.err, true, true)) return false;
-    const DecodePlan& p = j.plan;
-    j.payload.reset(new Heap<uint8_t>(p.need.payload));
-    j.tables.reset(new Heap<uint8_t>(p.need.tables));
-    j.flag.reset(new Heap<uint8_t>(p.need.blocks, kFill));
-    j.image.reset(new Heap<uint8_t>(p.need.image, kFill));
-    j.L.reset(new Heap<int32_t>(p.need.pcm_frames, kFill));
-    j.R.reset(new Heap<int32_t>(p.need.pcm_frames, kFill));
-    j.st.reset(new Heap<uint32_t>(p.need.blocks, zero_status ? 0 : kFill));
-    plan_fill_tables(p, j.in.data(), PlanBases{j.payload->p, j.L->p, j.R->p, j.image->p}, j.tables->p);
-    const DecodeArgs a = j.a = plan_args(p, j.tables->p, j.payload->p, j.st->p, j.flag->p);
-    for (const PlanItem& it : p.items) std::memcpy(j.payload->p + it.item.pay_off, j.in[it.src].lac + it.head + it.pay_src, it.pay_bytes);
-    if (p.items.empty()) return true;
+    if (plan_decode(in, n, f, kWholeStreams, false, j.plan, j.code, j.err, true, true)) return false;
+    j.run.reset(new Run(j.plan, in, (uint32_t)kDecodeTailPad, kFill, zero_status ? 0 : kFill));
+    const DecodeArgs& a = j.run->a;
+    place_payload(j.plan, in, j.run->payload.p);
+    if (j.plan.items.empty()) return true;
     if (!a.present || !a.block_raw) return false;
-
-    Heap<unsigned char> rawmem(kDecBytesPerCol * (size_t)cols, 0xA5);
-    DecMem dm = dec_mem(rawmem.p, (uint32_t)cols);
-    DecWave wave;
-    for (uint32_t g = 0; g < a.lanes; ++g) {  // k_decode
-        const uint32_t blk = a.lane_blk[g];
-        if (blk == ~0u) continue;
-        const DecodeItem& it = a.items[a.blk_item[blk]];
-        decode_block_lane(blk, it.channels, it.stereo_mode, a.payload, a.byte_off, a.frame_off, it.frame0, it.left, it.right, a.status,
-                          a.ms_flag, dm, cols - 1, wave);
-    }
-    for (uint32_t g = 0; g < a.nv2; ++g) {  // k_decode_serial
-        const DecodeItem& it = a.items[a.v2_items[g]];
-        decode_serial_lane(it.blocks, it.channels, it.stereo_mode, a.payload + it.pay_off, it.pay_bits, a.frame_off + it.block0, it.frame0,
-                           it.left, it.right, a.status + it.block0, a.ms_flag + it.block0, dm, cols - 1, wave);
-    }
-    for (uint32_t blk = 0; blk < a.total_blocks; ++blk) {  // k_ms_inverse
-        if (a.status[blk]) continue;
-        const DecodeItem& it = a.items[a.blk_item[blk]];
-        const unsigned long long f0 = a.frame_off[blk];
-        const uint32_t nfr = (uint32_t)(a.frame_off[blk + 1] - f0);
-        for (uint32_t tile = 0; tile < (uint32_t)kMaxBlock / 1024u; ++tile)
-            for (uint32_t tid = 0; tid < 256u; ++tid)
-                ms_inverse_tile(blk, tile, it.channels, it.bit_depth, f0 - it.frame0, nfr, it.left, it.right, a.ms_flag, a.status, tid);
-    }
+    Lane ln(cols, 0);
+    run_lanes(a, ln);
+    run_ms_inverse(a);
     // k_digest_blocks
-    const bool agreed = sum_like_kernel(a.nitems, a.total_units, a.unit_off, [&](uint32_t item, unsigned long long f0, Lane& t) {
+    const bool agreed = sum_like_kernel(a.nitems, a.total_units, a.unit_off, [&](uint32_t item, unsigned long long f0, UnitLane& t) {
         const DecodeItem& it = a.items[item];
         t.align = (uint32_t)it.channels * (it.bit_depth / 8u);
         t.fmt = crc_format(it.channels, it.bit_depth);
@@ -231,43 +154,23 @@ bool run(const uint8_t* const* lacs, const uint64_t* sizes, const uint8_t* const
                         (uint32_t)it.channels * (it.bit_depth / 8u), a.block_raw, a.block_expect, a.status);
         }
     }
-    if (a.no_output) return true;
-    if (a.wav) {  // k_salvage_wav
-        uint32_t item = 0;
-        for (unsigned long long u = 0; u < a.total_units; ++u) {
-            while (a.unit_off[item + 1] <= u) ++item;
-            const DecodeItem& it = a.items[item];
-            salvage_wav_unit(4ull * (u - a.unit_off[item]), it.blocks, a.present[item], it.channels, it.bit_depth, it.frames,
-                             a.frame_off + it.block0, it.frame0, it.left, it.right, a.status + it.block0, it.wav);
-        }
-    } else {  // k_salvage_blank
-        for (uint32_t blk = 0; blk < a.total_blocks; ++blk) {
-            const uint32_t item = a.blk_item[blk];
-            const DecodeItem& it = a.items[item];
-            if (!salvage_lost(a.status + it.block0, blk - it.block0, a.present[item])) continue;
-            const unsigned long long f0 = a.frame_off[blk];
-            const uint32_t nfr = (uint32_t)(a.frame_off[blk + 1] - f0);
-            for (uint32_t tile = 0; tile < (uint32_t)kMaxBlock / 1024u; ++tile)
-                for (uint32_t tid = 0; tid < 256u; ++tid)
-                    salvage_blank_tile(tile, f0 - it.frame0, nfr, it.left, it.channels == 2 ? it.right : nullptr, tid);
-        }
-    }
+    if (!a.no_output) run_salvage_pass(a);
     return true;
 }
 
-// the rows of a planned item as the host side makes them (collect of api_decode.cpp): 3 words per block
-void rows_of(const Job& j, const PlanItem& p, const std::vector<lacx_block_fault>& faults, uint32_t* rows) {
-    const uint32_t align = (uint32_t)p.info.channels * (p.info.bit_depth / 8u);
-    for (uint32_t b = 0; b < p.item.blocks; ++b) rows[3 * b] = row_frames(j.in[p.src].lac, p.info.version, b), rows[3 * b + 1] = rows[3 * b + 2] = 0;
-    for (const lacx_block_fault& f : faults) rows[3 * f.block + 2] = f.code;
-    for (uint32_t b = 0; b < p.item.blocks; ++b)
-        if (!rows[3 * b + 2]) rows[3 * b + 1] = crc_finish(j.a.block_raw[p.item.block0 + b], (unsigned long long)rows[3 * b] * align);
+// the rows of a planned item, made by the code the host side makes them with (manifest.h, called by collect of api_decode.cpp)
+std::vector<lacx_block_digest> rows_of(const Job& j, const PlanItem& p, const std::vector<lacx_block_fault>& faults) {
+    std::vector<lacx_block_digest> rows;
+    rows_of_decoded(j.src.in[p.src].lac, p.info.version, p.item.blocks, p.info.channels, p.info.bit_depth, faults, j.run->a.block_raw + p.item.block0, rows);
+    return rows;
 }
 
-bool planar(uint32_t layout) { return layout == (uint32_t)PCM_PLANAR_I32 || layout == (uint32_t)PCM_PLANAR_I16 || layout == (uint32_t)PCM_PLANAR_F32; }
-uint32_t elem_bytes(uint32_t layout) {
-    if (layout == (uint32_t)PCM_INTERLEAVED_I16 || layout == (uint32_t)PCM_PLANAR_I16) return 2;
-    return layout == (uint32_t)PCM_INTERLEAVED_I24 ? 3 : 4;
+// "<frames:crc:code,...>" of the digest lines
+std::string rows_text(const std::vector<lacx_block_digest>& rows) {
+    std::string s;
+    for (size_t b = 0; b < rows.size(); ++b)
+        s += (b ? "," : "") + std::to_string(rows[b].frames) + ":" + std::to_string(rows[b].crc32) + ":" + std::to_string(rows[b].code);
+    return s;
 }
 
 }  // namespace
@@ -284,35 +187,35 @@ int64_t sim_blockdigest(const uint8_t* const* lacs, const uint64_t* sizes, const
                         int form, int cols, int zero_status, uint64_t* rec, uint32_t* rows, uint64_t rows_cap, uint8_t* image,
                         uint64_t image_cap, int32_t* left, int32_t* right, uint64_t pcm_cap, char* msg, uint32_t msg_cap, uint64_t* atomics) {
     if ((cols != 1 && cols != 64) || form < 0 || form > 2) return -1;
-    Job j;
-    if (!run(lacs, sizes, mans, man_sizes, n, form, cols, zero_status != 0, j)) return -1;
+    Job j(lacs, sizes, n, form);
+    if (!run(mans, man_sizes, n, form, cols, zero_status != 0, j)) return -1;
     std::string all;
     for (uint32_t i = 0; i < n; ++i) {
         rec[8 * i] = (uint64_t)j.code[i];
         all += (i ? "\n" : "") + j.err[i];
     }
     std::snprintf(msg, msg_cap, "%s", all.c_str());
-    uint64_t nrows = 0, at = 0;
-    for (const PlanItem& p : j.plan.items) {
-        std::vector<lacx_block_fault> faults;
-        const lacx_salvage_result r = salvage_report(p, j.in[p.src].lac, j.st->p, faults);
-        if (nrows + r.blocks > rows_cap) return -1;
-        rows_of(j, p, faults, rows + 3 * nrows);
-        nrows += r.blocks;
-        const uint64_t q[7] = {r.blocks, r.bad_blocks, r.frames, r.lost_frames, r.first_bad, r.flags, form == 2 ? at : p.image_at};
-        std::memcpy(rec + 8 * p.src + 1, q, sizeof(q));
+    uint64_t nrows = 0, written = 0;
+    bool fits = true;
+    salvage_records(j.plan, j.src.in.data(), j.run->st.p, form == 2,
+                    [&](const PlanItem& p, const lacx_salvage_result& r, const std::vector<lacx_block_fault>& faults, const uint64_t* q) {
+        if (nrows + r.blocks > rows_cap || (form == 2 && q[6] + r.frames > pcm_cap)) return fits = false;
+        const std::vector<lacx_block_digest> got = rows_of(j, p, faults);
+        for (uint32_t b = 0; b < r.blocks; ++b, ++nrows) rows[3 * nrows] = got[b].frames, rows[3 * nrows + 1] = got[b].crc32, rows[3 * nrows + 2] = got[b].code;
+        std::memcpy(rec + 8 * p.src + 1, q, 7 * sizeof(uint64_t));
         if (form == 2) {
-            if (at + r.frames > pcm_cap) return -1;
-            std::memcpy(left + at, j.in[p.src].left, 4 * r.frames);
-            if (j.in[p.src].right) std::memcpy(right + at, j.in[p.src].right, 4 * r.frames);
-            at += r.frames;
+            std::memcpy(left + q[6], j.src.in[p.src].left, 4 * r.frames);
+            if (j.src.in[p.src].right) std::memcpy(right + q[6], j.src.in[p.src].right, 4 * r.frames);
+            written = q[6] + r.frames;
         }
-    }
+        return true;
+    });
+    if (!fits) return -1;
     *atomics = j.atomics;
-    if (form == 2) return (int64_t)at;
+    if (form == 2) return (int64_t)written;
     if (form == 0) return 0;
     if (j.plan.need.image > image_cap) return -1;
-    std::memcpy(image, j.image->p, j.plan.need.image);
+    std::memcpy(image, j.run->image.p, j.plan.need.image);
     return (int64_t)j.plan.need.image;
 }
 
@@ -346,30 +249,20 @@ int sim_blockdigest_line(const uint8_t* blob, uint64_t size, uint32_t index, cha
         mans[i] = nullptr;
         if (msizes[i] != ~0ull && !(mans[i] = take(msizes[i]))) return -1;
     }
-    Job j;
     const int form = (int)(flags & 3u);
-    if (form > 2 || !run(lacs.data(), sizes.data(), mans.data(), msizes.data(), n, form, (flags & 4u) ? 64 : 1, (flags & 8u) != 0, j)) return -1;
+    if (form > 2) return -1;
+    Job j(lacs.data(), sizes.data(), n, form);
+    if (!run(mans.data(), msizes.data(), n, form, (flags & 4u) ? 64 : 1, (flags & 8u) != 0, j)) return -1;
     std::vector<std::string> item(n);
     for (uint32_t i = 0; i < n; ++i) item[i] = "!" + std::to_string(j.code[i]);
-    for (const PlanItem& p : j.plan.items) {
-        std::vector<lacx_block_fault> faults;
-        const lacx_salvage_result r = salvage_report(p, j.in[p.src].lac, j.st->p, faults);
-        uint64_t h = 0xCBF29CE484222325ull;
-        if (form == 2) {
-            h = fnv(j.in[p.src].left, 4 * r.frames, h);
-            if (j.in[p.src].right) h = fnv(j.in[p.src].right, 4 * r.frames, h);
-        } else if (form == 1) {
-            h = fnv(j.image->p + p.image_at + 44, p.image_size - 44, h);
-        }
+    salvage_records(j.plan, j.src.in.data(), j.run->st.p, form == 2,
+                    [&](const PlanItem& p, const lacx_salvage_result& r, const std::vector<lacx_block_fault>& faults, const uint64_t*) {
+        const uint64_t h = form == 0 ? kFnvStart : salvage_hash(p, j.src.in[p.src], j.run->image.p, form == 2, r.frames);
         char hex[24];
         std::snprintf(hex, sizeof(hex), "%016llx", (unsigned long long)h);
-        std::vector<uint32_t> rows(3 * (size_t)r.blocks + 1);
-        rows_of(j, p, faults, rows.data());
-        std::string s = std::string(hex) + " " + std::to_string(r.flags) + " ";
-        for (uint32_t b = 0; b < r.blocks; ++b)
-            s += (b ? "," : "") + std::to_string(rows[3 * b]) + ":" + std::to_string(rows[3 * b + 1]) + ":" + std::to_string(rows[3 * b + 2]);
-        item[p.src] = s;
-    }
+        item[p.src] = std::string(hex) + " " + std::to_string(r.flags) + " " + rows_text(rows_of(j, p, faults));
+        return true;
+    });
     std::string out = std::to_string(index) + " ";
     for (uint32_t i = 0; i < n; ++i) out += (i ? ";" : "") + item[i];
     if (out.size() + 1 > cap) return -1;
@@ -389,10 +282,10 @@ int64_t sim_blockdigest_source(uint32_t layout, uint32_t channels, uint32_t bit_
     const bool pl = planar(layout), f32 = layout == (uint32_t)PCM_PLANAR_F32 || layout == (uint32_t)PCM_INTERLEAVED_F32;
     const uint64_t bytes0 = pl ? frames * eb : frames * channels * eb;
     // exact allocations: malloc returns 16-byte aligned memory; we need base % 16 == offset and end == allocation end
-    const uint64_t lead = offset % 16u;
-    std::unique_ptr<Heap<uint8_t>> e0(new Heap<uint8_t>(lead + bytes0)), e1(pl && channels == 2 ? new Heap<uint8_t>(lead + bytes0) : nullptr);
-    uint8_t* s0 = e0->p + lead;
-    uint8_t* s1 = e1 ? e1->p + lead : nullptr;
+    const bool two_rows = pl && channels == 2;
+    Exact e0(bytes0, offset % 16u), e1(two_rows ? bytes0 : 0, offset % 16u);
+    uint8_t* s0 = e0.data;
+    uint8_t* s1 = two_rows ? e1.data : nullptr;
     for (uint64_t f = 0; f < frames; ++f)
         for (uint32_t c = 0; c < channels; ++c) {
             int32_t v = samples[c * frames + f];
@@ -400,8 +293,7 @@ int64_t sim_blockdigest_source(uint32_t layout, uint32_t channels, uint32_t bit_
                 const float x = (float)v / (float)(1 << (bit_depth - 1));
                 std::memcpy(&v, &x, 4);
             }
-            uint8_t* p = pl ? (c ? s1 : s0) + eb * f : s0 + eb * (f * channels + c);
-            for (uint32_t k = 0; k < eb; ++k) p[k] = (uint8_t)((uint32_t)v >> (8 * k));
+            put_elem(s0, s1, layout, channels, f, c, v);
         }
     const uint64_t nb = (frames + grid - 1) / grid;
     if (nb > rows_cap) return -1;
@@ -409,7 +301,7 @@ int64_t sim_blockdigest_source(uint32_t layout, uint32_t channels, uint32_t bit_
     const unsigned long long unit_off[2] = {0, (frames + 3u) / 4u};
     unsigned long long bad = kDigestClean;
     *atomics = 0;
-    const bool agreed = sum_like_kernel(1, unit_off[1], unit_off, [&](uint32_t, unsigned long long f0, Lane& t) {
+    const bool agreed = sum_like_kernel(1, unit_off[1], unit_off, [&](uint32_t, unsigned long long f0, UnitLane& t) {
         unsigned long long k = kDigestClean;
         t.align = channels * (bit_depth / 8u);
         t.fmt = crc_format((int)channels, (int)bit_depth);
@@ -419,12 +311,9 @@ int64_t sim_blockdigest_source(uint32_t layout, uint32_t channels, uint32_t bit_
     }, raw.data(), atomics);
     if (!agreed) return -1;
     *key = bad;
-    for (uint64_t b = 0; b < nb; ++b) {
-        const uint32_t nfr = b + 1 < nb ? grid : (uint32_t)(frames - grid * b);
-        rows[3 * b] = nfr;
-        rows[3 * b + 1] = crc_finish(raw[b], (unsigned long long)nfr * channels * (bit_depth / 8u));
-        rows[3 * b + 2] = 0;
-    }
+    std::vector<lacx_block_digest> got;
+    rows_of_source(frames, grid, (uint32_t)nb, channels, bit_depth, raw.data(), got);  // as digest_pcm_run of api_decode.cpp does
+    for (uint64_t b = 0; b < nb; ++b) rows[3 * b] = got[b].frames, rows[3 * b + 1] = got[b].crc32, rows[3 * b + 2] = got[b].code;
     return (int64_t)nb;
 }
 
@@ -470,38 +359,30 @@ int sim_manifest_parse(const uint8_t* m, uint64_t size, uint64_t* info, uint32_t
 // the end.
 int main(int argc, char** argv) {
     if (argc != 2) return 2;
-    FILE* f = std::fopen(argv[1], "rb");
-    if (!f) return 2;
     std::vector<char> line(1 << 22);
-    unsigned long done = 0;
-    for (uint8_t sz[4]; std::fread(sz, 1, 4, f) == 4; ++done) {
-        const uint32_t size = sz[0] | (sz[1] << 8) | (sz[2] << 16) | ((uint32_t)sz[3] << 24);
-        Heap<uint8_t> blob(size);
-        if (size < 1 || std::fread(blob.p, 1, size, f) != size) return 3;
-        if (blob.p[0] == 0) {
-            if (sim_blockdigest_line(blob.p + 1, size - 1, (uint32_t)done, line.data(), (uint32_t)line.size())) return 4;
+    return for_each_case(argv[1], [&](const uint8_t* blob, uint32_t size, uint32_t i) {
+        if (size < 1) return false;
+        if (blob[0] == 0) {
+            if (sim_blockdigest_line(blob + 1, size - 1, i, line.data(), (uint32_t)line.size())) return false;
         } else {
-            if (size < 1 + 28) return 3;
-            uint32_t w[5];
-            uint64_t frames;
-            std::memcpy(w, blob.p + 1, 20), std::memcpy(&frames, blob.p + 21, 8);
-            if ((uint64_t)size - 29 != 4ull * w[1] * frames) return 3;
-            Heap<int32_t> samples(w[1] * frames);
-            std::memcpy(samples.p, blob.p + 29, 4ull * w[1] * frames);
-            const uint64_t cap = frames / w[3] + 2;
+            Reader rd{blob + 1, blob + size};
+            const uint32_t layout = rd.get<uint32_t>(), channels = rd.get<uint32_t>(), depth = rd.get<uint32_t>(), grid = rd.get<uint32_t>();
+            const uint32_t offset = rd.get<uint32_t>();
+            const uint64_t frames = rd.get<uint64_t>();
+            if (!rd.ok || (uint64_t)(rd.end - rd.p) != 4ull * channels * frames) return false;
+            Heap<int32_t> samples(channels * frames);
+            std::memcpy(samples.p, rd.p, 4ull * channels * frames);
+            const uint64_t cap = frames / grid + 2;
             std::vector<uint32_t> rows(3 * cap);
             uint64_t key = 0, atomics = 0;
-            const int64_t nb = sim_blockdigest_source(w[0], w[1], w[2], frames, w[3], w[4], samples.p, rows.data(), cap, &key, &atomics);
-            if (nb < 0) return 4;
-            std::string s = std::to_string(done) + " " + std::to_string(key) + " ";
+            const int64_t nb = sim_blockdigest_source(layout, channels, depth, frames, grid, offset, samples.p, rows.data(), cap, &key, &atomics);
+            if (nb < 0) return false;
+            std::string s = std::to_string(i) + " " + std::to_string(key) + " ";
             for (int64_t b = 0; b < nb; ++b)
                 s += (b ? "," : "") + std::to_string(rows[3 * b]) + ":" + std::to_string(rows[3 * b + 1]) + ":" + std::to_string(rows[3 * b + 2]);
             std::snprintf(line.data(), line.size(), "%s", s.c_str());
         }
-        std::puts(line.data());
-    }
-    std::fclose(f);
-    std::printf("done %lu\n", done);
-    return 0;
+        return std::puts(line.data()) >= 0;
+    });
 }
 #endif

@@ -10,17 +10,11 @@
 //
 // Built twice by tests/dectwin.py: a plain -O2 shared library for ctypes, and (-DSIM_DECODE_MAIN) a sanitized program that
 // walks a corpus file through every switch setting and prints one digest line per stream, or a file of batch cases.
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
-
-#include "decode_core.h"
-#include "decode_plan.h"
+#define SIM_JOB_SIMULATOR
+#include "sim_job.h"
 
 using namespace lacx;
+using namespace simjob;
 
 namespace {
 
@@ -33,77 +27,7 @@ void shuffle(std::vector<uint32_t>& v, uint32_t seed) {
     }
 }
 
-template <typename T>
-struct Heap {  // exactly n elements, nothing behind them
-    T* p;
-    explicit Heap(size_t n, int fill = 0) : p(static_cast<T*>(std::malloc(n ? n * sizeof(T) : 1))) {
-        if (n) std::memset(p, fill, n * sizeof(T));
-    }
-    ~Heap() { std::free(p); }
-    Heap(const Heap&) = delete;
-    Heap& operator=(const Heap&) = delete;
-};
-
 constexpr uint32_t kSimDefaultPad = ~0u;
-
-// The buffers of a run, each of exactly the plan's capacity (`pad` bytes in place of kDecodeTailPad behind the payload),
-// the tables filled with their addresses, and the kernels' arguments.
-struct Run {
-    Heap<uint8_t> payload, tables, flag, image;
-    Heap<int32_t> L, R;
-    Heap<uint32_t> st;
-    DecodeArgs a;
-    Run(const DecodePlan& p, const BatchIn* in, uint32_t pad)
-        : payload(p.need.payload - kDecodeTailPad + pad), tables(p.need.tables), flag(p.need.blocks), image(p.need.image),
-          L(p.need.pcm_frames), R(p.need.pcm_frames), st(p.need.blocks) {
-        plan_fill_tables(p, in, PlanBases{payload.p, L.p, R.p, image.p}, tables.p);
-        a = plan_args(p, tables.p, payload.p, st.p, flag.p);
-    }
-};
-
-struct Lane {  // one column of lane memory (the last of `cols`) and the wave policy
-    Heap<unsigned char> raw;
-    DecMem dm;
-    int lane;
-    DecWave wave;
-    Lane(int cols, int never_lean) : raw(kDecBytesPerCol * (size_t)cols, 0xA5), dm(dec_mem(raw.p, (uint32_t)cols)), lane(cols - 1) {
-        wave.never_lean = never_lean != 0;
-    }
-};
-
-// k_decode: lane g decodes block lane_blk[g]; k_decode_serial: one lane per version-2 item
-void run_lanes(const DecodeArgs& a, Lane& ln) {
-    for (uint32_t g = 0; g < a.lanes; ++g) {
-        const uint32_t blk = a.lane_blk[g];
-        if (blk == ~0u) continue;
-        const DecodeItem& it = a.items[a.blk_item[blk]];
-        decode_block_lane(blk, it.channels, it.stereo_mode, a.payload, a.byte_off, a.frame_off, it.frame0, it.left, it.right, a.status,
-                          a.ms_flag, ln.dm, ln.lane, ln.wave);
-    }
-    for (uint32_t g = 0; g < a.nv2; ++g) {
-        const DecodeItem& it = a.items[a.v2_items[g]];
-        decode_serial_lane(it.blocks, it.channels, it.stereo_mode, a.payload + it.pay_off, it.pay_bits, a.frame_off + it.block0, it.frame0,
-                           it.left, it.right, a.status + it.block0, a.ms_flag + it.block0, ln.dm, ln.lane, ln.wave);
-    }
-}
-
-// k_ms_inverse: grid (blocks, 16 tiles) x 256 threads
-void run_ms_inverse(const DecodeArgs& a) {
-    for (uint32_t blk = 0; blk < a.total_blocks; ++blk) {
-        if (a.status[blk]) continue;
-        const DecodeItem& it = a.items[a.blk_item[blk]];
-        const unsigned long long f0 = a.frame_off[blk];
-        const uint32_t n = (uint32_t)(a.frame_off[blk + 1] - f0);
-        for (uint32_t tile = 0; tile < (uint32_t)kMaxBlock / 1024u; ++tile)
-            for (uint32_t tid = 0; tid < 256u; ++tid)
-                ms_inverse_tile(blk, tile, it.channels, it.bit_depth, f0 - it.frame0, n, it.left, it.right, a.ms_flag, a.status, tid);
-    }
-}
-
-// every item's payload range where the plan puts it
-void place_payload(const DecodePlan& plan, const BatchIn* in, uint8_t* payload) {
-    for (const PlanItem& p : plan.items) std::memcpy(payload + p.item.pay_off, in[p.src].lac + p.head + p.pay_src, p.pay_bytes);
-}
 
 // a whole stream into host arrays, as a batch of one; false where the plan refuses it
 bool plan_one(const uint8_t* lac, uint64_t size, int32_t* left, int32_t* right, BatchIn& in, DecodePlan& plan) {
@@ -403,40 +327,15 @@ int sim_digest(const uint8_t* lac, uint64_t size, uint32_t index, uint32_t setti
 int main(int argc, char** argv) {
     const bool batch = argc == 3 && !std::strcmp(argv[1], "batch");
     if (argc != 6 && !batch) return 2;
-    FILE* f = std::fopen(argv[batch ? 2 : 1], "rb");
-    if (!f) return 2;
     std::vector<char> line(1 << 20);
-    unsigned long done = 0;
-    for (uint8_t sz[4]; batch && std::fread(sz, 1, 4, f) == 4; ++done) {
-        const uint32_t size = sz[0] | (sz[1] << 8) | (sz[2] << 16) | ((uint32_t)sz[3] << 24);
-        Heap<uint8_t> blob(size);
-        if (std::fread(blob.p, 1, size, f) != size) return 3;
-        if (sim_batch_digest(blob.p, size, (uint32_t)done, line.data(), (uint32_t)line.size())) return 4;
-        std::puts(line.data());
-    }
-    if (batch) {
-        std::fclose(f);
-        std::printf("done %lu\n", done);
-        return 0;
-    }
+    if (batch)
+        return for_each_case(argv[2], [&](const uint8_t* blob, uint32_t size, uint32_t i) {
+            return !sim_batch_digest(blob, size, i, line.data(), (uint32_t)line.size()) && std::puts(line.data()) >= 0;
+        });
     const unsigned long first = std::strtoul(argv[2], nullptr, 10), count = std::strtoul(argv[3], nullptr, 10);
     const uint32_t settings = (uint32_t)std::strtoul(argv[4], nullptr, 10), pad = (uint32_t)std::strtoul(argv[5], nullptr, 10);
-    for (unsigned long i = 0; i < first + count; ++i) {
-        uint8_t sz[4];
-        if (std::fread(sz, 1, 4, f) != 4) break;
-        const uint32_t size = sz[0] | (sz[1] << 8) | (sz[2] << 16) | ((uint32_t)sz[3] << 24);
-        if (i < first) {
-            std::fseek(f, (long)size, SEEK_CUR);
-            continue;
-        }
-        Heap<uint8_t> lac(size);  // the stream itself, exact too: the container walk is checked with it
-        if (std::fread(lac.p, 1, size, f) != size) return 3;
-        if (sim_digest(lac.p, size, (uint32_t)i, settings, pad, line.data(), (uint32_t)line.size())) return 4;
-        std::puts(line.data());
-        ++done;
-    }
-    std::fclose(f);
-    std::printf("done %lu\n", done);
-    return 0;
+    return for_each_case(argv[1], [&](const uint8_t* lac, uint32_t size, uint32_t i) {  // the stream itself exact too: the container walk is checked with it
+        return !sim_digest(lac, size, i, settings, pad, line.data(), (uint32_t)line.size()) && std::puts(line.data()) >= 0;
+    }, first, count);
 }
 #endif

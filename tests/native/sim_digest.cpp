@@ -19,62 +19,13 @@
 //   "<case> <offset> <crc of the decoded form> <crc of the source form> <source key> <status,status,...>"
 // Built twice by tests/digesttwin.py: a plain -O2 shared library for ctypes, and (-DSIM_DIGEST_MAIN) a sanitized program
 // that walks a file of cases.
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
-
 #include "digest_core.h"
+#include "sim_job.h"
 
 using namespace lacx;
+using namespace simjob;
 
 namespace {
-
-struct Reader {
-    const uint8_t* p;
-    const uint8_t* end;
-    bool ok = true;
-    template <typename T>
-    T get() {
-        T v{};
-        if ((size_t)(end - p) < sizeof(T)) return ok = false, v;
-        std::memcpy(&v, p, sizeof(T));
-        p += sizeof(T);
-        return v;
-    }
-    template <typename T>
-    std::vector<T> array(uint64_t n) {
-        std::vector<T> v;
-        if (n > (uint64_t)(end - p) / sizeof(T)) return ok = false, v;
-        v.resize(n);
-        if (n) std::memcpy(v.data(), p, n * sizeof(T));
-        p += n * sizeof(T);
-        return v;
-    }
-};
-
-// `bytes` bytes whose first lies `offset` bytes behind a 16-byte aligned address and whose last is the last of the allocation
-struct Exact {
-    uint8_t* raw;
-    uint8_t* data;
-    Exact(uint64_t bytes, uint32_t offset) : raw(static_cast<uint8_t*>(std::malloc(offset + bytes ? offset + bytes : 1))), data(raw + offset) {}
-    ~Exact() { std::free(raw); }
-    Exact(const Exact&) = delete;
-    Exact& operator=(const Exact&) = delete;
-};
-
-bool planar(uint32_t layout) { return layout == (uint32_t)PCM_PLANAR_I32 || layout == (uint32_t)PCM_PLANAR_I16 || layout == (uint32_t)PCM_PLANAR_F32; }
-uint32_t elem_bytes(uint32_t layout) {
-    if (layout == (uint32_t)PCM_INTERLEAVED_I16 || layout == (uint32_t)PCM_PLANAR_I16) return 2;
-    return layout == (uint32_t)PCM_INTERLEAVED_I24 ? 3 : 4;
-}
-void put_elem(uint8_t* src0, uint8_t* src1, uint32_t layout, uint32_t channels, uint64_t f, uint32_t c, int32_t v) {
-    const uint32_t eb = elem_bytes(layout);
-    uint8_t* p = planar(layout) ? (c ? src1 : src0) + eb * f : src0 + eb * (f * channels + c);
-    for (uint32_t k = 0; k < eb; ++k) p[k] = (uint8_t)((uint32_t)v >> (8 * k));
-}
 
 // k_digest's sum over the units of one item: piece(u) is unit u's value and byte count
 template <typename Piece>
@@ -185,22 +136,9 @@ int sim_digest_lines(const uint8_t* blob, uint64_t size, uint32_t index, char* l
 // stdout, "done <cases>" at the end.
 int main(int argc, char** argv) {
     if (argc != 2) return 2;
-    FILE* f = std::fopen(argv[1], "rb");
-    if (!f) return 2;
-    unsigned long done = 0;
-    for (;; ++done) {
-        uint8_t sz[4];
-        if (std::fread(sz, 1, 4, f) != 4) break;
-        const uint32_t size = sz[0] | (sz[1] << 8) | (sz[2] << 16) | ((uint32_t)sz[3] << 24);
-        uint8_t* blob = static_cast<uint8_t*>(std::malloc(size ? size : 1));  // exact: the case reader is checked too
-        if (std::fread(blob, 1, size, f) != size) return 3;
+    return for_each_case(argv[1], [](const uint8_t* blob, uint32_t size, uint32_t i) {
         std::string out;
-        if (sim_digest_case(blob, size, (uint32_t)done, &out)) return 4;
-        std::fputs(out.c_str(), stdout);
-        std::free(blob);
-    }
-    std::fclose(f);
-    std::printf("done %lu\n", done);
-    return 0;
+        return !sim_digest_case(blob, size, i, &out) && std::fputs(out.c_str(), stdout) >= 0;
+    });
 }
 #endif

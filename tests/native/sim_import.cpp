@@ -14,27 +14,13 @@
 // Answer: u32 alias, u32 code, u64 key_left, u64 key_right, u64 nbytes, the destination's bytes, u32 message length, message.
 // Built twice by tests/importtwin.py: a plain -O2 shared library for ctypes, and (-DSIM_IMPORT_MAIN) a sanitized program
 // that walks a file of cases and writes a file of answers.
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
-
 #include "import_msg.h"
+#include "sim_job.h"
 
 using namespace lacx;
+using namespace simjob;
 
 namespace {
-
-struct Exact {  // `bytes` bytes whose first lies `offset` bytes behind a 16-byte aligned address (malloc's), and whose last
-    uint8_t* raw;  // is the last of its allocation
-    uint8_t* data;
-    Exact(uint64_t bytes, uint64_t offset) : raw(static_cast<uint8_t*>(std::malloc(offset + bytes ? offset + bytes : 1))), data(raw + offset) {}
-    ~Exact() { std::free(raw); }
-    Exact(const Exact&) = delete;
-    Exact& operator=(const Exact&) = delete;
-};
 
 void put(std::string& out, const void* p, size_t n) { out.append(static_cast<const char*>(p), n); }
 
@@ -119,24 +105,13 @@ int sim_f32_to_pcm(uint32_t bits, int depth, int32_t* v) { return f32_to_pcm(bit
 // back to back into ANSWERS, "done <cases>" on stdout.
 int main(int argc, char** argv) {
     if (argc != 3) return 2;
-    FILE* f = std::fopen(argv[1], "rb");
     FILE* o = std::fopen(argv[2], "wb");
-    if (!f || !o) return 2;
-    unsigned long done = 0;
-    for (;; ++done) {
-        uint8_t sz[4];
-        if (std::fread(sz, 1, 4, f) != 4) break;
-        const uint32_t size = sz[0] | (sz[1] << 8) | (sz[2] << 16) | ((uint32_t)sz[3] << 24);
-        uint8_t* blob = static_cast<uint8_t*>(std::malloc(size ? size : 1));  // exact: the case reader is checked too
-        if (std::fread(blob, 1, size, f) != size) return 3;
+    if (!o) return 2;
+    const int rc = for_each_case(argv[1], [&](const uint8_t* blob, uint32_t size, uint32_t) {
         std::string out;
-        if (sim_import_case(blob, size, &out)) return 4;
-        std::fwrite(out.data(), 1, out.size(), o);
-        std::free(blob);
-    }
-    std::fclose(f);
+        return !sim_import_case(blob, size, &out) && std::fwrite(out.data(), 1, out.size(), o) == out.size();
+    });
     std::fclose(o);
-    std::printf("done %lu\n", done);
-    return 0;
+    return rc;
 }
 #endif

@@ -14,6 +14,7 @@
 #include <memory>
 
 #include "recovery_plan.h"
+#include "sim_job.h"
 
 using namespace lacx;
 
@@ -221,19 +222,10 @@ int sim_recovery_parse(const uint8_t* m, uint64_t size, lacx_recovery_info* info
 // file of cases (u32 length, case)*: prints "<index> <length of the answer> <its CRC-32>" per case and "done <count>"
 int main(int argc, char** argv) {
     if (argc < 2) return 2;
-    std::FILE* f = std::fopen(argv[1], "rb");
-    if (!f) return 2;
-    uint32_t len = 0, count = 0;
-    while (std::fread(&len, 4, 1, f) == 1) {
-        std::vector<uint8_t> blob(len);
-        if (len && std::fread(blob.data(), 1, len, f) != len) return 2;
+    return simjob::for_each_case(argv[1], [](const uint8_t* blob, uint32_t size, uint32_t i) {
         Writer w;
-        if (!run_case(blob.data(), blob.size(), w)) return 3;
-        std::printf("%u %zu %08x\n", count, w.bytes.size(), recovery_detail::crc32_of(w.bytes.data(), w.bytes.size()));
-        ++count;
-    }
-    std::fclose(f);
-    std::printf("done %u\n", count);
-    return 0;
+        if (!run_case(blob, size, w)) return false;
+        return std::printf("%u %zu %08x\n", i, w.bytes.size(), recovery_detail::crc32_of(w.bytes.data(), w.bytes.size())) > 0;
+    });
 }
 #endif

@@ -15,138 +15,39 @@
 //
 // Built twice by tests/salvagetwin.py: a plain -O2 shared library for ctypes, and (-DSIM_SALVAGE_MAIN) a sanitized program
 // that runs a file of cases and prints one digest line per case.
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <string>
-#include <vector>
-
-#include "decode_core.h"
-#include "decode_plan.h"
-#include "salvage_core.h"
+#define SIM_JOB_SIMULATOR
+#include "sim_job.h"
 
 using namespace lacx;
+using namespace simjob;
 
 namespace {
 
-template <typename T>
-struct Heap {  // exactly n elements, nothing behind them
-    T* p;
-    explicit Heap(size_t n, int fill = 0) : p(static_cast<T*>(std::malloc(n ? n * sizeof(T) : 1))) {
-        if (n) std::memset(p, fill, n * sizeof(T));
-    }
-    ~Heap() { std::free(p); }
-    Heap(const Heap&) = delete;
-    Heap& operator=(const Heap&) = delete;
-};
-
 constexpr int kFill = 0xCD;
 
-uint64_t fnv(const void* data, uint64_t bytes, uint64_t h) {
-    const uint8_t* p = static_cast<const uint8_t*>(data);
-    for (uint64_t i = 0; i < bytes; ++i) {
-        h ^= p[i];
-        h *= 0x100000001B3ull;
-    }
-    return h;
-}
-
 struct Job {
-    std::vector<BatchIn> in;
-    std::vector<std::unique_ptr<Heap<int32_t>>> own;  // device form: the caller's arrays
+    SalvageIn src;
     DecodePlan plan;
     std::vector<int> code;
     std::vector<std::string> err;
-    std::unique_ptr<Heap<uint8_t>> payload, tables, flag, image;
-    std::unique_ptr<Heap<int32_t>> L, R;
-    std::unique_ptr<Heap<uint32_t>> st;
-    DecodeArgs a;
+    std::unique_ptr<Run> run;
     uint32_t over = 0;
+    Job(const uint8_t* const* lacs, const uint64_t* sizes, uint32_t n, bool device) : src(lacs, sizes, n, device) {}
 };
 
 // plans and runs; false where the plan refuses the job as a whole
-bool run(const uint8_t* const* lacs, const uint64_t* sizes, uint32_t n, bool device, int cols, bool never_lean, bool zero_status, Job& j) {
-    j.in.resize(n);
-    for (uint32_t i = 0; i < n; ++i) {
-        lacx_stream_info info{};
-        uint32_t present = 0, flags = 0;
-        const char* why = nullptr;
-        int32_t *l = nullptr, *r = nullptr;
-        uint64_t frames = 0;
-        if (device && scan_stream(lacs[i], sizes[i], &info, &present, &flags, &why) == LACX_OK) {
-            frames = info.frames;  // what lacx_stream_scan tells the caller to allocate
-            j.own.emplace_back(new Heap<int32_t>(frames, 0x5A));
-            l = j.own.back()->p;
-            if (info.channels == 2) {
-                j.own.emplace_back(new Heap<int32_t>(frames, 0x5A));
-                r = j.own.back()->p;
-            }
-        }
-        j.in[i] = BatchIn{lacs[i], sizes[i], l, r, frames};
-    }
-    if (plan_decode(j.in.data(), n, device ? DecodeForm::device : DecodeForm::wav, kWholeStreams, false, j.plan, j.code, j.err, true)) return false;
-    const DecodePlan& p = j.plan;
-    j.payload.reset(new Heap<uint8_t>(p.need.payload));  // zeroed: the tail pad
-    j.tables.reset(new Heap<uint8_t>(p.need.tables));
-    j.flag.reset(new Heap<uint8_t>(p.need.blocks, kFill));
-    j.image.reset(new Heap<uint8_t>(p.need.image, kFill));
-    j.L.reset(new Heap<int32_t>(p.need.pcm_frames, kFill));
-    j.R.reset(new Heap<int32_t>(p.need.pcm_frames, kFill));
-    j.st.reset(new Heap<uint32_t>(p.need.blocks, zero_status ? 0 : kFill));
-    plan_fill_tables(p, j.in.data(), PlanBases{j.payload->p, j.L->p, j.R->p, j.image->p}, j.tables->p);
-    const DecodeArgs a = j.a = plan_args(p, j.tables->p, j.payload->p, j.st->p, j.flag->p);
-    for (const PlanItem& it : p.items) std::memcpy(j.payload->p + it.item.pay_off, j.in[it.src].lac + it.head + it.pay_src, it.pay_bytes);
-    if (p.items.empty()) return true;
-
-    Heap<unsigned char> raw(kDecBytesPerCol * (size_t)cols, 0xA5);
-    DecMem dm = dec_mem(raw.p, (uint32_t)cols);
-    DecWave wave;
-    wave.never_lean = never_lean;
-    for (uint32_t g = 0; g < a.lanes; ++g) {  // k_decode
-        const uint32_t blk = a.lane_blk[g];
-        if (blk == ~0u) continue;
-        const DecodeItem& it = a.items[a.blk_item[blk]];
-        decode_block_lane(blk, it.channels, it.stereo_mode, a.payload, a.byte_off, a.frame_off, it.frame0, it.left, it.right, a.status,
-                          a.ms_flag, dm, cols - 1, wave);
-    }
-    for (uint32_t g = 0; g < a.nv2; ++g) {  // k_decode_serial
-        const DecodeItem& it = a.items[a.v2_items[g]];
-        decode_serial_lane(it.blocks, it.channels, it.stereo_mode, a.payload + it.pay_off, it.pay_bits, a.frame_off + it.block0, it.frame0,
-                           it.left, it.right, a.status + it.block0, a.ms_flag + it.block0, dm, cols - 1, wave);
-    }
-    j.over = wave.over;
-    for (uint32_t blk = 0; blk < a.total_blocks; ++blk) {  // k_ms_inverse: grid (blocks, 16 tiles) x 256 threads
-        if (a.status[blk]) continue;
-        const DecodeItem& it = a.items[a.blk_item[blk]];
-        const unsigned long long f0 = a.frame_off[blk];
-        const uint32_t nfr = (uint32_t)(a.frame_off[blk + 1] - f0);
-        for (uint32_t tile = 0; tile < (uint32_t)kMaxBlock / 1024u; ++tile)
-            for (uint32_t tid = 0; tid < 256u; ++tid)
-                ms_inverse_tile(blk, tile, it.channels, it.bit_depth, f0 - it.frame0, nfr, it.left, it.right, a.ms_flag, a.status, tid);
-    }
-    if (!a.present) return false;
-    if (a.wav) {  // k_salvage_wav: thread u of the concatenated unit ranges
-        uint32_t item = 0;
-        for (unsigned long long u = 0; u < a.total_units; ++u) {
-            while (a.unit_off[item + 1] <= u) ++item;
-            const DecodeItem& it = a.items[item];
-            salvage_wav_unit(4ull * (u - a.unit_off[item]), it.blocks, a.present[item], it.channels, it.bit_depth, it.frames,
-                             a.frame_off + it.block0, it.frame0, it.left, it.right, a.status + it.block0, it.wav);
-        }
-    } else {  // k_salvage_blank: grid (blocks, 16 tiles) x 256 threads
-        for (uint32_t blk = 0; blk < a.total_blocks; ++blk) {
-            const uint32_t item = a.blk_item[blk];
-            const DecodeItem& it = a.items[item];
-            if (!salvage_lost(a.status + it.block0, blk - it.block0, a.present[item])) continue;
-            const unsigned long long f0 = a.frame_off[blk];
-            const uint32_t nfr = (uint32_t)(a.frame_off[blk + 1] - f0);
-            for (uint32_t tile = 0; tile < (uint32_t)kMaxBlock / 1024u; ++tile)
-                for (uint32_t tid = 0; tid < 256u; ++tid)
-                    salvage_blank_tile(tile, f0 - it.frame0, nfr, it.left, it.channels == 2 ? it.right : nullptr, tid);
-        }
-    }
+bool run(uint32_t n, bool device, int cols, bool never_lean, bool zero_status, Job& j) {
+    const BatchIn* in = j.src.in.data();
+    if (plan_decode(in, n, device ? DecodeForm::device : DecodeForm::wav, kWholeStreams, false, j.plan, j.code, j.err, true)) return false;
+    j.run.reset(new Run(j.plan, in, (uint32_t)kDecodeTailPad, kFill, zero_status ? 0 : kFill));
+    place_payload(j.plan, in, j.run->payload.p);
+    if (j.plan.items.empty()) return true;
+    Lane ln(cols, never_lean);
+    run_lanes(j.run->a, ln);
+    j.over = ln.wave.over;
+    run_ms_inverse(j.run->a);
+    if (!j.run->a.present) return false;
+    run_salvage_pass(j.run->a);
     return true;
 }
 
@@ -167,35 +68,35 @@ int64_t sim_salvage(const uint8_t* const* lacs, const uint64_t* sizes, uint32_t 
                     uint32_t* codes, uint64_t codes_cap, uint8_t* image, uint64_t image_cap, int32_t* left, int32_t* right,
                     uint64_t pcm_cap, char* msg, uint32_t msg_cap, uint32_t* over) {
     if (cols != 1 && cols != 64) return -1;
-    Job j;
-    if (!run(lacs, sizes, n, device != 0, cols, never_lean != 0, zero_status != 0, j)) return -1;
+    Job j(lacs, sizes, n, device != 0);
+    if (!run(n, device != 0, cols, never_lean != 0, zero_status != 0, j)) return -1;
     std::string all;
     for (uint32_t i = 0; i < n; ++i) {
         rec[8 * i] = j.code[i] != LACX_OK;
         all += (i ? "\n" : "") + j.err[i];
     }
     std::snprintf(msg, msg_cap, "%s", all.c_str());
-    uint64_t ncodes = 0, at = 0;
-    for (const PlanItem& p : j.plan.items) {
-        std::vector<lacx_block_fault> faults;
-        const lacx_salvage_result r = salvage_report(p, j.in[p.src].lac, j.st->p, faults);
-        if (ncodes + r.blocks > codes_cap) return -1;
+    uint64_t ncodes = 0, written = 0;
+    bool fits = true;
+    salvage_records(j.plan, j.src.in.data(), j.run->st.p, device != 0,
+                    [&](const PlanItem& p, const lacx_salvage_result& r, const std::vector<lacx_block_fault>& faults, const uint64_t* q) {
+        if (ncodes + r.blocks > codes_cap || (device && q[6] + r.frames > pcm_cap)) return fits = false;
         std::memset(codes + ncodes, 0, 4ull * r.blocks);
         for (const lacx_block_fault& f : faults) codes[ncodes + f.block] = f.code;
         ncodes += r.blocks;
-        const uint64_t q[7] = {r.blocks, r.bad_blocks, r.frames, r.lost_frames, r.first_bad, r.flags, device ? at : p.image_at};
-        std::memcpy(rec + 8 * p.src + 1, q, sizeof(q));
+        std::memcpy(rec + 8 * p.src + 1, q, 7 * sizeof(uint64_t));
         if (device) {
-            if (at + r.frames > pcm_cap) return -1;
-            std::memcpy(left + at, j.in[p.src].left, 4 * r.frames);
-            if (j.in[p.src].right) std::memcpy(right + at, j.in[p.src].right, 4 * r.frames);
-            at += r.frames;
+            std::memcpy(left + q[6], j.src.in[p.src].left, 4 * r.frames);
+            if (j.src.in[p.src].right) std::memcpy(right + q[6], j.src.in[p.src].right, 4 * r.frames);
+            written = q[6] + r.frames;
         }
-    }
+        return true;
+    });
+    if (!fits) return -1;
     *over = j.over;
-    if (device) return (int64_t)at;
+    if (device) return (int64_t)written;
     if (j.plan.need.image > image_cap) return -1;
-    std::memcpy(image, j.image->p, j.plan.need.image);
+    std::memcpy(image, j.run->image.p, j.plan.need.image);
     return (int64_t)j.plan.need.image;
 }
 
@@ -220,28 +121,21 @@ int sim_salvage_digest(const uint8_t* blob, uint64_t size, uint32_t index, char*
         lacs[i] = own.back()->p;
         at += sizes[i];
     }
-    Job j;
     const bool device = flags & 1u;
-    if (!run(lacs.data(), sizes.data(), n, device, (flags & 2u) ? 64 : 1, (flags & 4u) != 0, (flags & 8u) != 0, j)) return -1;
+    Job j(lacs.data(), sizes.data(), n, device);
+    if (!run(n, device, (flags & 2u) ? 64 : 1, (flags & 4u) != 0, (flags & 8u) != 0, j)) return -1;
     std::vector<std::string> item(n, "-");
-    for (const PlanItem& p : j.plan.items) {
-        std::vector<lacx_block_fault> faults;
-        const lacx_salvage_result r = salvage_report(p, j.in[p.src].lac, j.st->p, faults);
-        uint64_t h = 0xCBF29CE484222325ull;
-        if (device) {
-            h = fnv(j.in[p.src].left, 4 * r.frames, h);
-            if (j.in[p.src].right) h = fnv(j.in[p.src].right, 4 * r.frames, h);
-        } else {
-            h = fnv(j.image->p + p.image_at + 44, p.image_size - 44, h);
-        }
+    salvage_records(j.plan, j.src.in.data(), j.run->st.p, device,
+                    [&](const PlanItem& p, const lacx_salvage_result& r, const std::vector<lacx_block_fault>& faults, const uint64_t*) {
         char hex[24];
-        std::snprintf(hex, sizeof(hex), "%016llx", (unsigned long long)h);
+        std::snprintf(hex, sizeof(hex), "%016llx", (unsigned long long)salvage_hash(p, j.src.in[p.src], j.run->image.p, device, r.frames));
         std::vector<uint32_t> codes(r.blocks, 0);
         for (const lacx_block_fault& f : faults) codes[f.block] = f.code;
         std::string s = std::string(hex) + " " + std::to_string(r.flags) + " ";
         for (uint32_t b = 0; b < r.blocks; ++b) s += (b ? "," : "") + std::to_string(codes[b]);
         item[p.src] = s;
-    }
+        return true;
+    });
     std::string out = std::to_string(index) + " " + std::to_string(j.over) + " ";
     for (uint32_t i = 0; i < n; ++i) out += (i ? ";" : "") + item[i];
     if (out.size() + 1 > cap) return -1;
@@ -303,19 +197,9 @@ int64_t sim_salvage_plan(const uint8_t* const* lacs, const uint64_t* sizes, uint
 // sim_salvage_digest), one line each on stdout, "done <count>" at the end.
 int main(int argc, char** argv) {
     if (argc != 2) return 2;
-    FILE* f = std::fopen(argv[1], "rb");
-    if (!f) return 2;
     std::vector<char> line(1 << 22);
-    unsigned long done = 0;
-    for (uint8_t sz[4]; std::fread(sz, 1, 4, f) == 4; ++done) {
-        const uint32_t size = sz[0] | (sz[1] << 8) | (sz[2] << 16) | ((uint32_t)sz[3] << 24);
-        Heap<uint8_t> blob(size);
-        if (std::fread(blob.p, 1, size, f) != size) return 3;
-        if (sim_salvage_digest(blob.p, size, (uint32_t)done, line.data(), (uint32_t)line.size())) return 4;
-        std::puts(line.data());
-    }
-    std::fclose(f);
-    std::printf("done %lu\n", done);
-    return 0;
+    return for_each_case(argv[1], [&](const uint8_t* blob, uint32_t size, uint32_t i) {
+        return !sim_salvage_digest(blob, size, i, line.data(), (uint32_t)line.size()) && std::puts(line.data()) >= 0;
+    });
 }
 #endif

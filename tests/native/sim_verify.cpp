@@ -18,66 +18,11 @@
 //   "<case> <offset> <group> <mismatches> <key> <decoded> <source> <block> <status,status,...>"
 // Built twice by tests/vertwin.py: a plain -O2 shared library for ctypes, and (-DSIM_VERIFY_MAIN) a sanitized program
 // that walks a file of cases.
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
-
+#include "sim_job.h"
 #include "verify_core.h"
 
 using namespace lacx;
-
-namespace {
-
-struct Reader {
-    const uint8_t* p;
-    const uint8_t* end;
-    bool ok = true;
-    template <typename T>
-    T get() {
-        T v{};
-        if ((size_t)(end - p) < sizeof(T)) return ok = false, v;
-        std::memcpy(&v, p, sizeof(T));
-        p += sizeof(T);
-        return v;
-    }
-    template <typename T>
-    std::vector<T> array(uint64_t n) {
-        std::vector<T> v;
-        if (n > (uint64_t)(end - p) / sizeof(T)) return ok = false, v;
-        v.resize(n);
-        if (n) std::memcpy(v.data(), p, n * sizeof(T));
-        p += n * sizeof(T);
-        return v;
-    }
-};
-
-// a source array of exactly `bytes` bytes whose first byte lies `offset` bytes behind a 16-byte aligned address (malloc's)
-// and whose last byte is the last of its allocation
-struct Exact {
-    uint8_t* raw;
-    uint8_t* data;
-    Exact(uint64_t bytes, uint32_t offset) : raw(static_cast<uint8_t*>(std::malloc(offset + bytes ? offset + bytes : 1))), data(raw + offset) {}
-    ~Exact() { std::free(raw); }
-    Exact(const Exact&) = delete;
-    Exact& operator=(const Exact&) = delete;
-};
-
-void put_sample(uint8_t* src0, uint8_t* src1, uint32_t layout, int channels, uint64_t f, uint32_t c, int32_t v) {
-    if (layout == (uint32_t)PCM_PLANAR_I32) {
-        std::memcpy((c ? src1 : src0) + 4 * f, &v, 4);
-    } else if (layout == (uint32_t)PCM_INTERLEAVED_I16) {
-        const int16_t s = (int16_t)v;
-        std::memcpy(src0 + 2 * (f * (uint64_t)channels + c), &s, 2);
-    } else {
-        uint8_t* p = src0 + 3 * (f * (uint64_t)channels + c);
-        p[0] = (uint8_t)v, p[1] = (uint8_t)((uint32_t)v >> 8), p[2] = (uint8_t)((uint32_t)v >> 16);
-    }
-}
-
-}  // namespace
+using namespace simjob;
 
 extern "C" {
 
@@ -97,8 +42,8 @@ int sim_verify_case(const uint8_t* blob, uint64_t size, uint32_t index, std::str
     std::vector<uint8_t> ms(nb);
     for (uint32_t b = 0; b < nb; ++b) frame_off[b + 1] = frame_off[b] + bf[b], ms[b] = (uint8_t)ms32[b];
     if (frame_off[nb] != frames) return -1;
-    const bool planar = layout == (uint32_t)PCM_PLANAR_I32;
-    const uint64_t bytes = planar ? 4 * frames : frames * channels * (layout == (uint32_t)PCM_INTERLEAVED_I16 ? 2u : 3u);
+    const bool two_rows = planar(layout) && channels == 2;
+    const uint64_t bytes = (uint64_t)elem_bytes(layout) * frames * (planar(layout) ? 1u : channels);
     for (uint32_t g = 0; g < ngroups; ++g) {
         const uint32_t nedits = rd.get<uint32_t>();
         struct Edit {
@@ -121,13 +66,13 @@ int sim_verify_case(const uint8_t* blob, uint64_t size, uint32_t index, std::str
             std::memcpy(L, dl.data(), 4 * frames);
             if (R) std::memcpy(R, dr.data(), 4 * frames);
             std::vector<uint32_t> status(st_in);
-            Exact s0(bytes, off), s1(planar && channels == 2 ? bytes : 0, off);
-            uint8_t* p1 = planar && channels == 2 ? s1.data : nullptr;
+            Exact s0(bytes, off), s1(two_rows ? bytes : 0, off);
+            uint8_t* p1 = two_rows ? s1.data : nullptr;
             for (uint64_t f = 0; f < frames; ++f) {
-                put_sample(s0.data, p1, layout, (int)channels, f, 0, nedits == ~0u ? sl[f] ^ 1 : sl[f]);
-                if (channels == 2) put_sample(s0.data, p1, layout, (int)channels, f, 1, nedits == ~0u ? sr[f] ^ 1 : sr[f]);
+                put_elem(s0.data, p1, layout, channels, f, 0, nedits == ~0u ? sl[f] ^ 1 : sl[f]);
+                if (channels == 2) put_elem(s0.data, p1, layout, channels, f, 1, nedits == ~0u ? sr[f] ^ 1 : sr[f]);
             }
-            for (const Edit& x : edits) put_sample(s0.data, p1, layout, (int)channels, x.f, x.c, x.v);
+            for (const Edit& x : edits) put_elem(s0.data, p1, layout, channels, x.f, x.c, x.v);
             VerifyWords w{0, ~0ull, 0, 0, 0, 0};
             for (uint64_t u = 0; u < (frames + 3) / 4; ++u) {  // k_verify, thread by thread
                 const uint32_t differ = verify_unit(4 * u, nb, (int)channels, (int)bit_depth, frames, frame_off.data(), 0, L, R,
@@ -167,22 +112,9 @@ int sim_verify_lines(const uint8_t* blob, uint64_t size, uint32_t index, char* l
 // stdout, "done <cases>" at the end.
 int main(int argc, char** argv) {
     if (argc != 2) return 2;
-    FILE* f = std::fopen(argv[1], "rb");
-    if (!f) return 2;
-    unsigned long done = 0;
-    for (;; ++done) {
-        uint8_t sz[4];
-        if (std::fread(sz, 1, 4, f) != 4) break;
-        const uint32_t size = sz[0] | (sz[1] << 8) | (sz[2] << 16) | ((uint32_t)sz[3] << 24);
-        uint8_t* blob = static_cast<uint8_t*>(std::malloc(size ? size : 1));  // exact: the case reader is checked too
-        if (std::fread(blob, 1, size, f) != size) return 3;
+    return for_each_case(argv[1], [](const uint8_t* blob, uint32_t size, uint32_t i) {
         std::string out;
-        if (sim_verify_case(blob, size, (uint32_t)done, &out)) return 4;
-        std::fputs(out.c_str(), stdout);
-        std::free(blob);
-    }
-    std::fclose(f);
-    std::printf("done %lu\n", done);
-    return 0;
+        return !sim_verify_case(blob, size, i, &out) && std::fputs(out.c_str(), stdout) >= 0;
+    });
 }
 #endif

@@ -5,17 +5,14 @@ it into one matrix).  Also the harness of the CPU twin, tests/native/sim_recover
 sanitized build as a program of its own, and cleared(), which lets a job to the device only after the sanitized twin has
 passed it in this run."""
 import ctypes as C
-import os
 import struct
-import subprocess
-import tempfile
+import sys
 import zlib
 from collections import namedtuple
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-import dectwin
+import twinbuild
 
 OK, INVALID, RUNTIME, DEVICE, MISMATCH = 0, 1, 2, 3, 4
 TRUNCATED, TRAILING, SIDECAR_TRUNCATED, UNREPAIRED = 1, 2, 4, 8
@@ -254,16 +251,8 @@ def repair(file: bytes, side: bytes, best_effort=False) -> Outcome:
 
 
 # ---- the CPU twin ---------------------------------------------------------------------------------------------------------
-SRC = os.path.join(dectwin.ROOT, "tests", "native", "sim_recovery.cpp")
+SRC = twinbuild.NATIVE + "/sim_recovery.cpp"
 _lib = None
-
-
-def _sources():
-    return [SRC] + [os.path.join(dectwin.CSRC, h) for h in ("recovery_plan.h", "recovery_core.h", "crc32_core.h")] + [os.path.join(dectwin.INCLUDE, "lacx.h")]
-
-
-def _stale(target):
-    return not os.path.exists(target) or any(os.path.getmtime(target) < os.path.getmtime(s) for s in _sources())
 
 
 class Info(C.Structure):
@@ -275,11 +264,7 @@ class Info(C.Structure):
 def lib():
     global _lib
     if _lib is None:
-        os.makedirs(dectwin.BUILD, exist_ok=True)
-        so = os.path.join(dectwin.BUILD, "libsim_recovery.so")
-        if _stale(so):
-            subprocess.check_call(["g++", "-O2", "-std=c++20", "-fPIC", "-shared", "-I", dectwin.CSRC, "-I", dectwin.INCLUDE, SRC, "-o", so])
-        _lib = C.CDLL(so)
+        _lib = C.CDLL(twinbuild.shared_lib("sim_recovery", [SRC]))
         _lib.sim_recovery.restype = C.c_longlong
         _lib.sim_recovery.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64]
         _lib.sim_gf_mul4.restype = C.c_uint32
@@ -292,18 +277,7 @@ def lib():
 
 def sanitized_exe():
     """The sanitized program's path, or (None, why) where the sanitizer runtime is missing."""
-    os.makedirs(dectwin.BUILD, exist_ok=True)
-    exe = os.path.join(dectwin.BUILD, "sim_recovery_san")
-    if _stale(exe):
-        obj = exe + ".o"
-        flags = ["g++", "-std=c++20", *dectwin.SANITIZE, "-DSIM_RECOVERY_MAIN", "-I", dectwin.CSRC, "-I", dectwin.INCLUDE]
-        built = subprocess.run(flags + ["-c", SRC, "-o", obj], capture_output=True, text=True)
-        assert built.returncode == 0, built.stderr
-        linked = subprocess.run(["g++", *dectwin.SANITIZE, obj, "-o", exe], capture_output=True, text=True)
-        if linked.returncode != 0 and any(w in linked.stderr for w in ("asan", "ubsan", "sanitize")):
-            return None, "sanitizer runtime not available: " + linked.stderr.strip().splitlines()[-1]
-        assert linked.returncode == 0, linked.stderr
-    return exe, ""
+    return twinbuild.sanitized_exe("sim_recovery_san", [SRC], ["-DSIM_RECOVERY_MAIN"])
 
 
 def build_case(files, S=0, r=0, K=0) -> bytes:
@@ -359,54 +333,25 @@ def outcomes(case: bytes, blob: bytes = None):
     return out
 
 
-def run_sanitized(cases, exe=None, workers=None):
+def run_sanitized(cases, exe=None, workers=8):
     """Every case through the sanitized program, split over a few processes: (lines, returncode, stderr)."""
     if exe is None:
         exe, why = sanitized_exe()
         assert exe, why
-    workers = max(1, min(workers or 8, os.cpu_count() or 1, len(cases)))
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-
-    def part(k):
-        mine = cases[k::workers]
-        with tempfile.NamedTemporaryFile(prefix="lac_recovery_", suffix=".bin") as f:
-            for c in mine:
-                f.write(struct.pack("<I", len(c)))
-                f.write(c)
-            f.flush()
-            done = subprocess.run([exe, f.name], capture_output=True, text=True, env=env, timeout=900)
-        got = [t for t in done.stdout.splitlines() if t and not t.startswith("done")]
-        return got, done.returncode or (0 if "done %d" % len(mine) in done.stdout else 1), done.stderr[-4000:]
-
-    with ThreadPoolExecutor(workers) as pool:
-        runs = list(pool.map(part, range(workers)))
-    lines, rc, err = [None] * len(cases), 0, ""
-    for k, (got, code, text) in enumerate(runs):
-        for i, t in enumerate(got):
-            lines[k + i * workers] = t
-        rc, err = rc or code, err + text
-    return lines, rc, err
+    env = dict(ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    return twinbuild.run_cases(exe, cases, env, workers=workers, prefix="lac_recovery_")
 
 
 def digest_line(blob: bytes) -> str:
     return "%d %08x" % (len(blob), zlib.crc32(blob))
 
 
-_cleared = {}
-
-
 def cleared(key, cases):
     """[the plain build's answer per case], once the sanitized twin has shown in this run that each of these jobs stays inside
     buffers of exactly the plan's capacities and answers as the plain build does.  Fails, never skips, where that cannot
     be shown."""
-    if key in _cleared:
-        return _cleared[key]
-    exe, why = sanitized_exe()
-    assert exe, "the sanitized recovery twin is not available, nothing goes to the device unchecked: %s" % why
-    lines, rc, err = run_sanitized(cases, exe)
-    assert rc == 0, "the sanitized recovery twin stopped (exit %d)\n%s" % (rc, err)
-    answers = [answer(c) for c in cases]
-    for i, a in enumerate(answers):
-        assert lines[i] is not None and lines[i].split(" ", 1)[1] == digest_line(a), "case %d: the sanitized build and the plain build differ" % i
-    _cleared[key] = answers
-    return answers
+    def make():
+        answers = [answer(c) for c in cases]
+        return cases, lambda c, i: digest_line(answers[i]), None, answers
+
+    return twinbuild.cleared("recovery", key, sys.modules[__name__], make)

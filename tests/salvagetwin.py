@@ -22,21 +22,19 @@ must agree: its refused block is the first lost one."""
 from __future__ import annotations
 
 import ctypes as C
-import os
 import struct
-import subprocess
-import tempfile
+import sys
 from collections import namedtuple
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
 import dectwin
 import lacmutate
 import lacstreams
+import twinbuild
 import wavutil
 
-SRC = os.path.join(dectwin.ROOT, "tests", "native", "sim_salvage.cpp")
+SRC = twinbuild.NATIVE + "/sim_salvage.cpp"
 LIMIT = 1 << 30
 MISSING, NOT_REACHED, BEYOND = 10, 8, 9
 TRUNCATED, TRAILING = 1, 2
@@ -52,41 +50,17 @@ _lib = None
 _blocks = {}
 
 
-def _sources():
-    return [SRC] + [os.path.join(dectwin.CSRC, h) for h in ("decode_core.h", "analyze_core.h", "lacx_types.h", "x87.h", "decode_plan.h",
-                                                           "container.h", "salvage_core.h")]
-
-
-def _stale(target):
-    return not os.path.exists(target) or any(os.path.getmtime(target) < os.path.getmtime(s) for s in _sources())
-
-
 def lib():
     global _lib
     if _lib is None:
-        os.makedirs(dectwin.BUILD, exist_ok=True)
-        so = os.path.join(dectwin.BUILD, "libsim_salvage.so")
-        if _stale(so):
-            subprocess.check_call(["g++", "-O2", "-std=c++20", "-fPIC", "-shared", "-I", dectwin.CSRC, "-I", dectwin.INCLUDE, SRC, "-o", so])
-        _lib = C.CDLL(so)
+        _lib = C.CDLL(twinbuild.shared_lib("sim_salvage", [SRC]))
         _lib.sim_salvage.restype = C.c_int64
     return _lib
 
 
 def sanitized_exe():
     """The sanitized program's path, or (None, why) where the sanitizer runtime is missing."""
-    os.makedirs(dectwin.BUILD, exist_ok=True)
-    exe = os.path.join(dectwin.BUILD, "sim_salvage_san")
-    if _stale(exe):
-        obj = exe + ".o"
-        flags = ["g++", "-std=c++20", *dectwin.SANITIZE, "-DSIM_SALVAGE_MAIN", "-I", dectwin.CSRC, "-I", dectwin.INCLUDE]
-        built = subprocess.run(flags + ["-c", SRC, "-o", obj], capture_output=True, text=True)
-        assert built.returncode == 0, built.stderr
-        linked = subprocess.run(["g++", *dectwin.SANITIZE, obj, "-o", exe], capture_output=True, text=True)
-        if linked.returncode != 0 and any(w in linked.stderr for w in ("asan", "ubsan", "sanitize")):
-            return None, "sanitizer runtime not available: " + linked.stderr.strip().splitlines()[-1]
-        assert linked.returncode == 0, linked.stderr
-    return exe, ""
+    return twinbuild.sanitized_exe("sim_salvage_san", [SRC], ["-DSIM_SALVAGE_MAIN"])
 
 
 # ---- expectations -----------------------------------------------------------------------------------------------------
@@ -353,58 +327,33 @@ def digest(blob: bytes, index: int) -> str:
     return buf.value.decode()
 
 
-def run_sanitized(cases, exe=None, workers=None):
+def run_sanitized(cases, exe=None, workers=8):
     """Every case through the sanitized program, split over a few processes: (lines, returncode, stderr)."""
     if exe is None:
         exe, why = sanitized_exe()
         assert exe, why
-    workers = max(1, min(workers or 8, os.cpu_count() or 1, len(cases)))
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:verify_asan_link_order=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-
-    def part(k):  # cases k, k + workers, ...: the long cases do not land in one process
-        mine = cases[k::workers]
-        with tempfile.NamedTemporaryFile(prefix="lac_salvage_", suffix=".bin") as f:
-            for c in mine:
-                f.write(struct.pack("<I", len(c)))
-                f.write(c)
-            f.flush()
-            done = subprocess.run([exe, f.name], capture_output=True, text=True, env=env, timeout=900)
-        got = [t for t in done.stdout.splitlines() if t and not t.startswith("done")]
-        return got, done.returncode or (0 if "done %d" % len(mine) in done.stdout else 1), done.stderr[-4000:]
-
-    with ThreadPoolExecutor(workers) as pool:
-        runs = list(pool.map(part, range(workers)))
-    lines, rc, err = [None] * len(cases), 0, ""
-    for k, (got, code, text) in enumerate(runs):
-        for i, t in enumerate(got):
-            lines[k + i * workers] = t
-        rc, err = rc or code, err + text
-    return lines, rc, err
+    return twinbuild.run_cases(exe, cases, dectwin.ENV, workers=workers, prefix="lac_salvage_")
 
 
 BATCH = 64
-_cleared = {}
 
 
 def cleared(key, lacs):
     """`lacs`, once the sanitized twin has shown in this run that a salvage job over each of them stays inside buffers of
     exactly the plan's capacities -- both forms, both status fills, 1 and 64 columns, in batches -- and answers as the
     plain build does.  Fails, never skips, where that cannot be shown."""
-    if key in _cleared:
-        return _cleared[key]
-    exe, why = sanitized_exe()
-    assert exe, "the sanitized salvage twin is not available, nothing goes to the device unchecked: %s" % why
-    cases = []
-    for at in range(0, len(lacs), BATCH):
-        part = lacs[at:at + BATCH]
-        k = at // BATCH
-        cases.append(case(part, device=False, cols=64 if k & 1 else 1, never_lean=bool(k & 2), zero_status=bool(k & 1)))
-        cases.append(case(part, device=True, cols=1 if k & 1 else 64, never_lean=not (k & 2), zero_status=not (k & 1)))
-    lines, rc, err = run_sanitized(cases, exe)
-    assert rc == 0, "the sanitized salvage twin stopped (exit %d)\n%s" % (rc, err)
-    for i, c in enumerate(cases):
-        assert lines[i] is not None and lines[i].split(" ", 1)[1] == digest(c, i).split(" ", 1)[1], "case %d: the sanitized build and the plain build differ" % i
-        over = int(lines[i].split()[1])
-        assert over <= DERIVED_OVERSHOOT, "case %d: a load reached %d bytes past its block" % (i, over)
-    _cleared[key] = list(lacs)
-    return _cleared[key]
+    def make():
+        cases = []
+        for at in range(0, len(lacs), BATCH):
+            part = lacs[at:at + BATCH]
+            k = at // BATCH
+            cases.append(case(part, device=False, cols=64 if k & 1 else 1, never_lean=bool(k & 2), zero_status=bool(k & 1)))
+            cases.append(case(part, device=True, cols=1 if k & 1 else 64, never_lean=not (k & 2), zero_status=not (k & 1)))
+
+        def check(i, text):
+            over = int(text.split()[1])
+            assert over <= DERIVED_OVERSHOOT, "case %d: a load reached %d bytes past its block" % (i, over)
+
+        return cases, lambda c, i: digest(c, i).split(" ", 1)[1], check, list(lacs)
+
+    return twinbuild.cleared("salvage", key, sys.modules[__name__], make)

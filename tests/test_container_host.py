@@ -6,30 +6,23 @@ import glob
 import itertools
 import json
 import os
-import re
 import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "lossless-audio-codec_amd", "csrc")
-BUILD = os.path.join(ROOT, "tests", "native", "_build")
-SRC = os.path.join(ROOT, "tests", "native", "sim_container.cpp")
+import twinbuild
+
+ROOT = twinbuild.ROOT
+SRC = os.path.join(twinbuild.NATIVE, "sim_container.cpp")
 BLOCK = 16384
 
 
 @functools.lru_cache(maxsize=None)
 def _exe(sanitized):
-    os.makedirs(BUILD, exist_ok=True)
-    exe = os.path.join(BUILD, "sim_container" + ("_san" if sanitized else ""))
-    flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"] if sanitized else ["-O1"]
-    cmd = ["g++", "-std=c++20", "-Wall", "-Werror", *flags, "-I", CSRC, "-I", os.path.join(ROOT, "include"), SRC, "-o", exe]
-    built = subprocess.run(cmd, capture_output=True, text=True)
-    if sanitized and built.returncode != 0 and re.search("asan|ubsan|sanitize", built.stderr):
-        return None, built.stderr.strip().splitlines()[-1]
-    assert built.returncode == 0, built.stderr
-    return exe, ""
+    if sanitized:
+        return twinbuild.sanitized_exe("sim_container_san", [SRC], ["-Wall", "-Werror"])
+    return twinbuild.program("sim_container", [SRC], ["-std=c++20", "-Wall", "-Werror", "-O1"]), ""
 
 
 @functools.lru_cache(maxsize=None)

@@ -12,6 +12,7 @@ Version-2 mutants, where the oracle refuses block b: one lane walks the stream, 
 and those that end before the first changed byte must equal the base's (damage may decode and only fail later); the
 blocks behind b are "not reached" (status 8) unless b only failed the bit-depth check, which runs after the walk."""
 import collections
+import os
 import time
 
 import numpy as np
@@ -22,6 +23,7 @@ import lacgrammar as g
 import lacmutate
 import lacstreams
 import mutantjudge
+import twinbuild
 
 
 @pytest.fixture(scope="module")
@@ -81,7 +83,7 @@ def test_twin_pad_is_the_products():
     """The twin's payload pad is kDecodeTailPad of lacx_types.h -- the constant api_decode.cpp allocates and clears --
     and that constant covers the derived overshoot (a pad below the measured one is reported: next test)."""
     assert dectwin.tail_pad() >= mutantjudge.DERIVED_OVERSHOOT
-    with open(dectwin._sources()[3]) as f:  # lacx_types.h
+    with open(os.path.join(twinbuild.CSRC, "lacx_types.h")) as f:
         assert "constexpr size_t kDecodeTailPad = %d;" % dectwin.tail_pad() in f.read()
 
 

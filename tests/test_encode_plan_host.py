@@ -11,25 +11,18 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "lossless-audio-codec_amd", "csrc")
-BUILD = os.path.join(ROOT, "tests", "native", "_build")
-SRC = os.path.join(ROOT, "tests", "native", "sim_encode_plan.cpp")
+import twinbuild
+
+SRC = os.path.join(twinbuild.NATIVE, "sim_encode_plan.cpp")
 BLOCK, STREAMS, MAX_CHUNKS, MIN_CHUNK_BLOCKS, RANGE_ITEMS, BOTH_WAYS = 16384, 4, 16, 192, 256, 4096
 PLANAR_I32, INTER_I16, INTER_I24, PLANAR_I16, PLANAR_F32, INTER_F32 = 0, 1, 2, 16, 17, 18
 
 
 @functools.lru_cache(maxsize=None)
 def _exe(sanitized):
-    os.makedirs(BUILD, exist_ok=True)
-    exe = os.path.join(BUILD, "sim_encode_plan" + ("_san" if sanitized else ""))
-    flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"] if sanitized else ["-O1"]
-    cmd = ["g++", "-std=c++20", "-Wall", "-Werror", *flags, "-I", CSRC, "-I", os.path.join(ROOT, "include"), SRC, "-o", exe]
-    built = subprocess.run(cmd, capture_output=True, text=True)
-    if sanitized and built.returncode != 0 and re.search("asan|ubsan|sanitize", built.stderr):
-        return None, built.stderr.strip().splitlines()[-1]
-    assert built.returncode == 0, built.stderr
-    return exe, ""
+    if sanitized:
+        return twinbuild.sanitized_exe("sim_encode_plan_san", [SRC], ["-Wall", "-Werror"])
+    return twinbuild.program("sim_encode_plan", [SRC], ["-std=c++20", "-Wall", "-Werror", "-O1"]), ""
 
 
 @functools.lru_cache(maxsize=None)

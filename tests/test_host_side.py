@@ -90,16 +90,12 @@ def test_assemble_matches_single_stream(pkg, oracle):
 
 
 def _build_mirror_test():
-    import subprocess
+    import twinbuild
 
-    build = os.path.join(ROOT, "tests", "native", "_build")
-    os.makedirs(build, exist_ok=True)
-    exe = os.path.join(build, "mirror_api_test")
     pkgdir = os.path.join(ROOT, "lossless-audio-codec_amd")
-    subprocess.check_call(["g++", "-std=c++20", "-O1", "-I", os.path.join(pkgdir, "include"), "-I",
-                           os.path.join(pkgdir, "include_decoder"), "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "native", "mirror_api_test.cpp"),
-                           "-L", pkgdir, "-llacx", "-Wl,-rpath," + pkgdir, "-o", exe])
-    return exe
+    return twinbuild.program("mirror_api_test", [os.path.join(twinbuild.NATIVE, "mirror_api_test.cpp")], ["-std=c++20", "-O1"],
+                             link=["-L", pkgdir, "-llacx", "-Wl,-rpath," + pkgdir],
+                             include=[os.path.join(pkgdir, "include"), os.path.join(pkgdir, "include_decoder")])
 
 
 def test_cpp_mirror_classes_compile_and_validate_arguments(pkg):

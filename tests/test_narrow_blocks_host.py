@@ -8,13 +8,13 @@ every block -- default variant, forced 64-bit arithmetic (1) and every phase_b_q
 Measured on the CPU: the whole module about 47 s, of which check_coverage() + check_flag_coverage() about 10 s."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import narrowrecipes as N
-from test_native_units import BUILD, CSRC, ROOT, CPlan
+import twinbuild
+from test_native_units import CPlan
 
 VARIANTS = (0, 1, 32)
 
@@ -49,11 +49,7 @@ def test_oracle_gives_the_reference_bytes(oracle, ref, family):
 
 @pytest.fixture(scope="module")
 def sim():
-    os.makedirs(BUILD, exist_ok=True)
-    so = os.path.join(BUILD, "libsim_narrow.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++20", "-fPIC", "-shared", "-I", CSRC,
-                           os.path.join(ROOT, "tests", "native", "sim_analyze.cpp"), "-o", so])
-    return C.CDLL(so)
+    return C.CDLL(twinbuild.shared_lib("sim_narrow", [os.path.join(twinbuild.NATIVE, "sim_analyze.cpp")]))
 
 
 def _sim_diffs(sim, b, rec, data, zr, pt, variants, out):

@@ -2,25 +2,19 @@
 the lock-step simulator from the kernel's own per-thread phases and compared with the oracle's plan and size.  No GPU."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import twinbuild
+
 from test_native_units import CPlan
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "lossless-audio-codec_amd", "csrc")
-BUILD = os.path.join(ROOT, "tests", "native", "_build")
 
 
 @pytest.fixture(scope="module")
 def sim8x32():
-    os.makedirs(BUILD, exist_ok=True)
-    so = os.path.join(BUILD, "libsim_probe_halves.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++20", "-fPIC", "-shared", "-I", CSRC, "-I", os.path.join(ROOT, "tests", "native"),
-                           os.path.join(ROOT, "tests", "native", "sim_probe_halves.cpp"), "-o", so])
-    return C.CDLL(so)
+    return C.CDLL(twinbuild.shared_lib("sim_probe_halves", [os.path.join(twinbuild.NATIVE, "sim_probe_halves.cpp")], include=[twinbuild.NATIVE]))
 
 
 def _check(sim, oracle, x, zr=True, pt=True, wide=0):

@@ -13,19 +13,14 @@ when there is none (decoded, source and block are then zero)."""
 from __future__ import annotations
 
 import ctypes as C
-import os
 import struct
-import subprocess
-import tempfile
 from collections import namedtuple
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "lossless-audio-codec_amd", "csrc")
-BUILD = os.path.join(ROOT, "tests", "native", "_build")
-SRC = os.path.join(ROOT, "tests", "native", "sim_verify.cpp")
-SANITIZE = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
+import twinbuild
+
+SRC = twinbuild.NATIVE + "/sim_verify.cpp"
 PLANAR, I16, I24 = 0, 1, 2
 ALL_DIFFERENT = 0xFFFFFFFF  # a group's edit count that stands for "every sample ^ 1"
 NO_KEY = (1 << 64) - 1
@@ -35,40 +30,17 @@ Line = namedtuple("Line", "mismatches key decoded source block status")
 _lib = None
 
 
-def _sources():
-    return [SRC] + [os.path.join(CSRC, h) for h in ("verify_core.h", "decode_core.h", "analyze_core.h", "lacx_types.h", "x87.h")]
-
-
-def _stale(target):
-    return not os.path.exists(target) or any(os.path.getmtime(target) < os.path.getmtime(s) for s in _sources())
-
-
 def lib():
     """The plain build."""
     global _lib
     if _lib is None:
-        os.makedirs(BUILD, exist_ok=True)
-        so = os.path.join(BUILD, "libsim_verify.so")
-        if _stale(so):
-            subprocess.check_call(["g++", "-O2", "-std=c++20", "-fPIC", "-shared", "-I", CSRC, SRC, "-o", so])
-        _lib = C.CDLL(so)
+        _lib = C.CDLL(twinbuild.shared_lib("sim_verify", [SRC]))
     return _lib
 
 
 def sanitized_exe():
     """The sanitized program's path, or (None, why) where the sanitizer runtime is missing."""
-    os.makedirs(BUILD, exist_ok=True)
-    exe = os.path.join(BUILD, "sim_verify_san")
-    if _stale(exe):
-        obj = exe + ".o"
-        built = subprocess.run(["g++", "-std=c++20", *SANITIZE, "-DSIM_VERIFY_MAIN", "-I", CSRC, "-c", SRC, "-o", obj],
-                               capture_output=True, text=True)
-        assert built.returncode == 0, built.stderr
-        linked = subprocess.run(["g++", *SANITIZE, obj, "-o", exe], capture_output=True, text=True)
-        if linked.returncode != 0 and any(w in linked.stderr for w in ("asan", "ubsan", "sanitize")):
-            return None, "sanitizer runtime not available: " + linked.stderr.strip().splitlines()[-1]
-        assert linked.returncode == 0, linked.stderr
-    return exe, ""
+    return twinbuild.sanitized_exe("sim_verify_san", [SRC], ["-DSIM_VERIFY_MAIN"])
 
 
 def to_scratch(left, right, block_frames, ms):
@@ -166,14 +138,6 @@ def run_sanitized(cases, exe=None):
     if exe is None:
         exe, why = sanitized_exe()
         assert exe, why
-    with tempfile.NamedTemporaryFile(prefix="verify_cases_", suffix=".bin") as f:
-        for case in cases:
-            blob = case.blob()
-            f.write(struct.pack("<I", len(blob)))
-            f.write(blob)
-        f.flush()
-        env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:verify_asan_link_order=0:abort_on_error=0",
-                   UBSAN_OPTIONS="print_stacktrace=1")
-        run = subprocess.run([exe, f.name], capture_output=True, text=True, env=env, timeout=600)
-    rc = run.returncode if run.returncode != 0 or f"done {len(cases)}" in run.stdout else 1
-    return parse_lines(run.stdout), rc, run.stderr[-4000:]
+    env = dict(ASAN_OPTIONS="detect_leaks=0:verify_asan_link_order=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    lines, rc, err = twinbuild.run_cases(exe, [case.blob() for case in cases], env, prefix="verify_cases_", timeout=600)
+    return parse_lines("\n".join(lines)), rc, err

@@ -4,15 +4,12 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
+import twinbuild
 import x87recipes as X
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "lossless-audio-codec_amd", "csrc")
-BUILD = os.path.join(ROOT, "tests", "native", "_build")
 HOOKS = ("lacx_hook_x87_ops", "lacx_hook_levinson_tables")
 
 
@@ -38,11 +35,7 @@ _host = None
 def host_lib():
     global _host
     if _host is None:
-        os.makedirs(BUILD, exist_ok=True)
-        so = os.path.join(BUILD, "libx87_host.so")
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-I", CSRC,
-                               os.path.join(ROOT, "tests", "native", "x87_host.cpp"), "-o", so])
-        _host = C.CDLL(so)
+        _host = C.CDLL(twinbuild.shared_lib("x87_host", [os.path.join(twinbuild.NATIVE, "x87_host.cpp")], std="c++17"))
         _host.x87_host_ops.restype = None
         _host.x87_host_levinson.restype = None
     return _host
