@@ -48,6 +48,10 @@
  *   lacx_decoder_salvage_wav_batch_view_checked,
  *   lacx_decoder_salvage_batch_device_checked <- damage that still decodes: one CRC-32 per block, kept in a manifest
  *                             beside the stream and honoured by the decoder (code 11, "digest mismatch")
+ *   lacx_decoder_stats_batch_device, lacx_decoder_stats_pcm_batch_device,
+ *   lacx_decoder_item_block_stats,
+ *   lacx_stats_combine      <- what the audio is, not whether it decodes: per block and per stream peaks, energy, silence,
+ *                             full-scale hits, channel equality and bit use, exact integers made on the device
  *   lacx_recovery_build, lacx_recovery_build_batch_view, lacx_recovery_parse,
  *   lacx_recovery_scan_batch, lacx_recovery_repair, lacx_recovery_repair_batch_view,
  *   lacx_decoder_item_bad_slices <- bringing lost bytes back: a parity sidecar ("LACR", Reed-Solomon over GF(2^8)) beside
@@ -694,6 +698,82 @@ int lacx_decoder_salvage_wav_batch_view_checked(lacx_decoder* dec, const lacx_sp
                                                 lacx_span* out, int* item_rc, lacx_salvage_result* results, float* device_ms);
 int lacx_decoder_salvage_batch_device_checked(lacx_decoder* dec, const lacx_decode_item* items, const lacx_span* manifests, uint32_t n,
                                               void* stream, int* item_rc, lacx_salvage_result* results, float* device_ms);
+
+/* Audio statistics: peaks, energy, silence and bit use, made on the device where the samples lie.  Decode, verify, digest
+ * and check answer whether a stream decodes and to what bytes; these entry points answer what the audio is: is it digital
+ * silence and where does the sound start and stop, does it hit full scale, is this stereo file two identical channels, is
+ * this 24-bit file 16-bit audio with eight zero bits, what are its peak, DC and energy and where along the stream is the
+ * energy.  Every quantity is an exact integer reduction over the final left / right samples of the stream's bit depth b;
+ * nothing floating-point crosses this ABI (dBFS, RMS and the like are derived by the caller).
+ * A stats job is the blocks form of a salvage job: k_stats_blocks runs behind the in-place mid/side inverse in the slot
+ * k_digest_blocks has, every block's status final, and leaves one row per block (at most 16384 frames): about 100 bytes per
+ * block come back, not the PCM.  The rows are the stream's energy and silence envelope.
+ * lacx_channel_stats, per block and per channel: min, max; or_bits: OR of the samples' low b bits; full_scale: samples equal
+ *   to -2^(b-1) or 2^(b-1)-1; zeros: samples equal to 0; sum; sum_sq (at most 16384 * 2^46).
+ * lacx_block_stats: frames; code: 0, or why the block is lost (1..10, as lacx_block_digest.code); lead_zero_frames /
+ *   trail_zero_frames: the leading / trailing frames whose samples are 0 in every channel (both equal frames for a silent
+ *   block); differing: frames with left != right (0 for mono); ch[1] is all zero for mono.  A lost block's row has its
+ *   frames and code, every other field 0.
+ * lacx_stats, per item, made on the host from the rows by lacx_stats_combine: totals over the decoded blocks.
+ *   silent_blocks: decoded blocks with lead_zero_frames == frames.  lead_zero_frames / trail_zero_frames: the frames before
+ *   the first, and after the last, frame that is non-zero or lies in a lost block (a lost block is not known to be silent,
+ *   so it counts as sound).  sum and sum_sq are 128-bit pairs: a stream may have 2^56 frames.  With no decoded block min
+ *   and max are 0.
+ * lacx_decoder_stats_batch_device: lenient exactly like lacx_decoder_digest_blocks_batch_device -- versions 3 and 2,
+ *   truncated files, LACX_OK whenever the container is accepted; a refused container keeps the strict code and text and
+ *   gets a zeroed result.  out: nullable array of n.
+ * lacx_decoder_stats_pcm_batch_device: device-resident source PCM in any LACX_PCM_* layout on a regular grid of
+ *   block_frames frames (0 means 16384; else 256..16384, anything else LACX_E_INVALID for the call); the per-item host
+ *   checks, the device-found validation texts and the bounds are those of lacx_decoder_digest_pcm_blocks_batch_device.  A
+ *   failed item gets a zeroed result and no rows.
+ * lacx_decoder_item_block_stats: the rows of item i of the decoder's last stats call, valid until its next call;
+ *   LACX_E_INVALID outside that call.
+ * lacx_stats_combine: host only, no device: the totals of `count` rows (rows may be null when count is 0), public so that
+ *   a caller can total a sub-range of rows (a window's blocks).  LACX_E_INVALID: null out, null rows with count > 0,
+ *   channels not 1 or 2, bit depth not 16 or 24.
+ * Everything else as lacx_decoder_decode_batch_device: the return code, "stream i: " prefixes, lacx_decoder_item_error,
+ * n = 0, null arrays, device-less behaviour (host-side outcomes filled, then LACX_E_DEVICE) and `stream`.
+ * Time (scripts/stats_bench.py, profiles/stats_bench.txt): on 48 four-minute stereo streams as one job 24.4 ms of
+ * kernels, 1.9 ms below the block digests' job; k_stats_blocks alone 6.1 ms for 4.06 GB of PCM, which is not bound by
+ * reading it once.  What bounds it is not measured yet. */
+typedef struct lacx_channel_stats { /* 40 bytes */
+    int32_t min, max;
+    uint32_t or_bits, full_scale, zeros, reserved;
+    int64_t sum;
+    uint64_t sum_sq;
+} lacx_channel_stats;
+typedef struct lacx_block_stats {   /* 104 bytes */
+    uint32_t frames, code;
+    uint32_t lead_zero_frames, trail_zero_frames;
+    uint32_t differing, reserved;
+    lacx_channel_stats ch[2];
+} lacx_block_stats;
+typedef struct lacx_channel_totals { /* 64 bytes */
+    int32_t min, max;
+    uint32_t or_bits, reserved;
+    uint64_t full_scale, zeros;
+    uint64_t sum_lo;                /* sum as a signed 128-bit value: sum_hi * 2^64 + sum_lo */
+    int64_t sum_hi;
+    uint64_t sum_sq_lo, sum_sq_hi;  /* sum_sq as an unsigned 128-bit value */
+} lacx_channel_totals;
+typedef struct lacx_stats {         /* 192 bytes */
+    uint64_t frames;
+    uint32_t sample_rate;
+    uint8_t channels, bit_depth, reserved[2];
+    uint32_t blocks, lost_blocks;
+    uint64_t lost_frames;
+    uint32_t silent_blocks, reserved2;
+    uint64_t lead_zero_frames, trail_zero_frames;
+    uint64_t differing;
+    lacx_channel_totals ch[2];
+} lacx_stats;
+int lacx_decoder_stats_batch_device(lacx_decoder* dec, const lacx_span* lacs, uint32_t n, void* stream, int* item_rc, lacx_stats* out,
+                                    float* device_ms);
+int lacx_decoder_stats_pcm_batch_device(lacx_decoder* dec, const lacx_digest_source* src, uint32_t n, uint32_t block_frames, void* stream,
+                                        int* item_rc, lacx_stats* out, float* device_ms);
+int lacx_decoder_item_block_stats(const lacx_decoder* dec, uint32_t i, const lacx_block_stats** rows, uint32_t* count);
+int lacx_stats_combine(const lacx_block_stats* rows, uint32_t count, uint8_t channels, uint8_t bit_depth, uint32_t sample_rate,
+                       lacx_stats* out);
 
 /* Recovery data: repairing a damaged .lac file from a parity sidecar.  Digests, salvage and the manifest all end in "this
  * block is lost"; the container has no redundancy of its own.  A recovery sidecar ("LACR") kept beside the file brings the

@@ -493,7 +493,12 @@ uint32_t lacx_sizeof(const char* name) {
                  {"digest_source", sizeof(lacx_digest_source)}, {"block_fault", sizeof(lacx_block_fault)},
                  {"salvage_result", sizeof(lacx_salvage_result)}, {"block_digest", sizeof(lacx_block_digest)},
                  {"manifest_info", sizeof(lacx_manifest_info)},   {"recovery_params", sizeof(lacx_recovery_params)},
-                 {"recovery_info", sizeof(lacx_recovery_info)}, {"repair_result", sizeof(lacx_repair_result)}};
+                 {"recovery_info", sizeof(lacx_recovery_info)}, {"repair_result", sizeof(lacx_repair_result)},
+                 {"channel_stats", sizeof(lacx_channel_stats)}, {"block_stats", sizeof(lacx_block_stats)},
+                 {"channel_totals", sizeof(lacx_channel_totals)}, {"stats", sizeof(lacx_stats)}};
+    static_assert(sizeof(lacx_channel_stats) == 40 && sizeof(lacx_block_stats) == 104 && sizeof(lacx_channel_totals) == 64 &&
+                      sizeof(lacx_stats) == 192,
+                  "the statistics' records have fixed sizes (lacx.h)");
     for (const auto& t : table)
         if (std::strcmp(name, t.name) == 0) return (uint32_t)t.size;
     return 0;

@@ -5,6 +5,7 @@
 #include "device_buf.h"
 #include "encoder_impl.h"
 #include "import_msg.h"
+#include "stats_rows.h"
 
 // (the entry points are declared extern "C" in lacx.h)
 // ---- decode -------------------------------------------------------------------------------------
@@ -102,7 +103,10 @@ struct DecodeJob {
     lacx_salvage_result* sres = nullptr; // salvage: [n]
     bool blocks = false;                 // salvage with block digests (DecodePlan::blocks); the items' manifests in BatchIn
     bool check = false;                  // ... as a question: a fault or a truncation fails the item with LACX_E_MISMATCH
+    bool stats = false;                  // salvage in the blocks form with the statistics kernel (DecodePlan::stats)
+    lacx_stats* stres = nullptr;         // stats: [n]
 };
+static_assert(sizeof(StatsAcc) == kStatsRowBytes, "the plan lays the accumulator rows out kStatsRowBytes apart");
 
 // What the digest kernel left for an item (DigestWords::raw), as the caller's record: the init term and the final xor
 // depend on the length alone, and the image's CRC-32 follows from its parts -- header, data, pad byte.
@@ -233,6 +237,8 @@ DevErr launch_and_wait(lacx_decoder* d, const DecodeJob& job, const DecodePlan& 
     const size_t res = plan.at.res, m = plan.items.size();
     if (DevErr e = chk(hipEventRecord(d->e0, st), "event record")) return e;
     if (DevErr e = chk(launch_decode(a, st), "decode launch")) return e;
+    if (plan.stats)  // behind k_ms_inverse, every block's status final: the slot k_digest_blocks has in a digest job
+        if (DevErr e = chk(launch_stats_blocks(plan_stats_args(plan, a, d->d_meta()), st), "stats launch")) return e;
     if (DevErr e = chk(hipEventRecord(d->e1, st), "event record")) return e;
     if (DevErr e = chk(hipMemcpyAsync(d->h_status(), d->d_status(), (size_t)plan.total_blocks * sizeof(uint32_t), hipMemcpyDeviceToHost, st), "D2H status"))
         return e;
@@ -252,6 +258,12 @@ DevErr launch_and_wait(lacx_decoder* d, const DecodeJob& job, const DecodePlan& 
         if (DevErr e = chk(hipMemcpyAsync(d->h_meta() + plan.at.raw, d->d_meta() + plan.at.raw, 4 * (size_t)plan.total_blocks, hipMemcpyDeviceToHost, st),
                            "D2H block digests"))
             return e;
+    // statistics: kStatsRowBytes per block beside the statuses
+    if (plan.stats && plan.total_blocks)
+        if (DevErr e = chk(hipMemcpyAsync(d->h_meta() + plan.at.stats, d->d_meta() + plan.at.stats, kStatsRowBytes * (size_t)plan.need.stats_rows,
+                                          hipMemcpyDeviceToHost, st),
+                           "D2H statistics"))
+            return e;
     if (DevErr e = chk(hipStreamSynchronize(st), "synchronize")) return e;
     if (job.device_ms) (void)hipEventElapsedTime(job.device_ms, d->e0, d->e1);
     return DevErr{};
@@ -268,6 +280,12 @@ DevErr collect(lacx_decoder* d, const DecodeJob& job, const DecodePlan& plan, hi
         if (plan.salvage) {  // every block's outcome, not the first: the status words and present_blocks are the whole report
             const lacx_salvage_result r = salvage_report(p, x.lac, d->h_status(), d->item_faults[i]);
             if (job.sres) job.sres[i] = r;
+            if (plan.stats) {  // the rows: every block's frames and, where it decoded, its statistics; the totals from the rows
+                const StatsAcc* acc = reinterpret_cast<const StatsAcc*>(d->h_meta() + plan.at.stats) + p.item.block0;
+                std::vector<lacx_block_stats>& rows = d->item_stats[i];
+                stats_rows_of_decoded(x.lac, p.info.version, p.item.blocks, p.info.channels, d->item_faults[i], acc, rows);
+                if (job.stres) job.stres[i] = stats_combine(rows.data(), (uint32_t)rows.size(), p.info.channels, p.info.bit_depth, p.info.sample_rate);
+            }
             if (plan.blocks) {  // the rows: every block's frames and, where it decoded, its finished CRC-32
                 const uint32_t* raw = reinterpret_cast<const uint32_t*>(d->h_meta() + plan.at.raw) + p.item.block0;
                 std::vector<lacx_block_digest>& rows = d->item_rows[i];
@@ -341,10 +359,12 @@ int decode_batch_run(lacx_decoder* d, const DecodeJob& job, std::vector<int>& co
     if (job.sres) std::memset(job.sres, 0, sizeof(lacx_salvage_result) * job.n);
     if (job.salvage) d->item_faults.assign(job.n, {});
     if (job.blocks) d->item_rows.assign(job.n, {});
+    if (job.stres) std::memset(job.stres, 0, sizeof(lacx_stats) * job.n);
+    if (job.stats) d->item_stats.assign(job.n, {});
     // LACX_DECODE_BATCH_PAD=1 (tuning knob, read per call): every item's blocks start a new wave
     const char* pad_env = std::getenv("LACX_DECODE_BATCH_PAD");
     DecodePlan plan;
-    const char* whole = plan_decode(job.in, job.n, job.form, job.sample_type, pad_env && pad_env[0] == '1', plan, code, err, job.salvage, job.blocks);
+    const char* whole = plan_decode(job.in, job.n, job.form, job.sample_type, pad_env && pad_env[0] == '1', plan, code, err, job.salvage, job.blocks, job.stats);
     if (lacx_device_count() <= 0) whole = "no usable HIP device";
     int rc = whole ? decode_fail(LACX_E_DEVICE, whole) : LACX_OK;
     if (!whole && !plan.items.empty()) {
@@ -364,6 +384,8 @@ int decode_batch_run(lacx_decoder* d, const DecodeJob& job, std::vector<int>& co
         if (job.sres) std::memset(job.sres, 0, sizeof(lacx_salvage_result) * job.n);
         if (job.salvage) d->item_faults.assign(job.n, {});
         if (job.blocks) d->item_rows.assign(job.n, {});
+        if (job.stats) d->item_stats.assign(job.n, {});
+        if (job.stres) std::memset(job.stres, 0, sizeof(lacx_stats) * job.n);
         if (job.dres) std::memset(job.dres, 0, sizeof(lacx_digest) * job.n);
         for (uint32_t i = 0; i < job.n; ++i) {
             if (code[i] != LACX_OK) continue;
@@ -587,10 +609,13 @@ const char* check_digest_source(const lacx_digest_source& x, std::string& text) 
 // invalid sample's key).  Table layout: src [m] | unit_off [m + 1] | res [m] | bad [m].
 // grid != 0: block digests on a regular grid of `grid` frames instead (k_digest_blocks); the tables then go on with
 // | block_off [m + 1] | raw [blocks], and every item's rows are left in d->item_rows.
+// stats (with a grid): the audio statistics on that grid instead (k_stats_blocks) -- in place of the raw words the
+// accumulator rows | acc [blocks] (StatsAcc, 16-byte aligned, zeroed), the rows left in d->item_stats, the totals in sout.
 int digest_pcm_run(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, hipStream_t st, lacx_digest* out, float* device_ms,
-                   std::vector<int>& code, std::vector<std::string>& err, uint32_t grid = 0) {
+                   std::vector<int>& code, std::vector<std::string>& err, uint32_t grid = 0, bool stats = false, lacx_stats* sout = nullptr) {
     if (device_ms) *device_ms = 0.f;
     if (out) std::memset(out, 0, sizeof(lacx_digest) * n);
+    if (sout) std::memset(sout, 0, sizeof(lacx_stats) * n);
     code.assign(n, LACX_OK);
     err.assign(n, std::string());
     std::vector<uint32_t> went;  // the items that go to the device
@@ -605,13 +630,15 @@ int digest_pcm_run(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, h
     }
     int rc = lacx_device_count() <= 0 ? decode_fail(LACX_E_DEVICE, "no usable HIP device") : LACX_OK;
     const size_t m = went.size();
-    if (grid) d->item_rows.assign(n, {});
+    if (grid && !stats) d->item_rows.assign(n, {});
+    if (stats) d->item_stats.assign(n, {});
     unsigned long long nblocks = 0;
     for (size_t j = 0; grid && j < m; ++j) nblocks += (src[went[j]].frames + grid - 1u) / grid;
     if (rc == LACX_OK && nblocks >= (1ull << 31)) rc = decode_fail(LACX_E_DEVICE, "batch holds 2^31 blocks or more");
     if (rc == LACX_OK && m) {
         const size_t at_off = sizeof(DigestSource) * m, at_res = at_off + 8 * (m + 1), at_bad = at_res + sizeof(DigestWords) * m,
-                     at_blk = at_bad + 8 * m, at_raw = at_blk + (grid ? 8 * (m + 1) : 0), size = at_raw + 4 * (size_t)nblocks;
+                     at_blk = at_bad + 8 * m, at_raw = stats ? plan_detail::up16(at_blk + 8 * (m + 1)) : at_blk + (grid ? 8 * (m + 1) : 0),
+                     size = at_raw + (stats ? sizeof(StatsAcc) : 4) * (size_t)nblocks;
         int prev_device = -1;
         DevErr e = decoder_open(d, &prev_device);
         if (!e) e = buf_grow(d->tables, size, size / 8 + 256);
@@ -623,7 +650,7 @@ int digest_pcm_run(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, h
             if (grid) {
                 block_off[0] = 0;
                 for (size_t j = 0; j < m; ++j) block_off[j + 1] = block_off[j] + (src[went[j]].frames + grid - 1u) / grid;
-                std::memset(d->h_meta() + at_raw, 0, 4 * (size_t)nblocks);
+                std::memset(d->h_meta() + at_raw, 0, size - at_raw);
             }
             for (size_t j = 0; j < m; ++j) {
                 const lacx_digest_source& x = src[went[j]];
@@ -647,7 +674,12 @@ int digest_pcm_run(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, h
             ba.grid = grid;
             ba.block_off = reinterpret_cast<const unsigned long long*>(d->d_meta() + at_blk);
             ba.raw = reinterpret_cast<uint32_t*>(d->d_meta() + at_raw);
-            if (!e) e = chk(grid ? launch_digest_pcm_blocks(ba, st) : launch_digest_pcm(a, st), "digest launch");
+            StatsPcmArgs sa;
+            sa.pcm = a;
+            sa.grid = grid;
+            sa.block_off = ba.block_off;
+            sa.rows = reinterpret_cast<StatsAcc*>(d->d_meta() + at_raw);
+            if (!e) e = stats ? chk(launch_stats_pcm_blocks(sa, st), "stats launch") : chk(grid ? launch_digest_pcm_blocks(ba, st) : launch_digest_pcm(a, st), "digest launch");
             if (!e) e = chk(hipEventRecord(d->e1, st), "event record");
             if (!e) e = chk(hipMemcpyAsync(d->h_meta() + at_res, d->d_meta() + at_res, size - at_res, hipMemcpyDeviceToHost, st), "D2H digests");
             if (!e) e = chk(hipStreamSynchronize(st), "synchronize");
@@ -670,6 +702,14 @@ int digest_pcm_run(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, h
                     code[i] = LACX_E_INVALID;
                     continue;
                 }
+                if (stats) {
+                    const auto* block_off = reinterpret_cast<const unsigned long long*>(d->h_meta() + at_blk);
+                    const StatsAcc* acc = reinterpret_cast<const StatsAcc*>(d->h_meta() + at_raw) + block_off[j];
+                    std::vector<lacx_block_stats>& rows = d->item_stats[i];
+                    stats_rows_of_source(x.frames, grid, (uint32_t)(block_off[j + 1] - block_off[j]), (uint32_t)x.pcm.channels, acc, rows);
+                    if (sout) sout[i] = stats_combine(rows.data(), (uint32_t)rows.size(), (uint8_t)x.pcm.channels, x.bit_depth, x.sample_rate);
+                    continue;
+                }
                 if (grid) {
                     const auto* block_off = reinterpret_cast<const unsigned long long*>(d->h_meta() + at_blk);
                     const uint32_t* braw = reinterpret_cast<const uint32_t*>(d->h_meta() + at_raw) + block_off[j];
@@ -684,7 +724,9 @@ int digest_pcm_run(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, h
         }
     }
     if (rc != LACX_OK) {  // the whole call failed: no item was digested
-        if (grid) d->item_rows.assign(n, {});
+        if (grid && !stats) d->item_rows.assign(n, {});
+        if (stats) d->item_stats.assign(n, {});
+        if (sout) std::memset(sout, 0, sizeof(lacx_stats) * n);
         for (uint32_t i = 0; i < n; ++i) {
             if (code[i] != LACX_OK) continue;
             code[i] = rc;
@@ -832,6 +874,52 @@ int lacx_decoder_item_block_digests(const lacx_decoder* d, uint32_t i, const lac
     if (i >= d->item_rows.size()) return decode_fail(LACX_E_INVALID, "no such item in the last block digest call");
     *rows = d->item_rows[i].data();
     *count = (uint32_t)d->item_rows[i].size();
+    return LACX_OK;
+}
+
+// ---- audio statistics (lacx.h) ----
+int lacx_decoder_stats_batch_device(lacx_decoder* d, const lacx_span* lacs, uint32_t n, void* stream, int* item_rc, lacx_stats* out,
+                                    float* device_ms) {
+    if (!d) return decode_fail(LACX_E_INVALID, "null decoder");
+    if (!lacs || n == 0) return decode_fail(LACX_E_INVALID, "null argument or empty batch");
+    std::vector<BatchIn> in(n);
+    for (uint32_t i = 0; i < n; ++i) in[i] = BatchIn{lacs[i].data, lacs[i].size, nullptr, nullptr, 0};
+    DecodeJob job = salvage_job(DecodeForm::blocks, static_cast<hipStream_t>(stream), nullptr, nullptr, device_ms);
+    job.in = in.data();
+    job.n = n;
+    job.stats = true;
+    job.stres = out;
+    return run_batch(d, job, item_rc);
+}
+
+int lacx_decoder_stats_pcm_batch_device(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, uint32_t block_frames, void* stream,
+                                        int* item_rc, lacx_stats* out, float* device_ms) {
+    if (!d) return decode_fail(LACX_E_INVALID, "null decoder");
+    if (!src || n == 0) return decode_fail(LACX_E_INVALID, "null argument or empty batch");
+    if (block_frames != 0 && (block_frames < 256u || block_frames > (uint32_t)kMaxBlock)) return decode_fail(LACX_E_INVALID, "block_frames must be 0 or 256..16384");
+    std::vector<int> code;
+    std::vector<std::string> err;
+    const int rc = digest_pcm_run(d, src, n, static_cast<hipStream_t>(stream), nullptr, device_ms, code, err, block_frames ? block_frames : (uint32_t)kMaxBlock,
+                                  true, out);
+    return batch_outcome(d, rc, code, err, item_rc);
+}
+
+int lacx_decoder_item_block_stats(const lacx_decoder* d, uint32_t i, const lacx_block_stats** rows, uint32_t* count) {
+    if (rows) *rows = nullptr;
+    if (count) *count = 0;
+    if (!d || !rows || !count) return decode_fail(LACX_E_INVALID, "null argument");
+    if (i >= d->item_stats.size()) return decode_fail(LACX_E_INVALID, "no such item in the last stats call");
+    *rows = d->item_stats[i].data();
+    *count = (uint32_t)d->item_stats[i].size();
+    return LACX_OK;
+}
+
+int lacx_stats_combine(const lacx_block_stats* rows, uint32_t count, uint8_t channels, uint8_t bit_depth, uint32_t sample_rate, lacx_stats* out) {
+    if (out) std::memset(out, 0, sizeof(*out));
+    if (!out || (!rows && count)) return decode_fail(LACX_E_INVALID, "null argument");
+    if (channels != 1 && channels != 2) return decode_fail(LACX_E_INVALID, "unsupported channel count");
+    if (bit_depth != 16 && bit_depth != 24) return decode_fail(LACX_E_INVALID, "unsupported bit depth: " + std::to_string((int)bit_depth));
+    *out = stats_combine(rows, count, channels, bit_depth, sample_rate);
     return LACX_OK;
 }
 

@@ -60,8 +60,12 @@ struct BatchIn {
 // (DecodePlan::judged) k_digest_judge compares them with the expected words and stores status 11 in front of the salvage
 // pass.  blocks: the form of such a job that outputs nothing -- the decoder's own PCM buffers as verify and digest have
 // them, and no salvage pass.
+// The blocks form is also that of a stats job (DecodePlan::stats, lacx_decoder_stats_batch_device): the same salvage job
+// with k_stats_blocks (stats_core.h) in place of k_digest_blocks -- no manifests, no judge, no raw words; one accumulator
+// row of kStatsRowBytes per global block instead, zeroed with the tables.
 enum class DecodeForm { wav, device, host, verify, digest, blocks };
 constexpr int kWholeStreams = -1;
+constexpr size_t kStatsRowBytes = 96;  // sizeof(StatsAcc), stats_core.h (k_stats.hip asserts it)
 
 // One item that goes to the device (j counts these; the items that failed their checks are not among them).
 struct PlanItem {
@@ -84,10 +88,12 @@ struct PlanItem {
 // The tables the kernels read, one upload: items | byte_off [T + 1] | frame_off [T + 1] | unit_off [m + 1] | blk_item [T]
 // | lane_blk | v2_items, then for a window job | win [m], for the verify form | ver [m] | res [m], for the digest form
 // | res [m] at `win`, for a salvage job | present [m] (uint32) at `win` (byte offsets); with block digests behind that
-// | judged [m] (uint32) | raw [T] (uint32, 16-byte aligned) and for a judged job | expect [T] (uint32)
+// | judged [m] (uint32) | raw [T] (uint32, 16-byte aligned) and for a judged job | expect [T] (uint32); a stats job
+// behind present [m] | stats [T] (kStatsRowBytes each, 16-byte aligned)
 struct TableLayout {
     size_t items, byte_off, frame_off, unit_off, blk_item, lane_blk, v2_items, win, res, size;
     size_t judged = 0, raw = 0, expect = 0;  // block digests only
+    size_t stats = 0;                        // stats job only
 };
 
 struct DecodePlan {
@@ -96,9 +102,10 @@ struct DecodePlan {
     bool salvage = false;  // wav and device forms of whole streams only, and the blocks form
     bool blocks = false;   // salvage job with block digests; judged: one item at least has a manifest
     bool judged = false;
+    bool stats = false;    // salvage job in the blocks form with the statistics' accumulator rows (no block digests)
     bool window() const { return sample_type != kWholeStreams; }
     bool own_pcm() const { return form != DecodeForm::device || window(); }  // into the decoder's PCM buffers
-    bool post_units() const { return window() || form == DecodeForm::verify || form == DecodeForm::wav || form == DecodeForm::digest || blocks; }
+    bool post_units() const { return window() || form == DecodeForm::verify || form == DecodeForm::wav || form == DecodeForm::digest || blocks || stats; }
     bool host_window() const { return form == DecodeForm::host && window(); }
     std::vector<PlanItem> items;
     // k_decode's lanes: lane g decodes global block lane_blk[g] (~0u: idle); version-3 blocks only, an item's in
@@ -112,9 +119,10 @@ struct DecodePlan {
     TableLayout at{};
     // What the run must provide (0: that buffer is not used).  payload: bytes, with kDecodeTailPad behind the last block
     // (and behind the host source, where there is one); blocks: status and flag entries; pcm_frames: samples of each
-    // channel's buffer; image, stage (the pinned payload stage of a window job), tables: bytes.
+    // channel's buffer; image, stage (the pinned payload stage of a window job), tables: bytes.  stats_rows: the
+    // accumulator rows of a stats job, which lie inside the tables at TableLayout::stats.
     struct {
-        uint64_t payload, blocks, pcm_frames, image, stage, tables;
+        uint64_t payload, blocks, pcm_frames, image, stage, tables, stats_rows;
     } need{};
 };
 
@@ -184,19 +192,22 @@ inline int check_manifest(const BatchIn& x, const lacx_stream_info& f, std::vect
 // salvage: a salvage job (DecodeForm above): an item's blocks and frames are still the whole table's, its payload the
 // bytes of its present blocks.
 inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, int sample_type, bool pad_waves, DecodePlan& plan,
-                               std::vector<int>& code, std::vector<std::string>& err, bool salvage = false, bool blocks = false) {
+                               std::vector<int>& code, std::vector<std::string>& err, bool salvage = false, bool blocks = false,
+                               bool stats = false) {
     using namespace plan_detail;
     plan = DecodePlan{};
     plan.form = form;
     plan.sample_type = sample_type;
     plan.salvage = salvage;
     plan.blocks = blocks;
+    plan.stats = stats;
     const bool window = plan.window(), own_pcm = plan.own_pcm(), wav = form == DecodeForm::wav, verify = form == DecodeForm::verify,
                digest = form == DecodeForm::digest, quiet = form == DecodeForm::blocks;
     code.assign(n, LACX_OK);
     err.assign(n, std::string());
     if (salvage && (sample_type != kWholeStreams || (form != DecodeForm::wav && form != DecodeForm::device && !quiet))) return "salvage is a whole-stream WAV or device job";
-    if ((quiet && !blocks) || (blocks && !salvage)) return "block digests belong to a salvage job";
+    if (stats && (!quiet || blocks || !salvage)) return "statistics are a salvage job in the blocks form without block digests";
+    if ((quiet && !blocks && !stats) || (blocks && !salvage)) return "block digests belong to a salvage job";
     plan.items.reserve(n);
     uint32_t v3_blocks = 0;
     for (uint32_t i = 0; i < n; ++i) {
@@ -310,13 +321,15 @@ inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, i
         at.raw = at.res = up16(at.judged + 4 * m);
         at.expect = at.raw + 4 * T;
     }
-    at.size = blocks ? at.expect + (plan.judged ? 4 * T : 0) : salvage ? at.win + 4 * m : verify ? at.res + sizeof(VerifyWords) * m : digest ? at.res + sizeof(DigestWords) * m : window ? at.win + sizeof(WindowOut) * m : end;
+    if (stats) at.stats = up16(at.win + 4 * m);
+    at.size = stats ? at.stats + kStatsRowBytes * T : blocks ? at.expect + (plan.judged ? 4 * T : 0) : salvage ? at.win + 4 * m : verify ? at.res + sizeof(VerifyWords) * m : digest ? at.res + sizeof(DigestWords) * m : window ? at.win + sizeof(WindowOut) * m : end;
     plan.need.payload = (plan.host_src ? plan.src_at + plan.host_src_bytes : plan.total_pay) + kDecodeTailPad;
     plan.need.blocks = T;
     plan.need.pcm_frames = own_pcm ? plan.pcm_total : 0;
     plan.need.image = wav || plan.host_window() ? up16(plan.image_total) : 0;  // k_wav_pack writes whole dwords, and only inside the image
     plan.need.stage = window ? plan.total_pay : 0;
     plan.need.tables = at.size;
+    plan.need.stats_rows = stats ? T : 0;
     return nullptr;
 }
 
@@ -399,6 +412,7 @@ inline void plan_fill_tables(const DecodePlan& plan, const BatchIn* in, const Pl
         }
         if (plan.form == DecodeForm::digest) reinterpret_cast<DigestWords*>(h + at.res)[j] = DigestWords{0, 0};
         if (plan.salvage) reinterpret_cast<uint32_t*>(h + at.win)[j] = p.present_blocks;
+        if (plan.stats) std::memset(h + at.stats + kStatsRowBytes * (size_t)y.block0, 0, kStatsRowBytes * (size_t)y.blocks);
         if (plan.blocks) {
             reinterpret_cast<uint32_t*>(h + at.judged)[j] = p.judged ? 1u : 0u;
             std::memset(h + at.raw + 4 * (size_t)y.block0, 0, 4 * (size_t)y.blocks);
@@ -446,7 +460,16 @@ inline DecodeArgs plan_args(const DecodePlan& plan, const uint8_t* tables, const
         a.no_output = plan.form == DecodeForm::blocks;
     }
     if (plan.form == DecodeForm::digest) a.digest = reinterpret_cast<DigestWords*>(const_cast<uint8_t*>(tables) + at.res);
+    if (plan.stats) a.no_output = true;  // launch_decode ends with k_ms_inverse; k_stats_blocks follows it (plan_stats_args)
     return a;
+}
+
+// A stats job's arguments for k_stats_blocks: the decode's own and the accumulator rows inside the tables.
+inline StatsArgs plan_stats_args(const DecodePlan& plan, const DecodeArgs& a, const uint8_t* tables) {
+    StatsArgs s;
+    s.dec = a;
+    s.rows = reinterpret_cast<StatsAcc*>(const_cast<uint8_t*>(tables) + plan.at.stats);
+    return s;
 }
 
 }  // namespace lacx

@@ -35,6 +35,7 @@ struct lacx_decoder {
     std::vector<std::string> item_err;  // the last batch call's message per item ("" = decoded)
     std::vector<std::vector<lacx_block_fault>> item_faults;  // the last salvage call's lost blocks per item
     std::vector<std::vector<lacx_block_digest>> item_rows;   // the last block digest call's rows per item
+    std::vector<std::vector<lacx_block_stats>> item_stats;   // the last stats call's rows per item
     std::vector<std::vector<uint32_t>> item_bad;             // the last recovery scan / repair call's damaged slices per item
     std::string err;
 };

@@ -203,4 +203,18 @@ struct BlockPcmArgs {
     const unsigned long long* block_off = nullptr; // [nitems + 1] prefix sums of ceil(frames / grid)
     uint32_t* raw = nullptr;                       // [block_off[nitems]], zero on entry
 };
+// Audio statistics (k_stats_blocks, stats_core.h): one accumulator row per global block, all-zero bytes on entry.
+struct StatsAcc;
+// ... of a stats job's items behind k_ms_inverse: the blocks form of a salvage job without block digests
+struct StatsArgs {
+    DecodeArgs dec;
+    StatsAcc* rows = nullptr;                      // [dec.total_blocks]
+};
+// ... of device-resident source PCM on a regular grid
+struct StatsPcmArgs {
+    DigestPcmArgs pcm;                             // (res is not used)
+    uint32_t grid = 0;                             // frames per block, 256 .. 16384
+    const unsigned long long* block_off = nullptr; // [nitems + 1] prefix sums of ceil(frames / grid)
+    StatsAcc* rows = nullptr;                      // [block_off[nitems]]
+};
 }  // namespace lacx

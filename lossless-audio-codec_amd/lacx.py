@@ -11,6 +11,7 @@ to the library by raw pointer (no torch types cross the ABI).
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import subprocess
 
@@ -119,6 +120,7 @@ EXPORTS = (
     "lacx_decoder_salvage_wav_batch_view_checked", "lacx_decoder_salvage_batch_device_checked",
     "lacx_recovery_build_batch_view", "lacx_recovery_build", "lacx_recovery_parse", "lacx_recovery_scan_batch",
     "lacx_recovery_repair_batch_view", "lacx_recovery_repair", "lacx_decoder_item_bad_slices",
+    "lacx_decoder_stats_batch_device", "lacx_decoder_stats_pcm_batch_device", "lacx_decoder_item_block_stats", "lacx_stats_combine",
 )
 
 
@@ -225,6 +227,12 @@ def lib():
         L.lacx_recovery_repair.argtypes = [C.c_void_p, u8p, C.c_uint64, u8p, C.c_uint64, C.c_uint32, C.POINTER(u8p), C.POINTER(C.c_uint64),
                                            C.POINTER(RepairResult), C.POINTER(C.c_float)]
         L.lacx_decoder_item_bad_slices.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint32)]
+        L.lacx_decoder_stats_batch_device.argtypes = [C.c_void_p, C.POINTER(Span), C.c_uint32, C.c_void_p, C.POINTER(C.c_int),
+                                                      C.POINTER(Stats), C.POINTER(C.c_float)]
+        L.lacx_decoder_stats_pcm_batch_device.argtypes = [C.c_void_p, C.POINTER(DigestSource), C.c_uint32, C.c_uint32, C.c_void_p,
+                                                          C.POINTER(C.c_int), C.POINTER(Stats), C.POINTER(C.c_float)]
+        L.lacx_decoder_item_block_stats.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.POINTER(BlockStats)), C.POINTER(C.c_uint32)]
+        L.lacx_stats_combine.argtypes = [C.POINTER(BlockStats), C.c_uint32, C.c_uint8, C.c_uint8, C.c_uint32, C.POINTER(Stats)]
         L.lacx_block_fault_text.restype = C.c_char_p
         L.lacx_block_fault_text.argtypes = [C.c_uint32]
         L.lacx_decoder_item_error.restype = C.c_char_p
@@ -251,7 +259,8 @@ def abi_structs() -> dict:
             "verify_result": VerifyResult, "digest": Digest, "digest_source": DigestSource,
             "block_fault": BlockFault, "salvage_result": SalvageResult, "block_digest": BlockDigest,
             "manifest_info": ManifestInfo, "recovery_params": RecoveryParams, "recovery_info": RecoveryInfo,
-            "repair_result": RepairResult}
+            "repair_result": RepairResult, "channel_stats": ChannelStats, "block_stats": BlockStats,
+            "channel_totals": ChannelTotals, "stats": Stats}
 
 
 def device_count() -> int:
@@ -827,6 +836,112 @@ class ManifestInfo(C.Structure):
                 ("channels", C.c_uint8), ("bit_depth", C.c_uint8), ("reserved", C.c_uint8 * 2)]
 
 
+# ---- audio statistics: exact integers from the device; the float conveniences are DERIVED here and documented as such ----
+def _wasted_bits(or_bits: int, depth: int) -> int:
+    """Trailing zero bits of an OR of samples; the whole depth where it is 0 (silence uses no bit)."""
+    return depth if or_bits == 0 else (or_bits & -or_bits).bit_length() - 1
+
+
+def _dbfs(ratio: float) -> float:
+    return 20.0 * math.log10(ratio) if ratio > 0 else float("-inf")
+
+
+class ChannelStats(C.Structure):
+    """One channel of one block: min, max, OR of the samples' low bits, the counts of full-scale and of zero samples, the
+    sum and the sum of squares -- all exact."""
+    _fields_ = [("min", C.c_int32), ("max", C.c_int32), ("or_bits", C.c_uint32), ("full_scale", C.c_uint32), ("zeros", C.c_uint32),
+                ("reserved", C.c_uint32), ("sum", C.c_int64), ("sum_sq", C.c_uint64)]
+
+    @property
+    def peak(self) -> int:
+        return max(abs(self.min), abs(self.max))
+
+
+class BlockStats(C.Structure):
+    """One block of a stream or of source PCM.  code != 0: the block is lost (1..10) and every other field but frames is
+    0.  lead_zero_frames / trail_zero_frames: leading / trailing frames that are 0 in every channel (both == frames for a
+    silent block); differing: frames with left != right."""
+    _fields_ = [("frames", C.c_uint32), ("code", C.c_uint32), ("lead_zero_frames", C.c_uint32), ("trail_zero_frames", C.c_uint32),
+                ("differing", C.c_uint32), ("reserved", C.c_uint32), ("ch", ChannelStats * 2)]
+
+    @property
+    def silent(self) -> bool:
+        return self.code == 0 and self.lead_zero_frames == self.frames
+
+
+class ChannelTotals(C.Structure):
+    """One channel of an item: as ChannelStats, the sums 128 bits wide (`sum` and `sum_sq` give them as Python ints)."""
+    _fields_ = [("min", C.c_int32), ("max", C.c_int32), ("or_bits", C.c_uint32), ("reserved", C.c_uint32), ("full_scale", C.c_uint64),
+                ("zeros", C.c_uint64), ("sum_lo", C.c_uint64), ("sum_hi", C.c_int64), ("sum_sq_lo", C.c_uint64), ("sum_sq_hi", C.c_uint64)]
+
+    @property
+    def sum(self) -> int:
+        return (self.sum_hi << 64) + self.sum_lo
+
+    @property
+    def sum_sq(self) -> int:
+        return (self.sum_sq_hi << 64) + self.sum_sq_lo
+
+    @property
+    def peak(self) -> int:
+        return max(abs(self.min), abs(self.max))
+
+
+class Stats(C.Structure):
+    """The totals of an item over its decoded blocks (lacx_stats).  Exact: every field, `peak`, `wasted_bits`, `dual_mono`
+    and the channels' `sum` / `sum_sq`.  Derived floats, not part of any equality: `peak_dbfs`, `rms_dbfs`, `dc`."""
+    _fields_ = [("frames", C.c_uint64), ("sample_rate", C.c_uint32), ("channels", C.c_uint8), ("bit_depth", C.c_uint8),
+                ("reserved", C.c_uint8 * 2), ("blocks", C.c_uint32), ("lost_blocks", C.c_uint32), ("lost_frames", C.c_uint64),
+                ("silent_blocks", C.c_uint32), ("reserved2", C.c_uint32), ("lead_zero_frames", C.c_uint64),
+                ("trail_zero_frames", C.c_uint64), ("differing", C.c_uint64), ("ch", ChannelTotals * 2)]
+
+    @property
+    def peak(self) -> int:
+        return max(self.ch[c].peak for c in range(self.channels)) if self.channels else 0
+
+    @property
+    def wasted_bits(self) -> int:
+        bits = 0
+        for c in range(self.channels):
+            bits |= self.ch[c].or_bits
+        return _wasted_bits(bits, self.bit_depth)
+
+    @property
+    def dual_mono(self) -> bool:
+        return self.channels == 2 and self.differing == 0
+
+    @property
+    def decoded_frames(self) -> int:
+        return self.frames - self.lost_frames
+
+    @property
+    def peak_dbfs(self) -> float:
+        """Derived: 20 log10(peak / 2^(b-1)); -inf for silence."""
+        return _dbfs(self.peak / float(1 << (self.bit_depth - 1))) if self.bit_depth else float("-inf")
+
+    def rms_dbfs(self, channel: int = 0) -> float:
+        """Derived: the channel's RMS over the decoded frames against full scale, in dB; -inf for silence."""
+        n = self.decoded_frames
+        if n == 0 or not self.bit_depth:
+            return float("-inf")
+        return _dbfs(math.sqrt(self.ch[channel].sum_sq / n) / float(1 << (self.bit_depth - 1)))
+
+    def dc(self, channel: int = 0) -> float:
+        """Derived: the channel's mean over the decoded frames / 2^(b-1)."""
+        n = self.decoded_frames
+        return self.ch[channel].sum / n / float(1 << (self.bit_depth - 1)) if n and self.bit_depth else 0.0
+
+
+def stats_combine(rows, channels: int, bit_depth: int, sample_rate: int = 0) -> Stats:
+    """The totals of BlockStats rows (all of an item's, or a sub-range: a window's blocks), as stats_batch makes an item's.
+    ValueError for a channel count or depth the library does not know.  Host only."""
+    arr = (BlockStats * max(1, len(rows)))(*rows)
+    out = Stats()
+    if lib().lacx_stats_combine(arr, C.c_uint32(len(rows)), C.c_uint8(channels), C.c_uint8(bit_depth), C.c_uint32(sample_rate), C.byref(out)) != OK:
+        raise ValueError(lib().lacx_decode_last_error().decode(errors="replace"))
+    return out
+
+
 REPAIR_TRUNCATED, REPAIR_TRAILING, REPAIR_SIDECAR_TRUNCATED, REPAIR_UNREPAIRED = 1, 2, 4, 8  # LACX_REPAIR_* (result flags)
 REPAIR_BEST_EFFORT = 1                                                                       # LACX_REPAIR_BEST_EFFORT (call flag)
 
@@ -1397,6 +1512,61 @@ class Decoder:
             raise RuntimeError(lib().lacx_decode_last_error().decode(errors="replace"))
         errors = {i: lib().lacx_decoder_item_error(self._h, i).decode(errors="replace") for i in range(n) if rcs[i] != OK}
         return self._raise_batch(rc, errors, [None if i in errors else (_copy_struct(out[i]), self._rows(i)) for i in range(n)])
+
+    # ---- audio statistics: peaks, energy, silence and bit use ----
+    def _stat_rows(self, i) -> list:
+        ptr, count = C.POINTER(BlockStats)(), C.c_uint32()
+        if lib().lacx_decoder_item_block_stats(self._h, C.c_uint32(i), C.byref(ptr), C.byref(count)) != OK:
+            return []
+        return [_copy_struct(ptr[k]) for k in range(count.value)]  # copies: the rows die with the decoder's next call
+
+    def stats_batch(self, lacs, stream: int = 0) -> list:
+        """Many streams decoded and measured block by block as one device job, lenient like salvage: per item
+        (Stats, [BlockStats]), None where the container is refused (those raise BatchDecodeError once the others are
+        done).  A lost block's row carries its fault code and is otherwise 0; the totals cover the decoded blocks.  Only
+        about 100 bytes per block come back; kernel milliseconds in `last_ms`."""
+        bufs = [np.frombuffer(x, dtype=np.uint8) for x in lacs]
+        n = len(bufs)
+        spans = (Span * max(1, n))(*[Span(b.ctypes.data_as(C.POINTER(C.c_uint8)), b.size) for b in bufs])
+        out = (Stats * max(1, n))()
+        rc, errors = self._batch(n, lambda rcs, ms: lib().lacx_decoder_stats_batch_device(
+            self._h, spans, C.c_uint32(n), C.c_void_p(stream), rcs, out, ms))
+        return self._raise_batch(rc, errors, [None if i in errors else (_copy_struct(out[i]), self._stat_rows(i)) for i in range(n)])
+
+    def stats(self, lac) -> Stats:
+        """The totals of stats_batch of one stream; RuntimeError with the parser's message where the container is refused."""
+        try:
+            return self.stats_batch([lac])[0][0]
+        except BatchDecodeError as e:
+            raise RuntimeError(e.errors[0]) from None
+
+    def stats_pcm_batch(self, sources, block_frames: int = 16384, stream: int = 0) -> list:
+        """Device-resident PCM measured where it lies on a regular grid of block_frames frames (256..16384): per item
+        (Stats, [BlockStats]) -- with the encoder's grid of 16384, what stats_batch gives for the .lac made from it.
+        Sources as digest_pcm_blocks_batch takes them: (pcm, sample_rate, bit_depth) with pcm a device tensor or a tuple
+        (data0_ptr, data1_ptr or None, layout, channels, frames)."""
+        n = len(sources)
+        items = (DigestSource * max(1, n))()
+        for it, (pcm, rate, depth) in zip(items, sources):
+            if isinstance(pcm, (tuple, list)):
+                d0, d1, layout, channels, frames = pcm
+                it.pcm = Pcm(d0, d1, layout, channels)
+            else:
+                it.pcm, frames = pcm_of(pcm, depth)
+            it.frames, it.sample_rate, it.bit_depth = frames, rate, depth
+        out = (Stats * max(1, n))()
+        if self._h is None:
+            raise RuntimeError("decoder is closed")
+        rcs, ms = (C.c_int * max(1, n))(), C.c_float()
+        rc = lib().lacx_decoder_stats_pcm_batch_device(self._h, items, C.c_uint32(n), C.c_uint32(block_frames), C.c_void_p(stream),
+                                                       rcs, out, C.byref(ms))
+        self.last_ms = float(ms.value)
+        if rc == E_INVALID and all(rcs[i] == OK for i in range(n)):  # the call's own arguments
+            raise ValueError(lib().lacx_decode_last_error().decode(errors="replace"))
+        if rc == E_DEVICE:
+            raise RuntimeError(lib().lacx_decode_last_error().decode(errors="replace"))
+        errors = {i: lib().lacx_decoder_item_error(self._h, i).decode(errors="replace") for i in range(n) if rcs[i] != OK}
+        return self._raise_batch(rc, errors, [None if i in errors else (_copy_struct(out[i]), self._stat_rows(i)) for i in range(n)])
 
     def check_batch(self, lacs, manifests, stream: int = 0) -> list:
         """Is each stream intact -- does every block decode to what its manifest says?  Per item (SalvageResult,

@@ -19,6 +19,8 @@
 // digest (no counterpart in the reference's tool; `flac -t` without the source, and the STREAMINFO MD5's role): the CRC-32
 // of what every .lac decodes to and of every WAV's data chunk, made on the device (lacx_decoder_digest_batch_device /
 // lacx_decoder_digest_pcm_batch_device): a .lac and the WAV it was made from print the same fields.
+// stats (no counterpart in the reference's tool; `sox stat` without the floats): the audio statistics of the same two
+// kinds of file, made on the device (lacx_decoder_stats_batch_device / lacx_decoder_stats_pcm_batch_device).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -55,6 +57,8 @@ void usage() {
                  "  lacx_cli repair input.lac input.lacr output.lac [--best-effort]\n"
                  "      exit 0 intact or fully repaired, 1 not fully repaired (output.lac only with --best-effort), 2 refused\n"
                  "  lacx_cli digest FILE...   (.lac and .wav files, told apart by content)\n"
+                 "  lacx_cli stats FILE... [--blocks]   (.lac and .wav files: peaks, energy, silence and bit use as integers, one line\n"
+                 "      per file; --blocks: one further line per block; exit 0 when every file gave statistics, else 1)\n"
                  "  lacx_cli selftest\n";
 }
 
@@ -565,6 +569,156 @@ int digest_command(int argc, char** argv) {
     return status;
 }
 
+// a 128-bit value as decimal text (hi: the upper word; negative: two's complement over both words)
+std::string dec128(uint64_t lo, uint64_t hi, bool is_signed) {
+    const bool neg = is_signed && (hi >> 63) != 0;
+    if (neg) {
+        lo = ~lo + 1u;
+        hi = ~hi + (lo == 0 ? 1u : 0u);
+    }
+    std::string s;
+    do {  // long division by 10, 32 bits at a time
+        uint32_t w[4] = {(uint32_t)(hi >> 32), (uint32_t)hi, (uint32_t)(lo >> 32), (uint32_t)lo};
+        uint64_t rem = 0;
+        for (uint32_t& x : w) {
+            const uint64_t cur = (rem << 32) | x;
+            x = (uint32_t)(cur / 10u);
+            rem = cur % 10u;
+        }
+        hi = ((uint64_t)w[0] << 32) | w[1], lo = ((uint64_t)w[2] << 32) | w[3];
+        s.insert(s.begin(), (char)('0' + rem));
+    } while (hi || lo);
+    return neg ? "-" + s : s;
+}
+
+// lacx_cli stats FILE... [--blocks]: the audio statistics of what every .lac decodes to and of every WAV's data chunk, made on
+// the device (lacx_decoder_stats_batch_device / lacx_decoder_stats_pcm_batch_device on the default grid of 16384 frames,
+// the encoder's, so that a .lac and the WAV it was made from print the same fields).  One line per file that gave
+// statistics, integers only, in argument order; with --blocks one further line per block.  The streams are one device
+// job, the WAV files' data chunks, uploaded as they are, another.  Lenient like salvage: a damaged stream prints its line
+// with lost_blocks counted.  Exit 0 when every file gave statistics; otherwise the failed files' messages on stderr and
+// exit 1.
+int stats_command(int argc, char** argv) {
+    bool per_block = false;
+    std::vector<const char*> paths;
+    for (int i = 2; i < argc; ++i) {
+        if (std::strcmp(argv[i], "--blocks") == 0) per_block = true;
+        else paths.push_back(argv[i]);
+    }
+    const int n = (int)paths.size();
+    if (n == 0) {
+        usage();
+        return 1;
+    }
+    std::vector<std::vector<uint8_t>> data(n);
+    std::vector<std::string> error(n);
+    std::vector<lacx_stats> stats(n, lacx_stats{});
+    std::vector<std::vector<lacx_block_stats>> rows(n);
+    std::vector<int> lacs, wavs;  // indices of the files of each kind that go to the device
+    std::vector<lacx_wav_info> winfo(n, lacx_wav_info{});
+    for (int i = 0; i < n; ++i) {
+        if (!load_file(paths[i], data[i])) {
+            error[i] = "Failed to read file";
+        } else if (data[i].size() >= 4 && std::memcmp(data[i].data(), "RIFF", 4) == 0) {
+            if (lacx_wav_parse(data[i].data(), data[i].size(), &winfo[i]) != LACX_OK) error[i] = "Failed to read WAV";
+            else wavs.push_back(i);
+        } else {
+            lacs.push_back(i);
+        }
+    }
+    lacx_decoder* dec = nullptr;
+    if (lacx_decoder_create(-1, &dec) != LACX_OK) {
+        std::cerr << "Error: lacx_decoder_create failed\n";
+        return 1;
+    }
+    // the outcome of a batch call for its files: the items' totals, rows and messages
+    auto collect = [&](const std::vector<int>& which, int rc, const std::vector<int>& item_rc, const std::vector<lacx_stats>& out) {
+        for (size_t k = 0; k < which.size(); ++k) {
+            const lacx_block_stats* r = nullptr;
+            uint32_t count = 0;
+            if (item_rc[k] == LACX_OK && lacx_decoder_item_block_stats(dec, (uint32_t)k, &r, &count) == LACX_OK) {
+                stats[which[k]] = out[k];
+                rows[which[k]].assign(r, r + count);
+            } else {
+                error[which[k]] = rc == LACX_E_DEVICE || item_rc[k] == LACX_OK ? lacx_decode_last_error() : lacx_decoder_item_error(dec, (uint32_t)k);
+            }
+        }
+    };
+    if (!lacs.empty()) {
+        std::vector<lacx_span> spans;
+        for (int i : lacs) spans.push_back(lacx_span{data[i].data(), data[i].size()});
+        std::vector<int> item_rc(lacs.size(), LACX_OK);
+        std::vector<lacx_stats> out(lacs.size());
+        const int rc = lacx_decoder_stats_batch_device(dec, spans.data(), (uint32_t)spans.size(), nullptr, item_rc.data(), out.data(), nullptr);
+        collect(lacs, rc, item_rc, out);
+    }
+    if (!wavs.empty()) {
+        std::vector<lacx_digest_source> src;
+        std::vector<void*> dev;
+        std::vector<int> sent;
+        for (int i : wavs) {
+            const lacx_wav_info& w = winfo[i];
+            const uint64_t bytes = w.frames * w.channels * (uint64_t)(w.bit_depth / 8);
+            void* p = nullptr;
+            if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess ||
+                hipMemcpy(p, data[i].data() + w.data_offset, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+                error[i] = "Failed to upload WAV data to the device";
+                if (p) (void)hipFree(p);
+                continue;
+            }
+            lacx_digest_source s{};
+            s.pcm = lacx_pcm{p, nullptr, w.bit_depth == 16 ? LACX_PCM_INTERLEAVED_I16 : LACX_PCM_INTERLEAVED_I24, w.channels};
+            s.frames = w.frames;
+            s.sample_rate = w.sample_rate;
+            s.bit_depth = (uint8_t)w.bit_depth;
+            src.push_back(s), dev.push_back(p), sent.push_back(i);
+        }
+        if (!src.empty()) {
+            std::vector<int> item_rc(src.size(), LACX_OK);
+            std::vector<lacx_stats> out(src.size());
+            const int rc = lacx_decoder_stats_pcm_batch_device(dec, src.data(), (uint32_t)src.size(), 0, nullptr, item_rc.data(), out.data(), nullptr);
+            collect(sent, rc, item_rc, out);
+        }
+        for (void* p : dev) (void)hipFree(p);
+    }
+    lacx_decoder_destroy(dec);
+    int status = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!error[i].empty()) {
+            std::cerr << "Stats failed: " << paths[i] << ": " << error[i] << "\n";
+            status = 1;
+            continue;
+        }
+        const lacx_stats& t = stats[i];
+        uint32_t all = 0;
+        for (uint32_t c = 0; c < t.channels; ++c) all |= t.ch[c].or_bits;
+        uint32_t wasted = t.bit_depth;  // trailing zero bits of the OR over all channels; the whole depth for silence
+        if (all) for (wasted = 0; !((all >> wasted) & 1u); ++wasted) {}
+        std::cout << "frames=" << t.frames << " channels=" << (unsigned)t.channels << " bits=" << (unsigned)t.bit_depth << " rate=" << t.sample_rate
+                  << " blocks=" << t.blocks << " lost_blocks=" << t.lost_blocks << " lead_zero=" << t.lead_zero_frames
+                  << " trail_zero=" << t.trail_zero_frames << " silent_blocks=" << t.silent_blocks << " differing=" << t.differing
+                  << " wasted_bits=" << wasted;
+        for (uint32_t c = 0; c < t.channels; ++c) {
+            const lacx_channel_totals& s = t.ch[c];
+            std::cout << " ch" << c << ": min=" << s.min << " max=" << s.max << " full_scale=" << s.full_scale << " zeros=" << s.zeros
+                      << " sum=" << dec128(s.sum_lo, (uint64_t)s.sum_hi, true) << " sum_sq=" << dec128(s.sum_sq_lo, s.sum_sq_hi, false);
+        }
+        std::cout << " " << paths[i] << "\n";
+        for (size_t b = 0; per_block && b < rows[i].size(); ++b) {
+            const lacx_block_stats& r = rows[i][b];
+            std::cout << "  block=" << b << " frames=" << r.frames << " code=" << r.code << " lead_zero=" << r.lead_zero_frames
+                      << " trail_zero=" << r.trail_zero_frames << " differing=" << r.differing;
+            for (uint32_t c = 0; c < t.channels; ++c) {
+                const lacx_channel_stats& s = r.ch[c];
+                std::cout << " ch" << c << ": min=" << s.min << " max=" << s.max << " or_bits=" << s.or_bits << " full_scale=" << s.full_scale
+                          << " zeros=" << s.zeros << " sum=" << (long long)s.sum << " sum_sq=" << (unsigned long long)s.sum_sq;
+            }
+            std::cout << "\n";
+        }
+    }
+    return status;
+}
+
 // The canonical WAV image of planar PCM (the source form lacx_decoder_verify_wav takes).
 std::vector<uint8_t> wav_image(const std::vector<int32_t>& left, const std::vector<int32_t>* right, uint32_t rate, uint32_t bits) {
     const uint32_t ch = right ? 2u : 1u, bps = bits / 8u, align = ch * bps;
@@ -691,6 +845,7 @@ int main(int argc, char** argv) {
     if (mode == "selftest" && argc == 2) return selftest_command();
     if (mode == "verify" && argc == 4) return verify_command(argv);
     if (mode == "digest" && argc >= 3) return digest_command(argc, argv);
+    if (mode == "stats" && argc >= 3) return stats_command(argc, argv);
     if (mode == "manifest" && argc == 4) return manifest_command(argv);
     if (mode == "check" && argc == 4) return check_command(argv);
     if (mode == "protect" && argc >= 4) return protect_command(argc, argv);
