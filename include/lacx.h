@@ -52,6 +52,9 @@
  *   lacx_decoder_item_block_stats,
  *   lacx_stats_combine      <- what the audio is, not whether it decodes: per block and per stream peaks, energy, silence,
  *                             full-scale hits, channel equality and bit use, exact integers made on the device
+ *   lacx_decoder_inspect_batch_device, lacx_decoder_item_block_info, lacx_decoder_item_partitions,
+ *   lacx_inspect_combine, lacx_decoder_inspect_guard <- how a stream was coded and where its bits go: per block and per stream predictors, partition
+ *                             orders, residual modes, bit and sample classes, read by a parse-only walk on the device
  *   lacx_recovery_build, lacx_recovery_build_batch_view, lacx_recovery_parse,
  *   lacx_recovery_scan_batch, lacx_recovery_repair, lacx_recovery_repair_batch_view,
  *   lacx_decoder_item_bad_slices <- bringing lost bytes back: a parity sidecar ("LACR", Reed-Solomon over GF(2^8)) beside
@@ -774,6 +777,94 @@ int lacx_decoder_stats_pcm_batch_device(lacx_decoder* dec, const lacx_digest_sou
 int lacx_decoder_item_block_stats(const lacx_decoder* dec, uint32_t i, const lacx_block_stats** rows, uint32_t* count);
 int lacx_stats_combine(const lacx_block_stats* rows, uint32_t count, uint8_t channels, uint8_t bit_depth, uint32_t sample_rate,
                        lacx_stats* out);
+
+/* Stream inspection: how a stream was coded and where its bits go.  Decode and salvage say whether a stream decodes,
+ * digest and manifest to what bytes, recovery whether it can be repaired, stats what the audio is; these entry points
+ * say which predictor, order and partition order every channel block got, which residual mode every partition, how the
+ * bits divide into header, unary quotients, remainders, tags, escapes and padding, and how many samples sit in zero runs.
+ * An inspection job is a parse-only walk: k_inspect (one lane per version-3 block) and k_inspect_serial (one lane per
+ * version-2 stream) read the tokens, follow the Rice adaptation -- which depends on residual magnitudes alone -- and keep
+ * a tally.  Nothing is synthesised and no PCM exists anywhere in the job; one lacx_block_info per block comes back.
+ * Verdict of a block (code, the decoder's codes, lacx_block_fault_text): 0 the block parses, 1 block header, 2 channel
+ *   header, 3 residual, 4 padding, 6 trailing bytes, 8 not reached (version 2, behind a block that does not parse), 9 a
+ *   zigzag value of 2^30 or more, 10 the file does not hold the block.  Within one token a parse fault wins over
+ *   anything else, as in the decoder.  Codes 5 (sample overflow) and 7 (sample outside the bit depth) need reconstructed
+ *   samples: inspection NEVER reports them, and a block that fails with one of them in a decode inspects as 0 (or, for
+ *   code 5, as whatever the parse finds behind the sample at which the decoder stopped).  lacx_decoder_check_* and
+ *   lacx_decoder_stats_* are the tools for those codes.
+ * lacx_channel_info, per channel block (160 bytes):
+ *   predictor_type (0 fixed, 1 FIR, 2 LPC), order, partition_order; coef: the LPC coefficients as stored, zero beyond order.
+ *   Bit classes, which sum to bits: header_bits (type, order, 16 per coefficient, control byte, 7 per partition),
+ *   tag_bits (2 per tagged token), unary_bits (ones plus terminator, of residual codes and of run-length codes),
+ *   remainder_bits (k-bit remainders, the run code's 2 bits, bin sign bits), escape_bits (32 per escape), pad_bits.
+ *   Sample classes, which sum to the block's frames: rice_samples (bare codes of modes 0 and 3, tag 00 of mode 1, tag 11 of
+ *   mode 2), run_samples (in run_tokens runs), escape_samples, bin_samples[t] (tags 00, 01, 10 of mode 2).
+ *   mode_parts[m] / mode_samples[m]: partitions and samples by residual mode (0 adaptive Rice, 1 zero-run, 2 bin, 3 static).
+ *   k_min / k_max: the parameter in force at the Rice-coded residuals (255 and 0 when there are none); unary_max: the
+ *   longest quotient of any unary part; max_u / sum_u: over the zigzag magnitudes of all samples.
+ * lacx_block_info, 336 bytes: frames and bytes from the block table (version 2 has no sizes: bytes is what the walk
+ *   found); code; ms: 1 when the block is mid/side, by flag or by stream mode; channels; ch[1] is all zero for mono.
+ *   8 * bytes == 8 * (per-block flag present) + ch[0].bits + ch[1].bits.  A block that does not parse or is missing
+ *   keeps frames, bytes and code (bytes 0 for version 2); every other field is 0.
+ * lacx_stream_report, 456 bytes, per item, made on the host from the rows by lacx_inspect_combine: integers only (bits
+ *   per sample and shares are the caller's to derive).  Totals run over the blocks that parse: payload_bytes is the sum
+ *   of their bytes, so 8 * payload_bytes == flag_bits + bits.  fixed_blocks[o], fir_blocks, lpc_blocks[o] (o = 1..32,
+ *   [0] unused), partition_order_blocks[p] count channel blocks.  sum_u is a 128-bit pair.  k_min 255 / k_max 0 with no
+ *   Rice-coded residual.
+ * lacx_decoder_inspect_batch_device: lenient exactly like lacx_decoder_stats_batch_device -- versions 3 and 2, truncated
+ *   files (their missing blocks get code 10), LACX_OK whenever the container is accepted; a refused container keeps the
+ *   strict code and text and gets a zeroed report and no rows.  flags: 0 or LACX_INSPECT_PARTITIONS (anything else
+ *   LACX_E_INVALID).  out_reports: nullable array of n.  The return code, "stream i: " prefixes, lacx_decoder_item_error,
+ *   n = 0, null arrays, device-less behaviour (host-side outcomes filled, then LACX_E_DEVICE) and `stream` as
+ *   lacx_decoder_stats_batch_device.  Inspection may alternate with every other job form on one decoder.
+ * lacx_decoder_item_block_info: the rows of item i of the decoder's last inspection call, valid until its next call;
+ *   LACX_E_INVALID outside that call.
+ * lacx_decoder_item_partitions: with LACX_INSPECT_PARTITIONS, channel block `channel` of block `block` of item i:
+ *   mode_k[p] = (mode << 5) | k of partition p's table entry, as lacx_channel_plan.part_mode_k, part_bits[p] the bits of
+ *   its tokens; count = the partitions (0 for a block that does not parse).  LACX_E_INVALID when the last call did not ask
+ *   for them or the indices are outside it.  Without the flag the partition buffer is neither allocated nor copied.
+ * lacx_inspect_combine: host only, no device: the totals of `count` rows (rows may be null when count is 0), public so
+ *   that a caller can total a sub-range.  info: the stream (format fields and head_bytes from it), or null: those are 0. */
+#define LACX_INSPECT_PARTITIONS 1u
+typedef struct lacx_channel_info { /* 160 bytes */
+    uint8_t predictor_type, order, partition_order, k_min, k_max, reserved[3];
+    int16_t coef[32];
+    uint32_t bits, header_bits, tag_bits, unary_bits, remainder_bits, escape_bits, pad_bits;
+    uint32_t rice_samples, run_tokens, run_samples, escape_samples, bin_samples[3];
+    uint16_t mode_parts[4], mode_samples[4];
+    uint32_t unary_max, max_u;
+    uint64_t sum_u;
+} lacx_channel_info;
+typedef struct lacx_block_info {   /* 336 bytes */
+    uint32_t frames, bytes, code;
+    uint8_t ms, channels, reserved[2];
+    lacx_channel_info ch[2];
+} lacx_block_info;
+typedef struct lacx_stream_report { /* 456 bytes */
+    uint64_t frames, head_bytes, payload_bytes;
+    uint32_t sample_rate;
+    uint8_t channels, bit_depth, stereo_mode, version;
+    uint32_t blocks, lost_blocks, ms_blocks, channel_blocks;
+    uint32_t fixed_blocks[5], fir_blocks, lpc_blocks[33], partition_order_blocks[9];
+    uint64_t mode_parts[4], mode_samples[4];
+    uint64_t bits, flag_bits, header_bits, tag_bits, unary_bits, remainder_bits, escape_bits, pad_bits;
+    uint64_t rice_samples, run_tokens, run_samples, escape_samples, bin_samples[3];
+    uint64_t sum_u_lo, sum_u_hi;
+    uint32_t max_u, unary_max;
+    uint8_t k_min, k_max, reserved[6];
+} lacx_stream_report;
+int lacx_decoder_inspect_batch_device(lacx_decoder* dec, const lacx_span* lacs, uint32_t n, uint32_t flags, void* stream, int* item_rc,
+                                      lacx_stream_report* out_reports, float* device_ms);
+int lacx_decoder_item_block_info(const lacx_decoder* dec, uint32_t i, const lacx_block_info** rows, uint32_t* count);
+int lacx_decoder_item_partitions(const lacx_decoder* dec, uint32_t i, uint32_t block, uint32_t channel, const uint8_t** mode_k,
+                                 const uint32_t** part_bits, uint32_t* count);
+int lacx_inspect_combine(const lacx_block_info* rows, uint32_t count, const lacx_stream_info* info, lacx_stream_report* out);
+/* Diagnostic.  With LACX_INSPECT_GUARD=1 in the environment (read per call) an inspection job's tables buffer is made
+ * larger than its plan asks by a guard -- 4096 bytes, and without LACX_INSPECT_PARTITIONS also the bytes the partition
+ * entries of the job's blocks would take -- which is filled with a pattern on the device before the kernels run and read
+ * back behind them: *guarded = its bytes in the decoder's last inspection call (0: no guard), *changed = those that no
+ * longer hold the pattern.  A call that changed any fails as a whole with LACX_E_DEVICE. */
+int lacx_decoder_inspect_guard(const lacx_decoder* dec, uint64_t* guarded, uint64_t* changed);
 
 /* Recovery data: repairing a damaged .lac file from a parity sidecar.  Digests, salvage and the manifest all end in "this
  * block is lost"; the container has no redundancy of its own.  A recovery sidecar ("LACR") kept beside the file brings the

@@ -495,7 +495,11 @@ uint32_t lacx_sizeof(const char* name) {
                  {"manifest_info", sizeof(lacx_manifest_info)},   {"recovery_params", sizeof(lacx_recovery_params)},
                  {"recovery_info", sizeof(lacx_recovery_info)}, {"repair_result", sizeof(lacx_repair_result)},
                  {"channel_stats", sizeof(lacx_channel_stats)}, {"block_stats", sizeof(lacx_block_stats)},
-                 {"channel_totals", sizeof(lacx_channel_totals)}, {"stats", sizeof(lacx_stats)}};
+                 {"channel_totals", sizeof(lacx_channel_totals)}, {"stats", sizeof(lacx_stats)},
+                 {"channel_info", sizeof(lacx_channel_info)}, {"block_info", sizeof(lacx_block_info)},
+                 {"stream_report", sizeof(lacx_stream_report)}};
+    static_assert(sizeof(lacx_channel_info) == 160 && sizeof(lacx_block_info) == 336 && sizeof(lacx_stream_report) == 456,
+                  "the inspection's records have fixed sizes (lacx.h)");
     static_assert(sizeof(lacx_channel_stats) == 40 && sizeof(lacx_block_stats) == 104 && sizeof(lacx_channel_totals) == 64 &&
                       sizeof(lacx_stats) == 192,
                   "the statistics' records have fixed sizes (lacx.h)");

@@ -5,6 +5,8 @@
 #include "device_buf.h"
 #include "encoder_impl.h"
 #include "import_msg.h"
+#include "inspect_plan.h"
+#include "inspect_rows.h"
 #include "stats_rows.h"
 
 // (the entry points are declared extern "C" in lacx.h)
@@ -920,6 +922,150 @@ int lacx_stats_combine(const lacx_block_stats* rows, uint32_t count, uint8_t cha
     if (channels != 1 && channels != 2) return decode_fail(LACX_E_INVALID, "unsupported channel count");
     if (bit_depth != 16 && bit_depth != 24) return decode_fail(LACX_E_INVALID, "unsupported bit depth: " + std::to_string((int)bit_depth));
     *out = stats_combine(rows, count, channels, bit_depth, sample_rate);
+    return LACX_OK;
+}
+
+// ---- stream inspection (lacx.h) ----
+namespace {
+// An inspection job: planned by plan_inspect (a salvage job's items and tables, none of its decode), run as the decoder
+// runs its jobs -- tables and payload up, k_inspect / k_inspect_serial between the two events, the rows back.
+int inspect_run(lacx_decoder* d, const BatchIn* in, uint32_t n, bool partitions, hipStream_t st, lacx_stream_report* out, float* device_ms,
+                std::vector<int>& code, std::vector<std::string>& err) {
+    if (device_ms) *device_ms = 0.f;
+    if (out) std::memset(out, 0, sizeof(lacx_stream_report) * n);
+    auto clear = [&] {
+        d->item_info.assign(n, {});
+        d->info_mode_k.clear();
+        d->info_part_bits.clear();
+        d->info_block0.assign(n, ~0u);
+    };
+    clear();
+    d->info_guard = d->info_guard_changed = 0;
+    const char* pad_env = std::getenv("LACX_DECODE_BATCH_PAD");
+    // LACX_INSPECT_GUARD=1 (diagnostic, read per call): the tables buffer is made larger than the plan asks by a guard --
+    // 4096 bytes, and for a job without partition detail the bytes the partition entries of its blocks would take -- that
+    // is filled with kGuardByte before the kernels run and read back behind them (lacx_decoder_inspect_guard)
+    const char* guard_env = std::getenv("LACX_INSPECT_GUARD");
+    constexpr int kGuardByte = 0xA5;
+    InspectPlan plan;
+    const char* whole = plan_inspect(in, n, partitions, pad_env && pad_env[0] == '1', plan, code, err);
+    if (lacx_device_count() <= 0) whole = "no usable HIP device";
+    int rc = whole ? decode_fail(LACX_E_DEVICE, whole) : LACX_OK;
+    const DecodePlan& base = plan.base;
+    if (!whole && !base.items.empty()) {
+        DecodeJob job{in, n, DecodeForm::blocks};
+        const size_t T = (size_t)base.total_blocks;
+        const uint64_t guard = guard_env && guard_env[0] == '1'
+                                   ? 4096u + (partitions ? 0u : (kInspectPartModeBytes + kInspectPartBitsBytes) * (uint64_t)T + 16u)
+                                   : 0u;
+        int prev_device = -1;
+        DevErr e = decoder_open(d, &prev_device);
+        if (!e && guard) e = buf_grow(d->tables, plan.need.tables + guard, 0);
+        if (!e) e = ensure_capacities(d, base);
+        if (!e) e = upload_tables(d, job, base, st);
+        if (!e) e = upload_payload(d, job, base, st);
+        if (!e && guard) e = chk(hipMemsetAsync(d->d_meta() + plan.need.tables, kGuardByte, guard, st), "memset");
+        if (!e) e = chk(hipEventRecord(d->e0, st), "event record");
+        if (!e) e = chk(launch_inspect(plan_inspect_args(plan, d->d_meta(), d->d_pay()), st), "inspect launch");
+        if (!e) e = chk(hipEventRecord(d->e1, st), "event record");
+        if (!e) e = chk(hipMemcpyAsync(d->h_meta() + plan.at_rows, d->d_meta() + plan.at_rows, plan.need.tables + guard - plan.at_rows, hipMemcpyDeviceToHost, st),
+                        "D2H inspection rows");
+        if (!e) e = chk(hipStreamSynchronize(st), "synchronize");
+        if (!e && device_ms) (void)hipEventElapsedTime(device_ms, d->e0, d->e1);
+        if (prev_device >= 0) (void)hipSetDevice(prev_device);
+        if (!e && guard) {
+            d->info_guard = guard;
+            for (uint64_t k = 0; k < guard; ++k) d->info_guard_changed += d->h_meta()[plan.need.tables + k] != (uint8_t)kGuardByte;
+        }
+        if (e) {
+            rc = decode_fail(LACX_E_DEVICE, std::string(e.what) + ": " + hipGetErrorString(e.e));
+        } else if (d->info_guard_changed) {
+            rc = decode_fail(LACX_E_DEVICE, "inspection wrote " + std::to_string(d->info_guard_changed) + " bytes behind its tables");
+        } else {
+            const lacx_block_info* dev = reinterpret_cast<const lacx_block_info*>(d->h_meta() + plan.at_rows);
+            for (const PlanItem& p : base.items) {
+                const uint32_t i = p.src;
+                inspect_rows_of_item(in[i].lac, p.info.version, p.item.blocks, p.present_blocks, dev + p.item.block0, d->item_info[i]);
+                if (out) out[i] = inspect_combine(d->item_info[i].data(), (uint32_t)d->item_info[i].size(), &p.info);
+                if (partitions) d->info_block0[i] = p.item.block0;
+            }
+            if (partitions) {
+                const uint8_t* mk = d->h_meta() + plan.at_mode_k;
+                const uint32_t* pb = reinterpret_cast<const uint32_t*>(d->h_meta() + plan.at_part_bits);
+                d->info_mode_k.assign(mk, mk + kInspectPartModeBytes * T);
+                d->info_part_bits.assign(pb, pb + kInspectPartBitsBytes / 4 * T);
+            }
+        }
+    }
+    if (rc != LACX_OK) {  // the whole call failed: no item was inspected
+        clear();
+        if (out) std::memset(out, 0, sizeof(lacx_stream_report) * n);
+        for (uint32_t i = 0; i < n; ++i) {
+            if (code[i] != LACX_OK) continue;
+            code[i] = rc;
+            err[i] = g_decode_err;
+        }
+    }
+    return rc;
+}
+}  // namespace
+
+int lacx_decoder_inspect_batch_device(lacx_decoder* d, const lacx_span* lacs, uint32_t n, uint32_t flags, void* stream, int* item_rc,
+                                      lacx_stream_report* out, float* device_ms) {
+    if (!d) return decode_fail(LACX_E_INVALID, "null decoder");
+    if (!lacs || n == 0) return decode_fail(LACX_E_INVALID, "null argument or empty batch");
+    if (flags & ~LACX_INSPECT_PARTITIONS) return decode_fail(LACX_E_INVALID, "unknown inspection flag");
+    std::vector<BatchIn> in(n);
+    for (uint32_t i = 0; i < n; ++i) in[i] = BatchIn{lacs[i].data, lacs[i].size, nullptr, nullptr, 0};
+    std::vector<int> code;
+    std::vector<std::string> err;
+    const int rc = inspect_run(d, in.data(), n, (flags & LACX_INSPECT_PARTITIONS) != 0, static_cast<hipStream_t>(stream), out, device_ms, code, err);
+    return batch_outcome(d, rc, code, err, item_rc);
+}
+
+int lacx_decoder_item_block_info(const lacx_decoder* d, uint32_t i, const lacx_block_info** rows, uint32_t* count) {
+    if (rows) *rows = nullptr;
+    if (count) *count = 0;
+    if (!d || !rows || !count) return decode_fail(LACX_E_INVALID, "null argument");
+    if (i >= d->item_info.size()) return decode_fail(LACX_E_INVALID, "no such item in the last inspection call");
+    *rows = d->item_info[i].data();
+    *count = (uint32_t)d->item_info[i].size();
+    return LACX_OK;
+}
+
+int lacx_decoder_item_partitions(const lacx_decoder* d, uint32_t i, uint32_t block, uint32_t channel, const uint8_t** mode_k,
+                                 const uint32_t** part_bits, uint32_t* count) {
+    if (mode_k) *mode_k = nullptr;
+    if (part_bits) *part_bits = nullptr;
+    if (count) *count = 0;
+    if (!d || !mode_k || !part_bits || !count) return decode_fail(LACX_E_INVALID, "null argument");
+    if (i >= d->item_info.size()) return decode_fail(LACX_E_INVALID, "no such item in the last inspection call");
+    if (d->info_mode_k.empty() || d->info_block0[i] == ~0u) return decode_fail(LACX_E_INVALID, "the last inspection call kept no partition detail for this item");
+    const std::vector<lacx_block_info>& rows = d->item_info[i];
+    if (block >= rows.size() || channel >= 2u) return decode_fail(LACX_E_INVALID, "no such channel block in the item");
+    const lacx_block_info& r = rows[block];
+    if (r.code == LACX_BLOCK_MISSING || r.code != 0 || channel >= r.channels) return LACX_OK;  // nothing to report: count 0
+    const size_t at = ((size_t)d->info_block0[i] + block) * 2u * kInspectPartSlots + (size_t)channel * kInspectPartSlots;
+    const lacx_channel_info& c = r.ch[channel];
+    *mode_k = d->info_mode_k.data() + at;
+    *part_bits = d->info_part_bits.data() + at;
+    *count = (uint32_t)c.mode_parts[0] + c.mode_parts[1] + c.mode_parts[2] + c.mode_parts[3];
+    return LACX_OK;
+}
+
+int lacx_decoder_inspect_guard(const lacx_decoder* d, uint64_t* guarded, uint64_t* changed) {
+    if (guarded) *guarded = 0;
+    if (changed) *changed = 0;
+    if (!d || !guarded || !changed) return decode_fail(LACX_E_INVALID, "null argument");
+    *guarded = d->info_guard;
+    *changed = d->info_guard_changed;
+    return LACX_OK;
+}
+
+int lacx_inspect_combine(const lacx_block_info* rows, uint32_t count, const lacx_stream_info* info, lacx_stream_report* out) {
+    if (out) std::memset(out, 0, sizeof(*out));
+    if (!out || (!rows && count)) return decode_fail(LACX_E_INVALID, "null argument");
+    *out = inspect_combine(rows, count, info);
     return LACX_OK;
 }
 

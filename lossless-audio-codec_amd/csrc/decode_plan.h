@@ -90,6 +90,8 @@ struct PlanItem {
 // | res [m] at `win`, for a salvage job | present [m] (uint32) at `win` (byte offsets); with block digests behind that
 // | judged [m] (uint32) | raw [T] (uint32, 16-byte aligned) and for a judged job | expect [T] (uint32); a stats job
 // behind present [m] | stats [T] (kStatsRowBytes each, 16-byte aligned)
+// (inspect_plan.h keeps items .. present [m] of a salvage job's layout and puts its rows behind them: a change of this
+// order is a change there too, and plan_inspect refuses a layout it does not know)
 struct TableLayout {
     size_t items, byte_off, frame_off, unit_off, blk_item, lane_blk, v2_items, win, res, size;
     size_t judged = 0, raw = 0, expect = 0;  // block digests only

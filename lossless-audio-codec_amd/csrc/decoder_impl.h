@@ -36,6 +36,13 @@ struct lacx_decoder {
     std::vector<std::vector<lacx_block_fault>> item_faults;  // the last salvage call's lost blocks per item
     std::vector<std::vector<lacx_block_digest>> item_rows;   // the last block digest call's rows per item
     std::vector<std::vector<lacx_block_stats>> item_stats;   // the last stats call's rows per item
+    std::vector<std::vector<lacx_block_info>> item_info;     // the last inspection call's rows per item
+    // ... and, where it asked for partition detail, the entries of all its blocks: [T][2][256] each, item i's blocks
+    // from info_block0[i] on (~0u: the item has none)
+    std::vector<uint8_t> info_mode_k;
+    std::vector<uint32_t> info_part_bits;
+    std::vector<uint32_t> info_block0;
+    uint64_t info_guard = 0, info_guard_changed = 0;         // LACX_INSPECT_GUARD: the guard bytes behind its tables, and those the job changed
     std::vector<std::vector<uint32_t>> item_bad;             // the last recovery scan / repair call's damaged slices per item
     std::string err;
 };

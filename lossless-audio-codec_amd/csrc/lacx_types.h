@@ -3,6 +3,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+struct lacx_block_info;  // lacx.h
+
 namespace lacx {
 
 constexpr int kMaxBlock = 16384;  // Block::MAX_BLOCK_SIZE        (ref src/codec/block/constants.hpp:6)
@@ -216,5 +218,15 @@ struct StatsPcmArgs {
     uint32_t grid = 0;                             // frames per block, 256 .. 16384
     const unsigned long long* block_off = nullptr; // [nitems + 1] prefix sums of ceil(frames / grid)
     StatsAcc* rows = nullptr;                      // [block_off[nitems]]
+};
+// Stream inspection (k_inspect / k_inspect_serial, inspect_core.h): the decode's tables without its outputs (status and
+// ms_flag are not used), one row per global block, and for a job with partition detail the entries of both channel blocks.
+constexpr uint32_t kInspectPartSlots = 256;        // partition entries per channel block: 1 << kMaxPartitionOrder
+static_assert(kInspectPartSlots == (uint32_t)kMaxParts, "a channel block has at most kMaxParts partitions");
+struct InspectArgs {
+    DecodeArgs dec;
+    lacx_block_info* rows = nullptr;               // [dec.total_blocks]
+    uint8_t* mode_k = nullptr;                     // [dec.total_blocks][2][256], zero on entry, or null
+    uint32_t* part_bits = nullptr;                 // [dec.total_blocks][2][256], zero on entry, or null
 };
 }  // namespace lacx

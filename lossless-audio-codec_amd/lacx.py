@@ -121,6 +121,8 @@ EXPORTS = (
     "lacx_recovery_build_batch_view", "lacx_recovery_build", "lacx_recovery_parse", "lacx_recovery_scan_batch",
     "lacx_recovery_repair_batch_view", "lacx_recovery_repair", "lacx_decoder_item_bad_slices",
     "lacx_decoder_stats_batch_device", "lacx_decoder_stats_pcm_batch_device", "lacx_decoder_item_block_stats", "lacx_stats_combine",
+    "lacx_decoder_inspect_batch_device", "lacx_decoder_item_block_info", "lacx_decoder_item_partitions", "lacx_inspect_combine",
+    "lacx_decoder_inspect_guard",
 )
 
 
@@ -233,6 +235,13 @@ def lib():
                                                           C.POINTER(C.c_int), C.POINTER(Stats), C.POINTER(C.c_float)]
         L.lacx_decoder_item_block_stats.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.POINTER(BlockStats)), C.POINTER(C.c_uint32)]
         L.lacx_stats_combine.argtypes = [C.POINTER(BlockStats), C.c_uint32, C.c_uint8, C.c_uint8, C.c_uint32, C.POINTER(Stats)]
+        L.lacx_decoder_inspect_batch_device.argtypes = [C.c_void_p, C.POINTER(Span), C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_int),
+                                                        C.POINTER(StreamReport), C.POINTER(C.c_float)]
+        L.lacx_decoder_item_block_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.POINTER(BlockInfo)), C.POINTER(C.c_uint32)]
+        L.lacx_decoder_item_partitions.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(u8p),
+                                                   C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint32)]
+        L.lacx_decoder_inspect_guard.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.lacx_inspect_combine.argtypes = [C.POINTER(BlockInfo), C.c_uint32, C.POINTER(StreamInfo), C.POINTER(StreamReport)]
         L.lacx_block_fault_text.restype = C.c_char_p
         L.lacx_block_fault_text.argtypes = [C.c_uint32]
         L.lacx_decoder_item_error.restype = C.c_char_p
@@ -260,7 +269,8 @@ def abi_structs() -> dict:
             "block_fault": BlockFault, "salvage_result": SalvageResult, "block_digest": BlockDigest,
             "manifest_info": ManifestInfo, "recovery_params": RecoveryParams, "recovery_info": RecoveryInfo,
             "repair_result": RepairResult, "channel_stats": ChannelStats, "block_stats": BlockStats,
-            "channel_totals": ChannelTotals, "stats": Stats}
+            "channel_totals": ChannelTotals, "stats": Stats, "channel_info": ChannelInfo, "block_info": BlockInfo,
+            "stream_report": StreamReport}
 
 
 def device_count() -> int:
@@ -942,6 +952,79 @@ def stats_combine(rows, channels: int, bit_depth: int, sample_rate: int = 0) -> 
     return out
 
 
+INSPECT_PARTITIONS = 1  # LACX_INSPECT_PARTITIONS (call flag)
+BIT_CLASSES = ("header_bits", "tag_bits", "unary_bits", "remainder_bits", "escape_bits", "pad_bits")
+
+
+class ChannelInfo(C.Structure):
+    """How one channel block was coded (lacx_channel_info): predictor, partition order, where its bits and samples go."""
+    _fields_ = [("predictor_type", C.c_uint8), ("order", C.c_uint8), ("partition_order", C.c_uint8), ("k_min", C.c_uint8),
+                ("k_max", C.c_uint8), ("reserved", C.c_uint8 * 3), ("coef", C.c_int16 * 32),
+                ("bits", C.c_uint32), ("header_bits", C.c_uint32), ("tag_bits", C.c_uint32), ("unary_bits", C.c_uint32),
+                ("remainder_bits", C.c_uint32), ("escape_bits", C.c_uint32), ("pad_bits", C.c_uint32),
+                ("rice_samples", C.c_uint32), ("run_tokens", C.c_uint32), ("run_samples", C.c_uint32),
+                ("escape_samples", C.c_uint32), ("bin_samples", C.c_uint32 * 3),
+                ("mode_parts", C.c_uint16 * 4), ("mode_samples", C.c_uint16 * 4),
+                ("unary_max", C.c_uint32), ("max_u", C.c_uint32), ("sum_u", C.c_uint64)]
+
+    @property
+    def partitions(self) -> int:
+        return sum(self.mode_parts)
+
+
+class BlockInfo(C.Structure):
+    """One block of an inspected stream (lacx_block_info); a block that does not parse keeps frames, bytes and code."""
+    _fields_ = [("frames", C.c_uint32), ("bytes", C.c_uint32), ("code", C.c_uint32), ("ms", C.c_uint8), ("channels", C.c_uint8),
+                ("reserved", C.c_uint8 * 2), ("ch", ChannelInfo * 2)]
+    # with Decoder.inspect_batch(partitions=True): per channel block [(mode_k, part_bits), ...], else None
+    partitions = None
+
+
+class StreamReport(C.Structure):
+    """The totals of an item over the blocks that parse (lacx_stream_report).  Exact integers; `bits_per_sample` and
+    `shares` are derived floats and part of no equality."""
+    _fields_ = [("frames", C.c_uint64), ("head_bytes", C.c_uint64), ("payload_bytes", C.c_uint64), ("sample_rate", C.c_uint32),
+                ("channels", C.c_uint8), ("bit_depth", C.c_uint8), ("stereo_mode", C.c_uint8), ("version", C.c_uint8),
+                ("blocks", C.c_uint32), ("lost_blocks", C.c_uint32), ("ms_blocks", C.c_uint32), ("channel_blocks", C.c_uint32),
+                ("fixed_blocks", C.c_uint32 * 5), ("fir_blocks", C.c_uint32), ("lpc_blocks", C.c_uint32 * 33),
+                ("partition_order_blocks", C.c_uint32 * 9), ("mode_parts", C.c_uint64 * 4), ("mode_samples", C.c_uint64 * 4),
+                ("bits", C.c_uint64), ("flag_bits", C.c_uint64), ("header_bits", C.c_uint64), ("tag_bits", C.c_uint64),
+                ("unary_bits", C.c_uint64), ("remainder_bits", C.c_uint64), ("escape_bits", C.c_uint64), ("pad_bits", C.c_uint64),
+                ("rice_samples", C.c_uint64), ("run_tokens", C.c_uint64), ("run_samples", C.c_uint64),
+                ("escape_samples", C.c_uint64), ("bin_samples", C.c_uint64 * 3), ("sum_u_lo", C.c_uint64), ("sum_u_hi", C.c_uint64),
+                ("max_u", C.c_uint32), ("unary_max", C.c_uint32), ("k_min", C.c_uint8), ("k_max", C.c_uint8),
+                ("reserved", C.c_uint8 * 6)]
+
+    @property
+    def sum_u(self) -> int:
+        return (self.sum_u_hi << 64) | self.sum_u_lo
+
+    @property
+    def samples(self) -> int:
+        """The samples of the channel blocks that parse."""
+        return sum(self.mode_samples)
+
+    @property
+    def bits_per_sample(self) -> float:
+        """Derived: payload bits of the blocks that parse per sample of theirs."""
+        return 8.0 * self.payload_bytes / self.samples if self.samples else 0.0
+
+    @property
+    def shares(self) -> dict:
+        """Derived: each bit class (and the per-block flags) as a share of the payload bits of the blocks that parse."""
+        total = 8.0 * self.payload_bytes
+        return {k: (getattr(self, k) / total if total else 0.0) for k in (*BIT_CLASSES, "flag_bits")}
+
+
+def inspect_combine(rows, info: "StreamInfo | None" = None) -> StreamReport:
+    """The totals of BlockInfo rows (all of an item's, or a sub-range), as inspect_batch makes an item's.  Host only."""
+    arr = (BlockInfo * max(1, len(rows)))(*rows)
+    out = StreamReport()
+    if lib().lacx_inspect_combine(arr, C.c_uint32(len(rows)), C.byref(info) if info is not None else None, C.byref(out)) != OK:
+        raise ValueError(lib().lacx_decode_last_error().decode(errors="replace"))
+    return out
+
+
 REPAIR_TRUNCATED, REPAIR_TRAILING, REPAIR_SIDECAR_TRUNCATED, REPAIR_UNREPAIRED = 1, 2, 4, 8  # LACX_REPAIR_* (result flags)
 REPAIR_BEST_EFFORT = 1                                                                       # LACX_REPAIR_BEST_EFFORT (call flag)
 
@@ -1567,6 +1650,50 @@ class Decoder:
             raise RuntimeError(lib().lacx_decode_last_error().decode(errors="replace"))
         errors = {i: lib().lacx_decoder_item_error(self._h, i).decode(errors="replace") for i in range(n) if rcs[i] != OK}
         return self._raise_batch(rc, errors, [None if i in errors else (_copy_struct(out[i]), self._stat_rows(i)) for i in range(n)])
+
+    # ---- stream inspection: predictors, modes, bit budget ----
+    def _info_rows(self, i, partitions) -> list:
+        ptr, count = C.POINTER(BlockInfo)(), C.c_uint32()
+        if lib().lacx_decoder_item_block_info(self._h, C.c_uint32(i), C.byref(ptr), C.byref(count)) != OK:
+            return []
+        rows = [_copy_struct(ptr[k]) for k in range(count.value)]  # copies: the rows die with the decoder's next call
+        for b, row in enumerate(rows if partitions else ()):
+            row.partitions = []
+            for c in range(row.channels):
+                mk, pb, n = C.POINTER(C.c_uint8)(), C.POINTER(C.c_uint32)(), C.c_uint32()
+                if lib().lacx_decoder_item_partitions(self._h, C.c_uint32(i), C.c_uint32(b), C.c_uint32(c), C.byref(mk), C.byref(pb), C.byref(n)) != OK:
+                    raise RuntimeError(lib().lacx_decode_last_error().decode(errors="replace"))
+                row.partitions.append([(int(mk[p]), int(pb[p])) for p in range(n.value)])
+        return rows
+
+    def inspect_batch(self, lacs, partitions: bool = False, stream: int = 0) -> list:
+        """Many streams walked token by token as one device job -- no synthesis, no PCM -- lenient like stats_batch: per
+        item (StreamReport, [BlockInfo]), None where the container is refused (those raise BatchDecodeError once the others
+        are done).  A block that does not parse carries its code and is otherwise 0; the totals cover the blocks that
+        parse.  Codes 5 and 7 need samples and are never reported here.  partitions: every row's `partitions` holds per
+        channel block the (mode_k, part_bits) of its partitions.  Kernel milliseconds in `last_ms`."""
+        bufs = [np.frombuffer(x, dtype=np.uint8) for x in lacs]
+        n = len(bufs)
+        spans = (Span * max(1, n))(*[Span(b.ctypes.data_as(C.POINTER(C.c_uint8)), b.size) for b in bufs])
+        out = (StreamReport * max(1, n))()
+        rc, errors = self._batch(n, lambda rcs, ms: lib().lacx_decoder_inspect_batch_device(
+            self._h, spans, C.c_uint32(n), C.c_uint32(INSPECT_PARTITIONS if partitions else 0), C.c_void_p(stream), rcs, out, ms))
+        return self._raise_batch(rc, errors, [None if i in errors else (_copy_struct(out[i]), self._info_rows(i, partitions)) for i in range(n)])
+
+    def inspect_guard(self):
+        """(guarded, changed): with LACX_INSPECT_GUARD=1 in the environment, the guard bytes behind the last inspection job's
+        tables on the device and how many of them the job changed (lacx_decoder_inspect_guard); (0, 0) without."""
+        guarded, changed = C.c_uint64(), C.c_uint64()
+        if lib().lacx_decoder_inspect_guard(self._h, C.byref(guarded), C.byref(changed)) != OK:
+            raise RuntimeError(lib().lacx_decode_last_error().decode(errors="replace"))
+        return guarded.value, changed.value
+
+    def inspect(self, lac) -> StreamReport:
+        """The totals of inspect_batch of one stream; RuntimeError with the parser's message where the container is refused."""
+        try:
+            return self.inspect_batch([lac])[0][0]
+        except BatchDecodeError as e:
+            raise RuntimeError(e.errors[0]) from None
 
     def check_batch(self, lacs, manifests, stream: int = 0) -> list:
         """Is each stream intact -- does every block decode to what its manifest says?  Per item (SalvageResult,

@@ -21,6 +21,8 @@
 // lacx_decoder_digest_pcm_batch_device): a .lac and the WAV it was made from print the same fields.
 // stats (no counterpart in the reference's tool; `sox stat` without the floats): the audio statistics of the same two
 // kinds of file, made on the device (lacx_decoder_stats_batch_device / lacx_decoder_stats_pcm_batch_device).
+// inspect (`flac -a` for .lac): how each stream was coded and where its bits go, read out of the bytes on the device by a
+// parse-only walk (lacx_decoder_inspect_batch_device).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -59,6 +61,9 @@ void usage() {
                  "  lacx_cli digest FILE...   (.lac and .wav files, told apart by content)\n"
                  "  lacx_cli stats FILE... [--blocks]   (.lac and .wav files: peaks, energy, silence and bit use as integers, one line\n"
                  "      per file; --blocks: one further line per block; exit 0 when every file gave statistics, else 1)\n"
+                 "  lacx_cli inspect FILE... [--blocks] [--partitions]   (.lac files: predictors, residual modes and where the bits go, as\n"
+                 "      integers, one line per file; --blocks: one further line per block; --partitions: and one per partition;\n"
+                 "      a damaged stream prints its line with lost_blocks counted; exit 0 when every file was inspected, else 1)\n"
                  "  lacx_cli selftest\n";
 }
 
@@ -719,6 +724,113 @@ int stats_command(int argc, char** argv) {
     return status;
 }
 
+// lacx_cli inspect FILE... [--blocks] [--partitions]: how every .lac was coded and where its bits go, read out of the bytes
+// on the device by a parse-only walk (lacx_decoder_inspect_batch_device), all files as one job.  One line of integers per
+// file in argument order; with --blocks one further line per block (its channel blocks behind it), with --partitions one
+// per partition: mode, table k, bits.  Lenient like stats: a damaged or truncated stream prints its line with lost_blocks
+// counted.  Exit 0 when every file was inspected; otherwise the refused files' messages on stderr and exit 1.
+int inspect_command(int argc, char** argv) {
+    bool per_block = false, per_part = false;
+    std::vector<const char*> paths;
+    for (int i = 2; i < argc; ++i) {
+        if (std::strcmp(argv[i], "--blocks") == 0) per_block = true;
+        else if (std::strcmp(argv[i], "--partitions") == 0) per_part = true;
+        else if (std::strncmp(argv[i], "--", 2) == 0) {
+            std::cerr << "Error: unknown option " << argv[i] << "\n";
+            usage();
+            return 1;
+        } else paths.push_back(argv[i]);
+    }
+    const int n = (int)paths.size();
+    if (n == 0) {
+        usage();
+        return 1;
+    }
+    std::vector<std::vector<uint8_t>> data(n);
+    std::vector<std::string> error(n);
+    std::vector<int> sent;
+    std::vector<lacx_span> spans;
+    for (int i = 0; i < n; ++i) {
+        if (!load_file(paths[i], data[i])) error[i] = "Failed to read file";
+        else sent.push_back(i), spans.push_back(lacx_span{data[i].data(), data[i].size()});
+    }
+    lacx_decoder* dec = nullptr;
+    if (lacx_decoder_create(-1, &dec) != LACX_OK) {
+        std::cerr << "Error: lacx_decoder_create failed\n";
+        return 1;
+    }
+    std::vector<lacx_stream_report> out(spans.size());
+    std::vector<int> item_rc(spans.size(), LACX_OK);
+    int rc = LACX_OK;
+    if (!spans.empty())
+        rc = lacx_decoder_inspect_batch_device(dec, spans.data(), (uint32_t)spans.size(), per_part ? LACX_INSPECT_PARTITIONS : 0u, nullptr,
+                                               item_rc.data(), out.data(), nullptr);
+    int status = 0;
+    size_t k = 0;
+    for (int i = 0; i < n; ++i) {
+        if (error[i].empty()) {
+            if (item_rc[k] != LACX_OK) error[i] = lacx_decoder_item_error(dec, (uint32_t)k);  // (a failure of the whole call is every item's)
+            else if (rc == LACX_E_DEVICE) error[i] = lacx_decode_last_error();
+            ++k;
+        }
+        if (!error[i].empty()) {
+            std::cerr << "Inspect failed: " << paths[i] << ": " << error[i] << "\n";
+            status = 1;
+            continue;
+        }
+        const uint32_t item = (uint32_t)(k - 1);
+        const lacx_stream_report& t = out[item];
+        std::cout << "frames=" << t.frames << " channels=" << (unsigned)t.channels << " bits=" << (unsigned)t.bit_depth << " rate=" << t.sample_rate
+                  << " version=" << (unsigned)t.version << " stereo_mode=" << (unsigned)t.stereo_mode << " blocks=" << t.blocks
+                  << " lost_blocks=" << t.lost_blocks << " head_bytes=" << t.head_bytes << " payload_bytes=" << t.payload_bytes
+                  << " ms_blocks=" << t.ms_blocks << " channel_blocks=" << t.channel_blocks << " fixed=";
+        for (int o = 0; o < 5; ++o) std::cout << (o ? "," : "") << t.fixed_blocks[o];
+        std::cout << " fir=" << t.fir_blocks << " lpc=";
+        for (int o = 1; o <= 32; ++o) std::cout << (o > 1 ? "," : "") << t.lpc_blocks[o];
+        std::cout << " partition_orders=";
+        for (int p = 0; p < 9; ++p) std::cout << (p ? "," : "") << t.partition_order_blocks[p];
+        std::cout << " mode_parts=" << t.mode_parts[0] << "," << t.mode_parts[1] << "," << t.mode_parts[2] << "," << t.mode_parts[3]
+                  << " mode_samples=" << t.mode_samples[0] << "," << t.mode_samples[1] << "," << t.mode_samples[2] << "," << t.mode_samples[3]
+                  << " flag_bits=" << t.flag_bits << " header_bits=" << t.header_bits << " tag_bits=" << t.tag_bits << " unary_bits=" << t.unary_bits
+                  << " remainder_bits=" << t.remainder_bits << " escape_bits=" << t.escape_bits << " pad_bits=" << t.pad_bits
+                  << " rice_samples=" << t.rice_samples << " run_tokens=" << t.run_tokens << " run_samples=" << t.run_samples
+                  << " escape_samples=" << t.escape_samples << " bin_samples=" << t.bin_samples[0] << "," << t.bin_samples[1] << "," << t.bin_samples[2]
+                  << " sum_u=" << dec128(t.sum_u_lo, t.sum_u_hi, false) << " max_u=" << t.max_u << " unary_max=" << t.unary_max
+                  << " k_min=" << (unsigned)t.k_min << " k_max=" << (unsigned)t.k_max << " " << paths[i] << "\n";
+        const lacx_block_info* rows = nullptr;
+        uint32_t count = 0;
+        if ((per_block || per_part) && lacx_decoder_item_block_info(dec, item, &rows, &count) != LACX_OK) count = 0;
+        for (uint32_t b = 0; b < count; ++b) {
+            const lacx_block_info& r = rows[b];
+            if (per_block) {
+                std::cout << "  block=" << b << " frames=" << r.frames << " bytes=" << r.bytes << " code=" << r.code << " ms=" << (unsigned)r.ms;
+                for (uint32_t c = 0; c < r.channels; ++c) {
+                    const lacx_channel_info& s = r.ch[c];
+                    std::cout << " ch" << c << ": type=" << (unsigned)s.predictor_type << " order=" << (unsigned)s.order
+                              << " partition_order=" << (unsigned)s.partition_order << " bits=" << s.bits << " header=" << s.header_bits
+                              << " tag=" << s.tag_bits << " unary=" << s.unary_bits << " remainder=" << s.remainder_bits << " escape=" << s.escape_bits
+                              << " pad=" << s.pad_bits << " rice=" << s.rice_samples << " runs=" << s.run_tokens << " run_samples=" << s.run_samples
+                              << " escapes=" << s.escape_samples << " bins=" << s.bin_samples[0] << "," << s.bin_samples[1] << "," << s.bin_samples[2]
+                              << " k=" << (unsigned)s.k_min << ".." << (unsigned)s.k_max << " unary_max=" << s.unary_max << " max_u=" << s.max_u
+                              << " sum_u=" << (unsigned long long)s.sum_u;
+                }
+                std::cout << "\n";
+            }
+            for (uint32_t c = 0; per_part && c < r.channels; ++c) {
+                const uint8_t* mk = nullptr;
+                const uint32_t* pb = nullptr;
+                uint32_t parts = 0;
+                if (lacx_decoder_item_partitions(dec, item, b, c, &mk, &pb, &parts) != LACX_OK) continue;
+                for (uint32_t p = 0; p < parts; ++p)
+                    std::cout << "    block=" << b << " ch=" << c << " partition=" << p << " mode=" << (mk[p] >> 5) << " k=" << (mk[p] & 31u)
+                              << " bits=" << pb[p] << "\n";
+            }
+        }
+    }
+    lacx_decoder_destroy(dec);
+    return status;
+}
+
 // The canonical WAV image of planar PCM (the source form lacx_decoder_verify_wav takes).
 std::vector<uint8_t> wav_image(const std::vector<int32_t>& left, const std::vector<int32_t>* right, uint32_t rate, uint32_t bits) {
     const uint32_t ch = right ? 2u : 1u, bps = bits / 8u, align = ch * bps;
@@ -846,6 +958,7 @@ int main(int argc, char** argv) {
     if (mode == "verify" && argc == 4) return verify_command(argv);
     if (mode == "digest" && argc >= 3) return digest_command(argc, argv);
     if (mode == "stats" && argc >= 3) return stats_command(argc, argv);
+    if (mode == "inspect" && argc >= 3) return inspect_command(argc, argv);
     if (mode == "manifest" && argc == 4) return manifest_command(argv);
     if (mode == "check" && argc == 4) return check_command(argv);
     if (mode == "protect" && argc >= 4) return protect_command(argc, argv);

@@ -1,7 +1,7 @@
 #!/bin/bash
-# Kernel resource usage (VGPRs, SGPRs, scratch, LDS, occupancy) of the kernel units (k_front, k_analyze, k_emit, decode, wide) as hipcc reports it.
+# Kernel resource usage (VGPRs, SGPRs, scratch, LDS, occupancy) of the kernel units (k_front, k_analyze, k_emit, decode, k_inspect, wide) as hipcc reports it.
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
-for u in k_front k_analyze k_emit decode wide; do
+for u in k_front k_analyze k_emit decode k_inspect wide; do
 hipcc -O3 -std=c++20 --offload-arch=gfx950 $EXTRA -I$ROOT/lossless-audio-codec_amd/csrc -I$ROOT/include -c $ROOT/lossless-audio-codec_amd/csrc/$u.hip \
   -Rpass-analysis=kernel-resource-usage -o /tmp/kres.o 2>&1
 done | python3 -c '
