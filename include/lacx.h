@@ -60,6 +60,9 @@
  *   lacx_decoder_item_bad_slices <- bringing lost bytes back: a parity sidecar ("LACR", Reed-Solomon over GF(2^8)) beside
  *                             the .lac file, made and used on the device; the manifest finds damage at the PCM level, this
  *                             sidecar locates and repairs it at the byte level
+ *   lacx_transcode_batch    <- beyond the reference (like `flac --skip / --until`, joining and `flac -f` re-encoding): .lac in,
+ *                             .lac out -- frame ranges of source streams cut and joined, re-channelled and re-quantised
+ *                             losslessly, re-encoded as one batch, the PCM never leaving the device
  *
  * All analysis (and the decode) runs in hand-written HIP kernels on a gfx950 device; there is no CPU fallback: every
  * call that needs the device fails with LACX_E_DEVICE when none is usable.
@@ -163,7 +166,7 @@ void lacx_get_timing(const lacx_encoder* enc, lacx_timing* out);
 
 /* sizeof() of a public struct as this library was built, by name without the prefix ("config", "channel_plan",
  * "block_plan", "timing", "pcm", "batch_item", "batch_out", "wav_info", "fanout_shard", "fanout_out", "fanout_stats",
- * "stream_info", "span", "decode_item", "window_item", "verify_item", "verify_result", "digest", "digest_source", "block_fault", "salvage_result", "block_digest", "manifest_info"); 0 for an unknown name.  A binding that declares the structs itself (ctypes, cgo, JNI) checks its layout
+ * "stream_info", "span", "decode_item", "window_item", "verify_item", "verify_result", "digest", "digest_source", "block_fault", "salvage_result", "block_digest", "manifest_info", "edit_segment", "edit_output", "edit_result"); 0 for an unknown name.  A binding that declares the structs itself (ctypes, cgo, JNI) checks its layout
  * against this before the first call that fills one. */
 uint32_t lacx_sizeof(const char* struct_name);
 
@@ -951,6 +954,70 @@ int lacx_recovery_repair_batch_view(lacx_decoder* dec, const lacx_span* files, c
 int lacx_recovery_repair(lacx_decoder* dec, const uint8_t* file, uint64_t size, const uint8_t* sidecar, uint64_t sidecar_size, uint32_t flags,
                          uint8_t** out, uint64_t* out_size, lacx_repair_result* result, float* device_ms);
 int lacx_decoder_item_bad_slices(const lacx_decoder* dec, uint32_t i, const uint32_t** slices, uint32_t* count);
+
+/* ---- transcode: .lac in, .lac out.  Many outputs as ONE job, each a list of frame ranges (segments) of source streams,
+ * optionally re-channelled and re-quantised losslessly, encoded as one batch; PCM never leaves the device.  out[i] is
+ * byte for byte the file LAC::Encoder::encode gives for the edited PCM: a complete version-3 .lac, malloc'd (lacx_free);
+ * a failed output gets {NULL, 0} and a zeroed result.  The encoder supplies the zero-run and partitioning switches;
+ * sample rate, depth and channels come from the sources through the output's transforms.  A version-2 source comes
+ * out as version 3.
+ * The job has two phases with one host look at the statuses between them.  Phase 1, on the decoder: one window job in
+ * the device form, every segment a window item whose arrays point into the decoder's planar int32 staging at the
+ * segment's frame offset inside its output (window semantics unchanged: only the blocks a segment overlaps are decoded,
+ * whole and checked; a segment fails if and only if one of them fails, "segment k: [decode-error] block=N ..." with the
+ * strict decode's code; damage outside the windows does not matter); then one launch, k_edit, over all outputs: the
+ * channel operation, then the depth change, both validated, into interleaved int16 / packed int24; then the PCM digest
+ * kernel over that buffer (data_crc32).  Phase 2: lacx_encode_batch_device over the outputs that survived, lacx_assemble
+ * per output, and with LACX_TRANSCODE_VERIFY the verify form on the decoder, every new stream against the buffer it was
+ * encoded from: a difference gives LACX_E_MISMATCH "[transcode-error] output does not decode to its sources: <verify
+ * text>" and no output, else verified = 1.
+ * The window job checks every decoded sample against the stream's bit depth ("sample outside the bit depth"), so what is
+ * staged always fits the source depth and no store cuts a sample off.
+ * Transforms are refused, never approximated; nothing is rounded.  24 -> 16 needs every sample of the output to be a
+ * multiple of 256 (the output sample is s >> 8); 16 -> 24 is s << 8; LACX_CH_FOLD needs left == right in every frame.  A
+ * violation fails that output with LACX_E_INVALID "[transcode-error] frame F <left|right> sample V is not a multiple of 256"
+ * or "[transcode-error] frame F: left L and right R differ": F counted in the output, the lowest frame; within a frame the
+ * channel operation comes before the depth change and left before right.
+ * Per output, on the host before any device work, each LACX_E_INVALID with the text in lacx_decoder_item_error(dec, i):
+ * "output has no segments", "segments outside the call's array", "unknown channel operation", "unsupported bit depth: B",
+ * "unknown stereo mode", "segment k: <lacx_stream_parse's text>", "segment k: empty window", "segment k: window outside
+ * the stream" (without wrap-around), "segment k: <channels|bit depth|sample rate> differs from segment 0: A, B" (A segment
+ * 0's), "channel operation needs a <stereo|mono> source"; k counts inside the output.
+ * The whole call, each LACX_E_INVALID: null arrays, nouts == 0, unknown flags, a fan-out encoder, an encoder on another
+ * device than the decoder's, and whatever lacx_encode_batch_device refuses (its text).  Without a device the host
+ * outcomes are still filled and the call returns LACX_E_DEVICE.  One failed output does not cost the others; the return
+ * code is the lowest failing output's, "output i: <message>" in lacx_decode_last_error.  Both handles are locked for the
+ * whole call (two transcode jobs that share one take turns; their other entry points take no lock).  device_ms (nullable): kernel time of phase 1 and the verification (the encode's: lacx_get_timing). */
+#define LACX_TO_END UINT64_MAX
+typedef struct lacx_edit_segment {   /* 32 bytes */
+    const uint8_t* lac; uint64_t size;   /* a source stream, version 3 or 2 */
+    uint64_t start, frames;              /* frames [start, start+frames); frames == LACX_TO_END: to the stream's end */
+} lacx_edit_segment;
+#define LACX_CH_KEEP 0u   /* channels as decoded */
+#define LACX_CH_LEFT 1u   /* stereo -> mono: left */
+#define LACX_CH_RIGHT 2u  /* stereo -> mono: right */
+#define LACX_CH_FOLD 3u   /* stereo -> mono, only if left == right in every frame */
+#define LACX_CH_SWAP 4u   /* stereo: channels exchanged */
+#define LACX_CH_DUAL 5u   /* mono -> stereo: the channel twice */
+typedef struct lacx_edit_output {    /* 16 bytes */
+    uint32_t first_segment, segments;    /* its segments, in order, in the call's segment array; >= 1 */
+    uint8_t bit_depth;                   /* 0 keep; 16 or 24 */
+    uint8_t channel_op;                  /* LACX_CH_* */
+    uint8_t stereo_mode;                 /* of the output: 0 LR, 1 MS, 2 auto; ignored for a mono output */
+    uint8_t reserved[5];
+} lacx_edit_output;
+typedef struct lacx_edit_result {    /* 40 bytes */
+    uint64_t frames, lac_bytes;
+    uint32_t blocks, data_crc32;         /* zlib CRC-32 of the output PCM as WAV data bytes (lacx_digest.data_crc32) */
+    uint32_t sample_rate;
+    uint8_t channels, bit_depth, verified, reserved;
+    uint64_t source_lac_bytes;           /* sum of its segments' stream sizes, each distinct (lac, size) once */
+} lacx_edit_result;
+#define LACX_TRANSCODE_VERIFY 1u
+int lacx_transcode_batch(lacx_decoder* dec, lacx_encoder* enc,
+                         const lacx_edit_segment* segs, uint32_t nsegs,
+                         const lacx_edit_output* outs, uint32_t nouts, uint32_t flags,
+                         lacx_span* out, int* item_rc, lacx_edit_result* results, float* device_ms);
 
 /* Block::Encoder::encode drop-in for one channel block of n <= 16384 samples of ANY int32 value: blocks inside the 25-bit
  * mid/side domain of validated 16 / 24-bit input run on the streaming kernels, wider ones on a kernel of their own that

@@ -497,7 +497,10 @@ uint32_t lacx_sizeof(const char* name) {
                  {"channel_stats", sizeof(lacx_channel_stats)}, {"block_stats", sizeof(lacx_block_stats)},
                  {"channel_totals", sizeof(lacx_channel_totals)}, {"stats", sizeof(lacx_stats)},
                  {"channel_info", sizeof(lacx_channel_info)}, {"block_info", sizeof(lacx_block_info)},
-                 {"stream_report", sizeof(lacx_stream_report)}};
+                 {"stream_report", sizeof(lacx_stream_report)}, {"edit_segment", sizeof(lacx_edit_segment)},
+                 {"edit_output", sizeof(lacx_edit_output)},     {"edit_result", sizeof(lacx_edit_result)}};
+    static_assert(sizeof(lacx_edit_segment) == 32 && sizeof(lacx_edit_output) == 16 && sizeof(lacx_edit_result) == 40,
+                  "the transcode job's records have fixed sizes (lacx.h)");
     static_assert(sizeof(lacx_channel_info) == 160 && sizeof(lacx_block_info) == 336 && sizeof(lacx_stream_report) == 456,
                   "the inspection's records have fixed sizes (lacx.h)");
     static_assert(sizeof(lacx_channel_stats) == 40 && sizeof(lacx_block_stats) == 104 && sizeof(lacx_channel_totals) == 64 &&

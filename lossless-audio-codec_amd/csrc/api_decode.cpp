@@ -35,7 +35,7 @@ void decoder_release(lacx_decoder* d) {
     if (d->e0) (void)hipEventDestroy(d->e0);
     if (d->e1) (void)hipEventDestroy(d->e1);
     if (d->stream) (void)hipStreamDestroy(d->stream);
-    for (Buf* b : {&d->pay, &d->stage, &d->pcm, &d->blocks, &d->image, &d->tables}) buf_free(*b);
+    for (Buf* b : {&d->pay, &d->stage, &d->pcm, &d->blocks, &d->image, &d->tables, &d->edit_stage, &d->edit_dst, &d->edit_tab}) buf_free(*b);
     *d = lacx_decoder{};
 }
 // lacx_decode (no handle): one decoder per device for the life of the process (never freed: releasing device memory from

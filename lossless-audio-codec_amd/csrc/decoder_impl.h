@@ -1,6 +1,8 @@
 // decoder_impl.h -- the decoder object behind lacx_decoder*, shared by the translation units of its entry points
-// (api_decode.cpp: decode, verify, digest, salvage, manifests; api_recovery.cpp: recovery data).
+// (api_decode.cpp: decode, verify, digest, salvage, manifests; api_recovery.cpp: recovery data; api_transcode.cpp).
 #pragma once
+#include <memory>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -21,6 +23,11 @@ struct lacx_decoder {
     lacx::Buf blocks{{{false, 4, "hipMalloc(status)"}, {false, 1, "hipMalloc(flags)"}, {true, 4, "hipHostMalloc(status)"}}};
     lacx::Buf image{{{false, 1, "hipMalloc(wav)"}, {true, 1, "hipHostMalloc(wav)"}}};  // WAV images (header + data + pad), host windows
     lacx::Buf tables{{{false, 1, "hipMalloc(batch tables)"}, {true, 1, "hipHostMalloc(batch tables)"}}};  // one upload (TableLayout)
+    // a transcode job (api_transcode.cpp, edit_plan.h): the planar int32 staging the window job splices the segments into;
+    // the destination k_edit writes and the encoder, the digest and the verification read; k_edit's tables
+    lacx::Buf edit_stage{{{false, 4, "hipMalloc(edit staging)"}}};
+    lacx::Buf edit_dst{{{false, 1, "hipMalloc(edit destination)"}}};
+    lacx::Buf edit_tab{{{false, 1, "hipMalloc(edit tables)"}, {true, 1, "hipHostMalloc(edit tables)"}}};
     uint8_t* d_pay() const { return static_cast<uint8_t*>(pay.part[0].p); }
     uint8_t* h_pay() const { return static_cast<uint8_t*>(stage.part[0].p); }
     int32_t* d_left() const { return static_cast<int32_t*>(pcm.part[0].p); }
@@ -45,6 +52,8 @@ struct lacx_decoder {
     uint64_t info_guard = 0, info_guard_changed = 0;         // LACX_INSPECT_GUARD: the guard bytes behind its tables, and those the job changed
     std::vector<std::vector<uint32_t>> item_bad;             // the last recovery scan / repair call's damaged slices per item
     std::string err;
+    // held by a transcode job for the whole call (the encoder has one too): its phases are calls of their own on this handle
+    std::shared_ptr<std::mutex> call_mu = std::make_shared<std::mutex>();
 };
 
 namespace lacx_host {

@@ -230,6 +230,7 @@ struct lacx_encoder {
     hipEvent_t up_ev[kMaxChunks] = {};
     std::atomic<int> up_done[kMaxChunks] = {};  // 1: the chunk's copy has been issued and its event recorded; -1: failed
     double up_ms = 0;                           // host time the uploader spent in the copies of the call
+    std::mutex call_mu;  // held by a transcode job for the whole call (api_transcode.cpp), with the decoder's
     std::string err;
     int bad_channel = -1;    // last sample-range error: 0 left / 1 right, and the sample's index in the call's input
     uint64_t bad_index = 0;  // (the fan-out rebuilds the reference's message with the stream-wide index)

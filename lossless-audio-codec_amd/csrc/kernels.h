@@ -1,9 +1,10 @@
 // kernels.h -- host-visible interface of the kernel translation units (k_front.hip, k_analyze.hip, k_emit.hip,
-// decode.hip, k_digest.hip, k_blockdigest.hip, k_stats.hip, k_inspect.hip, k_recovery.hip, wide.hip, k_import.hip).
+// decode.hip, k_digest.hip, k_blockdigest.hip, k_stats.hip, k_inspect.hip, k_recovery.hip, wide.hip, k_import.hip, k_edit.hip).
 #pragma once
 #include <cstdlib>
 #include <hip/hip_runtime_api.h>
 
+#include "edit_core.h"
 #include "import_core.h"
 #include "lacx_types.h"
 #include "recovery_core.h"
@@ -210,6 +211,10 @@ hipError_t launch_wide_block(const int32_t* d_x, uint32_t n, int zero_run, int p
 // The import pass (k_import.hip, import_core.h): every source of the job in one launch.  bad: [nitems] device words, all
 // ones on entry (ImportBad).
 hipError_t launch_import(const ImportJob& job, ImportBad* bad, hipStream_t stream);
+
+// The edit pass of a transcode job (k_edit.hip, edit_core.h): every output of the job in one launch.  bad: [nitems] device
+// words, all ones on entry (EditBad).
+hipError_t launch_edit(const EditJob& job, EditBad* bad, hipStream_t stream);
 
 size_t analyze_smem_bytes_full();
 // Diagnostic builds (-DLACX_STAMPS) only: per-phase shader-cycle sums over all waves; returns 0 otherwise.

@@ -122,7 +122,7 @@ EXPORTS = (
     "lacx_recovery_repair_batch_view", "lacx_recovery_repair", "lacx_decoder_item_bad_slices",
     "lacx_decoder_stats_batch_device", "lacx_decoder_stats_pcm_batch_device", "lacx_decoder_item_block_stats", "lacx_stats_combine",
     "lacx_decoder_inspect_batch_device", "lacx_decoder_item_block_info", "lacx_decoder_item_partitions", "lacx_inspect_combine",
-    "lacx_decoder_inspect_guard",
+    "lacx_decoder_inspect_guard", "lacx_transcode_batch",
 )
 
 
@@ -242,6 +242,8 @@ def lib():
                                                    C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint32)]
         L.lacx_decoder_inspect_guard.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.lacx_inspect_combine.argtypes = [C.POINTER(BlockInfo), C.c_uint32, C.POINTER(StreamInfo), C.POINTER(StreamReport)]
+        L.lacx_transcode_batch.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(EditSegment), C.c_uint32, C.POINTER(EditOutput), C.c_uint32,
+                                           C.c_uint32, C.POINTER(Span), C.POINTER(C.c_int), C.POINTER(EditResult), C.POINTER(C.c_float)]
         L.lacx_block_fault_text.restype = C.c_char_p
         L.lacx_block_fault_text.argtypes = [C.c_uint32]
         L.lacx_decoder_item_error.restype = C.c_char_p
@@ -270,7 +272,8 @@ def abi_structs() -> dict:
             "manifest_info": ManifestInfo, "recovery_params": RecoveryParams, "recovery_info": RecoveryInfo,
             "repair_result": RepairResult, "channel_stats": ChannelStats, "block_stats": BlockStats,
             "channel_totals": ChannelTotals, "stats": Stats, "channel_info": ChannelInfo, "block_info": BlockInfo,
-            "stream_report": StreamReport}
+            "stream_report": StreamReport, "edit_segment": EditSegment, "edit_output": EditOutput,
+            "edit_result": EditResult}
 
 
 def device_count() -> int:
@@ -1025,6 +1028,29 @@ def inspect_combine(rows, info: "StreamInfo | None" = None) -> StreamReport:
     return out
 
 
+# ---- transcode: .lac in, .lac out (lacx_transcode_batch) ----
+TO_END = (1 << 64) - 1                       # LACX_TO_END: a segment that runs to its stream's end
+CH_KEEP, CH_LEFT, CH_RIGHT, CH_FOLD, CH_SWAP, CH_DUAL = range(6)  # LACX_CH_*
+CHANNEL_OPS = {"keep": CH_KEEP, "left": CH_LEFT, "right": CH_RIGHT, "fold": CH_FOLD, "swap": CH_SWAP, "dual": CH_DUAL}
+TRANSCODE_VERIFY = 1                         # LACX_TRANSCODE_VERIFY (call flag)
+
+
+class EditSegment(C.Structure):
+    _fields_ = [("lac", C.POINTER(C.c_uint8)), ("size", C.c_uint64), ("start", C.c_uint64), ("frames", C.c_uint64)]
+
+
+class EditOutput(C.Structure):
+    _fields_ = [("first_segment", C.c_uint32), ("segments", C.c_uint32), ("bit_depth", C.c_uint8), ("channel_op", C.c_uint8),
+                ("stereo_mode", C.c_uint8), ("reserved", C.c_uint8 * 5)]
+
+
+class EditResult(C.Structure):
+    _fields_ = [("frames", C.c_uint64), ("lac_bytes", C.c_uint64), ("blocks", C.c_uint32), ("data_crc32", C.c_uint32),
+                ("sample_rate", C.c_uint32), ("channels", C.c_uint8), ("bit_depth", C.c_uint8), ("verified", C.c_uint8),
+                ("reserved", C.c_uint8), ("source_lac_bytes", C.c_uint64)]
+
+
+# ---- recovery data: the parity sidecar (lacx_recovery_*) ----
 REPAIR_TRUNCATED, REPAIR_TRAILING, REPAIR_SIDECAR_TRUNCATED, REPAIR_UNREPAIRED = 1, 2, 4, 8  # LACX_REPAIR_* (result flags)
 REPAIR_BEST_EFFORT = 1                                                                       # LACX_REPAIR_BEST_EFFORT (call flag)
 
@@ -1809,6 +1835,63 @@ class Decoder:
             err = RuntimeError(e.errors[0])
             err.result = e.results[0]
             raise err from None
+
+    def transcode_batch(self, encoder: "Encoder", outputs, verify: bool = False) -> list:
+        """.lac in, .lac out, many outputs as one device job (lacx_transcode_batch): every output is a list of frame ranges
+        of source streams, cut and joined, optionally re-channelled and re-quantised losslessly, and re-encoded by
+        `encoder` (its zero-run and partitioning switches; its format is not used: rate, depth and channels come from the
+        sources).  outputs[i]: a dict(segments=..., bit_depth=0, channels="keep", stereo_mode=2) or a tuple in that order;
+        segments: a list of .lac bytes (the whole stream) or (lac, start, frames) with frames None = to the stream's end;
+        bit_depth 0 keeps the sources', 16 / 24 change it where that loses nothing; channels: a CHANNEL_OPS name or a CH_*
+        code.  verify: every new stream is decoded again on the device and compared with what it was encoded from.
+        Returns [(bytes, EditResult)]; failed outputs raise BatchDecodeError once the others are done (errors[i] the
+        output's message, results[i] None)."""
+        if self._h is None:
+            raise RuntimeError("decoder is closed")
+        keep, segs, outs = [], [], []
+        for o in outputs:
+            if isinstance(o, dict):
+                o = (o["segments"], o.get("bit_depth", 0), o.get("channels", "keep"), o.get("stereo_mode", 2))
+            segments, depth, op, mode = (tuple(o) + (0, "keep", 2)[len(o) - 1:])[:4]
+            first = len(segs)
+            for sg in segments:
+                lac, start, frames = (sg, 0, None) if isinstance(sg, (bytes, bytearray, memoryview, np.ndarray)) else sg
+                b = np.frombuffer(lac, dtype=np.uint8)
+                keep.append(b)
+                segs.append(EditSegment(b.ctypes.data_as(C.POINTER(C.c_uint8)), b.size, int(start), TO_END if frames is None else int(frames)))
+            outs.append(EditOutput(first, len(segs) - first, int(depth or 0), CHANNEL_OPS[op] if isinstance(op, str) else int(op), int(mode)))
+        n = len(outs)
+        seg_arr = (EditSegment * max(1, len(segs)))(*segs)
+        out_arr = (EditOutput * max(1, n))(*outs)
+        spans = (Span * max(1, n))()
+        res = (EditResult * max(1, n))()
+        rc, errors = self._batch(n, lambda rcs, ms: lib().lacx_transcode_batch(
+            self._h, encoder._handle(), seg_arr, C.c_uint32(len(segs)), out_arr, C.c_uint32(n),
+            C.c_uint32(TRANSCODE_VERIFY if verify else 0), spans, rcs, res, ms))
+        results = []
+        for i in range(n):
+            if spans[i].data:
+                data = C.string_at(spans[i].data, spans[i].size)
+                lib().lacx_free(spans[i].data)
+                results.append(None if i in errors else (data, _copy_struct(res[i])))
+            else:
+                results.append(None)
+        if rc == E_INVALID and not errors:  # the whole call was refused
+            raise ValueError(lib().lacx_decode_last_error().decode(errors="replace"))
+        return self._raise_batch(rc, errors, results)
+
+    def cut(self, encoder: "Encoder", lac, start: int, frames=None, verify: bool = False) -> bytes:
+        """Frames [start, start + frames) of a .lac (frames None: to its end) as a .lac of their own."""
+        return self.transcode_batch(encoder, [([(lac, start, frames)],)], verify)[0][0]
+
+    def join(self, encoder: "Encoder", lacs, verify: bool = False) -> bytes:
+        """Streams of one format, one behind the other, as one .lac."""
+        return self.transcode_batch(encoder, [(list(lacs),)], verify)[0][0]
+
+    def recompress(self, encoder: "Encoder", lac, bit_depth: int = 0, channels="keep", stereo_mode: int = 2, verify: bool = False) -> bytes:
+        """A .lac coded again by `encoder` (a version-2 stream comes out as version 3), optionally re-channelled or
+        re-quantised where that loses nothing."""
+        return self.transcode_batch(encoder, [([lac], bit_depth, channels, stereo_mode)], verify)[0][0]
 
     def verify_wav(self, lac, wav) -> VerifyResult:
         """A .lac against the WAV file image it was made from (both in host memory): the image's data chunk goes to the

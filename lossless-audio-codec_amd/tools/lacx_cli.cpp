@@ -23,6 +23,8 @@
 // kinds of file, made on the device (lacx_decoder_stats_batch_device / lacx_decoder_stats_pcm_batch_device).
 // inspect (`flac -a` for .lac): how each stream was coded and where its bits go, read out of the bytes on the device by a
 // parse-only walk (lacx_decoder_inspect_batch_device).
+// recompress, cut, join (no counterpart in the reference's tool; `flac -f`, `--skip` / `--until` and joining, for .lac): .lac
+// in, .lac out through lacx_transcode_batch -- decoded, edited and encoded again on the device, the PCM never leaving it.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -64,6 +66,11 @@ void usage() {
                  "  lacx_cli inspect FILE... [--blocks] [--partitions]   (.lac files: predictors, residual modes and where the bits go, as\n"
                  "      integers, one line per file; --blocks: one further line per block; --partitions: and one per partition;\n"
                  "      a damaged stream prints its line with lost_blocks counted; exit 0 when every file was inspected, else 1)\n"
+                 "  lacx_cli recompress in.lac out.lac [--stereo=lr|ms|auto] [--no-zero-run] [--no-partitioning] [--depth=16|24]\n"
+                 "      [--channels=keep|left|right|fold|swap|dual] [--verify]   (coded again; depth and channels only where nothing is lost)\n"
+                 "  lacx_cli cut in.lac out.lac --start=F [--frames=N] [--verify]   (frames [F, F + N), or to the end)\n"
+                 "  lacx_cli join out.lac in1.lac in2.lac ... [--verify]   (streams of one format, one behind the other)\n"
+                 "      all three: exit 0 done, 1 mismatch under --verify, 2 refused; out.lac is written only on success\n"
                  "  lacx_cli selftest\n";
 }
 
@@ -945,6 +952,104 @@ int selftest_command() {
     return 0;
 }
 
+// recompress / cut / join: one output of lacx_transcode_batch over the input files.  Exit 0 done, 1 the new stream does not
+// decode to its sources (--verify), 2 refused; the output is published only on success.
+int transcode_command(const std::string& mode, int argc, char** argv) {
+    std::vector<std::string> in_paths;
+    std::string out_path;
+    int first_flag = 4;
+    if (mode == "join") {
+        out_path = argv[2];
+        for (first_flag = 3; first_flag < argc && std::string(argv[first_flag]).compare(0, 2, "--") != 0; ++first_flag) in_paths.push_back(argv[first_flag]);
+    } else {
+        in_paths.push_back(argv[2]);
+        out_path = argv[3];
+    }
+    lacx_edit_output o{};
+    o.stereo_mode = 2;
+    uint64_t start = 0, frames = LACX_TO_END;
+    bool verify = false, zero_run = true, partitioning = true, have_start = false;
+    const bool re = mode == "recompress", cut = mode == "cut";
+    auto number = [](const std::string& v, uint64_t& out) {
+        if (v.empty() || v.size() > 18) return false;
+        for (char c : v)
+            if (c < '0' || c > '9') return false;
+        out = std::stoull(v);
+        return true;
+    };
+    for (int i = first_flag; i < argc; ++i) {
+        const std::string flag = argv[i];
+        static const char* const kOps[] = {"keep", "left", "right", "fold", "swap", "dual"};
+        bool ok = flag == "--verify";
+        if (ok) verify = true;
+        if (re && flag == "--stereo=lr") ok = true, o.stereo_mode = 0;
+        if (re && flag == "--stereo=ms") ok = true, o.stereo_mode = 1;
+        if (re && flag == "--stereo=auto") ok = true, o.stereo_mode = 2;
+        if (re && flag == "--no-zero-run") ok = true, zero_run = false;
+        if (re && flag == "--no-partitioning") ok = true, partitioning = false;
+        if (re && flag == "--depth=16") ok = true, o.bit_depth = 16;
+        if (re && flag == "--depth=24") ok = true, o.bit_depth = 24;
+        for (uint8_t c = 0; re && c < 6; ++c)
+            if (flag == std::string("--channels=") + kOps[c]) ok = true, o.channel_op = c;
+        if (cut && flag.compare(0, 8, "--start=") == 0) ok = have_start = number(flag.substr(8), start);
+        if (cut && flag.compare(0, 9, "--frames=") == 0) ok = number(flag.substr(9), frames);
+        if (!ok) {
+            usage();
+            return 2;
+        }
+    }
+    if (in_paths.empty() || (cut && !have_start)) {
+        usage();
+        return 2;
+    }
+    std::vector<std::vector<uint8_t>> files(in_paths.size());
+    std::vector<lacx_edit_segment> segs;
+    for (size_t i = 0; i < in_paths.size(); ++i) {
+        if (same_file(in_paths[i], out_path)) {
+            std::cerr << "Input and output paths must be different\n";
+            return 2;
+        }
+        if (!load_file(in_paths[i], files[i])) {
+            std::cerr << "Failed to read LAC file: " << in_paths[i] << "\n";
+            return 2;
+        }
+        segs.push_back(lacx_edit_segment{files[i].data(), files[i].size(), start, frames});
+    }
+    o.first_segment = 0;
+    o.segments = (uint32_t)segs.size();
+    lacx_config cfg{};
+    cfg.sample_rate = 48000;  // (the outputs' formats come from their sources)
+    cfg.bit_depth = 16;
+    cfg.zero_run_enabled = zero_run ? 1 : 0;
+    cfg.partitioning_enabled = partitioning ? 1 : 0;
+    cfg.device = -1;
+    lacx_encoder* enc = nullptr;
+    lacx_decoder* dec = nullptr;
+    if (lacx_encoder_create(&cfg, &enc) != LACX_OK || lacx_decoder_create(-1, &dec) != LACX_OK) {
+        std::cerr << "Error: cannot create the encoder and the decoder\n";
+        if (enc) lacx_encoder_destroy(enc);
+        return 2;
+    }
+    lacx_span out{};
+    lacx_edit_result res{};
+    const int rc = lacx_transcode_batch(dec, enc, segs.data(), (uint32_t)segs.size(), &o, 1, verify ? LACX_TRANSCODE_VERIFY : 0u, &out, nullptr, &res, nullptr);
+    int status = rc == LACX_OK ? 0 : rc == LACX_E_MISMATCH ? 1 : 2;
+    if (status == 2) std::cerr << (rc == LACX_E_INVALID ? "Refused: " : "Error: ") << lacx_decode_last_error() << "\n";  // (no device, a failed decode)
+    if (status == 1) std::cerr << "Verify failed: " << lacx_decode_last_error() << "\n";
+    if (status == 0 && !save_file(out_path, out.data, out.size)) {
+        std::cerr << "Failed to write LAC file: " << out_path << "\n";
+        status = 2;
+    }
+    if (status == 0)
+        std::cout << (re ? "Recompressed " : cut ? "Cut " : "Joined ") << res.frames << " frames, " << (int)res.channels << " ch, " << (int)res.bit_depth << " bit, "
+                  << res.sample_rate << " Hz: " << res.source_lac_bytes << " -> " << res.lac_bytes << " bytes, data_crc32=" << std::hex << res.data_crc32 << std::dec
+                  << (res.verified ? ", verified" : "") << " -> " << out_path << "\n";
+    if (out.data) lacx_free(const_cast<uint8_t*>(out.data));
+    lacx_decoder_destroy(dec);
+    lacx_encoder_destroy(enc);
+    return status;
+}
+
 struct Encoded {
     const uint8_t* data = nullptr;
     uint64_t size = 0;
@@ -963,6 +1068,7 @@ int main(int argc, char** argv) {
     if (mode == "check" && argc == 4) return check_command(argv);
     if (mode == "protect" && argc >= 4) return protect_command(argc, argv);
     if (mode == "repair" && argc >= 5) return repair_command(argc, argv);
+    if ((mode == "recompress" || mode == "cut" || mode == "join") && argc >= 4) return transcode_command(mode, argc, argv);
     if (argc < 4 || (mode != "encode" && mode != "decode")) {
         usage();
         return 1;
