@@ -55,6 +55,9 @@
  *   lacx_decoder_inspect_batch_device, lacx_decoder_item_block_info, lacx_decoder_item_partitions,
  *   lacx_inspect_combine, lacx_decoder_inspect_guard <- how a stream was coded and where its bits go: per block and per stream predictors, partition
  *                             orders, residual modes, bit and sample classes, read by a parse-only walk on the device
+ *   lacx_decoder_runs_batch_device, lacx_decoder_runs_pcm_batch_device,
+ *   lacx_decoder_item_runs  <- where the audio is silent, clips or holds one value: runs of consecutive frames that satisfy
+ *                             a detector and reach a minimum length, found on the device
  *   lacx_recovery_build, lacx_recovery_build_batch_view, lacx_recovery_parse,
  *   lacx_recovery_scan_batch, lacx_recovery_repair, lacx_recovery_repair_batch_view,
  *   lacx_decoder_item_bad_slices <- bringing lost bytes back: a parity sidecar ("LACR", Reed-Solomon over GF(2^8)) beside
@@ -868,6 +871,80 @@ int lacx_inspect_combine(const lacx_block_info* rows, uint32_t count, const lacx
  * back behind them: *guarded = its bytes in the decoder's last inspection call (0: no guard), *changed = those that no
  * longer hold the pattern.  A call that changed any fails as a whole with LACX_E_DEVICE. */
 int lacx_decoder_inspect_guard(const lacx_decoder* dec, uint64_t* guarded, uint64_t* changed);
+
+/* Runs: WHERE a stream is silent, clips or holds one value.  The statistics say whether and how often, one row per block;
+ * these entry points give the intervals: "the pause runs from frame 1 234 567 to 1 301 222", "right clips for 37
+ * consecutive samples at 0:41.3", "one value was held for 2 000 samples here".  The minimum-length filter runs on the device
+ * where the samples lie (ordinary music crosses any small threshold at every zero crossing); what comes back is the runs
+ * and a small row per tile of 1024 frames, not the PCM.  Everything is an exact integer; there is no tolerance anywhere.
+ * A detector is {kind, channel, level, min_frames}.  channel: 0 (left), 1 (right) or LACX_RUN_ALL -- every channel of the
+ *   item must satisfy the predicate in that frame; a detector on channel 1 finds nothing in a mono item.  min_frames >= 1.
+ *   Samples x are the final left / right integers of the item's bit depth b, `level` is in those units (so a mixed batch
+ *   carries its detectors per item: lacx_run_query says which of the call's detectors are the item's, like
+ *   lacx_edit_output's segments; at most LACX_MAX_DETECTORS).  The frame predicate P(f):
+ *   LACX_RUN_QUIET: -level <= x <= level for every selected channel (level 0: digital silence);
+ *   LACX_RUN_PEAK:  x >= level or x <= -level - 1 for every selected channel (level 2^(b-1)-1: the statistics' full_scale);
+ *   LACX_RUN_FLAT:  f >= 1, frame f - 1 is counted, and x[f] == x[f-1] for every selected channel; level must be 0.  A
+ *                   stretch of N equal samples is N - 1 flagged frames.
+ *   A frame of a lost or missing block satisfies no predicate and the first frame behind such a block is never FLAT: a
+ *   lost block splits a run.
+ * A run is a maximal interval [start, start + frames) of consecutive frames with P true, reported if and only if
+ *   frames >= min_frames.  Per (item, detector): the complete list of runs ascending by start (lacx_decoder_item_runs;
+ *   never truncated) and the totals lacx_run_totals: runs, frames (in runs), longest and longest_start (the lowest start
+ *   among equals).
+ * lacx_runs_result, per item: frames, lost_frames, blocks, lost_blocks as a salvage reports them; flags: LACX_RUNS_RERUN --
+ *   the interior runs outgrew the list the plan reserves (min((frames + 1) / (min_frames + 1), R) entries per detector,
+ *   R = 8192, or LACX_RUNS_LIST_CAP in the environment at lacx_decoder_create) and the kernel ran once more with the exact
+ *   capacities its counters gave; det[k]: the totals of the item's k-th detector.
+ * lacx_decoder_runs_batch_device: lenient exactly like lacx_decoder_stats_batch_device -- versions 3 and 2, truncated
+ *   files, LACX_OK whenever the container is accepted; a refused container keeps the strict code and text and gets a
+ *   zeroed result.  out: nullable array of n.
+ * lacx_decoder_runs_pcm_batch_device: device-resident source PCM in any LACX_PCM_* layout; the per-item host checks, the
+ *   device-found validation texts and the bounds are those of lacx_decoder_stats_pcm_batch_device.  A failed item gets a
+ *   zeroed result and no runs.
+ * Host checks of an item's detectors, each LACX_E_INVALID with its text in lacx_decoder_item_error: "detectors outside
+ *   the call's array", "too many detectors", "item has no detectors", "unknown detector kind", "unknown detector
+ *   channel", "detector needs min_frames >= 1", "flat detector takes no level".  A null detector array or ndets == 0 fails
+ *   the whole call.
+ * lacx_decoder_item_runs: the runs of detector `detector` of item `item` of the decoder's last runs call, valid until its
+ *   next call; LACX_E_INVALID outside that call.
+ * Everything else as lacx_decoder_decode_batch_device: the return code, "stream i: " prefixes, lacx_decoder_item_error,
+ * n = 0, device-less behaviour (host-side outcomes filled, then LACX_E_DEVICE) and `stream`.
+ * Time (scripts/runs_bench.py, profiles/runs_bench.txt): on 48 four-minute stereo streams as one job with three
+ * detectors 39.6 ms of kernels, 2.6 ms below the stats job; k_runs alone 3.4 ms for 4.06 GB of PCM. */
+#define LACX_RUN_QUIET 0u
+#define LACX_RUN_PEAK  1u
+#define LACX_RUN_FLAT  2u
+#define LACX_RUN_ALL   255u
+#define LACX_MAX_DETECTORS 8u            /* per item */
+typedef struct lacx_run_detector { /* 16 bytes */
+    uint8_t kind, channel, reserved[2];
+    uint32_t level;
+    uint64_t min_frames;
+} lacx_run_detector;
+typedef struct lacx_run_query {    /* 8 bytes: detectors first_detector .. first_detector + detectors - 1 of the call's array */
+    uint32_t first_detector, detectors;
+} lacx_run_query;
+typedef struct lacx_run {          /* 16 bytes */
+    uint64_t start, frames;
+} lacx_run;
+typedef struct lacx_run_totals {   /* 32 bytes */
+    uint64_t runs, frames, longest, longest_start;
+} lacx_run_totals;
+typedef struct lacx_runs_result {  /* 296 bytes, per item */
+    uint64_t frames, lost_frames;
+    uint32_t sample_rate, blocks, lost_blocks, flags;
+    uint8_t channels, bit_depth, detectors, reserved[5];
+    lacx_run_totals det[LACX_MAX_DETECTORS];
+} lacx_runs_result;
+#define LACX_RUNS_RERUN 1u
+int lacx_decoder_runs_batch_device(lacx_decoder* dec, const lacx_span* lacs, const lacx_run_query* queries, uint32_t n,
+                                   const lacx_run_detector* dets, uint32_t ndets, void* stream, int* item_rc, lacx_runs_result* out,
+                                   float* device_ms);
+int lacx_decoder_runs_pcm_batch_device(lacx_decoder* dec, const lacx_digest_source* src, const lacx_run_query* queries, uint32_t n,
+                                       const lacx_run_detector* dets, uint32_t ndets, void* stream, int* item_rc, lacx_runs_result* out,
+                                       float* device_ms);
+int lacx_decoder_item_runs(const lacx_decoder* dec, uint32_t item, uint32_t detector, const lacx_run** runs, uint64_t* count);
 
 /* Recovery data: repairing a damaged .lac file from a parity sidecar.  Digests, salvage and the manifest all end in "this
  * block is lost"; the container has no redundancy of its own.  A recovery sidecar ("LACR") kept beside the file brings the

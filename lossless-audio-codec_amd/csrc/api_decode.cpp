@@ -7,6 +7,7 @@
 #include "import_msg.h"
 #include "inspect_plan.h"
 #include "inspect_rows.h"
+#include "runs_rows.h"
 #include "stats_rows.h"
 
 // (the entry points are declared extern "C" in lacx.h)
@@ -35,7 +36,7 @@ void decoder_release(lacx_decoder* d) {
     if (d->e0) (void)hipEventDestroy(d->e0);
     if (d->e1) (void)hipEventDestroy(d->e1);
     if (d->stream) (void)hipStreamDestroy(d->stream);
-    for (Buf* b : {&d->pay, &d->stage, &d->pcm, &d->blocks, &d->image, &d->tables, &d->edit_stage, &d->edit_dst, &d->edit_tab}) buf_free(*b);
+    for (Buf* b : {&d->pay, &d->stage, &d->pcm, &d->blocks, &d->image, &d->tables, &d->edit_stage, &d->edit_dst, &d->edit_tab, &d->runs_list}) buf_free(*b);
     *d = lacx_decoder{};
 }
 // lacx_decode (no handle): one decoder per device for the life of the process (never freed: releasing device memory from
@@ -53,6 +54,7 @@ int lacx_decoder_create(int device, lacx_decoder** out) {
     if (!out) return LACX_E_INVALID;
     lacx_decoder* d = new lacx_decoder();
     d->device = device;
+    if (const char* cap = std::getenv("LACX_RUNS_LIST_CAP")) d->runs_list_cap = std::strtoull(cap, nullptr, 10);
     *out = d;
     return LACX_OK;
 }
@@ -107,6 +109,8 @@ struct DecodeJob {
     bool check = false;                  // ... as a question: a fault or a truncation fails the item with LACX_E_MISMATCH
     bool stats = false;                  // salvage in the blocks form with the statistics kernel (DecodePlan::stats)
     lacx_stats* stres = nullptr;         // stats: [n]
+    bool runs = false;                   // salvage in the blocks form with the run finder (DecodePlan::runs); detectors in BatchIn
+    lacx_runs_result* rres = nullptr;    // runs: [n]
 };
 static_assert(sizeof(StatsAcc) == kStatsRowBytes, "the plan lays the accumulator rows out kStatsRowBytes apart");
 
@@ -168,6 +172,41 @@ DevErr decoder_open(lacx_decoder* d, int* prev_device) {  // *prev_device: to pu
 }
 }  // namespace lacx_host
 namespace {
+
+// What k_runs left, once the stream is idle: the lists' counters and the rows lie in h_meta (the caller copied the tables'
+// tail back, or does it here: `y.lists` to the tables' end).  Where a counter outgrew its list the lists are laid out
+// once more with exactly the capacities the counters gave, `again` launches the kernel over the same PCM, and *rerun is
+// set.  Then the stored entries of every list come back into d->runs_host, list by list.
+template <typename Again>
+DevErr runs_fetch(lacx_decoder* d, RunsLayout& y, hipStream_t st, Again again, bool* rerun) {
+    uint8_t* h = d->h_meta();
+    const size_t tail = y.size - y.lists;
+    auto back = [&] {
+        if (DevErr e = chk(hipMemcpyAsync(h + y.lists, d->d_meta() + y.lists, tail, hipMemcpyDeviceToHost, st), "D2H run rows")) return e;
+        return chk(hipStreamSynchronize(st), "synchronize");
+    };
+    if (DevErr e = back()) return e;
+    *rerun = runs_overflowed(y, h);
+    if (*rerun) {
+        runs_recap(y, h);
+        if (DevErr e = buf_grow(d->runs_list, y.list_entries, 64)) return e;
+        if (DevErr e = chk(hipMemcpyAsync(d->d_meta() + y.lists, h + y.lists, sizeof(RunsList) * (size_t)y.total_dets, hipMemcpyHostToDevice, st), "H2D run lists"))
+            return e;
+        if (DevErr e = chk(again(d->runs_list.as<lacx_run>()), "runs launch")) return e;
+        if (DevErr e = back()) return e;
+    }
+    const auto* lists = reinterpret_cast<const RunsList*>(h + y.lists);
+    d->runs_host.assign((size_t)y.list_entries, lacx_run{});
+    for (uint64_t q = 0; q < y.total_dets; ++q) {
+        const uint64_t stored = lists[q].count < lists[q].cap ? lists[q].count : lists[q].cap;
+        if (stored)
+            if (DevErr e = chk(hipMemcpyAsync(d->runs_host.data() + lists[q].off, d->runs_list.as<lacx_run>() + lists[q].off, sizeof(lacx_run) * (size_t)stored,
+                                              hipMemcpyDeviceToHost, st),
+                               "D2H runs"))
+                return e;
+    }
+    return chk(hipStreamSynchronize(st), "synchronize");
+}
 
 // The plan's capacities, each buffer with its own slack: the image buffer and the PCM buffers grow to what is asked.
 DevErr ensure_capacities(lacx_decoder* d, const DecodePlan& plan) {
@@ -234,13 +273,15 @@ DevErr upload_payload(lacx_decoder* d, const DecodeJob& job, const DecodePlan& p
 }
 
 // The kernels between the decoder's two events, then what every form reads back, and the wait for it.
-DevErr launch_and_wait(lacx_decoder* d, const DecodeJob& job, const DecodePlan& plan, hipStream_t st) {
+DevErr launch_and_wait(lacx_decoder* d, const DecodeJob& job, const DecodePlan& plan, hipStream_t st, bool* runs_rerun) {
     const DecodeArgs a = plan_args(plan, d->d_meta(), d->d_pay(), d->d_status(), d->d_ms());
     const size_t res = plan.at.res, m = plan.items.size();
     if (DevErr e = chk(hipEventRecord(d->e0, st), "event record")) return e;
     if (DevErr e = chk(launch_decode(a, st), "decode launch")) return e;
     if (plan.stats)  // behind k_ms_inverse, every block's status final: the slot k_digest_blocks has in a digest job
         if (DevErr e = chk(launch_stats_blocks(plan_stats_args(plan, a, d->d_meta()), st), "stats launch")) return e;
+    if (plan.runs)  // in the same slot
+        if (DevErr e = chk(launch_runs(plan_runs_args(plan, a, d->d_meta(), d->runs_list.as<lacx_run>()), st), "runs launch")) return e;
     if (DevErr e = chk(hipEventRecord(d->e1, st), "event record")) return e;
     if (DevErr e = chk(hipMemcpyAsync(d->h_status(), d->d_status(), (size_t)plan.total_blocks * sizeof(uint32_t), hipMemcpyDeviceToHost, st), "D2H status"))
         return e;
@@ -268,12 +309,22 @@ DevErr launch_and_wait(lacx_decoder* d, const DecodeJob& job, const DecodePlan& 
             return e;
     if (DevErr e = chk(hipStreamSynchronize(st), "synchronize")) return e;
     if (job.device_ms) (void)hipEventElapsedTime(job.device_ms, d->e0, d->e1);
+    if (plan.runs) {
+        RunsLayout y = plan.runs_at;
+        y.list_entries = plan.need.runs_list;
+        const RunsArgs r = plan_runs_args(plan, a, d->d_meta(), nullptr);
+        return runs_fetch(d, y, st, [&](lacx_run* list) {
+            RunsArgs again = r;
+            again.runs = list;
+            return launch_runs(again, st);
+        }, runs_rerun);
+    }
     return DevErr{};
 }
 
 // Per item: its first failing block, else what its form gives back.
 DevErr collect(lacx_decoder* d, const DecodeJob& job, const DecodePlan& plan, hipStream_t st, std::vector<int>& code,
-               std::vector<std::string>& err) {
+               std::vector<std::string>& err, bool runs_rerun) {
     const bool host = plan.form == DecodeForm::host;
     for (size_t j = 0; j < plan.items.size(); ++j) {
         const PlanItem& p = plan.items[j];
@@ -287,6 +338,13 @@ DevErr collect(lacx_decoder* d, const DecodeJob& job, const DecodePlan& plan, hi
                 std::vector<lacx_block_stats>& rows = d->item_stats[i];
                 stats_rows_of_decoded(x.lac, p.info.version, p.item.blocks, p.info.channels, d->item_faults[i], acc, rows);
                 if (job.stres) job.stres[i] = stats_combine(rows.data(), (uint32_t)rows.size(), p.info.channels, p.info.bit_depth, p.info.sample_rate);
+            }
+            if (plan.runs) {  // the lists: stitched from the rows, merged with what the kernel appended
+                lacx_runs_result res = runs_item_result(plan.runs_at, d->h_meta(), d->runs_host.data(), j, p.item.frames, d->item_runs[i]);
+                res.lost_frames = r.lost_frames, res.sample_rate = p.info.sample_rate, res.blocks = r.blocks, res.lost_blocks = r.bad_blocks;
+                res.flags = runs_rerun ? LACX_RUNS_RERUN : 0u;
+                res.channels = p.info.channels, res.bit_depth = p.info.bit_depth;
+                if (job.rres) job.rres[i] = res;
             }
             if (plan.blocks) {  // the rows: every block's frames and, where it decoded, its finished CRC-32
                 const uint32_t* raw = reinterpret_cast<const uint32_t*>(d->h_meta() + plan.at.raw) + p.item.block0;
@@ -363,10 +421,13 @@ int decode_batch_run(lacx_decoder* d, const DecodeJob& job, std::vector<int>& co
     if (job.blocks) d->item_rows.assign(job.n, {});
     if (job.stres) std::memset(job.stres, 0, sizeof(lacx_stats) * job.n);
     if (job.stats) d->item_stats.assign(job.n, {});
+    if (job.rres) std::memset(job.rres, 0, sizeof(lacx_runs_result) * job.n);
+    if (job.runs) d->item_runs.assign(job.n, {});
     // LACX_DECODE_BATCH_PAD=1 (tuning knob, read per call): every item's blocks start a new wave
     const char* pad_env = std::getenv("LACX_DECODE_BATCH_PAD");
     DecodePlan plan;
-    const char* whole = plan_decode(job.in, job.n, job.form, job.sample_type, pad_env && pad_env[0] == '1', plan, code, err, job.salvage, job.blocks, job.stats);
+    const char* whole = plan_decode(job.in, job.n, job.form, job.sample_type, pad_env && pad_env[0] == '1', plan, code, err, job.salvage, job.blocks, job.stats,
+                                    job.runs, d->runs_list_cap ? d->runs_list_cap : kRunsListCap);
     if (lacx_device_count() <= 0) whole = "no usable HIP device";
     int rc = whole ? decode_fail(LACX_E_DEVICE, whole) : LACX_OK;
     if (!whole && !plan.items.empty()) {
@@ -377,8 +438,10 @@ int decode_batch_run(lacx_decoder* d, const DecodeJob& job, std::vector<int>& co
         if (!e) e = ensure_capacities(d, plan);
         if (!e) e = upload_tables(d, job, plan, st);
         if (!e) e = upload_payload(d, job, plan, st);
-        if (!e) e = launch_and_wait(d, job, plan, st);
-        if (!e) e = collect(d, job, plan, st, code, err);
+        bool runs_rerun = false;
+        if (!e && plan.runs) e = buf_grow(d->runs_list, plan.need.runs_list, plan.need.runs_list / 8 + 64);
+        if (!e) e = launch_and_wait(d, job, plan, st, &runs_rerun);
+        if (!e) e = collect(d, job, plan, st, code, err, runs_rerun);
         if (prev_device >= 0) (void)hipSetDevice(prev_device);
         if (e) rc = decode_fail(LACX_E_DEVICE, std::string(e.what) + ": " + hipGetErrorString(e.e));
     }
@@ -388,6 +451,8 @@ int decode_batch_run(lacx_decoder* d, const DecodeJob& job, std::vector<int>& co
         if (job.blocks) d->item_rows.assign(job.n, {});
         if (job.stats) d->item_stats.assign(job.n, {});
         if (job.stres) std::memset(job.stres, 0, sizeof(lacx_stats) * job.n);
+        if (job.runs) d->item_runs.assign(job.n, {});
+        if (job.rres) std::memset(job.rres, 0, sizeof(lacx_runs_result) * job.n);
         if (job.dres) std::memset(job.dres, 0, sizeof(lacx_digest) * job.n);
         for (uint32_t i = 0; i < job.n; ++i) {
             if (code[i] != LACX_OK) continue;
@@ -613,9 +678,18 @@ const char* check_digest_source(const lacx_digest_source& x, std::string& text) 
 // | block_off [m + 1] | raw [blocks], and every item's rows are left in d->item_rows.
 // stats (with a grid): the audio statistics on that grid instead (k_stats_blocks) -- in place of the raw words the
 // accumulator rows | acc [blocks] (StatsAcc, 16-byte aligned, zeroed), the rows left in d->item_stats, the totals in sout.
+// runs (without a grid): the run finder instead (k_runs) -- behind bad [m] the tables of runs_plan.h (16-byte aligned), the
+// lists in the decoder's list buffer, every item's lists left in d->item_runs, the totals in runs->out.
+struct RunsPcm {
+    std::vector<BatchIn> in;  // per item its detectors, or why they are refused (BatchIn::dets, ndet, dets_why)
+    lacx_runs_result* out;
+};
 int digest_pcm_run(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, hipStream_t st, lacx_digest* out, float* device_ms,
-                   std::vector<int>& code, std::vector<std::string>& err, uint32_t grid = 0, bool stats = false, lacx_stats* sout = nullptr) {
+                   std::vector<int>& code, std::vector<std::string>& err, uint32_t grid = 0, bool stats = false, lacx_stats* sout = nullptr,
+                   const RunsPcm* runs = nullptr) {
     if (device_ms) *device_ms = 0.f;
+    if (runs && runs->out) std::memset(runs->out, 0, sizeof(lacx_runs_result) * n);
+    if (runs) d->item_runs.assign(n, {});
     if (out) std::memset(out, 0, sizeof(lacx_digest) * n);
     if (sout) std::memset(sout, 0, sizeof(lacx_stats) * n);
     code.assign(n, LACX_OK);
@@ -623,7 +697,9 @@ int digest_pcm_run(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, h
     std::vector<uint32_t> went;  // the items that go to the device
     for (uint32_t i = 0; i < n; ++i) {
         std::string text;
-        if (const char* why = check_digest_source(src[i], text)) {
+        const char* why = check_digest_source(src[i], text);
+        if (!why && runs) why = runs->in[i].dets_why;
+        if (why) {
             code[i] = LACX_E_INVALID;
             err[i] = why;
         } else {
@@ -640,11 +716,21 @@ int digest_pcm_run(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, h
     if (rc == LACX_OK && m) {
         const size_t at_off = sizeof(DigestSource) * m, at_res = at_off + 8 * (m + 1), at_bad = at_res + sizeof(DigestWords) * m,
                      at_blk = at_bad + 8 * m, at_raw = stats ? plan_detail::up16(at_blk + 8 * (m + 1)) : at_blk + (grid ? 8 * (m + 1) : 0),
-                     size = at_raw + (stats ? sizeof(StatsAcc) : 4) * (size_t)nblocks;
+                     size0 = at_raw + (stats ? sizeof(StatsAcc) : 4) * (size_t)nblocks;
+        std::vector<RunsIn> rin;
+        for (size_t j = 0; runs && j < m; ++j) rin.push_back(RunsIn{runs->in[went[j]].dets, runs->in[went[j]].ndet, src[went[j]].frames});
+        RunsLayout y = runs ? runs_layout(plan_detail::up16(at_blk), rin.data(), m) : RunsLayout{};
+        const size_t size = runs ? y.size : size0;
         int prev_device = -1;
         DevErr e = decoder_open(d, &prev_device);
+        if (!e && y.total_tiles >= (1ull << 31)) rc = decode_fail(LACX_E_DEVICE, "batch holds 2^31 tiles or more");
         if (!e) e = buf_grow(d->tables, size, size / 8 + 256);
-        if (!e) {
+        if (!e && runs && rc == LACX_OK) {
+            runs_fill(y, rin.data(), m, d->runs_list_cap ? d->runs_list_cap : kRunsListCap, d->h_meta());
+            e = buf_grow(d->runs_list, y.list_entries, y.list_entries / 8 + 64);
+        }
+        bool runs_rerun = false;
+        if (!e && rc == LACX_OK) {
             auto* hs = reinterpret_cast<DigestSource*>(d->h_meta());
             auto* unit_off = reinterpret_cast<unsigned long long*>(d->h_meta() + at_off);
             auto* block_off = reinterpret_cast<unsigned long long*>(d->h_meta() + at_blk);
@@ -681,16 +767,27 @@ int digest_pcm_run(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, h
             sa.grid = grid;
             sa.block_off = ba.block_off;
             sa.rows = reinterpret_cast<StatsAcc*>(d->d_meta() + at_raw);
-            if (!e) e = stats ? chk(launch_stats_pcm_blocks(sa, st), "stats launch") : chk(grid ? launch_digest_pcm_blocks(ba, st) : launch_digest_pcm(a, st), "digest launch");
+            RunsArgs ra;
+            if (runs) {
+                runs_args(y, m, d->d_meta(), d->runs_list.as<lacx_run>(), ra);
+                ra.src = a.src;
+                ra.bad = a.bad;
+            }
+            if (!e) e = runs ? chk(launch_runs_pcm(ra, st), "runs launch") : stats ? chk(launch_stats_pcm_blocks(sa, st), "stats launch") : chk(grid ? launch_digest_pcm_blocks(ba, st) : launch_digest_pcm(a, st), "digest launch");
             if (!e) e = chk(hipEventRecord(d->e1, st), "event record");
-            if (!e) e = chk(hipMemcpyAsync(d->h_meta() + at_res, d->d_meta() + at_res, size - at_res, hipMemcpyDeviceToHost, st), "D2H digests");
+            if (!e) e = chk(hipMemcpyAsync(d->h_meta() + at_res, d->d_meta() + at_res, (runs ? at_blk : size) - at_res, hipMemcpyDeviceToHost, st), "D2H digests");
             if (!e) e = chk(hipStreamSynchronize(st), "synchronize");
             if (!e && device_ms) (void)hipEventElapsedTime(device_ms, d->e0, d->e1);
+            if (!e && runs)
+                e = runs_fetch(d, y, st, [&](lacx_run* list) {
+                    ra.runs = list;
+                    return launch_runs_pcm(ra, st);
+                }, &runs_rerun);
         }
         if (prev_device >= 0) (void)hipSetDevice(prev_device);
         if (e) {
             rc = decode_fail(LACX_E_DEVICE, std::string(e.what) + ": " + hipGetErrorString(e.e));
-        } else {
+        } else if (rc == LACX_OK) {
             for (size_t j = 0; j < m; ++j) {
                 const uint32_t i = went[j];
                 const lacx_digest_source& x = src[i];
@@ -702,6 +799,14 @@ int digest_pcm_run(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, h
                     unsigned long long index = 0;
                     (void)import_bad_message(b, x.bit_depth, &ch, &index, err[i]);
                     code[i] = LACX_E_INVALID;
+                    continue;
+                }
+                if (runs) {
+                    lacx_runs_result res = runs_item_result(y, d->h_meta(), d->runs_host.data(), j, x.frames, d->item_runs[i]);
+                    res.sample_rate = x.sample_rate, res.blocks = (uint32_t)((x.frames + kMaxBlock - 1u) / kMaxBlock);
+                    res.flags = runs_rerun ? LACX_RUNS_RERUN : 0u;
+                    res.channels = (uint8_t)x.pcm.channels, res.bit_depth = x.bit_depth;
+                    if (runs->out) runs->out[i] = res;
                     continue;
                 }
                 if (stats) {
@@ -729,6 +834,8 @@ int digest_pcm_run(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, h
         if (grid && !stats) d->item_rows.assign(n, {});
         if (stats) d->item_stats.assign(n, {});
         if (sout) std::memset(sout, 0, sizeof(lacx_stats) * n);
+        if (runs) d->item_runs.assign(n, {});
+        if (runs && runs->out) std::memset(runs->out, 0, sizeof(lacx_runs_result) * n);
         for (uint32_t i = 0; i < n; ++i) {
             if (code[i] != LACX_OK) continue;
             code[i] = rc;
@@ -1066,6 +1173,58 @@ int lacx_inspect_combine(const lacx_block_info* rows, uint32_t count, const lacx
     if (out) std::memset(out, 0, sizeof(*out));
     if (!out || (!rows && count)) return decode_fail(LACX_E_INVALID, "null argument");
     *out = inspect_combine(rows, count, info);
+    return LACX_OK;
+}
+
+// ---- runs (lacx.h) ----
+namespace {
+// every item's lacx_run_query resolved against the call's detectors (BatchIn::dets, ndet, dets_why)
+void resolve_queries(const lacx_run_query* queries, const lacx_run_detector* dets, uint32_t ndets, std::vector<BatchIn>& in) {
+    for (size_t i = 0; i < in.size(); ++i) {
+        in[i].dets_why = check_detectors(queries[i], dets, ndets);
+        if (!in[i].dets_why) in[i].dets = dets + queries[i].first_detector, in[i].ndet = queries[i].detectors;
+    }
+}
+}  // namespace
+
+int lacx_decoder_runs_batch_device(lacx_decoder* d, const lacx_span* lacs, const lacx_run_query* queries, uint32_t n, const lacx_run_detector* dets,
+                                   uint32_t ndets, void* stream, int* item_rc, lacx_runs_result* out, float* device_ms) {
+    if (!d) return decode_fail(LACX_E_INVALID, "null decoder");
+    if (!lacs || !queries || n == 0) return decode_fail(LACX_E_INVALID, "null argument or empty batch");
+    if (!dets || ndets == 0) return decode_fail(LACX_E_INVALID, "no detectors");
+    std::vector<BatchIn> in(n);
+    for (uint32_t i = 0; i < n; ++i) in[i] = BatchIn{lacs[i].data, lacs[i].size, nullptr, nullptr, 0};
+    resolve_queries(queries, dets, ndets, in);
+    DecodeJob job = salvage_job(DecodeForm::blocks, static_cast<hipStream_t>(stream), nullptr, nullptr, device_ms);
+    job.in = in.data();
+    job.n = n;
+    job.runs = true;
+    job.rres = out;
+    return run_batch(d, job, item_rc);
+}
+
+int lacx_decoder_runs_pcm_batch_device(lacx_decoder* d, const lacx_digest_source* src, const lacx_run_query* queries, uint32_t n,
+                                       const lacx_run_detector* dets, uint32_t ndets, void* stream, int* item_rc, lacx_runs_result* out,
+                                       float* device_ms) {
+    if (!d) return decode_fail(LACX_E_INVALID, "null decoder");
+    if (!src || !queries || n == 0) return decode_fail(LACX_E_INVALID, "null argument or empty batch");
+    if (!dets || ndets == 0) return decode_fail(LACX_E_INVALID, "no detectors");
+    RunsPcm runs{std::vector<BatchIn>(n, BatchIn{nullptr, 0, nullptr, nullptr, 0}), out};
+    resolve_queries(queries, dets, ndets, runs.in);
+    std::vector<int> code;
+    std::vector<std::string> err;
+    const int rc = digest_pcm_run(d, src, n, static_cast<hipStream_t>(stream), nullptr, device_ms, code, err, 0, false, nullptr, &runs);
+    return batch_outcome(d, rc, code, err, item_rc);
+}
+
+int lacx_decoder_item_runs(const lacx_decoder* d, uint32_t item, uint32_t detector, const lacx_run** runs, uint64_t* count) {
+    if (runs) *runs = nullptr;
+    if (count) *count = 0;
+    if (!d || !runs || !count) return decode_fail(LACX_E_INVALID, "null argument");
+    if (item >= d->item_runs.size()) return decode_fail(LACX_E_INVALID, "no such item in the last runs call");
+    if (detector >= d->item_runs[item].size()) return decode_fail(LACX_E_INVALID, "no such detector of that item in the last runs call");
+    *runs = d->item_runs[item][detector].data();
+    *count = d->item_runs[item][detector].size();
     return LACX_OK;
 }
 

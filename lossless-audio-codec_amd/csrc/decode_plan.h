@@ -12,6 +12,7 @@
 #include "lacx.h"
 #include "lacx_types.h"
 #include "manifest.h"
+#include "runs_plan.h"
 
 namespace lacx {
 
@@ -38,6 +39,10 @@ struct BatchIn {
     // a job with block digests: the item's manifest, or null -- nothing is expected of its blocks
     const uint8_t* manifest = nullptr;
     uint64_t manifest_size = 0;
+    // a runs job: the item's detectors (its lacx_run_query resolved), or why they are refused (check_detectors)
+    const lacx_run_detector* dets = nullptr;
+    uint32_t ndet = 0;
+    const char* dets_why = nullptr;
 };
 
 // Where the decoded items go.  wav: the images into the decoder's pinned image buffer (each item's 16-byte aligned, one
@@ -63,6 +68,8 @@ struct BatchIn {
 // The blocks form is also that of a stats job (DecodePlan::stats, lacx_decoder_stats_batch_device): the same salvage job
 // with k_stats_blocks (stats_core.h) in place of k_digest_blocks -- no manifests, no judge, no raw words; one accumulator
 // row of kStatsRowBytes per global block instead, zeroed with the tables.
+// ... and of a runs job (DecodePlan::runs, lacx_decoder_runs_batch_device): the same salvage job with k_runs (runs_core.h)
+// in that slot -- behind present [m] the tables of runs_plan.h (DecodePlan::runs_at), the lists in a buffer of their own.
 enum class DecodeForm { wav, device, host, verify, digest, blocks };
 constexpr int kWholeStreams = -1;
 constexpr size_t kStatsRowBytes = 96;  // sizeof(StatsAcc), stats_core.h (k_stats.hip asserts it)
@@ -96,6 +103,7 @@ struct TableLayout {
     size_t items, byte_off, frame_off, unit_off, blk_item, lane_blk, v2_items, win, res, size;
     size_t judged = 0, raw = 0, expect = 0;  // block digests only
     size_t stats = 0;                        // stats job only
+    size_t runs = 0;                         // runs job only: RunsLayout::base
 };
 
 struct DecodePlan {
@@ -105,9 +113,12 @@ struct DecodePlan {
     bool blocks = false;   // salvage job with block digests; judged: one item at least has a manifest
     bool judged = false;
     bool stats = false;    // salvage job in the blocks form with the statistics' accumulator rows (no block digests)
+    bool runs = false;     // salvage job in the blocks form with the run finder's tables (no block digests, no statistics)
+    uint64_t runs_list_cap = 0;
+    RunsLayout runs_at{};  // ... inside the tables (byte offsets from the tables' first byte)
     bool window() const { return sample_type != kWholeStreams; }
     bool own_pcm() const { return form != DecodeForm::device || window(); }  // into the decoder's PCM buffers
-    bool post_units() const { return window() || form == DecodeForm::verify || form == DecodeForm::wav || form == DecodeForm::digest || blocks || stats; }
+    bool post_units() const { return window() || form == DecodeForm::verify || form == DecodeForm::wav || form == DecodeForm::digest || blocks || stats || runs; }
     bool host_window() const { return form == DecodeForm::host && window(); }
     std::vector<PlanItem> items;
     // k_decode's lanes: lane g decodes global block lane_blk[g] (~0u: idle); version-3 blocks only, an item's in
@@ -122,9 +133,10 @@ struct DecodePlan {
     // What the run must provide (0: that buffer is not used).  payload: bytes, with kDecodeTailPad behind the last block
     // (and behind the host source, where there is one); blocks: status and flag entries; pcm_frames: samples of each
     // channel's buffer; image, stage (the pinned payload stage of a window job), tables: bytes.  stats_rows: the
-    // accumulator rows of a stats job, which lie inside the tables at TableLayout::stats.
+    // accumulator rows of a stats job, which lie inside the tables at TableLayout::stats.  runs_list: the entries
+    // (lacx_run) of a runs job's list buffer.
     struct {
-        uint64_t payload, blocks, pcm_frames, image, stage, tables, stats_rows;
+        uint64_t payload, blocks, pcm_frames, image, stage, tables, stats_rows, runs_list;
     } need{};
 };
 
@@ -195,7 +207,7 @@ inline int check_manifest(const BatchIn& x, const lacx_stream_info& f, std::vect
 // bytes of its present blocks.
 inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, int sample_type, bool pad_waves, DecodePlan& plan,
                                std::vector<int>& code, std::vector<std::string>& err, bool salvage = false, bool blocks = false,
-                               bool stats = false) {
+                               bool stats = false, bool runs = false, uint64_t runs_list_cap = kRunsListCap) {
     using namespace plan_detail;
     plan = DecodePlan{};
     plan.form = form;
@@ -203,13 +215,15 @@ inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, i
     plan.salvage = salvage;
     plan.blocks = blocks;
     plan.stats = stats;
+    plan.runs = runs;
     const bool window = plan.window(), own_pcm = plan.own_pcm(), wav = form == DecodeForm::wav, verify = form == DecodeForm::verify,
                digest = form == DecodeForm::digest, quiet = form == DecodeForm::blocks;
     code.assign(n, LACX_OK);
     err.assign(n, std::string());
     if (salvage && (sample_type != kWholeStreams || (form != DecodeForm::wav && form != DecodeForm::device && !quiet))) return "salvage is a whole-stream WAV or device job";
     if (stats && (!quiet || blocks || !salvage)) return "statistics are a salvage job in the blocks form without block digests";
-    if ((quiet && !blocks && !stats) || (blocks && !salvage)) return "block digests belong to a salvage job";
+    if (runs && (!quiet || blocks || stats || !salvage)) return "runs are a salvage job in the blocks form without block digests or statistics";
+    if ((quiet && !blocks && !stats && !runs) || (blocks && !salvage)) return "block digests belong to a salvage job";
     plan.items.reserve(n);
     uint32_t v3_blocks = 0;
     for (uint32_t i = 0; i < n; ++i) {
@@ -220,6 +234,7 @@ inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, i
         int c = salvage ? scan_stream(x.lac, x.size, &f, &p.present_blocks, &p.scan_flags, &why) : parse_stream(x.lac, x.size, &f, &why);
         if (c == LACX_OK && (why = window ? check_window(x, f) : verify ? check_source(x, f) : wav || digest || quiet ? nullptr : check_arrays(x, f)))
             c = LACX_E_INVALID;
+        if (c == LACX_OK && runs && x.dets_why) why = x.dets_why, c = LACX_E_INVALID;
         std::string text;
         if (c == LACX_OK && blocks && x.manifest) {
             p.judged = true;
@@ -324,7 +339,17 @@ inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, i
         at.expect = at.raw + 4 * T;
     }
     if (stats) at.stats = up16(at.win + 4 * m);
-    at.size = stats ? at.stats + kStatsRowBytes * T : blocks ? at.expect + (plan.judged ? 4 * T : 0) : salvage ? at.win + 4 * m : verify ? at.res + sizeof(VerifyWords) * m : digest ? at.res + sizeof(DigestWords) * m : window ? at.win + sizeof(WindowOut) * m : end;
+    std::vector<RunsIn> rin;
+    if (runs) {
+        for (const PlanItem& p : plan.items) rin.push_back(RunsIn{in[p.src].dets, in[p.src].ndet, p.item.frames});
+        at.runs = up16(at.win + 4 * m);
+        plan.runs_at = runs_layout(at.runs, rin.data(), m);
+        if (plan.runs_at.total_tiles >= (1ull << 31)) return "batch holds 2^31 tiles or more";
+        for (const RunsIn& r : rin)  // (what runs_fill will reserve)
+            for (uint32_t k = 0; k < r.ndet; ++k) plan.need.runs_list += runs_reserve(r.frames, r.dets[k].min_frames, runs_list_cap);
+        plan.runs_list_cap = runs_list_cap;
+    }
+    at.size = runs ? plan.runs_at.size : stats ? at.stats + kStatsRowBytes * T : blocks ? at.expect + (plan.judged ? 4 * T : 0) : salvage ? at.win + 4 * m : verify ? at.res + sizeof(VerifyWords) * m : digest ? at.res + sizeof(DigestWords) * m : window ? at.win + sizeof(WindowOut) * m : end;
     plan.need.payload = (plan.host_src ? plan.src_at + plan.host_src_bytes : plan.total_pay) + kDecodeTailPad;
     plan.need.blocks = T;
     plan.need.pcm_frames = own_pcm ? plan.pcm_total : 0;
@@ -424,6 +449,12 @@ inline void plan_fill_tables(const DecodePlan& plan, const BatchIn* in, const Pl
             }
         }
     }
+    if (plan.runs) {
+        std::vector<RunsIn> rin;
+        for (const PlanItem& p : plan.items) rin.push_back(RunsIn{in[p.src].dets, in[p.src].ndet, p.item.frames});
+        RunsLayout y = plan.runs_at;
+        runs_fill(y, rin.data(), m, plan.runs_list_cap, h);
+    }
     if (!plan.lane_blk.empty()) std::memcpy(h + at.lane_blk, plan.lane_blk.data(), 4 * plan.lane_blk.size());
     if (!plan.v2_items.empty()) std::memcpy(h + at.v2_items, plan.v2_items.data(), 4 * plan.v2_items.size());
 }
@@ -462,7 +493,7 @@ inline DecodeArgs plan_args(const DecodePlan& plan, const uint8_t* tables, const
         a.no_output = plan.form == DecodeForm::blocks;
     }
     if (plan.form == DecodeForm::digest) a.digest = reinterpret_cast<DigestWords*>(const_cast<uint8_t*>(tables) + at.res);
-    if (plan.stats) a.no_output = true;  // launch_decode ends with k_ms_inverse; k_stats_blocks follows it (plan_stats_args)
+    if (plan.stats || plan.runs) a.no_output = true;  // launch_decode ends with k_ms_inverse; k_stats_blocks follows it (plan_stats_args)
     return a;
 }
 
@@ -472,6 +503,14 @@ inline StatsArgs plan_stats_args(const DecodePlan& plan, const DecodeArgs& a, co
     s.dec = a;
     s.rows = reinterpret_cast<StatsAcc*>(const_cast<uint8_t*>(tables) + plan.at.stats);
     return s;
+}
+
+// A runs job's arguments for k_runs: the decode's own, the tables of runs_plan.h inside the tables, and the list buffer.
+inline RunsArgs plan_runs_args(const DecodePlan& plan, const DecodeArgs& a, const uint8_t* tables, lacx_run* list) {
+    RunsArgs r;
+    r.dec = a;
+    runs_args(plan.runs_at, plan.items.size(), tables, list, r);
+    return r;
 }
 
 }  // namespace lacx

@@ -1,5 +1,5 @@
 // kernels.h -- host-visible interface of the kernel translation units (k_front.hip, k_analyze.hip, k_emit.hip,
-// decode.hip, k_digest.hip, k_blockdigest.hip, k_stats.hip, k_inspect.hip, k_recovery.hip, wide.hip, k_import.hip, k_edit.hip).
+// decode.hip, k_digest.hip, k_blockdigest.hip, k_stats.hip, k_runs.hip, k_inspect.hip, k_recovery.hip, wide.hip, k_import.hip, k_edit.hip).
 #pragma once
 #include <cstdlib>
 #include <hip/hip_runtime_api.h>
@@ -198,6 +198,11 @@ hipError_t launch_stats_pcm_blocks(const StatsPcmArgs& args, hipStream_t stream)
 // Stream inspection (k_inspect.hip, inspect_core.h): k_inspect over the job's lanes and k_inspect_serial over its
 // version-2 items; a job with partition detail has its entries zeroed on the stream first.
 hipError_t launch_inspect(const InspectArgs& args, hipStream_t stream);
+
+// Run finder (k_runs.hip, runs_core.h): k_runs over the tiles of a runs job's items, on the same stream behind launch_decode
+// (which for such a job ends with k_ms_inverse), and over device-resident source PCM.
+hipError_t launch_runs(const RunsArgs& args, hipStream_t stream);
+hipError_t launch_runs_pcm(const RunsArgs& args, hipStream_t stream);
 
 // Recovery data (k_recovery.hip, recovery_core.h): k_gf_combine over the task table, one launch per accumulator tier that
 // has tasks, then k_slice_crc over the listed byte ranges.

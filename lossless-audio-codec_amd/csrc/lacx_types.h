@@ -4,6 +4,8 @@
 #include <stdint.h>
 
 struct lacx_block_info;  // lacx.h
+struct lacx_run_detector;
+struct lacx_run;
 
 namespace lacx {
 
@@ -218,6 +220,24 @@ struct StatsPcmArgs {
     uint32_t grid = 0;                             // frames per block, 256 .. 16384
     const unsigned long long* block_off = nullptr; // [nitems + 1] prefix sums of ceil(frames / grid)
     StatsAcc* rows = nullptr;                      // [block_off[nitems]]
+};
+// Run finder (k_runs, runs_core.h): the tables runs_plan.h lays out -- per item its detectors and rows, per detector its
+// list region and counter (zero on entry), one row per (tile, detector) (zero on entry) -- and the list buffer.
+struct RunsItem;
+struct RunsList;
+struct RunsRow;
+struct RunsArgs {
+    DecodeArgs dec;                                // stream form: the job k_runs follows (behind k_ms_inverse)
+    uint32_t nitems = 0;
+    unsigned long long total_tiles = 0;
+    const unsigned long long* tile_off = nullptr;  // [nitems + 1] prefix sums of ceil(frames / kRunsTileFrames)
+    const RunsItem* items = nullptr;               // [nitems]
+    const lacx_run_detector* dets = nullptr;       // the items' detectors, an item's in a row
+    RunsList* lists = nullptr;                     // one per detector
+    RunsRow* rows = nullptr;
+    lacx_run* runs = nullptr;                      // the list buffer
+    const DigestSource* src = nullptr;             // source form: the items, and per item the lowest invalid sample's key
+    unsigned long long* bad = nullptr;
 };
 // Stream inspection (k_inspect / k_inspect_serial, inspect_core.h): the decode's tables without its outputs (status and
 // ms_flag are not used), one row per global block, and for a job with partition detail the entries of both channel blocks.

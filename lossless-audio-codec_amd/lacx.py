@@ -123,6 +123,7 @@ EXPORTS = (
     "lacx_decoder_stats_batch_device", "lacx_decoder_stats_pcm_batch_device", "lacx_decoder_item_block_stats", "lacx_stats_combine",
     "lacx_decoder_inspect_batch_device", "lacx_decoder_item_block_info", "lacx_decoder_item_partitions", "lacx_inspect_combine",
     "lacx_decoder_inspect_guard", "lacx_transcode_batch",
+    "lacx_decoder_runs_batch_device", "lacx_decoder_runs_pcm_batch_device", "lacx_decoder_item_runs",
 )
 
 
@@ -244,6 +245,12 @@ def lib():
         L.lacx_inspect_combine.argtypes = [C.POINTER(BlockInfo), C.c_uint32, C.POINTER(StreamInfo), C.POINTER(StreamReport)]
         L.lacx_transcode_batch.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(EditSegment), C.c_uint32, C.POINTER(EditOutput), C.c_uint32,
                                            C.c_uint32, C.POINTER(Span), C.POINTER(C.c_int), C.POINTER(EditResult), C.POINTER(C.c_float)]
+        L.lacx_decoder_runs_batch_device.argtypes = [C.c_void_p, C.POINTER(Span), C.POINTER(RunQuery), C.c_uint32, C.POINTER(RunDetector),
+                                                     C.c_uint32, C.c_void_p, C.POINTER(C.c_int), C.POINTER(RunsResult), C.POINTER(C.c_float)]
+        L.lacx_decoder_runs_pcm_batch_device.argtypes = [C.c_void_p, C.POINTER(DigestSource), C.POINTER(RunQuery), C.c_uint32,
+                                                         C.POINTER(RunDetector), C.c_uint32, C.c_void_p, C.POINTER(C.c_int),
+                                                         C.POINTER(RunsResult), C.POINTER(C.c_float)]
+        L.lacx_decoder_item_runs.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.POINTER(Run)), C.POINTER(C.c_uint64)]
         L.lacx_block_fault_text.restype = C.c_char_p
         L.lacx_block_fault_text.argtypes = [C.c_uint32]
         L.lacx_decoder_item_error.restype = C.c_char_p
@@ -273,7 +280,8 @@ def abi_structs() -> dict:
             "repair_result": RepairResult, "channel_stats": ChannelStats, "block_stats": BlockStats,
             "channel_totals": ChannelTotals, "stats": Stats, "channel_info": ChannelInfo, "block_info": BlockInfo,
             "stream_report": StreamReport, "edit_segment": EditSegment, "edit_output": EditOutput,
-            "edit_result": EditResult}
+            "edit_result": EditResult, "run_detector": RunDetector, "run_query": RunQuery, "run": Run,
+            "run_totals": RunTotals, "runs_result": RunsResult}
 
 
 def device_count() -> int:
@@ -945,6 +953,109 @@ class Stats(C.Structure):
         return self.ch[channel].sum / n / float(1 << (self.bit_depth - 1)) if n and self.bit_depth else 0.0
 
 
+# ---- runs: where a stream is silent, clips or holds one value (lacx.h) ----
+RUN_QUIET, RUN_PEAK, RUN_FLAT = 0, 1, 2  # LACX_RUN_*
+RUN_ALL = 255
+MAX_DETECTORS = 8
+RUNS_RERUN = 1
+RUN_CHANNELS = {"left": 0, "right": 1, "all": RUN_ALL}
+
+
+class RunDetector(C.Structure):
+    _fields_ = [("kind", C.c_uint8), ("channel", C.c_uint8), ("reserved", C.c_uint8 * 2), ("level", C.c_uint32),
+                ("min_frames", C.c_uint64)]
+
+
+class RunQuery(C.Structure):
+    _fields_ = [("first_detector", C.c_uint32), ("detectors", C.c_uint32)]
+
+
+class Run(C.Structure):
+    _fields_ = [("start", C.c_uint64), ("frames", C.c_uint64)]
+
+
+class RunTotals(C.Structure):
+    _fields_ = [("runs", C.c_uint64), ("frames", C.c_uint64), ("longest", C.c_uint64), ("longest_start", C.c_uint64)]
+
+
+class RunsResult(C.Structure):
+    """What a runs call says of an item (lacx_runs_result): the stream's size and losses and per detector the totals."""
+    _fields_ = [("frames", C.c_uint64), ("lost_frames", C.c_uint64), ("sample_rate", C.c_uint32), ("blocks", C.c_uint32),
+                ("lost_blocks", C.c_uint32), ("flags", C.c_uint32), ("channels", C.c_uint8), ("bit_depth", C.c_uint8),
+                ("detectors", C.c_uint8), ("reserved", C.c_uint8 * 5), ("det", RunTotals * MAX_DETECTORS)]
+
+    @property
+    def rerun(self) -> bool:
+        return bool(self.flags & RUNS_RERUN)
+
+
+class Detector:
+    """A detector as a caller states it, converted per item: level in sample units or dbfs (floor(2^(b-1) * 10^(dB/20))
+    at the item's depth b), min_frames or seconds (frames at the item's rate, at least 1)."""
+
+    def __init__(self, kind, level=None, dbfs=None, min_frames=None, seconds=None, channel="all"):
+        if level is not None and dbfs is not None:
+            raise ValueError("level and dbfs exclude each other")
+        if min_frames is not None and seconds is not None:
+            raise ValueError("min_frames and seconds exclude each other")
+        self.kind, self.level, self.dbfs, self.min_frames, self.seconds = kind, level, dbfs, min_frames, seconds
+        self.channel = RUN_CHANNELS[channel] if isinstance(channel, str) else int(channel)
+
+    def resolve(self, bit_depth: int, sample_rate: int) -> RunDetector:
+        level = (1 << (bit_depth - 1)) - 1 if self.level == "full" else int(self.level or 0)
+        if self.dbfs is not None:
+            level = int(math.floor((1 << (bit_depth - 1)) * 10.0 ** (self.dbfs / 20.0)))
+        frames = 1 if self.min_frames is None else int(self.min_frames)
+        if self.seconds is not None:
+            frames = max(1, int(math.floor(self.seconds * sample_rate)))
+        return RunDetector(self.kind, self.channel, (C.c_uint8 * 2)(), min(max(level, 0), 0xFFFFFFFF), frames)
+
+    def __repr__(self):
+        return f"Detector({('quiet', 'peak', 'flat')[self.kind]}, level={self.level}, dbfs={self.dbfs}, min_frames={self.min_frames}, seconds={self.seconds}, channel={self.channel})"
+
+
+def quiet(level=None, dbfs=None, min_frames=None, seconds=None, channel="all") -> Detector:
+    """Frames with -level <= x <= level in every selected channel (level 0, the default: digital silence)."""
+    return Detector(RUN_QUIET, level, dbfs, min_frames, seconds, channel)
+
+
+def peak(level=None, dbfs=None, min_frames=None, seconds=None, channel="all") -> Detector:
+    """Frames with x >= level or x <= -level - 1 in every selected channel; without level or dbfs: full scale, 2^(b-1) - 1."""
+    return Detector(RUN_PEAK, "full" if level is None and dbfs is None else level, dbfs, min_frames, seconds, channel)
+
+
+def flat(min_frames=None, seconds=None, channel="all") -> Detector:
+    """Frames whose samples equal the frame before in every selected channel: N equal samples are N - 1 flagged frames."""
+    return Detector(RUN_FLAT, 0, None, min_frames, seconds, channel)
+
+
+class RunList:
+    """One detector's answer for one item: `runs`, a [k, 2] uint64 array of (start, frames) ascending by start, and
+    `totals` (RunTotals)."""
+
+    def __init__(self, detector: RunDetector, runs: np.ndarray, totals: RunTotals):
+        self.detector, self.runs, self.totals = detector, runs, totals
+
+    def __repr__(self):
+        return f"RunList(runs={self.totals.runs}, frames={self.totals.frames}, longest={self.totals.longest}@{self.totals.longest_start})"
+
+
+def sound_pieces(frames: int, quiet_runs, pad: int = 0) -> list:
+    """The complement of quiet runs inside [0, frames) as (start, frames) pieces, each widened by `pad` frames on both
+    sides, clipped to the stream and merged where pieces touch or overlap.  Pure arithmetic: what split_on_silence cuts."""
+    pieces, at = [], 0
+    for start, n in list(quiet_runs) + [(frames, 0)]:
+        start, n = int(start), int(n)
+        if start > at:
+            lo, hi = max(0, at - pad), min(frames, start + pad)
+            if pieces and lo <= pieces[-1][1]:
+                pieces[-1][1] = max(pieces[-1][1], hi)
+            else:
+                pieces.append([lo, hi])
+        at = max(at, start + n)
+    return [(lo, hi - lo) for lo, hi in pieces]
+
+
 def stats_combine(rows, channels: int, bit_depth: int, sample_rate: int = 0) -> Stats:
     """The totals of BlockStats rows (all of an item's, or a sub-range: a window's blocks), as stats_batch makes an item's.
     ValueError for a channel count or depth the library does not know.  Host only."""
@@ -1160,6 +1271,13 @@ def stream_parse(lac: bytes):
     info = StreamInfo()
     buf = (C.c_uint8 * max(1, len(lac))).from_buffer_copy(lac if lac else b"\0")
     return info if lib().lacx_stream_parse(buf, C.c_uint64(len(lac)), C.byref(info)) == OK else None
+
+
+def _scan_in_place(buf: np.ndarray):
+    """The StreamInfo of stream_scan of a uint8 array, without copying it; None where it is refused."""
+    info, present, flags = StreamInfo(), C.c_uint32(), C.c_uint32()
+    rc = lib().lacx_stream_scan(buf.ctypes.data_as(C.POINTER(C.c_uint8)), C.c_uint64(buf.size), C.byref(info), C.byref(present), C.byref(flags))
+    return info if rc == OK else None
 
 
 def _parse_in_place(buf: np.ndarray):
@@ -1676,6 +1794,121 @@ class Decoder:
             raise RuntimeError(lib().lacx_decode_last_error().decode(errors="replace"))
         errors = {i: lib().lacx_decoder_item_error(self._h, i).decode(errors="replace") for i in range(n) if rcs[i] != OK}
         return self._raise_batch(rc, errors, [None if i in errors else (_copy_struct(out[i]), self._stat_rows(i)) for i in range(n)])
+
+    # ---- runs: where a stream is silent, clips or holds one value ----
+    @staticmethod
+    def _detector_tables(detectors, n, formats):
+        """detectors: one list for all items or one list per item (of Detector or RunDetector); formats[i]: (bit_depth,
+        sample_rate) or None.  -> (RunQuery array, RunDetector array, count, per item the resolved detectors)."""
+        per_item = n > 0 and len(detectors) == n and all(isinstance(x, (list, tuple)) for x in detectors)
+        flat_list, queries, resolved = [], (RunQuery * max(1, n))(), []
+        for i in range(n):
+            depth, rate = formats[i] or (16, 1)
+            mine = [d.resolve(depth, rate) if isinstance(d, Detector) else d for d in (detectors[i] if per_item else detectors)]
+            queries[i] = RunQuery(len(flat_list), len(mine))
+            flat_list.extend(mine)
+            resolved.append(mine)
+        return queries, (RunDetector * max(1, len(flat_list)))(*flat_list), len(flat_list), resolved
+
+    def _run_lists(self, i, resolved, res) -> list:
+        out = []
+        for k, det in enumerate(resolved):
+            ptr, count = C.POINTER(Run)(), C.c_uint64()
+            if lib().lacx_decoder_item_runs(self._h, C.c_uint32(i), C.c_uint32(k), C.byref(ptr), C.byref(count)) != OK:
+                raise RuntimeError(lib().lacx_decode_last_error().decode(errors="replace"))
+            runs = np.zeros((count.value, 2), dtype=np.uint64)  # a copy: the lists die with the decoder's next call
+            if count.value:
+                C.memmove(runs.ctypes.data, ptr, 16 * count.value)
+            out.append(RunList(det, runs, _copy_struct(res.det[k])))
+        return out
+
+    def runs_batch(self, lacs, detectors, stream: int = 0) -> list:
+        """Many streams decoded and searched for runs as one device job, lenient like stats_batch: per item
+        (RunsResult, [RunList per detector]), None where the container or the item's detectors are refused (those raise
+        BatchDecodeError once the others are done).  detectors: one list for all items or one list per item, of
+        lacx.quiet / peak / flat (converted at each item's depth and rate) or RunDetector records.  Every list is complete
+        and ascending by start; a lost block splits a run.  Kernel milliseconds in `last_ms`."""
+        bufs = [np.frombuffer(x, dtype=np.uint8) for x in lacs]
+        n = len(bufs)
+        spans = (Span * max(1, n))(*[Span(b.ctypes.data_as(C.POINTER(C.c_uint8)), b.size) for b in bufs])
+        formats = []
+        for b in bufs:
+            info = _scan_in_place(b)  # (the format: what the detectors' dBFS and seconds refer to)
+            formats.append((info.bit_depth, info.sample_rate) if info else None)
+        queries, dets, ndets, resolved = self._detector_tables(detectors, n, formats)
+        out = (RunsResult * max(1, n))()
+        if n and ndets == 0:
+            raise ValueError("no detectors")
+        rc, errors = self._batch(n, lambda rcs, ms: lib().lacx_decoder_runs_batch_device(
+            self._h, spans, queries, C.c_uint32(n), dets, C.c_uint32(ndets), C.c_void_p(stream), rcs, out, ms))
+        if rc == E_INVALID and not errors:
+            raise ValueError(lib().lacx_decode_last_error().decode(errors="replace"))
+        return self._raise_batch(rc, errors, [None if i in errors else (_copy_struct(out[i]), self._run_lists(i, resolved[i], out[i])) for i in range(n)])
+
+    def runs(self, lac, detectors) -> list:
+        """The [RunList per detector] of runs_batch of one stream; RuntimeError with the item's message where it is refused."""
+        try:
+            return self.runs_batch([lac], list(detectors))[0][1]
+        except BatchDecodeError as e:
+            raise RuntimeError(e.errors[0]) from None
+
+    def runs_pcm_batch(self, sources, detectors, stream: int = 0) -> list:
+        """Device-resident PCM searched for runs where it lies: per item (RunsResult, [RunList per detector]) -- what
+        runs_batch gives for the .lac made from it.  Sources as stats_pcm_batch takes them."""
+        n = len(sources)
+        items = (DigestSource * max(1, n))()
+        formats = []
+        for it, (pcm, rate, depth) in zip(items, sources):
+            if isinstance(pcm, (tuple, list)):
+                d0, d1, layout, channels, frames = pcm
+                it.pcm = Pcm(d0, d1, layout, channels)
+            else:
+                it.pcm, frames = pcm_of(pcm, depth)
+            it.frames, it.sample_rate, it.bit_depth = frames, rate, depth
+            formats.append((depth if depth in (16, 24) else 16, rate))
+        queries, dets, ndets, resolved = self._detector_tables(detectors, n, formats)
+        out = (RunsResult * max(1, n))()
+        if self._h is None:
+            raise RuntimeError("decoder is closed")
+        rcs, ms = (C.c_int * max(1, n))(), C.c_float()
+        rc = lib().lacx_decoder_runs_pcm_batch_device(self._h, items, queries, C.c_uint32(n), dets, C.c_uint32(ndets), C.c_void_p(stream),
+                                                      rcs, out, C.byref(ms))
+        self.last_ms = float(ms.value)
+        if rc == E_INVALID and all(rcs[i] == OK for i in range(n)):  # the call's own arguments
+            raise ValueError(lib().lacx_decode_last_error().decode(errors="replace"))
+        if rc == E_DEVICE:
+            raise RuntimeError(lib().lacx_decode_last_error().decode(errors="replace"))
+        errors = {i: lib().lacx_decoder_item_error(self._h, i).decode(errors="replace") for i in range(n) if rcs[i] != OK}
+        return self._raise_batch(rc, errors, [None if i in errors else (_copy_struct(out[i]), self._run_lists(i, resolved[i], out[i])) for i in range(n)])
+
+    def _sound_pieces(self, lac, level, min_frames, pad):
+        try:
+            res, lists = self.runs_batch([lac], [RunDetector(RUN_QUIET, RUN_ALL, (C.c_uint8 * 2)(), int(level), int(min_frames))])[0]
+        except BatchDecodeError as e:
+            raise RuntimeError(e.errors[0]) from None
+        if res.lost_blocks:
+            raise ValueError(f"stream has {res.lost_blocks} lost blocks: silence cannot be told from loss")
+        return sound_pieces(int(res.frames), lists[0].runs.tolist(), int(pad))
+
+    def split_on_silence(self, encoder: "Encoder", lac, level: int, min_frames: int, pad: int = 0, verify: bool = False) -> list:
+        """The stream cut at its silences: one QUIET detector over all channels (|x| <= level for min_frames frames at
+        least), the sounding pieces between its runs widened by `pad` frames, clipped and merged, then one transcode_batch
+        with one output per piece.  Returns [(start, frames, bytes)]: every output is byte for byte what `cut` gives for
+        that range.  A stream with a lost block is refused (ValueError); one that is all silence gives no outputs."""
+        pieces = self._sound_pieces(lac, level, min_frames, pad)
+        if not pieces:
+            return []
+        outs = self.transcode_batch(encoder, [([(lac, start, n)],) for start, n in pieces], verify)
+        return [(start, n, data) for (start, n), (data, _res) in zip(pieces, outs)]
+
+    def trim_silence(self, encoder: "Encoder", lac, level: int, min_frames: int, pad: int = 0, verify: bool = False):
+        """The stream without its leading and trailing silence: from the first sounding piece's start to the last one's
+        end, as (start, frames, bytes); None where the stream is all silence."""
+        pieces = self._sound_pieces(lac, level, min_frames, pad)
+        if not pieces:
+            return None
+        start, end = pieces[0][0], pieces[-1][0] + pieces[-1][1]
+        return start, end - start, self.cut(encoder, lac, start, end - start, verify)
 
     # ---- stream inspection: predictors, modes, bit budget ----
     def _info_rows(self, i, partitions) -> list:

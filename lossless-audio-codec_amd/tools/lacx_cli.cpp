@@ -71,6 +71,11 @@ void usage() {
                  "  lacx_cli cut in.lac out.lac --start=F [--frames=N] [--verify]   (frames [F, F + N), or to the end)\n"
                  "  lacx_cli join out.lac in1.lac in2.lac ... [--verify]   (streams of one format, one behind the other)\n"
                  "      all three: exit 0 done, 1 mismatch under --verify, 2 refused; out.lac is written only on success\n"
+                 "  lacx_cli find FILE... [--quiet=LEVEL|--quiet-db=X] [--peak=LEVEL|--clip] [--flat] [--channel=left|right|all]\n"
+                 "      [--min=FRAMES|--min-seconds=S]   (.lac and .wav files: where they are silent, clip or hold one value -- one line\n"
+                 "      per run of at least --min frames, then one totals line per detector; exit 0 nothing found, 1 runs found, 2 refused)\n"
+                 "  lacx_cli split in.lac PREFIX --quiet=LEVEL --min=FRAMES [--pad=N] [--verify]   (cut at the silences: PREFIX0001.lac ...;\n"
+                 "      exit 0 done, 1 mismatch under --verify, 2 refused)\n"
                  "  lacx_cli selftest\n";
 }
 
@@ -1050,6 +1055,306 @@ int transcode_command(const std::string& mode, int argc, char** argv) {
     return status;
 }
 
+// "12.345": n / rate seconds, cut to milliseconds, in integers
+std::string seconds_of(uint64_t n, uint32_t rate) {
+    const unsigned __int128 ms = (unsigned __int128)n * 1000u / (rate ? rate : 1u);
+    char text[48];
+    std::snprintf(text, sizeof(text), "%llu.%03u", (unsigned long long)(ms / 1000u), (unsigned)(ms % 1000u));
+    return text;
+}
+
+bool plain_number(const std::string& v, uint64_t& out) {
+    if (v.empty() || v.size() > 18) return false;
+    for (char c : v)
+        if (c < '0' || c > '9') return false;
+    out = std::stoull(v);
+    return true;
+}
+
+// lacx_cli find FILE... : the runs of every .lac (what it decodes to, leniently: a lost block splits a run) and of every
+// WAV's data chunk, found on the device (lacx_decoder_runs_batch_device / lacx_decoder_runs_pcm_batch_device), the files of
+// each kind as one job.  A level in dBFS becomes floor(2^(b-1) * 10^(dB/20)) at each file's depth b, --clip is 2^(b-1)-1,
+// seconds become frames at each file's rate.  Per file in argument order one line per run, then one totals line per
+// detector.  Exit 0 nothing found, 1 runs found, 2 a file was refused (its message on stderr).
+int find_command(int argc, char** argv) {
+    struct Want {
+        uint8_t kind;
+        bool db, clip;
+        double dbfs;
+        uint64_t level;
+    };
+    std::vector<Want> wants;
+    std::vector<const char*> paths;
+    uint8_t channel = LACX_RUN_ALL;
+    uint64_t min_frames = 1;
+    double min_seconds = -1.0;
+    for (int i = 2; i < argc; ++i) {
+        const std::string a = argv[i];
+        bool ok = true;
+        Want w{LACX_RUN_QUIET, false, false, 0.0, 0};
+        char* end = nullptr;
+        if (a.compare(0, 2, "--") != 0) paths.push_back(argv[i]);
+        else if (a.compare(0, 8, "--quiet=") == 0) ok = plain_number(a.substr(8), w.level) && w.level <= 0xFFFFFFFFull, wants.push_back(w);
+        else if (a.compare(0, 11, "--quiet-db=") == 0) w.db = true, w.dbfs = std::strtod(a.c_str() + 11, &end), ok = end != a.c_str() + 11 && !*end, wants.push_back(w);
+        else if (a.compare(0, 7, "--peak=") == 0) w.kind = LACX_RUN_PEAK, ok = plain_number(a.substr(7), w.level) && w.level <= 0xFFFFFFFFull, wants.push_back(w);
+        else if (a == "--clip") w.kind = LACX_RUN_PEAK, w.clip = true, wants.push_back(w);
+        else if (a == "--flat") w.kind = LACX_RUN_FLAT, wants.push_back(w);
+        else if (a == "--channel=left") channel = 0;
+        else if (a == "--channel=right") channel = 1;
+        else if (a == "--channel=all") channel = LACX_RUN_ALL;
+        else if (a.compare(0, 6, "--min=") == 0) ok = plain_number(a.substr(6), min_frames) && min_frames >= 1;
+        else if (a.compare(0, 14, "--min-seconds=") == 0) min_seconds = std::strtod(a.c_str() + 14, &end), ok = end != a.c_str() + 14 && !*end && min_seconds >= 0.0;
+        else ok = false;
+        if (!ok) {
+            usage();
+            return 2;
+        }
+    }
+    const int n = (int)paths.size();
+    if (n == 0 || wants.empty() || wants.size() > LACX_MAX_DETECTORS) {
+        usage();
+        return 2;
+    }
+    const uint32_t nd = (uint32_t)wants.size();
+    std::vector<std::vector<uint8_t>> data(n);
+    std::vector<std::string> error(n);
+    std::vector<lacx_runs_result> result(n, lacx_runs_result{});
+    std::vector<std::vector<std::vector<lacx_run>>> lists(n);
+    std::vector<lacx_run_detector> dets((size_t)n * nd);  // file i's detectors: dets[i * nd ...]
+    std::vector<int> lacs, wavs;
+    std::vector<lacx_wav_info> winfo(n, lacx_wav_info{});
+    auto resolve = [&](int i, uint32_t bits, uint32_t rate) {
+        for (uint32_t k = 0; k < nd; ++k) {
+            const Want& w = wants[k];
+            lacx_run_detector d{};
+            d.kind = w.kind;
+            d.channel = channel;
+            const double full = (double)(1u << (bits - 1));
+            d.level = w.clip ? (1u << (bits - 1)) - 1u : w.db ? (uint32_t)std::floor(std::min(full * std::pow(10.0, w.dbfs / 20.0), 4294967295.0)) : (uint32_t)w.level;
+            d.min_frames = min_seconds >= 0.0 ? std::max<uint64_t>(1, (uint64_t)std::floor(min_seconds * rate)) : min_frames;
+            dets[(size_t)i * nd + k] = d;
+        }
+    };
+    for (int i = 0; i < n; ++i) {
+        if (!load_file(paths[i], data[i])) {
+            error[i] = "Failed to read file";
+        } else if (data[i].size() >= 4 && std::memcmp(data[i].data(), "RIFF", 4) == 0) {
+            if (lacx_wav_parse(data[i].data(), data[i].size(), &winfo[i]) != LACX_OK) error[i] = "Failed to read WAV";
+            else wavs.push_back(i), resolve(i, winfo[i].bit_depth, winfo[i].sample_rate);
+        } else {
+            lacx_stream_info info{};
+            uint32_t present = 0, flags = 0;
+            if (lacx_stream_scan(data[i].data(), data[i].size(), &info, &present, &flags) != LACX_OK) error[i] = lacx_decode_last_error();
+            else lacs.push_back(i), resolve(i, info.bit_depth, info.sample_rate);
+        }
+    }
+    lacx_decoder* dec = nullptr;
+    if (lacx_decoder_create(-1, &dec) != LACX_OK) {
+        std::cerr << "Error: lacx_decoder_create failed\n";
+        return 2;
+    }
+    auto collect = [&](const std::vector<int>& which, int rc, const std::vector<int>& item_rc, const std::vector<lacx_runs_result>& out) {
+        for (size_t k = 0; k < which.size(); ++k) {
+            if (item_rc[k] != LACX_OK || rc == LACX_E_DEVICE) {
+                error[which[k]] = rc == LACX_E_DEVICE || item_rc[k] == LACX_OK ? lacx_decode_last_error() : lacx_decoder_item_error(dec, (uint32_t)k);
+                continue;
+            }
+            result[which[k]] = out[k];
+            lists[which[k]].resize(nd);
+            for (uint32_t q = 0; q < nd; ++q) {
+                const lacx_run* r = nullptr;
+                uint64_t count = 0;
+                if (lacx_decoder_item_runs(dec, (uint32_t)k, q, &r, &count) == LACX_OK) lists[which[k]][q].assign(r, r + count);
+            }
+        }
+    };
+    auto queries_of = [&](const std::vector<int>& which) {
+        std::vector<lacx_run_query> q;
+        for (int i : which) q.push_back(lacx_run_query{(uint32_t)i * nd, nd});
+        return q;
+    };
+    if (!lacs.empty()) {
+        std::vector<lacx_span> spans;
+        for (int i : lacs) spans.push_back(lacx_span{data[i].data(), data[i].size()});
+        const std::vector<lacx_run_query> q = queries_of(lacs);
+        std::vector<int> item_rc(lacs.size(), LACX_OK);
+        std::vector<lacx_runs_result> out(lacs.size());
+        const int rc = lacx_decoder_runs_batch_device(dec, spans.data(), q.data(), (uint32_t)spans.size(), dets.data(), (uint32_t)dets.size(), nullptr,
+                                                      item_rc.data(), out.data(), nullptr);
+        collect(lacs, rc, item_rc, out);
+    }
+    if (!wavs.empty()) {
+        std::vector<lacx_digest_source> src;
+        std::vector<void*> dev;
+        std::vector<int> sent;
+        for (int i : wavs) {
+            const lacx_wav_info& w = winfo[i];
+            const uint64_t bytes = w.frames * w.channels * (uint64_t)(w.bit_depth / 8);
+            void* p = nullptr;
+            if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess ||
+                hipMemcpy(p, data[i].data() + w.data_offset, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+                error[i] = "Failed to upload WAV data to the device";
+                if (p) (void)hipFree(p);
+                continue;
+            }
+            lacx_digest_source s{};
+            s.pcm = lacx_pcm{p, nullptr, w.bit_depth == 16 ? LACX_PCM_INTERLEAVED_I16 : LACX_PCM_INTERLEAVED_I24, w.channels};
+            s.frames = w.frames;
+            s.sample_rate = w.sample_rate;
+            s.bit_depth = (uint8_t)w.bit_depth;
+            src.push_back(s), dev.push_back(p), sent.push_back(i);
+        }
+        if (!src.empty()) {
+            const std::vector<lacx_run_query> q = queries_of(sent);
+            std::vector<int> item_rc(src.size(), LACX_OK);
+            std::vector<lacx_runs_result> out(src.size());
+            const int rc = lacx_decoder_runs_pcm_batch_device(dec, src.data(), q.data(), (uint32_t)src.size(), dets.data(), (uint32_t)dets.size(), nullptr,
+                                                              item_rc.data(), out.data(), nullptr);
+            collect(sent, rc, item_rc, out);
+        }
+        for (void* p : dev) (void)hipFree(p);
+    }
+    lacx_decoder_destroy(dec);
+    static const char* const kNames[] = {"quiet", "peak", "flat"};
+    bool refused = false, found = false;
+    for (int i = 0; i < n; ++i) {
+        if (!error[i].empty()) {
+            std::cerr << "Find failed: " << paths[i] << ": " << error[i] << "\n";
+            refused = true;
+            continue;
+        }
+        const lacx_runs_result& t = result[i];
+        for (uint32_t q = 0; q < nd; ++q) {
+            const lacx_run_detector& d = dets[(size_t)i * nd + q];
+            for (const lacx_run& r : lists[i][q]) {
+                found = true;
+                std::cout << kNames[d.kind] << " start=" << r.start << " frames=" << r.frames << " at=" << seconds_of(r.start, t.sample_rate)
+                          << "s length=" << seconds_of(r.frames, t.sample_rate) << "s " << paths[i] << "\n";
+            }
+        }
+        for (uint32_t q = 0; q < nd; ++q) {
+            const lacx_run_detector& d = dets[(size_t)i * nd + q];
+            const lacx_run_totals& s = t.det[q];
+            std::cout << kNames[d.kind] << " total level=" << d.level << " min=" << d.min_frames << " runs=" << s.runs << " frames=" << s.frames
+                      << " longest=" << s.longest << " longest_start=" << s.longest_start << " of=" << t.frames << " lost_blocks=" << t.lost_blocks << " "
+                      << paths[i] << "\n";
+        }
+    }
+    return refused ? 2 : found ? 1 : 0;
+}
+
+// lacx_cli split in.lac PREFIX --quiet=LEVEL --min=FRAMES [--pad=N] [--verify]: one QUIET detector over all channels, the
+// sounding pieces between its runs widened by --pad frames, clipped to the stream and merged where they touch, then one
+// lacx_transcode_batch with one output per piece: PREFIX0001.lac, ...  A stream with a lost block is refused (silence cannot
+// be told from loss); one that is all silence writes nothing.  Exit 0 done, 1 mismatch under --verify, 2 refused.
+int split_command(int argc, char** argv) {
+    const std::string in_path = argv[2], prefix = argv[3];
+    uint64_t level = 0, min_frames = 0, pad = 0;
+    bool verify = false, have_level = false, have_min = false;
+    for (int i = 4; i < argc; ++i) {
+        const std::string a = argv[i];
+        bool ok = a == "--verify";
+        if (ok) verify = true;
+        if (a.compare(0, 8, "--quiet=") == 0) ok = have_level = plain_number(a.substr(8), level) && level <= 0xFFFFFFFFull;
+        if (a.compare(0, 6, "--min=") == 0) ok = have_min = plain_number(a.substr(6), min_frames) && min_frames >= 1;
+        if (a.compare(0, 6, "--pad=") == 0) ok = plain_number(a.substr(6), pad);
+        if (!ok) {
+            usage();
+            return 2;
+        }
+    }
+    if (!have_level || !have_min) {
+        usage();
+        return 2;
+    }
+    std::vector<uint8_t> file;
+    if (!load_file(in_path, file)) {
+        std::cerr << "Failed to read LAC file: " << in_path << "\n";
+        return 2;
+    }
+    lacx_config cfg{};
+    cfg.sample_rate = 48000;  // (the outputs' formats come from their source)
+    cfg.bit_depth = 16;
+    cfg.zero_run_enabled = 1;
+    cfg.partitioning_enabled = 1;
+    cfg.device = -1;
+    lacx_encoder* enc = nullptr;
+    lacx_decoder* dec = nullptr;
+    if (lacx_encoder_create(&cfg, &enc) != LACX_OK || lacx_decoder_create(-1, &dec) != LACX_OK) {
+        std::cerr << "Error: cannot create the encoder and the decoder\n";
+        if (enc) lacx_encoder_destroy(enc);
+        return 2;
+    }
+    auto done = [&](int status) {
+        lacx_decoder_destroy(dec);
+        lacx_encoder_destroy(enc);
+        return status;
+    };
+    lacx_run_detector det{};
+    det.kind = LACX_RUN_QUIET, det.channel = LACX_RUN_ALL, det.level = (uint32_t)level, det.min_frames = min_frames;
+    const lacx_span span{file.data(), file.size()};
+    const lacx_run_query query{0, 1};
+    lacx_runs_result res{};
+    if (lacx_decoder_runs_batch_device(dec, &span, &query, 1, &det, 1, nullptr, nullptr, &res, nullptr) != LACX_OK) {
+        std::cerr << "Refused: " << lacx_decode_last_error() << "\n";
+        return done(2);
+    }
+    if (res.lost_blocks) {
+        std::cerr << "Refused: " << res.lost_blocks << " lost blocks: silence cannot be told from loss\n";
+        return done(2);
+    }
+    const lacx_run* runs = nullptr;
+    uint64_t count = 0;
+    (void)lacx_decoder_item_runs(dec, 0, 0, &runs, &count);
+    std::vector<lacx_run> pieces;  // [start, start + frames)
+    uint64_t at = 0;
+    for (uint64_t k = 0; k <= count; ++k) {
+        const uint64_t start = k < count ? runs[k].start : res.frames, n = k < count ? runs[k].frames : 0;
+        if (start > at) {
+            const uint64_t lo = at > pad ? at - pad : 0, hi = res.frames - start > pad ? start + pad : res.frames;
+            if (!pieces.empty() && lo <= pieces.back().start + pieces.back().frames) pieces.back().frames = std::max(pieces.back().start + pieces.back().frames, hi) - pieces.back().start;
+            else pieces.push_back(lacx_run{lo, hi - lo});
+        }
+        at = std::max(at, start + n);
+    }
+    if (pieces.empty()) {
+        std::cout << "Split " << in_path << ": all " << res.frames << " frames are silence, nothing written\n";
+        return done(0);
+    }
+    std::vector<lacx_edit_segment> segs;
+    std::vector<lacx_edit_output> outs;
+    for (const lacx_run& p : pieces) {
+        lacx_edit_output o{};
+        o.stereo_mode = 2;
+        o.first_segment = (uint32_t)segs.size();
+        o.segments = 1;
+        outs.push_back(o);
+        segs.push_back(lacx_edit_segment{file.data(), file.size(), p.start, p.frames});
+    }
+    std::vector<lacx_span> spans(outs.size(), lacx_span{});
+    std::vector<lacx_edit_result> er(outs.size(), lacx_edit_result{});
+    const int rc = lacx_transcode_batch(dec, enc, segs.data(), (uint32_t)segs.size(), outs.data(), (uint32_t)outs.size(), verify ? LACX_TRANSCODE_VERIFY : 0u,
+                                        spans.data(), nullptr, er.data(), nullptr);
+    int status = rc == LACX_OK ? 0 : rc == LACX_E_MISMATCH ? 1 : 2;
+    if (status == 2) std::cerr << (rc == LACX_E_INVALID ? "Refused: " : "Error: ") << lacx_decode_last_error() << "\n";
+    if (status == 1) std::cerr << "Verify failed: " << lacx_decode_last_error() << "\n";
+    for (size_t k = 0; status == 0 && k < pieces.size(); ++k) {
+        char number[24];
+        std::snprintf(number, sizeof(number), "%04zu", k + 1);
+        const std::string path = prefix + number + ".lac";
+        if (!save_file(path, spans[k].data, spans[k].size)) {
+            std::cerr << "Failed to write LAC file: " << path << "\n";
+            status = 2;
+            break;
+        }
+        std::cout << "Piece " << (k + 1) << " start=" << pieces[k].start << " frames=" << pieces[k].frames << " data_crc32=" << std::hex << er[k].data_crc32 << std::dec
+                  << (er[k].verified ? ", verified" : "") << " -> " << path << "\n";
+    }
+    for (const lacx_span& s : spans)
+        if (s.data) lacx_free(const_cast<uint8_t*>(s.data));
+    return done(status);
+}
+
 struct Encoded {
     const uint8_t* data = nullptr;
     uint64_t size = 0;
@@ -1064,6 +1369,8 @@ int main(int argc, char** argv) {
     if (mode == "digest" && argc >= 3) return digest_command(argc, argv);
     if (mode == "stats" && argc >= 3) return stats_command(argc, argv);
     if (mode == "inspect" && argc >= 3) return inspect_command(argc, argv);
+    if (mode == "find" && argc >= 3) return find_command(argc, argv);
+    if (mode == "split" && argc >= 4) return split_command(argc, argv);
     if (mode == "manifest" && argc == 4) return manifest_command(argv);
     if (mode == "check" && argc == 4) return check_command(argv);
     if (mode == "protect" && argc >= 4) return protect_command(argc, argv);
