@@ -7,6 +7,7 @@
 #include "import_msg.h"
 #include "inspect_plan.h"
 #include "inspect_rows.h"
+#include "loudness_rows.h"
 #include "runs_rows.h"
 #include "stats_rows.h"
 
@@ -36,7 +37,7 @@ void decoder_release(lacx_decoder* d) {
     if (d->e0) (void)hipEventDestroy(d->e0);
     if (d->e1) (void)hipEventDestroy(d->e1);
     if (d->stream) (void)hipStreamDestroy(d->stream);
-    for (Buf* b : {&d->pay, &d->stage, &d->pcm, &d->blocks, &d->image, &d->tables, &d->edit_stage, &d->edit_dst, &d->edit_tab, &d->runs_list}) buf_free(*b);
+    for (Buf* b : {&d->pay, &d->stage, &d->pcm, &d->blocks, &d->image, &d->tables, &d->edit_stage, &d->edit_dst, &d->edit_tab, &d->runs_list, &d->loud}) buf_free(*b);
     *d = lacx_decoder{};
 }
 // lacx_decode (no handle): one decoder per device for the life of the process (never freed: releasing device memory from
@@ -111,6 +112,8 @@ struct DecodeJob {
     lacx_stats* stres = nullptr;         // stats: [n]
     bool runs = false;                   // salvage in the blocks form with the run finder (DecodePlan::runs); detectors in BatchIn
     lacx_runs_result* rres = nullptr;    // runs: [n]
+    bool loudness = false;               // the digest form with the loudness kernels in k_digest's place (DecodePlan::loudness)
+    lacx_loudness* lres = nullptr;       // loudness: [n]
 };
 static_assert(sizeof(StatsAcc) == kStatsRowBytes, "the plan lays the accumulator rows out kStatsRowBytes apart");
 
@@ -282,7 +285,16 @@ DevErr launch_and_wait(lacx_decoder* d, const DecodeJob& job, const DecodePlan& 
         if (DevErr e = chk(launch_stats_blocks(plan_stats_args(plan, a, d->d_meta()), st), "stats launch")) return e;
     if (plan.runs)  // in the same slot
         if (DevErr e = chk(launch_runs(plan_runs_args(plan, a, d->d_meta(), d->runs_list.as<lacx_run>()), st), "runs launch")) return e;
+    if (plan.loudness)  // behind k_ms_inverse: the slot k_digest has in a digest job
+        if (DevErr e = chk(launch_loudness(plan_loud_args(plan, d->d_meta(), d->loud.as<uint8_t>()), st), "loudness launch")) return e;
     if (DevErr e = chk(hipEventRecord(d->e1, st), "event record")) return e;
+    if (plan.loudness && plan.loud_at.total_rows) {  // the rows: 16 bytes per sub-block
+        d->loud_host.resize((size_t)plan.loud_at.total_rows);
+        if (DevErr e = chk(hipMemcpyAsync(d->loud_host.data(), d->loud.as<uint8_t>() + plan.loud_at.rows, sizeof(lacx_loudness_row) * d->loud_host.size(),
+                                          hipMemcpyDeviceToHost, st),
+                           "D2H loudness rows"))
+            return e;
+    }
     if (DevErr e = chk(hipMemcpyAsync(d->h_status(), d->d_status(), (size_t)plan.total_blocks * sizeof(uint32_t), hipMemcpyDeviceToHost, st), "D2H status"))
         return e;
     // the images of the items that decoded are valid whatever the others did: one copy for all
@@ -293,7 +305,7 @@ DevErr launch_and_wait(lacx_decoder* d, const DecodeJob& job, const DecodePlan& 
         if (DevErr e = chk(hipMemcpyAsync(d->h_meta() + res, d->d_meta() + res, sizeof(VerifyWords) * m, hipMemcpyDeviceToHost, st), "D2H verify results"))
             return e;
     // the digest form's whole answer: 8 bytes per item
-    if (plan.form == DecodeForm::digest)
+    if (plan.form == DecodeForm::digest && !plan.loudness)
         if (DevErr e = chk(hipMemcpyAsync(d->h_meta() + res, d->d_meta() + res, sizeof(DigestWords) * m, hipMemcpyDeviceToHost, st), "D2H digests"))
             return e;
     // block digests: 4 bytes per block beside the statuses
@@ -373,7 +385,12 @@ DevErr collect(lacx_decoder* d, const DecodeJob& job, const DecodePlan& plan, hi
             }
         }
         if (code[i] != LACX_OK) continue;
-        if (plan.form == DecodeForm::digest) {
+        if (plan.loudness) {  // the item's rows, and the totals from the rows
+            const LoudItem& li = reinterpret_cast<const LoudItem*>(d->h_meta() + plan.loud_at.items)[j];
+            std::vector<lacx_loudness_row>& rows = d->item_loud[i];
+            if (li.rows) rows.assign(d->loud_host.begin() + (size_t)li.row0, d->loud_host.begin() + (size_t)(li.row0 + li.rows));
+            if (job.lres) job.lres[i] = loudness_of_rows(rows.data(), (uint32_t)rows.size(), p.info.channels, p.info.bit_depth, p.info.sample_rate);
+        } else if (plan.form == DecodeForm::digest) {
             const DigestWords& w = reinterpret_cast<const DigestWords*>(d->h_meta() + plan.at.res)[j];
             if (job.dres) job.dres[i] = make_digest(w.raw, p.info.frames, p.info.sample_rate, p.info.channels, p.info.bit_depth);
         } else if (plan.form == DecodeForm::verify) {
@@ -423,11 +440,13 @@ int decode_batch_run(lacx_decoder* d, const DecodeJob& job, std::vector<int>& co
     if (job.stats) d->item_stats.assign(job.n, {});
     if (job.rres) std::memset(job.rres, 0, sizeof(lacx_runs_result) * job.n);
     if (job.runs) d->item_runs.assign(job.n, {});
+    if (job.lres) std::memset(job.lres, 0, sizeof(lacx_loudness) * job.n);
+    if (job.loudness) d->item_loud.assign(job.n, {});
     // LACX_DECODE_BATCH_PAD=1 (tuning knob, read per call): every item's blocks start a new wave
     const char* pad_env = std::getenv("LACX_DECODE_BATCH_PAD");
     DecodePlan plan;
     const char* whole = plan_decode(job.in, job.n, job.form, job.sample_type, pad_env && pad_env[0] == '1', plan, code, err, job.salvage, job.blocks, job.stats,
-                                    job.runs, d->runs_list_cap ? d->runs_list_cap : kRunsListCap);
+                                    job.runs, d->runs_list_cap ? d->runs_list_cap : kRunsListCap, job.loudness);
     if (lacx_device_count() <= 0) whole = "no usable HIP device";
     int rc = whole ? decode_fail(LACX_E_DEVICE, whole) : LACX_OK;
     if (!whole && !plan.items.empty()) {
@@ -440,6 +459,7 @@ int decode_batch_run(lacx_decoder* d, const DecodeJob& job, std::vector<int>& co
         if (!e) e = upload_payload(d, job, plan, st);
         bool runs_rerun = false;
         if (!e && plan.runs) e = buf_grow(d->runs_list, plan.need.runs_list, plan.need.runs_list / 8 + 64);
+        if (!e && plan.loudness) e = buf_grow(d->loud, (plan.need.loud_scratch + 15u) / 16u, plan.need.loud_scratch / 128u + 64);
         if (!e) e = launch_and_wait(d, job, plan, st, &runs_rerun);
         if (!e) e = collect(d, job, plan, st, code, err, runs_rerun);
         if (prev_device >= 0) (void)hipSetDevice(prev_device);
@@ -453,6 +473,8 @@ int decode_batch_run(lacx_decoder* d, const DecodeJob& job, std::vector<int>& co
         if (job.stres) std::memset(job.stres, 0, sizeof(lacx_stats) * job.n);
         if (job.runs) d->item_runs.assign(job.n, {});
         if (job.rres) std::memset(job.rres, 0, sizeof(lacx_runs_result) * job.n);
+        if (job.loudness) d->item_loud.assign(job.n, {});
+        if (job.lres) std::memset(job.lres, 0, sizeof(lacx_loudness) * job.n);
         if (job.dres) std::memset(job.dres, 0, sizeof(lacx_digest) * job.n);
         for (uint32_t i = 0; i < job.n; ++i) {
             if (code[i] != LACX_OK) continue;
@@ -680,14 +702,21 @@ const char* check_digest_source(const lacx_digest_source& x, std::string& text) 
 // accumulator rows | acc [blocks] (StatsAcc, 16-byte aligned, zeroed), the rows left in d->item_stats, the totals in sout.
 // runs (without a grid): the run finder instead (k_runs) -- behind bad [m] the tables of runs_plan.h (16-byte aligned), the
 // lists in the decoder's list buffer, every item's lists left in d->item_runs, the totals in runs->out.
+// loud (without a grid): the loudness kernels instead (launch_loudness) -- behind bad [m] the tables of loudness_plan.h
+// (16-byte aligned), the scratch in the decoder's own buffer, every item's rows left in d->item_loud, the totals in loud->out.
+struct LoudPcm {
+    lacx_loudness* out;
+};
 struct RunsPcm {
     std::vector<BatchIn> in;  // per item its detectors, or why they are refused (BatchIn::dets, ndet, dets_why)
     lacx_runs_result* out;
 };
 int digest_pcm_run(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, hipStream_t st, lacx_digest* out, float* device_ms,
                    std::vector<int>& code, std::vector<std::string>& err, uint32_t grid = 0, bool stats = false, lacx_stats* sout = nullptr,
-                   const RunsPcm* runs = nullptr) {
+                   const RunsPcm* runs = nullptr, const LoudPcm* loud = nullptr) {
     if (device_ms) *device_ms = 0.f;
+    if (loud && loud->out) std::memset(loud->out, 0, sizeof(lacx_loudness) * n);
+    if (loud) d->item_loud.assign(n, {});
     if (runs && runs->out) std::memset(runs->out, 0, sizeof(lacx_runs_result) * n);
     if (runs) d->item_runs.assign(n, {});
     if (out) std::memset(out, 0, sizeof(lacx_digest) * n);
@@ -720,9 +749,18 @@ int digest_pcm_run(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, h
         std::vector<RunsIn> rin;
         for (size_t j = 0; runs && j < m; ++j) rin.push_back(RunsIn{runs->in[went[j]].dets, runs->in[went[j]].ndet, src[went[j]].frames});
         RunsLayout y = runs ? runs_layout(plan_detail::up16(at_blk), rin.data(), m) : RunsLayout{};
-        const size_t size = runs ? y.size : size0;
+        std::vector<LoudIn> lin;
+        for (size_t j = 0; loud && j < m; ++j) {
+            const lacx_digest_source& x = src[went[j]];
+            lin.push_back(LoudIn{x.pcm.data0, x.pcm.data1, x.frames, x.sample_rate, x.pcm.layout, (uint8_t)x.pcm.channels, x.bit_depth, true});
+        }
+        const LoudLayout ly = loud ? loud_layout(plan_detail::up16(at_blk), lin.data(), m) : LoudLayout{};
+        const size_t size = loud ? ly.size : runs ? y.size : size0;
         int prev_device = -1;
         DevErr e = decoder_open(d, &prev_device);
+        if (!e && loud)
+            if (const char* why = loud_check(lin.data(), m)) rc = decode_fail(LACX_E_DEVICE, why);
+        if (!e && loud && rc == LACX_OK) e = buf_grow(d->loud, (ly.scratch + 15u) / 16u, ly.scratch / 128u + 64);
         if (!e && y.total_tiles >= (1ull << 31)) rc = decode_fail(LACX_E_DEVICE, "batch holds 2^31 tiles or more");
         if (!e) e = buf_grow(d->tables, size, size / 8 + 256);
         if (!e && runs && rc == LACX_OK) {
@@ -748,6 +786,7 @@ int digest_pcm_run(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, h
                 reinterpret_cast<DigestWords*>(d->h_meta() + at_res)[j] = DigestWords{0, 0};
                 reinterpret_cast<unsigned long long*>(d->h_meta() + at_bad)[j] = kDigestClean;
             }
+            if (loud) loud_fill(ly, lin.data(), m, d->h_meta());
             DigestPcmArgs a;
             a.nitems = (uint32_t)m;
             a.total_units = unit_off[m];
@@ -773,9 +812,15 @@ int digest_pcm_run(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, h
                 ra.src = a.src;
                 ra.bad = a.bad;
             }
-            if (!e) e = runs ? chk(launch_runs_pcm(ra, st), "runs launch") : stats ? chk(launch_stats_pcm_blocks(sa, st), "stats launch") : chk(grid ? launch_digest_pcm_blocks(ba, st) : launch_digest_pcm(a, st), "digest launch");
+            if (!e && loud) e = chk(launch_loudness(loud_args(ly, m, d->d_meta(), d->loud.as<uint8_t>(), a.bad), st), "loudness launch");
+            if (!e && !loud) e = runs ? chk(launch_runs_pcm(ra, st), "runs launch") : stats ? chk(launch_stats_pcm_blocks(sa, st), "stats launch") : chk(grid ? launch_digest_pcm_blocks(ba, st) : launch_digest_pcm(a, st), "digest launch");
             if (!e) e = chk(hipEventRecord(d->e1, st), "event record");
-            if (!e) e = chk(hipMemcpyAsync(d->h_meta() + at_res, d->d_meta() + at_res, (runs ? at_blk : size) - at_res, hipMemcpyDeviceToHost, st), "D2H digests");
+            if (!e) e = chk(hipMemcpyAsync(d->h_meta() + at_res, d->d_meta() + at_res, (runs || loud ? at_blk : size) - at_res, hipMemcpyDeviceToHost, st), "D2H digests");
+            if (!e && loud && ly.total_rows) {
+                d->loud_host.resize((size_t)ly.total_rows);
+                e = chk(hipMemcpyAsync(d->loud_host.data(), d->loud.as<uint8_t>() + ly.rows, sizeof(lacx_loudness_row) * d->loud_host.size(), hipMemcpyDeviceToHost, st),
+                        "D2H loudness rows");
+            }
             if (!e) e = chk(hipStreamSynchronize(st), "synchronize");
             if (!e && device_ms) (void)hipEventElapsedTime(device_ms, d->e0, d->e1);
             if (!e && runs)
@@ -799,6 +844,13 @@ int digest_pcm_run(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, h
                     unsigned long long index = 0;
                     (void)import_bad_message(b, x.bit_depth, &ch, &index, err[i]);
                     code[i] = LACX_E_INVALID;
+                    continue;
+                }
+                if (loud) {
+                    const LoudItem& li = reinterpret_cast<const LoudItem*>(d->h_meta() + ly.items)[j];
+                    std::vector<lacx_loudness_row>& rows = d->item_loud[i];
+                    if (li.rows) rows.assign(d->loud_host.begin() + (size_t)li.row0, d->loud_host.begin() + (size_t)(li.row0 + li.rows));
+                    if (loud->out) loud->out[i] = loudness_of_rows(rows.data(), (uint32_t)rows.size(), (uint8_t)x.pcm.channels, x.bit_depth, x.sample_rate);
                     continue;
                 }
                 if (runs) {
@@ -836,6 +888,8 @@ int digest_pcm_run(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, h
         if (sout) std::memset(sout, 0, sizeof(lacx_stats) * n);
         if (runs) d->item_runs.assign(n, {});
         if (runs && runs->out) std::memset(runs->out, 0, sizeof(lacx_runs_result) * n);
+        if (loud) d->item_loud.assign(n, {});
+        if (loud && loud->out) std::memset(loud->out, 0, sizeof(lacx_loudness) * n);
         for (uint32_t i = 0; i < n; ++i) {
             if (code[i] != LACX_OK) continue;
             code[i] = rc;
@@ -1225,6 +1279,56 @@ int lacx_decoder_item_runs(const lacx_decoder* d, uint32_t item, uint32_t detect
     if (detector >= d->item_runs[item].size()) return decode_fail(LACX_E_INVALID, "no such detector of that item in the last runs call");
     *runs = d->item_runs[item][detector].data();
     *count = d->item_runs[item][detector].size();
+    return LACX_OK;
+}
+
+// ---- loudness (lacx.h) ----
+int lacx_decoder_loudness_batch_device(lacx_decoder* d, const lacx_span* lacs, uint32_t n, void* stream, int* item_rc, lacx_loudness* out,
+                                       float* device_ms) {
+    if (!d) return decode_fail(LACX_E_INVALID, "null decoder");
+    if (!lacs || n == 0) return decode_fail(LACX_E_INVALID, "null argument or empty batch");
+    std::vector<BatchIn> in(n);
+    for (uint32_t i = 0; i < n; ++i) in[i] = BatchIn{lacs[i].data, lacs[i].size, nullptr, nullptr, 0};
+    DecodeJob job{in.data(), n, DecodeForm::digest, kWholeStreams, static_cast<hipStream_t>(stream), nullptr, nullptr, device_ms};
+    job.loudness = true;
+    job.lres = out;
+    return run_batch(d, job, item_rc);
+}
+
+int lacx_decoder_loudness_pcm_batch_device(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, void* stream, int* item_rc,
+                                           lacx_loudness* out, float* device_ms) {
+    if (!d) return decode_fail(LACX_E_INVALID, "null decoder");
+    if (!src || n == 0) return decode_fail(LACX_E_INVALID, "null argument or empty batch");
+    const LoudPcm loud{out};
+    std::vector<int> code;
+    std::vector<std::string> err;
+    const int rc = digest_pcm_run(d, src, n, static_cast<hipStream_t>(stream), nullptr, device_ms, code, err, 0, false, nullptr, nullptr, &loud);
+    return batch_outcome(d, rc, code, err, item_rc);
+}
+
+int lacx_decoder_item_loudness_rows(const lacx_decoder* d, uint32_t i, const lacx_loudness_row** rows, uint32_t* count) {
+    if (rows) *rows = nullptr;
+    if (count) *count = 0;
+    if (!d || !rows || !count) return decode_fail(LACX_E_INVALID, "null argument");
+    if (i >= d->item_loud.size()) return decode_fail(LACX_E_INVALID, "no such item in the last loudness call");
+    *rows = d->item_loud[i].data();
+    *count = (uint32_t)d->item_loud[i].size();
+    return LACX_OK;
+}
+
+int lacx_loudness_combine(const lacx_loudness_row* const* rows, const uint32_t* counts, const uint8_t* channels, const uint8_t* bit_depths,
+                          const uint32_t* sample_rates, uint32_t nsets, lacx_loudness* out) {
+    if (out) std::memset(out, 0, sizeof(*out));
+    if (!out || !rows || !counts || !channels || !bit_depths || !sample_rates || nsets == 0) return decode_fail(LACX_E_INVALID, "null argument or no sets");
+    std::vector<LoudSet> sets(nsets);
+    for (uint32_t k = 0; k < nsets; ++k) {
+        if (!rows[k] && counts[k]) return decode_fail(LACX_E_INVALID, "null argument");
+        if (channels[k] != 1 && channels[k] != 2) return decode_fail(LACX_E_INVALID, "unsupported channel count");
+        if (bit_depths[k] != 16 && bit_depths[k] != 24) return decode_fail(LACX_E_INVALID, "unsupported bit depth: " + std::to_string((int)bit_depths[k]));
+        if (loud_rate_index(sample_rates[k]) < 0) return decode_fail(LACX_E_INVALID, "unsupported sample rate: " + std::to_string(sample_rates[k]));
+        sets[k] = LoudSet{rows[k], counts[k], channels[k], bit_depths[k], sample_rates[k]};
+    }
+    *out = loudness_combine(sets.data(), nsets);
     return LACX_OK;
 }
 

@@ -11,6 +11,7 @@
 #include "container.h"
 #include "lacx.h"
 #include "lacx_types.h"
+#include "loudness_plan.h"
 #include "manifest.h"
 #include "runs_plan.h"
 
@@ -70,6 +71,10 @@ struct BatchIn {
 // row of kStatsRowBytes per global block instead, zeroed with the tables.
 // ... and of a runs job (DecodePlan::runs, lacx_decoder_runs_batch_device): the same salvage job with k_runs (runs_core.h)
 // in that slot -- behind present [m] the tables of runs_plan.h (DecodePlan::runs_at), the lists in a buffer of their own.
+// The digest form is also that of a loudness job (DecodePlan::loudness, lacx_decoder_loudness_batch_device): the same strict
+// job with k_ms_inverse in place and then the four loudness kernels (loudness_core.h) in the slot k_digest has -- behind
+// res [m] the tables of loudness_plan.h (DecodePlan::loud_at), whose items are the decoder's own PCM buffers as planar
+// int32 sources; the scratch is a buffer of its own.
 enum class DecodeForm { wav, device, host, verify, digest, blocks };
 constexpr int kWholeStreams = -1;
 constexpr size_t kStatsRowBytes = 96;  // sizeof(StatsAcc), stats_core.h (k_stats.hip asserts it)
@@ -104,6 +109,7 @@ struct TableLayout {
     size_t judged = 0, raw = 0, expect = 0;  // block digests only
     size_t stats = 0;                        // stats job only
     size_t runs = 0;                         // runs job only: RunsLayout::base
+    size_t loud = 0;                         // loudness job only: LoudLayout::base
 };
 
 struct DecodePlan {
@@ -116,6 +122,8 @@ struct DecodePlan {
     bool runs = false;     // salvage job in the blocks form with the run finder's tables (no block digests, no statistics)
     uint64_t runs_list_cap = 0;
     RunsLayout runs_at{};  // ... inside the tables (byte offsets from the tables' first byte)
+    bool loudness = false; // strict job in the digest form with the loudness kernels in k_digest's place
+    LoudLayout loud_at{};  // ... inside the tables, and the scratch's layout
     bool window() const { return sample_type != kWholeStreams; }
     bool own_pcm() const { return form != DecodeForm::device || window(); }  // into the decoder's PCM buffers
     bool post_units() const { return window() || form == DecodeForm::verify || form == DecodeForm::wav || form == DecodeForm::digest || blocks || stats || runs; }
@@ -134,9 +142,9 @@ struct DecodePlan {
     // (and behind the host source, where there is one); blocks: status and flag entries; pcm_frames: samples of each
     // channel's buffer; image, stage (the pinned payload stage of a window job), tables: bytes.  stats_rows: the
     // accumulator rows of a stats job, which lie inside the tables at TableLayout::stats.  runs_list: the entries
-    // (lacx_run) of a runs job's list buffer.
+    // (lacx_run) of a runs job's list buffer.  loud_scratch: the bytes of a loudness job's scratch.
     struct {
-        uint64_t payload, blocks, pcm_frames, image, stage, tables, stats_rows, runs_list;
+        uint64_t payload, blocks, pcm_frames, image, stage, tables, stats_rows, runs_list, loud_scratch;
     } need{};
 };
 
@@ -207,7 +215,7 @@ inline int check_manifest(const BatchIn& x, const lacx_stream_info& f, std::vect
 // bytes of its present blocks.
 inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, int sample_type, bool pad_waves, DecodePlan& plan,
                                std::vector<int>& code, std::vector<std::string>& err, bool salvage = false, bool blocks = false,
-                               bool stats = false, bool runs = false, uint64_t runs_list_cap = kRunsListCap) {
+                               bool stats = false, bool runs = false, uint64_t runs_list_cap = kRunsListCap, bool loudness = false) {
     using namespace plan_detail;
     plan = DecodePlan{};
     plan.form = form;
@@ -216,6 +224,7 @@ inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, i
     plan.blocks = blocks;
     plan.stats = stats;
     plan.runs = runs;
+    plan.loudness = loudness;
     const bool window = plan.window(), own_pcm = plan.own_pcm(), wav = form == DecodeForm::wav, verify = form == DecodeForm::verify,
                digest = form == DecodeForm::digest, quiet = form == DecodeForm::blocks;
     code.assign(n, LACX_OK);
@@ -224,6 +233,7 @@ inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, i
     if (stats && (!quiet || blocks || !salvage)) return "statistics are a salvage job in the blocks form without block digests";
     if (runs && (!quiet || blocks || stats || !salvage)) return "runs are a salvage job in the blocks form without block digests or statistics";
     if ((quiet && !blocks && !stats && !runs) || (blocks && !salvage)) return "block digests belong to a salvage job";
+    if (loudness && (!digest || salvage)) return "loudness is a strict job in the digest form";
     plan.items.reserve(n);
     uint32_t v3_blocks = 0;
     for (uint32_t i = 0; i < n; ++i) {
@@ -349,7 +359,15 @@ inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, i
             for (uint32_t k = 0; k < r.ndet; ++k) plan.need.runs_list += runs_reserve(r.frames, r.dets[k].min_frames, runs_list_cap);
         plan.runs_list_cap = runs_list_cap;
     }
-    at.size = runs ? plan.runs_at.size : stats ? at.stats + kStatsRowBytes * T : blocks ? at.expect + (plan.judged ? 4 * T : 0) : salvage ? at.win + 4 * m : verify ? at.res + sizeof(VerifyWords) * m : digest ? at.res + sizeof(DigestWords) * m : window ? at.win + sizeof(WindowOut) * m : end;
+    if (loudness) {  // the items' addresses are plan_fill_tables's; the layout needs frames, channels and rates alone
+        std::vector<LoudIn> lin;
+        for (const PlanItem& p : plan.items) lin.push_back(LoudIn{nullptr, nullptr, p.item.frames, p.info.sample_rate, (uint32_t)LACX_PCM_PLANAR_I32, p.info.channels, p.info.bit_depth, false});
+        if (const char* why = loud_check(lin.data(), m)) return why;
+        at.loud = up16(at.res + sizeof(DigestWords) * m);
+        plan.loud_at = loud_layout(at.loud, lin.data(), m);
+        plan.need.loud_scratch = plan.loud_at.scratch;
+    }
+    at.size = loudness ? plan.loud_at.size : runs ? plan.runs_at.size : stats ? at.stats + kStatsRowBytes * T : blocks ? at.expect + (plan.judged ? 4 * T : 0) : salvage ? at.win + 4 * m : verify ? at.res + sizeof(VerifyWords) * m : digest ? at.res + sizeof(DigestWords) * m : window ? at.win + sizeof(WindowOut) * m : end;
     plan.need.payload = (plan.host_src ? plan.src_at + plan.host_src_bytes : plan.total_pay) + kDecodeTailPad;
     plan.need.blocks = T;
     plan.need.pcm_frames = own_pcm ? plan.pcm_total : 0;
@@ -455,6 +473,13 @@ inline void plan_fill_tables(const DecodePlan& plan, const BatchIn* in, const Pl
         RunsLayout y = plan.runs_at;
         runs_fill(y, rin.data(), m, plan.runs_list_cap, h);
     }
+    if (plan.loudness) {  // every item as a planar int32 source: its place in the decoder's own PCM buffers
+        std::vector<LoudIn> lin;
+        for (const PlanItem& p : plan.items)
+            lin.push_back(LoudIn{base.left + p.pcm_at, p.item.channels == 2 ? base.right + p.pcm_at : nullptr, p.item.frames, p.info.sample_rate,
+                                 (uint32_t)LACX_PCM_PLANAR_I32, p.info.channels, p.info.bit_depth, false});
+        loud_fill(plan.loud_at, lin.data(), m, h);
+    }
     if (!plan.lane_blk.empty()) std::memcpy(h + at.lane_blk, plan.lane_blk.data(), 4 * plan.lane_blk.size());
     if (!plan.v2_items.empty()) std::memcpy(h + at.v2_items, plan.v2_items.data(), 4 * plan.v2_items.size());
 }
@@ -492,7 +517,8 @@ inline DecodeArgs plan_args(const DecodePlan& plan, const uint8_t* tables, const
         if (plan.judged) a.block_expect = reinterpret_cast<const uint32_t*>(tables + at.expect);
         a.no_output = plan.form == DecodeForm::blocks;
     }
-    if (plan.form == DecodeForm::digest) a.digest = reinterpret_cast<DigestWords*>(const_cast<uint8_t*>(tables) + at.res);
+    // (a loudness job has no digest: launch_decode then ends with k_ms_inverse in place, and the loudness kernels follow it)
+    if (plan.form == DecodeForm::digest && !plan.loudness) a.digest = reinterpret_cast<DigestWords*>(const_cast<uint8_t*>(tables) + at.res);
     if (plan.stats || plan.runs) a.no_output = true;  // launch_decode ends with k_ms_inverse; k_stats_blocks follows it (plan_stats_args)
     return a;
 }
@@ -511,6 +537,11 @@ inline RunsArgs plan_runs_args(const DecodePlan& plan, const DecodeArgs& a, cons
     r.dec = a;
     runs_args(plan.runs_at, plan.items.size(), tables, list, r);
     return r;
+}
+
+// A loudness job's arguments for the four loudness kernels: the tables of loudness_plan.h inside the tables, and the scratch.
+inline LoudArgs plan_loud_args(const DecodePlan& plan, const uint8_t* tables, uint8_t* scratch) {
+    return loud_args(plan.loud_at, plan.items.size(), tables, scratch, nullptr);
 }
 
 }  // namespace lacx

@@ -29,6 +29,7 @@ struct lacx_decoder {
     lacx::Buf edit_dst{{{false, 1, "hipMalloc(edit destination)"}}};
     lacx::Buf edit_tab{{{false, 1, "hipMalloc(edit tables)"}, {true, 1, "hipHostMalloc(edit tables)"}}};
     lacx::Buf runs_list{{{false, 16, "hipMalloc(run lists)"}}};  // a runs job's interior runs (lacx_run), runs_plan.h
+    lacx::Buf loud{{{false, 16, "hipMalloc(loudness scratch)"}}};  // a loudness job's states, partial sums and rows, loudness_plan.h
     uint64_t runs_list_cap = 0;  // R of a runs job (0: kRunsListCap); LACX_RUNS_LIST_CAP at creation, tests force the second run with it
     uint8_t* d_pay() const { return static_cast<uint8_t*>(pay.part[0].p); }
     uint8_t* h_pay() const { return static_cast<uint8_t*>(stage.part[0].p); }
@@ -47,6 +48,8 @@ struct lacx_decoder {
     std::vector<std::vector<lacx_block_stats>> item_stats;   // the last stats call's rows per item
     std::vector<lacx_run> runs_host;                             // ... as the device left them (k_runs's list buffer)
     std::vector<std::vector<std::vector<lacx_run>>> item_runs;  // the last runs call's lists per item and detector
+    std::vector<lacx_loudness_row> loud_host;                    // the last loudness call's rows as the device left them
+    std::vector<std::vector<lacx_loudness_row>> item_loud;       // ... per item
     std::vector<std::vector<lacx_block_info>> item_info;     // the last inspection call's rows per item
     // ... and, where it asked for partition detail, the entries of all its blocks: [T][2][256] each, item i's blocks
     // from info_block0[i] on (~0u: the item has none)

@@ -1,5 +1,5 @@
 // kernels.h -- host-visible interface of the kernel translation units (k_front.hip, k_analyze.hip, k_emit.hip,
-// decode.hip, k_digest.hip, k_blockdigest.hip, k_stats.hip, k_runs.hip, k_inspect.hip, k_recovery.hip, wide.hip, k_import.hip, k_edit.hip).
+// decode.hip, k_digest.hip, k_blockdigest.hip, k_stats.hip, k_runs.hip, k_loudness.hip, k_inspect.hip, k_recovery.hip, wide.hip, k_import.hip, k_edit.hip).
 #pragma once
 #include <cstdlib>
 #include <hip/hip_runtime_api.h>
@@ -203,6 +203,11 @@ hipError_t launch_inspect(const InspectArgs& args, hipStream_t stream);
 // (which for such a job ends with k_ms_inverse), and over device-resident source PCM.
 hipError_t launch_runs(const RunsArgs& args, hipStream_t stream);
 hipError_t launch_runs_pcm(const RunsArgs& args, hipStream_t stream);
+
+// Loudness (k_loudness.hip, loudness_core.h): k_loud_states, k_loud_carry, k_loud_energy and k_loud_rows over the items of
+// a loudness job, on the same stream behind launch_decode (which for such a job ends with k_ms_inverse) or over
+// device-resident source PCM: one form, the items say where their PCM lies (loudness_plan.h).
+hipError_t launch_loudness(const LoudArgs& args, hipStream_t stream);
 
 // Recovery data (k_recovery.hip, recovery_core.h): k_gf_combine over the task table, one launch per accumulator tier that
 // has tasks, then k_slice_crc over the listed byte ranges.

@@ -6,6 +6,7 @@
 struct lacx_block_info;  // lacx.h
 struct lacx_run_detector;
 struct lacx_run;
+struct lacx_loudness_row;
 
 namespace lacx {
 
@@ -248,5 +249,45 @@ struct InspectArgs {
     lacx_block_info* rows = nullptr;               // [dec.total_blocks]
     uint8_t* mode_k = nullptr;                     // [dec.total_blocks][2][256], zero on entry, or null
     uint32_t* part_bits = nullptr;                 // [dec.total_blocks][2][256], zero on entry, or null
+};
+// Loudness (k_loud_* of k_loudness.hip, loudness_core.h): the tables loudness_plan.h lays out and the job's scratch.
+// One form for both jobs: an item is PCM in a layout -- a stream's is the decoder's planar int32 staging as k_ms_inverse
+// left it (validate 0: its blocks' statuses say whether it counts), a source's its own (validate 1: an invalid sample
+// lowers bad[j]).
+constexpr uint32_t kLoudChunk = 256;               // frames per chunk, counted in the item's frames from 0
+struct LoudFilter {                                // the K-weighting of one sample rate (loudness_plan.h makes it)
+    double sb[3], sna[2];                          // shelf: b0 b1 b2, -a1 -a2
+    double hb[3], hna[2];                          // high-pass
+    double A[4][4];                                // kLoudChunk zero-input steps as a map of the four state words
+};
+struct LoudState {                                 // 32 bytes: shelf s1 s2, high-pass s1 s2
+    double s[4];
+};
+struct LoudPartial {                               // 16 bytes: the chunk's sums in its first and its second sub-block
+    double p[2];
+};
+struct LoudItem {
+    const void* data0;                             // as DigestSource
+    const void* data1;
+    unsigned long long frames;                     // the item's frames: what may be loaded, and is validated
+    unsigned long long used;                       // rows * sub: the frames that are filtered
+    unsigned long long lane0;                      // the item's first record in the state and partial arrays
+    unsigned long long row0;                       // the item's first row
+    uint32_t chunks, rows;                         // ceil(frames / kLoudChunk), floor(frames / sub)
+    uint32_t sub, layout;                          // frames per sub-block: sample_rate / 10
+    uint8_t channels, bit_depth, rate, validate;   // rate: index into the filters
+    uint32_t pad;
+};
+struct LoudArgs {
+    uint32_t nitems = 0;
+    unsigned long long total_chunks = 0, total_rows = 0;
+    const LoudFilter* filters = nullptr;           // [4]: 44 100, 48 000, 96 000, 192 000
+    const LoudItem* items = nullptr;               // [nitems]
+    const unsigned long long* chunk_off = nullptr; // [nitems + 1] prefix sums of the items' chunks
+    const unsigned long long* row_off = nullptr;   // [nitems + 1] prefix sums of the items' rows
+    LoudState* states = nullptr;                   // [sum of chunks * channels], record lane0 + chunk * channels + channel
+    LoudPartial* partials = nullptr;               // the same
+    lacx_loudness_row* rows = nullptr;             // [total_rows]
+    unsigned long long* bad = nullptr;             // [nitems] lowest digest_bad_key per item (all ones on entry), or null
 };
 }  // namespace lacx

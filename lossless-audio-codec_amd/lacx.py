@@ -121,6 +121,7 @@ EXPORTS = (
     "lacx_recovery_build_batch_view", "lacx_recovery_build", "lacx_recovery_parse", "lacx_recovery_scan_batch",
     "lacx_recovery_repair_batch_view", "lacx_recovery_repair", "lacx_decoder_item_bad_slices",
     "lacx_decoder_stats_batch_device", "lacx_decoder_stats_pcm_batch_device", "lacx_decoder_item_block_stats", "lacx_stats_combine",
+    "lacx_decoder_loudness_batch_device", "lacx_decoder_loudness_pcm_batch_device", "lacx_decoder_item_loudness_rows", "lacx_loudness_combine",
     "lacx_decoder_inspect_batch_device", "lacx_decoder_item_block_info", "lacx_decoder_item_partitions", "lacx_inspect_combine",
     "lacx_decoder_inspect_guard", "lacx_transcode_batch",
     "lacx_decoder_runs_batch_device", "lacx_decoder_runs_pcm_batch_device", "lacx_decoder_item_runs",
@@ -236,6 +237,13 @@ def lib():
                                                           C.POINTER(C.c_int), C.POINTER(Stats), C.POINTER(C.c_float)]
         L.lacx_decoder_item_block_stats.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.POINTER(BlockStats)), C.POINTER(C.c_uint32)]
         L.lacx_stats_combine.argtypes = [C.POINTER(BlockStats), C.c_uint32, C.c_uint8, C.c_uint8, C.c_uint32, C.POINTER(Stats)]
+        L.lacx_decoder_loudness_batch_device.argtypes = [C.c_void_p, C.POINTER(Span), C.c_uint32, C.c_void_p, C.POINTER(C.c_int),
+                                                         C.POINTER(Loudness), C.POINTER(C.c_float)]
+        L.lacx_decoder_loudness_pcm_batch_device.argtypes = [C.c_void_p, C.POINTER(DigestSource), C.c_uint32, C.c_void_p, C.POINTER(C.c_int),
+                                                             C.POINTER(Loudness), C.POINTER(C.c_float)]
+        L.lacx_decoder_item_loudness_rows.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.POINTER(LoudnessRow)), C.POINTER(C.c_uint32)]
+        L.lacx_loudness_combine.argtypes = [C.POINTER(C.POINTER(LoudnessRow)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8),
+                                            C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(Loudness)]
         L.lacx_decoder_inspect_batch_device.argtypes = [C.c_void_p, C.POINTER(Span), C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_int),
                                                         C.POINTER(StreamReport), C.POINTER(C.c_float)]
         L.lacx_decoder_item_block_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.POINTER(BlockInfo)), C.POINTER(C.c_uint32)]
@@ -278,7 +286,7 @@ def abi_structs() -> dict:
             "block_fault": BlockFault, "salvage_result": SalvageResult, "block_digest": BlockDigest,
             "manifest_info": ManifestInfo, "recovery_params": RecoveryParams, "recovery_info": RecoveryInfo,
             "repair_result": RepairResult, "channel_stats": ChannelStats, "block_stats": BlockStats,
-            "channel_totals": ChannelTotals, "stats": Stats, "channel_info": ChannelInfo, "block_info": BlockInfo,
+            "channel_totals": ChannelTotals, "stats": Stats, "loudness_row": LoudnessRow, "loudness": Loudness, "channel_info": ChannelInfo, "block_info": BlockInfo,
             "stream_report": StreamReport, "edit_segment": EditSegment, "edit_output": EditOutput,
             "edit_result": EditResult, "run_detector": RunDetector, "run_query": RunQuery, "run": Run,
             "run_totals": RunTotals, "runs_result": RunsResult}
@@ -951,6 +959,60 @@ class Stats(C.Structure):
         """Derived: the channel's mean over the decoded frames / 2^(b-1)."""
         n = self.decoded_frames
         return self.ch[channel].sum / n / float(1 << (self.bit_depth - 1)) if n and self.bit_depth else 0.0
+
+
+# ---- loudness: BS.1770 integrated, momentary, short-term and range (lacx.h) ----
+LOUDNESS_TOO_SHORT, LOUDNESS_SILENT = 1, 2  # LACX_LOUDNESS_*
+
+
+class LoudnessRow(C.Structure):
+    """One sub-block of sample_rate / 10 frames: the K-weighted energy per channel (lacx_loudness_row)."""
+    _fields_ = [("energy", C.c_double * 2)]
+
+
+class Loudness(C.Structure):
+    """The loudness of an item or an album (lacx_loudness): levels in LUFS, `range_lu` in LU; -inf where lacx.h says so.
+    `gain` = -18 - integrated, the ReplayGain 2 reference, as a number only: nothing is ever applied to the audio."""
+    _fields_ = [("frames", C.c_uint64), ("sample_rate", C.c_uint32), ("channels", C.c_uint8), ("bit_depth", C.c_uint8), ("flags", C.c_uint8),
+                ("reserved", C.c_uint8), ("subblocks", C.c_uint32), ("gating_blocks", C.c_uint32), ("above_absolute", C.c_uint32),
+                ("above_relative", C.c_uint32), ("integrated_lufs", C.c_double), ("relative_gate_lufs", C.c_double),
+                ("momentary_max_lufs", C.c_double), ("shortterm_max_lufs", C.c_double), ("range_lu", C.c_double)]
+
+    @property
+    def too_short(self) -> bool:
+        return bool(self.flags & LOUDNESS_TOO_SHORT)
+
+    @property
+    def silent(self) -> bool:
+        return bool(self.flags & LOUDNESS_SILENT)
+
+    @property
+    def gain(self) -> float:
+        return -18.0 - self.integrated_lufs
+
+
+def loudness_combine(sets) -> Loudness:
+    """Host only: the loudness of [(rows, channels, bit_depth, sample_rate)] -- one set gives an item's totals as
+    loudness_batch makes them, several give album loudness (lacx.h).  rows: LoudnessRow records or an (S, 2) array."""
+    n = len(sets)
+    arrays = []
+    for rows, _, _, _ in sets:
+        if isinstance(rows, np.ndarray):
+            a = np.ascontiguousarray(np.asarray(rows, dtype=np.float64).reshape(-1, 2))
+        elif isinstance(rows, C.Array):  # what loudness_batch hands out
+            a = np.frombuffer(bytes(rows), dtype=np.float64).reshape(-1, 2)
+        else:
+            a = np.array([[r.energy[0], r.energy[1]] for r in rows], dtype=np.float64).reshape(-1, 2)
+        arrays.append(a)
+    ptrs = (C.POINTER(LoudnessRow) * max(1, n))(*[C.cast(a.ctypes.data, C.POINTER(LoudnessRow)) for a in arrays])
+    counts = (C.c_uint32 * max(1, n))(*[len(a) for a in arrays])
+    channels = (C.c_uint8 * max(1, n))(*[s[1] for s in sets])
+    depths = (C.c_uint8 * max(1, n))(*[s[2] for s in sets])
+    rates = (C.c_uint32 * max(1, n))(*[s[3] for s in sets])
+    out = Loudness()
+    if lib().lacx_loudness_combine(ptrs, counts, channels, depths, rates, C.c_uint32(n), C.byref(out)) != OK:
+        raise ValueError(lib().lacx_decode_last_error().decode(errors="replace"))
+    return out
 
 
 # ---- runs: where a stream is silent, clips or holds one value (lacx.h) ----
@@ -1794,6 +1856,62 @@ class Decoder:
             raise RuntimeError(lib().lacx_decode_last_error().decode(errors="replace"))
         errors = {i: lib().lacx_decoder_item_error(self._h, i).decode(errors="replace") for i in range(n) if rcs[i] != OK}
         return self._raise_batch(rc, errors, [None if i in errors else (_copy_struct(out[i]), self._stat_rows(i)) for i in range(n)])
+
+    # ---- loudness: BS.1770 integrated, momentary, short-term and range ----
+    def _loud_rows(self, i):
+        ptr, count = C.POINTER(LoudnessRow)(), C.c_uint32()
+        if lib().lacx_decoder_item_loudness_rows(self._h, C.c_uint32(i), C.byref(ptr), C.byref(count)) != OK:
+            count.value = 0
+        rows = (LoudnessRow * count.value)()  # one copy: the rows die with the decoder's next call (a song has thousands)
+        if count.value:
+            C.memmove(rows, ptr, C.sizeof(rows))
+        return rows
+
+    def loudness_batch(self, lacs, stream: int = 0) -> list:
+        """Many streams decoded and measured after ITU-R BS.1770 as one device job, strict like digest_batch: per item
+        (Loudness, a ctypes array of LoudnessRow), None where the stream does not parse or decode (those raise BatchDecodeError once the
+        others are done).  One row per sub-block of sample_rate / 10 frames comes back, not the PCM; kernel milliseconds
+        in `last_ms`.  Nothing is applied to the audio."""
+        bufs = [np.frombuffer(x, dtype=np.uint8) for x in lacs]
+        n = len(bufs)
+        spans = (Span * max(1, n))(*[Span(b.ctypes.data_as(C.POINTER(C.c_uint8)), b.size) for b in bufs])
+        out = (Loudness * max(1, n))()
+        rc, errors = self._batch(n, lambda rcs, ms: lib().lacx_decoder_loudness_batch_device(
+            self._h, spans, C.c_uint32(n), C.c_void_p(stream), rcs, out, ms))
+        return self._raise_batch(rc, errors, [None if i in errors else (_copy_struct(out[i]), self._loud_rows(i)) for i in range(n)])
+
+    def loudness(self, lac) -> Loudness:
+        """The totals of loudness_batch of one stream; RuntimeError with the decode's message where it fails."""
+        try:
+            return self.loudness_batch([lac])[0][0]
+        except BatchDecodeError as e:
+            raise RuntimeError(e.errors[0]) from None
+
+    def loudness_pcm_batch(self, sources, stream: int = 0) -> list:
+        """Device-resident PCM measured where it lies: per item (Loudness, [LoudnessRow]) -- what loudness_batch gives for
+        the .lac made from it.  Sources as digest_pcm_blocks_batch takes them: (pcm, sample_rate, bit_depth) with pcm a
+        device tensor or a tuple (data0_ptr, data1_ptr or None, layout, channels, frames)."""
+        n = len(sources)
+        items = (DigestSource * max(1, n))()
+        for it, (pcm, rate, depth) in zip(items, sources):
+            if isinstance(pcm, (tuple, list)):
+                d0, d1, layout, channels, frames = pcm
+                it.pcm = Pcm(d0, d1, layout, channels)
+            else:
+                it.pcm, frames = pcm_of(pcm, depth)
+            it.frames, it.sample_rate, it.bit_depth = frames, rate, depth
+        out = (Loudness * max(1, n))()
+        if self._h is None:
+            raise RuntimeError("decoder is closed")
+        rcs, ms = (C.c_int * max(1, n))(), C.c_float()
+        rc = lib().lacx_decoder_loudness_pcm_batch_device(self._h, items, C.c_uint32(n), C.c_void_p(stream), rcs, out, C.byref(ms))
+        self.last_ms = float(ms.value)
+        if rc == E_INVALID and all(rcs[i] == OK for i in range(n)):  # the call's own arguments
+            raise ValueError(lib().lacx_decode_last_error().decode(errors="replace"))
+        if rc == E_DEVICE:
+            raise RuntimeError(lib().lacx_decode_last_error().decode(errors="replace"))
+        errors = {i: lib().lacx_decoder_item_error(self._h, i).decode(errors="replace") for i in range(n) if rcs[i] != OK}
+        return self._raise_batch(rc, errors, [None if i in errors else (_copy_struct(out[i]), self._loud_rows(i)) for i in range(n)])
 
     # ---- runs: where a stream is silent, clips or holds one value ----
     @staticmethod

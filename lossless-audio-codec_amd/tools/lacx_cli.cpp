@@ -21,6 +21,9 @@
 // lacx_decoder_digest_pcm_batch_device): a .lac and the WAV it was made from print the same fields.
 // stats (no counterpart in the reference's tool; `sox stat` without the floats): the audio statistics of the same two
 // kinds of file, made on the device (lacx_decoder_stats_batch_device / lacx_decoder_stats_pcm_batch_device).
+// loudness (no counterpart in the reference's tool; `loudgain`, `ffmpeg ebur128`): ITU-R BS.1770 integrated loudness, loudness
+// range, momentary and short-term maxima of the same two kinds of file, the K-weighted energy made on the device
+// (lacx_decoder_loudness_batch_device / lacx_decoder_loudness_pcm_batch_device).  It only measures.
 // inspect (`flac -a` for .lac): how each stream was coded and where its bits go, read out of the bytes on the device by a
 // parse-only walk (lacx_decoder_inspect_batch_device).
 // recompress, cut, join (no counterpart in the reference's tool; `flac -f`, `--skip` / `--until` and joining, for .lac): .lac
@@ -63,6 +66,9 @@ void usage() {
                  "  lacx_cli digest FILE...   (.lac and .wav files, told apart by content)\n"
                  "  lacx_cli stats FILE... [--blocks]   (.lac and .wav files: peaks, energy, silence and bit use as integers, one line\n"
                  "      per file; --blocks: one further line per block; exit 0 when every file gave statistics, else 1)\n"
+                 "  lacx_cli loudness FILE... [--album] [--blocks]   (.lac and .wav files: BS.1770 integrated loudness, range, momentary and\n"
+                 "      short-term maxima and gain = -18 - integrated, one line per file; --album: one further line for all files together;\n"
+                 "      --blocks: one further line per sub-block of a tenth of a second; nothing is applied to the audio; exit 0 done, 2 refused)\n"
                  "  lacx_cli inspect FILE... [--blocks] [--partitions]   (.lac files: predictors, residual modes and where the bits go, as\n"
                  "      integers, one line per file; --blocks: one further line per block; --partitions: and one per partition;\n"
                  "      a damaged stream prints its line with lost_blocks counted; exit 0 when every file was inspected, else 1)\n"
@@ -736,6 +742,142 @@ int stats_command(int argc, char** argv) {
     return status;
 }
 
+// lacx_cli loudness FILE... [--album] [--blocks]: the loudness after ITU-R BS.1770 / EBU R 128 of what every .lac decodes to
+// and of every WAV's data chunk (lacx_decoder_loudness_batch_device / lacx_decoder_loudness_pcm_batch_device): a .lac and
+// the WAV it was made from print the same numbers.  One line per file in argument order: integrated LUFS, range LU,
+// momentary and short-term maxima, and gain = -18 - integrated (the ReplayGain 2 reference) -- as text only: nothing is
+// ever applied to the audio, gain is not lossless.  --album: one further line for all files together
+// (lacx_loudness_combine over every file's rows); --blocks: one further line per sub-block.  The streams are one device
+// job, strict like digest; the WAV files' data chunks, uploaded as they are, another.  Exit 0 when every file was measured;
+// otherwise the failed files' messages on stderr, nothing on stdout, and exit 2.
+std::string loudness_text(const lacx_loudness& t) {
+    auto num = [](double x) {
+        if (std::isinf(x)) return std::string(x < 0 ? "-inf" : "inf");
+        char s[32];
+        std::snprintf(s, sizeof(s), "%.2f", x);
+        return std::string(s);
+    };
+    return "integrated=" + num(t.integrated_lufs) + " LUFS range=" + num(t.range_lu) + " LU momentary_max=" + num(t.momentary_max_lufs) +
+           " LUFS shortterm_max=" + num(t.shortterm_max_lufs) + " LUFS gain=" + num(-18.0 - t.integrated_lufs) + " dB";
+}
+
+int loudness_command(int argc, char** argv) {
+    bool album = false, per_block = false;
+    std::vector<const char*> paths;
+    for (int i = 2; i < argc; ++i) {
+        if (std::strcmp(argv[i], "--album") == 0) album = true;
+        else if (std::strcmp(argv[i], "--blocks") == 0) per_block = true;
+        else paths.push_back(argv[i]);
+    }
+    const int n = (int)paths.size();
+    if (n == 0) {
+        usage();
+        return 2;
+    }
+    std::vector<std::vector<uint8_t>> data(n);
+    std::vector<std::string> error(n);
+    std::vector<lacx_loudness> loud(n, lacx_loudness{});
+    std::vector<std::vector<lacx_loudness_row>> rows(n);
+    std::vector<int> lacs, wavs;  // indices of the files of each kind that go to the device
+    std::vector<lacx_wav_info> winfo(n, lacx_wav_info{});
+    for (int i = 0; i < n; ++i) {
+        if (!load_file(paths[i], data[i])) {
+            error[i] = "Failed to read file";
+        } else if (data[i].size() >= 4 && std::memcmp(data[i].data(), "RIFF", 4) == 0) {
+            if (lacx_wav_parse(data[i].data(), data[i].size(), &winfo[i]) != LACX_OK) error[i] = "Failed to read WAV";
+            else wavs.push_back(i);
+        } else {
+            lacs.push_back(i);
+        }
+    }
+    lacx_decoder* dec = nullptr;
+    if (lacx_decoder_create(-1, &dec) != LACX_OK) {
+        std::cerr << "Error: lacx_decoder_create failed\n";
+        return 2;
+    }
+    auto collect = [&](const std::vector<int>& which, int rc, const std::vector<int>& item_rc, const std::vector<lacx_loudness>& out) {
+        for (size_t k = 0; k < which.size(); ++k) {
+            const lacx_loudness_row* r = nullptr;
+            uint32_t count = 0;
+            if (item_rc[k] == LACX_OK && lacx_decoder_item_loudness_rows(dec, (uint32_t)k, &r, &count) == LACX_OK) {
+                loud[which[k]] = out[k];
+                rows[which[k]].assign(r, r + count);
+            } else {
+                error[which[k]] = rc == LACX_E_DEVICE || item_rc[k] == LACX_OK ? lacx_decode_last_error() : lacx_decoder_item_error(dec, (uint32_t)k);
+            }
+        }
+    };
+    if (!lacs.empty()) {
+        std::vector<lacx_span> spans;
+        for (int i : lacs) spans.push_back(lacx_span{data[i].data(), data[i].size()});
+        std::vector<int> item_rc(lacs.size(), LACX_OK);
+        std::vector<lacx_loudness> out(lacs.size());
+        const int rc = lacx_decoder_loudness_batch_device(dec, spans.data(), (uint32_t)spans.size(), nullptr, item_rc.data(), out.data(), nullptr);
+        collect(lacs, rc, item_rc, out);
+    }
+    if (!wavs.empty()) {
+        std::vector<lacx_digest_source> src;
+        std::vector<void*> dev;
+        std::vector<int> sent;
+        for (int i : wavs) {
+            const lacx_wav_info& w = winfo[i];
+            const uint64_t bytes = w.frames * w.channels * (uint64_t)(w.bit_depth / 8);
+            void* p = nullptr;
+            if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess ||
+                hipMemcpy(p, data[i].data() + w.data_offset, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+                error[i] = "Failed to upload WAV data to the device";
+                if (p) (void)hipFree(p);
+                continue;
+            }
+            lacx_digest_source s{};
+            s.pcm = lacx_pcm{p, nullptr, w.bit_depth == 16 ? LACX_PCM_INTERLEAVED_I16 : LACX_PCM_INTERLEAVED_I24, w.channels};
+            s.frames = w.frames;
+            s.sample_rate = w.sample_rate;
+            s.bit_depth = (uint8_t)w.bit_depth;
+            src.push_back(s), dev.push_back(p), sent.push_back(i);
+        }
+        if (!src.empty()) {
+            std::vector<int> item_rc(src.size(), LACX_OK);
+            std::vector<lacx_loudness> out(src.size());
+            const int rc = lacx_decoder_loudness_pcm_batch_device(dec, src.data(), (uint32_t)src.size(), nullptr, item_rc.data(), out.data(), nullptr);
+            collect(sent, rc, item_rc, out);
+        }
+        for (void* p : dev) (void)hipFree(p);
+    }
+    lacx_decoder_destroy(dec);
+    bool refused = false;
+    for (int i = 0; i < n; ++i) {
+        if (error[i].empty()) continue;
+        std::cerr << "Loudness failed: " << paths[i] << ": " << error[i] << "\n";
+        refused = true;
+    }
+    if (refused) return 2;
+    for (int i = 0; i < n; ++i) {
+        std::cout << loudness_text(loud[i]) << " " << paths[i] << "\n";
+        for (size_t s = 0; per_block && s < rows[i].size(); ++s) {
+            char line[128];
+            std::snprintf(line, sizeof(line), "  subblock=%zu energy0=%.17g energy1=%.17g", s, rows[i][s].energy[0], rows[i][s].energy[1]);
+            std::cout << line << "\n";
+        }
+    }
+    if (album) {
+        std::vector<const lacx_loudness_row*> sets;
+        std::vector<uint32_t> counts, rates;
+        std::vector<uint8_t> channels, depths;
+        for (int i = 0; i < n; ++i) {
+            sets.push_back(rows[i].data()), counts.push_back((uint32_t)rows[i].size()), rates.push_back(loud[i].sample_rate);
+            channels.push_back(loud[i].channels), depths.push_back(loud[i].bit_depth);
+        }
+        lacx_loudness all{};
+        if (lacx_loudness_combine(sets.data(), counts.data(), channels.data(), depths.data(), rates.data(), (uint32_t)n, &all) != LACX_OK) {
+            std::cerr << "Loudness failed: album: " << lacx_decode_last_error() << "\n";
+            return 2;
+        }
+        std::cout << loudness_text(all) << " album\n";
+    }
+    return 0;
+}
+
 // lacx_cli inspect FILE... [--blocks] [--partitions]: how every .lac was coded and where its bits go, read out of the bytes
 // on the device by a parse-only walk (lacx_decoder_inspect_batch_device), all files as one job.  One line of integers per
 // file in argument order; with --blocks one further line per block (its channel blocks behind it), with --partitions one
@@ -1368,6 +1510,7 @@ int main(int argc, char** argv) {
     if (mode == "verify" && argc == 4) return verify_command(argv);
     if (mode == "digest" && argc >= 3) return digest_command(argc, argv);
     if (mode == "stats" && argc >= 3) return stats_command(argc, argv);
+    if (mode == "loudness") return loudness_command(argc, argv);
     if (mode == "inspect" && argc >= 3) return inspect_command(argc, argv);
     if (mode == "find" && argc >= 3) return find_command(argc, argv);
     if (mode == "split" && argc >= 4) return split_command(argc, argv);
