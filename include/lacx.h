@@ -62,6 +62,10 @@
  *   lacx_decoder_item_loudness_rows,
  *   lacx_loudness_combine   <- how loud the audio is: ITU-R BS.1770 integrated, momentary and short-term loudness and the
  *                             loudness range of a stream or an album, the K-weighted energy made on the device
+ *   lacx_decoder_truepeak_batch_device, lacx_decoder_truepeak_pcm_batch_device,
+ *   lacx_decoder_item_truepeak_rows,
+ *   lacx_truepeak_combine   <- how far the audio can be turned up: the ITU-R BS.1770 true peak (the maximum of the 4x
+ *                             oversampled signal) of a stream or an album, in exact integers, made on the device
  *   lacx_recovery_build, lacx_recovery_build_batch_view, lacx_recovery_parse,
  *   lacx_recovery_scan_batch, lacx_recovery_repair, lacx_recovery_repair_batch_view,
  *   lacx_decoder_item_bad_slices <- bringing lost bytes back: a parity sidecar ("LACR", Reed-Solomon over GF(2^8)) beside
@@ -953,7 +957,7 @@ int lacx_decoder_item_runs(const lacx_decoder* dec, uint32_t item, uint32_t dete
 /* Loudness: ITU-R BS.1770-4 / EBU R 128 integrated, momentary and short-term loudness and the loudness range (EBU Tech
  * 3342), made on the device where the samples lie.  Stats gives peak and plain energy; loudness is the energy behind the
  * K-weighting filter, in 400 ms gating blocks, behind two gates.  Nothing is ever applied to the audio: gain is not
- * lossless, and these entry points only measure.  Out of scope: true peak, more than two channels, a lenient form.
+ * lossless, and these entry points only measure.  Out of scope: more than two channels, a lenient form (true peak: the next section).
  * Definition (csrc/loudness_core.h states every operation and its order):
  *   Input: the final left / right integer samples of the item's bit depth b, converted to double (exact); the scaling by
  *   2^-(b-1) is applied to energies on the host as the exact factor 4^-(b-1).
@@ -1023,6 +1027,83 @@ int lacx_decoder_loudness_pcm_batch_device(lacx_decoder* dec, const lacx_digest_
 int lacx_decoder_item_loudness_rows(const lacx_decoder* dec, uint32_t i, const lacx_loudness_row** rows, uint32_t* count);
 int lacx_loudness_combine(const lacx_loudness_row* const* rows, const uint32_t* counts, const uint8_t* channels,
                           const uint8_t* bit_depths, const uint32_t* sample_rates, uint32_t nsets, lacx_loudness* out);
+
+/* True peak: ITU-R BS.1770-4 Annex 2 / EBU R 128, the maximum of the 4x oversampled signal, made on the device where the
+ * samples lie.  Loudness gives the gain a levelling tool writes into a tag; the true peak is the other half of the pair: how
+ * much of that gain can be applied before the signal clips behind a D/A converter or a lossy encoder.  The largest sample
+ * (stats) can miss a peak between samples by 3 dB and more.  Nothing is ever applied to the audio.  Out of scope: a lenient
+ * form, more than two channels, applying gain.
+ * Definition (csrc/truepeak_core.h is its only statement in code).  The Annex 2 filter is exact in integers:
+ *   Coefficients c[p][k], phase p = 0..3, tap k = 0..11, the BS.1770-4 Annex 2 table times 8192 -- every entry of the
+ *   table is a whole multiple of 2^-13:
+ *     c[0] = {   14,   90, -161,  272,  -487, 1125, 7964,  -838,  390, -218,  122,  -68 }
+ *     c[1] = { -239,  240, -424,  730, -1364, 3810, 6388, -1641,  832, -477,  271, -155 }
+ *     c[2] = c[1] reversed, c[3] = c[0] reversed
+ *   (sums 8205 / 7971 / 7971 / 8205, sums of magnitudes 11749 / 16571 / 16571 / 11749).
+ *   For a channel x of an item of bit depth b, x[n] = 0 outside [0, frames): y[4n + p] = sum over k of c[p][k] x[n - k] for
+ *   n = 0 .. frames + 10 -- the full convolution: the filter delays by about 5.9 frames, and the last peak lies in the 11
+ *   flush frames behind the end.  y is an exact integer, |y| <= 16571 * 2^(b-1), and y / 8192 is the oversampled signal in
+ *   sample units.  All four phases are used at every sample rate (the standard's lower factors at higher rates are a
+ *   minimum; more phases never read lower).  Integer maxima do not depend on the order of evaluation: device, CPU twin and a
+ *   numpy restatement agree bit for bit, and a row is the same bits in any batch.
+ * lacx_truepeak_row: one per segment of 16384 frames counted from the item's frame 0 (the blocks of every stream the
+ *   encoder writes, but the grid does not read the block table); output n belongs to segment min(n, frames - 1) / 16384, so
+ *   the flush frames go to the last row.  Per channel: peak = max |y| over the row's outputs; pos = 4 (n - 16384 row) + p of
+ *   the lowest output index that attains it, 0 when peak is 0 (pos < 4 * 16395); sample_peak = max |x| over the row's
+ *   frames (-2^23 gives 8388608).  A mono item's second channel is all zero.
+ * lacx_truepeak, made on the host from the rows by lacx_truepeak_combine.  One set: frames, sample_rate, channels,
+ *   bit_depth and rows as given; per channel ch[c]: peak, position = 4n + p in the stream (the lowest on ties), sample_peak
+ *   and sample_peak_row, the first row that holds it (a row carries no frame for it); peak_channel: the channel with the
+ *   larger peak (0 on ties); true_peak = that peak / (8192 * 2^(b-1)), exact, the linear value a REPLAYGAIN_*_PEAK tag
+ *   holds; true_peak_dbtp = 20 log10 of it; sample_peak_dbfs = 20 log10 (largest sample_peak / 2^(b-1)); both -INFINITY for
+ *   all-zero audio.  flags: LACX_TRUEPEAK_OVER: a peak exceeds 8192 * 2^(b-1), an inter-sample over;
+ *   LACX_TRUEPEAK_SAMPLE_FULL: a sample sits at full scale (|x| >= 2^(b-1) - 1).  set: 0.
+ *   Several sets, an album: the totals of the set whose peak is largest -- depths are compared exactly, a 16-bit peak
+ *   shifted by 8; the lowest index on ties -- with set its index; frames and rows are summed over the sets, flags are
+ *   those of all sets, and sample_peak_dbfs is the largest of all sets.
+ * lacx_decoder_truepeak_batch_device: strict, exactly like lacx_decoder_digest_batch_device -- versions 3 and 2; the
+ *   decode, the in-place mid/side inverse, then k_truepeak (one launch) on the job's stream.  An item that does not parse or
+ *   decode keeps the decode's own code and message, gets a zeroed result and no rows, and does not cost the other items.
+ *   out: nullable array of n.
+ * lacx_decoder_truepeak_pcm_batch_device: device-resident source PCM in any LACX_PCM_* layout; the per-item host checks,
+ *   the device-found validation texts and the bounds are those of lacx_decoder_digest_pcm_batch_device.  A failed item gets a
+ *   zeroed result and no rows.
+ * lacx_decoder_item_truepeak_rows: the rows of item i of the decoder's last true-peak call, valid until its next call;
+ *   LACX_E_INVALID outside that call.
+ * lacx_truepeak_combine: host only, no device.  One set gives exactly the per-item totals the batch calls return (they use
+ *   it).  LACX_E_INVALID: null out, nsets == 0, a null array, null rows with a count > 0, channels not 1 or 2, bit depth not
+ *   16 or 24, a sample rate that is none of the four, a count that is not ceil(frames / 16384).
+ * Everything else as lacx_decoder_loudness_batch_device.  No scratch: 32 bytes per 16384 frames inside the job's tables.
+ * Time (scripts/truepeak_bench.py, profiles/truepeak_bench.txt): on 48 four-minute stereo 16-bit streams as one job
+ * 22.3 ms of kernels, 2.3 ms below the statistics' job, and 46 ms of wall against 861 ms for decode plus a float64 conv1d
+ * and amax in torch on the same device; k_truepeak alone 4.0 ms for 4.06 GB of PCM (1.3 ms for 1.02 GB at 24 bit). */
+typedef struct lacx_truepeak_row { /* 32 bytes */
+    uint64_t peak[2];
+    uint32_t pos[2];
+    uint32_t sample_peak[2];
+} lacx_truepeak_row;
+typedef struct lacx_truepeak_channel { /* 24 bytes */
+    uint64_t peak, position;
+    uint32_t sample_peak, sample_peak_row;
+} lacx_truepeak_channel;
+typedef struct lacx_truepeak {     /* 96 bytes */
+    uint64_t frames;
+    uint32_t sample_rate;
+    uint8_t channels, bit_depth, flags, peak_channel;
+    uint32_t rows, set;
+    lacx_truepeak_channel ch[2];
+    double true_peak, true_peak_dbtp, sample_peak_dbfs;
+} lacx_truepeak;
+#define LACX_TRUEPEAK_OVER 1u
+#define LACX_TRUEPEAK_SAMPLE_FULL 2u
+int lacx_decoder_truepeak_batch_device(lacx_decoder* dec, const lacx_span* lacs, uint32_t n, void* stream, int* item_rc,
+                                       lacx_truepeak* out, float* device_ms);
+int lacx_decoder_truepeak_pcm_batch_device(lacx_decoder* dec, const lacx_digest_source* src, uint32_t n, void* stream,
+                                           int* item_rc, lacx_truepeak* out, float* device_ms);
+int lacx_decoder_item_truepeak_rows(const lacx_decoder* dec, uint32_t i, const lacx_truepeak_row** rows, uint32_t* count);
+int lacx_truepeak_combine(const lacx_truepeak_row* const* rows, const uint32_t* counts, const uint8_t* channels,
+                          const uint8_t* bit_depths, const uint64_t* frames, const uint32_t* sample_rates, uint32_t nsets,
+                          lacx_truepeak* out);
 
 /* Recovery data: repairing a damaged .lac file from a parity sidecar.  Digests, salvage and the manifest all end in "this
  * block is lost"; the container has no redundancy of its own.  A recovery sidecar ("LACR") kept beside the file brings the

@@ -10,6 +10,7 @@
 #include "loudness_rows.h"
 #include "runs_rows.h"
 #include "stats_rows.h"
+#include "truepeak_rows.h"
 
 // (the entry points are declared extern "C" in lacx.h)
 // ---- decode -------------------------------------------------------------------------------------
@@ -114,6 +115,8 @@ struct DecodeJob {
     lacx_runs_result* rres = nullptr;    // runs: [n]
     bool loudness = false;               // the digest form with the loudness kernels in k_digest's place (DecodePlan::loudness)
     lacx_loudness* lres = nullptr;       // loudness: [n]
+    bool truepeak = false;               // the digest form with k_truepeak in k_digest's place (DecodePlan::truepeak)
+    lacx_truepeak* pres = nullptr;       // true peak: [n]
 };
 static_assert(sizeof(StatsAcc) == kStatsRowBytes, "the plan lays the accumulator rows out kStatsRowBytes apart");
 
@@ -287,7 +290,14 @@ DevErr launch_and_wait(lacx_decoder* d, const DecodeJob& job, const DecodePlan& 
         if (DevErr e = chk(launch_runs(plan_runs_args(plan, a, d->d_meta(), d->runs_list.as<lacx_run>()), st), "runs launch")) return e;
     if (plan.loudness)  // behind k_ms_inverse: the slot k_digest has in a digest job
         if (DevErr e = chk(launch_loudness(plan_loud_args(plan, d->d_meta(), d->loud.as<uint8_t>()), st), "loudness launch")) return e;
+    if (plan.truepeak)  // in the same slot
+        if (DevErr e = chk(launch_truepeak(plan_peak_args(plan, d->d_meta()), st), "true peak launch")) return e;
     if (DevErr e = chk(hipEventRecord(d->e1, st), "event record")) return e;
+    if (plan.truepeak && plan.peak_at.total_rows)  // the rows: 32 bytes per 16384 frames, inside the tables
+        if (DevErr e = chk(hipMemcpyAsync(d->h_meta() + plan.peak_at.rows, d->d_meta() + plan.peak_at.rows, sizeof(TpAcc) * (size_t)plan.peak_at.total_rows,
+                                          hipMemcpyDeviceToHost, st),
+                           "D2H true peak rows"))
+            return e;
     if (plan.loudness && plan.loud_at.total_rows) {  // the rows: 16 bytes per sub-block
         d->loud_host.resize((size_t)plan.loud_at.total_rows);
         if (DevErr e = chk(hipMemcpyAsync(d->loud_host.data(), d->loud.as<uint8_t>() + plan.loud_at.rows, sizeof(lacx_loudness_row) * d->loud_host.size(),
@@ -305,7 +315,7 @@ DevErr launch_and_wait(lacx_decoder* d, const DecodeJob& job, const DecodePlan& 
         if (DevErr e = chk(hipMemcpyAsync(d->h_meta() + res, d->d_meta() + res, sizeof(VerifyWords) * m, hipMemcpyDeviceToHost, st), "D2H verify results"))
             return e;
     // the digest form's whole answer: 8 bytes per item
-    if (plan.form == DecodeForm::digest && !plan.loudness)
+    if (plan.form == DecodeForm::digest && !plan.loudness && !plan.truepeak)
         if (DevErr e = chk(hipMemcpyAsync(d->h_meta() + res, d->d_meta() + res, sizeof(DigestWords) * m, hipMemcpyDeviceToHost, st), "D2H digests"))
             return e;
     // block digests: 4 bytes per block beside the statuses
@@ -390,6 +400,11 @@ DevErr collect(lacx_decoder* d, const DecodeJob& job, const DecodePlan& plan, hi
             std::vector<lacx_loudness_row>& rows = d->item_loud[i];
             if (li.rows) rows.assign(d->loud_host.begin() + (size_t)li.row0, d->loud_host.begin() + (size_t)(li.row0 + li.rows));
             if (job.lres) job.lres[i] = loudness_of_rows(rows.data(), (uint32_t)rows.size(), p.info.channels, p.info.bit_depth, p.info.sample_rate);
+        } else if (plan.truepeak) {  // likewise
+            const TpItem& ti = reinterpret_cast<const TpItem*>(d->h_meta() + plan.peak_at.items)[j];
+            std::vector<lacx_truepeak_row>& rows = d->item_peak[i];
+            truepeak_rows_of(reinterpret_cast<const TpAcc*>(d->h_meta() + plan.peak_at.rows) + ti.row0, ti.rows, rows);
+            if (job.pres) job.pres[i] = truepeak_of_rows(TpSet{rows.data(), (uint32_t)rows.size(), p.info.channels, p.info.bit_depth, p.info.frames, p.info.sample_rate});
         } else if (plan.form == DecodeForm::digest) {
             const DigestWords& w = reinterpret_cast<const DigestWords*>(d->h_meta() + plan.at.res)[j];
             if (job.dres) job.dres[i] = make_digest(w.raw, p.info.frames, p.info.sample_rate, p.info.channels, p.info.bit_depth);
@@ -442,11 +457,13 @@ int decode_batch_run(lacx_decoder* d, const DecodeJob& job, std::vector<int>& co
     if (job.runs) d->item_runs.assign(job.n, {});
     if (job.lres) std::memset(job.lres, 0, sizeof(lacx_loudness) * job.n);
     if (job.loudness) d->item_loud.assign(job.n, {});
+    if (job.pres) std::memset(job.pres, 0, sizeof(lacx_truepeak) * job.n);
+    if (job.truepeak) d->item_peak.assign(job.n, {});
     // LACX_DECODE_BATCH_PAD=1 (tuning knob, read per call): every item's blocks start a new wave
     const char* pad_env = std::getenv("LACX_DECODE_BATCH_PAD");
     DecodePlan plan;
     const char* whole = plan_decode(job.in, job.n, job.form, job.sample_type, pad_env && pad_env[0] == '1', plan, code, err, job.salvage, job.blocks, job.stats,
-                                    job.runs, d->runs_list_cap ? d->runs_list_cap : kRunsListCap, job.loudness);
+                                    job.runs, d->runs_list_cap ? d->runs_list_cap : kRunsListCap, job.loudness, job.truepeak);
     if (lacx_device_count() <= 0) whole = "no usable HIP device";
     int rc = whole ? decode_fail(LACX_E_DEVICE, whole) : LACX_OK;
     if (!whole && !plan.items.empty()) {
@@ -475,6 +492,8 @@ int decode_batch_run(lacx_decoder* d, const DecodeJob& job, std::vector<int>& co
         if (job.rres) std::memset(job.rres, 0, sizeof(lacx_runs_result) * job.n);
         if (job.loudness) d->item_loud.assign(job.n, {});
         if (job.lres) std::memset(job.lres, 0, sizeof(lacx_loudness) * job.n);
+        if (job.truepeak) d->item_peak.assign(job.n, {});
+        if (job.pres) std::memset(job.pres, 0, sizeof(lacx_truepeak) * job.n);
         if (job.dres) std::memset(job.dres, 0, sizeof(lacx_digest) * job.n);
         for (uint32_t i = 0; i < job.n; ++i) {
             if (code[i] != LACX_OK) continue;
@@ -704,8 +723,13 @@ const char* check_digest_source(const lacx_digest_source& x, std::string& text) 
 // lists in the decoder's list buffer, every item's lists left in d->item_runs, the totals in runs->out.
 // loud (without a grid): the loudness kernels instead (launch_loudness) -- behind bad [m] the tables of loudness_plan.h
 // (16-byte aligned), the scratch in the decoder's own buffer, every item's rows left in d->item_loud, the totals in loud->out.
+// peak (without a grid): k_truepeak instead -- behind bad [m] the tables of truepeak_plan.h (16-byte aligned, zeroed rows
+// included), every item's rows left in d->item_peak, the totals in peak->out.
 struct LoudPcm {
     lacx_loudness* out;
+};
+struct PeakPcm {
+    lacx_truepeak* out;
 };
 struct RunsPcm {
     std::vector<BatchIn> in;  // per item its detectors, or why they are refused (BatchIn::dets, ndet, dets_why)
@@ -713,8 +737,10 @@ struct RunsPcm {
 };
 int digest_pcm_run(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, hipStream_t st, lacx_digest* out, float* device_ms,
                    std::vector<int>& code, std::vector<std::string>& err, uint32_t grid = 0, bool stats = false, lacx_stats* sout = nullptr,
-                   const RunsPcm* runs = nullptr, const LoudPcm* loud = nullptr) {
+                   const RunsPcm* runs = nullptr, const LoudPcm* loud = nullptr, const PeakPcm* peak = nullptr) {
     if (device_ms) *device_ms = 0.f;
+    if (peak && peak->out) std::memset(peak->out, 0, sizeof(lacx_truepeak) * n);
+    if (peak) d->item_peak.assign(n, {});
     if (loud && loud->out) std::memset(loud->out, 0, sizeof(lacx_loudness) * n);
     if (loud) d->item_loud.assign(n, {});
     if (runs && runs->out) std::memset(runs->out, 0, sizeof(lacx_runs_result) * n);
@@ -755,12 +781,20 @@ int digest_pcm_run(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, h
             lin.push_back(LoudIn{x.pcm.data0, x.pcm.data1, x.frames, x.sample_rate, x.pcm.layout, (uint8_t)x.pcm.channels, x.bit_depth, true});
         }
         const LoudLayout ly = loud ? loud_layout(plan_detail::up16(at_blk), lin.data(), m) : LoudLayout{};
-        const size_t size = loud ? ly.size : runs ? y.size : size0;
+        std::vector<TpIn> tin;
+        for (size_t j = 0; peak && j < m; ++j) {
+            const lacx_digest_source& x = src[went[j]];
+            tin.push_back(TpIn{x.pcm.data0, x.pcm.data1, x.frames, x.pcm.layout, (uint8_t)x.pcm.channels, x.bit_depth, true});
+        }
+        const TpLayout ty = peak ? tp_layout(plan_detail::up16(at_blk), tin.data(), m) : TpLayout{};
+        const size_t size = peak ? ty.size : loud ? ly.size : runs ? y.size : size0;
         int prev_device = -1;
         DevErr e = decoder_open(d, &prev_device);
         if (!e && loud)
             if (const char* why = loud_check(lin.data(), m)) rc = decode_fail(LACX_E_DEVICE, why);
         if (!e && loud && rc == LACX_OK) e = buf_grow(d->loud, (ly.scratch + 15u) / 16u, ly.scratch / 128u + 64);
+        if (!e && peak)
+            if (const char* why = tp_check(tin.data(), m)) rc = decode_fail(LACX_E_DEVICE, why);
         if (!e && y.total_tiles >= (1ull << 31)) rc = decode_fail(LACX_E_DEVICE, "batch holds 2^31 tiles or more");
         if (!e) e = buf_grow(d->tables, size, size / 8 + 256);
         if (!e && runs && rc == LACX_OK) {
@@ -787,6 +821,7 @@ int digest_pcm_run(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, h
                 reinterpret_cast<unsigned long long*>(d->h_meta() + at_bad)[j] = kDigestClean;
             }
             if (loud) loud_fill(ly, lin.data(), m, d->h_meta());
+            if (peak) tp_fill(ty, tin.data(), m, d->h_meta());
             DigestPcmArgs a;
             a.nitems = (uint32_t)m;
             a.total_units = unit_off[m];
@@ -813,9 +848,12 @@ int digest_pcm_run(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, h
                 ra.bad = a.bad;
             }
             if (!e && loud) e = chk(launch_loudness(loud_args(ly, m, d->d_meta(), d->loud.as<uint8_t>(), a.bad), st), "loudness launch");
-            if (!e && !loud) e = runs ? chk(launch_runs_pcm(ra, st), "runs launch") : stats ? chk(launch_stats_pcm_blocks(sa, st), "stats launch") : chk(grid ? launch_digest_pcm_blocks(ba, st) : launch_digest_pcm(a, st), "digest launch");
+            if (!e && peak) e = chk(launch_truepeak(tp_args(ty, m, d->d_meta(), a.bad), st), "true peak launch");
+            if (!e && !loud && !peak) e = runs ? chk(launch_runs_pcm(ra, st), "runs launch") : stats ? chk(launch_stats_pcm_blocks(sa, st), "stats launch") : chk(grid ? launch_digest_pcm_blocks(ba, st) : launch_digest_pcm(a, st), "digest launch");
             if (!e) e = chk(hipEventRecord(d->e1, st), "event record");
-            if (!e) e = chk(hipMemcpyAsync(d->h_meta() + at_res, d->d_meta() + at_res, (runs || loud ? at_blk : size) - at_res, hipMemcpyDeviceToHost, st), "D2H digests");
+            if (!e) e = chk(hipMemcpyAsync(d->h_meta() + at_res, d->d_meta() + at_res, (runs || loud || peak ? at_blk : size) - at_res, hipMemcpyDeviceToHost, st), "D2H digests");
+            if (!e && peak && ty.total_rows)
+                e = chk(hipMemcpyAsync(d->h_meta() + ty.rows, d->d_meta() + ty.rows, sizeof(TpAcc) * (size_t)ty.total_rows, hipMemcpyDeviceToHost, st), "D2H true peak rows");
             if (!e && loud && ly.total_rows) {
                 d->loud_host.resize((size_t)ly.total_rows);
                 e = chk(hipMemcpyAsync(d->loud_host.data(), d->loud.as<uint8_t>() + ly.rows, sizeof(lacx_loudness_row) * d->loud_host.size(), hipMemcpyDeviceToHost, st),
@@ -851,6 +889,13 @@ int digest_pcm_run(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, h
                     std::vector<lacx_loudness_row>& rows = d->item_loud[i];
                     if (li.rows) rows.assign(d->loud_host.begin() + (size_t)li.row0, d->loud_host.begin() + (size_t)(li.row0 + li.rows));
                     if (loud->out) loud->out[i] = loudness_of_rows(rows.data(), (uint32_t)rows.size(), (uint8_t)x.pcm.channels, x.bit_depth, x.sample_rate);
+                    continue;
+                }
+                if (peak) {
+                    const TpItem& ti = reinterpret_cast<const TpItem*>(d->h_meta() + ty.items)[j];
+                    std::vector<lacx_truepeak_row>& rows = d->item_peak[i];
+                    truepeak_rows_of(reinterpret_cast<const TpAcc*>(d->h_meta() + ty.rows) + ti.row0, ti.rows, rows);
+                    if (peak->out) peak->out[i] = truepeak_of_rows(TpSet{rows.data(), (uint32_t)rows.size(), (uint8_t)x.pcm.channels, x.bit_depth, x.frames, x.sample_rate});
                     continue;
                 }
                 if (runs) {
@@ -890,6 +935,8 @@ int digest_pcm_run(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, h
         if (runs && runs->out) std::memset(runs->out, 0, sizeof(lacx_runs_result) * n);
         if (loud) d->item_loud.assign(n, {});
         if (loud && loud->out) std::memset(loud->out, 0, sizeof(lacx_loudness) * n);
+        if (peak) d->item_peak.assign(n, {});
+        if (peak && peak->out) std::memset(peak->out, 0, sizeof(lacx_truepeak) * n);
         for (uint32_t i = 0; i < n; ++i) {
             if (code[i] != LACX_OK) continue;
             code[i] = rc;
@@ -1329,6 +1376,57 @@ int lacx_loudness_combine(const lacx_loudness_row* const* rows, const uint32_t* 
         sets[k] = LoudSet{rows[k], counts[k], channels[k], bit_depths[k], sample_rates[k]};
     }
     *out = loudness_combine(sets.data(), nsets);
+    return LACX_OK;
+}
+
+// ---- true peak (lacx.h) ----
+int lacx_decoder_truepeak_batch_device(lacx_decoder* d, const lacx_span* lacs, uint32_t n, void* stream, int* item_rc, lacx_truepeak* out,
+                                       float* device_ms) {
+    if (!d) return decode_fail(LACX_E_INVALID, "null decoder");
+    if (!lacs || n == 0) return decode_fail(LACX_E_INVALID, "null argument or empty batch");
+    std::vector<BatchIn> in(n);
+    for (uint32_t i = 0; i < n; ++i) in[i] = BatchIn{lacs[i].data, lacs[i].size, nullptr, nullptr, 0};
+    DecodeJob job{in.data(), n, DecodeForm::digest, kWholeStreams, static_cast<hipStream_t>(stream), nullptr, nullptr, device_ms};
+    job.truepeak = true;
+    job.pres = out;
+    return run_batch(d, job, item_rc);
+}
+
+int lacx_decoder_truepeak_pcm_batch_device(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, void* stream, int* item_rc,
+                                           lacx_truepeak* out, float* device_ms) {
+    if (!d) return decode_fail(LACX_E_INVALID, "null decoder");
+    if (!src || n == 0) return decode_fail(LACX_E_INVALID, "null argument or empty batch");
+    const PeakPcm peak{out};
+    std::vector<int> code;
+    std::vector<std::string> err;
+    const int rc = digest_pcm_run(d, src, n, static_cast<hipStream_t>(stream), nullptr, device_ms, code, err, 0, false, nullptr, nullptr, nullptr, &peak);
+    return batch_outcome(d, rc, code, err, item_rc);
+}
+
+int lacx_decoder_item_truepeak_rows(const lacx_decoder* d, uint32_t i, const lacx_truepeak_row** rows, uint32_t* count) {
+    if (rows) *rows = nullptr;
+    if (count) *count = 0;
+    if (!d || !rows || !count) return decode_fail(LACX_E_INVALID, "null argument");
+    if (i >= d->item_peak.size()) return decode_fail(LACX_E_INVALID, "no such item in the last true peak call");
+    *rows = d->item_peak[i].data();
+    *count = (uint32_t)d->item_peak[i].size();
+    return LACX_OK;
+}
+
+int lacx_truepeak_combine(const lacx_truepeak_row* const* rows, const uint32_t* counts, const uint8_t* channels, const uint8_t* bit_depths,
+                          const uint64_t* frames, const uint32_t* sample_rates, uint32_t nsets, lacx_truepeak* out) {
+    if (out) std::memset(out, 0, sizeof(*out));
+    if (!out || !rows || !counts || !channels || !bit_depths || !frames || !sample_rates || nsets == 0) return decode_fail(LACX_E_INVALID, "null argument or no sets");
+    std::vector<TpSet> sets(nsets);
+    for (uint32_t k = 0; k < nsets; ++k) {
+        if (!rows[k] && counts[k]) return decode_fail(LACX_E_INVALID, "null argument");
+        if (channels[k] != 1 && channels[k] != 2) return decode_fail(LACX_E_INVALID, "unsupported channel count");
+        if (bit_depths[k] != 16 && bit_depths[k] != 24) return decode_fail(LACX_E_INVALID, "unsupported bit depth: " + std::to_string((int)bit_depths[k]));
+        if (loud_rate_index(sample_rates[k]) < 0) return decode_fail(LACX_E_INVALID, "unsupported sample rate: " + std::to_string(sample_rates[k]));
+        if (tp_rows(frames[k]) != counts[k]) return decode_fail(LACX_E_INVALID, "row count does not match the frames");
+        sets[k] = TpSet{rows[k], counts[k], channels[k], bit_depths[k], frames[k], sample_rates[k]};
+    }
+    *out = truepeak_combine(sets.data(), nsets);
     return LACX_OK;
 }
 

@@ -14,6 +14,7 @@
 #include "loudness_plan.h"
 #include "manifest.h"
 #include "runs_plan.h"
+#include "truepeak_plan.h"
 
 namespace lacx {
 
@@ -75,6 +76,8 @@ struct BatchIn {
 // job with k_ms_inverse in place and then the four loudness kernels (loudness_core.h) in the slot k_digest has -- behind
 // res [m] the tables of loudness_plan.h (DecodePlan::loud_at), whose items are the decoder's own PCM buffers as planar
 // int32 sources; the scratch is a buffer of its own.
+// ... and of a true-peak job (DecodePlan::truepeak, lacx_decoder_truepeak_batch_device): the same strict job with k_truepeak
+// (truepeak_core.h) in that slot -- behind res [m] the tables of truepeak_plan.h (DecodePlan::peak_at), zeroed rows included.
 enum class DecodeForm { wav, device, host, verify, digest, blocks };
 constexpr int kWholeStreams = -1;
 constexpr size_t kStatsRowBytes = 96;  // sizeof(StatsAcc), stats_core.h (k_stats.hip asserts it)
@@ -110,6 +113,7 @@ struct TableLayout {
     size_t stats = 0;                        // stats job only
     size_t runs = 0;                         // runs job only: RunsLayout::base
     size_t loud = 0;                         // loudness job only: LoudLayout::base
+    size_t peak = 0;                         // true-peak job only: TpLayout::base
 };
 
 struct DecodePlan {
@@ -124,6 +128,8 @@ struct DecodePlan {
     RunsLayout runs_at{};  // ... inside the tables (byte offsets from the tables' first byte)
     bool loudness = false; // strict job in the digest form with the loudness kernels in k_digest's place
     LoudLayout loud_at{};  // ... inside the tables, and the scratch's layout
+    bool truepeak = false; // strict job in the digest form with k_truepeak in k_digest's place
+    TpLayout peak_at{};    // ... inside the tables
     bool window() const { return sample_type != kWholeStreams; }
     bool own_pcm() const { return form != DecodeForm::device || window(); }  // into the decoder's PCM buffers
     bool post_units() const { return window() || form == DecodeForm::verify || form == DecodeForm::wav || form == DecodeForm::digest || blocks || stats || runs; }
@@ -215,7 +221,7 @@ inline int check_manifest(const BatchIn& x, const lacx_stream_info& f, std::vect
 // bytes of its present blocks.
 inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, int sample_type, bool pad_waves, DecodePlan& plan,
                                std::vector<int>& code, std::vector<std::string>& err, bool salvage = false, bool blocks = false,
-                               bool stats = false, bool runs = false, uint64_t runs_list_cap = kRunsListCap, bool loudness = false) {
+                               bool stats = false, bool runs = false, uint64_t runs_list_cap = kRunsListCap, bool loudness = false, bool truepeak = false) {
     using namespace plan_detail;
     plan = DecodePlan{};
     plan.form = form;
@@ -225,6 +231,7 @@ inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, i
     plan.stats = stats;
     plan.runs = runs;
     plan.loudness = loudness;
+    plan.truepeak = truepeak;
     const bool window = plan.window(), own_pcm = plan.own_pcm(), wav = form == DecodeForm::wav, verify = form == DecodeForm::verify,
                digest = form == DecodeForm::digest, quiet = form == DecodeForm::blocks;
     code.assign(n, LACX_OK);
@@ -234,6 +241,7 @@ inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, i
     if (runs && (!quiet || blocks || stats || !salvage)) return "runs are a salvage job in the blocks form without block digests or statistics";
     if ((quiet && !blocks && !stats && !runs) || (blocks && !salvage)) return "block digests belong to a salvage job";
     if (loudness && (!digest || salvage)) return "loudness is a strict job in the digest form";
+    if (truepeak && (!digest || salvage || loudness)) return "true peak is a strict job in the digest form";
     plan.items.reserve(n);
     uint32_t v3_blocks = 0;
     for (uint32_t i = 0; i < n; ++i) {
@@ -367,7 +375,14 @@ inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, i
         plan.loud_at = loud_layout(at.loud, lin.data(), m);
         plan.need.loud_scratch = plan.loud_at.scratch;
     }
-    at.size = loudness ? plan.loud_at.size : runs ? plan.runs_at.size : stats ? at.stats + kStatsRowBytes * T : blocks ? at.expect + (plan.judged ? 4 * T : 0) : salvage ? at.win + 4 * m : verify ? at.res + sizeof(VerifyWords) * m : digest ? at.res + sizeof(DigestWords) * m : window ? at.win + sizeof(WindowOut) * m : end;
+    if (truepeak) {  // as loudness: the items' addresses are plan_fill_tables's
+        std::vector<TpIn> tin;
+        for (const PlanItem& p : plan.items) tin.push_back(TpIn{nullptr, nullptr, p.item.frames, (uint32_t)LACX_PCM_PLANAR_I32, p.info.channels, p.info.bit_depth, false});
+        if (const char* why = tp_check(tin.data(), m)) return why;
+        at.peak = up16(at.res + sizeof(DigestWords) * m);
+        plan.peak_at = tp_layout(at.peak, tin.data(), m);
+    }
+    at.size = truepeak ? plan.peak_at.size : loudness ? plan.loud_at.size : runs ? plan.runs_at.size : stats ? at.stats + kStatsRowBytes * T : blocks ? at.expect + (plan.judged ? 4 * T : 0) : salvage ? at.win + 4 * m : verify ? at.res + sizeof(VerifyWords) * m : digest ? at.res + sizeof(DigestWords) * m : window ? at.win + sizeof(WindowOut) * m : end;
     plan.need.payload = (plan.host_src ? plan.src_at + plan.host_src_bytes : plan.total_pay) + kDecodeTailPad;
     plan.need.blocks = T;
     plan.need.pcm_frames = own_pcm ? plan.pcm_total : 0;
@@ -480,6 +495,13 @@ inline void plan_fill_tables(const DecodePlan& plan, const BatchIn* in, const Pl
                                  (uint32_t)LACX_PCM_PLANAR_I32, p.info.channels, p.info.bit_depth, false});
         loud_fill(plan.loud_at, lin.data(), m, h);
     }
+    if (plan.truepeak) {  // the same sources; the rows are zeroed here
+        std::vector<TpIn> tin;
+        for (const PlanItem& p : plan.items)
+            tin.push_back(TpIn{base.left + p.pcm_at, p.item.channels == 2 ? base.right + p.pcm_at : nullptr, p.item.frames, (uint32_t)LACX_PCM_PLANAR_I32,
+                               p.info.channels, p.info.bit_depth, false});
+        tp_fill(plan.peak_at, tin.data(), m, h);
+    }
     if (!plan.lane_blk.empty()) std::memcpy(h + at.lane_blk, plan.lane_blk.data(), 4 * plan.lane_blk.size());
     if (!plan.v2_items.empty()) std::memcpy(h + at.v2_items, plan.v2_items.data(), 4 * plan.v2_items.size());
 }
@@ -517,8 +539,9 @@ inline DecodeArgs plan_args(const DecodePlan& plan, const uint8_t* tables, const
         if (plan.judged) a.block_expect = reinterpret_cast<const uint32_t*>(tables + at.expect);
         a.no_output = plan.form == DecodeForm::blocks;
     }
-    // (a loudness job has no digest: launch_decode then ends with k_ms_inverse in place, and the loudness kernels follow it)
-    if (plan.form == DecodeForm::digest && !plan.loudness) a.digest = reinterpret_cast<DigestWords*>(const_cast<uint8_t*>(tables) + at.res);
+    // (a loudness job has no digest: launch_decode then ends with k_ms_inverse in place, and the loudness kernels follow it;
+    // a true-peak job likewise)
+    if (plan.form == DecodeForm::digest && !plan.loudness && !plan.truepeak) a.digest = reinterpret_cast<DigestWords*>(const_cast<uint8_t*>(tables) + at.res);
     if (plan.stats || plan.runs) a.no_output = true;  // launch_decode ends with k_ms_inverse; k_stats_blocks follows it (plan_stats_args)
     return a;
 }
@@ -543,5 +566,8 @@ inline RunsArgs plan_runs_args(const DecodePlan& plan, const DecodeArgs& a, cons
 inline LoudArgs plan_loud_args(const DecodePlan& plan, const uint8_t* tables, uint8_t* scratch) {
     return loud_args(plan.loud_at, plan.items.size(), tables, scratch, nullptr);
 }
+
+// A true-peak job's arguments for k_truepeak: the tables of truepeak_plan.h inside the tables.
+inline TpArgs plan_peak_args(const DecodePlan& plan, uint8_t* tables) { return tp_args(plan.peak_at, plan.items.size(), tables, nullptr); }
 
 }  // namespace lacx

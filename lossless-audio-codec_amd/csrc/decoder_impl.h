@@ -50,6 +50,7 @@ struct lacx_decoder {
     std::vector<std::vector<std::vector<lacx_run>>> item_runs;  // the last runs call's lists per item and detector
     std::vector<lacx_loudness_row> loud_host;                    // the last loudness call's rows as the device left them
     std::vector<std::vector<lacx_loudness_row>> item_loud;       // ... per item
+    std::vector<std::vector<lacx_truepeak_row>> item_peak;       // the last true-peak call's rows per item
     std::vector<std::vector<lacx_block_info>> item_info;     // the last inspection call's rows per item
     // ... and, where it asked for partition detail, the entries of all its blocks: [T][2][256] each, item i's blocks
     // from info_block0[i] on (~0u: the item has none)

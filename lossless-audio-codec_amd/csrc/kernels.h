@@ -1,5 +1,5 @@
 // kernels.h -- host-visible interface of the kernel translation units (k_front.hip, k_analyze.hip, k_emit.hip,
-// decode.hip, k_digest.hip, k_blockdigest.hip, k_stats.hip, k_runs.hip, k_loudness.hip, k_inspect.hip, k_recovery.hip, wide.hip, k_import.hip, k_edit.hip).
+// decode.hip, k_digest.hip, k_blockdigest.hip, k_stats.hip, k_runs.hip, k_loudness.hip, k_truepeak.hip, k_inspect.hip, k_recovery.hip, wide.hip, k_import.hip, k_edit.hip).
 #pragma once
 #include <cstdlib>
 #include <hip/hip_runtime_api.h>
@@ -208,6 +208,11 @@ hipError_t launch_runs_pcm(const RunsArgs& args, hipStream_t stream);
 // a loudness job, on the same stream behind launch_decode (which for such a job ends with k_ms_inverse) or over
 // device-resident source PCM: one form, the items say where their PCM lies (loudness_plan.h).
 hipError_t launch_loudness(const LoudArgs& args, hipStream_t stream);
+
+// True peak (k_truepeak.hip, truepeak_core.h): k_truepeak over the items of a true-peak job, on the same stream behind
+// launch_decode (which for such a job ends with k_ms_inverse) or over device-resident source PCM: one form, as loudness has
+// it (truepeak_plan.h).  The rows must be zero on entry.
+hipError_t launch_truepeak(const TpArgs& args, hipStream_t stream);
 
 // Recovery data (k_recovery.hip, recovery_core.h): k_gf_combine over the task table, one launch per accumulator tier that
 // has tasks, then k_slice_crc over the listed byte ranges.

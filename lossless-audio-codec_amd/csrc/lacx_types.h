@@ -7,6 +7,7 @@ struct lacx_block_info;  // lacx.h
 struct lacx_run_detector;
 struct lacx_run;
 struct lacx_loudness_row;
+struct lacx_truepeak_row;
 
 namespace lacx {
 
@@ -288,6 +289,38 @@ struct LoudArgs {
     LoudState* states = nullptr;                   // [sum of chunks * channels], record lane0 + chunk * channels + channel
     LoudPartial* partials = nullptr;               // the same
     lacx_loudness_row* rows = nullptr;             // [total_rows]
+    unsigned long long* bad = nullptr;             // [nitems] lowest digest_bad_key per item (all ones on entry), or null
+};
+// True peak (k_truepeak of k_truepeak.hip, truepeak_core.h): the tables truepeak_plan.h lays out.  One form for both jobs,
+// as loudness has it: an item is PCM in a layout -- a stream's is the decoder's planar int32 staging as k_ms_inverse left
+// it (validate 0), a source's its own (validate 1: an invalid sample lowers bad[j]).
+constexpr uint32_t kTpTileFrames = 1024;           // outputs-frames n per workgroup, counted in the item's frames from 0
+constexpr uint32_t kTpThreads = 256;               // ... four per lane
+constexpr uint32_t kTpTaps = 12, kTpPhases = 4;
+constexpr uint32_t kTpFlush = kTpTaps - 1;         // outputs-frames behind the item's last frame: n = frames .. frames + 10
+constexpr uint32_t kTpHistory = 12;                // frames staged in front of a tile: three units, of which 11 frames are read
+constexpr uint32_t kTpRowFrames = 16384;           // frames per row, counted from the item's frame 0
+constexpr uint32_t kTpPosBits = 18;                // pos < 4 * (16384 + 11) < 2^18
+struct TpAcc {                                     // 32 bytes: the device's row; all-zero bytes are the empty row
+    unsigned long long key[2];                     // per channel max of peak << kTpPosBits | (2^kTpPosBits - 1 - pos)
+    uint32_t sample_peak[2];                       // per channel max |x|
+    uint32_t pad[2];
+};
+struct TpItem {
+    const void* data0;                             // as DigestSource
+    const void* data1;
+    unsigned long long frames;
+    unsigned long long row0;                       // the item's first row
+    uint32_t tiles, rows;                          // ceil((frames + 11) / kTpTileFrames), ceil(frames / kTpRowFrames)
+    uint32_t layout;
+    uint8_t channels, bit_depth, validate, pad;
+};
+struct TpArgs {
+    uint32_t nitems = 0;
+    unsigned long long total_tiles = 0, total_rows = 0;
+    const TpItem* items = nullptr;                 // [nitems]
+    const unsigned long long* tile_off = nullptr;  // [nitems + 1] prefix sums of the items' tiles
+    TpAcc* rows = nullptr;                         // [total_rows], zero on entry
     unsigned long long* bad = nullptr;             // [nitems] lowest digest_bad_key per item (all ones on entry), or null
 };
 }  // namespace lacx

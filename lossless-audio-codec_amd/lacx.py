@@ -122,6 +122,7 @@ EXPORTS = (
     "lacx_recovery_repair_batch_view", "lacx_recovery_repair", "lacx_decoder_item_bad_slices",
     "lacx_decoder_stats_batch_device", "lacx_decoder_stats_pcm_batch_device", "lacx_decoder_item_block_stats", "lacx_stats_combine",
     "lacx_decoder_loudness_batch_device", "lacx_decoder_loudness_pcm_batch_device", "lacx_decoder_item_loudness_rows", "lacx_loudness_combine",
+    "lacx_decoder_truepeak_batch_device", "lacx_decoder_truepeak_pcm_batch_device", "lacx_decoder_item_truepeak_rows", "lacx_truepeak_combine",
     "lacx_decoder_inspect_batch_device", "lacx_decoder_item_block_info", "lacx_decoder_item_partitions", "lacx_inspect_combine",
     "lacx_decoder_inspect_guard", "lacx_transcode_batch",
     "lacx_decoder_runs_batch_device", "lacx_decoder_runs_pcm_batch_device", "lacx_decoder_item_runs",
@@ -244,6 +245,13 @@ def lib():
         L.lacx_decoder_item_loudness_rows.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.POINTER(LoudnessRow)), C.POINTER(C.c_uint32)]
         L.lacx_loudness_combine.argtypes = [C.POINTER(C.POINTER(LoudnessRow)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8),
                                             C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(Loudness)]
+        L.lacx_decoder_truepeak_batch_device.argtypes = [C.c_void_p, C.POINTER(Span), C.c_uint32, C.c_void_p, C.POINTER(C.c_int),
+                                                         C.POINTER(TruePeak), C.POINTER(C.c_float)]
+        L.lacx_decoder_truepeak_pcm_batch_device.argtypes = [C.c_void_p, C.POINTER(DigestSource), C.c_uint32, C.c_void_p, C.POINTER(C.c_int),
+                                                             C.POINTER(TruePeak), C.POINTER(C.c_float)]
+        L.lacx_decoder_item_truepeak_rows.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.POINTER(TruePeakRow)), C.POINTER(C.c_uint32)]
+        L.lacx_truepeak_combine.argtypes = [C.POINTER(C.POINTER(TruePeakRow)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8),
+                                            C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(TruePeak)]
         L.lacx_decoder_inspect_batch_device.argtypes = [C.c_void_p, C.POINTER(Span), C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_int),
                                                         C.POINTER(StreamReport), C.POINTER(C.c_float)]
         L.lacx_decoder_item_block_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.POINTER(BlockInfo)), C.POINTER(C.c_uint32)]
@@ -286,7 +294,8 @@ def abi_structs() -> dict:
             "block_fault": BlockFault, "salvage_result": SalvageResult, "block_digest": BlockDigest,
             "manifest_info": ManifestInfo, "recovery_params": RecoveryParams, "recovery_info": RecoveryInfo,
             "repair_result": RepairResult, "channel_stats": ChannelStats, "block_stats": BlockStats,
-            "channel_totals": ChannelTotals, "stats": Stats, "loudness_row": LoudnessRow, "loudness": Loudness, "channel_info": ChannelInfo, "block_info": BlockInfo,
+            "channel_totals": ChannelTotals, "stats": Stats, "loudness_row": LoudnessRow, "loudness": Loudness,
+            "truepeak_row": TruePeakRow, "truepeak_channel": TruePeakChannel, "truepeak": TruePeak, "channel_info": ChannelInfo, "block_info": BlockInfo,
             "stream_report": StreamReport, "edit_segment": EditSegment, "edit_output": EditOutput,
             "edit_result": EditResult, "run_detector": RunDetector, "run_query": RunQuery, "run": Run,
             "run_totals": RunTotals, "runs_result": RunsResult}
@@ -1011,6 +1020,62 @@ def loudness_combine(sets) -> Loudness:
     rates = (C.c_uint32 * max(1, n))(*[s[3] for s in sets])
     out = Loudness()
     if lib().lacx_loudness_combine(ptrs, counts, channels, depths, rates, C.c_uint32(n), C.byref(out)) != OK:
+        raise ValueError(lib().lacx_decode_last_error().decode(errors="replace"))
+    return out
+
+
+# ---- true peak: the BS.1770 maximum of the 4x oversampled signal (lacx.h) ----
+TRUEPEAK_OVER, TRUEPEAK_SAMPLE_FULL = 1, 2  # LACX_TRUEPEAK_*
+TRUEPEAK_ROW_FRAMES = 16384
+
+
+class TruePeakRow(C.Structure):
+    """One segment of 16384 frames: per channel max |y| of the oversampled signal times 8192, its first position inside the
+    row as 4 * frame + phase, and the largest sample (lacx_truepeak_row)."""
+    _fields_ = [("peak", C.c_uint64 * 2), ("pos", C.c_uint32 * 2), ("sample_peak", C.c_uint32 * 2)]
+
+
+class TruePeakChannel(C.Structure):
+    _fields_ = [("peak", C.c_uint64), ("position", C.c_uint64), ("sample_peak", C.c_uint32), ("sample_peak_row", C.c_uint32)]
+
+
+class TruePeak(C.Structure):
+    """The true peak of an item or an album (lacx_truepeak): `true_peak` linear (what a REPLAYGAIN_*_PEAK tag holds),
+    `true_peak_dbtp` and `sample_peak_dbfs` in dB, -inf for all-zero audio.  Nothing is ever applied to the audio."""
+    _fields_ = [("frames", C.c_uint64), ("sample_rate", C.c_uint32), ("channels", C.c_uint8), ("bit_depth", C.c_uint8), ("flags", C.c_uint8),
+                ("peak_channel", C.c_uint8), ("rows", C.c_uint32), ("set", C.c_uint32), ("ch", TruePeakChannel * 2),
+                ("true_peak", C.c_double), ("true_peak_dbtp", C.c_double), ("sample_peak_dbfs", C.c_double)]
+
+    @property
+    def over(self) -> bool:
+        return bool(self.flags & TRUEPEAK_OVER)
+
+    @property
+    def sample_full(self) -> bool:
+        return bool(self.flags & TRUEPEAK_SAMPLE_FULL)
+
+    @property
+    def position(self) -> int:
+        """4 * frame + phase of the peak in the stream (of the winning set for an album)."""
+        return int(self.ch[self.peak_channel].position)
+
+
+def truepeak_combine(sets) -> TruePeak:
+    """Host only: the true peak of [(rows, channels, bit_depth, frames, sample_rate)] -- one set gives an item's totals as
+    truepeak_batch makes them, several give the album peak (lacx.h).  rows: TruePeakRow records or their bytes."""
+    n = len(sets)
+    blobs = []
+    for rows, _, _, _, _ in sets:
+        raw = bytes(rows) if isinstance(rows, (C.Array, bytes, bytearray, np.ndarray)) else b"".join(bytes(r) for r in rows)
+        blobs.append(np.frombuffer(raw, dtype=np.uint8).copy())
+    ptrs = (C.POINTER(TruePeakRow) * max(1, n))(*[C.cast(a.ctypes.data, C.POINTER(TruePeakRow)) for a in blobs])
+    counts = (C.c_uint32 * max(1, n))(*[len(a) // C.sizeof(TruePeakRow) for a in blobs])
+    channels = (C.c_uint8 * max(1, n))(*[s[1] for s in sets])
+    depths = (C.c_uint8 * max(1, n))(*[s[2] for s in sets])
+    frames = (C.c_uint64 * max(1, n))(*[s[3] for s in sets])
+    rates = (C.c_uint32 * max(1, n))(*[s[4] for s in sets])
+    out = TruePeak()
+    if lib().lacx_truepeak_combine(ptrs, counts, channels, depths, frames, rates, C.c_uint32(n), C.byref(out)) != OK:
         raise ValueError(lib().lacx_decode_last_error().decode(errors="replace"))
     return out
 
@@ -1912,6 +1977,61 @@ class Decoder:
             raise RuntimeError(lib().lacx_decode_last_error().decode(errors="replace"))
         errors = {i: lib().lacx_decoder_item_error(self._h, i).decode(errors="replace") for i in range(n) if rcs[i] != OK}
         return self._raise_batch(rc, errors, [None if i in errors else (_copy_struct(out[i]), self._loud_rows(i)) for i in range(n)])
+
+    # ---- true peak: the BS.1770 maximum of the 4x oversampled signal ----
+    def _peak_rows(self, i):
+        ptr, count = C.POINTER(TruePeakRow)(), C.c_uint32()
+        if lib().lacx_decoder_item_truepeak_rows(self._h, C.c_uint32(i), C.byref(ptr), C.byref(count)) != OK:
+            count.value = 0
+        rows = (TruePeakRow * count.value)()  # one copy: the rows die with the decoder's next call
+        if count.value:
+            C.memmove(rows, ptr, C.sizeof(rows))
+        return rows
+
+    def truepeak_batch(self, lacs, stream: int = 0) -> list:
+        """Many streams decoded and their true peak (ITU-R BS.1770 Annex 2) taken as one device job, strict like digest_batch:
+        per item (TruePeak, a ctypes array of TruePeakRow), None where the stream does not parse or decode (those raise
+        BatchDecodeError once the others are done).  One row per 16384 frames comes back, not the PCM; kernel milliseconds in
+        `last_ms`.  Nothing is applied to the audio."""
+        bufs = [np.frombuffer(x, dtype=np.uint8) for x in lacs]
+        n = len(bufs)
+        spans = (Span * max(1, n))(*[Span(b.ctypes.data_as(C.POINTER(C.c_uint8)), b.size) for b in bufs])
+        out = (TruePeak * max(1, n))()
+        rc, errors = self._batch(n, lambda rcs, ms: lib().lacx_decoder_truepeak_batch_device(
+            self._h, spans, C.c_uint32(n), C.c_void_p(stream), rcs, out, ms))
+        return self._raise_batch(rc, errors, [None if i in errors else (_copy_struct(out[i]), self._peak_rows(i)) for i in range(n)])
+
+    def truepeak(self, lac) -> TruePeak:
+        """The totals of truepeak_batch of one stream; RuntimeError with the decode's message where it fails."""
+        try:
+            return self.truepeak_batch([lac])[0][0]
+        except BatchDecodeError as e:
+            raise RuntimeError(e.errors[0]) from None
+
+    def truepeak_pcm_batch(self, sources, stream: int = 0) -> list:
+        """Device-resident PCM measured where it lies: per item (TruePeak, [TruePeakRow]) -- what truepeak_batch gives for the
+        .lac made from it.  Sources as loudness_pcm_batch takes them."""
+        n = len(sources)
+        items = (DigestSource * max(1, n))()
+        for it, (pcm, rate, depth) in zip(items, sources):
+            if isinstance(pcm, (tuple, list)):
+                d0, d1, layout, channels, frames = pcm
+                it.pcm = Pcm(d0, d1, layout, channels)
+            else:
+                it.pcm, frames = pcm_of(pcm, depth)
+            it.frames, it.sample_rate, it.bit_depth = frames, rate, depth
+        out = (TruePeak * max(1, n))()
+        if self._h is None:
+            raise RuntimeError("decoder is closed")
+        rcs, ms = (C.c_int * max(1, n))(), C.c_float()
+        rc = lib().lacx_decoder_truepeak_pcm_batch_device(self._h, items, C.c_uint32(n), C.c_void_p(stream), rcs, out, C.byref(ms))
+        self.last_ms = float(ms.value)
+        if rc == E_INVALID and all(rcs[i] == OK for i in range(n)):  # the call's own arguments
+            raise ValueError(lib().lacx_decode_last_error().decode(errors="replace"))
+        if rc == E_DEVICE:
+            raise RuntimeError(lib().lacx_decode_last_error().decode(errors="replace"))
+        errors = {i: lib().lacx_decoder_item_error(self._h, i).decode(errors="replace") for i in range(n) if rcs[i] != OK}
+        return self._raise_batch(rc, errors, [None if i in errors else (_copy_struct(out[i]), self._peak_rows(i)) for i in range(n)])
 
     # ---- runs: where a stream is silent, clips or holds one value ----
     @staticmethod

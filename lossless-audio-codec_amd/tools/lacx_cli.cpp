@@ -24,6 +24,9 @@
 // loudness (no counterpart in the reference's tool; `loudgain`, `ffmpeg ebur128`): ITU-R BS.1770 integrated loudness, loudness
 // range, momentary and short-term maxima of the same two kinds of file, the K-weighted energy made on the device
 // (lacx_decoder_loudness_batch_device / lacx_decoder_loudness_pcm_batch_device).  It only measures.
+// peak (the other half of what those tools write): the ITU-R BS.1770 true peak of the same two kinds of file, the 4x
+// oversampled maximum made on the device in exact integers (lacx_decoder_truepeak_batch_device /
+// lacx_decoder_truepeak_pcm_batch_device).  It only measures.
 // inspect (`flac -a` for .lac): how each stream was coded and where its bits go, read out of the bytes on the device by a
 // parse-only walk (lacx_decoder_inspect_batch_device).
 // recompress, cut, join (no counterpart in the reference's tool; `flac -f`, `--skip` / `--until` and joining, for .lac): .lac
@@ -69,6 +72,9 @@ void usage() {
                  "  lacx_cli loudness FILE... [--album] [--blocks]   (.lac and .wav files: BS.1770 integrated loudness, range, momentary and\n"
                  "      short-term maxima and gain = -18 - integrated, one line per file; --album: one further line for all files together;\n"
                  "      --blocks: one further line per sub-block of a tenth of a second; nothing is applied to the audio; exit 0 done, 2 refused)\n"
+                 "  lacx_cli peak FILE... [--album] [--blocks]   (.lac and .wav files: BS.1770 true peak in dBTP and linear, sample peak in\n"
+                 "      dBFS, where the peak lies, `over` for an inter-sample over, one line per file; --album: one further line for all files\n"
+                 "      together; --blocks: one further line per 16384 frames; nothing is applied to the audio; exit 0 done, 2 refused)\n"
                  "  lacx_cli inspect FILE... [--blocks] [--partitions]   (.lac files: predictors, residual modes and where the bits go, as\n"
                  "      integers, one line per file; --blocks: one further line per block; --partitions: and one per partition;\n"
                  "      a damaged stream prints its line with lost_blocks counted; exit 0 when every file was inspected, else 1)\n"
@@ -878,6 +884,148 @@ int loudness_command(int argc, char** argv) {
     return 0;
 }
 
+// lacx_cli peak FILE... [--album] [--blocks]: the true peak after ITU-R BS.1770-4 Annex 2 of what every .lac decodes to and
+// of every WAV's data chunk (lacx_decoder_truepeak_batch_device / lacx_decoder_truepeak_pcm_batch_device): a .lac and the WAV
+// it was made from print the same numbers.  One line per file in argument order: the true peak in dBTP and as the linear
+// value a REPLAYGAIN_*_PEAK tag holds, the sample peak in dBFS, the peak's channel, frame, phase and time, and `over` for an
+// inter-sample over.  --album: one further line for all files together (lacx_truepeak_combine over every file's rows; its
+// position is the one inside the file named by set=); --blocks: one further line per row of 16384 frames.  Jobs, exit codes
+// and messages as `loudness` has them.
+std::string peak_text(const lacx_truepeak& t) {
+    auto db = [](double x) {
+        if (std::isinf(x)) return std::string(x < 0 ? "-inf" : "inf");
+        char s[32];
+        std::snprintf(s, sizeof(s), "%.2f", x);
+        return std::string(s);
+    };
+    const lacx_truepeak_channel& c = t.ch[t.peak_channel];
+    char s[256];
+    std::snprintf(s, sizeof(s), " peak=%.6f sample_peak=%s dBFS channel=%u frame=%llu phase=%u time=%.6f", t.true_peak, db(t.sample_peak_dbfs).c_str(),
+                  (unsigned)t.peak_channel, (unsigned long long)(c.position / 4u), (unsigned)(c.position % 4u),
+                  t.sample_rate ? (double)c.position / (4.0 * t.sample_rate) : 0.0);
+    return "true_peak=" + db(t.true_peak_dbtp) + " dBTP" + s + (t.flags & LACX_TRUEPEAK_OVER ? " over" : "");
+}
+
+int peak_command(int argc, char** argv) {
+    bool album = false, per_block = false;
+    std::vector<const char*> paths;
+    for (int i = 2; i < argc; ++i) {
+        if (std::strcmp(argv[i], "--album") == 0) album = true;
+        else if (std::strcmp(argv[i], "--blocks") == 0) per_block = true;
+        else paths.push_back(argv[i]);
+    }
+    const int n = (int)paths.size();
+    if (n == 0) {
+        usage();
+        return 2;
+    }
+    std::vector<std::vector<uint8_t>> data(n);
+    std::vector<std::string> error(n);
+    std::vector<lacx_truepeak> peak(n, lacx_truepeak{});
+    std::vector<std::vector<lacx_truepeak_row>> rows(n);
+    std::vector<int> lacs, wavs;  // indices of the files of each kind that go to the device
+    std::vector<lacx_wav_info> winfo(n, lacx_wav_info{});
+    for (int i = 0; i < n; ++i) {
+        if (!load_file(paths[i], data[i])) {
+            error[i] = "Failed to read file";
+        } else if (data[i].size() >= 4 && std::memcmp(data[i].data(), "RIFF", 4) == 0) {
+            if (lacx_wav_parse(data[i].data(), data[i].size(), &winfo[i]) != LACX_OK) error[i] = "Failed to read WAV";
+            else wavs.push_back(i);
+        } else {
+            lacs.push_back(i);
+        }
+    }
+    lacx_decoder* dec = nullptr;
+    if (lacx_decoder_create(-1, &dec) != LACX_OK) {
+        std::cerr << "Error: lacx_decoder_create failed\n";
+        return 2;
+    }
+    auto collect = [&](const std::vector<int>& which, int rc, const std::vector<int>& item_rc, const std::vector<lacx_truepeak>& out) {
+        for (size_t k = 0; k < which.size(); ++k) {
+            const lacx_truepeak_row* r = nullptr;
+            uint32_t count = 0;
+            if (item_rc[k] == LACX_OK && lacx_decoder_item_truepeak_rows(dec, (uint32_t)k, &r, &count) == LACX_OK) {
+                peak[which[k]] = out[k];
+                rows[which[k]].assign(r, r + count);
+            } else {
+                error[which[k]] = rc == LACX_E_DEVICE || item_rc[k] == LACX_OK ? lacx_decode_last_error() : lacx_decoder_item_error(dec, (uint32_t)k);
+            }
+        }
+    };
+    if (!lacs.empty()) {
+        std::vector<lacx_span> spans;
+        for (int i : lacs) spans.push_back(lacx_span{data[i].data(), data[i].size()});
+        std::vector<int> item_rc(lacs.size(), LACX_OK);
+        std::vector<lacx_truepeak> out(lacs.size());
+        const int rc = lacx_decoder_truepeak_batch_device(dec, spans.data(), (uint32_t)spans.size(), nullptr, item_rc.data(), out.data(), nullptr);
+        collect(lacs, rc, item_rc, out);
+    }
+    if (!wavs.empty()) {
+        std::vector<lacx_digest_source> src;
+        std::vector<void*> dev;
+        std::vector<int> sent;
+        for (int i : wavs) {
+            const lacx_wav_info& w = winfo[i];
+            const uint64_t bytes = w.frames * w.channels * (uint64_t)(w.bit_depth / 8);
+            void* p = nullptr;
+            if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess ||
+                hipMemcpy(p, data[i].data() + w.data_offset, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+                error[i] = "Failed to upload WAV data to the device";
+                if (p) (void)hipFree(p);
+                continue;
+            }
+            lacx_digest_source s{};
+            s.pcm = lacx_pcm{p, nullptr, w.bit_depth == 16 ? LACX_PCM_INTERLEAVED_I16 : LACX_PCM_INTERLEAVED_I24, w.channels};
+            s.frames = w.frames;
+            s.sample_rate = w.sample_rate;
+            s.bit_depth = (uint8_t)w.bit_depth;
+            src.push_back(s), dev.push_back(p), sent.push_back(i);
+        }
+        if (!src.empty()) {
+            std::vector<int> item_rc(src.size(), LACX_OK);
+            std::vector<lacx_truepeak> out(src.size());
+            const int rc = lacx_decoder_truepeak_pcm_batch_device(dec, src.data(), (uint32_t)src.size(), nullptr, item_rc.data(), out.data(), nullptr);
+            collect(sent, rc, item_rc, out);
+        }
+        for (void* p : dev) (void)hipFree(p);
+    }
+    lacx_decoder_destroy(dec);
+    bool refused = false;
+    for (int i = 0; i < n; ++i) {
+        if (error[i].empty()) continue;
+        std::cerr << "Peak failed: " << paths[i] << ": " << error[i] << "\n";
+        refused = true;
+    }
+    if (refused) return 2;
+    for (int i = 0; i < n; ++i) {
+        std::cout << peak_text(peak[i]) << " " << paths[i] << "\n";
+        for (size_t s = 0; per_block && s < rows[i].size(); ++s) {
+            const lacx_truepeak_row& r = rows[i][s];
+            char line[192];
+            std::snprintf(line, sizeof(line), "  row=%zu peak0=%llu pos0=%u sample_peak0=%u peak1=%llu pos1=%u sample_peak1=%u", s, (unsigned long long)r.peak[0],
+                          r.pos[0], r.sample_peak[0], (unsigned long long)r.peak[1], r.pos[1], r.sample_peak[1]);
+            std::cout << line << "\n";
+        }
+    }
+    if (album) {
+        std::vector<const lacx_truepeak_row*> sets;
+        std::vector<uint32_t> counts, rates;
+        std::vector<uint64_t> frames;
+        std::vector<uint8_t> channels, depths;
+        for (int i = 0; i < n; ++i) {
+            sets.push_back(rows[i].data()), counts.push_back((uint32_t)rows[i].size()), rates.push_back(peak[i].sample_rate);
+            channels.push_back(peak[i].channels), depths.push_back(peak[i].bit_depth), frames.push_back(peak[i].frames);
+        }
+        lacx_truepeak all{};
+        if (lacx_truepeak_combine(sets.data(), counts.data(), channels.data(), depths.data(), frames.data(), rates.data(), (uint32_t)n, &all) != LACX_OK) {
+            std::cerr << "Peak failed: album: " << lacx_decode_last_error() << "\n";
+            return 2;
+        }
+        std::cout << peak_text(all) << " set=" << all.set << " album\n";
+    }
+    return 0;
+}
+
 // lacx_cli inspect FILE... [--blocks] [--partitions]: how every .lac was coded and where its bits go, read out of the bytes
 // on the device by a parse-only walk (lacx_decoder_inspect_batch_device), all files as one job.  One line of integers per
 // file in argument order; with --blocks one further line per block (its channel blocks behind it), with --partitions one
@@ -1511,6 +1659,7 @@ int main(int argc, char** argv) {
     if (mode == "digest" && argc >= 3) return digest_command(argc, argv);
     if (mode == "stats" && argc >= 3) return stats_command(argc, argv);
     if (mode == "loudness") return loudness_command(argc, argv);
+    if (mode == "peak") return peak_command(argc, argv);
     if (mode == "inspect" && argc >= 3) return inspect_command(argc, argv);
     if (mode == "find" && argc >= 3) return find_command(argc, argv);
     if (mode == "split" && argc >= 4) return split_command(argc, argv);
