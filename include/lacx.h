@@ -66,6 +66,10 @@
  *   lacx_decoder_item_truepeak_rows,
  *   lacx_truepeak_combine   <- how far the audio can be turned up: the ITU-R BS.1770 true peak (the maximum of the 4x
  *                             oversampled signal) of a stream or an album, in exact integers, made on the device
+ *   lacx_decoder_spectrum_batch_device, lacx_decoder_spectrum_pcm_batch_device,
+ *   lacx_decoder_item_spectrum_rows,
+ *   lacx_spectrum_combine   <- whether the audio is what it claims to be: the long-term power spectrum in 64 bands (Hann
+ *                             STFT in FP64) and the bandwidth of a stream, made on the device
  *   lacx_recovery_build, lacx_recovery_build_batch_view, lacx_recovery_parse,
  *   lacx_recovery_scan_batch, lacx_recovery_repair, lacx_recovery_repair_batch_view,
  *   lacx_decoder_item_bad_slices <- bringing lost bytes back: a parity sidecar ("LACR", Reed-Solomon over GF(2^8)) beside
@@ -1104,6 +1108,76 @@ int lacx_decoder_item_truepeak_rows(const lacx_decoder* dec, uint32_t i, const l
 int lacx_truepeak_combine(const lacx_truepeak_row* const* rows, const uint32_t* counts, const uint8_t* channels,
                           const uint8_t* bit_depths, const uint64_t* frames, const uint32_t* sample_rates, uint32_t nsets,
                           lacx_truepeak* out);
+
+/* Spectrum: the long-term power spectrum of a stream in 64 uniform bands and its bandwidth, made on the device where the
+ * samples lie.  Everything else here looks at the time domain; the question an archive of lossless audio gets asked most
+ * -- is this really what it claims to be? -- is read off the spectrum: a "lossless" file made from a lossy one has a
+ * brick-wall cutoff at 16 - 20 kHz, a 96 kHz file upsampled from 44.1 kHz has nothing above 22.05 kHz.  It only measures.
+ * Out of scope: a lenient form, more than two channels, windows other than Hann, hops other than N / 2, per-window output
+ * (a spectrogram), phase.
+ * Definition (csrc/spectrum_core.h is its only statement in code).
+ *   window: the window length N, one of 256, 512, 1024, 2048, 4096, one value per call (the binding's default is 2048);
+ *   the hop is H = N / 2.  Window k of an item covers frames [k H, k H + N), k = 0 .. ceil(frames / H) - 1; frames at or
+ *   behind the item's end are zeros; an item without frames has no windows and no rows.
+ *   w[n] = 0.5 - 0.5 cos(2 pi n / N), the periodic Hann window.  The host makes the window and the twiddles (cos, -sin of
+ *   2 pi k / N), every entry evaluated in long double and rounded once to double; the device never evaluates a sine or
+ *   cosine, device and CPU twin read the same tables.
+ *   A sample enters as (double)x, exact; w[n] x is one rounding.  Stereo items take both channels through one complex
+ *   transform, z = w l + i w r, separated by L_k = (Z_k + conj Z_{N-k}) / 2, R_k = (Z_k - conj Z_{N-k}) / 2i; mono runs
+ *   the same transform with a zero imaginary part.  The transform is a radix-2 decimation-in-frequency FFT whose every
+ *   operation is fixed in the core (a' = a + b; d = a - b; b' = (fma(d.re, c, -(d.im s)), fma(d.re, s, d.im c)) with the
+ *   twiddle (c, s)); |X|^2 = fma(x.re, x.re, x.im x.im).  The one-sided power of bin k is c_k |X_k|^2, c_0 = c_{N/2} = 1,
+ *   c_k = 2 otherwise.  64 uniform bands: bin k < N / 2 belongs to band k / (N / 128), the Nyquist bin to band 63, summed in
+ *   ascending bin order; the bands of a window add up to N sum (w[n] x[n])^2 up to rounding (Parseval).
+ * lacx_spectrum_row: one per segment of 16384 frames counted from the item's frame 0 (true peak's row grid): per channel and
+ *   band the sum, in window order, of the band powers of the windows whose FIRST frame lies in the segment: 16384 / H
+ *   windows per full row.  1024 bytes per 16384 frames, about 1.8 MB for ten minutes.  A mono item's second channel is all
+ *   zero; digital silence is +0.0 in every byte.  There are no floating-point atomics and nothing but the written fused
+ *   multiply-adds is fused (the kernel, the totals and the CPU twin are compiled with -ffp-contract=off): a row is the same
+ *   bits on the device and on the twin, from run to run, in any batch and at any place in a job.
+ * lacx_spectrum, made on the host from the rows by lacx_spectrum_combine: frames, sample_rate, channels, bit_depth, rows,
+ *   window as given, windows = ceil(frames / H), floor_db as given; per channel and band, with P the rows' powers added in
+ *   row order, level_db = 10 log10(P / (windows (3 N^2 / 8) 2^(2b-3))), b the bit depth: the band's mean square relative to
+ *   a full-scale sine (sum w^2 = 3 N / 8 exactly), so that a full-scale sine on an exact bin 2 .. N / 2 - 2 reads 0.00 dBFS
+ *   summed over the bands it falls into (the zero-padded last windows of a short item read lower); -INFINITY for a zero
+ *   band.  bandwidth_hz: the upper edge (band + 1) sample_rate / 128 of the highest band whose level is at least floor_db, 0
+ *   when no band is; TPDF dither at 16 bits puts about -111 dBFS into each band, so at the bindings' default of -100 dither
+ *   alone does not count as signal.  peak_band: the lowest band with the largest power (0 for silence).
+ * lacx_decoder_spectrum_batch_device: strict, exactly like lacx_decoder_digest_batch_device -- versions 3 and 2; the
+ *   decode, the in-place mid/side inverse, then k_spectrum (one launch) on the job's stream.  An item that does not parse or
+ *   decode keeps the decode's own code and message, gets a zeroed result and no rows, and does not cost the other items.
+ *   A window that is none of the five values fails the call with LACX_E_INVALID "unsupported spectrum window: W" and
+ *   launches nothing.  out: nullable array of n.
+ * lacx_decoder_spectrum_pcm_batch_device: device-resident source PCM in any LACX_PCM_* layout; the per-item host checks,
+ *   the device-found validation texts and the bounds are those of lacx_decoder_digest_pcm_batch_device.  A failed item gets a
+ *   zeroed result and no rows.
+ * lacx_decoder_item_spectrum_rows: the rows of item i of the decoder's last spectrum call, valid until its next call;
+ *   LACX_E_INVALID outside that call.
+ * lacx_spectrum_combine: host only, no device; one item's rows give exactly the totals the batch calls return (they use
+ *   it).  LACX_E_INVALID: a null argument (null rows with a count > 0), channels not 1 or 2, bit depth not 16 or 24, a
+ *   sample rate that is none of the four, an unsupported window, a count that is not ceil(frames / 16384).
+ * Everything else as lacx_decoder_truepeak_batch_device.  No scratch: the rows lie inside the job's tables.
+ * Time (scripts/spectrum_bench.py, profiles/spectrum_bench.txt): on 48 four-minute stereo 16-bit streams as one job
+ * 33.0 ms of kernels and 66.7 ms of wall at N = 2048 (30.7 / 65.4 ms at N = 256) against 146.7 ms (145.1 ms) for decode plus
+ * torch.stft in float64 and the band sums on the same device; k_spectrum alone 14.4 ms (12.4 ms) for 4.06 GB of PCM. */
+typedef struct lacx_spectrum_row { /* 1024 bytes */
+    double power[2][64];
+} lacx_spectrum_row;
+typedef struct lacx_spectrum {     /* 1080 bytes */
+    uint64_t frames, windows;
+    uint32_t sample_rate, window, rows;
+    uint8_t channels, bit_depth, peak_band[2];
+    double floor_db;
+    double bandwidth_hz[2];
+    double level_db[2][64];
+} lacx_spectrum;
+int lacx_decoder_spectrum_batch_device(lacx_decoder* dec, const lacx_span* lacs, uint32_t n, uint32_t window, double floor_db,
+                                       void* stream, int* item_rc, lacx_spectrum* out, float* device_ms);
+int lacx_decoder_spectrum_pcm_batch_device(lacx_decoder* dec, const lacx_digest_source* src, uint32_t n, uint32_t window,
+                                           double floor_db, void* stream, int* item_rc, lacx_spectrum* out, float* device_ms);
+int lacx_decoder_item_spectrum_rows(const lacx_decoder* dec, uint32_t i, const lacx_spectrum_row** rows, uint32_t* count);
+int lacx_spectrum_combine(const lacx_spectrum_row* rows, uint32_t count, uint8_t channels, uint8_t bit_depth, uint64_t frames,
+                          uint32_t sample_rate, uint32_t window, double floor_db, lacx_spectrum* out);
 
 /* Recovery data: repairing a damaged .lac file from a parity sidecar.  Digests, salvage and the manifest all end in "this
  * block is lost"; the container has no redundancy of its own.  A recovery sidecar ("LACR") kept beside the file brings the

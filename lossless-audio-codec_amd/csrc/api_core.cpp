@@ -500,6 +500,7 @@ uint32_t lacx_sizeof(const char* name) {
                  {"run_totals", sizeof(lacx_run_totals)}, {"runs_result", sizeof(lacx_runs_result)},
                  {"loudness_row", sizeof(lacx_loudness_row)}, {"loudness", sizeof(lacx_loudness)},
                  {"truepeak_row", sizeof(lacx_truepeak_row)}, {"truepeak_channel", sizeof(lacx_truepeak_channel)}, {"truepeak", sizeof(lacx_truepeak)},
+                 {"spectrum_row", sizeof(lacx_spectrum_row)}, {"spectrum", sizeof(lacx_spectrum)},
                  {"channel_info", sizeof(lacx_channel_info)}, {"block_info", sizeof(lacx_block_info)},
                  {"stream_report", sizeof(lacx_stream_report)}, {"edit_segment", sizeof(lacx_edit_segment)},
                  {"edit_output", sizeof(lacx_edit_output)},     {"edit_result", sizeof(lacx_edit_result)}};

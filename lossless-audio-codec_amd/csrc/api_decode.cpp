@@ -9,6 +9,7 @@
 #include "inspect_rows.h"
 #include "loudness_rows.h"
 #include "runs_rows.h"
+#include "spectrum_rows.h"
 #include "stats_rows.h"
 #include "truepeak_rows.h"
 
@@ -117,6 +118,9 @@ struct DecodeJob {
     lacx_loudness* lres = nullptr;       // loudness: [n]
     bool truepeak = false;               // the digest form with k_truepeak in k_digest's place (DecodePlan::truepeak)
     lacx_truepeak* pres = nullptr;       // true peak: [n]
+    uint32_t spectrum = 0;               // the digest form with k_spectrum in k_digest's place (DecodePlan::spectrum): the window length
+    double floor_db = 0.0;               // ... the totals' floor
+    lacx_spectrum* xres = nullptr;       // spectrum: [n]
 };
 static_assert(sizeof(StatsAcc) == kStatsRowBytes, "the plan lays the accumulator rows out kStatsRowBytes apart");
 
@@ -292,11 +296,18 @@ DevErr launch_and_wait(lacx_decoder* d, const DecodeJob& job, const DecodePlan& 
         if (DevErr e = chk(launch_loudness(plan_loud_args(plan, d->d_meta(), d->loud.as<uint8_t>()), st), "loudness launch")) return e;
     if (plan.truepeak)  // in the same slot
         if (DevErr e = chk(launch_truepeak(plan_peak_args(plan, d->d_meta()), st), "true peak launch")) return e;
+    if (plan.spectrum)  // likewise
+        if (DevErr e = chk(launch_spectrum(plan_spec_args(plan, d->d_meta()), st), "spectrum launch")) return e;
     if (DevErr e = chk(hipEventRecord(d->e1, st), "event record")) return e;
     if (plan.truepeak && plan.peak_at.total_rows)  // the rows: 32 bytes per 16384 frames, inside the tables
         if (DevErr e = chk(hipMemcpyAsync(d->h_meta() + plan.peak_at.rows, d->d_meta() + plan.peak_at.rows, sizeof(TpAcc) * (size_t)plan.peak_at.total_rows,
                                           hipMemcpyDeviceToHost, st),
                            "D2H true peak rows"))
+            return e;
+    if (plan.spectrum && plan.spec_at.total_rows)  // the rows: 1024 bytes per 16384 frames, inside the tables
+        if (DevErr e = chk(hipMemcpyAsync(d->h_meta() + plan.spec_at.rows, d->d_meta() + plan.spec_at.rows, sizeof(lacx_spectrum_row) * (size_t)plan.spec_at.total_rows,
+                                          hipMemcpyDeviceToHost, st),
+                           "D2H spectrum rows"))
             return e;
     if (plan.loudness && plan.loud_at.total_rows) {  // the rows: 16 bytes per sub-block
         d->loud_host.resize((size_t)plan.loud_at.total_rows);
@@ -315,7 +326,7 @@ DevErr launch_and_wait(lacx_decoder* d, const DecodeJob& job, const DecodePlan& 
         if (DevErr e = chk(hipMemcpyAsync(d->h_meta() + res, d->d_meta() + res, sizeof(VerifyWords) * m, hipMemcpyDeviceToHost, st), "D2H verify results"))
             return e;
     // the digest form's whole answer: 8 bytes per item
-    if (plan.form == DecodeForm::digest && !plan.loudness && !plan.truepeak)
+    if (plan.form == DecodeForm::digest && !plan.loudness && !plan.truepeak && !plan.spectrum)
         if (DevErr e = chk(hipMemcpyAsync(d->h_meta() + res, d->d_meta() + res, sizeof(DigestWords) * m, hipMemcpyDeviceToHost, st), "D2H digests"))
             return e;
     // block digests: 4 bytes per block beside the statuses
@@ -405,6 +416,12 @@ DevErr collect(lacx_decoder* d, const DecodeJob& job, const DecodePlan& plan, hi
             std::vector<lacx_truepeak_row>& rows = d->item_peak[i];
             truepeak_rows_of(reinterpret_cast<const TpAcc*>(d->h_meta() + plan.peak_at.rows) + ti.row0, ti.rows, rows);
             if (job.pres) job.pres[i] = truepeak_of_rows(TpSet{rows.data(), (uint32_t)rows.size(), p.info.channels, p.info.bit_depth, p.info.frames, p.info.sample_rate});
+        } else if (plan.spectrum) {  // likewise
+            const SpItem& si = reinterpret_cast<const SpItem*>(d->h_meta() + plan.spec_at.items)[j];
+            std::vector<lacx_spectrum_row>& rows = d->item_spec[i];
+            const auto* all = reinterpret_cast<const lacx_spectrum_row*>(d->h_meta() + plan.spec_at.rows);
+            rows.assign(all + si.row0, all + si.row0 + si.rows);
+            if (job.xres) job.xres[i] = spectrum_of_rows(SpSet{rows.data(), (uint32_t)rows.size(), p.info.channels, p.info.bit_depth, p.info.frames, p.info.sample_rate, plan.spectrum, job.floor_db});
         } else if (plan.form == DecodeForm::digest) {
             const DigestWords& w = reinterpret_cast<const DigestWords*>(d->h_meta() + plan.at.res)[j];
             if (job.dres) job.dres[i] = make_digest(w.raw, p.info.frames, p.info.sample_rate, p.info.channels, p.info.bit_depth);
@@ -459,11 +476,13 @@ int decode_batch_run(lacx_decoder* d, const DecodeJob& job, std::vector<int>& co
     if (job.loudness) d->item_loud.assign(job.n, {});
     if (job.pres) std::memset(job.pres, 0, sizeof(lacx_truepeak) * job.n);
     if (job.truepeak) d->item_peak.assign(job.n, {});
+    if (job.xres) std::memset(job.xres, 0, sizeof(lacx_spectrum) * job.n);
+    if (job.spectrum) d->item_spec.assign(job.n, {});
     // LACX_DECODE_BATCH_PAD=1 (tuning knob, read per call): every item's blocks start a new wave
     const char* pad_env = std::getenv("LACX_DECODE_BATCH_PAD");
     DecodePlan plan;
     const char* whole = plan_decode(job.in, job.n, job.form, job.sample_type, pad_env && pad_env[0] == '1', plan, code, err, job.salvage, job.blocks, job.stats,
-                                    job.runs, d->runs_list_cap ? d->runs_list_cap : kRunsListCap, job.loudness, job.truepeak);
+                                    job.runs, d->runs_list_cap ? d->runs_list_cap : kRunsListCap, job.loudness, job.truepeak, job.spectrum);
     if (lacx_device_count() <= 0) whole = "no usable HIP device";
     int rc = whole ? decode_fail(LACX_E_DEVICE, whole) : LACX_OK;
     if (!whole && !plan.items.empty()) {
@@ -494,6 +513,8 @@ int decode_batch_run(lacx_decoder* d, const DecodeJob& job, std::vector<int>& co
         if (job.lres) std::memset(job.lres, 0, sizeof(lacx_loudness) * job.n);
         if (job.truepeak) d->item_peak.assign(job.n, {});
         if (job.pres) std::memset(job.pres, 0, sizeof(lacx_truepeak) * job.n);
+        if (job.spectrum) d->item_spec.assign(job.n, {});
+        if (job.xres) std::memset(job.xres, 0, sizeof(lacx_spectrum) * job.n);
         if (job.dres) std::memset(job.dres, 0, sizeof(lacx_digest) * job.n);
         for (uint32_t i = 0; i < job.n; ++i) {
             if (code[i] != LACX_OK) continue;
@@ -725,11 +746,18 @@ const char* check_digest_source(const lacx_digest_source& x, std::string& text) 
 // (16-byte aligned), the scratch in the decoder's own buffer, every item's rows left in d->item_loud, the totals in loud->out.
 // peak (without a grid): k_truepeak instead -- behind bad [m] the tables of truepeak_plan.h (16-byte aligned, zeroed rows
 // included), every item's rows left in d->item_peak, the totals in peak->out.
+// spec (without a grid): k_spectrum instead -- behind bad [m] the tables of spectrum_plan.h (window, twiddles and zeroed rows
+// included), every item's rows left in d->item_spec, the totals in spec->out.
 struct LoudPcm {
     lacx_loudness* out;
 };
 struct PeakPcm {
     lacx_truepeak* out;
+};
+struct SpecPcm {
+    lacx_spectrum* out;
+    uint32_t window;  // a supported length
+    double floor_db;
 };
 struct RunsPcm {
     std::vector<BatchIn> in;  // per item its detectors, or why they are refused (BatchIn::dets, ndet, dets_why)
@@ -737,8 +765,11 @@ struct RunsPcm {
 };
 int digest_pcm_run(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, hipStream_t st, lacx_digest* out, float* device_ms,
                    std::vector<int>& code, std::vector<std::string>& err, uint32_t grid = 0, bool stats = false, lacx_stats* sout = nullptr,
-                   const RunsPcm* runs = nullptr, const LoudPcm* loud = nullptr, const PeakPcm* peak = nullptr) {
+                   const RunsPcm* runs = nullptr, const LoudPcm* loud = nullptr, const PeakPcm* peak = nullptr,
+                   const SpecPcm* spec = nullptr) {
     if (device_ms) *device_ms = 0.f;
+    if (spec && spec->out) std::memset(spec->out, 0, sizeof(lacx_spectrum) * n);
+    if (spec) d->item_spec.assign(n, {});
     if (peak && peak->out) std::memset(peak->out, 0, sizeof(lacx_truepeak) * n);
     if (peak) d->item_peak.assign(n, {});
     if (loud && loud->out) std::memset(loud->out, 0, sizeof(lacx_loudness) * n);
@@ -787,7 +818,13 @@ int digest_pcm_run(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, h
             tin.push_back(TpIn{x.pcm.data0, x.pcm.data1, x.frames, x.pcm.layout, (uint8_t)x.pcm.channels, x.bit_depth, true});
         }
         const TpLayout ty = peak ? tp_layout(plan_detail::up16(at_blk), tin.data(), m) : TpLayout{};
-        const size_t size = peak ? ty.size : loud ? ly.size : runs ? y.size : size0;
+        std::vector<SpIn> xin;
+        for (size_t j = 0; spec && j < m; ++j) {
+            const lacx_digest_source& x = src[went[j]];
+            xin.push_back(SpIn{x.pcm.data0, x.pcm.data1, x.frames, x.pcm.layout, (uint8_t)x.pcm.channels, x.bit_depth, true});
+        }
+        const SpLayout sy = spec ? sp_layout(plan_detail::up16(at_blk), xin.data(), m, sp_logn(spec->window)) : SpLayout{};
+        const size_t size = spec ? sy.size : peak ? ty.size : loud ? ly.size : runs ? y.size : size0;
         int prev_device = -1;
         DevErr e = decoder_open(d, &prev_device);
         if (!e && loud)
@@ -795,6 +832,8 @@ int digest_pcm_run(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, h
         if (!e && loud && rc == LACX_OK) e = buf_grow(d->loud, (ly.scratch + 15u) / 16u, ly.scratch / 128u + 64);
         if (!e && peak)
             if (const char* why = tp_check(tin.data(), m)) rc = decode_fail(LACX_E_DEVICE, why);
+        if (!e && spec)
+            if (const char* why = sp_check(xin.data(), m, sy.logn)) rc = decode_fail(LACX_E_DEVICE, why);
         if (!e && y.total_tiles >= (1ull << 31)) rc = decode_fail(LACX_E_DEVICE, "batch holds 2^31 tiles or more");
         if (!e) e = buf_grow(d->tables, size, size / 8 + 256);
         if (!e && runs && rc == LACX_OK) {
@@ -822,6 +861,7 @@ int digest_pcm_run(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, h
             }
             if (loud) loud_fill(ly, lin.data(), m, d->h_meta());
             if (peak) tp_fill(ty, tin.data(), m, d->h_meta());
+            if (spec) sp_fill(sy, xin.data(), m, d->h_meta());
             DigestPcmArgs a;
             a.nitems = (uint32_t)m;
             a.total_units = unit_off[m];
@@ -849,9 +889,12 @@ int digest_pcm_run(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, h
             }
             if (!e && loud) e = chk(launch_loudness(loud_args(ly, m, d->d_meta(), d->loud.as<uint8_t>(), a.bad), st), "loudness launch");
             if (!e && peak) e = chk(launch_truepeak(tp_args(ty, m, d->d_meta(), a.bad), st), "true peak launch");
-            if (!e && !loud && !peak) e = runs ? chk(launch_runs_pcm(ra, st), "runs launch") : stats ? chk(launch_stats_pcm_blocks(sa, st), "stats launch") : chk(grid ? launch_digest_pcm_blocks(ba, st) : launch_digest_pcm(a, st), "digest launch");
+            if (!e && spec) e = chk(launch_spectrum(sp_args(sy, m, d->d_meta(), a.bad), st), "spectrum launch");
+            if (!e && !loud && !peak && !spec) e = runs ? chk(launch_runs_pcm(ra, st), "runs launch") : stats ? chk(launch_stats_pcm_blocks(sa, st), "stats launch") : chk(grid ? launch_digest_pcm_blocks(ba, st) : launch_digest_pcm(a, st), "digest launch");
             if (!e) e = chk(hipEventRecord(d->e1, st), "event record");
-            if (!e) e = chk(hipMemcpyAsync(d->h_meta() + at_res, d->d_meta() + at_res, (runs || loud || peak ? at_blk : size) - at_res, hipMemcpyDeviceToHost, st), "D2H digests");
+            if (!e) e = chk(hipMemcpyAsync(d->h_meta() + at_res, d->d_meta() + at_res, (runs || loud || peak || spec ? at_blk : size) - at_res, hipMemcpyDeviceToHost, st), "D2H digests");
+            if (!e && spec && sy.total_rows)
+                e = chk(hipMemcpyAsync(d->h_meta() + sy.rows, d->d_meta() + sy.rows, sizeof(lacx_spectrum_row) * (size_t)sy.total_rows, hipMemcpyDeviceToHost, st), "D2H spectrum rows");
             if (!e && peak && ty.total_rows)
                 e = chk(hipMemcpyAsync(d->h_meta() + ty.rows, d->d_meta() + ty.rows, sizeof(TpAcc) * (size_t)ty.total_rows, hipMemcpyDeviceToHost, st), "D2H true peak rows");
             if (!e && loud && ly.total_rows) {
@@ -898,6 +941,14 @@ int digest_pcm_run(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, h
                     if (peak->out) peak->out[i] = truepeak_of_rows(TpSet{rows.data(), (uint32_t)rows.size(), (uint8_t)x.pcm.channels, x.bit_depth, x.frames, x.sample_rate});
                     continue;
                 }
+                if (spec) {
+                    const SpItem& si = reinterpret_cast<const SpItem*>(d->h_meta() + sy.items)[j];
+                    std::vector<lacx_spectrum_row>& rows = d->item_spec[i];
+                    const auto* all = reinterpret_cast<const lacx_spectrum_row*>(d->h_meta() + sy.rows);
+                    rows.assign(all + si.row0, all + si.row0 + si.rows);
+                    if (spec->out) spec->out[i] = spectrum_of_rows(SpSet{rows.data(), (uint32_t)rows.size(), (uint8_t)x.pcm.channels, x.bit_depth, x.frames, x.sample_rate, spec->window, spec->floor_db});
+                    continue;
+                }
                 if (runs) {
                     lacx_runs_result res = runs_item_result(y, d->h_meta(), d->runs_host.data(), j, x.frames, d->item_runs[i]);
                     res.sample_rate = x.sample_rate, res.blocks = (uint32_t)((x.frames + kMaxBlock - 1u) / kMaxBlock);
@@ -937,6 +988,8 @@ int digest_pcm_run(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, h
         if (loud && loud->out) std::memset(loud->out, 0, sizeof(lacx_loudness) * n);
         if (peak) d->item_peak.assign(n, {});
         if (peak && peak->out) std::memset(peak->out, 0, sizeof(lacx_truepeak) * n);
+        if (spec) d->item_spec.assign(n, {});
+        if (spec && spec->out) std::memset(spec->out, 0, sizeof(lacx_spectrum) * n);
         for (uint32_t i = 0; i < n; ++i) {
             if (code[i] != LACX_OK) continue;
             code[i] = rc;
@@ -1427,6 +1480,56 @@ int lacx_truepeak_combine(const lacx_truepeak_row* const* rows, const uint32_t* 
         sets[k] = TpSet{rows[k], counts[k], channels[k], bit_depths[k], frames[k], sample_rates[k]};
     }
     *out = truepeak_combine(sets.data(), nsets);
+    return LACX_OK;
+}
+
+// ---- spectrum (lacx.h) ----
+int lacx_decoder_spectrum_batch_device(lacx_decoder* d, const lacx_span* lacs, uint32_t n, uint32_t window, double floor_db, void* stream, int* item_rc,
+                                       lacx_spectrum* out, float* device_ms) {
+    if (!d) return decode_fail(LACX_E_INVALID, "null decoder");
+    if (!lacs || n == 0) return decode_fail(LACX_E_INVALID, "null argument or empty batch");
+    if (!sp_logn(window)) return decode_fail(LACX_E_INVALID, "unsupported spectrum window: " + std::to_string(window));
+    std::vector<BatchIn> in(n);
+    for (uint32_t i = 0; i < n; ++i) in[i] = BatchIn{lacs[i].data, lacs[i].size, nullptr, nullptr, 0};
+    DecodeJob job{in.data(), n, DecodeForm::digest, kWholeStreams, static_cast<hipStream_t>(stream), nullptr, nullptr, device_ms};
+    job.spectrum = window;
+    job.floor_db = floor_db;
+    job.xres = out;
+    return run_batch(d, job, item_rc);
+}
+
+int lacx_decoder_spectrum_pcm_batch_device(lacx_decoder* d, const lacx_digest_source* src, uint32_t n, uint32_t window, double floor_db, void* stream,
+                                           int* item_rc, lacx_spectrum* out, float* device_ms) {
+    if (!d) return decode_fail(LACX_E_INVALID, "null decoder");
+    if (!src || n == 0) return decode_fail(LACX_E_INVALID, "null argument or empty batch");
+    if (!sp_logn(window)) return decode_fail(LACX_E_INVALID, "unsupported spectrum window: " + std::to_string(window));
+    const SpecPcm spec{out, window, floor_db};
+    std::vector<int> code;
+    std::vector<std::string> err;
+    const int rc = digest_pcm_run(d, src, n, static_cast<hipStream_t>(stream), nullptr, device_ms, code, err, 0, false, nullptr, nullptr, nullptr, nullptr, &spec);
+    return batch_outcome(d, rc, code, err, item_rc);
+}
+
+int lacx_decoder_item_spectrum_rows(const lacx_decoder* d, uint32_t i, const lacx_spectrum_row** rows, uint32_t* count) {
+    if (rows) *rows = nullptr;
+    if (count) *count = 0;
+    if (!d || !rows || !count) return decode_fail(LACX_E_INVALID, "null argument");
+    if (i >= d->item_spec.size()) return decode_fail(LACX_E_INVALID, "no such item in the last spectrum call");
+    *rows = d->item_spec[i].data();
+    *count = (uint32_t)d->item_spec[i].size();
+    return LACX_OK;
+}
+
+int lacx_spectrum_combine(const lacx_spectrum_row* rows, uint32_t count, uint8_t channels, uint8_t bit_depth, uint64_t frames, uint32_t sample_rate,
+                          uint32_t window, double floor_db, lacx_spectrum* out) {
+    if (out) std::memset(out, 0, sizeof(*out));
+    if (!out || (!rows && count)) return decode_fail(LACX_E_INVALID, "null argument");
+    if (channels != 1 && channels != 2) return decode_fail(LACX_E_INVALID, "unsupported channel count");
+    if (bit_depth != 16 && bit_depth != 24) return decode_fail(LACX_E_INVALID, "unsupported bit depth: " + std::to_string((int)bit_depth));
+    if (loud_rate_index(sample_rate) < 0) return decode_fail(LACX_E_INVALID, "unsupported sample rate: " + std::to_string(sample_rate));
+    if (!sp_logn(window)) return decode_fail(LACX_E_INVALID, "unsupported spectrum window: " + std::to_string(window));
+    if (sp_rows(frames) != count) return decode_fail(LACX_E_INVALID, "row count does not match the frames");
+    *out = spectrum_of_rows(SpSet{rows, count, channels, bit_depth, frames, sample_rate, window, floor_db});
     return LACX_OK;
 }
 

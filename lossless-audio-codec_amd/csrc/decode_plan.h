@@ -14,6 +14,7 @@
 #include "loudness_plan.h"
 #include "manifest.h"
 #include "runs_plan.h"
+#include "spectrum_plan.h"
 #include "truepeak_plan.h"
 
 namespace lacx {
@@ -78,6 +79,8 @@ struct BatchIn {
 // int32 sources; the scratch is a buffer of its own.
 // ... and of a true-peak job (DecodePlan::truepeak, lacx_decoder_truepeak_batch_device): the same strict job with k_truepeak
 // (truepeak_core.h) in that slot -- behind res [m] the tables of truepeak_plan.h (DecodePlan::peak_at), zeroed rows included.
+// ... and of a spectrum job (DecodePlan::spectrum, lacx_decoder_spectrum_batch_device): likewise with k_spectrum
+// (spectrum_core.h) -- behind res [m] the tables of spectrum_plan.h (DecodePlan::spec_at), window, twiddles and zeroed rows.
 enum class DecodeForm { wav, device, host, verify, digest, blocks };
 constexpr int kWholeStreams = -1;
 constexpr size_t kStatsRowBytes = 96;  // sizeof(StatsAcc), stats_core.h (k_stats.hip asserts it)
@@ -114,6 +117,7 @@ struct TableLayout {
     size_t runs = 0;                         // runs job only: RunsLayout::base
     size_t loud = 0;                         // loudness job only: LoudLayout::base
     size_t peak = 0;                         // true-peak job only: TpLayout::base
+    size_t spec = 0;                         // spectrum job only: SpLayout::base
 };
 
 struct DecodePlan {
@@ -130,6 +134,8 @@ struct DecodePlan {
     LoudLayout loud_at{};  // ... inside the tables, and the scratch's layout
     bool truepeak = false; // strict job in the digest form with k_truepeak in k_digest's place
     TpLayout peak_at{};    // ... inside the tables
+    uint32_t spectrum = 0; // strict job in the digest form with k_spectrum in k_digest's place: the window length, 0: none
+    SpLayout spec_at{};    // ... inside the tables
     bool window() const { return sample_type != kWholeStreams; }
     bool own_pcm() const { return form != DecodeForm::device || window(); }  // into the decoder's PCM buffers
     bool post_units() const { return window() || form == DecodeForm::verify || form == DecodeForm::wav || form == DecodeForm::digest || blocks || stats || runs; }
@@ -221,7 +227,8 @@ inline int check_manifest(const BatchIn& x, const lacx_stream_info& f, std::vect
 // bytes of its present blocks.
 inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, int sample_type, bool pad_waves, DecodePlan& plan,
                                std::vector<int>& code, std::vector<std::string>& err, bool salvage = false, bool blocks = false,
-                               bool stats = false, bool runs = false, uint64_t runs_list_cap = kRunsListCap, bool loudness = false, bool truepeak = false) {
+                               bool stats = false, bool runs = false, uint64_t runs_list_cap = kRunsListCap, bool loudness = false, bool truepeak = false,
+                               uint32_t spectrum = 0) {
     using namespace plan_detail;
     plan = DecodePlan{};
     plan.form = form;
@@ -232,6 +239,7 @@ inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, i
     plan.runs = runs;
     plan.loudness = loudness;
     plan.truepeak = truepeak;
+    plan.spectrum = spectrum;
     const bool window = plan.window(), own_pcm = plan.own_pcm(), wav = form == DecodeForm::wav, verify = form == DecodeForm::verify,
                digest = form == DecodeForm::digest, quiet = form == DecodeForm::blocks;
     code.assign(n, LACX_OK);
@@ -242,6 +250,7 @@ inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, i
     if ((quiet && !blocks && !stats && !runs) || (blocks && !salvage)) return "block digests belong to a salvage job";
     if (loudness && (!digest || salvage)) return "loudness is a strict job in the digest form";
     if (truepeak && (!digest || salvage || loudness)) return "true peak is a strict job in the digest form";
+    if (spectrum && (!digest || salvage || loudness || truepeak || !sp_logn(spectrum))) return "spectrum is a strict job in the digest form with a supported window";
     plan.items.reserve(n);
     uint32_t v3_blocks = 0;
     for (uint32_t i = 0; i < n; ++i) {
@@ -382,7 +391,14 @@ inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, i
         at.peak = up16(at.res + sizeof(DigestWords) * m);
         plan.peak_at = tp_layout(at.peak, tin.data(), m);
     }
-    at.size = truepeak ? plan.peak_at.size : loudness ? plan.loud_at.size : runs ? plan.runs_at.size : stats ? at.stats + kStatsRowBytes * T : blocks ? at.expect + (plan.judged ? 4 * T : 0) : salvage ? at.win + 4 * m : verify ? at.res + sizeof(VerifyWords) * m : digest ? at.res + sizeof(DigestWords) * m : window ? at.win + sizeof(WindowOut) * m : end;
+    if (spectrum) {  // likewise
+        std::vector<SpIn> xin;
+        for (const PlanItem& p : plan.items) xin.push_back(SpIn{nullptr, nullptr, p.item.frames, (uint32_t)LACX_PCM_PLANAR_I32, p.info.channels, p.info.bit_depth, false});
+        if (const char* why = sp_check(xin.data(), m, sp_logn(spectrum))) return why;
+        at.spec = up16(at.res + sizeof(DigestWords) * m);
+        plan.spec_at = sp_layout(at.spec, xin.data(), m, sp_logn(spectrum));
+    }
+    at.size = spectrum ? plan.spec_at.size : truepeak ? plan.peak_at.size : loudness ? plan.loud_at.size : runs ? plan.runs_at.size : stats ? at.stats + kStatsRowBytes * T : blocks ? at.expect + (plan.judged ? 4 * T : 0) : salvage ? at.win + 4 * m : verify ? at.res + sizeof(VerifyWords) * m : digest ? at.res + sizeof(DigestWords) * m : window ? at.win + sizeof(WindowOut) * m : end;
     plan.need.payload = (plan.host_src ? plan.src_at + plan.host_src_bytes : plan.total_pay) + kDecodeTailPad;
     plan.need.blocks = T;
     plan.need.pcm_frames = own_pcm ? plan.pcm_total : 0;
@@ -502,6 +518,13 @@ inline void plan_fill_tables(const DecodePlan& plan, const BatchIn* in, const Pl
                                p.info.channels, p.info.bit_depth, false});
         tp_fill(plan.peak_at, tin.data(), m, h);
     }
+    if (plan.spectrum) {  // likewise, and the window and twiddle tables
+        std::vector<SpIn> xin;
+        for (const PlanItem& p : plan.items)
+            xin.push_back(SpIn{base.left + p.pcm_at, p.item.channels == 2 ? base.right + p.pcm_at : nullptr, p.item.frames, (uint32_t)LACX_PCM_PLANAR_I32,
+                               p.info.channels, p.info.bit_depth, false});
+        sp_fill(plan.spec_at, xin.data(), m, h);
+    }
     if (!plan.lane_blk.empty()) std::memcpy(h + at.lane_blk, plan.lane_blk.data(), 4 * plan.lane_blk.size());
     if (!plan.v2_items.empty()) std::memcpy(h + at.v2_items, plan.v2_items.data(), 4 * plan.v2_items.size());
 }
@@ -540,8 +563,8 @@ inline DecodeArgs plan_args(const DecodePlan& plan, const uint8_t* tables, const
         a.no_output = plan.form == DecodeForm::blocks;
     }
     // (a loudness job has no digest: launch_decode then ends with k_ms_inverse in place, and the loudness kernels follow it;
-    // a true-peak job likewise)
-    if (plan.form == DecodeForm::digest && !plan.loudness && !plan.truepeak) a.digest = reinterpret_cast<DigestWords*>(const_cast<uint8_t*>(tables) + at.res);
+    // a true-peak and a spectrum job likewise)
+    if (plan.form == DecodeForm::digest && !plan.loudness && !plan.truepeak && !plan.spectrum) a.digest = reinterpret_cast<DigestWords*>(const_cast<uint8_t*>(tables) + at.res);
     if (plan.stats || plan.runs) a.no_output = true;  // launch_decode ends with k_ms_inverse; k_stats_blocks follows it (plan_stats_args)
     return a;
 }
@@ -569,5 +592,8 @@ inline LoudArgs plan_loud_args(const DecodePlan& plan, const uint8_t* tables, ui
 
 // A true-peak job's arguments for k_truepeak: the tables of truepeak_plan.h inside the tables.
 inline TpArgs plan_peak_args(const DecodePlan& plan, uint8_t* tables) { return tp_args(plan.peak_at, plan.items.size(), tables, nullptr); }
+
+// A spectrum job's arguments for k_spectrum: the tables of spectrum_plan.h inside the tables.
+inline SpArgs plan_spec_args(const DecodePlan& plan, uint8_t* tables) { return sp_args(plan.spec_at, plan.items.size(), tables, nullptr); }
 
 }  // namespace lacx

@@ -51,6 +51,7 @@ struct lacx_decoder {
     std::vector<lacx_loudness_row> loud_host;                    // the last loudness call's rows as the device left them
     std::vector<std::vector<lacx_loudness_row>> item_loud;       // ... per item
     std::vector<std::vector<lacx_truepeak_row>> item_peak;       // the last true-peak call's rows per item
+    std::vector<std::vector<lacx_spectrum_row>> item_spec;       // the last spectrum call's rows per item
     std::vector<std::vector<lacx_block_info>> item_info;     // the last inspection call's rows per item
     // ... and, where it asked for partition detail, the entries of all its blocks: [T][2][256] each, item i's blocks
     // from info_block0[i] on (~0u: the item has none)

@@ -8,6 +8,7 @@ struct lacx_run_detector;
 struct lacx_run;
 struct lacx_loudness_row;
 struct lacx_truepeak_row;
+struct lacx_spectrum_row;
 
 namespace lacx {
 
@@ -321,6 +322,33 @@ struct TpArgs {
     const TpItem* items = nullptr;                 // [nitems]
     const unsigned long long* tile_off = nullptr;  // [nitems + 1] prefix sums of the items' tiles
     TpAcc* rows = nullptr;                         // [total_rows], zero on entry
+    unsigned long long* bad = nullptr;             // [nitems] lowest digest_bad_key per item (all ones on entry), or null
+};
+// Spectrum (k_spectrum of k_spectrum.hip, spectrum_core.h): the tables spectrum_plan.h lays out.  One form for both jobs, as
+// true peak has it.  A workgroup takes one row of one item: the windows whose first frame lies in the row's 16384 frames.
+constexpr uint32_t kSpThreads = 256;
+constexpr uint32_t kSpBands = 64;                  // uniform bands of N / 128 bins; the Nyquist bin belongs to the last
+constexpr uint32_t kSpRowFrames = 16384;           // frames per row, counted from the item's frame 0
+constexpr uint32_t kSpMinLog = 8, kSpMaxLog = 12;  // window lengths N = 256 .. 4096; the hop is N / 2
+struct SpItem {
+    const void* data0;                             // as DigestSource
+    const void* data1;
+    unsigned long long frames;
+    unsigned long long row0;                       // the item's first row
+    unsigned long long windows;                    // ceil(frames / (N / 2))
+    uint32_t rows;                                 // ceil(frames / kSpRowFrames)
+    uint32_t layout;
+    uint8_t channels, bit_depth, validate, pad[5];
+};
+struct SpArgs {
+    uint32_t nitems = 0;
+    uint32_t logn = 0;                             // N = 1 << logn
+    unsigned long long total_rows = 0;
+    const SpItem* items = nullptr;                 // [nitems]
+    const unsigned long long* row_off = nullptr;   // [nitems + 1] prefix sums of the items' rows
+    const double* window = nullptr;                // [N] the periodic Hann window
+    const double* twiddle = nullptr;               // [N / 2][2] cos, -sin of 2 pi k / N
+    lacx_spectrum_row* rows = nullptr;             // [total_rows], zero on entry
     unsigned long long* bad = nullptr;             // [nitems] lowest digest_bad_key per item (all ones on entry), or null
 };
 }  // namespace lacx

@@ -123,6 +123,7 @@ EXPORTS = (
     "lacx_decoder_stats_batch_device", "lacx_decoder_stats_pcm_batch_device", "lacx_decoder_item_block_stats", "lacx_stats_combine",
     "lacx_decoder_loudness_batch_device", "lacx_decoder_loudness_pcm_batch_device", "lacx_decoder_item_loudness_rows", "lacx_loudness_combine",
     "lacx_decoder_truepeak_batch_device", "lacx_decoder_truepeak_pcm_batch_device", "lacx_decoder_item_truepeak_rows", "lacx_truepeak_combine",
+    "lacx_decoder_spectrum_batch_device", "lacx_decoder_spectrum_pcm_batch_device", "lacx_decoder_item_spectrum_rows", "lacx_spectrum_combine",
     "lacx_decoder_inspect_batch_device", "lacx_decoder_item_block_info", "lacx_decoder_item_partitions", "lacx_inspect_combine",
     "lacx_decoder_inspect_guard", "lacx_transcode_batch",
     "lacx_decoder_runs_batch_device", "lacx_decoder_runs_pcm_batch_device", "lacx_decoder_item_runs",
@@ -252,6 +253,13 @@ def lib():
         L.lacx_decoder_item_truepeak_rows.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.POINTER(TruePeakRow)), C.POINTER(C.c_uint32)]
         L.lacx_truepeak_combine.argtypes = [C.POINTER(C.POINTER(TruePeakRow)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8),
                                             C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(TruePeak)]
+        L.lacx_decoder_spectrum_batch_device.argtypes = [C.c_void_p, C.POINTER(Span), C.c_uint32, C.c_uint32, C.c_double, C.c_void_p, C.POINTER(C.c_int),
+                                                         C.POINTER(Spectrum), C.POINTER(C.c_float)]
+        L.lacx_decoder_spectrum_pcm_batch_device.argtypes = [C.c_void_p, C.POINTER(DigestSource), C.c_uint32, C.c_uint32, C.c_double, C.c_void_p,
+                                                             C.POINTER(C.c_int), C.POINTER(Spectrum), C.POINTER(C.c_float)]
+        L.lacx_decoder_item_spectrum_rows.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.POINTER(SpectrumRow)), C.POINTER(C.c_uint32)]
+        L.lacx_spectrum_combine.argtypes = [C.POINTER(SpectrumRow), C.c_uint32, C.c_uint8, C.c_uint8, C.c_uint64, C.c_uint32, C.c_uint32, C.c_double,
+                                            C.POINTER(Spectrum)]
         L.lacx_decoder_inspect_batch_device.argtypes = [C.c_void_p, C.POINTER(Span), C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_int),
                                                         C.POINTER(StreamReport), C.POINTER(C.c_float)]
         L.lacx_decoder_item_block_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.POINTER(BlockInfo)), C.POINTER(C.c_uint32)]
@@ -295,7 +303,8 @@ def abi_structs() -> dict:
             "manifest_info": ManifestInfo, "recovery_params": RecoveryParams, "recovery_info": RecoveryInfo,
             "repair_result": RepairResult, "channel_stats": ChannelStats, "block_stats": BlockStats,
             "channel_totals": ChannelTotals, "stats": Stats, "loudness_row": LoudnessRow, "loudness": Loudness,
-            "truepeak_row": TruePeakRow, "truepeak_channel": TruePeakChannel, "truepeak": TruePeak, "channel_info": ChannelInfo, "block_info": BlockInfo,
+            "truepeak_row": TruePeakRow, "truepeak_channel": TruePeakChannel, "truepeak": TruePeak,
+            "spectrum_row": SpectrumRow, "spectrum": Spectrum, "channel_info": ChannelInfo, "block_info": BlockInfo,
             "stream_report": StreamReport, "edit_segment": EditSegment, "edit_output": EditOutput,
             "edit_result": EditResult, "run_detector": RunDetector, "run_query": RunQuery, "run": Run,
             "run_totals": RunTotals, "runs_result": RunsResult}
@@ -1076,6 +1085,44 @@ def truepeak_combine(sets) -> TruePeak:
     rates = (C.c_uint32 * max(1, n))(*[s[4] for s in sets])
     out = TruePeak()
     if lib().lacx_truepeak_combine(ptrs, counts, channels, depths, frames, rates, C.c_uint32(n), C.byref(out)) != OK:
+        raise ValueError(lib().lacx_decode_last_error().decode(errors="replace"))
+    return out
+
+
+# ---- spectrum: the long-term power spectrum in 64 bands and the bandwidth (lacx.h) ----
+SPECTRUM_WINDOWS = (256, 512, 1024, 2048, 4096)
+SPECTRUM_BANDS = 64
+SPECTRUM_ROW_FRAMES = 16384
+
+
+class SpectrumRow(C.Structure):
+    """One segment of 16384 frames: per channel and band the summed one-sided power of the Hann windows whose first frame
+    lies in it (lacx_spectrum_row)."""
+    _fields_ = [("power", (C.c_double * 64) * 2)]
+
+
+class Spectrum(C.Structure):
+    """The long-term spectrum of an item (lacx_spectrum): per channel `level_db[64]` in dB relative to a full-scale sine (-inf
+    for a zero band), `bandwidth_hz` (the upper edge of the highest band at or above `floor_db`, 0 when none is) and
+    `peak_band`.  It only measures."""
+    _fields_ = [("frames", C.c_uint64), ("windows", C.c_uint64), ("sample_rate", C.c_uint32), ("window", C.c_uint32), ("rows", C.c_uint32),
+                ("channels", C.c_uint8), ("bit_depth", C.c_uint8), ("peak_band", C.c_uint8 * 2), ("floor_db", C.c_double),
+                ("bandwidth_hz", C.c_double * 2), ("level_db", (C.c_double * 64) * 2)]
+
+    def peak_hz(self, channel: int) -> float:
+        """The centre of the channel's strongest band."""
+        return (self.peak_band[channel] + 0.5) * self.sample_rate / (2.0 * SPECTRUM_BANDS)
+
+
+def spectrum_combine(rows, channels, bit_depth, frames, sample_rate, window=2048, floor_db=-100.0) -> Spectrum:
+    """Host only: the totals of one item's rows as spectrum_batch makes them (lacx.h).  rows: SpectrumRow records or their
+    bytes."""
+    raw = bytes(rows) if isinstance(rows, (C.Array, bytes, bytearray, np.ndarray)) else b"".join(bytes(r) for r in rows)
+    blob = np.frombuffer(raw, dtype=np.uint8).copy()
+    out = Spectrum()
+    if lib().lacx_spectrum_combine(C.cast(blob.ctypes.data, C.POINTER(SpectrumRow)), C.c_uint32(len(blob) // C.sizeof(SpectrumRow)), C.c_uint8(channels),
+                                   C.c_uint8(bit_depth), C.c_uint64(frames), C.c_uint32(sample_rate), C.c_uint32(window), C.c_double(floor_db),
+                                   C.byref(out)) != OK:
         raise ValueError(lib().lacx_decode_last_error().decode(errors="replace"))
     return out
 
@@ -2032,6 +2079,64 @@ class Decoder:
             raise RuntimeError(lib().lacx_decode_last_error().decode(errors="replace"))
         errors = {i: lib().lacx_decoder_item_error(self._h, i).decode(errors="replace") for i in range(n) if rcs[i] != OK}
         return self._raise_batch(rc, errors, [None if i in errors else (_copy_struct(out[i]), self._peak_rows(i)) for i in range(n)])
+
+    # ---- spectrum: the long-term power spectrum in 64 bands and the bandwidth ----
+    def _spec_rows(self, i):
+        ptr, count = C.POINTER(SpectrumRow)(), C.c_uint32()
+        if lib().lacx_decoder_item_spectrum_rows(self._h, C.c_uint32(i), C.byref(ptr), C.byref(count)) != OK:
+            count.value = 0
+        rows = (SpectrumRow * count.value)()  # one copy: the rows die with the decoder's next call
+        if count.value:
+            C.memmove(rows, ptr, C.sizeof(rows))
+        return rows
+
+    def spectrum_batch(self, lacs, window: int = 2048, floor_db: float = -100.0, stream: int = 0) -> list:
+        """Many streams decoded and their banded power spectrum (Hann windows of `window` frames, hop window / 2, FP64) taken
+        as one device job, strict like digest_batch: per item (Spectrum, a ctypes array of SpectrumRow), None where the stream
+        does not parse or decode (those raise BatchDecodeError once the others are done).  One row per 16384 frames comes
+        back, not the PCM; kernel milliseconds in `last_ms`.  ValueError for a window that is none of SPECTRUM_WINDOWS."""
+        bufs = [np.frombuffer(x, dtype=np.uint8) for x in lacs]
+        n = len(bufs)
+        spans = (Span * max(1, n))(*[Span(b.ctypes.data_as(C.POINTER(C.c_uint8)), b.size) for b in bufs])
+        out = (Spectrum * max(1, n))()
+        rc, errors = self._batch(n, lambda rcs, ms: lib().lacx_decoder_spectrum_batch_device(
+            self._h, spans, C.c_uint32(n), C.c_uint32(window), C.c_double(floor_db), C.c_void_p(stream), rcs, out, ms))
+        if rc == E_INVALID and not errors:  # the call's own arguments: the window
+            raise ValueError(lib().lacx_decode_last_error().decode(errors="replace"))
+        return self._raise_batch(rc, errors, [None if i in errors else (_copy_struct(out[i]), self._spec_rows(i)) for i in range(n)])
+
+    def spectrum(self, lac, window: int = 2048, floor_db: float = -100.0) -> Spectrum:
+        """The totals of spectrum_batch of one stream; RuntimeError with the decode's message where it fails."""
+        try:
+            return self.spectrum_batch([lac], window, floor_db)[0][0]
+        except BatchDecodeError as e:
+            raise RuntimeError(e.errors[0]) from None
+
+    def spectrum_pcm_batch(self, sources, window: int = 2048, floor_db: float = -100.0, stream: int = 0) -> list:
+        """Device-resident PCM measured where it lies: per item (Spectrum, [SpectrumRow]) -- what spectrum_batch gives for the
+        .lac made from it.  Sources as truepeak_pcm_batch takes them."""
+        n = len(sources)
+        items = (DigestSource * max(1, n))()
+        for it, (pcm, rate, depth) in zip(items, sources):
+            if isinstance(pcm, (tuple, list)):
+                d0, d1, layout, channels, frames = pcm
+                it.pcm = Pcm(d0, d1, layout, channels)
+            else:
+                it.pcm, frames = pcm_of(pcm, depth)
+            it.frames, it.sample_rate, it.bit_depth = frames, rate, depth
+        out = (Spectrum * max(1, n))()
+        if self._h is None:
+            raise RuntimeError("decoder is closed")
+        rcs, ms = (C.c_int * max(1, n))(), C.c_float()
+        rc = lib().lacx_decoder_spectrum_pcm_batch_device(self._h, items, C.c_uint32(n), C.c_uint32(window), C.c_double(floor_db), C.c_void_p(stream),
+                                                          rcs, out, C.byref(ms))
+        self.last_ms = float(ms.value)
+        if rc == E_INVALID and all(rcs[i] == OK for i in range(n)):  # the call's own arguments
+            raise ValueError(lib().lacx_decode_last_error().decode(errors="replace"))
+        if rc == E_DEVICE:
+            raise RuntimeError(lib().lacx_decode_last_error().decode(errors="replace"))
+        errors = {i: lib().lacx_decoder_item_error(self._h, i).decode(errors="replace") for i in range(n) if rcs[i] != OK}
+        return self._raise_batch(rc, errors, [None if i in errors else (_copy_struct(out[i]), self._spec_rows(i)) for i in range(n)])
 
     # ---- runs: where a stream is silent, clips or holds one value ----
     @staticmethod

@@ -27,6 +27,9 @@
 // peak (the other half of what those tools write): the ITU-R BS.1770 true peak of the same two kinds of file, the 4x
 // oversampled maximum made on the device in exact integers (lacx_decoder_truepeak_batch_device /
 // lacx_decoder_truepeak_pcm_batch_device).  It only measures.
+// spectrum (no counterpart in the reference's tool; `spek`, `sox ... stat -freq`): the long-term power spectrum of the same
+// two kinds of file in 64 bands and the bandwidth read off it, the Hann STFT made on the device in FP64
+// (lacx_decoder_spectrum_batch_device / lacx_decoder_spectrum_pcm_batch_device).  It only measures.
 // inspect (`flac -a` for .lac): how each stream was coded and where its bits go, read out of the bytes on the device by a
 // parse-only walk (lacx_decoder_inspect_batch_device).
 // recompress, cut, join (no counterpart in the reference's tool; `flac -f`, `--skip` / `--until` and joining, for .lac): .lac
@@ -75,6 +78,9 @@ void usage() {
                  "  lacx_cli peak FILE... [--album] [--blocks]   (.lac and .wav files: BS.1770 true peak in dBTP and linear, sample peak in\n"
                  "      dBFS, where the peak lies, `over` for an inter-sample over, one line per file; --album: one further line for all files\n"
                  "      together; --blocks: one further line per 16384 frames; nothing is applied to the audio; exit 0 done, 2 refused)\n"
+                 "  lacx_cli spectrum FILE... [--window=N] [--floor=DB] [--blocks]   (.lac and .wav files: per channel the bandwidth -- the upper\n"
+                 "      edge of the highest of 64 bands at or above the floor, default -100 dBFS -- and the strongest band, one line per file;\n"
+                 "      --window: 256, 512, 1024, 2048 (default) or 4096 frames; --blocks: the 64 levels of every 16384 frames; exit 0 done, 2 refused)\n"
                  "  lacx_cli inspect FILE... [--blocks] [--partitions]   (.lac files: predictors, residual modes and where the bits go, as\n"
                  "      integers, one line per file; --blocks: one further line per block; --partitions: and one per partition;\n"
                  "      a damaged stream prints its line with lost_blocks counted; exit 0 when every file was inspected, else 1)\n"
@@ -1026,6 +1032,135 @@ int peak_command(int argc, char** argv) {
     return 0;
 }
 
+// lacx_cli spectrum FILE... [--window=N] [--floor=DB] [--blocks]: the banded long-term power spectrum of what every .lac
+// decodes to and of every WAV's data chunk (lacx_decoder_spectrum_batch_device / lacx_decoder_spectrum_pcm_batch_device): a
+// .lac and the WAV it was made from print the same numbers.  One line per file in argument order: per channel the bandwidth
+// (the upper edge of the highest band at or above the floor) and the centre of the strongest band, then the format.
+// --blocks: per row of 16384 frames and channel one further line with the 64 band powers (%.17g: every bit).  Jobs, exit
+// codes and messages as `peak` has them.
+std::string spectrum_text(const lacx_spectrum& t) {
+    std::string out;
+    for (unsigned c = 0; c < t.channels; ++c) {
+        char s[128];
+        std::snprintf(s, sizeof(s), "%sch%u: bandwidth=%.1f Hz peak=%.1f Hz", c ? " " : "", c, t.bandwidth_hz[c], (t.peak_band[c] + 0.5) * t.sample_rate / 128.0);
+        out += s;
+    }
+    char s[160];
+    std::snprintf(s, sizeof(s), " %u Hz %u bit window=%u windows=%llu floor=%.1f dBFS", t.sample_rate, (unsigned)t.bit_depth, t.window, (unsigned long long)t.windows,
+                  t.floor_db);
+    return out + s;
+}
+
+int spectrum_command(int argc, char** argv) {
+    bool per_block = false;
+    uint32_t window = 2048;
+    double floor_db = -100.0;
+    std::vector<const char*> paths;
+    for (int i = 2; i < argc; ++i) {
+        if (std::strcmp(argv[i], "--blocks") == 0) per_block = true;
+        else if (std::strncmp(argv[i], "--window=", 9) == 0) window = (uint32_t)std::strtoul(argv[i] + 9, nullptr, 10);
+        else if (std::strncmp(argv[i], "--floor=", 8) == 0) floor_db = std::strtod(argv[i] + 8, nullptr);
+        else paths.push_back(argv[i]);
+    }
+    const int n = (int)paths.size();
+    if (n == 0) {
+        usage();
+        return 2;
+    }
+    std::vector<std::vector<uint8_t>> data(n);
+    std::vector<std::string> error(n);
+    std::vector<lacx_spectrum> spec(n, lacx_spectrum{});
+    std::vector<std::vector<lacx_spectrum_row>> rows(n);
+    std::vector<int> lacs, wavs;  // indices of the files of each kind that go to the device
+    std::vector<lacx_wav_info> winfo(n, lacx_wav_info{});
+    for (int i = 0; i < n; ++i) {
+        if (!load_file(paths[i], data[i])) {
+            error[i] = "Failed to read file";
+        } else if (data[i].size() >= 4 && std::memcmp(data[i].data(), "RIFF", 4) == 0) {
+            if (lacx_wav_parse(data[i].data(), data[i].size(), &winfo[i]) != LACX_OK) error[i] = "Failed to read WAV";
+            else wavs.push_back(i);
+        } else {
+            lacs.push_back(i);
+        }
+    }
+    lacx_decoder* dec = nullptr;
+    if (lacx_decoder_create(-1, &dec) != LACX_OK) {
+        std::cerr << "Error: lacx_decoder_create failed\n";
+        return 2;
+    }
+    auto collect = [&](const std::vector<int>& which, int rc, const std::vector<int>& item_rc, const std::vector<lacx_spectrum>& out) {
+        for (size_t k = 0; k < which.size(); ++k) {
+            const lacx_spectrum_row* r = nullptr;
+            uint32_t count = 0;
+            if (rc != LACX_E_DEVICE && item_rc[k] == LACX_OK && (rc == LACX_OK || out[k].window) && lacx_decoder_item_spectrum_rows(dec, (uint32_t)k, &r, &count) == LACX_OK) {
+                spec[which[k]] = out[k];
+                rows[which[k]].assign(r, r + count);
+            } else {
+                error[which[k]] = rc == LACX_E_DEVICE || item_rc[k] == LACX_OK ? lacx_decode_last_error() : lacx_decoder_item_error(dec, (uint32_t)k);
+            }
+        }
+    };
+    if (!lacs.empty()) {
+        std::vector<lacx_span> spans;
+        for (int i : lacs) spans.push_back(lacx_span{data[i].data(), data[i].size()});
+        std::vector<int> item_rc(lacs.size(), LACX_OK);
+        std::vector<lacx_spectrum> out(lacs.size());
+        const int rc = lacx_decoder_spectrum_batch_device(dec, spans.data(), (uint32_t)spans.size(), window, floor_db, nullptr, item_rc.data(), out.data(), nullptr);
+        collect(lacs, rc, item_rc, out);
+    }
+    if (!wavs.empty()) {
+        std::vector<lacx_digest_source> src;
+        std::vector<void*> dev;
+        std::vector<int> sent;
+        for (int i : wavs) {
+            const lacx_wav_info& w = winfo[i];
+            const uint64_t bytes = w.frames * w.channels * (uint64_t)(w.bit_depth / 8);
+            void* p = nullptr;
+            if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess ||
+                hipMemcpy(p, data[i].data() + w.data_offset, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+                error[i] = "Failed to upload WAV data to the device";
+                if (p) (void)hipFree(p);
+                continue;
+            }
+            lacx_digest_source s{};
+            s.pcm = lacx_pcm{p, nullptr, w.bit_depth == 16 ? LACX_PCM_INTERLEAVED_I16 : LACX_PCM_INTERLEAVED_I24, w.channels};
+            s.frames = w.frames;
+            s.sample_rate = w.sample_rate;
+            s.bit_depth = (uint8_t)w.bit_depth;
+            src.push_back(s), dev.push_back(p), sent.push_back(i);
+        }
+        if (!src.empty()) {
+            std::vector<int> item_rc(src.size(), LACX_OK);
+            std::vector<lacx_spectrum> out(src.size());
+            const int rc = lacx_decoder_spectrum_pcm_batch_device(dec, src.data(), (uint32_t)src.size(), window, floor_db, nullptr, item_rc.data(), out.data(), nullptr);
+            collect(sent, rc, item_rc, out);
+        }
+        for (void* p : dev) (void)hipFree(p);
+    }
+    bool refused = false;
+    for (int i = 0; i < n; ++i) {
+        if (error[i].empty()) continue;
+        std::cerr << "Spectrum failed: " << paths[i] << ": " << error[i] << "\n";
+        refused = true;
+    }
+    lacx_decoder_destroy(dec);
+    if (refused) return 2;
+    for (int i = 0; i < n; ++i) {
+        std::cout << spectrum_text(spec[i]) << " " << paths[i] << "\n";
+        for (size_t s = 0; per_block && s < rows[i].size(); ++s)
+            for (unsigned c = 0; c < spec[i].channels; ++c) {
+                std::string line = "  row=" + std::to_string(s) + " ch" + std::to_string(c) + ":";
+                for (int b = 0; b < 64; ++b) {
+                    char v[40];
+                    std::snprintf(v, sizeof(v), " %.17g", rows[i][s].power[c][b]);
+                    line += v;
+                }
+                std::cout << line << "\n";
+            }
+    }
+    return 0;
+}
+
 // lacx_cli inspect FILE... [--blocks] [--partitions]: how every .lac was coded and where its bits go, read out of the bytes
 // on the device by a parse-only walk (lacx_decoder_inspect_batch_device), all files as one job.  One line of integers per
 // file in argument order; with --blocks one further line per block (its channel blocks behind it), with --partitions one
@@ -1660,6 +1795,7 @@ int main(int argc, char** argv) {
     if (mode == "stats" && argc >= 3) return stats_command(argc, argv);
     if (mode == "loudness") return loudness_command(argc, argv);
     if (mode == "peak") return peak_command(argc, argv);
+    if (mode == "spectrum") return spectrum_command(argc, argv);
     if (mode == "inspect" && argc >= 3) return inspect_command(argc, argv);
     if (mode == "find" && argc >= 3) return find_command(argc, argv);
     if (mode == "split" && argc >= 4) return split_command(argc, argv);
