@@ -70,6 +70,10 @@
  *   lacx_decoder_item_spectrum_rows,
  *   lacx_spectrum_combine   <- whether the audio is what it claims to be: the long-term power spectrum in 64 bands (Hann
  *                             STFT in FP64) and the bandwidth of a stream, made on the device
+ *   lacx_decoder_accuraterip_batch_device, lacx_decoder_accuraterip_pcm_batch_device,
+ *   lacx_decoder_item_ar_tracks, lacx_decoder_item_ar_sums,
+ *   lacx_ar_ids             <- whether the audio is an accurate rip, and of which pressing: the AccurateRip v1 / v2 track
+ *                             checksums of a disc of CD audio at every read offset within a radius, made on the device
  *   lacx_recovery_build, lacx_recovery_build_batch_view, lacx_recovery_parse,
  *   lacx_recovery_scan_batch, lacx_recovery_repair, lacx_recovery_repair_batch_view,
  *   lacx_decoder_item_bad_slices <- bringing lost bytes back: a parity sidecar ("LACR", Reed-Solomon over GF(2^8)) beside
@@ -1178,6 +1182,91 @@ int lacx_decoder_spectrum_pcm_batch_device(lacx_decoder* dec, const lacx_digest_
 int lacx_decoder_item_spectrum_rows(const lacx_decoder* dec, uint32_t i, const lacx_spectrum_row** rows, uint32_t* count);
 int lacx_spectrum_combine(const lacx_spectrum_row* rows, uint32_t count, uint8_t channels, uint8_t bit_depth, uint64_t frames,
                           uint32_t sample_rate, uint32_t window, double floor_db, lacx_spectrum* out);
+
+/* Rip checksums: the two AccurateRip track checksums of a disc of CD audio (2 channels, 16 bit, 44100 Hz) at every read
+ * offset within a radius, made on the device where the samples lie.  Ripping tools compare these sums with a database of
+ * other people's rips of the same disc; a pressing whose audio is shifted by a few hundred samples shows at another offset.
+ * The v1 sum is linear and follows from prefix sums at every offset; the v2 sum adds the high half of a 64-bit product and
+ * has no such shortcut, so CPU tools give it at offset 0 only.  Here every (multiplier, offset) pair is one multiply on the
+ * device.  Out of scope: the database lookup, cue sheets (track lengths come in as frames), the CTDB CRC, data tracks, a
+ * lenient form, anything that is not 2 channels / 16 bit / 44100 Hz.
+ * Definition (csrc/accuraterip_core.h is its only statement in code).  The formulas are the widely published
+ * ones, written down without access to the database.
+ *   Disc: an ordered list of S >= 1 whole sources, concatenated to D frames, and T track lengths n_0 .. n_(T-1) in frames, 1
+ *   <= T <= 99, every n_t >= 1, their sum D; track t starts at disc frame s_t = n_0 + .. + n_(t-1).  Tracks and sources are
+ *   independent partitions of the disc: one image with a cue sheet is S = 1, T > 1; one file per track is S = T.  Frame j is
+ *   the word w[j] = (uint16)left[j] | (uint16)right[j] << 16; x(j) = w[j] for 0 <= j < D and 0 elsewhere.
+ *   Sums: LACX_AR_FIRST / LACX_AR_LAST say that track 0 is the disc's first track / track T-1 its last.  lo_t = 2940 if t =
+ *   0 and FIRST, else 1; hi_t = n_t - 2940 if t = T-1 and LAST, else n_t.  For 0 <= radius <= 2939, every offset o in
+ *   [-radius, radius] and every track, with the multiplier m a uint32 and p = (uint64)m * x(s_t + o + m - 1):
+ *     v1[t][o]   = sum over m = lo_t .. hi_t of lo32(p)              mod 2^32
+ *     v2[t][o]   = sum over m = lo_t .. hi_t of lo32(p) + hi32(p)    mod 2^32
+ *     s450[t][o] = sum over k = 1 .. 588 of lo32(k * x(s_t + o + 450 * 588 + k - 1))   mod 2^32, where n_t >= 451 * 588;
+ *                  elsewhere 0 and the track carries LACX_AR_TRACK_NO_S450.
+ *   An empty range (hi_t < lo_t) gives 0 and LACX_AR_TRACK_SHORT.  With both flags no sum reads outside [0, D); a partial
+ *   disc reads zeros there.  Sums mod 2^32 do not depend on the order of evaluation: device, CPU twin and a numpy
+ *   restatement agree bit for bit, in any batch.
+ *   Ids (host only), given when every n_t is a multiple of 588 and both flags are set, else all 0 and LACX_AR_NO_IDS:
+ *   lba_t = lba0 + s_t / 588, leadout = lba0 + D / 588; id1 = (sum of lba_t + leadout) mod 2^32; id2 = (sum of max(lba_t, 1)
+ *   (t + 1) + leadout (T + 1)) mod 2^32; cddb = ((sum of digitsum((lba_t + 150) / 75)) mod 255) << 24 | ((leadout + 150) / 75
+ *   - (lba_0 + 150) / 75) << 8 | T, integer divisions.
+ * lacx_ar_disc: the disc's sources [first_source, first_source + sources) of the call's source array and its track lengths
+ *   [first_track, first_track + tracks) of the call's track_frames array; tracks = 0: one track per source, its frames.
+ * lacx_decoder_accuraterip_batch_device: strict, like lacx_decoder_digest_batch_device -- the decode, the in-place mid/side
+ *   inverse, then k_accuraterip (one launch) on `stream`.  A disc's streams lie side by side in the decoder's buffers; a
+ *   track boundary need not be a stream boundary, and an offset reaches into the neighbouring stream.  Refused per disc on
+ *   the host before any device work, each LACX_E_INVALID: "disc has no sources", "sources outside the call's array",
+ *   "tracks outside the call's array", "more than 99 tracks", "track T is empty", "track lengths do not sum to the disc's
+ *   frames (A, B)", "radius above 2939", "unknown flags", "source k: not CD audio (C channels, B bit, R Hz)", "source k:
+ *   <lacx_stream_parse's text>" (with that call's code).  A source that fails to decode fails its disc with the decode's
+ *   own code and "source k: ..."; the disc gets a zeroed result and no sums, and does not cost the other discs.  disc_rc,
+ *   out: nullable arrays of ndiscs.  lacx_decoder_item_error(dec, disc) is the disc's text.
+ * lacx_decoder_accuraterip_pcm_batch_device: device-resident source PCM in any LACX_PCM_* layout that can hold 16-bit
+ *   audio; the per-source host checks ("source k: <text>"), the device-found validation texts ("source k: <text>") and the
+ *   bounds are those of lacx_decoder_digest_pcm_batch_device.
+ * lacx_decoder_item_ar_tracks: per track of disc `disc` of the decoder's last rip-checksum call its start, frames, flags and
+ *   the three sums at offset 0.  lacx_decoder_item_ar_sums: the sums of one track at every offset, count = 2 radius + 1,
+ *   ordered o = -radius .. radius.  Both valid until the decoder's next call; LACX_E_INVALID outside that call, and for a
+ *   disc that failed (it has no sums).
+ * lacx_ar_ids: host only.  LACX_E_INVALID: null arguments, no tracks, more than 99, an empty track, unknown flags.  A disc
+ *   that has no ids gives LACX_OK and zeros.
+ * Everything else as lacx_decoder_truepeak_batch_device.  No scratch: 12 (2 radius + 1) bytes per track inside the tables.
+ * Time (scripts/accuraterip_bench.py, profiles/accuraterip_bench.txt): on 48 four-minute stereo 16-bit streams as
+ * four discs of twelve tracks 20.3 ms of kernels and 44.3 ms of wall at radius 0, 4.7 ms of kernels below the digest's job,
+ * against 128.9 ms of wall for decode plus the same sums in torch int64 on the same device; at radius 2939 (2.99e12
+ * multiplier-offset pairs) 201.4 ms of kernels and 226.1 ms of wall; k_accuraterip alone 1.91 ms and 180.8 ms. */
+#define LACX_AR_FIRST 1u
+#define LACX_AR_LAST 2u
+#define LACX_AR_NO_IDS 4u            /* lacx_ar_result.flags only */
+#define LACX_AR_TRACK_SHORT 1u
+#define LACX_AR_TRACK_NO_S450 2u
+typedef struct lacx_ar_disc {   /* 28 bytes */
+    uint32_t first_source, sources;
+    uint32_t first_track, tracks;
+    uint32_t flags, radius, lba0;
+} lacx_ar_disc;
+typedef struct lacx_ar_id {     /* 12 bytes */
+    uint32_t id1, id2, cddb;
+} lacx_ar_id;
+typedef struct lacx_ar_result { /* 32 bytes */
+    uint64_t frames;
+    uint32_t tracks, radius, flags;
+    lacx_ar_id ids;
+} lacx_ar_result;
+typedef struct lacx_ar_track {  /* 32 bytes */
+    uint64_t start, frames;
+    uint32_t flags, v1, v2, s450;
+} lacx_ar_track;
+int lacx_decoder_accuraterip_batch_device(lacx_decoder* dec, const lacx_span* lacs, uint32_t nlacs, const uint64_t* track_frames,
+                                          uint32_t ntracks, const lacx_ar_disc* discs, uint32_t ndiscs, void* stream, int* disc_rc,
+                                          lacx_ar_result* out, float* device_ms);
+int lacx_decoder_accuraterip_pcm_batch_device(lacx_decoder* dec, const lacx_digest_source* src, uint32_t nsrc,
+                                              const uint64_t* track_frames, uint32_t ntracks, const lacx_ar_disc* discs, uint32_t ndiscs,
+                                              void* stream, int* disc_rc, lacx_ar_result* out, float* device_ms);
+int lacx_decoder_item_ar_tracks(const lacx_decoder* dec, uint32_t disc, const lacx_ar_track** tracks, uint32_t* count);
+int lacx_decoder_item_ar_sums(const lacx_decoder* dec, uint32_t disc, uint32_t track, const uint32_t** v1, const uint32_t** v2,
+                              const uint32_t** s450, uint32_t* count);
+int lacx_ar_ids(const uint64_t* track_frames, uint32_t ntracks, uint32_t flags, uint32_t lba0, lacx_ar_id* out);
 
 /* Recovery data: repairing a damaged .lac file from a parity sidecar.  Digests, salvage and the manifest all end in "this
  * block is lost"; the container has no redundancy of its own.  A recovery sidecar ("LACR") kept beside the file brings the

@@ -121,6 +121,8 @@ struct DecodeJob {
     uint32_t spectrum = 0;               // the digest form with k_spectrum in k_digest's place (DecodePlan::spectrum): the window length
     double floor_db = 0.0;               // ... the totals' floor
     lacx_spectrum* xres = nullptr;       // spectrum: [n]
+    const ArJobIn* ar = nullptr;         // the digest form with k_accuraterip in k_digest's place (DecodePlan::accuraterip): the discs
+    std::vector<uint32_t>* ar_planned = nullptr;  // ... those that went to the device (DecodePlan::ar_disc); the rest in d->ar_at, d->ar_sums
 };
 static_assert(sizeof(StatsAcc) == kStatsRowBytes, "the plan lays the accumulator rows out kStatsRowBytes apart");
 
@@ -298,7 +300,13 @@ DevErr launch_and_wait(lacx_decoder* d, const DecodeJob& job, const DecodePlan& 
         if (DevErr e = chk(launch_truepeak(plan_peak_args(plan, d->d_meta()), st), "true peak launch")) return e;
     if (plan.spectrum)  // likewise
         if (DevErr e = chk(launch_spectrum(plan_spec_args(plan, d->d_meta()), st), "spectrum launch")) return e;
+    if (plan.accuraterip)  // likewise
+        if (DevErr e = chk(launch_accuraterip(plan_ar_args(plan, d->d_meta()), st), "rip checksum launch")) return e;
     if (DevErr e = chk(hipEventRecord(d->e1, st), "event record")) return e;
+    if (plan.accuraterip && plan.ar_at.total_sums)  // the sums: 12 bytes per track and offset, inside the tables
+        if (DevErr e = chk(hipMemcpyAsync(d->h_meta() + plan.ar_at.sums, d->d_meta() + plan.ar_at.sums, 4 * (size_t)plan.ar_at.total_sums, hipMemcpyDeviceToHost, st),
+                           "D2H rip checksums"))
+            return e;
     if (plan.truepeak && plan.peak_at.total_rows)  // the rows: 32 bytes per 16384 frames, inside the tables
         if (DevErr e = chk(hipMemcpyAsync(d->h_meta() + plan.peak_at.rows, d->d_meta() + plan.peak_at.rows, sizeof(TpAcc) * (size_t)plan.peak_at.total_rows,
                                           hipMemcpyDeviceToHost, st),
@@ -326,7 +334,7 @@ DevErr launch_and_wait(lacx_decoder* d, const DecodeJob& job, const DecodePlan& 
         if (DevErr e = chk(hipMemcpyAsync(d->h_meta() + res, d->d_meta() + res, sizeof(VerifyWords) * m, hipMemcpyDeviceToHost, st), "D2H verify results"))
             return e;
     // the digest form's whole answer: 8 bytes per item
-    if (plan.form == DecodeForm::digest && !plan.loudness && !plan.truepeak && !plan.spectrum)
+    if (plan.form == DecodeForm::digest && !plan.loudness && !plan.truepeak && !plan.spectrum && !plan.accuraterip)
         if (DevErr e = chk(hipMemcpyAsync(d->h_meta() + res, d->d_meta() + res, sizeof(DigestWords) * m, hipMemcpyDeviceToHost, st), "D2H digests"))
             return e;
     // block digests: 4 bytes per block beside the statuses
@@ -359,6 +367,12 @@ DevErr launch_and_wait(lacx_decoder* d, const DecodeJob& job, const DecodePlan& 
 DevErr collect(lacx_decoder* d, const DecodeJob& job, const DecodePlan& plan, hipStream_t st, std::vector<int>& code,
                std::vector<std::string>& err, bool runs_rerun) {
     const bool host = plan.form == DecodeForm::host;
+    if (plan.accuraterip) {  // a disc's answer needs all of its items: the caller puts it together from these
+        d->ar_at = plan.ar_at;
+        const auto* sums = reinterpret_cast<const uint32_t*>(d->h_meta() + plan.ar_at.sums);
+        d->ar_sums.assign(sums, sums + plan.ar_at.total_sums);
+        if (job.ar_planned) *job.ar_planned = plan.ar_disc;
+    }
     for (size_t j = 0; j < plan.items.size(); ++j) {
         const PlanItem& p = plan.items[j];
         const BatchIn& x = job.in[p.src];
@@ -422,6 +436,7 @@ DevErr collect(lacx_decoder* d, const DecodeJob& job, const DecodePlan& plan, hi
             const auto* all = reinterpret_cast<const lacx_spectrum_row*>(d->h_meta() + plan.spec_at.rows);
             rows.assign(all + si.row0, all + si.row0 + si.rows);
             if (job.xres) job.xres[i] = spectrum_of_rows(SpSet{rows.data(), (uint32_t)rows.size(), p.info.channels, p.info.bit_depth, p.info.frames, p.info.sample_rate, plan.spectrum, job.floor_db});
+        } else if (plan.accuraterip) {  // (per disc, not per item)
         } else if (plan.form == DecodeForm::digest) {
             const DigestWords& w = reinterpret_cast<const DigestWords*>(d->h_meta() + plan.at.res)[j];
             if (job.dres) job.dres[i] = make_digest(w.raw, p.info.frames, p.info.sample_rate, p.info.channels, p.info.bit_depth);
@@ -482,7 +497,7 @@ int decode_batch_run(lacx_decoder* d, const DecodeJob& job, std::vector<int>& co
     const char* pad_env = std::getenv("LACX_DECODE_BATCH_PAD");
     DecodePlan plan;
     const char* whole = plan_decode(job.in, job.n, job.form, job.sample_type, pad_env && pad_env[0] == '1', plan, code, err, job.salvage, job.blocks, job.stats,
-                                    job.runs, d->runs_list_cap ? d->runs_list_cap : kRunsListCap, job.loudness, job.truepeak, job.spectrum);
+                                    job.runs, d->runs_list_cap ? d->runs_list_cap : kRunsListCap, job.loudness, job.truepeak, job.spectrum, job.ar);
     if (lacx_device_count() <= 0) whole = "no usable HIP device";
     int rc = whole ? decode_fail(LACX_E_DEVICE, whole) : LACX_OK;
     if (!whole && !plan.items.empty()) {
@@ -1530,6 +1545,255 @@ int lacx_spectrum_combine(const lacx_spectrum_row* rows, uint32_t count, uint8_t
     if (!sp_logn(window)) return decode_fail(LACX_E_INVALID, "unsupported spectrum window: " + std::to_string(window));
     if (sp_rows(frames) != count) return decode_fail(LACX_E_INVALID, "row count does not match the frames");
     *out = spectrum_of_rows(SpSet{rows, count, channels, bit_depth, frames, sample_rate, window, floor_db});
+    return LACX_OK;
+}
+
+// ---- rip checksums (lacx.h) ----
+namespace {
+// The discs of a call against its arrays: per disc its code and text ("" = it goes to the device) and its track lengths.
+// frames / src_code / src_why: per source of the call its frames, or why it is refused.
+struct ArCall {
+    std::vector<int> code;
+    std::vector<std::string> err;
+    std::vector<std::vector<uint64_t>> tracks;
+};
+void ar_resolve(const lacx_ar_disc* discs, uint32_t ndiscs, uint32_t nsrc, const uint64_t* track_frames, uint32_t ntracks, const std::vector<uint64_t>& frames,
+                const std::vector<int>& src_code, const std::vector<std::string>& src_why, ArCall& c) {
+    c.code.assign(ndiscs, LACX_OK);
+    c.err.assign(ndiscs, std::string());
+    c.tracks.assign(ndiscs, {});
+    for (uint32_t k = 0; k < ndiscs; ++k) {
+        const lacx_ar_disc& x = discs[k];
+        auto refuse = [&](int code, const std::string& why) { c.code[k] = code, c.err[k] = why; };
+        if (x.sources == 0) { refuse(LACX_E_INVALID, "disc has no sources"); continue; }
+        if (x.first_source > nsrc || x.sources > nsrc - x.first_source) { refuse(LACX_E_INVALID, "sources outside the call's array"); continue; }
+        if (x.tracks && (!track_frames || x.first_track > ntracks || x.tracks > ntracks - x.first_track)) { refuse(LACX_E_INVALID, "tracks outside the call's array"); continue; }
+        uint64_t total = 0;
+        for (uint32_t i = 0; i < x.sources && c.code[k] == LACX_OK; ++i) {
+            const uint32_t at = x.first_source + i;
+            if (src_code[at] != LACX_OK) refuse(src_code[at], "source " + std::to_string(i) + ": " + src_why[at]);
+            total += frames[at];
+        }
+        if (c.code[k] != LACX_OK) continue;
+        if (x.tracks) c.tracks[k].assign(track_frames + x.first_track, track_frames + x.first_track + x.tracks);
+        else c.tracks[k].assign(frames.begin() + x.first_source, frames.begin() + x.first_source + x.sources);
+        const std::string why = ar_disc_why(x.sources, total, c.tracks[k].data(), (uint32_t)c.tracks[k].size(), x.flags, x.radius);
+        if (!why.empty()) refuse(LACX_E_INVALID, why);
+    }
+}
+
+void ar_reset(lacx_decoder* d, uint32_t ndiscs, lacx_ar_result* out, float* device_ms) {
+    if (device_ms) *device_ms = 0.f;
+    if (out) std::memset(out, 0, sizeof(lacx_ar_result) * ndiscs);
+    d->ar_at = ArLayout{};
+    d->ar_sums.clear();
+    d->ar_ok.assign(ndiscs, 0);
+    d->ar_slot.assign(ndiscs, 0);
+    d->ar_tracks.assign(ndiscs, {});
+}
+
+// Disc k of the call went to the device as the plan's disc `slot` and all of its sources are good: its answer.
+void ar_accept(lacx_decoder* d, uint32_t k, size_t slot, const lacx_ar_disc& x, const std::vector<uint64_t>& tracks, lacx_ar_result* out) {
+    d->ar_ok[k] = 1;
+    d->ar_slot[k] = (uint32_t)slot;
+    ar_tracks(d->ar_at, slot, d->ar_sums.data(), d->ar_tracks[k]);
+    if (out) out[k] = ar_result(d->ar_at, slot, x.lba0, tracks.data());
+}
+
+// How a rip-checksum call ends: as batch_outcome, per disc.
+int ar_outcome(lacx_decoder* d, int rc, ArCall& c, int* disc_rc) {
+    if (disc_rc) std::copy(c.code.begin(), c.code.end(), disc_rc);
+    d->item_err = std::move(c.err);
+    if (rc != LACX_OK) return rc;
+    for (size_t k = 0; k < c.code.size(); ++k)
+        if (c.code[k] != LACX_OK) return decode_fail(c.code[k], "disc " + std::to_string(k) + ": " + d->item_err[k]);
+    return LACX_OK;
+}
+}  // namespace
+
+int lacx_decoder_accuraterip_batch_device(lacx_decoder* d, const lacx_span* lacs, uint32_t nlacs, const uint64_t* track_frames, uint32_t ntracks,
+                                          const lacx_ar_disc* discs, uint32_t ndiscs, void* stream, int* disc_rc, lacx_ar_result* out, float* device_ms) {
+    if (!d) return decode_fail(LACX_E_INVALID, "null decoder");
+    if (!lacs || nlacs == 0 || !discs || ndiscs == 0) return decode_fail(LACX_E_INVALID, "null argument or empty batch");
+    ar_reset(d, ndiscs, out, device_ms);
+    std::vector<uint64_t> frames(nlacs, 0);
+    std::vector<int> src_code(nlacs, LACX_OK);
+    std::vector<std::string> src_why(nlacs);
+    for (uint32_t i = 0; i < nlacs; ++i) {
+        lacx_stream_info f{};
+        const char* why = nullptr;
+        src_code[i] = parse_stream(lacs[i].data, lacs[i].size, &f, &why);
+        if (src_code[i] != LACX_OK) {
+            src_why[i] = why ? why : "";
+        } else if (f.channels != 2 || f.bit_depth != 16 || f.sample_rate != 44100) {
+            src_code[i] = LACX_E_INVALID;
+            src_why[i] = "not CD audio (" + std::to_string((int)f.channels) + " channels, " + std::to_string((int)f.bit_depth) + " bit, " + std::to_string(f.sample_rate) + " Hz)";
+        }
+        frames[i] = f.frames;
+    }
+    ArCall c;
+    ar_resolve(discs, ndiscs, nlacs, track_frames, ntracks, frames, src_code, src_why, c);
+    std::vector<BatchIn> in;  // the accepted discs' sources, disc after disc
+    std::vector<ArDiscIn> adiscs;
+    std::vector<uint32_t> which;  // ... their indices in the call
+    for (uint32_t k = 0; k < ndiscs; ++k) {
+        if (c.code[k] != LACX_OK) continue;
+        adiscs.push_back(ArDiscIn{(uint32_t)in.size(), discs[k].sources, c.tracks[k].data(), (uint32_t)c.tracks[k].size(), discs[k].flags, discs[k].radius, false});
+        which.push_back(k);
+        for (uint32_t i = 0; i < discs[k].sources; ++i) {
+            const lacx_span& x = lacs[discs[k].first_source + i];
+            in.push_back(BatchIn{x.data, x.size, nullptr, nullptr, 0});
+        }
+    }
+    int rc = LACX_OK;
+    if (!adiscs.empty()) {
+        const ArJobIn arjob{adiscs.data(), (uint32_t)adiscs.size()};
+        std::vector<uint32_t> planned;
+        DecodeJob job{in.data(), (uint32_t)in.size(), DecodeForm::digest, kWholeStreams, static_cast<hipStream_t>(stream), nullptr, nullptr, device_ms};
+        job.ar = &arjob;
+        job.ar_planned = &planned;
+        std::vector<int> code;
+        std::vector<std::string> err;
+        rc = decode_batch_run(d, job, code, err);
+        for (size_t a = 0; a < adiscs.size(); ++a) {
+            const uint32_t k = which[a];
+            for (uint32_t i = 0; i < adiscs[a].nsrc && c.code[k] == LACX_OK; ++i)
+                if (code[adiscs[a].src0 + i] != LACX_OK) c.code[k] = code[adiscs[a].src0 + i], c.err[k] = rc != LACX_OK ? err[adiscs[a].src0 + i] : "source " + std::to_string(i) + ": " + err[adiscs[a].src0 + i];
+            if (c.code[k] != LACX_OK) continue;
+            const auto slot = std::find(planned.begin(), planned.end(), (uint32_t)a);
+            if (slot == planned.end()) c.code[k] = LACX_E_RUNTIME, c.err[k] = "disc was not planned";
+            else ar_accept(d, k, (size_t)(slot - planned.begin()), discs[k], c.tracks[k], out);
+        }
+        if (rc != LACX_OK) ar_reset(d, ndiscs, out, nullptr);
+    } else if (lacx_device_count() <= 0) {
+        rc = decode_fail(LACX_E_DEVICE, "no usable HIP device");
+    }
+    return ar_outcome(d, rc, c, disc_rc);
+}
+
+int lacx_decoder_accuraterip_pcm_batch_device(lacx_decoder* d, const lacx_digest_source* src, uint32_t nsrc, const uint64_t* track_frames, uint32_t ntracks,
+                                              const lacx_ar_disc* discs, uint32_t ndiscs, void* stream, int* disc_rc, lacx_ar_result* out, float* device_ms) {
+    if (!d) return decode_fail(LACX_E_INVALID, "null decoder");
+    if (!src || nsrc == 0 || !discs || ndiscs == 0) return decode_fail(LACX_E_INVALID, "null argument or empty batch");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    ar_reset(d, ndiscs, out, device_ms);
+    std::vector<uint64_t> frames(nsrc, 0);
+    std::vector<int> src_code(nsrc, LACX_OK);
+    std::vector<std::string> src_why(nsrc);
+    for (uint32_t i = 0; i < nsrc; ++i) {
+        std::string text;
+        if (const char* why = check_digest_source(src[i], text)) {
+            src_code[i] = LACX_E_INVALID, src_why[i] = why;
+        } else if (src[i].pcm.channels != 2 || src[i].bit_depth != 16 || src[i].sample_rate != 44100) {
+            src_code[i] = LACX_E_INVALID;
+            src_why[i] = "not CD audio (" + std::to_string(src[i].pcm.channels) + " channels, " + std::to_string((int)src[i].bit_depth) + " bit, " + std::to_string(src[i].sample_rate) + " Hz)";
+        }
+        frames[i] = src[i].frames;
+    }
+    ArCall c;
+    ar_resolve(discs, ndiscs, nsrc, track_frames, ntracks, frames, src_code, src_why, c);
+    std::vector<ArSrcIn> in;
+    std::vector<ArDiscIn> adiscs;
+    std::vector<uint32_t> which;
+    for (uint32_t k = 0; k < ndiscs; ++k) {
+        if (c.code[k] != LACX_OK) continue;
+        adiscs.push_back(ArDiscIn{(uint32_t)in.size(), discs[k].sources, c.tracks[k].data(), (uint32_t)c.tracks[k].size(), discs[k].flags, discs[k].radius, true});
+        which.push_back(k);
+        for (uint32_t i = 0; i < discs[k].sources; ++i) {
+            const lacx_digest_source& x = src[discs[k].first_source + i];
+            in.push_back(ArSrcIn{x.pcm.data0, x.pcm.data1, x.frames, x.pcm.layout, (uint32_t)in.size()});
+        }
+    }
+    int rc = lacx_device_count() <= 0 ? decode_fail(LACX_E_DEVICE, "no usable HIP device") : LACX_OK;
+    if (rc == LACX_OK && !adiscs.empty()) {
+        const size_t ns = in.size();
+        if (const char* why = ar_check(in.data(), adiscs.data(), adiscs.size())) rc = decode_fail(LACX_E_DEVICE, why);
+        if (rc == LACX_OK) {  // the tables: bad [ns] | the tables of accuraterip_plan.h (16-byte aligned)
+            const ArLayout y = ar_layout(plan_detail::up16(8 * ns), in.data(), adiscs.data(), adiscs.size());
+            int prev_device = -1;
+            DevErr e = decoder_open(d, &prev_device);
+            if (!e) e = buf_grow(d->tables, y.size, y.size / 8 + 256);
+            if (!e) {
+                for (size_t j = 0; j < ns; ++j) reinterpret_cast<unsigned long long*>(d->h_meta())[j] = kDigestClean;
+                ar_fill(y, in.data(), adiscs.data(), adiscs.size(), d->h_meta());
+                e = chk(hipMemcpyAsync(d->d_meta(), d->h_meta(), y.size, hipMemcpyHostToDevice, st), "H2D rip checksum tables");
+            }
+            if (!e) e = chk(hipEventRecord(d->e0, st), "event record");
+            if (!e) e = chk(launch_accuraterip(ar_args(y, d->d_meta(), reinterpret_cast<unsigned long long*>(d->d_meta())), st), "rip checksum launch");
+            if (!e) e = chk(hipEventRecord(d->e1, st), "event record");
+            if (!e) e = chk(hipMemcpyAsync(d->h_meta(), d->d_meta(), 8 * ns, hipMemcpyDeviceToHost, st), "D2H validation keys");
+            if (!e && y.total_sums) e = chk(hipMemcpyAsync(d->h_meta() + y.sums, d->d_meta() + y.sums, 4 * (size_t)y.total_sums, hipMemcpyDeviceToHost, st), "D2H rip checksums");
+            if (!e) e = chk(hipStreamSynchronize(st), "synchronize");
+            if (!e && device_ms) (void)hipEventElapsedTime(device_ms, d->e0, d->e1);
+            if (prev_device >= 0) (void)hipSetDevice(prev_device);
+            if (e) {
+                rc = decode_fail(LACX_E_DEVICE, std::string(e.what) + ": " + hipGetErrorString(e.e));
+            } else {
+                d->ar_at = y;
+                const auto* sums = reinterpret_cast<const uint32_t*>(d->h_meta() + y.sums);
+                d->ar_sums.assign(sums, sums + y.total_sums);
+                const auto* bad = reinterpret_cast<const unsigned long long*>(d->h_meta());
+                for (size_t a = 0; a < adiscs.size(); ++a) {
+                    const uint32_t k = which[a];
+                    for (uint32_t i = 0; i < adiscs[a].nsrc && c.code[k] == LACX_OK; ++i) {
+                        const unsigned long long key = bad[adiscs[a].src0 + i];
+                        if (key == kDigestClean) continue;
+                        ImportBad b{{kImportClean, kImportClean}};  // the encoder's words for it (import_msg.h)
+                        b.key[key >> 63] = key & ~(1ull << 63);
+                        int ch = 0;
+                        unsigned long long index = 0;
+                        std::string text;
+                        (void)import_bad_message(b, 16, &ch, &index, text);
+                        c.code[k] = LACX_E_INVALID, c.err[k] = "source " + std::to_string(i) + ": " + text;
+                    }
+                    if (c.code[k] == LACX_OK) ar_accept(d, k, a, discs[k], c.tracks[k], out);
+                }
+            }
+        }
+    }
+    if (rc != LACX_OK) {  // the whole call failed: no disc has an answer
+        ar_reset(d, ndiscs, out, nullptr);
+        for (uint32_t k = 0; k < ndiscs; ++k)
+            if (c.code[k] == LACX_OK) c.code[k] = rc, c.err[k] = g_decode_err;
+    }
+    return ar_outcome(d, rc, c, disc_rc);
+}
+
+int lacx_decoder_item_ar_tracks(const lacx_decoder* d, uint32_t disc, const lacx_ar_track** tracks, uint32_t* count) {
+    if (tracks) *tracks = nullptr;
+    if (count) *count = 0;
+    if (!d || !tracks || !count) return decode_fail(LACX_E_INVALID, "null argument");
+    if (disc >= d->ar_ok.size() || !d->ar_ok[disc]) return decode_fail(LACX_E_INVALID, "no such disc in the last rip checksum call");
+    *tracks = d->ar_tracks[disc].data();
+    *count = (uint32_t)d->ar_tracks[disc].size();
+    return LACX_OK;
+}
+
+int lacx_decoder_item_ar_sums(const lacx_decoder* d, uint32_t disc, uint32_t track, const uint32_t** v1, const uint32_t** v2, const uint32_t** s450,
+                              uint32_t* count) {
+    if (v1) *v1 = nullptr;
+    if (v2) *v2 = nullptr;
+    if (s450) *s450 = nullptr;
+    if (count) *count = 0;
+    if (!d || !v1 || !v2 || !s450 || !count) return decode_fail(LACX_E_INVALID, "null argument");
+    if (disc >= d->ar_ok.size() || !d->ar_ok[disc]) return decode_fail(LACX_E_INVALID, "no such disc in the last rip checksum call");
+    const ArDiscAt& at = d->ar_at.discs[d->ar_slot[disc]];
+    if (track >= at.ntracks) return decode_fail(LACX_E_INVALID, "no such track on the disc");
+    const uint32_t width = 2u * at.radius + 1u;
+    const uint32_t* row = d->ar_sums.data() + at.sum0 + 3ull * width * track;
+    *v1 = row, *v2 = row + width, *s450 = row + 2u * width, *count = width;
+    return LACX_OK;
+}
+
+int lacx_ar_ids(const uint64_t* track_frames, uint32_t ntracks, uint32_t flags, uint32_t lba0, lacx_ar_id* out) {
+    if (out) *out = lacx_ar_id{0, 0, 0};
+    if (!out || !track_frames) return decode_fail(LACX_E_INVALID, "null argument");
+    if (ntracks == 0) return decode_fail(LACX_E_INVALID, "disc has no tracks");
+    if (ntracks > 99) return decode_fail(LACX_E_INVALID, "more than 99 tracks");
+    for (uint32_t t = 0; t < ntracks; ++t)
+        if (track_frames[t] == 0) return decode_fail(LACX_E_INVALID, "track " + std::to_string(t) + " is empty");
+    if (flags & ~(uint32_t)(LACX_AR_FIRST | LACX_AR_LAST)) return decode_fail(LACX_E_INVALID, "unknown flags");
+    (void)ar_ids(track_frames, ntracks, flags, lba0, *out);
     return LACX_OK;
 }
 

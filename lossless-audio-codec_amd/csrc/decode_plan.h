@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "accuraterip_plan.h"
 #include "container.h"
 #include "lacx.h"
 #include "lacx_types.h"
@@ -81,9 +82,20 @@ struct BatchIn {
 // (truepeak_core.h) in that slot -- behind res [m] the tables of truepeak_plan.h (DecodePlan::peak_at), zeroed rows included.
 // ... and of a spectrum job (DecodePlan::spectrum, lacx_decoder_spectrum_batch_device): likewise with k_spectrum
 // (spectrum_core.h) -- behind res [m] the tables of spectrum_plan.h (DecodePlan::spec_at), window, twiddles and zeroed rows.
+// ... and of a rip-checksum job (DecodePlan::accuraterip, lacx_decoder_accuraterip_batch_device): likewise with k_accuraterip
+// (accuraterip_core.h) -- behind res [m] the tables of accuraterip_plan.h (DecodePlan::ar_at).  Its discs are runs of
+// consecutive items (ArJobIn); a disc's items lie side by side in the decoder's PCM buffers, but the kernel reads them
+// through the disc's source table, so nothing depends on that.
 enum class DecodeForm { wav, device, host, verify, digest, blocks };
 constexpr int kWholeStreams = -1;
 constexpr size_t kStatsRowBytes = 96;  // sizeof(StatsAcc), stats_core.h (k_stats.hip asserts it)
+
+// The discs of a rip-checksum job: ArDiscIn::src0 / nsrc name items of the job's BatchIn array; every disc has passed
+// ar_disc_why with its items' parsed frame counts (the caller parses them first: the track lengths may default to them).
+struct ArJobIn {
+    const ArDiscIn* discs;
+    uint32_t ndiscs;
+};
 
 // One item that goes to the device (j counts these; the items that failed their checks are not among them).
 struct PlanItem {
@@ -118,6 +130,7 @@ struct TableLayout {
     size_t loud = 0;                         // loudness job only: LoudLayout::base
     size_t peak = 0;                         // true-peak job only: TpLayout::base
     size_t spec = 0;                         // spectrum job only: SpLayout::base
+    size_t ar = 0;                           // rip-checksum job only: ArLayout::base
 };
 
 struct DecodePlan {
@@ -136,6 +149,13 @@ struct DecodePlan {
     TpLayout peak_at{};    // ... inside the tables
     uint32_t spectrum = 0; // strict job in the digest form with k_spectrum in k_digest's place: the window length, 0: none
     SpLayout spec_at{};    // ... inside the tables
+    bool accuraterip = false;  // strict job in the digest form with k_accuraterip in k_digest's place
+    ArLayout ar_at{};          // ... inside the tables
+    // ... its discs that go to the device (every item of theirs does): src0 / nsrc name ar_src, whose entries name the
+    // planned items j (ArSrcIn::item; addresses null until plan_fill_tables); ar_disc[k]: the disc's index in the job
+    std::vector<ArDiscIn> ar_discs;
+    std::vector<ArSrcIn> ar_src;
+    std::vector<uint32_t> ar_disc;
     bool window() const { return sample_type != kWholeStreams; }
     bool own_pcm() const { return form != DecodeForm::device || window(); }  // into the decoder's PCM buffers
     bool post_units() const { return window() || form == DecodeForm::verify || form == DecodeForm::wav || form == DecodeForm::digest || blocks || stats || runs; }
@@ -228,7 +248,7 @@ inline int check_manifest(const BatchIn& x, const lacx_stream_info& f, std::vect
 inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, int sample_type, bool pad_waves, DecodePlan& plan,
                                std::vector<int>& code, std::vector<std::string>& err, bool salvage = false, bool blocks = false,
                                bool stats = false, bool runs = false, uint64_t runs_list_cap = kRunsListCap, bool loudness = false, bool truepeak = false,
-                               uint32_t spectrum = 0) {
+                               uint32_t spectrum = 0, const ArJobIn* ar = nullptr) {
     using namespace plan_detail;
     plan = DecodePlan{};
     plan.form = form;
@@ -240,6 +260,7 @@ inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, i
     plan.loudness = loudness;
     plan.truepeak = truepeak;
     plan.spectrum = spectrum;
+    plan.accuraterip = ar != nullptr;
     const bool window = plan.window(), own_pcm = plan.own_pcm(), wav = form == DecodeForm::wav, verify = form == DecodeForm::verify,
                digest = form == DecodeForm::digest, quiet = form == DecodeForm::blocks;
     code.assign(n, LACX_OK);
@@ -251,6 +272,7 @@ inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, i
     if (loudness && (!digest || salvage)) return "loudness is a strict job in the digest form";
     if (truepeak && (!digest || salvage || loudness)) return "true peak is a strict job in the digest form";
     if (spectrum && (!digest || salvage || loudness || truepeak || !sp_logn(spectrum))) return "spectrum is a strict job in the digest form with a supported window";
+    if (ar && (!digest || salvage || loudness || truepeak || spectrum)) return "rip checksums are a strict job in the digest form";
     plan.items.reserve(n);
     uint32_t v3_blocks = 0;
     for (uint32_t i = 0; i < n; ++i) {
@@ -398,7 +420,31 @@ inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, i
         at.spec = up16(at.res + sizeof(DigestWords) * m);
         plan.spec_at = sp_layout(at.spec, xin.data(), m, sp_logn(spectrum));
     }
-    at.size = spectrum ? plan.spec_at.size : truepeak ? plan.peak_at.size : loudness ? plan.loud_at.size : runs ? plan.runs_at.size : stats ? at.stats + kStatsRowBytes * T : blocks ? at.expect + (plan.judged ? 4 * T : 0) : salvage ? at.win + 4 * m : verify ? at.res + sizeof(VerifyWords) * m : digest ? at.res + sizeof(DigestWords) * m : window ? at.win + sizeof(WindowOut) * m : end;
+    if (ar) {  // likewise; a disc one of whose items was refused above (or is no 16-bit stereo) does not go to the device
+        std::vector<uint32_t> where(n, ~0u);
+        for (uint32_t j = 0; j < m; ++j) where[plan.items[j].src] = j;
+        for (uint32_t k = 0; k < ar->ndiscs; ++k) {
+            ArDiscIn d = ar->discs[k];
+            bool whole = d.nsrc != 0 && d.src0 <= n && d.nsrc <= n - d.src0;
+            for (uint32_t i = 0; whole && i < d.nsrc; ++i) {
+                const uint32_t j = where[d.src0 + i];
+                whole = j != ~0u && plan.items[j].info.channels == 2 && plan.items[j].info.bit_depth == 16 && plan.items[j].item.frames != 0;
+            }
+            if (!whole) continue;
+            const uint32_t first = (uint32_t)plan.ar_src.size();
+            for (uint32_t i = 0; i < d.nsrc; ++i) {
+                const uint32_t j = where[d.src0 + i];
+                plan.ar_src.push_back(ArSrcIn{nullptr, nullptr, plan.items[j].item.frames, (uint32_t)LACX_PCM_PLANAR_I32, j});
+            }
+            d.src0 = first, d.validate = false;
+            plan.ar_discs.push_back(d);
+            plan.ar_disc.push_back(k);
+        }
+        if (const char* why = ar_check(plan.ar_src.data(), plan.ar_discs.data(), plan.ar_discs.size())) return why;
+        at.ar = up16(at.res + sizeof(DigestWords) * m);
+        plan.ar_at = ar_layout(at.ar, plan.ar_src.data(), plan.ar_discs.data(), plan.ar_discs.size());
+    }
+    at.size = ar ? plan.ar_at.size : spectrum ? plan.spec_at.size : truepeak ? plan.peak_at.size : loudness ? plan.loud_at.size : runs ? plan.runs_at.size : stats ? at.stats + kStatsRowBytes * T : blocks ? at.expect + (plan.judged ? 4 * T : 0) : salvage ? at.win + 4 * m : verify ? at.res + sizeof(VerifyWords) * m : digest ? at.res + sizeof(DigestWords) * m : window ? at.win + sizeof(WindowOut) * m : end;
     plan.need.payload = (plan.host_src ? plan.src_at + plan.host_src_bytes : plan.total_pay) + kDecodeTailPad;
     plan.need.blocks = T;
     plan.need.pcm_frames = own_pcm ? plan.pcm_total : 0;
@@ -525,6 +571,11 @@ inline void plan_fill_tables(const DecodePlan& plan, const BatchIn* in, const Pl
                                p.info.channels, p.info.bit_depth, false});
         sp_fill(plan.spec_at, xin.data(), m, h);
     }
+    if (plan.accuraterip) {  // the discs' sources: their items' places in the decoder's own PCM buffers
+        std::vector<ArSrcIn> src = plan.ar_src;
+        for (ArSrcIn& x : src) x.data0 = base.left + plan.items[x.item].pcm_at, x.data1 = base.right + plan.items[x.item].pcm_at;
+        ar_fill(plan.ar_at, src.data(), plan.ar_discs.data(), plan.ar_discs.size(), h);
+    }
     if (!plan.lane_blk.empty()) std::memcpy(h + at.lane_blk, plan.lane_blk.data(), 4 * plan.lane_blk.size());
     if (!plan.v2_items.empty()) std::memcpy(h + at.v2_items, plan.v2_items.data(), 4 * plan.v2_items.size());
 }
@@ -563,8 +614,8 @@ inline DecodeArgs plan_args(const DecodePlan& plan, const uint8_t* tables, const
         a.no_output = plan.form == DecodeForm::blocks;
     }
     // (a loudness job has no digest: launch_decode then ends with k_ms_inverse in place, and the loudness kernels follow it;
-    // a true-peak and a spectrum job likewise)
-    if (plan.form == DecodeForm::digest && !plan.loudness && !plan.truepeak && !plan.spectrum) a.digest = reinterpret_cast<DigestWords*>(const_cast<uint8_t*>(tables) + at.res);
+    // a true-peak, a spectrum and a rip-checksum job likewise)
+    if (plan.form == DecodeForm::digest && !plan.loudness && !plan.truepeak && !plan.spectrum && !plan.accuraterip) a.digest = reinterpret_cast<DigestWords*>(const_cast<uint8_t*>(tables) + at.res);
     if (plan.stats || plan.runs) a.no_output = true;  // launch_decode ends with k_ms_inverse; k_stats_blocks follows it (plan_stats_args)
     return a;
 }
@@ -595,5 +646,8 @@ inline TpArgs plan_peak_args(const DecodePlan& plan, uint8_t* tables) { return t
 
 // A spectrum job's arguments for k_spectrum: the tables of spectrum_plan.h inside the tables.
 inline SpArgs plan_spec_args(const DecodePlan& plan, uint8_t* tables) { return sp_args(plan.spec_at, plan.items.size(), tables, nullptr); }
+
+// A rip-checksum job's arguments for k_accuraterip: the tables of accuraterip_plan.h inside the tables.
+inline ArArgs plan_ar_args(const DecodePlan& plan, uint8_t* tables) { return ar_args(plan.ar_at, tables, nullptr); }
 
 }  // namespace lacx

@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 
+#include "accuraterip_plan.h"
 #include "device_buf.h"
 #include "lacx.h"
 
@@ -52,6 +53,13 @@ struct lacx_decoder {
     std::vector<std::vector<lacx_loudness_row>> item_loud;       // ... per item
     std::vector<std::vector<lacx_truepeak_row>> item_peak;       // the last true-peak call's rows per item
     std::vector<std::vector<lacx_spectrum_row>> item_spec;       // the last spectrum call's rows per item
+    // the last rip-checksum call: the plan's discs and tracks, the sums as the device left them, per disc whether it has any,
+    // and its tracks as the ABI gives them
+    lacx::ArLayout ar_at;
+    std::vector<uint32_t> ar_sums;
+    std::vector<uint8_t> ar_ok;
+    std::vector<uint32_t> ar_slot;  // ... and its place among ar_at's discs
+    std::vector<std::vector<lacx_ar_track>> ar_tracks;
     std::vector<std::vector<lacx_block_info>> item_info;     // the last inspection call's rows per item
     // ... and, where it asked for partition detail, the entries of all its blocks: [T][2][256] each, item i's blocks
     // from info_block0[i] on (~0u: the item has none)

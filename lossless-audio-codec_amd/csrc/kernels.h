@@ -1,5 +1,5 @@
 // kernels.h -- host-visible interface of the kernel translation units (k_front.hip, k_analyze.hip, k_emit.hip,
-// decode.hip, k_digest.hip, k_blockdigest.hip, k_stats.hip, k_runs.hip, k_loudness.hip, k_truepeak.hip, k_spectrum.hip, k_inspect.hip, k_recovery.hip, wide.hip, k_import.hip, k_edit.hip).
+// decode.hip, k_digest.hip, k_blockdigest.hip, k_stats.hip, k_runs.hip, k_loudness.hip, k_truepeak.hip, k_spectrum.hip, k_accuraterip.hip, k_inspect.hip, k_recovery.hip, wide.hip, k_import.hip, k_edit.hip).
 #pragma once
 #include <cstdlib>
 #include <hip/hip_runtime_api.h>
@@ -217,6 +217,10 @@ hipError_t launch_truepeak(const TpArgs& args, hipStream_t stream);
 // Spectrum (k_spectrum.hip, spectrum_core.h): k_spectrum<log2 N> over the rows of a spectrum job, in the slot and the two
 // forms launch_truepeak has (spectrum_plan.h).  The rows must be zero on entry.
 hipError_t launch_spectrum(const SpArgs& args, hipStream_t stream);
+
+// Rip checksums (k_accuraterip.hip, accuraterip_core.h): k_accuraterip over the tiles of a rip-checksum job, in the slot and
+// the two forms launch_truepeak has (accuraterip_plan.h).  The sums must be zero on entry.
+hipError_t launch_accuraterip(const ArArgs& args, hipStream_t stream);
 
 // Recovery data (k_recovery.hip, recovery_core.h): k_gf_combine over the task table, one launch per accumulator tier that
 // has tasks, then k_slice_crc over the listed byte ranges.

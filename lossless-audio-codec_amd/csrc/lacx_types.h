@@ -351,4 +351,44 @@ struct SpArgs {
     lacx_spectrum_row* rows = nullptr;             // [total_rows], zero on entry
     unsigned long long* bad = nullptr;             // [nitems] lowest digest_bad_key per item (all ones on entry), or null
 };
+// Rip checksums (k_accuraterip of k_accuraterip.hip, accuraterip_core.h): the tables accuraterip_plan.h lays out.  One form
+// for both jobs: a disc is a run of sources, each PCM in a layout (a stream's is the decoder's planar int32 staging,
+// validate 0; a source's its own, validate 1), and a list of spans over the disc's frames.
+constexpr uint32_t kArThreads = 256;
+constexpr uint32_t kArTileMults = 4096;            // multipliers per workgroup
+constexpr uint32_t kArMaxRadius = 2939;            // 5 sectors of 588 frames less one frame
+constexpr uint32_t kArSector = 588;
+constexpr uint32_t kArStageWords = kArTileMults + kArThreads + 4u;  // a tile's words: M + offsets - 1, and up to 3 in front (units of four)
+struct ArSource {                                  // 40 bytes
+    const void* data0;                             // as DigestSource; always two channels of 16 bits
+    const void* data1;
+    unsigned long long start, frames;              // the source's first disc frame, its frames (> 0)
+    uint32_t layout;
+    uint32_t item;                                 // whose bad[] an invalid sample lowers
+};
+struct ArSpan {                                    // 48 bytes: sum over m = m_lo .. m_hi of m * x(frame1 + o + m - 1), every o in [-radius, radius]
+    unsigned long long frame1;                     // the disc frame multiplier 1 reads at offset 0
+    unsigned long long disc_frames;                // x is zero outside [0, disc_frames)
+    uint32_t src0, nsrc;                           // the disc's sources, ascending by start, back to back from frame 0
+    uint32_t m_lo, m_hi;                           // m_lo <= m_hi
+    uint32_t sum0;                                 // sums[sum0 + radius + o]: the low halves; with keep_hi, sums[sum0 + 2 radius + 1 + radius + o]: low + high
+    uint32_t radius;
+    uint32_t lanes;                                // offsets per tile: a power of two <= kArThreads; kArThreads / lanes stripes share the multipliers
+    uint8_t keep_hi, validate, pad[2];
+};
+// (constexpr: the host-only plan counts a span's tiles as the kernel does)
+constexpr uint32_t ar_width(const ArSpan& s) { return 2u * s.radius + 1u; }
+constexpr uint32_t ar_offset_tiles(const ArSpan& s) { return (ar_width(s) + s.lanes - 1u) / s.lanes; }
+constexpr unsigned long long ar_span_tiles(const ArSpan& s) {
+    return (unsigned long long)((s.m_hi - s.m_lo) / kArTileMults + 1u) * ar_offset_tiles(s);
+}
+struct ArArgs {
+    uint32_t nspans = 0;
+    unsigned long long total_tiles = 0;
+    const ArSpan* spans = nullptr;                 // [nspans]
+    const unsigned long long* tile_off = nullptr;  // [nspans + 1] prefix sums of the spans' tiles (multiplier tile major, offset tile minor)
+    const ArSource* sources = nullptr;
+    uint32_t* sums = nullptr;                      // zero on entry
+    unsigned long long* bad = nullptr;             // [items] lowest digest_bad_key per item (all ones on entry), or null
+};
 }  // namespace lacx

@@ -124,6 +124,8 @@ EXPORTS = (
     "lacx_decoder_loudness_batch_device", "lacx_decoder_loudness_pcm_batch_device", "lacx_decoder_item_loudness_rows", "lacx_loudness_combine",
     "lacx_decoder_truepeak_batch_device", "lacx_decoder_truepeak_pcm_batch_device", "lacx_decoder_item_truepeak_rows", "lacx_truepeak_combine",
     "lacx_decoder_spectrum_batch_device", "lacx_decoder_spectrum_pcm_batch_device", "lacx_decoder_item_spectrum_rows", "lacx_spectrum_combine",
+    "lacx_decoder_accuraterip_batch_device", "lacx_decoder_accuraterip_pcm_batch_device", "lacx_decoder_item_ar_tracks", "lacx_decoder_item_ar_sums",
+    "lacx_ar_ids",
     "lacx_decoder_inspect_batch_device", "lacx_decoder_item_block_info", "lacx_decoder_item_partitions", "lacx_inspect_combine",
     "lacx_decoder_inspect_guard", "lacx_transcode_batch",
     "lacx_decoder_runs_batch_device", "lacx_decoder_runs_pcm_batch_device", "lacx_decoder_item_runs",
@@ -260,6 +262,14 @@ def lib():
         L.lacx_decoder_item_spectrum_rows.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.POINTER(SpectrumRow)), C.POINTER(C.c_uint32)]
         L.lacx_spectrum_combine.argtypes = [C.POINTER(SpectrumRow), C.c_uint32, C.c_uint8, C.c_uint8, C.c_uint64, C.c_uint32, C.c_uint32, C.c_double,
                                             C.POINTER(Spectrum)]
+        u32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+        L.lacx_decoder_accuraterip_batch_device.argtypes = [C.c_void_p, C.POINTER(Span), C.c_uint32, u64p, C.c_uint32, C.POINTER(ArDisc), C.c_uint32,
+                                                            C.c_void_p, C.POINTER(C.c_int), C.POINTER(ArResult), C.POINTER(C.c_float)]
+        L.lacx_decoder_accuraterip_pcm_batch_device.argtypes = [C.c_void_p, C.POINTER(DigestSource), C.c_uint32, u64p, C.c_uint32, C.POINTER(ArDisc),
+                                                                C.c_uint32, C.c_void_p, C.POINTER(C.c_int), C.POINTER(ArResult), C.POINTER(C.c_float)]
+        L.lacx_decoder_item_ar_tracks.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.POINTER(ArTrack)), u32p]
+        L.lacx_decoder_item_ar_sums.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(u32p), C.POINTER(u32p), C.POINTER(u32p), u32p]
+        L.lacx_ar_ids.argtypes = [u64p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(ArId)]
         L.lacx_decoder_inspect_batch_device.argtypes = [C.c_void_p, C.POINTER(Span), C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_int),
                                                         C.POINTER(StreamReport), C.POINTER(C.c_float)]
         L.lacx_decoder_item_block_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.POINTER(BlockInfo)), C.POINTER(C.c_uint32)]
@@ -304,7 +314,7 @@ def abi_structs() -> dict:
             "repair_result": RepairResult, "channel_stats": ChannelStats, "block_stats": BlockStats,
             "channel_totals": ChannelTotals, "stats": Stats, "loudness_row": LoudnessRow, "loudness": Loudness,
             "truepeak_row": TruePeakRow, "truepeak_channel": TruePeakChannel, "truepeak": TruePeak,
-            "spectrum_row": SpectrumRow, "spectrum": Spectrum, "channel_info": ChannelInfo, "block_info": BlockInfo,
+            "ar_disc": ArDisc, "ar_id": ArId, "ar_result": ArResult, "ar_track": ArTrack, "spectrum_row": SpectrumRow, "spectrum": Spectrum, "channel_info": ChannelInfo, "block_info": BlockInfo,
             "stream_report": StreamReport, "edit_segment": EditSegment, "edit_output": EditOutput,
             "edit_result": EditResult, "run_detector": RunDetector, "run_query": RunQuery, "run": Run,
             "run_totals": RunTotals, "runs_result": RunsResult}
@@ -1123,6 +1133,65 @@ def spectrum_combine(rows, channels, bit_depth, frames, sample_rate, window=2048
     if lib().lacx_spectrum_combine(C.cast(blob.ctypes.data, C.POINTER(SpectrumRow)), C.c_uint32(len(blob) // C.sizeof(SpectrumRow)), C.c_uint8(channels),
                                    C.c_uint8(bit_depth), C.c_uint64(frames), C.c_uint32(sample_rate), C.c_uint32(window), C.c_double(floor_db),
                                    C.byref(out)) != OK:
+        raise ValueError(lib().lacx_decode_last_error().decode(errors="replace"))
+    return out
+
+
+# ---- rip checksums: AccurateRip v1 / v2 at every read offset (lacx.h) ----
+AR_FIRST, AR_LAST, AR_NO_IDS = 1, 2, 4  # LACX_AR_*
+AR_TRACK_SHORT, AR_TRACK_NO_S450 = 1, 2
+AR_MAX_RADIUS = 2939
+
+
+class ArDisc(C.Structure):
+    _fields_ = [("first_source", C.c_uint32), ("sources", C.c_uint32), ("first_track", C.c_uint32), ("tracks", C.c_uint32),
+                ("flags", C.c_uint32), ("radius", C.c_uint32), ("lba0", C.c_uint32)]
+
+
+class ArId(C.Structure):
+    """The ids a rip database files a disc under (lacx_ar_id); all zero where the disc has none."""
+    _fields_ = [("id1", C.c_uint32), ("id2", C.c_uint32), ("cddb", C.c_uint32)]
+
+
+class ArResult(C.Structure):
+    _fields_ = [("frames", C.c_uint64), ("tracks", C.c_uint32), ("radius", C.c_uint32), ("flags", C.c_uint32), ("ids", ArId)]
+
+
+class ArTrack(C.Structure):
+    """One track: its first disc frame, frames, LACX_AR_TRACK_* flags and the three sums at offset 0 (lacx_ar_track)."""
+    _fields_ = [("start", C.c_uint64), ("frames", C.c_uint64), ("flags", C.c_uint32), ("v1", C.c_uint32), ("v2", C.c_uint32), ("s450", C.c_uint32)]
+
+
+class AccurateRip:
+    """The rip checksums of one disc: `v1`, `v2`, `s450` as (tracks, 2 radius + 1) uint32 arrays ordered by `offsets` (-radius
+    .. radius), `tracks` ([ArTrack]), `ids` (ArId), `frames`, `radius`, `flags`."""
+
+    def __init__(self, result, tracks, v1, v2, s450):
+        self.frames, self.radius, self.flags, self.ids = int(result.frames), int(result.radius), int(result.flags), _copy_struct(result.ids)
+        self.tracks, self.v1, self.v2, self.s450 = tracks, v1, v2, s450
+        self.offsets = np.arange(-self.radius, self.radius + 1)
+
+    def find(self, value: int) -> list:
+        """[(track, offset, 'v1' | 'v2' | 's450')] of every sum equal to `value` (a checksum from a rip database).  An s450
+        of a track too short to have one is never a match.  Host only."""
+        out = []
+        for kind, a in (("v1", self.v1), ("v2", self.v2), ("s450", self.s450)):
+            for t, k in zip(*np.nonzero(a == np.uint32(value))):
+                if kind == "s450" and self.tracks[t].flags & AR_TRACK_NO_S450:
+                    continue
+                if kind != "s450" and self.tracks[t].flags & AR_TRACK_SHORT:
+                    continue
+                out.append((int(t), int(self.offsets[k]), kind))
+        return sorted(out)
+
+
+def ar_ids(track_frames, first=True, last=True, lba0=0) -> ArId:
+    """Host only: the disc ids of track lengths in frames (lacx.h); all zero unless the disc is whole (first and last) and
+    every track a whole number of 588-frame sectors."""
+    n = len(track_frames)
+    tf = (C.c_uint64 * max(1, n))(*track_frames)
+    out = ArId()
+    if lib().lacx_ar_ids(tf, C.c_uint32(n), C.c_uint32((AR_FIRST if first else 0) | (AR_LAST if last else 0)), C.c_uint32(lba0), C.byref(out)) != OK:
         raise ValueError(lib().lacx_decode_last_error().decode(errors="replace"))
     return out
 
@@ -2137,6 +2206,100 @@ class Decoder:
             raise RuntimeError(lib().lacx_decode_last_error().decode(errors="replace"))
         errors = {i: lib().lacx_decoder_item_error(self._h, i).decode(errors="replace") for i in range(n) if rcs[i] != OK}
         return self._raise_batch(rc, errors, [None if i in errors else (_copy_struct(out[i]), self._spec_rows(i)) for i in range(n)])
+
+    # ---- rip checksums: AccurateRip v1 / v2 at every read offset ----
+    @staticmethod
+    def _ar_discs(discs):
+        """[(sources, tracks or None, radius, first, last, lba0)] -> the flat source list, track_frames, ArDisc array."""
+        flat, tf = [], []
+        recs = (ArDisc * max(1, len(discs)))()
+        for rec, d in zip(recs, discs):
+            sources, tracks, radius, first, last, lba0 = (tuple(d) + (None, 0, True, True, 0)[len(d) - 1:])[:6]
+            rec.first_source, rec.sources = len(flat), len(sources)
+            rec.first_track, rec.tracks = len(tf), len(tracks) if tracks is not None else 0
+            rec.flags, rec.radius, rec.lba0 = (AR_FIRST if first else 0) | (AR_LAST if last else 0), radius, lba0
+            flat += list(sources)
+            tf += list(tracks) if tracks is not None else []
+        return flat, (C.c_uint64 * max(1, len(tf)))(*tf), len(tf), recs
+
+    def _ar_finish(self, n, rc, rcs, out):
+        if rc == E_DEVICE:
+            raise RuntimeError(lib().lacx_decode_last_error().decode(errors="replace"))
+        errors = {k: lib().lacx_decoder_item_error(self._h, k).decode(errors="replace") for k in range(n) if rcs[k] != OK}
+        results = []
+        for k in range(n):
+            if k in errors:
+                results.append(None)
+                continue
+            ptr, count = C.POINTER(ArTrack)(), C.c_uint32()
+            assert lib().lacx_decoder_item_ar_tracks(self._h, C.c_uint32(k), C.byref(ptr), C.byref(count)) == OK
+            tracks = [_copy_struct(ptr[t]) for t in range(count.value)]
+            width = 2 * out[k].radius + 1
+            sums = np.zeros((3, count.value, width), np.uint32)
+            for t in range(count.value):
+                p = [C.POINTER(C.c_uint32)() for _ in range(3)]
+                w = C.c_uint32()
+                assert lib().lacx_decoder_item_ar_sums(self._h, C.c_uint32(k), C.c_uint32(t), C.byref(p[0]), C.byref(p[1]), C.byref(p[2]), C.byref(w)) == OK
+                for q in range(3):  # one copy: the sums die with the decoder's next call
+                    sums[q, t] = np.ctypeslib.as_array(p[q], shape=(w.value,))
+            results.append(AccurateRip(out[k], tracks, sums[0], sums[1], sums[2]))
+        if rc != OK:
+            e = BatchDecodeError(lib().lacx_decode_last_error().decode(errors="replace"), errors, results)
+            e.codes = {k: int(rcs[k]) for k in errors}
+            raise e
+        return results
+
+    def accuraterip_batch(self, discs, stream: int = 0) -> list:
+        """Many discs of CD audio (2 channels, 16 bit, 44100 Hz) decoded and their AccurateRip v1 / v2 track checksums and
+        450th-sector sums taken at every read offset within a radius, as one device job, strict like digest_batch.  discs:
+        [(lacs, tracks=None, radius=0, first=True, last=True, lba0=0)] -- the streams that together are the disc, in order;
+        the track lengths in frames (None: one track per stream); the radius in frames, at most 2939.  Per disc an
+        AccurateRip, None where it is refused or one of its streams does not decode (those raise BatchDecodeError once the
+        others are done).  Kernel milliseconds in `last_ms`."""
+        if self._h is None:
+            raise RuntimeError("decoder is closed")
+        flat, tf, ntf, recs = self._ar_discs(discs)
+        bufs = [np.frombuffer(x, dtype=np.uint8) for x in flat]
+        spans = (Span * max(1, len(bufs)))(*[Span(b.ctypes.data_as(C.POINTER(C.c_uint8)), b.size) for b in bufs])
+        n = len(discs)
+        out, rcs, ms = (ArResult * max(1, n))(), (C.c_int * max(1, n))(), C.c_float()
+        rc = lib().lacx_decoder_accuraterip_batch_device(self._h, spans, C.c_uint32(len(bufs)), tf, C.c_uint32(ntf), recs, C.c_uint32(n), C.c_void_p(stream),
+                                                         rcs, out, C.byref(ms))
+        self.last_ms = float(ms.value)
+        if rc == E_INVALID and all(rcs[k] == OK for k in range(n)):  # the call's own arguments
+            raise ValueError(lib().lacx_decode_last_error().decode(errors="replace"))
+        return self._ar_finish(n, rc, rcs, out)
+
+    def accuraterip(self, lacs, tracks=None, radius: int = 0, first: bool = True, last: bool = True, lba0: int = 0) -> AccurateRip:
+        """accuraterip_batch of one disc; ValueError where the disc is refused, RuntimeError where a stream does not decode."""
+        try:
+            return self.accuraterip_batch([(lacs, tracks, radius, first, last, lba0)])[0]
+        except BatchDecodeError as e:
+            raise (ValueError if e.codes[0] == E_INVALID else RuntimeError)(e.errors[0]) from None
+
+    def accuraterip_pcm_batch(self, discs, stream: int = 0) -> list:
+        """Device-resident PCM checked where it lies: discs as accuraterip_batch takes them, with sources as
+        truepeak_pcm_batch takes them in the place of streams -- what accuraterip_batch gives for the .lac files made from
+        them."""
+        if self._h is None:
+            raise RuntimeError("decoder is closed")
+        flat, tf, ntf, recs = self._ar_discs(discs)
+        items = (DigestSource * max(1, len(flat)))()
+        for it, (pcm, rate, depth) in zip(items, flat):
+            if isinstance(pcm, (tuple, list)):
+                d0, d1, layout, channels, frames = pcm
+                it.pcm = Pcm(d0, d1, layout, channels)
+            else:
+                it.pcm, frames = pcm_of(pcm, depth)
+            it.frames, it.sample_rate, it.bit_depth = frames, rate, depth
+        n = len(discs)
+        out, rcs, ms = (ArResult * max(1, n))(), (C.c_int * max(1, n))(), C.c_float()
+        rc = lib().lacx_decoder_accuraterip_pcm_batch_device(self._h, items, C.c_uint32(len(flat)), tf, C.c_uint32(ntf), recs, C.c_uint32(n),
+                                                             C.c_void_p(stream), rcs, out, C.byref(ms))
+        self.last_ms = float(ms.value)
+        if rc == E_INVALID and all(rcs[k] == OK for k in range(n)):
+            raise ValueError(lib().lacx_decode_last_error().decode(errors="replace"))
+        return self._ar_finish(n, rc, rcs, out)
 
     # ---- runs: where a stream is silent, clips or holds one value ----
     @staticmethod

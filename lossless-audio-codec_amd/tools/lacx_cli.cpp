@@ -30,6 +30,9 @@
 // spectrum (no counterpart in the reference's tool; `spek`, `sox ... stat -freq`): the long-term power spectrum of the same
 // two kinds of file in 64 bands and the bandwidth read off it, the Hann STFT made on the device in FP64
 // (lacx_decoder_spectrum_batch_device / lacx_decoder_spectrum_pcm_batch_device).  It only measures.
+// accuraterip (what EAC, dBpoweramp, CUETools and whipper print for a rip): the AccurateRip v1 / v2 track checksums of the files
+// as one disc of CD audio, made on the device at every read offset within a radius (lacx_decoder_accuraterip_batch_device /
+// lacx_decoder_accuraterip_pcm_batch_device).  The database lookup is not part of it.
 // inspect (`flac -a` for .lac): how each stream was coded and where its bits go, read out of the bytes on the device by a
 // parse-only walk (lacx_decoder_inspect_batch_device).
 // recompress, cut, join (no counterpart in the reference's tool; `flac -f`, `--skip` / `--until` and joining, for .lac): .lac
@@ -81,6 +84,10 @@ void usage() {
                  "  lacx_cli spectrum FILE... [--window=N] [--floor=DB] [--blocks]   (.lac and .wav files: per channel the bandwidth -- the upper\n"
                  "      edge of the highest of 64 bands at or above the floor, default -100 dBFS -- and the strongest band, one line per file;\n"
                  "      --window: 256, 512, 1024, 2048 (default) or 4096 frames; --blocks: the 64 levels of every 16384 frames; exit 0 done, 2 refused)\n"
+                 "  lacx_cli accuraterip FILE... [--tracks=n0,n1,...] [--radius=N] [--not-first] [--not-last] [--lba0=N] [--match=HEX[,HEX...]]\n"
+                 "      (.lac and .wav files of CD audio, together one disc in argument order: the disc ids and per track `NN start frames v1 v2\n"
+                 "      s450` at offset 0; --tracks: the track lengths in frames, default one track per file; --radius: read offsets -N .. N,\n"
+                 "      at most 2939; --match: every (track, offset, kind) whose sum is one of the values; exit 0 done, 1 nothing matched, 2 refused)\n"
                  "  lacx_cli inspect FILE... [--blocks] [--partitions]   (.lac files: predictors, residual modes and where the bits go, as\n"
                  "      integers, one line per file; --blocks: one further line per block; --partitions: and one per partition;\n"
                  "      a damaged stream prints its line with lost_blocks counted; exit 0 when every file was inspected, else 1)\n"
@@ -1161,6 +1168,144 @@ int spectrum_command(int argc, char** argv) {
     return 0;
 }
 
+// lacx_cli accuraterip FILE... [--tracks=n0,n1,...] [--radius=N] [--not-first] [--not-last] [--lba0=N] [--match=HEX[,HEX...]]:
+// the files, .lac and WAV, are together one disc of CD audio in argument order.  All .lac: one stream job
+// (lacx_decoder_accuraterip_batch_device).  Otherwise every .lac is decoded to its WAV image first and the data chunks go to
+// the device as one source job (lacx_decoder_accuraterip_pcm_batch_device): the same sums either way.  Prints the ids, then per
+// track `NN start frames v1 v2 s450` at offset 0 (sums in hex), then with --match one line per (track, offset, kind) whose sum
+// is one of the values.  Exit 0 done, 1 with --match when nothing matched, 2 refused (the message on stderr).
+int accuraterip_command(int argc, char** argv) {
+    std::vector<const char*> paths;
+    std::vector<uint64_t> tracks;
+    std::vector<uint32_t> match;
+    bool matching = false;
+    lacx_ar_disc disc{};
+    disc.flags = LACX_AR_FIRST | LACX_AR_LAST;
+    auto numbers = [](const char* text, int base, auto& out) {
+        for (const char* p = text; *p;) {
+            char* end = nullptr;
+            const unsigned long long v = std::strtoull(p, &end, base);
+            if (end == p || (*end && *end != ',')) return false;
+            out.push_back((typename std::remove_reference_t<decltype(out)>::value_type)v);
+            p = *end ? end + 1 : end;
+        }
+        return !out.empty();
+    };
+    bool bad_option = false;
+    for (int i = 2; i < argc; ++i) {
+        const char* a = argv[i];
+        std::vector<uint64_t> one;
+        if (std::strncmp(a, "--tracks=", 9) == 0) bad_option |= !numbers(a + 9, 10, tracks);
+        else if (std::strncmp(a, "--radius=", 9) == 0) bad_option |= !numbers(a + 9, 10, one) || one.size() != 1 || (disc.radius = (uint32_t)one[0], one[0] >> 32);
+        else if (std::strncmp(a, "--lba0=", 7) == 0) bad_option |= !numbers(a + 7, 10, one) || one.size() != 1 || (disc.lba0 = (uint32_t)one[0], one[0] >> 32);
+        else if (std::strncmp(a, "--match=", 8) == 0) matching = true, bad_option |= !numbers(a + 8, 16, match);
+        else if (std::strcmp(a, "--not-first") == 0) disc.flags &= ~LACX_AR_FIRST;
+        else if (std::strcmp(a, "--not-last") == 0) disc.flags &= ~LACX_AR_LAST;
+        else if (std::strncmp(a, "--", 2) == 0) bad_option = true;
+        else paths.push_back(a);
+    }
+    const int n = (int)paths.size();
+    if (n == 0 || bad_option) {
+        usage();
+        return 2;
+    }
+    std::vector<std::vector<uint8_t>> data(n);
+    bool all_lac = true;
+    for (int i = 0; i < n; ++i) {
+        if (!load_file(paths[i], data[i])) {
+            std::cerr << "AccurateRip failed: " << paths[i] << ": Failed to read file\n";
+            return 2;
+        }
+        if (data[i].size() >= 4 && std::memcmp(data[i].data(), "RIFF", 4) == 0) all_lac = false;
+    }
+    lacx_decoder* dec = nullptr;
+    if (lacx_decoder_create(-1, &dec) != LACX_OK) {
+        std::cerr << "Error: lacx_decoder_create failed\n";
+        return 2;
+    }
+    disc.first_source = 0, disc.sources = (uint32_t)n, disc.first_track = 0, disc.tracks = (uint32_t)tracks.size();
+    lacx_ar_result res{};
+    int rc = LACX_OK, disc_rc = LACX_OK;
+    std::vector<void*> dev;
+    std::string why;
+    if (all_lac) {
+        std::vector<lacx_span> spans;
+        for (int i = 0; i < n; ++i) spans.push_back(lacx_span{data[i].data(), data[i].size()});
+        rc = lacx_decoder_accuraterip_batch_device(dec, spans.data(), (uint32_t)n, tracks.data(), (uint32_t)tracks.size(), &disc, 1, nullptr, &disc_rc, &res, nullptr);
+    } else {
+        std::vector<lacx_digest_source> src;
+        for (int i = 0; i < n && why.empty(); ++i) {
+            if (data[i].size() < 4 || std::memcmp(data[i].data(), "RIFF", 4) != 0) {  // a .lac among WAV files: its WAV image
+                uint8_t* img = nullptr;
+                uint64_t size = 0;
+                if (lacx_decoder_decode_wav(dec, data[i].data(), data[i].size(), &img, &size, nullptr) != LACX_OK) {
+                    why = std::string(paths[i]) + ": " + lacx_decode_last_error();
+                    break;
+                }
+                data[i].assign(img, img + size);
+                lacx_free(img);
+            }
+            lacx_wav_info w{};
+            if (lacx_wav_parse(data[i].data(), data[i].size(), &w) != LACX_OK) {
+                why = std::string(paths[i]) + ": Failed to read WAV";
+                break;
+            }
+            const uint64_t bytes = w.frames * w.channels * (uint64_t)(w.bit_depth / 8);
+            void* p = nullptr;
+            if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess || hipMemcpy(p, data[i].data() + w.data_offset, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+                why = std::string(paths[i]) + ": Failed to upload WAV data to the device";
+                if (p) (void)hipFree(p);
+                break;
+            }
+            dev.push_back(p);
+            lacx_digest_source x{};
+            x.pcm = lacx_pcm{p, nullptr, w.bit_depth == 16 ? LACX_PCM_INTERLEAVED_I16 : LACX_PCM_INTERLEAVED_I24, w.channels};
+            x.frames = w.frames, x.sample_rate = w.sample_rate, x.bit_depth = (uint8_t)w.bit_depth;
+            src.push_back(x);
+        }
+        if (why.empty())
+            rc = lacx_decoder_accuraterip_pcm_batch_device(dec, src.data(), (uint32_t)n, tracks.data(), (uint32_t)tracks.size(), &disc, 1, nullptr, &disc_rc, &res, nullptr);
+    }
+    if (why.empty() && rc != LACX_OK) why = disc_rc != LACX_OK && rc != LACX_E_DEVICE ? lacx_decoder_item_error(dec, 0) : lacx_decode_last_error();
+    int code = 0;
+    if (!why.empty()) {
+        std::cerr << "AccurateRip failed: " << why << "\n";
+        code = 2;
+    } else {
+        const lacx_ar_track* tr = nullptr;
+        uint32_t count = 0;
+        (void)lacx_decoder_item_ar_tracks(dec, 0, &tr, &count);
+        char line[192];
+        std::snprintf(line, sizeof(line), "id1=%08x id2=%08x cddb=%08x tracks=%u frames=%llu radius=%u", res.ids.id1, res.ids.id2, res.ids.cddb, res.tracks,
+                      (unsigned long long)res.frames, res.radius);
+        std::cout << line << (res.flags & LACX_AR_NO_IDS ? " no-ids" : "") << "\n";
+        for (uint32_t t = 0; t < count; ++t) {
+            std::snprintf(line, sizeof(line), "%02u %llu %llu %08x %08x %08x", t + 1, (unsigned long long)tr[t].start, (unsigned long long)tr[t].frames, tr[t].v1,
+                          tr[t].v2, tr[t].s450);
+            std::cout << line << (tr[t].flags & LACX_AR_TRACK_SHORT ? " short" : "") << (tr[t].flags & LACX_AR_TRACK_NO_S450 ? " no-s450" : "") << "\n";
+        }
+        size_t found = 0;
+        for (uint32_t t = 0; matching && t < count; ++t) {
+            const uint32_t* sums[3] = {nullptr, nullptr, nullptr};
+            uint32_t width = 0;
+            if (lacx_decoder_item_ar_sums(dec, 0, t, &sums[0], &sums[1], &sums[2], &width) != LACX_OK) continue;
+            const char* kind[3] = {"v1", "v2", "s450"};
+            for (uint32_t k = 0; k < width; ++k)
+                for (int q = 0; q < 3; ++q) {
+                    if ((q == 2 && (tr[t].flags & LACX_AR_TRACK_NO_S450)) || (q < 2 && (tr[t].flags & LACX_AR_TRACK_SHORT))) continue;
+                    if (std::find(match.begin(), match.end(), sums[q][k]) == match.end()) continue;
+                    std::snprintf(line, sizeof(line), "match track=%02u offset=%d kind=%s value=%08x", t + 1, (int)k - (int)res.radius, kind[q], sums[q][k]);
+                    std::cout << line << "\n";
+                    ++found;
+                }
+        }
+        if (matching && !found) code = 1;
+    }
+    for (void* p : dev) (void)hipFree(p);
+    lacx_decoder_destroy(dec);
+    return code;
+}
+
 // lacx_cli inspect FILE... [--blocks] [--partitions]: how every .lac was coded and where its bits go, read out of the bytes
 // on the device by a parse-only walk (lacx_decoder_inspect_batch_device), all files as one job.  One line of integers per
 // file in argument order; with --blocks one further line per block (its channel blocks behind it), with --partitions one
@@ -1796,6 +1941,7 @@ int main(int argc, char** argv) {
     if (mode == "loudness") return loudness_command(argc, argv);
     if (mode == "peak") return peak_command(argc, argv);
     if (mode == "spectrum") return spectrum_command(argc, argv);
+    if (mode == "accuraterip") return accuraterip_command(argc, argv);
     if (mode == "inspect" && argc >= 3) return inspect_command(argc, argv);
     if (mode == "find" && argc >= 3) return find_command(argc, argv);
     if (mode == "split" && argc >= 4) return split_command(argc, argv);
