@@ -197,9 +197,10 @@ def test_multi_device_encoder_without_a_device_fails_loudly(pkg):
 
 def test_hooks_library_is_a_separate_build(pkg):
     """The product library carries no test hook: LACX_DEBUG_SKIP only acts in liblacx_hooks.so (-DLACX_TEST_HOOKS), which
-    exports the same ABI -- and, alone, the x87 test entry points (csrc/k_x87_hooks.hip)."""
+    exports the same ABI -- and, alone, the x87 and ingest test entry points (csrc/k_x87_hooks.hip, csrc/k_front_hooks.hip)."""
     import ctypes as C
 
+    import ingestdev
     import x87dev
 
     assert os.path.exists(pkg.lacx.HOOKS_LIB_PATH), "liblacx_hooks.so missing: make -C lossless-audio-codec_amd all"
@@ -207,7 +208,7 @@ def test_hooks_library_is_a_separate_build(pkg):
     for name in pkg.lacx.EXPORTS:
         assert hasattr(hooks, name)
     product = C.CDLL(pkg.lacx.LIB_PATH)
-    for name in x87dev.HOOKS:
+    for name in x87dev.HOOKS + ingestdev.HOOKS:
         assert hasattr(hooks, name), name
         assert not hasattr(product, name), f"{name} is a test entry point: it must not be in liblacx.so"
 
