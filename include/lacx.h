@@ -74,6 +74,10 @@
  *   lacx_decoder_item_ar_tracks, lacx_decoder_item_ar_sums,
  *   lacx_ar_ids             <- whether the audio is an accurate rip, and of which pressing: the AccurateRip v1 / v2 track
  *                             checksums of a disc of CD audio at every read offset within a radius, made on the device
+ *   lacx_decoder_compare_batch_device, lacx_decoder_compare_pcm_batch_device,
+ *   lacx_decoder_item_compare_rows, lacx_decoder_item_compare_counts,
+ *   lacx_compare_combine    <- how two streams relate: the differing samples at every offset within a radius and, at the
+ *                             offset with the fewest, the null-test residual a - b in rows and totals, made on the device
  *   lacx_recovery_build, lacx_recovery_build_batch_view, lacx_recovery_parse,
  *   lacx_recovery_scan_batch, lacx_recovery_repair, lacx_recovery_repair_batch_view,
  *   lacx_decoder_item_bad_slices <- bringing lost bytes back: a parity sidecar ("LACR", Reed-Solomon over GF(2^8)) beside
@@ -1267,6 +1271,101 @@ int lacx_decoder_item_ar_tracks(const lacx_decoder* dec, uint32_t disc, const la
 int lacx_decoder_item_ar_sums(const lacx_decoder* dec, uint32_t disc, uint32_t track, const uint32_t** v1, const uint32_t** v2,
                               const uint32_t** s450, uint32_t* count);
 int lacx_ar_ids(const uint64_t* track_frames, uint32_t ntracks, uint32_t flags, uint32_t lba0, lacx_ar_id* out);
+
+/* Bit-compare: how two streams relate -- whether they decode to the same samples, if not how many samples differ, where and
+ * by how much (the null test: the peak and energy of a - b), and whether they become identical once one is shifted by up to
+ * 32767 frames, as two CD drives with different read offsets or two pressings produce.  What other tool chains call
+ * "bit-compare tracks" or "compare WAVs", made on the device where the samples lie.  Out of scope: comparing across bit
+ * depths, sample rates or channel counts, a lenient form, a .lac against PCM in one call (lacx_decoder_verify_batch_device
+ * does that at offset 0), sub-sample or fuzzy alignment, applying the shift (the edit calls do that), more than two channels.
+ * Definition (csrc/compare_core.h is its only statement in code).  Everything is an exact integer and does not
+ * depend on the order of evaluation, the batch or the place in a job: device, CPU twin and a numpy restatement agree byte for
+ * byte.
+ *   Pair: (a, b, centre, radius) -- two indices into the call's source array (one source may stand in many pairs and is
+ *   decoded once; a == b is allowed), a signed centre and a radius, 0 <= radius <= 32767, |centre| + radius < 2^31; both
+ *   sources of 1 or 2 channels, 16 or 24 bit, alike in channels, depth and sample rate, each of fewer than 2^32 frames.
+ *   Pairing: with na, nb the frame counts, A(f) = a[f] for 0 <= f < na and 0 in every channel elsewhere, B likewise.  At
+ *   offset o frame f of A is paired with frame f + o of B over the union domain f in [fmin(o), fmax(o)), fmin(o) = min(0,
+ *   -o), fmax(o) = max(na, nb - o): audio one side has and the other lacks counts as differing from zeros.
+ *   Search: for every o in [centre - radius, centre + radius], mis[o] = the (frame, channel) samples of the domain with
+ *   A(f)[c] != B(f + o)[c], a uint64.  The chosen offset has the fewest mismatches; ties go to the smallest |o - centre|,
+ *   then to the larger o.  At radius 0 there is no search and the chosen offset is the centre.
+ *   Rows: at the chosen offset o* the domain is cut into rows of 16384 frames from fmin(o*).  Per row and channel, with d =
+ *   A - B: the mismatches, the first and last differing frame and the lowest frame of max |d| (counted from the domain's
+ *   first frame; LACX_COMPARE_NONE where nothing differs), max |d|, the sum of |d| and the sum of d^2 (|d| < 2^25).
+ *   Totals (host, lacx_compare_combine): per channel and together the mismatches, the first and last differing frame, the
+ *   peak difference with its frame (the lowest; the lower channel first), the sums as 128-bit integers, the rows that
+ *   differ, and lead / tail: the frames at either end of the domain that only one side has (at most the domain) and which
+ *   side (LACX_COMPARE_SIDE_*).  Frame positions of the totals are on A's axis as int64: they may be negative or >= na; 0
+ *   where nothing differs.
+ * lacx_decoder_compare_batch_device: strict, like lacx_decoder_digest_batch_device -- the decode, the in-place mid/side
+ *   inverse, then k_compare_search (one launch; not launched where every pair has radius 0), a host look at 8 (2 radius + 1)
+ *   bytes per pair, and k_compare_rows (one launch) on `stream`: two round trips where any radius is above 0, else one.
+ *   Refused per pair on the host before any device work, each LACX_E_INVALID: "sources outside the call's array", "channel
+ *   counts differ (A, B)", "bit depths differ (A, B)", "sample rates differ (A, B)", "radius above 32767", "centre out of
+ *   range", "source k holds 2^32 frames or more", "source k: <lacx_stream_parse's text>" (with that call's code; k: the index
+ *   in the call's array).  A source that fails to decode fails the pairs that name it with the decode's own code and "source
+ *   k: ..." and does not cost the other pairs.  pair_rc, out: nullable arrays of npairs.  lacx_decoder_item_error(dec, pair)
+ *   is the pair's text.
+ * lacx_decoder_compare_pcm_batch_device: device-resident source PCM in any LACX_PCM_* layout; the per-source host checks
+ *   ("source k: <text>"), the device-found validation texts ("source k: <text>") and the bounds are those of
+ *   lacx_decoder_digest_pcm_batch_device.
+ * lacx_decoder_item_compare_rows: the rows of pair `pair` of the decoder's last compare call.
+ *   lacx_decoder_item_compare_counts: mis[] over its searched offsets, count = 2 radius + 1, ordered o = centre - radius ..
+ *   centre + radius; a pair of radius 0 was not searched and gives count = 0.  Both valid until the decoder's next call;
+ *   LACX_E_INVALID outside that call and for a pair that failed.
+ * lacx_compare_combine: host only; the totals the batch calls return, from rows.  LACX_E_INVALID: null arguments, channels
+ *   not 1 or 2, bit depth not 16 or 24, a row count that is not the domain's.
+ * Everything else as lacx_decoder_truepeak_batch_device.  No scratch.
+ * Time (scripts/compare_bench.py, profiles/compare_bench.txt): on 24 pairs of four-minute stereo 16-bit streams, each
+ * a song against a copy shifted by up to 587 frames, 21.0 ms of kernels and 44.6 ms of wall at radius 0 (the digest's job on
+ * the same 48 streams: 25.3 / 48.5 ms); at radius 588 94.9 ms of kernels, at radius 2939 (2.99e12 sample comparisons) 239.2 ms
+ * of kernels and 263.1 ms of wall, the search and its round trip 216.8 ms; k_compare_rows alone 2.4 to 3.8 ms. */
+#define LACX_COMPARE_NONE (~0ull)
+#define LACX_COMPARE_SIDE_NONE 0u
+#define LACX_COMPARE_SIDE_A 1u
+#define LACX_COMPARE_SIDE_B 2u
+typedef struct lacx_compare_pair {        /* 24 bytes */
+    uint32_t a, b;
+    int64_t centre;
+    uint32_t radius, reserved;
+} lacx_compare_pair;
+typedef struct lacx_compare_channel_row { /* 48 bytes */
+    uint64_t first, last, max_at;         /* frames from the domain's first; LACX_COMPARE_NONE: nothing differs */
+    uint64_t sum_abs, sum_sq;
+    uint32_t mismatches, max_abs;
+} lacx_compare_channel_row;
+typedef struct lacx_compare_row {         /* 96 bytes */
+    lacx_compare_channel_row ch[2];
+} lacx_compare_row;
+typedef struct lacx_compare_channel {     /* 72 bytes */
+    uint64_t mismatches;
+    int64_t first, last, peak_at;
+    uint64_t sum_abs_lo, sum_abs_hi, sum_sq_lo, sum_sq_hi;
+    uint32_t peak, reserved;
+} lacx_compare_channel;
+typedef struct lacx_compare {             /* 296 bytes */
+    int64_t offset;                       /* the chosen offset */
+    int64_t domain_first;                 /* fmin(offset), on A's axis */
+    uint64_t domain_frames;
+    uint64_t frames_a, frames_b;
+    uint64_t mismatches;                  /* all channels */
+    int64_t first, last, peak_at;
+    uint64_t sum_abs_lo, sum_abs_hi, sum_sq_lo, sum_sq_hi;
+    uint64_t rows, rows_differ;
+    uint64_t lead, tail;
+    uint32_t peak, sample_rate;
+    uint8_t peak_channel, channels, bit_depth, lead_side, tail_side, reserved[3];
+    lacx_compare_channel ch[2];
+} lacx_compare;
+int lacx_decoder_compare_batch_device(lacx_decoder* dec, const lacx_span* lacs, uint32_t nlacs, const lacx_compare_pair* pairs, uint32_t npairs,
+                                      void* stream, int* pair_rc, lacx_compare* out, float* device_ms);
+int lacx_decoder_compare_pcm_batch_device(lacx_decoder* dec, const lacx_digest_source* src, uint32_t nsrc, const lacx_compare_pair* pairs,
+                                          uint32_t npairs, void* stream, int* pair_rc, lacx_compare* out, float* device_ms);
+int lacx_decoder_item_compare_rows(const lacx_decoder* dec, uint32_t pair, const lacx_compare_row** rows, uint32_t* count);
+int lacx_decoder_item_compare_counts(const lacx_decoder* dec, uint32_t pair, const uint64_t** counts, uint32_t* count);
+int lacx_compare_combine(const lacx_compare_row* rows, uint32_t count, uint8_t channels, uint8_t bit_depth, uint32_t sample_rate, uint64_t frames_a,
+                         uint64_t frames_b, int64_t offset, lacx_compare* out);
 
 /* Recovery data: repairing a damaged .lac file from a parity sidecar.  Digests, salvage and the manifest all end in "this
  * block is lost"; the container has no redundancy of its own.  A recovery sidecar ("LACR") kept beside the file brings the

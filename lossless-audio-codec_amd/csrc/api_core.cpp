@@ -502,6 +502,8 @@ uint32_t lacx_sizeof(const char* name) {
                  {"truepeak_row", sizeof(lacx_truepeak_row)}, {"truepeak_channel", sizeof(lacx_truepeak_channel)}, {"truepeak", sizeof(lacx_truepeak)},
                  {"spectrum_row", sizeof(lacx_spectrum_row)}, {"spectrum", sizeof(lacx_spectrum)},
                  {"ar_disc", sizeof(lacx_ar_disc)}, {"ar_id", sizeof(lacx_ar_id)}, {"ar_result", sizeof(lacx_ar_result)}, {"ar_track", sizeof(lacx_ar_track)},
+                 {"compare_pair", sizeof(lacx_compare_pair)}, {"compare_channel_row", sizeof(lacx_compare_channel_row)}, {"compare_row", sizeof(lacx_compare_row)},
+                 {"compare_channel", sizeof(lacx_compare_channel)}, {"compare", sizeof(lacx_compare)},
                  {"channel_info", sizeof(lacx_channel_info)}, {"block_info", sizeof(lacx_block_info)},
                  {"stream_report", sizeof(lacx_stream_report)}, {"edit_segment", sizeof(lacx_edit_segment)},
                  {"edit_output", sizeof(lacx_edit_output)},     {"edit_result", sizeof(lacx_edit_result)}};

@@ -123,6 +123,8 @@ struct DecodeJob {
     lacx_spectrum* xres = nullptr;       // spectrum: [n]
     const ArJobIn* ar = nullptr;         // the digest form with k_accuraterip in k_digest's place (DecodePlan::accuraterip): the discs
     std::vector<uint32_t>* ar_planned = nullptr;  // ... those that went to the device (DecodePlan::ar_disc); the rest in d->ar_at, d->ar_sums
+    const CmpJobIn* cmp = nullptr;       // the digest form with k_compare_search / k_compare_rows in k_digest's place (DecodePlan::compare): the pairs
+    std::vector<uint32_t>* cmp_planned = nullptr;  // ... those that went to the device (DecodePlan::cmp_pair); the rest in d->cmp_at, d->cmp_counts, d->cmp_rows
 };
 static_assert(sizeof(StatsAcc) == kStatsRowBytes, "the plan lays the accumulator rows out kStatsRowBytes apart");
 
@@ -284,6 +286,34 @@ DevErr upload_payload(lacx_decoder* d, const DecodeJob& job, const DecodePlan& p
     return chk(hipMemcpyAsync(d->d_pay() + plan.src_at, plan.host_src, plan.host_src_bytes, hipMemcpyHostToDevice, st), "H2D source");
 }
 
+// The kernels of a compare job whose tables (y, compare_plan.h) lie filled at d->d_meta() and d->h_meta(): where a pair has a
+// radius the search, its counts back, the host's choice of the offsets and the pairs and row offsets to the device again --
+// the second round trip -- then the rows.  y leaves with the choice.
+DevErr compare_kernels(lacx_decoder* d, CmpLayout& y, unsigned long long* bad, hipStream_t st) {
+    if (y.search) {
+        if (DevErr e = chk(launch_compare_search(cmp_args(y, d->d_meta(), bad), st), "compare search launch")) return e;
+        if (DevErr e = chk(hipMemcpyAsync(d->h_meta() + y.counts, d->d_meta() + y.counts, 8 * (size_t)y.total_counts, hipMemcpyDeviceToHost, st), "D2H compare counts"))
+            return e;
+        if (DevErr e = chk(hipStreamSynchronize(st), "synchronize")) return e;
+        cmp_choose_all(y, reinterpret_cast<const unsigned long long*>(d->h_meta() + y.counts));
+        cmp_fill_choice(y, d->h_meta());
+        if (DevErr e = chk(hipMemcpyAsync(d->d_meta() + y.pairs, d->h_meta() + y.pairs, y.choice_bytes(), hipMemcpyHostToDevice, st), "H2D compare choice")) return e;
+    }
+    return chk(launch_compare_rows(cmp_args(y, d->d_meta(), bad), st), "compare rows launch");
+}
+// ... and its rows back (queued): 96 bytes per 16384 frames of a domain, inside the tables
+DevErr compare_fetch(lacx_decoder* d, const CmpLayout& y, hipStream_t st) {
+    if (!y.rows_cap) return DevErr{};
+    return chk(hipMemcpyAsync(d->h_meta() + y.rows, d->d_meta() + y.rows, (size_t)kCmpRowBytes * (size_t)y.rows_cap, hipMemcpyDeviceToHost, st), "D2H compare rows");
+}
+// ... and what the item calls give, out of the host's copy of the tables
+void compare_keep(lacx_decoder* d, const CmpLayout& y) {
+    const auto* counts = reinterpret_cast<const uint64_t*>(d->h_meta() + y.counts);
+    d->cmp_counts.assign(counts, counts + y.total_counts);
+    const auto* rows = reinterpret_cast<const lacx_compare_row*>(d->h_meta() + y.rows);
+    d->cmp_rows.assign(rows, rows + y.rows_cap);
+}
+
 // The kernels between the decoder's two events, then what every form reads back, and the wait for it.
 DevErr launch_and_wait(lacx_decoder* d, const DecodeJob& job, const DecodePlan& plan, hipStream_t st, bool* runs_rerun) {
     const DecodeArgs a = plan_args(plan, d->d_meta(), d->d_pay(), d->d_status(), d->d_ms());
@@ -302,7 +332,13 @@ DevErr launch_and_wait(lacx_decoder* d, const DecodeJob& job, const DecodePlan& 
         if (DevErr e = chk(launch_spectrum(plan_spec_args(plan, d->d_meta()), st), "spectrum launch")) return e;
     if (plan.accuraterip)  // likewise
         if (DevErr e = chk(launch_accuraterip(plan_ar_args(plan, d->d_meta()), st), "rip checksum launch")) return e;
+    if (plan.compare) {  // likewise, in two round trips where a pair has a radius
+        d->cmp_at = plan.cmp_at;
+        if (DevErr e = compare_kernels(d, d->cmp_at, nullptr, st)) return e;
+    }
     if (DevErr e = chk(hipEventRecord(d->e1, st), "event record")) return e;
+    if (plan.compare)
+        if (DevErr e = compare_fetch(d, d->cmp_at, st)) return e;
     if (plan.accuraterip && plan.ar_at.total_sums)  // the sums: 12 bytes per track and offset, inside the tables
         if (DevErr e = chk(hipMemcpyAsync(d->h_meta() + plan.ar_at.sums, d->d_meta() + plan.ar_at.sums, 4 * (size_t)plan.ar_at.total_sums, hipMemcpyDeviceToHost, st),
                            "D2H rip checksums"))
@@ -334,7 +370,7 @@ DevErr launch_and_wait(lacx_decoder* d, const DecodeJob& job, const DecodePlan& 
         if (DevErr e = chk(hipMemcpyAsync(d->h_meta() + res, d->d_meta() + res, sizeof(VerifyWords) * m, hipMemcpyDeviceToHost, st), "D2H verify results"))
             return e;
     // the digest form's whole answer: 8 bytes per item
-    if (plan.form == DecodeForm::digest && !plan.loudness && !plan.truepeak && !plan.spectrum && !plan.accuraterip)
+    if (plan.form == DecodeForm::digest && !plan.loudness && !plan.truepeak && !plan.spectrum && !plan.accuraterip && !plan.compare)
         if (DevErr e = chk(hipMemcpyAsync(d->h_meta() + res, d->d_meta() + res, sizeof(DigestWords) * m, hipMemcpyDeviceToHost, st), "D2H digests"))
             return e;
     // block digests: 4 bytes per block beside the statuses
@@ -372,6 +408,10 @@ DevErr collect(lacx_decoder* d, const DecodeJob& job, const DecodePlan& plan, hi
         const auto* sums = reinterpret_cast<const uint32_t*>(d->h_meta() + plan.ar_at.sums);
         d->ar_sums.assign(sums, sums + plan.ar_at.total_sums);
         if (job.ar_planned) *job.ar_planned = plan.ar_disc;
+    }
+    if (plan.compare) {  // a pair's answer needs both of its items: the caller puts it together from these
+        compare_keep(d, d->cmp_at);
+        if (job.cmp_planned) *job.cmp_planned = plan.cmp_pair;
     }
     for (size_t j = 0; j < plan.items.size(); ++j) {
         const PlanItem& p = plan.items[j];
@@ -437,6 +477,7 @@ DevErr collect(lacx_decoder* d, const DecodeJob& job, const DecodePlan& plan, hi
             rows.assign(all + si.row0, all + si.row0 + si.rows);
             if (job.xres) job.xres[i] = spectrum_of_rows(SpSet{rows.data(), (uint32_t)rows.size(), p.info.channels, p.info.bit_depth, p.info.frames, p.info.sample_rate, plan.spectrum, job.floor_db});
         } else if (plan.accuraterip) {  // (per disc, not per item)
+        } else if (plan.compare) {      // (per pair, not per item)
         } else if (plan.form == DecodeForm::digest) {
             const DigestWords& w = reinterpret_cast<const DigestWords*>(d->h_meta() + plan.at.res)[j];
             if (job.dres) job.dres[i] = make_digest(w.raw, p.info.frames, p.info.sample_rate, p.info.channels, p.info.bit_depth);
@@ -496,8 +537,8 @@ int decode_batch_run(lacx_decoder* d, const DecodeJob& job, std::vector<int>& co
     // LACX_DECODE_BATCH_PAD=1 (tuning knob, read per call): every item's blocks start a new wave
     const char* pad_env = std::getenv("LACX_DECODE_BATCH_PAD");
     DecodePlan plan;
-    const char* whole = plan_decode(job.in, job.n, job.form, job.sample_type, pad_env && pad_env[0] == '1', plan, code, err, job.salvage, job.blocks, job.stats,
-                                    job.runs, d->runs_list_cap ? d->runs_list_cap : kRunsListCap, job.loudness, job.truepeak, job.spectrum, job.ar);
+    const char* whole = plan_decode_job(job.in, job.n, job.form, job.sample_type, pad_env && pad_env[0] == '1', plan, code, err, job.salvage, job.blocks, job.stats,
+                                    job.runs, d->runs_list_cap ? d->runs_list_cap : kRunsListCap, job.loudness, job.truepeak, job.spectrum, job.ar, job.cmp);
     if (lacx_device_count() <= 0) whole = "no usable HIP device";
     int rc = whole ? decode_fail(LACX_E_DEVICE, whole) : LACX_OK;
     if (!whole && !plan.items.empty()) {
@@ -1794,6 +1835,237 @@ int lacx_ar_ids(const uint64_t* track_frames, uint32_t ntracks, uint32_t flags, 
         if (track_frames[t] == 0) return decode_fail(LACX_E_INVALID, "track " + std::to_string(t) + " is empty");
     if (flags & ~(uint32_t)(LACX_AR_FIRST | LACX_AR_LAST)) return decode_fail(LACX_E_INVALID, "unknown flags");
     (void)ar_ids(track_frames, ntracks, flags, lba0, *out);
+    return LACX_OK;
+}
+
+// ---- bit-compare (lacx.h) ----
+namespace {
+// The pairs of a call against its sources: per pair its code and text ("" = it goes to the device).  fmt / src_code / src_why:
+// per source of the call its format, or why it is refused.
+struct CmpCall {
+    std::vector<int> code;
+    std::vector<std::string> err;
+};
+void cmp_resolve(const lacx_compare_pair* pairs, uint32_t npairs, uint32_t nsrc, const std::vector<CmpFmt>& fmt, const std::vector<int>& src_code,
+                 const std::vector<std::string>& src_why, CmpCall& c) {
+    c.code.assign(npairs, LACX_OK);
+    c.err.assign(npairs, std::string());
+    for (uint32_t k = 0; k < npairs; ++k) {
+        const lacx_compare_pair& x = pairs[k];
+        if (x.a >= nsrc || x.b >= nsrc) {
+            c.code[k] = LACX_E_INVALID, c.err[k] = "sources outside the call's array";
+            continue;
+        }
+        for (uint32_t at : {x.a, x.b})
+            if (c.code[k] == LACX_OK && src_code[at] != LACX_OK) c.code[k] = src_code[at], c.err[k] = "source " + std::to_string(at) + ": " + src_why[at];
+        if (c.code[k] != LACX_OK) continue;
+        const std::string why = cmp_pair_why(x, fmt.data(), nsrc);
+        if (!why.empty()) c.code[k] = LACX_E_INVALID, c.err[k] = why;
+    }
+}
+
+void cmp_reset(lacx_decoder* d, uint32_t npairs, lacx_compare* out, float* device_ms) {
+    if (device_ms) *device_ms = 0.f;
+    if (out) std::memset(out, 0, sizeof(lacx_compare) * npairs);
+    d->cmp_at = CmpLayout{};
+    d->cmp_counts.clear();
+    d->cmp_rows.clear();
+    d->cmp_ok.assign(npairs, 0);
+    d->cmp_slot.assign(npairs, 0);
+}
+
+// Pair k of the call went to the device as the plan's pair `slot` and both of its sources are good: its answer.
+void cmp_accept(lacx_decoder* d, uint32_t k, size_t slot, uint32_t sample_rate, lacx_compare* out) {
+    d->cmp_ok[k] = 1;
+    d->cmp_slot[k] = (uint32_t)slot;
+    if (out) out[k] = cmp_result(d->cmp_at, slot, d->cmp_rows.data() + d->cmp_at.pair[slot].row0, sample_rate);
+}
+
+// How a compare call ends: as batch_outcome, per pair.
+int cmp_outcome(lacx_decoder* d, int rc, CmpCall& c, int* pair_rc) {
+    if (pair_rc) std::copy(c.code.begin(), c.code.end(), pair_rc);
+    d->item_err = std::move(c.err);
+    if (rc != LACX_OK) return rc;
+    for (size_t k = 0; k < c.code.size(); ++k)
+        if (c.code[k] != LACX_OK) return decode_fail(c.code[k], "pair " + std::to_string(k) + ": " + d->item_err[k]);
+    return LACX_OK;
+}
+
+// The accepted pairs over the sources they name, each source once: used[i] = the source's place among them, or ~0u.
+void cmp_gather(const lacx_compare_pair* pairs, uint32_t npairs, const CmpCall& c, uint32_t nsrc, std::vector<uint32_t>& used, std::vector<uint32_t>& order,
+                std::vector<CmpPairIn>& apairs, std::vector<uint32_t>& which) {
+    used.assign(nsrc, ~0u);
+    for (uint32_t k = 0; k < npairs; ++k) {
+        if (c.code[k] != LACX_OK) continue;
+        for (uint32_t at : {pairs[k].a, pairs[k].b})
+            if (used[at] == ~0u) used[at] = (uint32_t)order.size(), order.push_back(at);
+        apairs.push_back(CmpPairIn{used[pairs[k].a], used[pairs[k].b], (long long)pairs[k].centre, pairs[k].radius});
+        which.push_back(k);
+    }
+}
+}  // namespace
+
+int lacx_decoder_compare_batch_device(lacx_decoder* d, const lacx_span* lacs, uint32_t nlacs, const lacx_compare_pair* pairs, uint32_t npairs, void* stream,
+                                      int* pair_rc, lacx_compare* out, float* device_ms) {
+    if (!d) return decode_fail(LACX_E_INVALID, "null decoder");
+    if (!lacs || nlacs == 0 || !pairs || npairs == 0) return decode_fail(LACX_E_INVALID, "null argument or empty batch");
+    cmp_reset(d, npairs, out, device_ms);
+    std::vector<CmpFmt> fmt(nlacs);
+    std::vector<int> src_code(nlacs, LACX_OK);
+    std::vector<std::string> src_why(nlacs);
+    for (uint32_t i = 0; i < nlacs; ++i) {
+        lacx_stream_info f{};
+        const char* why = nullptr;
+        src_code[i] = parse_stream(lacs[i].data, lacs[i].size, &f, &why);
+        if (src_code[i] != LACX_OK) src_why[i] = why ? why : "";
+        else if (f.frames == 0) src_code[i] = LACX_E_INVALID, src_why[i] = "source has no frames";
+        fmt[i] = CmpFmt{f.frames, f.sample_rate, (uint8_t)f.channels, (uint8_t)f.bit_depth};
+    }
+    CmpCall c;
+    cmp_resolve(pairs, npairs, nlacs, fmt, src_code, src_why, c);
+    std::vector<uint32_t> used, order, which;
+    std::vector<CmpPairIn> apairs;
+    cmp_gather(pairs, npairs, c, nlacs, used, order, apairs, which);
+    int rc = LACX_OK;
+    if (!apairs.empty()) {
+        std::vector<BatchIn> in;
+        for (uint32_t at : order) in.push_back(BatchIn{lacs[at].data, lacs[at].size, nullptr, nullptr, 0});
+        const CmpJobIn cjob{apairs.data(), (uint32_t)apairs.size()};
+        std::vector<uint32_t> planned;
+        DecodeJob job{in.data(), (uint32_t)in.size(), DecodeForm::digest, kWholeStreams, static_cast<hipStream_t>(stream), nullptr, nullptr, device_ms};
+        job.cmp = &cjob;
+        job.cmp_planned = &planned;
+        std::vector<int> code;
+        std::vector<std::string> err;
+        rc = decode_batch_run(d, job, code, err);
+        for (size_t a = 0; a < apairs.size(); ++a) {
+            const uint32_t k = which[a];
+            for (uint32_t at : {pairs[k].a, pairs[k].b})
+                if (c.code[k] == LACX_OK && code[used[at]] != LACX_OK)
+                    c.code[k] = code[used[at]], c.err[k] = rc != LACX_OK ? err[used[at]] : "source " + std::to_string(at) + ": " + err[used[at]];
+            if (c.code[k] != LACX_OK) continue;
+            const auto slot = std::find(planned.begin(), planned.end(), (uint32_t)a);
+            if (slot == planned.end()) c.code[k] = LACX_E_RUNTIME, c.err[k] = "pair was not planned";
+            else cmp_accept(d, k, (size_t)(slot - planned.begin()), fmt[pairs[k].a].sample_rate, out);
+        }
+        if (rc != LACX_OK) cmp_reset(d, npairs, out, nullptr);
+    } else if (lacx_device_count() <= 0) {
+        rc = decode_fail(LACX_E_DEVICE, "no usable HIP device");
+    }
+    return cmp_outcome(d, rc, c, pair_rc);
+}
+
+int lacx_decoder_compare_pcm_batch_device(lacx_decoder* d, const lacx_digest_source* src, uint32_t nsrc, const lacx_compare_pair* pairs, uint32_t npairs,
+                                          void* stream, int* pair_rc, lacx_compare* out, float* device_ms) {
+    if (!d) return decode_fail(LACX_E_INVALID, "null decoder");
+    if (!src || nsrc == 0 || !pairs || npairs == 0) return decode_fail(LACX_E_INVALID, "null argument or empty batch");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    cmp_reset(d, npairs, out, device_ms);
+    std::vector<CmpFmt> fmt(nsrc);
+    std::vector<int> src_code(nsrc, LACX_OK);
+    std::vector<std::string> src_why(nsrc);
+    for (uint32_t i = 0; i < nsrc; ++i) {
+        std::string text;
+        if (const char* why = check_digest_source(src[i], text)) src_code[i] = LACX_E_INVALID, src_why[i] = why;
+        fmt[i] = CmpFmt{src[i].frames, src[i].sample_rate, (uint8_t)src[i].pcm.channels, src[i].bit_depth};
+    }
+    CmpCall c;
+    cmp_resolve(pairs, npairs, nsrc, fmt, src_code, src_why, c);
+    std::vector<uint32_t> used, order, which;
+    std::vector<CmpPairIn> apairs;
+    cmp_gather(pairs, npairs, c, nsrc, used, order, apairs, which);
+    std::vector<CmpSrcIn> in;
+    for (uint32_t at : order) {
+        const lacx_digest_source& x = src[at];
+        in.push_back(CmpSrcIn{x.pcm.data0, x.pcm.data1, x.frames, x.pcm.layout, (uint32_t)in.size(), (uint8_t)x.pcm.channels, x.bit_depth, true});
+    }
+    int rc = lacx_device_count() <= 0 ? decode_fail(LACX_E_DEVICE, "no usable HIP device") : LACX_OK;
+    if (rc == LACX_OK && !apairs.empty()) {
+        const size_t ns = in.size();
+        if (const char* why = cmp_check(in.data(), apairs.data(), apairs.size())) rc = decode_fail(LACX_E_DEVICE, why);
+        if (rc == LACX_OK) {  // the tables: bad [ns] | the tables of compare_plan.h (16-byte aligned)
+            d->cmp_at = cmp_layout(plan_detail::up16(8 * ns), in.data(), ns, apairs.data(), apairs.size());
+            CmpLayout& y = d->cmp_at;
+            int prev_device = -1;
+            DevErr e = decoder_open(d, &prev_device);
+            if (!e) e = buf_grow(d->tables, y.size, y.size / 8 + 256);
+            if (!e) {
+                for (size_t j = 0; j < ns; ++j) reinterpret_cast<unsigned long long*>(d->h_meta())[j] = kDigestClean;
+                std::memset(d->h_meta() + 8 * ns, 0, y.base - 8 * ns);
+                cmp_fill(y, in.data(), d->h_meta());
+                e = chk(hipMemcpyAsync(d->d_meta(), d->h_meta(), y.rows, hipMemcpyHostToDevice, st), "H2D compare tables");
+            }
+            if (!e) e = chk(hipEventRecord(d->e0, st), "event record");
+            if (!e) e = compare_kernels(d, y, reinterpret_cast<unsigned long long*>(d->d_meta()), st);
+            if (!e) e = chk(hipEventRecord(d->e1, st), "event record");
+            if (!e) e = chk(hipMemcpyAsync(d->h_meta(), d->d_meta(), 8 * ns, hipMemcpyDeviceToHost, st), "D2H validation keys");
+            if (!e) e = compare_fetch(d, y, st);
+            if (!e) e = chk(hipStreamSynchronize(st), "synchronize");
+            if (!e && device_ms) (void)hipEventElapsedTime(device_ms, d->e0, d->e1);
+            if (prev_device >= 0) (void)hipSetDevice(prev_device);
+            if (e) {
+                rc = decode_fail(LACX_E_DEVICE, std::string(e.what) + ": " + hipGetErrorString(e.e));
+            } else {
+                compare_keep(d, y);
+                const auto* bad = reinterpret_cast<const unsigned long long*>(d->h_meta());
+                for (size_t a = 0; a < apairs.size(); ++a) {
+                    const uint32_t k = which[a];
+                    for (uint32_t at : {pairs[k].a, pairs[k].b}) {
+                        const unsigned long long key = bad[used[at]];
+                        if (c.code[k] != LACX_OK || key == kDigestClean) continue;
+                        ImportBad b{{kImportClean, kImportClean}};  // the encoder's words for it (import_msg.h)
+                        b.key[key >> 63] = key & ~(1ull << 63);
+                        int ch = 0;
+                        unsigned long long index = 0;
+                        std::string text;
+                        (void)import_bad_message(b, src[at].bit_depth, &ch, &index, text);
+                        c.code[k] = LACX_E_INVALID, c.err[k] = "source " + std::to_string(at) + ": " + text;
+                    }
+                    if (c.code[k] == LACX_OK) cmp_accept(d, k, a, fmt[pairs[k].a].sample_rate, out);
+                }
+            }
+        }
+    }
+    if (rc != LACX_OK) {  // the whole call failed: no pair has an answer
+        cmp_reset(d, npairs, out, nullptr);
+        for (uint32_t k = 0; k < npairs; ++k)
+            if (c.code[k] == LACX_OK) c.code[k] = rc, c.err[k] = g_decode_err;
+    }
+    return cmp_outcome(d, rc, c, pair_rc);
+}
+
+int lacx_decoder_item_compare_rows(const lacx_decoder* d, uint32_t pair, const lacx_compare_row** rows, uint32_t* count) {
+    if (rows) *rows = nullptr;
+    if (count) *count = 0;
+    if (!d || !rows || !count) return decode_fail(LACX_E_INVALID, "null argument");
+    if (pair >= d->cmp_ok.size() || !d->cmp_ok[pair]) return decode_fail(LACX_E_INVALID, "no such pair in the last compare call");
+    const CmpPair& p = d->cmp_at.pair[d->cmp_slot[pair]];
+    *rows = d->cmp_rows.data() + p.row0;
+    *count = (uint32_t)p.nrows;
+    return LACX_OK;
+}
+
+int lacx_decoder_item_compare_counts(const lacx_decoder* d, uint32_t pair, const uint64_t** counts, uint32_t* count) {
+    if (counts) *counts = nullptr;
+    if (count) *count = 0;
+    if (!d || !counts || !count) return decode_fail(LACX_E_INVALID, "null argument");
+    if (pair >= d->cmp_ok.size() || !d->cmp_ok[pair]) return decode_fail(LACX_E_INVALID, "no such pair in the last compare call");
+    const CmpPair& p = d->cmp_at.pair[d->cmp_slot[pair]];
+    if (p.radius == 0) return LACX_OK;  // not searched
+    *counts = d->cmp_counts.data() + p.count0;
+    *count = cmp_width(p);
+    return LACX_OK;
+}
+
+int lacx_compare_combine(const lacx_compare_row* rows, uint32_t count, uint8_t channels, uint8_t bit_depth, uint32_t sample_rate, uint64_t frames_a,
+                         uint64_t frames_b, int64_t offset, lacx_compare* out) {
+    if (out) std::memset(out, 0, sizeof(*out));
+    if (!out || (!rows && count)) return decode_fail(LACX_E_INVALID, "null argument");
+    if (channels != 1 && channels != 2) return decode_fail(LACX_E_INVALID, "unsupported channel count");
+    if (bit_depth != 16 && bit_depth != 24) return decode_fail(LACX_E_INVALID, "unsupported bit depth: " + std::to_string((int)bit_depth));
+    if ((frames_a >> 32) || (frames_b >> 32) || offset <= -(1ll << 31) || offset >= (1ll << 31)) return decode_fail(LACX_E_INVALID, "frames or offset out of range");
+    if (cmp_rows_at(frames_a, frames_b, offset) != count) return decode_fail(LACX_E_INVALID, "row count is not the domain's");
+    *out = cmp_combine(rows, count, channels, bit_depth, sample_rate, frames_a, frames_b, offset);
     return LACX_OK;
 }
 

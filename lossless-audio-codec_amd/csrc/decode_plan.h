@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "accuraterip_plan.h"
+#include "compare_plan.h"
 #include "container.h"
 #include "lacx.h"
 #include "lacx_types.h"
@@ -86,6 +87,9 @@ struct BatchIn {
 // (accuraterip_core.h) -- behind res [m] the tables of accuraterip_plan.h (DecodePlan::ar_at).  Its discs are runs of
 // consecutive items (ArJobIn); a disc's items lie side by side in the decoder's PCM buffers, but the kernel reads them
 // through the disc's source table, so nothing depends on that.
+// ... and of a bit-compare job (DecodePlan::compare, lacx_decoder_compare_batch_device): likewise with k_compare_search and
+// k_compare_rows (compare_core.h) -- behind res [m] the tables of compare_plan.h (DecodePlan::cmp_at).  Its sources are the
+// planned items, each once however many pairs name it; the kernels read them through the source table.
 enum class DecodeForm { wav, device, host, verify, digest, blocks };
 constexpr int kWholeStreams = -1;
 constexpr size_t kStatsRowBytes = 96;  // sizeof(StatsAcc), stats_core.h (k_stats.hip asserts it)
@@ -95,6 +99,13 @@ constexpr size_t kStatsRowBytes = 96;  // sizeof(StatsAcc), stats_core.h (k_stat
 struct ArJobIn {
     const ArDiscIn* discs;
     uint32_t ndiscs;
+};
+
+// The pairs of a bit-compare job: CmpPairIn::a / b name items of the job's BatchIn array; every pair has passed cmp_pair_why
+// with its items' parsed formats.
+struct CmpJobIn {
+    const CmpPairIn* pairs;
+    uint32_t npairs;
 };
 
 // One item that goes to the device (j counts these; the items that failed their checks are not among them).
@@ -131,6 +142,7 @@ struct TableLayout {
     size_t peak = 0;                         // true-peak job only: TpLayout::base
     size_t spec = 0;                         // spectrum job only: SpLayout::base
     size_t ar = 0;                           // rip-checksum job only: ArLayout::base
+    size_t cmp = 0;                          // bit-compare job only: CmpLayout::base
 };
 
 struct DecodePlan {
@@ -156,6 +168,13 @@ struct DecodePlan {
     std::vector<ArDiscIn> ar_discs;
     std::vector<ArSrcIn> ar_src;
     std::vector<uint32_t> ar_disc;
+    bool compare = false;      // strict job in the digest form with k_compare_search / k_compare_rows in k_digest's place
+    CmpLayout cmp_at{};        // ... inside the tables
+    // ... its sources (one per planned item j, ArSrcIn-like: item = j; addresses null until plan_fill_tables), its pairs that
+    // go to the device (both items do; a / b name cmp_src) and cmp_pair[k]: the pair's index in the job
+    std::vector<CmpSrcIn> cmp_src;
+    std::vector<CmpPairIn> cmp_pairs;
+    std::vector<uint32_t> cmp_pair;
     bool window() const { return sample_type != kWholeStreams; }
     bool own_pcm() const { return form != DecodeForm::device || window(); }  // into the decoder's PCM buffers
     bool post_units() const { return window() || form == DecodeForm::verify || form == DecodeForm::wav || form == DecodeForm::digest || blocks || stats || runs; }
@@ -245,10 +264,9 @@ inline int check_manifest(const BatchIn& x, const lacx_stream_info& f, std::vect
 // Returns null, or why the job as a whole cannot run (nothing is laid out then).
 // salvage: a salvage job (DecodeForm above): an item's blocks and frames are still the whole table's, its payload the
 // bytes of its present blocks.
-inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, int sample_type, bool pad_waves, DecodePlan& plan,
-                               std::vector<int>& code, std::vector<std::string>& err, bool salvage = false, bool blocks = false,
-                               bool stats = false, bool runs = false, uint64_t runs_list_cap = kRunsListCap, bool loudness = false, bool truepeak = false,
-                               uint32_t spectrum = 0, const ArJobIn* ar = nullptr) {
+inline const char* plan_decode_job(const BatchIn* in, uint32_t n, DecodeForm form, int sample_type, bool pad_waves, DecodePlan& plan,
+                                   std::vector<int>& code, std::vector<std::string>& err, bool salvage, bool blocks, bool stats, bool runs,
+                                   uint64_t runs_list_cap, bool loudness, bool truepeak, uint32_t spectrum, const ArJobIn* ar, const CmpJobIn* cmp) {
     using namespace plan_detail;
     plan = DecodePlan{};
     plan.form = form;
@@ -261,6 +279,7 @@ inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, i
     plan.truepeak = truepeak;
     plan.spectrum = spectrum;
     plan.accuraterip = ar != nullptr;
+    plan.compare = cmp != nullptr;
     const bool window = plan.window(), own_pcm = plan.own_pcm(), wav = form == DecodeForm::wav, verify = form == DecodeForm::verify,
                digest = form == DecodeForm::digest, quiet = form == DecodeForm::blocks;
     code.assign(n, LACX_OK);
@@ -273,6 +292,7 @@ inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, i
     if (truepeak && (!digest || salvage || loudness)) return "true peak is a strict job in the digest form";
     if (spectrum && (!digest || salvage || loudness || truepeak || !sp_logn(spectrum))) return "spectrum is a strict job in the digest form with a supported window";
     if (ar && (!digest || salvage || loudness || truepeak || spectrum)) return "rip checksums are a strict job in the digest form";
+    if (cmp && (!digest || salvage || loudness || truepeak || spectrum || ar)) return "bit-compare is a strict job in the digest form";
     plan.items.reserve(n);
     uint32_t v3_blocks = 0;
     for (uint32_t i = 0; i < n; ++i) {
@@ -444,7 +464,25 @@ inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, i
         at.ar = up16(at.res + sizeof(DigestWords) * m);
         plan.ar_at = ar_layout(at.ar, plan.ar_src.data(), plan.ar_discs.data(), plan.ar_discs.size());
     }
-    at.size = ar ? plan.ar_at.size : spectrum ? plan.spec_at.size : truepeak ? plan.peak_at.size : loudness ? plan.loud_at.size : runs ? plan.runs_at.size : stats ? at.stats + kStatsRowBytes * T : blocks ? at.expect + (plan.judged ? 4 * T : 0) : salvage ? at.win + 4 * m : verify ? at.res + sizeof(VerifyWords) * m : digest ? at.res + sizeof(DigestWords) * m : window ? at.win + sizeof(WindowOut) * m : end;
+    if (cmp) {  // likewise; a pair one of whose items was refused above does not go to the device
+        std::vector<uint32_t> where(n, ~0u);
+        for (uint32_t j = 0; j < m; ++j) {
+            where[plan.items[j].src] = j;
+            const PlanItem& p = plan.items[j];
+            plan.cmp_src.push_back(CmpSrcIn{nullptr, nullptr, p.item.frames, (uint32_t)LACX_PCM_PLANAR_I32, j, (uint8_t)p.info.channels, (uint8_t)p.info.bit_depth, false});
+        }
+        for (uint32_t k = 0; k < cmp->npairs; ++k) {
+            CmpPairIn q = cmp->pairs[k];
+            if (q.a >= n || q.b >= n || where[q.a] == ~0u || where[q.b] == ~0u) continue;
+            q.a = where[q.a], q.b = where[q.b];
+            plan.cmp_pairs.push_back(q);
+            plan.cmp_pair.push_back(k);
+        }
+        if (const char* why = cmp_check(plan.cmp_src.data(), plan.cmp_pairs.data(), plan.cmp_pairs.size())) return why;
+        at.cmp = up16(at.res + sizeof(DigestWords) * m);
+        plan.cmp_at = cmp_layout(at.cmp, plan.cmp_src.data(), plan.cmp_src.size(), plan.cmp_pairs.data(), plan.cmp_pairs.size());
+    }
+    at.size = cmp ? plan.cmp_at.size : ar ? plan.ar_at.size : spectrum ? plan.spec_at.size : truepeak ? plan.peak_at.size : loudness ? plan.loud_at.size : runs ? plan.runs_at.size : stats ? at.stats + kStatsRowBytes * T : blocks ? at.expect + (plan.judged ? 4 * T : 0) : salvage ? at.win + 4 * m : verify ? at.res + sizeof(VerifyWords) * m : digest ? at.res + sizeof(DigestWords) * m : window ? at.win + sizeof(WindowOut) * m : end;
     plan.need.payload = (plan.host_src ? plan.src_at + plan.host_src_bytes : plan.total_pay) + kDecodeTailPad;
     plan.need.blocks = T;
     plan.need.pcm_frames = own_pcm ? plan.pcm_total : 0;
@@ -453,6 +491,14 @@ inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, i
     plan.need.tables = at.size;
     plan.need.stats_rows = stats ? T : 0;
     return nullptr;
+}
+
+// plan_decode_job without a bit-compare job: what every caller but the compare calls uses, its parameters defaulted as ever.
+inline const char* plan_decode(const BatchIn* in, uint32_t n, DecodeForm form, int sample_type, bool pad_waves, DecodePlan& plan,
+                               std::vector<int>& code, std::vector<std::string>& err, bool salvage = false, bool blocks = false,
+                               bool stats = false, bool runs = false, uint64_t runs_list_cap = kRunsListCap, bool loudness = false, bool truepeak = false,
+                               uint32_t spectrum = 0, const ArJobIn* ar = nullptr) {
+    return plan_decode_job(in, n, form, sample_type, pad_waves, plan, code, err, salvage, blocks, stats, runs, runs_list_cap, loudness, truepeak, spectrum, ar, nullptr);
 }
 
 // What a salvage job reports for an item, from what every decode copies back anyway: the job's status words (status, by
@@ -576,6 +622,11 @@ inline void plan_fill_tables(const DecodePlan& plan, const BatchIn* in, const Pl
         for (ArSrcIn& x : src) x.data0 = base.left + plan.items[x.item].pcm_at, x.data1 = base.right + plan.items[x.item].pcm_at;
         ar_fill(plan.ar_at, src.data(), plan.ar_discs.data(), plan.ar_discs.size(), h);
     }
+    if (plan.compare) {  // the sources: the items' places in the decoder's own PCM buffers
+        std::vector<CmpSrcIn> src = plan.cmp_src;
+        for (CmpSrcIn& x : src) x.data0 = base.left + plan.items[x.item].pcm_at, x.data1 = x.channels == 2 ? base.right + plan.items[x.item].pcm_at : nullptr;
+        cmp_fill(plan.cmp_at, src.data(), h);
+    }
     if (!plan.lane_blk.empty()) std::memcpy(h + at.lane_blk, plan.lane_blk.data(), 4 * plan.lane_blk.size());
     if (!plan.v2_items.empty()) std::memcpy(h + at.v2_items, plan.v2_items.data(), 4 * plan.v2_items.size());
 }
@@ -614,8 +665,8 @@ inline DecodeArgs plan_args(const DecodePlan& plan, const uint8_t* tables, const
         a.no_output = plan.form == DecodeForm::blocks;
     }
     // (a loudness job has no digest: launch_decode then ends with k_ms_inverse in place, and the loudness kernels follow it;
-    // a true-peak, a spectrum and a rip-checksum job likewise)
-    if (plan.form == DecodeForm::digest && !plan.loudness && !plan.truepeak && !plan.spectrum && !plan.accuraterip) a.digest = reinterpret_cast<DigestWords*>(const_cast<uint8_t*>(tables) + at.res);
+    // a true-peak, a spectrum, a rip-checksum and a bit-compare job likewise)
+    if (plan.form == DecodeForm::digest && !plan.loudness && !plan.truepeak && !plan.spectrum && !plan.accuraterip && !plan.compare) a.digest = reinterpret_cast<DigestWords*>(const_cast<uint8_t*>(tables) + at.res);
     if (plan.stats || plan.runs) a.no_output = true;  // launch_decode ends with k_ms_inverse; k_stats_blocks follows it (plan_stats_args)
     return a;
 }
@@ -649,5 +700,9 @@ inline SpArgs plan_spec_args(const DecodePlan& plan, uint8_t* tables) { return s
 
 // A rip-checksum job's arguments for k_accuraterip: the tables of accuraterip_plan.h inside the tables.
 inline ArArgs plan_ar_args(const DecodePlan& plan, uint8_t* tables) { return ar_args(plan.ar_at, tables, nullptr); }
+
+// A bit-compare job's arguments for k_compare_search / k_compare_rows: the tables of compare_plan.h inside the tables; y: the
+// plan's layout, or the caller's copy of it with the chosen offsets.
+inline CmpArgs plan_cmp_args(const CmpLayout& y, uint8_t* tables) { return cmp_args(y, tables, nullptr); }
 
 }  // namespace lacx

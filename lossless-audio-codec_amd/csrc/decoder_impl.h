@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "accuraterip_plan.h"
+#include "compare_plan.h"
 #include "device_buf.h"
 #include "lacx.h"
 
@@ -60,6 +61,13 @@ struct lacx_decoder {
     std::vector<uint8_t> ar_ok;
     std::vector<uint32_t> ar_slot;  // ... and its place among ar_at's discs
     std::vector<std::vector<lacx_ar_track>> ar_tracks;
+    // the last compare call: the plan's pairs with their chosen offsets, the counts and the rows as the device left them, per
+    // pair of the call whether it has an answer and its place among cmp_at's pairs
+    lacx::CmpLayout cmp_at;
+    std::vector<uint64_t> cmp_counts;
+    std::vector<lacx_compare_row> cmp_rows;
+    std::vector<uint8_t> cmp_ok;
+    std::vector<uint32_t> cmp_slot;
     std::vector<std::vector<lacx_block_info>> item_info;     // the last inspection call's rows per item
     // ... and, where it asked for partition detail, the entries of all its blocks: [T][2][256] each, item i's blocks
     // from info_block0[i] on (~0u: the item has none)

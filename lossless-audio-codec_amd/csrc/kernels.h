@@ -1,5 +1,5 @@
 // kernels.h -- host-visible interface of the kernel translation units (k_front.hip, k_analyze.hip, k_emit.hip,
-// decode.hip, k_digest.hip, k_blockdigest.hip, k_stats.hip, k_runs.hip, k_loudness.hip, k_truepeak.hip, k_spectrum.hip, k_accuraterip.hip, k_inspect.hip, k_recovery.hip, wide.hip, k_import.hip, k_edit.hip).
+// decode.hip, k_digest.hip, k_blockdigest.hip, k_stats.hip, k_runs.hip, k_loudness.hip, k_truepeak.hip, k_spectrum.hip, k_accuraterip.hip, k_compare.hip, k_inspect.hip, k_recovery.hip, wide.hip, k_import.hip, k_edit.hip).
 #pragma once
 #include <cstdlib>
 #include <hip/hip_runtime_api.h>
@@ -221,6 +221,12 @@ hipError_t launch_spectrum(const SpArgs& args, hipStream_t stream);
 // Rip checksums (k_accuraterip.hip, accuraterip_core.h): k_accuraterip over the tiles of a rip-checksum job, in the slot and
 // the two forms launch_truepeak has (accuraterip_plan.h).  The sums must be zero on entry.
 hipError_t launch_accuraterip(const ArArgs& args, hipStream_t stream);
+
+// Bit-compare (k_compare.hip, compare_core.h): k_compare_search over the search tiles of a compare job (nothing where no pair
+// has a radius; the counts must be zero on entry), and k_compare_rows over the rows of the pairs at their chosen offsets, in
+// the slot and the two forms launch_truepeak has (compare_plan.h).
+hipError_t launch_compare_search(const CmpArgs& args, hipStream_t stream);
+hipError_t launch_compare_rows(const CmpArgs& args, hipStream_t stream);
 
 // Recovery data (k_recovery.hip, recovery_core.h): k_gf_combine over the task table, one launch per accumulator tier that
 // has tasks, then k_slice_crc over the listed byte ranges.

@@ -391,4 +391,63 @@ struct ArArgs {
     uint32_t* sums = nullptr;                      // zero on entry
     unsigned long long* bad = nullptr;             // [items] lowest digest_bad_key per item (all ones on entry), or null
 };
+// Bit-compare (k_compare_search / k_compare_rows of k_compare.hip, compare_core.h): the tables compare_plan.h lays out.  One
+// form for both jobs, as for the rip checksums: a source is PCM in a layout (a stream's is the decoder's planar int32
+// staging, validate 0; a source's its own, validate 1).  A pair names two sources; a span is a stretch of A's axis (both
+// ends multiples of 4) on which A or the B window of the pair's offsets can be non-zero, and the search tiles it.
+constexpr uint32_t kCmpThreads = 256;
+constexpr uint32_t kCmpTileFrames = 2048;          // frames of A per search tile
+constexpr uint32_t kCmpLaneOffsets = 4;            // consecutive offsets a search lane owns
+constexpr uint32_t kCmpMaxRadius = 32767;
+constexpr uint32_t kCmpRowFrames = 16384;          // frames per row, counted from the domain's first frame
+constexpr uint32_t kCmpRowBytes = 96;              // sizeof(lacx_compare_row): per channel first, last, max_at, sum_abs, sum_sq (uint64), mismatches, max_abs (uint32)
+constexpr unsigned long long kCmpNone = ~0ull;     // first / last / max_at of a row and channel in which nothing differs
+constexpr uint32_t kCmpStageA = kCmpTileFrames;                                        // words per plane
+constexpr uint32_t kCmpStageB = kCmpTileFrames + kCmpLaneOffsets * kCmpThreads;        // the window a full tile's offsets reach
+struct CmpSource {                                 // 40 bytes
+    const void* data0;                             // as DigestSource
+    const void* data1;
+    unsigned long long frames;
+    uint32_t layout;
+    uint32_t item;                                 // whose bad[] an invalid sample lowers
+    uint8_t channels, bit_depth, validate, pad[5];
+};
+struct CmpPair {                                   // 48 bytes
+    uint32_t a, b;                                 // its sources
+    int32_t centre;
+    uint32_t radius;
+    long long chosen;                              // the offset the rows are made at: the host's, before k_compare_rows runs
+    unsigned long long count0;                     // counts[count0 + (o - (centre - radius))]: mis[o]; radius 0: none
+    unsigned long long row0;                       // its first row
+    unsigned long long nrows;                      // ... and how many the chosen offset's domain has
+};
+struct CmpSpan {                                   // 32 bytes
+    long long f_lo, f_hi;                          // A's frames [f_lo, f_hi), both multiples of 4, f_lo < f_hi
+    uint32_t pair;
+    uint32_t lanes;                                // threads across the offsets of a tile (each owns kCmpLaneOffsets): a power of two <= kCmpThreads
+    uint32_t otiles;                               // offset tiles
+    uint32_t pad;
+};
+// (constexpr: the host-only plan counts as the kernel does)
+constexpr long long cmp_floor4(long long v) { return v & ~3ll; }  // (floors a negative frame too)
+constexpr long long cmp_obase(const CmpPair& p) { return cmp_floor4((long long)p.centre - (long long)p.radius); }  // a tile's first offset is obase + a multiple of 4
+constexpr uint32_t cmp_width(const CmpPair& p) { return 2u * p.radius + 1u; }
+constexpr unsigned long long cmp_span_tiles(const CmpSpan& s) {
+    return (unsigned long long)((s.f_hi - s.f_lo + kCmpTileFrames - 1) / kCmpTileFrames) * s.otiles;
+}
+// the union domain of offset o (lacx.h)
+constexpr long long cmp_fmin(long long o) { return o > 0 ? -o : 0; }
+constexpr long long cmp_fmax(unsigned long long na, unsigned long long nb, long long o) { return (long long)nb - o > (long long)na ? (long long)nb - o : (long long)na; }
+struct CmpArgs {
+    uint32_t npairs = 0, nspans = 0;
+    unsigned long long total_tiles = 0, total_rows = 0;
+    const CmpSource* sources = nullptr;
+    const CmpPair* pairs = nullptr;                // [npairs]
+    const CmpSpan* spans = nullptr;                // [nspans]
+    const unsigned long long* tile_off = nullptr;  // [nspans + 1] prefix sums of the spans' tiles (frame tile major, offset tile minor)
+    const unsigned long long* row_off = nullptr;   // [npairs + 1] prefix sums of the pairs' rows at their chosen offsets
+    unsigned long long* counts = nullptr;          // zero on entry
+    void* rows = nullptr;                          // lacx_compare_row [rows_cap]; every row of a pair is written whole
+    unsigned long long* bad = nullptr;             // [items] lowest digest_bad_key per item (all ones on entry), or null
+};
 }  // namespace lacx

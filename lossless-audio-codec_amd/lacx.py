@@ -126,6 +126,8 @@ EXPORTS = (
     "lacx_decoder_spectrum_batch_device", "lacx_decoder_spectrum_pcm_batch_device", "lacx_decoder_item_spectrum_rows", "lacx_spectrum_combine",
     "lacx_decoder_accuraterip_batch_device", "lacx_decoder_accuraterip_pcm_batch_device", "lacx_decoder_item_ar_tracks", "lacx_decoder_item_ar_sums",
     "lacx_ar_ids",
+    "lacx_decoder_compare_batch_device", "lacx_decoder_compare_pcm_batch_device", "lacx_decoder_item_compare_rows", "lacx_decoder_item_compare_counts",
+    "lacx_compare_combine",
     "lacx_decoder_inspect_batch_device", "lacx_decoder_item_block_info", "lacx_decoder_item_partitions", "lacx_inspect_combine",
     "lacx_decoder_inspect_guard", "lacx_transcode_batch",
     "lacx_decoder_runs_batch_device", "lacx_decoder_runs_pcm_batch_device", "lacx_decoder_item_runs",
@@ -270,6 +272,14 @@ def lib():
         L.lacx_decoder_item_ar_tracks.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.POINTER(ArTrack)), u32p]
         L.lacx_decoder_item_ar_sums.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(u32p), C.POINTER(u32p), C.POINTER(u32p), u32p]
         L.lacx_ar_ids.argtypes = [u64p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(ArId)]
+        L.lacx_decoder_compare_batch_device.argtypes = [C.c_void_p, C.POINTER(Span), C.c_uint32, C.POINTER(ComparePair), C.c_uint32, C.c_void_p,
+                                                        C.POINTER(C.c_int), C.POINTER(Compare), C.POINTER(C.c_float)]
+        L.lacx_decoder_compare_pcm_batch_device.argtypes = [C.c_void_p, C.POINTER(DigestSource), C.c_uint32, C.POINTER(ComparePair), C.c_uint32, C.c_void_p,
+                                                            C.POINTER(C.c_int), C.POINTER(Compare), C.POINTER(C.c_float)]
+        L.lacx_decoder_item_compare_rows.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.POINTER(CompareRow)), u32p]
+        L.lacx_decoder_item_compare_counts.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(u64p), u32p]
+        L.lacx_compare_combine.argtypes = [C.POINTER(CompareRow), C.c_uint32, C.c_uint8, C.c_uint8, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int64,
+                                           C.POINTER(Compare)]
         L.lacx_decoder_inspect_batch_device.argtypes = [C.c_void_p, C.POINTER(Span), C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_int),
                                                         C.POINTER(StreamReport), C.POINTER(C.c_float)]
         L.lacx_decoder_item_block_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.POINTER(BlockInfo)), C.POINTER(C.c_uint32)]
@@ -314,7 +324,8 @@ def abi_structs() -> dict:
             "repair_result": RepairResult, "channel_stats": ChannelStats, "block_stats": BlockStats,
             "channel_totals": ChannelTotals, "stats": Stats, "loudness_row": LoudnessRow, "loudness": Loudness,
             "truepeak_row": TruePeakRow, "truepeak_channel": TruePeakChannel, "truepeak": TruePeak,
-            "ar_disc": ArDisc, "ar_id": ArId, "ar_result": ArResult, "ar_track": ArTrack, "spectrum_row": SpectrumRow, "spectrum": Spectrum, "channel_info": ChannelInfo, "block_info": BlockInfo,
+            "ar_disc": ArDisc, "ar_id": ArId, "ar_result": ArResult, "ar_track": ArTrack, "compare_pair": ComparePair, "compare_channel_row": CompareChannelRow,
+            "compare_row": CompareRow, "compare_channel": CompareChannel, "compare": Compare, "spectrum_row": SpectrumRow, "spectrum": Spectrum, "channel_info": ChannelInfo, "block_info": BlockInfo,
             "stream_report": StreamReport, "edit_segment": EditSegment, "edit_output": EditOutput,
             "edit_result": EditResult, "run_detector": RunDetector, "run_query": RunQuery, "run": Run,
             "run_totals": RunTotals, "runs_result": RunsResult}
@@ -1192,6 +1203,91 @@ def ar_ids(track_frames, first=True, last=True, lba0=0) -> ArId:
     tf = (C.c_uint64 * max(1, n))(*track_frames)
     out = ArId()
     if lib().lacx_ar_ids(tf, C.c_uint32(n), C.c_uint32((AR_FIRST if first else 0) | (AR_LAST if last else 0)), C.c_uint32(lba0), C.byref(out)) != OK:
+        raise ValueError(lib().lacx_decode_last_error().decode(errors="replace"))
+    return out
+
+
+# ---- bit-compare: offset search and null-test residual (lacx.h) ----
+COMPARE_NONE = 2 ** 64 - 1  # LACX_COMPARE_NONE
+COMPARE_SIDE_NONE, COMPARE_SIDE_A, COMPARE_SIDE_B = 0, 1, 2
+COMPARE_MAX_RADIUS = 32767
+COMPARE_ROW_FRAMES = 16384
+
+
+class ComparePair(C.Structure):
+    _fields_ = [("a", C.c_uint32), ("b", C.c_uint32), ("centre", C.c_int64), ("radius", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class CompareChannelRow(C.Structure):
+    """One channel of one row of 16384 domain frames (lacx_compare_channel_row): positions count from the domain's first
+    frame, COMPARE_NONE where nothing differs."""
+    _fields_ = [("first", C.c_uint64), ("last", C.c_uint64), ("max_at", C.c_uint64), ("sum_abs", C.c_uint64), ("sum_sq", C.c_uint64),
+                ("mismatches", C.c_uint32), ("max_abs", C.c_uint32)]
+
+
+class CompareRow(C.Structure):
+    _fields_ = [("ch", CompareChannelRow * 2)]
+
+
+class CompareChannel(C.Structure):
+    _fields_ = [("mismatches", C.c_uint64), ("first", C.c_int64), ("last", C.c_int64), ("peak_at", C.c_int64), ("sum_abs_lo", C.c_uint64),
+                ("sum_abs_hi", C.c_uint64), ("sum_sq_lo", C.c_uint64), ("sum_sq_hi", C.c_uint64), ("peak", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class Compare(C.Structure):
+    """The totals of one pair at its chosen offset (lacx_compare).  Frame positions are on A's axis."""
+    _fields_ = [("offset", C.c_int64), ("domain_first", C.c_int64), ("domain_frames", C.c_uint64), ("frames_a", C.c_uint64), ("frames_b", C.c_uint64),
+                ("mismatches", C.c_uint64), ("first", C.c_int64), ("last", C.c_int64), ("peak_at", C.c_int64), ("sum_abs_lo", C.c_uint64),
+                ("sum_abs_hi", C.c_uint64), ("sum_sq_lo", C.c_uint64), ("sum_sq_hi", C.c_uint64), ("rows", C.c_uint64), ("rows_differ", C.c_uint64),
+                ("lead", C.c_uint64), ("tail", C.c_uint64), ("peak", C.c_uint32), ("sample_rate", C.c_uint32), ("peak_channel", C.c_uint8),
+                ("channels", C.c_uint8), ("bit_depth", C.c_uint8), ("lead_side", C.c_uint8), ("tail_side", C.c_uint8), ("reserved", C.c_uint8 * 3),
+                ("ch", CompareChannel * 2)]
+
+    @property
+    def identical(self) -> bool:
+        return self.mismatches == 0
+
+    @property
+    def sum_abs(self) -> int:
+        return self.sum_abs_lo | (self.sum_abs_hi << 64)
+
+    @property
+    def sum_sq(self) -> int:
+        return self.sum_sq_lo | (self.sum_sq_hi << 64)
+
+    @property
+    def peak_dbfs(self) -> float:
+        """The residual's peak against full scale of the bit depth; -inf where nothing differs."""
+        return 20.0 * math.log10(self.peak / float(1 << (self.bit_depth - 1))) if self.peak else float("-inf")
+
+    @property
+    def rms_dbfs(self) -> float:
+        """The residual's RMS over every sample of the domain against full scale; -inf where nothing differs."""
+        n = self.domain_frames * self.channels
+        if not self.sum_sq or not n:
+            return float("-inf")
+        return 10.0 * math.log10(self.sum_sq / n / float(1 << (self.bit_depth - 1)) ** 2)
+
+
+class CompareResult:
+    """One pair: `totals` (Compare), `rows` (an array of CompareRow), `counts` (uint64 array of mis[] over `offsets`, empty at radius
+    0).  Attributes of the totals read through."""
+
+    def __init__(self, totals, rows, counts, centre, radius):
+        self.totals, self.rows, self.counts = totals, rows, counts
+        self.offsets = np.arange(centre - radius, centre + radius + 1) if len(counts) else np.zeros(0, np.int64)
+
+    def __getattr__(self, name):
+        return getattr(self.totals, name)
+
+
+def compare_combine(rows, channels, bit_depth, sample_rate, frames_a, frames_b, offset=0) -> Compare:
+    """Host only: the totals of a pair's rows (lacx_compare_combine)."""
+    n = len(rows)
+    arr = (CompareRow * max(1, n))(*rows)
+    out = Compare()
+    if lib().lacx_compare_combine(arr, C.c_uint32(n), C.c_uint8(channels), C.c_uint8(bit_depth), C.c_uint32(sample_rate), C.c_uint64(frames_a),
+                                  C.c_uint64(frames_b), C.c_int64(offset), C.byref(out)) != OK:
         raise ValueError(lib().lacx_decode_last_error().decode(errors="replace"))
     return out
 
@@ -2300,6 +2396,87 @@ class Decoder:
         if rc == E_INVALID and all(rcs[k] == OK for k in range(n)):
             raise ValueError(lib().lacx_decode_last_error().decode(errors="replace"))
         return self._ar_finish(n, rc, rcs, out)
+
+    # ---- bit-compare: offset search and null-test residual ----
+    @staticmethod
+    def _compare_pairs(pairs):
+        recs = (ComparePair * max(1, len(pairs)))()
+        for rec, p in zip(recs, pairs):
+            a, b, centre, radius = (tuple(p) + (0, 0))[:4]
+            if not (0 <= a < 2 ** 32 and 0 <= b < 2 ** 32 and -2 ** 63 <= centre < 2 ** 63 and 0 <= radius < 2 ** 32):
+                raise ValueError("pair out of the ABI's range: %r" % (p,))
+            rec.a, rec.b, rec.centre, rec.radius = a, b, centre, radius
+        return recs
+
+    def _compare_finish(self, recs, n, rc, rcs, out):
+        if rc == E_DEVICE:
+            raise RuntimeError(lib().lacx_decode_last_error().decode(errors="replace"))
+        errors = {k: lib().lacx_decoder_item_error(self._h, k).decode(errors="replace") for k in range(n) if rcs[k] != OK}
+        results = []
+        for k in range(n):
+            if k in errors:
+                results.append(None)
+                continue
+            ptr, count = C.POINTER(CompareRow)(), C.c_uint32()
+            assert lib().lacx_decoder_item_compare_rows(self._h, C.c_uint32(k), C.byref(ptr), C.byref(count)) == OK
+            rows = (CompareRow * count.value).from_buffer_copy(C.string_at(ptr, C.sizeof(CompareRow) * count.value))  # one copy: they die with the next call
+            cp, cn = C.POINTER(C.c_uint64)(), C.c_uint32()
+            assert lib().lacx_decoder_item_compare_counts(self._h, C.c_uint32(k), C.byref(cp), C.byref(cn)) == OK
+            counts = np.array(np.ctypeslib.as_array(cp, shape=(cn.value,)), np.uint64) if cn.value else np.zeros(0, np.uint64)
+            results.append(CompareResult(_copy_struct(out[k]), rows, counts, int(recs[k].centre), int(recs[k].radius)))
+        if rc != OK:
+            e = BatchDecodeError(lib().lacx_decode_last_error().decode(errors="replace"), errors, results)
+            e.codes = {k: int(rcs[k]) for k in errors}
+            raise e
+        return results
+
+    def compare_batch(self, lacs, pairs, stream: int = 0) -> list:
+        """Many .lac streams decoded and compared in pairs as one device job, strict like digest_batch.  pairs: [(a, b,
+        centre=0, radius=0)] -- two indices into `lacs` (one stream may stand in many pairs and is decoded once), and the
+        offsets centre - radius .. centre + radius of b against a to search (radius at most 32767).  Per pair a
+        CompareResult at the offset with the fewest mismatches, None where the pair is refused or one of its streams does
+        not decode (those raise BatchDecodeError once the others are done).  Kernel milliseconds in `last_ms`."""
+        if self._h is None:
+            raise RuntimeError("decoder is closed")
+        bufs = [np.frombuffer(x, dtype=np.uint8) for x in lacs]
+        spans = (Span * max(1, len(bufs)))(*[Span(b.ctypes.data_as(C.POINTER(C.c_uint8)), b.size) for b in bufs])
+        recs, n = self._compare_pairs(pairs), len(pairs)
+        out, rcs, ms = (Compare * max(1, n))(), (C.c_int * max(1, n))(), C.c_float()
+        rc = lib().lacx_decoder_compare_batch_device(self._h, spans, C.c_uint32(len(bufs)), recs, C.c_uint32(n), C.c_void_p(stream), rcs, out, C.byref(ms))
+        self.last_ms = float(ms.value)
+        if rc == E_INVALID and all(rcs[k] == OK for k in range(n)):  # the call's own arguments
+            raise ValueError(lib().lacx_decode_last_error().decode(errors="replace"))
+        return self._compare_finish(recs, n, rc, rcs, out)
+
+    def compare(self, a, b, centre: int = 0, radius: int = 0) -> CompareResult:
+        """compare_batch of one pair of .lac streams; ValueError where the pair is refused, RuntimeError where a stream does
+        not decode."""
+        try:
+            return self.compare_batch([a, b], [(0, 1, centre, radius)])[0]
+        except BatchDecodeError as e:
+            raise (ValueError if e.codes[0] == E_INVALID else RuntimeError)(e.errors[0]) from None
+
+    def compare_pcm_batch(self, sources, pairs, stream: int = 0) -> list:
+        """Device-resident PCM compared where it lies: sources as truepeak_pcm_batch takes them, pairs as compare_batch --
+        what compare_batch gives for the .lac files made from them."""
+        if self._h is None:
+            raise RuntimeError("decoder is closed")
+        items = (DigestSource * max(1, len(sources)))()
+        for it, (pcm, rate, depth) in zip(items, sources):
+            if isinstance(pcm, (tuple, list)):
+                d0, d1, layout, channels, frames = pcm
+                it.pcm = Pcm(d0, d1, layout, channels)
+            else:
+                it.pcm, frames = pcm_of(pcm, depth)
+            it.frames, it.sample_rate, it.bit_depth = frames, rate, depth
+        recs, n = self._compare_pairs(pairs), len(pairs)
+        out, rcs, ms = (Compare * max(1, n))(), (C.c_int * max(1, n))(), C.c_float()
+        rc = lib().lacx_decoder_compare_pcm_batch_device(self._h, items, C.c_uint32(len(sources)), recs, C.c_uint32(n), C.c_void_p(stream), rcs, out,
+                                                         C.byref(ms))
+        self.last_ms = float(ms.value)
+        if rc == E_INVALID and all(rcs[k] == OK for k in range(n)):
+            raise ValueError(lib().lacx_decode_last_error().decode(errors="replace"))
+        return self._compare_finish(recs, n, rc, rcs, out)
 
     # ---- runs: where a stream is silent, clips or holds one value ----
     @staticmethod

@@ -33,6 +33,9 @@
 // accuraterip (what EAC, dBpoweramp, CUETools and whipper print for a rip): the AccurateRip v1 / v2 track checksums of the files
 // as one disc of CD audio, made on the device at every read offset within a radius (lacx_decoder_accuraterip_batch_device /
 // lacx_decoder_accuraterip_pcm_batch_device).  The database lookup is not part of it.
+// compare (what foobar2000's "bit-compare tracks", EAC's "compare WAVs" and `cmp` on decoded audio answer): whether two files
+// decode to the same samples, if not how many differ, where and by how much, and whether they do once one is shifted by up to
+// 32767 frames, made on the device (lacx_decoder_compare_batch_device / lacx_decoder_compare_pcm_batch_device).
 // inspect (`flac -a` for .lac): how each stream was coded and where its bits go, read out of the bytes on the device by a
 // parse-only walk (lacx_decoder_inspect_batch_device).
 // recompress, cut, join (no counterpart in the reference's tool; `flac -f`, `--skip` / `--until` and joining, for .lac): .lac
@@ -88,6 +91,11 @@ void usage() {
                  "      (.lac and .wav files of CD audio, together one disc in argument order: the disc ids and per track `NN start frames v1 v2\n"
                  "      s450` at offset 0; --tracks: the track lengths in frames, default one track per file; --radius: read offsets -N .. N,\n"
                  "      at most 2939; --match: every (track, offset, kind) whose sum is one of the values; exit 0 done, 1 nothing matched, 2 refused)\n"
+                 "  lacx_cli compare A B [--radius=N] [--centre=N] [--blocks] [--offsets]   (A and B each a .lac or a .wav: the offset of B\n"
+                 "      against A with the fewest differing samples among centre - N .. centre + N, N at most 32767, default 0; at it the\n"
+                 "      mismatches per channel, the first and last differing time, the peak and RMS of A - B, and the frames only one file has\n"
+                 "      at either end; --blocks: one line per 16384 frames; --offsets: the mismatches at every offset searched;\n"
+                 "      exit 0 no sample differs at the chosen offset, 1 they differ, 2 refused)\n"
                  "  lacx_cli inspect FILE... [--blocks] [--partitions]   (.lac files: predictors, residual modes and where the bits go, as\n"
                  "      integers, one line per file; --blocks: one further line per block; --partitions: and one per partition;\n"
                  "      a damaged stream prints its line with lost_blocks counted; exit 0 when every file was inspected, else 1)\n"
@@ -1306,6 +1314,161 @@ int accuraterip_command(int argc, char** argv) {
     return code;
 }
 
+// lacx_cli compare A B [--radius=N] [--centre=N] [--blocks] [--offsets]: A and B each a .lac or a WAV.  Both .lac: one stream
+// job (lacx_decoder_compare_batch_device).  Otherwise the source form (lacx_decoder_compare_pcm_batch_device): a .lac is first
+// decoded into planar int32 on the device (lacx_decoder_decode_batch_device), a WAV's data chunk goes there as it is: the same
+// answer either way.  Prints `offset=O identical ...` or `offset=O mismatches=N (left[, right]) first=T last=T peak=P (dBFS) ch=C
+// at=T rms=dBFS`, then frames, rows, lead and tail; times as frames on A's axis and seconds.  Exit 0 no sample differs at the
+// chosen offset, 1 they differ, 2 refused (the message on stderr).
+int compare_command(int argc, char** argv) {
+    std::vector<const char*> paths;
+    lacx_compare_pair pair{};
+    bool blocks = false, offsets = false, bad_option = false;
+    for (int i = 2; i < argc; ++i) {
+        const char* a = argv[i];
+        char* end = nullptr;
+        if (std::strncmp(a, "--radius=", 9) == 0) {
+            const unsigned long long v = std::strtoull(a + 9, &end, 10);
+            bad_option |= end == a + 9 || *end || v >> 32;
+            pair.radius = (uint32_t)v;
+        } else if (std::strncmp(a, "--centre=", 9) == 0) {
+            pair.centre = std::strtoll(a + 9, &end, 10);
+            bad_option |= end == a + 9 || *end;
+        } else if (std::strcmp(a, "--blocks") == 0) blocks = true;
+        else if (std::strcmp(a, "--offsets") == 0) offsets = true;
+        else if (std::strncmp(a, "--", 2) == 0) bad_option = true;
+        else paths.push_back(a);
+    }
+    if (paths.size() != 2 || bad_option) {
+        usage();
+        return 2;
+    }
+    std::vector<uint8_t> data[2];
+    bool all_lac = true;
+    for (int i = 0; i < 2; ++i) {
+        if (!load_file(paths[i], data[i])) {
+            std::cerr << "Compare failed: " << paths[i] << ": Failed to read file\n";
+            return 2;
+        }
+        if (data[i].size() >= 4 && std::memcmp(data[i].data(), "RIFF", 4) == 0) all_lac = false;
+    }
+    lacx_decoder* dec = nullptr;
+    if (lacx_decoder_create(-1, &dec) != LACX_OK) {
+        std::cerr << "Error: lacx_decoder_create failed\n";
+        return 2;
+    }
+    pair.a = 0, pair.b = 1;
+    lacx_compare res{};
+    int rc = LACX_OK, pair_rc = LACX_OK;
+    std::vector<void*> dev;
+    std::string why;
+    if (all_lac) {
+        const lacx_span spans[2] = {{data[0].data(), data[0].size()}, {data[1].data(), data[1].size()}};
+        rc = lacx_decoder_compare_batch_device(dec, spans, 2, &pair, 1, nullptr, &pair_rc, &res, nullptr);
+    } else {
+        lacx_digest_source src[2]{};
+        auto device = [&](uint64_t bytes, const void* from) -> void* {
+            void* p = nullptr;
+            if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) return nullptr;
+            dev.push_back(p);
+            if (from && hipMemcpy(p, from, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+            return p;
+        };
+        for (int i = 0; i < 2 && why.empty(); ++i) {
+            lacx_digest_source& x = src[i];
+            if (data[i].size() < 4 || std::memcmp(data[i].data(), "RIFF", 4) != 0) {  // a .lac beside a WAV: decoded into planar int32
+                lacx_stream_info f{};
+                if (lacx_stream_parse(data[i].data(), data[i].size(), &f) != LACX_OK) {
+                    why = std::string(paths[i]) + ": " + lacx_decode_last_error();
+                    break;
+                }
+                int32_t* l = static_cast<int32_t*>(device(4 * f.frames, nullptr));
+                int32_t* r = f.channels == 2 ? static_cast<int32_t*>(device(4 * f.frames, nullptr)) : nullptr;
+                if (!l || (f.channels == 2 && !r)) {
+                    why = std::string(paths[i]) + ": Failed to allocate on the device";
+                    break;
+                }
+                const lacx_decode_item item{data[i].data(), data[i].size(), l, r, f.frames};
+                if (lacx_decoder_decode_batch_device(dec, &item, 1, nullptr, nullptr, nullptr) != LACX_OK) {
+                    why = std::string(paths[i]) + ": " + lacx_decode_last_error();
+                    break;
+                }
+                x.pcm = lacx_pcm{l, r, LACX_PCM_PLANAR_I32, f.channels};
+                x.frames = f.frames, x.sample_rate = f.sample_rate, x.bit_depth = (uint8_t)f.bit_depth;
+                continue;
+            }
+            lacx_wav_info w{};
+            if (lacx_wav_parse(data[i].data(), data[i].size(), &w) != LACX_OK) {
+                why = std::string(paths[i]) + ": Failed to read WAV";
+                break;
+            }
+            const uint64_t bytes = w.frames * w.channels * (uint64_t)(w.bit_depth / 8);
+            void* p = device(bytes, data[i].data() + w.data_offset);
+            if (!p) {
+                why = std::string(paths[i]) + ": Failed to upload WAV data to the device";
+                break;
+            }
+            x.pcm = lacx_pcm{p, nullptr, w.bit_depth == 16 ? LACX_PCM_INTERLEAVED_I16 : LACX_PCM_INTERLEAVED_I24, w.channels};
+            x.frames = w.frames, x.sample_rate = w.sample_rate, x.bit_depth = (uint8_t)w.bit_depth;
+        }
+        if (why.empty()) rc = lacx_decoder_compare_pcm_batch_device(dec, src, 2, &pair, 1, nullptr, &pair_rc, &res, nullptr);
+    }
+    if (why.empty() && rc != LACX_OK) why = pair_rc != LACX_OK && rc != LACX_E_DEVICE ? lacx_decoder_item_error(dec, 0) : lacx_decode_last_error();
+    int code = 0;
+    if (!why.empty()) {
+        std::cerr << "Compare failed: " << why << "\n";
+        code = 2;
+    } else {
+        char line[320];
+        const double rate = res.sample_rate ? (double)res.sample_rate : 1.0, full = (double)(1u << (res.bit_depth - 1));
+        const char* side[3] = {"-", "A", "B"};
+        if (res.mismatches == 0) {
+            std::snprintf(line, sizeof(line), "offset=%lld identical", (long long)res.offset);
+        } else {
+            code = 1;
+            char per[64];
+            if (res.channels == 2) std::snprintf(per, sizeof(per), "%llu, %llu", (unsigned long long)res.ch[0].mismatches, (unsigned long long)res.ch[1].mismatches);
+            else std::snprintf(per, sizeof(per), "%llu", (unsigned long long)res.ch[0].mismatches);
+            const long double sq = (long double)res.sum_sq_hi * 18446744073709551616.0L + (long double)res.sum_sq_lo;
+            const double rms = std::sqrt((double)(sq / ((long double)res.domain_frames * res.channels))) / full;
+            std::snprintf(line, sizeof(line), "offset=%lld mismatches=%llu (%s) first=%lld (%.6f s) last=%lld (%.6f s) peak=%u (%.2f dBFS) ch=%u at=%lld (%.6f s) rms=%.2f dBFS",
+                          (long long)res.offset, (unsigned long long)res.mismatches, per, (long long)res.first, (double)res.first / rate, (long long)res.last,
+                          (double)res.last / rate, res.peak, 20.0 * std::log10((double)res.peak / full), (unsigned)res.peak_channel, (long long)res.peak_at,
+                          (double)res.peak_at / rate, 20.0 * std::log10(rms));
+        }
+        std::cout << line;
+        std::snprintf(line, sizeof(line), " frames=%llu,%llu domain=%lld+%llu rows=%llu differing_rows=%llu lead=%llu (%s) tail=%llu (%s)", (unsigned long long)res.frames_a,
+                      (unsigned long long)res.frames_b, (long long)res.domain_first, (unsigned long long)res.domain_frames, (unsigned long long)res.rows,
+                      (unsigned long long)res.rows_differ, (unsigned long long)res.lead, side[res.lead_side % 3], (unsigned long long)res.tail, side[res.tail_side % 3]);
+        std::cout << line << "\n";
+        if (offsets) {
+            const uint64_t* counts = nullptr;
+            uint32_t n = 0;
+            (void)lacx_decoder_item_compare_counts(dec, 0, &counts, &n);
+            for (uint32_t k = 0; k < n; ++k) std::cout << "o=" << (long long)pair.centre - (long long)pair.radius + (long long)k << " " << counts[k] << "\n";
+        }
+        if (blocks) {
+            const lacx_compare_row* rows = nullptr;
+            uint32_t n = 0;
+            (void)lacx_decoder_item_compare_rows(dec, 0, &rows, &n);
+            for (uint32_t r = 0; r < n; ++r) {
+                std::cout << "row " << r;
+                for (uint32_t c = 0; c < res.channels; ++c) {
+                    const lacx_compare_channel_row& x = rows[r].ch[c];
+                    if (!x.mismatches) std::cout << " | 0";
+                    else
+                        std::cout << " | " << x.mismatches << " first=" << (long long)(res.domain_first + (int64_t)x.first) << " last=" << (long long)(res.domain_first + (int64_t)x.last)
+                                  << " peak=" << x.max_abs << " at=" << (long long)(res.domain_first + (int64_t)x.max_at) << " sum_abs=" << x.sum_abs << " sum_sq=" << x.sum_sq;
+                }
+                std::cout << "\n";
+            }
+        }
+    }
+    for (void* p : dev) (void)hipFree(p);
+    lacx_decoder_destroy(dec);
+    return code;
+}
+
 // lacx_cli inspect FILE... [--blocks] [--partitions]: how every .lac was coded and where its bits go, read out of the bytes
 // on the device by a parse-only walk (lacx_decoder_inspect_batch_device), all files as one job.  One line of integers per
 // file in argument order; with --blocks one further line per block (its channel blocks behind it), with --partitions one
@@ -1942,6 +2105,7 @@ int main(int argc, char** argv) {
     if (mode == "peak") return peak_command(argc, argv);
     if (mode == "spectrum") return spectrum_command(argc, argv);
     if (mode == "accuraterip") return accuraterip_command(argc, argv);
+    if (mode == "compare") return compare_command(argc, argv);
     if (mode == "inspect" && argc >= 3) return inspect_command(argc, argv);
     if (mode == "find" && argc >= 3) return find_command(argc, argv);
     if (mode == "split" && argc >= 4) return split_command(argc, argv);
