@@ -23,7 +23,9 @@ __device__ unsigned long long g_stamp_acc[40];
 
 // Test hooks and timing ablations (AnalyzeParams::debug_skip, from LACX_DEBUG_SKIP) exist only in the diagnostic library
 // (liblacx_hooks.so, -DLACX_TEST_HOOKS): bits 10 / 11 / 13 force the repair paths of the fused emit for the parity tests,
-// the other bits switch phases off for timing experiments.  The production kernel carries none of them.
+// bits 21..31 take candidates 0..10 out of the predictor search (each candidate against the oracle on every block),
+// the other bits switch phases off for timing experiments or swap an optimised path for its plain sibling.  The
+// production kernel carries none of them.
 #ifdef LACX_TEST_HOOKS
 #define LACX_HOOK(prm, bits) (((prm).debug_skip & (bits)) != 0u)
 #else
@@ -415,8 +417,17 @@ __device__ __forceinline__ void analyze_slot(unsigned char* smem_raw, const Anal
     slot_sync<G>();
     if (tid <= 10) {
         // one lane per candidate: its bound as a sortable key (bound * 16 + index), all ones when it is not available
-        const bool avail = !((tid >= 6 && (sh.lpc.used[tid >= 6 ? tid - 6 : 0] == 0 || LACX_HOOK(prm, 16u))) ||
-                             (tid >= 1 && LACX_HOOK(prm, 64u)));
+        const bool offered = !((tid >= 6 && (sh.lpc.used[tid >= 6 ? tid - 6 : 0] == 0 || LACX_HOOK(prm, 16u))) ||
+                               (tid >= 1 && LACX_HOOK(prm, 64u)));
+#ifdef LACX_TEST_HOOKS
+        // test hook (bit 21 + c): candidate c is taken out of the search -- unless that leaves the slot without a candidate
+        // (the only orders left in are LPC orders whose recursion stopped or that exceed n - 1): then the mask is ignored
+        // for this slot.  The eleven lanes of the slot decide together, so best_cand is never left at -1.
+        const bool kept = offered && ((prm.debug_skip >> (21 + tid)) & 1u) == 0u;
+        const bool avail = slot_ballot<G::SW>(kept) != 0ull ? kept : offered;
+#else
+        const bool avail = offered;
+#endif
         sh.cand_key[tid] = avail ? ((candidate_lower_bound(sh.lbacc[tid][0], sh.lbacc[tid][1], sh.lbacc[tid][2], n, prm.zero_run) << 4) | (uint64_t)tid)
                                  : ~0ull;
     }

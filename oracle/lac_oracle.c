@@ -527,8 +527,21 @@ typedef struct {
 
 /* The analysis half of Block::Encoder::encode (encoder.cpp:313-552). Fills `plan`; returns the
  * winning residual in `best_res` (caller provides n int32). */
-static void analyze_block(const int32_t* x, uint32_t n, int zero_run, int partitioning, laco_plan* plan,
-                          int32_t* best_res) {
+static void analyze_block_masked(const int32_t* x, uint32_t n, int zero_run, int partitioning, uint32_t mask,
+                                 int* rule_out, laco_plan* plan, int32_t* best_res) {
+    /* The candidate mask (test variant, not reference text): bit c takes candidate c -- fixed 0..4, FIR, LPC 4..12 in
+     * the order of the loops below -- out of the search.  Two rules: a block of nothing but zeros is searched as ever,
+     * and so is a block for which the mask leaves no candidate that the search would have considered. */
+    uint32_t m = mask & LACO_MASK_ALL;
+    int rule = LACO_MASK_APPLIED;
+    if (m) {
+        int silent = 1;
+        for (uint32_t i = 0; i < n && silent; ++i) silent = x[i] == 0;
+        if (silent) {
+            m = 0;
+            rule = LACO_MASK_SILENT;
+        }
+    }
     const int max_valid_order = (n > 1) ? (int)((n - 1 < 32u) ? n - 1 : 32u) : 0;
     int32_t* scratch = (int32_t*)malloc(sizeof(int32_t) * (n ? n : 1));
     pred_eval best;
@@ -545,7 +558,9 @@ static void analyze_block(const int32_t* x, uint32_t n, int zero_run, int partit
         }                                                                                   \
     } while (0)
 
+search:
     for (int fo = 0; fo <= 4; ++fo) { /* encoder.cpp:362-369 */
+        if ((m >> fo) & 1u) continue;
         memset(&ev, 0, sizeof(ev));
         ev.type = kPredFixed;
         ev.order_param = fo;
@@ -554,7 +569,7 @@ static void analyze_block(const int32_t* x, uint32_t n, int zero_run, int partit
         score(&ev, n, zero_run);
         CONSIDER();
     }
-    { /* encoder.cpp:372-379 */
+    if (!((m >> 5) & 1u)) { /* encoder.cpp:372-379 */
         memset(&ev, 0, sizeof(ev));
         ev.type = kPredFir;
         ev.order_param = 2;
@@ -566,6 +581,7 @@ static void analyze_block(const int32_t* x, uint32_t n, int zero_run, int partit
     for (int ci = 0; ci < 5; ++ci) { /* encoder.cpp:382-407 */
         const int cand = kOrderCandidates[ci];
         if (cand > max_valid_order) continue;
+        if ((m >> (6 + ci)) & 1u) continue;
         memset(&ev, 0, sizeof(ev));
         ev.type = kPredLpc;
         ev.order_param = cand;
@@ -577,6 +593,12 @@ static void analyze_block(const int32_t* x, uint32_t n, int zero_run, int partit
         score(&ev, n, zero_run);
         CONSIDER();
     }
+    if (!have_best && m) { /* the mask left nothing that is available: search as if there were none */
+        m = 0;
+        rule = LACO_MASK_NONE_LEFT;
+        goto search;
+    }
+    if (rule_out) *rule_out = rule;
     if (!have_best) { /* encoder.cpp:410-417 (unreachable: fixed-0 is always considered) */
         memset(&ev, 0, sizeof(ev));
         ev.residual = scratch;
@@ -788,31 +810,46 @@ static void emit_block(const laco_plan* plan, const int32_t* res, uint32_t n, bi
     bw_flush(w); /* encoder.cpp:822 */
 }
 
-static void block_encode_into(const int32_t* pcm, uint32_t n, int zero_run, int partitioning, bitw* w,
-                              laco_plan* plan_out) {
+static void block_encode_into_masked(const int32_t* pcm, uint32_t n, int zero_run, int partitioning, uint32_t mask,
+                                     bitw* w, laco_plan* plan_out, int* rule_out) {
     laco_plan plan;
     int32_t* res = (int32_t*)malloc(sizeof(int32_t) * (n ? n : 1));
-    analyze_block(pcm, n, zero_run, partitioning, &plan, res);
+    analyze_block_masked(pcm, n, zero_run, partitioning, mask, rule_out, &plan, res);
     emit_block(&plan, res, n, w);
     if (plan_out) *plan_out = plan;
     free(res);
 }
 
-int laco_block_encode(const int32_t* pcm, uint32_t n, int zero_run, int partitioning, uint8_t** out,
-                      uint64_t* out_size) {
+int laco_block_plan_encode_masked(const int32_t* pcm, uint32_t n, int zero_run, int partitioning, uint32_t mask,
+                                  laco_plan* plan, int* rule, uint8_t** out, uint64_t* out_size) {
     bitw w;
     memset(&w, 0, sizeof(w));
-    block_encode_into(pcm, n, zero_run, partitioning, &w, NULL);
+    block_encode_into_masked(pcm, n, zero_run, partitioning, mask, &w, plan, rule);
     *out = w.buf ? w.buf : (uint8_t*)malloc(1);
     *out_size = w.len;
     return 0;
 }
 
-int laco_block_plan(const int32_t* pcm, uint32_t n, int zero_run, int partitioning, laco_plan* plan) {
+int laco_block_encode_masked(const int32_t* pcm, uint32_t n, int zero_run, int partitioning, uint32_t mask,
+                             uint8_t** out, uint64_t* out_size) {
+    return laco_block_plan_encode_masked(pcm, n, zero_run, partitioning, mask, NULL, NULL, out, out_size);
+}
+
+int laco_block_encode(const int32_t* pcm, uint32_t n, int zero_run, int partitioning, uint8_t** out,
+                      uint64_t* out_size) {
+    return laco_block_encode_masked(pcm, n, zero_run, partitioning, 0, out, out_size);
+}
+
+int laco_block_plan_masked(const int32_t* pcm, uint32_t n, int zero_run, int partitioning, uint32_t mask,
+                           laco_plan* plan, int* rule) {
     int32_t* res = (int32_t*)malloc(sizeof(int32_t) * (n ? n : 1));
-    analyze_block(pcm, n, zero_run, partitioning, plan, res);
+    analyze_block_masked(pcm, n, zero_run, partitioning, mask, rule, plan, res);
     free(res);
     return 0;
+}
+
+int laco_block_plan(const int32_t* pcm, uint32_t n, int zero_run, int partitioning, laco_plan* plan) {
+    return laco_block_plan_masked(pcm, n, zero_run, partitioning, 0, plan, NULL);
 }
 
 /* ------------------------------------------------------------------------------------------------
@@ -881,6 +918,7 @@ typedef struct {
     const int32_t *left, *right;
     uint64_t frames;
     int stereo_mode, zero_run, partitioning, channels;
+    uint32_t mask; /* candidate mask of the test variant (0: the reference's search) */
     uint32_t nblocks;
     uint8_t** payload;
     size_t* payload_len;
@@ -892,8 +930,8 @@ static size_t encode_pair(const stream_job* j, uint64_t start, uint32_t size, in
     /* encode_lr / encode_ms: lac/encoder.cpp:284-317 ; M/S: simd/neon.cpp:14-30 */
     const size_t before = w->len;
     if (!ms) {
-        block_encode_into(j->left + start, size, j->zero_run, j->partitioning, w, NULL);
-        if (j->channels == 2) block_encode_into(j->right + start, size, j->zero_run, j->partitioning, w, NULL);
+        block_encode_into_masked(j->left + start, size, j->zero_run, j->partitioning, j->mask, w, NULL, NULL);
+        if (j->channels == 2) block_encode_into_masked(j->right + start, size, j->zero_run, j->partitioning, j->mask, w, NULL, NULL);
     } else {
         int32_t* m = (int32_t*)malloc(sizeof(int32_t) * size);
         int32_t* s = (int32_t*)malloc(sizeof(int32_t) * size);
@@ -902,8 +940,8 @@ static size_t encode_pair(const stream_job* j, uint64_t start, uint32_t size, in
             m[i] = (int32_t)((uint32_t)l + (uint32_t)r) >> 1;
             s[i] = (int32_t)((uint32_t)l - (uint32_t)r);
         }
-        block_encode_into(m, size, j->zero_run, j->partitioning, w, NULL);
-        block_encode_into(s, size, j->zero_run, j->partitioning, w, NULL);
+        block_encode_into_masked(m, size, j->zero_run, j->partitioning, j->mask, w, NULL, NULL);
+        block_encode_into_masked(s, size, j->zero_run, j->partitioning, j->mask, w, NULL, NULL);
         free(m);
         free(s);
     }
@@ -969,9 +1007,9 @@ static void* stream_worker(void* arg) { /* lac/encoder.cpp:404-435 */
     }
 }
 
-int laco_encode(const int32_t* left, const int32_t* right, uint64_t frames, uint32_t sample_rate,
-                int bit_depth, int stereo_mode, int zero_run, int partitioning, int threads,
-                uint8_t** out, uint64_t* out_size) {
+int laco_encode_masked(const int32_t* left, const int32_t* right, uint64_t frames, uint32_t sample_rate,
+                       int bit_depth, int stereo_mode, int zero_run, int partitioning, int threads, uint32_t mask,
+                       uint8_t** out, uint64_t* out_size) {
     /* validation: lac/encoder.cpp:220-241, 71-102 */
     if (frames == 0 || left == NULL) return 1;
     if (!(sample_rate == 44100 || sample_rate == 48000 || sample_rate == 96000 || sample_rate == 192000))
@@ -993,6 +1031,7 @@ int laco_encode(const int32_t* left, const int32_t* right, uint64_t frames, uint
     j.stereo_mode = right ? stereo_mode : 0;
     j.zero_run = zero_run;
     j.partitioning = partitioning;
+    j.mask = mask;
     j.nblocks = (uint32_t)((frames + kMaxBlock - 1) / kMaxBlock); /* plan_blocks: lac/encoder.cpp:59-69 */
     j.payload = (uint8_t**)calloc(j.nblocks, sizeof(uint8_t*));
     j.payload_len = (size_t*)calloc(j.nblocks, sizeof(size_t));
@@ -1056,6 +1095,13 @@ int laco_encode(const int32_t* left, const int32_t* right, uint64_t frames, uint
     *out = o;
     *out_size = total;
     return 0;
+}
+
+int laco_encode(const int32_t* left, const int32_t* right, uint64_t frames, uint32_t sample_rate,
+                int bit_depth, int stereo_mode, int zero_run, int partitioning, int threads,
+                uint8_t** out, uint64_t* out_size) {
+    return laco_encode_masked(left, right, frames, sample_rate, bit_depth, stereo_mode, zero_run, partitioning, threads,
+                              0, out, out_size);
 }
 
 /* ------------------------------------------------------------------------------------------------

@@ -55,6 +55,27 @@ int laco_block_encode(const int32_t* pcm, uint32_t n, int zero_run, int partitio
 /* Same analysis, returning the decisions instead of the bytes. */
 int laco_block_plan(const int32_t* pcm, uint32_t n, int zero_run, int partitioning, laco_plan* plan);
 
+/* Test variants with a candidate mask (this repository's addition; the reference cannot force a candidate).  Bit c of
+ * `mask` takes candidate c out of the predictor search: 0..4 the fixed orders, 5 the FIR predictor, 6..10 LPC of order
+ * 4, 6, 8, 10, 12 (the order of block/encoder.cpp:362-407).  Two rules: a block of nothing but zeros is searched as ever,
+ * and so is a block for which the mask leaves no candidate that the search would have considered (an LPC order above
+ * n - 1, or one whose recursion stopped at once).  Mask 0 IS the function without the mask.  `rule` (may be NULL) says
+ * which applied. */
+#define LACO_MASK_ALL 0x7FFu
+#define LACO_MASK_APPLIED 0
+#define LACO_MASK_NONE_LEFT 1
+#define LACO_MASK_SILENT 2
+int laco_block_plan_masked(const int32_t* pcm, uint32_t n, int zero_run, int partitioning, uint32_t mask,
+                           laco_plan* plan, int* rule);
+int laco_block_encode_masked(const int32_t* pcm, uint32_t n, int zero_run, int partitioning, uint32_t mask,
+                             uint8_t** out, uint64_t* out_size);
+/* plan and bytes of one analysis (`plan` and `rule` may be NULL) */
+int laco_block_plan_encode_masked(const int32_t* pcm, uint32_t n, int zero_run, int partitioning, uint32_t mask,
+                                  laco_plan* plan, int* rule, uint8_t** out, uint64_t* out_size);
+int laco_encode_masked(const int32_t* left, const int32_t* right, uint64_t frames, uint32_t sample_rate,
+                       int bit_depth, int stereo_mode, int zero_run, int partitioning, int threads, uint32_t mask,
+                       uint8_t** out, uint64_t* out_size);
+
 /* LPC::autocorrelation (src/codec/lpc/lpc.cpp:80-96), exact int64, lags 0..order. */
 void laco_autocorr(const int32_t* pcm, uint32_t n, int order, int64_t* r);
 

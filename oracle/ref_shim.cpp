@@ -10,6 +10,7 @@
 //   LAC::Encoder::encode         src/codec/lac/encoder.hpp:12-43, encoder.cpp:215
 //   LAC::Decoder::decode         src/codec/lac/decoder.hpp:10-24
 //   Block::Encoder::encode       src/codec/block/encoder.hpp:9-30, encoder.cpp:313
+//   Block::Decoder::decode       src/codec/block/decoder.hpp:9-15
 //   LPC::analyze_block_q15       src/codec/lpc/lpc.hpp:11-14
 //   Rice::adapt_k                src/codec/rice/rice.hpp:38
 #include <cstdint>
@@ -20,6 +21,8 @@
 #include <string>
 #include <vector>
 
+#include "codec/bitstream/bit_reader.hpp"
+#include "codec/block/decoder.hpp"
 #include "codec/block/encoder.hpp"
 #include "codec/lac/decoder.hpp"
 #include "codec/lac/encoder.hpp"
@@ -109,6 +112,29 @@ int lacref_block_encode(const int32_t* pcm, uint32_t n, int zero_run, int partit
         enc.set_partitioning_enabled(partitioning != 0);
         std::vector<uint8_t> bytes = enc.encode(v);
         *out = dup_bytes(bytes, out_size);
+        return 0;
+    } catch (const std::exception& e) {
+        g_last_error = e.what();
+        return 1;
+    }
+}
+
+// Block::Decoder::decode of one channel block of n samples that fills `data` exactly (byte padding included).
+// Returns 0 ok, 1 refused, 2 bits left over; `out` holds n samples.
+int lacref_block_decode(const uint8_t* data, uint64_t size, uint32_t n, int32_t* out) {
+    try {
+        BitReader br(data, static_cast<size_t>(size));
+        Block::Decoder dec;
+        std::vector<int32_t> v;
+        if (!dec.decode(br, n, v) || v.size() != n) {
+            g_last_error = "Block::Decoder::decode refused the block";
+            return 1;
+        }
+        std::memcpy(out, v.data(), sizeof(int32_t) * n);
+        if (br.bits_remaining() != 0) {
+            g_last_error = "bits left behind the block";
+            return 2;
+        }
         return 0;
     } catch (const std::exception& e) {
         g_last_error = e.what();

@@ -94,6 +94,68 @@ def block_plan(pcm, zero_run=True, partitioning=True) -> Plan:
     return plan
 
 
+# The candidate mask of the oracle's test variants (oracle/lac_oracle.h): bit c takes candidate c -- fixed 0..4, FIR,
+# LPC 4, 6, 8, 10, 12 -- out of the predictor search; the rule that applied comes back beside the plan.
+MASK_ALL = 0x7FF
+MASK_APPLIED, MASK_NONE_LEFT, MASK_SILENT = 0, 1, 2
+
+
+def encode_masked(left, right=None, sample_rate=48000, bit_depth=16, stereo_mode=2, zero_run=True,
+                  partitioning=True, threads=1, mask=0) -> bytes:
+    L, lp = _i32(left)
+    rp = None
+    if right is not None:
+        R, rp = _i32(right)
+    out = C.POINTER(C.c_uint8)()
+    size = C.c_uint64()
+    rc = lib().laco_encode_masked(lp, rp, C.c_uint64(L.size), C.c_uint32(sample_rate), bit_depth, stereo_mode,
+                                  int(zero_run), int(partitioning), threads, C.c_uint32(mask), C.byref(out),
+                                  C.byref(size))
+    if rc == 1:
+        raise ValueError("invalid argument")
+    if rc != 0:
+        raise RuntimeError("encode failed")
+    data = C.string_at(out, size.value)
+    lib().laco_free(out)
+    return data
+
+
+def block_encode_masked(pcm, zero_run=True, partitioning=True, mask=0) -> bytes:
+    P, pp = _i32(pcm)
+    out = C.POINTER(C.c_uint8)()
+    size = C.c_uint64()
+    lib().laco_block_encode_masked(pp, C.c_uint32(P.size), int(zero_run), int(partitioning), C.c_uint32(mask),
+                                   C.byref(out), C.byref(size))
+    data = C.string_at(out, size.value)
+    lib().laco_free(out)
+    return data
+
+
+def block_plan_encode_masked(pcm, zero_run=True, partitioning=True, mask=0):
+    """(plan, rule, bytes) of one analysis."""
+    P, pp = _i32(pcm)
+    plan = Plan()
+    rule = C.c_int(-1)
+    out = C.POINTER(C.c_uint8)()
+    size = C.c_uint64()
+    lib().laco_block_plan_encode_masked(pp, C.c_uint32(P.size), int(zero_run), int(partitioning), C.c_uint32(mask),
+                                        C.byref(plan), C.byref(rule), C.byref(out), C.byref(size))
+    data = C.string_at(out, size.value)
+    lib().laco_free(out)
+    return plan, rule.value, data
+
+
+def block_plan_masked(pcm, zero_run=True, partitioning=True, mask=0):
+    """(plan, rule): rule is MASK_APPLIED, MASK_NONE_LEFT (the mask left no available candidate and was ignored) or
+    MASK_SILENT (a block of zeros: the mask has no effect)."""
+    P, pp = _i32(pcm)
+    plan = Plan()
+    rule = C.c_int(-1)
+    lib().laco_block_plan_masked(pp, C.c_uint32(P.size), int(zero_run), int(partitioning), C.c_uint32(mask),
+                                 C.byref(plan), C.byref(rule))
+    return plan, rule.value
+
+
 def autocorr(pcm, order=12):
     P, pp = _i32(pcm)
     r = np.zeros(order + 1, dtype=np.int64)

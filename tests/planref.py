@@ -87,8 +87,15 @@ def slot_window(frames: int, slot: int):
     return (0, (frames - PROBE) // 2, frames - PROBE)[win - 1], PROBE
 
 
-def slot_record(oracle, x, zr=True, pt=True, start=0) -> SlotRecord:
-    """The oracle's plan of one channel of one slot, in the fields of lacx_channel_plan."""
+def slot_record(oracle, x, zr=True, pt=True, start=0, mask=0) -> SlotRecord:
+    """The oracle's plan of one channel of one slot, in the fields of lacx_channel_plan.  mask != 0: of the search
+    without the candidates of the mask (oracleshim.block_plan_encode_masked; the hooks library's LACX_DEBUG_SKIP bits 21..31)."""
+    if mask:
+        op, _, data = oracle.block_plan_encode_masked(x, zr, pt, mask)
+        coef = tuple(int(op.coeffs_q15[i + 1]) for i in range(op.order)) if op.predictor_type == 2 else ()
+        pmk = tuple((int(op.part_mode[i]) << 5) | int(op.part_k[i]) for i in range(op.part_count))
+        return SlotRecord(int(op.predictor_type), int(op.order), int(op.partition_order), coef, pmk, int(op.total_bits),
+                          len(data), start, int(np.asarray(x).size))
     op = oracle.block_plan(x, zr, pt)
     coef = tuple(int(op.coeffs_q15[i + 1]) for i in range(op.order)) if op.predictor_type == 2 else ()
     pmk = tuple((int(op.part_mode[i]) << 5) | int(op.part_k[i]) for i in range(op.part_count))
@@ -109,20 +116,21 @@ def wide_slot_record(oracle, x, zr=True, pt=True) -> SlotRecord:
                       payload, 0, int(np.asarray(x).size))
 
 
-def expected_block(oracle, l, r, stereo_mode, zr=True, pt=True, chosen_only=False, records=True) -> BlockRecord:
+def expected_block(oracle, l, r, stereo_mode, zr=True, pt=True, chosen_only=False, records=True, mask=0) -> BlockRecord:
     """The expectation of one block (r is None: mono).  chosen_only: only the pair (or the mono slot) that is emitted,
     which is all lacx_emit_from_plans needs.  records=False: a whole-block slot whose record decides nothing is expected
     valid but its fields are left open (None) -- the valid set and the block record without the oracle's most expensive
-    plans."""
+    plans.  mask: every slot's search without the candidates of the mask (slot_record); the probe sizes, and with them
+    `choose_ms`, are those of the masked search."""
     n = int(l.size)
     if r is None:
-        return BlockRecord(n, 0, 0, 0, 0, {0: slot_record(oracle, l, zr, pt) if records else None})
+        return BlockRecord(n, 0, 0, 0, 0, {0: slot_record(oracle, l, zr, pt, 0, mask) if records else None})
     m, s = mid_side(l, r)
     chans = (l, r, m, s)
 
     def rec(slot):
         a, cnt = slot_window(n, slot)
-        return slot_record(oracle, chans[slot & 3][a:a + cnt], zr, pt, a)
+        return slot_record(oracle, chans[slot & 3][a:a + cnt], zr, pt, a, mask)
 
     est_ms = uncertain = 0
     slots = {}
@@ -153,12 +161,12 @@ def expected_block(oracle, l, r, stereo_mode, zr=True, pt=True, chosen_only=Fals
     return BlockRecord(n, 0, est_ms, uncertain, choose_ms, slots)
 
 
-def expected_stream(oracle, left, right, stereo_mode, zr=True, pt=True, chosen_only=False, records=True) -> list:
+def expected_stream(oracle, left, right, stereo_mode, zr=True, pt=True, chosen_only=False, records=True, mask=0) -> list:
     """One BlockRecord per 16384-frame block of the stream."""
     out = []
     for a in range(0, int(left.size), BLOCK):
         out.append(expected_block(oracle, left[a:a + BLOCK], None if right is None else right[a:a + BLOCK], stereo_mode,
-                                  zr, pt, chosen_only, records))
+                                  zr, pt, chosen_only, records, mask))
     return out
 
 

@@ -92,6 +92,22 @@ def block_encode(pcm, zero_run=True, partitioning=True) -> bytes:
     return data
 
 
+def has_block_decode() -> bool:
+    """A reference build from before lacref_block_decode (a prebuilt oracle/_ref where the reference sources are absent)
+    lacks the entry point; the callers then go through `decode`."""
+    return hasattr(lib(), "lacref_block_decode")
+
+
+def block_decode(data: bytes, n: int):
+    """Block::Decoder::decode of one channel block of n samples that fills `data` exactly."""
+    out = np.zeros(n, dtype=np.int32)
+    lib().lacref_block_decode.restype = C.c_int
+    rc = lib().lacref_block_decode(data, C.c_uint64(len(data)), C.c_uint32(n), out.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc != 0:
+        raise RuntimeError(lib().lacref_last_error().decode())
+    return out
+
+
 def lpc_analyze(pcm, order):
     P, pp = _i32(pcm)
     co = np.zeros(order + 1, dtype=np.int16)
